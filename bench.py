@@ -9,11 +9,19 @@ BASELINE.json configs[1]): `lvt_amd_track_device_async` on a frame resident in H
 `lvt_amd_wait_status` (at most --depth frames in flight).  Independent sequences (seed = rank) shard one per GPU, there is
 no collective on the data path (lvt_amd/shard.py) -> "scaling": "weak".  Rank 0 prints ONE JSON line.
 
-Beside the headline the line carries (rank 0, N = 1): `se3` = the timed poses against the CPU oracle's on the same frames
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps (the run fails if a timed frame is not
+TRACKING), the outputs if --dump-outputs is given, the line.  The frames are rendered once, at most FRAMES_RENDERED_MAX of them: a run with
+more steps walks them back and forth (frame_index), a continuous camera path, so that set-up does not grow with --steps.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0: the pose R, t and the tracking state, float64) as
+DIR/<name>.npy; the inputs are seeded, identical from run to run for the same arguments.
+
+With --full the line also carries (rank 0, N = 1): `se3` = the timed poses against the CPU oracle's on the same frames
 (the run FAILS above 1e-4), `sync` = latency of the synchronous entry points the reference's callers use (lvt_track with
 host buffers), `batch` = the lock-step batch, `configs` = EuRoC- and TUM-shaped legs, `roofline` = the batched Hamming
 matcher against the HBM roof (HIP events on its launch stream, inside this process), `cpu_baseline` = the oracle on this
-box's host cores.  The oracle is imported for `se3` / `cpu_baseline` only, outside the timed region.
+box's host cores, `kernels` / `device_resident` / `single_handle_list_kernels`.  The oracle is imported for `se3` / `cpu_baseline`
+only, outside the timed region.
 """
 import argparse
 import json
@@ -31,6 +39,14 @@ from lvt_amd.shard import aggregate_fps, gpu_cpu_affinity, rank_env, sum_over_ra
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md); ~6300 GB/s is achievable
 POSE_TOL = 1e-4        # BASELINE.json: per-frame SE3 within 1e-4 rel of the CPU reference
 METRIC = "stereo frames/sec (KITTI-shaped 1241x376), per-frame SE3 vs CPU ref"
+FRAMES_RENDERED_MAX = 512   # per sequence: ~1 GB of HBM + page-locked host memory, a few seconds of rendering
+
+
+def frame_index(i):
+    """the frame step i tracks: i itself below FRAMES_RENDERED_MAX, then back and forth over the rendered frames (..., 510, 511, 510, ..., 0, 1, ...)"""
+    n = FRAMES_RENDERED_MAX
+    j = i % (2 * (n - 1))
+    return j if j < n else 2 * (n - 1) - j
 
 
 def bmatch(M, N):
@@ -100,6 +116,10 @@ def run_rank(args, env, dist, backend):
     lost = sum_over_ranks(not_tracking, dist, None)
     if env.rank != 0:
         return None
+    if args.dump_outputs:   # before the --full legs, which run more frames on the same handle
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in backend.outputs().items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
     S = backend.sequences_per_gpu
     fps = aggregate_fps(K * S, env.world_size, dt)
     result = {
@@ -162,11 +182,12 @@ class HipBackend:
         torch.cuda.synchronize()
         return fr, H, W, pitch
 
-    def prepare(self, n_frames):
+    def prepare(self, n_steps):
         S, rank = self.sequences_per_gpu, self.env.rank
         self.worlds = [self.make_world("kitti", seed=rank * S + s) for s in range(S)]
         self.prm = self.lvt.kitti_params()
-        self.n_frames = n_frames
+        self.order = [frame_index(i) for i in range(n_steps)]   # the frame of every warm-up and timed step
+        self.n_frames = n_frames = min(n_steps, FRAMES_RENDERED_MAX)
         self.frames, self.H, self.W, self.pitch = self._render(self.worlds, n_frames)
         if S == 1:
             self.vo = self.lvt.LvtSystem.create(self.prm, self.lvt.eSensor_STEREO)
@@ -190,7 +211,7 @@ class HipBackend:
         out = []
         if self.sequences_per_gpu == 1 and self.host_frames:  # through the asynchronous host-buffer entry, like the timed frames
             inflight = 0
-            for i in range(Wm):
+            for i in self.order[:Wm]:
                 assert self.vo.track_async_ptr(self.hptr[i][0], self.hptr[i][1], self.H, self.W) == 0
                 inflight += 1
                 if inflight >= self.depth:
@@ -198,7 +219,7 @@ class HipBackend:
             while inflight:
                 out.append(self.vo.wait()); inflight -= 1
             return out
-        for i in range(Wm):
+        for i in self.order[:Wm]:
             if self.sequences_per_gpu == 1:
                 l, r = self._ptrs(i)
                 out.append(self.vo.track_device(l, r, self.H, self.W, self.pitch))
@@ -223,8 +244,9 @@ class HipBackend:
                 R, t, st = vo.wait()
                 bad += int((st != 2).sum())
             poses.append((R, t))
+            self.last_state = st
         host = single and self.host_frames
-        for i in range(first, first + K):
+        for i in self.order[first:first + K]:
             if host:
                 vo.track_async_ptr(self.hptr[i][0], self.hptr[i][1], H, W)
             elif single:
@@ -238,7 +260,13 @@ class HipBackend:
         while inflight:
             collect(); inflight -= 1
         assert len(poses) == K
+        self.last_pose = poses[-1]
         return poses, bad
+
+    def outputs(self):
+        """what the last timed step returned to its caller: pose (R, t) and tracking state (2 = TRACKING); one row per sequence in a batch"""
+        R, t = self.last_pose
+        return {"pose_R": R, "pose_t": t, "tracking_state": self.last_state}
 
     # ---- everything beside the headline (rank 0 only, outside the timed region) -----------------------------------------
     def extras(self, args, env, warm, poses):
@@ -250,8 +278,10 @@ class HipBackend:
         c = self.vo.counts()
         out["tracking_last_frame"] = {"features_left": c["n_left"], "map_size": c["map_size"], "matches": c["n_matches"]}
         out["host_route"] = self.vo.host_stats()
-        legs = [("device_resident", self._leg_device_resident), ("kernels", self._leg_kernels), ("roofline", self._leg_roofline)]
-        if env.world_size == 1:  # reported at N = 1 only (rank 0's host cores / one GPU to itself)
+        legs = []
+        if args.full:
+            legs += [("device_resident", self._leg_device_resident), ("kernels", self._leg_kernels), ("roofline", self._leg_roofline)]
+        if args.full and env.world_size == 1:  # reported at N = 1 only (rank 0's host cores / one GPU to itself)
             legs += [("sync", self._leg_sync), ("batch", self._leg_batch), ("lists_ab", self._leg_lists_ab), ("configs", self._leg_configs)]
             if not args.no_cpu:
                 legs += [("cpu", lambda a: self._leg_cpu(a, warm, poses))]
@@ -271,7 +301,7 @@ class HipBackend:
         warm-up and timed frames, the same depth; a side field, never `value`."""
         if not self.host_frames:
             return {}
-        n = min(self.n_frames, args.warmup + args.steps)
+        n = len(self.order)
         Wm = min(args.warmup, n - 1)
         os.environ["LVT_AMD_ORDERING"] = "polling"   # (a handle created beside a live one would order with events: not the path being compared)
         try:
@@ -282,7 +312,7 @@ class HipBackend:
         for tag in ("first", "second"):   # (twice on the same handle after a reset: the second pass runs with warm clocks)
             vo.reset()
             inflight, bad = 0, 0
-            for i in range(Wm):
+            for i in self.order[:Wm]:
                 l, r = self._ptrs(i)
                 vo.track_device_async(l, r, self.H, self.W, self.pitch); inflight += 1
                 if inflight >= self.depth:
@@ -291,7 +321,7 @@ class HipBackend:
                 vo.wait(); inflight -= 1
             self.sync()
             t0 = time.perf_counter()
-            for i in range(Wm, n):
+            for i in self.order[Wm:n]:
                 l, r = self._ptrs(i)
                 vo.track_device_async(l, r, self.H, self.W, self.pitch); inflight += 1
                 if inflight >= self.depth:
@@ -313,7 +343,7 @@ class HipBackend:
         world = self.worlds[0]
         extra = self.torch.zeros((P, 2, self.H, self.pitch), dtype=self.torch.uint8, device=self.device)
         for k in range(P):
-            extra[k, :, :, :self.W] = world.render_stereo_torch(self.n_frames + k, device=self.device)
+            extra[k, :, :, :self.W] = world.render_stereo_torch(frame_index(len(self.order) + k), device=self.device)
         self.sync()
         vo.profile_enable(True)
         nl = nr = mp = nm = 0
@@ -808,8 +838,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline (se3 against the CPU oracle, cpu_baseline, sync, batch, "
+                    "configs, roofline, kernels, device_resident, single_handle_list_kernels); off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float64")
     ap.add_argument("--depth", type=int, default=0, help="poses outstanding in the async pipeline (1 = synchronous; default: 4 for one sequence per GPU, 3 for a lock-step batch)")
     ap.add_argument("--seqs-per-gpu", type=int, default=1, help="independent sequences advanced in lock-step on each GPU (cfg 5 on G < 8 GPUs: ceil(8 / G))")
+    # --profile-steps .. --config-frames shape the --full legs only
     ap.add_argument("--profile-steps", type=int, default=40, help="extra frames run with per-kernel HIP events")
     ap.add_argument("--cpu-frames", type=int, default=600, help="upper bound of frames run through the CPU oracle (baseline + SE3 check)")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
@@ -827,7 +861,7 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="hip", choices=["hip", "standin"], help="standin: sleeps instead of GPU work (CPU test of the multi-rank launch path)")
     ap.add_argument("--standin-ms", type=float, default=0.0, help="stand-in backend: every rank's step takes this long (default: rank r takes 1 + r ms)")
     ap.add_argument("--standin-tail-ms", type=float, default=0.0, help="stand-in backend: rank 1 sleeps this long between its timed window and the reductions")
-    ap.add_argument("--skip", default="", help="comma-separated side legs to skip: kernels,roofline,pmc (the live counter passes of the roofline leg),sync,batch,lists_ab,configs,cpu")
+    ap.add_argument("--skip", default="", help="with --full, comma-separated side legs to skip: kernels,roofline,pmc (the live counter passes of the roofline leg),sync,batch,lists_ab,configs,cpu")
     args = ap.parse_args(argv)
     args.skip = [s for s in args.skip.split(",") if s]
     args.depth_auto = args.depth <= 0
@@ -867,6 +901,9 @@ class StandInBackend:
         """(tests) a rank that dawdles between its timed window and the reductions: must not show in anybody's time"""
         if self.args.standin_tail_ms > 0 and self.env.rank == 1:
             time.sleep(0.001 * self.args.standin_tail_ms)
+
+    def outputs(self):
+        return {}
 
     def extras(self, args, env, warm, poses):
         return {"roofline": None, "cpu_baseline": None}
