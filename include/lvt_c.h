@@ -15,11 +15,14 @@
  * fallback.  If no HIP device is usable lvt_create() returns NULL.
  *
  * Capacities (compile-time, lvt_amd/csrc/lvt_dev.h; the reference's containers grow without
- * bound): 4096 features per image after BRIEF's border filter, 16384 external corners per
- * list, 32768 map points, 16384 staged points, 64 detection cells.  Exceeding one never passes
- * silently: the frame is tracked on what fits and lvt_amd_last_error() / the `overflow` count
- * (include/lvt_amd_ext.h) say which capacity was hit.  Every shipped configuration of the
- * reference (KITTI, EuRoC, TUM) stays an order of magnitude below them.
+ * bound).  The detection grid is fixed at creation, and lvt_create() returns NULL for one it
+ * cannot hold: more than 64 detection cells, or a cell side (the cell size, clipped to the
+ * image) over 4096 px.  Per frame: 2048 key points one cell may emit after ANMS, 4096 features
+ * per image after BRIEF's border filter, 16384 external corners per list, 32768 map points,
+ * 16384 staged points.  Exceeding one of these never passes silently: the frame is tracked on
+ * what fits -- a cell's first 2048 key points, an image's first 4096 features -- and
+ * lvt_amd_last_error() / the `overflow` count (include/lvt_amd_ext.h) say which capacity was
+ * hit.  Every shipped configuration of the reference (KITTI, EuRoC, TUM) stays well below them.
  */
 #ifndef LVT_C_INTERFACE_H__
 #define LVT_C_INTERFACE_H__

@@ -70,10 +70,15 @@ __device__ __forceinline__ s16x2 seg_pair(uint32_t w0, uint32_t w1, uint32_t w2,
     return __builtin_bit_cast(s16x2, r);
 }
 
-// raw-corner key: (ly << 18) | (lx << 8) | score    (cell-local coords < 1024, score <= 254)
-__device__ __forceinline__ uint32_t mk_key(int ly, int lx, int s) { return ((uint32_t)ly << 18) | ((uint32_t)lx << 8) | (uint32_t)s; }
-__device__ __forceinline__ int key_y(uint32_t k) { return (int)(k >> 18); }
-__device__ __forceinline__ int key_x(uint32_t k) { return (int)((k >> 8) & 1023); }
+// raw-corner key: (ly << (8 + XB)) | (lx << 8) | score    (score <= 254).  XB = 10 -- cell-local coords < 1024 -- is the format of k_score's
+// segments and of every cell whose sides are at most CELL_SIDE_LDS; a cell with a longer side has its own global-memory path with XB = 12
+// (cell_global_path_wide: sides up to CELL_SIDE_MAX).  key_pos is raster order in either format.
+template <int XB = 10>
+__device__ __forceinline__ uint32_t mk_key(int ly, int lx, int s) { return ((uint32_t)ly << (8 + XB)) | ((uint32_t)lx << 8) | (uint32_t)s; }
+template <int XB = 10>
+__device__ __forceinline__ int key_y(uint32_t k) { return (int)(k >> (8 + XB)); }
+template <int XB = 10>
+__device__ __forceinline__ int key_x(uint32_t k) { return (int)((k >> 8) & ((1u << XB) - 1u)); }
 __device__ __forceinline__ int key_r(uint32_t k) { return (int)(k & 255); }
 __device__ __forceinline__ uint32_t key_pos(uint32_t k) { return k >> 8; }
 
@@ -545,6 +550,7 @@ struct CellGeom {
 // compared at once (s >= th  <=>  bit 7 of (s & 0x7F) + (0x80 - th), or bit 7 of s itself), so a 16-pixel chunk costs ~25
 // instructions to count and a find-first-set walk over its corners to emit, instead of ~100 + ~160 for the scalar loops
 // -- one CU runs all 16 wavefronts of the cell, so this phase is VALU-bound.
+template <int XB = 10>
 __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, int cap, int *scan, long long *dbg = nullptr, int ly_off = 0) {
     const int tid = threadIdx.x;
     const int xa = g.X0 + 3, xb = g.X0 + g.cw - 4;  // inclusive pixel range
@@ -619,7 +625,7 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
                     const int b = (__ffs((int)m) - 1) >> 3;
                     m &= m - 1;
                     const int s = (w[k] >> (8 * b)) & 255;
-                    if (off < cap) keys[off] = mk_key(ly + ly_off, gx0 + 4 * k + b - g.X0, s);
+                    if (off < cap) keys[off] = mk_key<XB>(ly + ly_off, gx0 + 4 * k + b - g.X0, s);
                     off++;
                 }
             }
@@ -630,7 +636,7 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
             const int s = (w[b >> 2] >> (8 * (b & 3))) & 255;
             const int gx = gx0 + b;
             if (s >= g.threshold && gx >= xa && gx <= xb) {
-                if (off < cap) keys[off] = mk_key(ly + ly_off, gx - g.X0, s);
+                if (off < cap) keys[off] = mk_key<XB>(ly + ly_off, gx - g.X0, s);
                 off++;
             }
         }
@@ -701,30 +707,31 @@ __device__ __forceinline__ int cell_gather_segments(const FrameBuf &FB, int eye,
 // (I = u32).  Writes the cell's key points to `out` and returns how many.
 #define STAMP(k) do { if (dbg && threadIdx.x == 0) dbg[k] = clock64(); } while (0)
 // first half: AGAST's NMS.  keys[0..n_raw) = raw corners in raster order; on return uf[0..n_kp) (= `arr`) holds the survivors in raster
-// order, keys / root are intact (root[i] = representative of corner i's 4-connected component).
-template <typename I>
+// order, keys / root are intact (root[i] = representative of corner i's 4-connected component).  row_first / row_end: n_rows entries (the cell's height
+// at most).
+template <typename I, int XB = 10>
 __device__ __forceinline__ int cell_nms(uint32_t *keys, uint32_t *uf, I *root, I *abv, I *nms, uint8_t *tie, int n_raw, int *row_first, int *row_end, int *scan,
-                                        long long *dbg) {
+                                        long long *dbg, int n_rows = CELL_SIDE_LDS) {
     constexpr uint32_t NONE = IdxT<I>::NONE, LEFT = IdxT<I>::LEFT, MAXF = IdxT<I>::MAXF;
     const int tid = threadIdx.x;
     STAMP(2);
     // ---------------- neighbour links, union-find over 4-connected corner pixels
-    for (int i = tid; i < 1024; i += 1024) {
+    for (int i = tid; i < n_rows; i += 1024) {
         row_first[i] = -1;
         row_end[i] = 0;
     }
     __syncthreads();
     for (int i = tid; i < n_raw; i += 1024) {
-        const int y = key_y(keys[i]);
-        if (i == 0 || key_y(keys[i - 1]) != y) row_first[y] = i;
-        if (i == n_raw - 1 || key_y(keys[i + 1]) != y) row_end[y] = i + 1;
+        const int y = key_y<XB>(keys[i]);
+        if (i == 0 || key_y<XB>(keys[i - 1]) != y) row_first[y] = i;
+        if (i == n_raw - 1 || key_y<XB>(keys[i + 1]) != y) row_end[y] = i + 1;
         uf[i] = (uint32_t)i;
         nms[i] = (I)MAXF;
     }
     __syncthreads();
     for (int i = tid; i < n_raw; i += 1024) {
         const uint32_t k = keys[i];
-        const int y = key_y(k), x = key_x(k);
+        const int y = key_y<XB>(k), x = key_x<XB>(k);
         const bool left = (i > 0) && (key_pos(keys[i - 1]) + 1 == key_pos(k));
         uint32_t above = NONE;
         if (y > 0 && row_first[y - 1] >= 0) {
@@ -732,11 +739,11 @@ __device__ __forceinline__ int cell_nms(uint32_t *keys, uint32_t *uf, I *root, I
             const int end = hi;
             while (lo < hi) {
                 const int m = (lo + hi) >> 1;
-                const int mx = key_x(keys[m]);
+                const int mx = key_x<XB>(keys[m]);
                 if (mx < x) lo = m + 1;
                 else hi = m;
             }
-            if (lo < end && key_x(keys[lo]) == x) above = (uint32_t)lo;
+            if (lo < end && key_x<XB>(keys[lo]) == x) above = (uint32_t)lo;
         }
         abv[i] = (I)(above | (left ? LEFT : 0u));
     }
@@ -895,7 +902,7 @@ __device__ __forceinline__ int cell_nms(uint32_t *keys, uint32_t *uf, I *root, I
 // (sorted[] in keys -> r2[] in uf), 4 = decision radius + emit (sorted[] in keys, r2[] in uf).  7 = the whole thing on one workgroup;
 // the oversized-cell kernels run the parts in three launches, the radii on several workgroups (they are n^2 / 2 distances).
 constexpr int ANMS_SORT = 1, ANMS_RADII = 2, ANMS_SELECT = 4, ANMS_ALL = 7;
-template <typename I>
+template <typename I, int XB = 10>
 __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32_t *keys, uint32_t *uf, I *root, I *abv, I *nms, int n_kp, int n_cap, int *row_first,
                                          int *row_end, int *scan, int *misc, float *out, long long *dbg, int n_raw_dbg, int parts = ANMS_ALL, int i_first = 0,
                                          int i_stride = 1) {
@@ -1072,7 +1079,7 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
         uint32_t *sxy = reinterpret_cast<uint32_t *>(root);  // posL (and, with 16-bit indices, the adjacent posR) are dead: x | y << 16
         for (int i = tid; i < n_kp; i += 1024) {
             const uint32_t k = sorted[i];
-            sxy[i] = (uint32_t)key_x(k) | ((uint32_t)key_y(k) << 16);
+            sxy[i] = (uint32_t)key_x<XB>(k) | ((uint32_t)key_y<XB>(k) << 16);
         }
         __syncthreads();
         // this workgroup's key points: i_first + k * i_stride, k = 0 .. n_pts - 1 (all of them when the cell has one workgroup)
@@ -1132,7 +1139,11 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
         if (!(parts & ANMS_SELECT)) return n_kp;
         STAMP(8);
         // ---- decisionRadius = (max_kp)-th element (0-based) of the radii sorted descending: radix select over
-        // three 8-bit digits (finite radii^2 < 2^24; 0xFFFFFFFF stands for sqrt(FLT_MAX))
+        // three 8-bit digits (finite radii^2 < 2^24 in a cell of at most CELL_SIDE_LDS px; 0xFFFFFFFF stands for sqrt(FLT_MAX)).  The wide
+        // path's radii^2 reach 2 (CELL_SIDE_MAX - 7)^2 > 2^24: a fourth digit.
+        constexpr int TOP_SHIFT = (XB > 10) ? 24 : 16;
+        constexpr uint32_t VAL_MASK = (XB > 10) ? 0xFFFFFFFFu : 0xFFFFFFu;
+        static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 24), "three digits hold every finite radius^2 of an LDS-path cell");
         {
             int *h = row_first;  // [256]
             if (tid == 0) {
@@ -1155,11 +1166,11 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
             }
             __syncthreads();
             if (!misc[5]) {
-                for (int shift = 16; shift >= 0; shift -= 8) {
+                for (int shift = TOP_SHIFT; shift >= 0; shift -= 8) {
                     for (int k = tid; k < 256; k += 1024) h[k] = 0;
                     __syncthreads();
                     const uint32_t prefix = (uint32_t)misc[0];
-                    const uint32_t himask = (shift == 16) ? 0u : (0xFFFFFFu & ~((1u << (shift + 8)) - 1u));
+                    const uint32_t himask = (shift == TOP_SHIFT) ? 0u : (VAL_MASK & ~((1u << (shift + 8)) - 1u));
                     for (int i = tid; i < n_kp; i += 1024) {
                         const uint32_t v = r2[i];
                         if (v != 0xFFFFFFFFu && (v & himask) == (prefix & himask)) atomicAdd(&h[(v >> shift) & 255u], 1);
@@ -1204,15 +1215,27 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
         STAMP(9);
         const uint32_t decision = (uint32_t)misc[0];
         __syncthreads();
+        // the reference keeps sqrtf(radius^2) >= sqrtf(decision^2) on float radii^2 (handler.cpp:64-77).  Below 2^22 distinct integers have distinct
+        // square roots and the integer test is the same test -- every cell of at most CELL_SIDE_LDS px; above, neighbouring integers can share one,
+        // so the wide path also keeps a radius^2 below a decision of 2^22 or more whose square root equals the decision's (the float of the exact
+        // integer is the reference's once-rounded dx^2 + dy^2).  Infinite radii (0xFFFFFFFF) only ever take the integer test.
+        static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 22), "integer radius test exact");
+        auto keep_r2 = [&](uint32_t v) -> bool {
+            if constexpr (XB > 10) {
+                return v >= decision || (decision >= (1u << 22) && decision != 0xFFFFFFFFu && __fsqrt_rn((float)v) == __fsqrt_rn((float)decision));
+            } else {
+                return v >= decision;
+            }
+        };
         for (int base = 0; base < n_kp; base += 1024) {
             const int i = base + tid;
-            const bool keep = (i < n_kp) && (r2[i] >= decision);
+            const bool keep = (i < n_kp) && keep_r2(r2[i]);
             int total;
             const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);
             if (keep && off < CELL_OUT_CAP) {
                 const uint32_t k = sorted[i];
-                out[3 * off] = (float)key_x(k) + fX0;
-                out[3 * off + 1] = (float)key_y(k) + fY0;
+                out[3 * off] = (float)key_x<XB>(k) + fX0;
+                out[3 * off + 1] = (float)key_y<XB>(k) + fY0;
                 out[3 * off + 2] = (float)key_r(k);
             }
             n_out += total;
@@ -1221,8 +1244,8 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
         for (int i = tid; i < n_kp; i += 1024) {
             if (i < CELL_OUT_CAP) {
                 const uint32_t k = arr[i];
-                out[3 * i] = (float)key_x(k) + fX0;
-                out[3 * i + 1] = (float)key_y(k) + fY0;
+                out[3 * i] = (float)key_x<XB>(k) + fX0;
+                out[3 * i + 1] = (float)key_y<XB>(k) + fY0;
                 out[3 * i + 2] = (float)key_r(k);
             }
         }
@@ -1310,6 +1333,25 @@ __device__ __forceinline__ int cell_global_path(const Seq &S, const FrameBuf &FB
                                    dbg);
 }
 
+// a cell with a side over CELL_SIDE_LDS (a camera wider or taller than 1024 px under a cell size that large, e.g. the reference's TUM config on a
+// 1280 x 720 camera): the global-memory path in both passes, on 12-bit keys that k_score's segments do not carry -- the score map is compacted
+// here -- and with the row tables in the cell's own scratch, behind the tie bytes (the region is cw ch 6 words; this takes 5.25 cw ch + 2 ch).
+// The ANMS reuses the LDS row tables as its histograms (256 entries each), as on every other path.
+__device__ __forceinline__ int cell_global_path_wide(const Seq &S, const FrameBuf &FB, int eye, int cell, const CellGeom &g, const CellLds &L, float *out,
+                                                     long long *dbg) {
+    constexpr int XB = 12;
+    static_assert(CELL_SIDE_MAX <= (1 << XB) && (CELL_SIDE_MAX - 6) * (CELL_SIDE_MAX - 6) < (1 << 24), "12-bit cell-local coordinates; 24-bit corner indices");
+    static_assert(2ll * (CELL_SIDE_MAX - 7) * (CELL_SIDE_MAX - 7) < (1ll << 31), "radius^2 as sdot2's int32 and below cell_anms' 0xFFFFFFFF (its four-digit select)");
+    const size_t cap = (size_t)g.cw * g.ch;
+    uint32_t *gk = S.cell_scratch[eye] + S.cell_scratch_off[cell];
+    uint32_t *guf = gk + cap, *groot = guf + cap, *gabv = groot + cap, *gnms = gabv + cap;
+    uint8_t *gtie = reinterpret_cast<uint8_t *>(gnms + cap);
+    int *grow = reinterpret_cast<int *>(gnms + cap + (cap + 3) / 4);  // row_first [ch], row_end [ch]
+    const int n_raw = cell_compact<XB>(g, gk, (int)cap, L.scan);
+    const int n_kp = cell_nms<uint32_t, XB>(gk, guf, groot, gabv, gnms, gtie, n_raw, grow, grow + g.ch, L.scan, dbg, g.ch);
+    return cell_anms<uint32_t, XB>(S, g, gk, guf, groot, gabv, gnms, n_kp, (int)cap, L.row_first, L.row_end, L.scan, L.misc, out, dbg, n_raw);
+}
+
 // one detection cell of one image: AGAST NMS + LVT's ANMS (or the hand-over of an oversized cell to the strip kernels)
 __device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int eye, int cell, int pass, const CellLds &L, int raw_cap = RAW_CAP) {
     FeatCtl &ctl = *FB.fc;
@@ -1323,8 +1365,11 @@ __device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int
     long long *dbg = (cell == 0 && eye == 0 && pass == 0) ? S.ctl->dbg : nullptr;
     if (dbg && tid == 0) dbg[0] = clock64();
     int n_out = 0;
-    if (g.cw > 1024 || g.ch > 1024) {
+    if (g.cw > CELL_SIDE_MAX || g.ch > CELL_SIDE_MAX) {  // (lvt_create refuses such a grid)
         if (tid == 0) atomicOr(&ctl.overflow, OVF_CELL_DIM);
+    } else if ((g.cw > CELL_SIDE_LDS || g.ch > CELL_SIDE_LDS) && g.cw >= 7 && g.ch >= 7) {
+        n_out = cell_global_path_wide(S, FB, eye, cell, g, L, out, dbg);
+        if (dbg && tid == 0) dbg[10] = 1004;  // (tests: the wide global path -- in place of cell_anms' last phase stamp)
     } else if (g.cw >= 7 && g.ch >= 7) {
         // pass 0 with cells of at least one tile width: gather k_score's segments; otherwise compact the score map here
         const bool segs = (pass == 0) && (cs >= TS_W);
@@ -1363,7 +1408,7 @@ __device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &F
     int cxi;
     if (!cell_begin(S, FB, eye, cell, 0, g, cxi)) return;
     const int cs = S.prm.cell_size;
-    const bool splittable = g.cw >= 7 && g.ch >= SPLIT_MIN_ROWS && g.cw <= 1024 && g.ch <= 1024 && cs >= TS_W && !S.prm.big_cell_strips;
+    const bool splittable = g.cw >= 7 && g.ch >= SPLIT_MIN_ROWS && g.cw <= CELL_SIDE_LDS && g.ch <= CELL_SIDE_LDS && cs >= TS_W && !S.prm.big_cell_strips;
     if (!splittable) {
         if (strip == 0) cells_work(S, FB, eye, cell, 0, L, raw_cap);
         return;

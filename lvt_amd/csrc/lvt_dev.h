@@ -16,6 +16,9 @@ constexpr int NF_MAX = 4096;       // features per image after BRIEF's border fi
 constexpr int CELLS_MAX = 64;      // detection grid cells per image
 constexpr int CELL_OUT_CAP = 2048; // key points one cell may emit (after ANMS)
 constexpr int RAW_CAP = 10240;     // raw (pre-NMS) corners one cell may hold in LDS
+constexpr int CELL_SIDE_LDS = 1024;  // longest side of a detection cell on the LDS paths (10-bit cell-local x of a raw-corner key)
+constexpr int CELL_SIDE_MAX = 4096;  // longest side of a detection cell at all (a longer side: the 12-bit keys of the wide global path; lvt_create refuses more).
+                                     // Its ANMS radii^2 reach 2 (4089)^2 > 2^24: a four-digit select and the reference's sqrtf test (cell_anms)
 constexpr int MAP_MAX = 32768;     // local map points
 constexpr int STAGED_MAX = 16384;  // staged points
 constexpr int KC = 128;            // candidate-list capacity per query (overflow -> exact slow path)

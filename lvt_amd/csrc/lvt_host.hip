@@ -326,6 +326,7 @@ static bool derive_params(const lvt_amd_params &in, int sensor, Params &p) {
     p.cells_x = 1 + ((p.W - 1) / p.cell_size);
     p.n_cells = p.cells_x * p.cells_y;
     if (p.n_cells > CELLS_MAX) return false;
+    if (std::min(p.cell_size, p.W) > CELL_SIDE_MAX || std::min(p.cell_size, p.H) > CELL_SIDE_MAX) return false;  // (k_features.hip: 12-bit cell-local keys)
     // matching hash grid -- struct.cpp:47-53
     const float kc = (float)HASH_CELL;
     p.hash_ccx = (int)std::ceil(p.W / kc);

@@ -213,9 +213,14 @@ class SynthWorld:
         return torch.stack(outs, 0)
 
 
-def make_world(kind: str = "kitti", seed: int = 0, scale: float = 1.0, **kw) -> SynthWorld:
-    """kind in {kitti, euroc, tum}.  `scale` < 1 shrinks the image (and intrinsics) for fast CPU tests."""
+def make_world(kind: str = "kitti", seed: int = 0, scale: float = 1.0, size=None, **kw) -> SynthWorld:
+    """kind in {kitti, euroc, tum}.  `scale` < 1 shrinks the image (and intrinsics) for fast CPU tests.  `size` = (W, H) gives the
+    kind's camera any other image shape: focal lengths scale with the width, the principal point with each side."""
     base = dict({"kitti": KITTI, "euroc": EUROC, "tum": TUM1}[kind])
+    if size is not None:
+        W, H = int(size[0]), int(size[1])
+        s = W / base["width"]
+        base.update(fx=base["fx"] * s, fy=base["fy"] * s, cx=base["cx"] * W / base["width"], cy=base["cy"] * H / base["height"], width=W, height=H)
     if scale != 1.0:
         base["width"] = int(round(base["width"] * scale)); base["height"] = int(round(base["height"] * scale))
         for k in ("fx", "fy", "cx", "cy"):

@@ -10,8 +10,42 @@ XYZ_TOL = 1e-7       # map point positions (fp64, different summation order only
 PRED_TOL = 1e-7      # motion-model prediction (fp64: quaternion w x y z, position) -- it inherits the optimised pose's last digits
 
 
-def make_case(kind="kitti", seed=0, scale=1.0, overrides=None):
-    world = make_world(kind, seed=seed, scale=scale)
+class _FrameCache:
+    """a world whose rendered frames are kept: the geometry cases below run one world under several cell sizes and radii, and rendering
+    a full-size frame costs far more CPU than tracking it"""
+
+    def __init__(self, world):
+        self.w, self.W, self.H = world, world.W, world.H
+        self.fx, self.fy, self.cx, self.cy, self.baseline = world.fx, world.fy, world.cx, world.cy, world.baseline
+        self._st, self._rgbd = {}, {}
+
+    def render_stereo(self, i):
+        if i not in self._st:
+            self._st[i] = self.w.render_stereo(i)
+        return self._st[i]
+
+    def render_rgbd(self, i):
+        if i not in self._rgbd:
+            self._rgbd[i] = self.w.render_rgbd(i)
+        return self._rgbd[i]
+
+    def pose(self, i):
+        return self.w.pose(i)
+
+
+_WORLDS = {}
+
+
+def make_case(kind="kitti", seed=0, scale=1.0, overrides=None, size=None):
+    """(world, params, sensor) of a named config; `size` = (W, H) renders the kind's world at another image shape (synthetic intrinsics
+    scaled to it) and keeps its frames for the next case of the same shape and seed"""
+    if size is None:
+        world = make_world(kind, seed=seed, scale=scale)
+    else:
+        key = (kind, seed, scale, tuple(size))
+        if key not in _WORLDS:
+            _WORLDS[key] = _FrameCache(make_world(kind, seed=seed, scale=scale, size=size))
+        world = _WORLDS[key]
     mk = {"kitti": lvt_amd.kitti_params, "euroc": lvt_amd.euroc_params, "tum": lvt_amd.tum_params}[kind]
     kw = dict(width=world.W, height=world.H, fx=world.fx, fy=world.fy, cx=world.cx, cy=world.cy)
     if kind != "tum":

@@ -2,12 +2,17 @@
 liblvt_c.so) and compares it with the CPU oracle on the same seeded synthetic input: key points, descriptors,
 match indices, row matches, map bookkeeping bit-exact; map positions and per-frame SE3 within tolerance
 (POSE_TOL = 1e-4, the tolerance BASELINE.json states)."""
+import ctypes
+import re
+
 import numpy as np
 import pytest
 
 from parity_util import make_case, run_sequence, diff_frame, sparse_pair, HardWorld, POSE_TOL
 
 pytestmark = pytest.mark.gpu
+
+TUM_DISTORTION = {"k1": 0.262383, "k2": -0.953104, "p1": -0.005358, "p2": 0.002628, "k3": 1.163314}
 
 CASES = [
     # name, kind, seed, scale, overrides, frame ids
@@ -33,14 +38,46 @@ CASES = [
     ("kitti_map_size_policy", "kitti", 6, 0.5, {"triangulation_policy": 3}, list(range(10))),
     ("euroc", "euroc", 0, 1.0, {}, list(range(10))),                           # configs[2] shape
     ("tum_rgbd", "tum", 0, 1.0, {}, list(range(8))),                           # configs[3] shape (single 640x480 cell)
-    ("tum_rgbd_distorted", "tum", 1, 1.0, {"k1": 0.262383, "k2": -0.953104, "p1": -0.005358, "p2": 0.002628, "k3": 1.163314},
-     list(range(5))),
+    ("tum_rgbd_distorted", "tum", 1, 1.0, TUM_DISTORTION, list(range(120))),
 ]
+# geometry: the feature stage picks its route from the image and cell shape alone (k_score's compaction below 64-px cells, the two-workgroup
+# split up to 256, row strips + three-launch ANMS above, the wide global path over 1024 px), the list kernels from the hash grid and the search
+# radius.  Every shape the reference accepts runs through the same diff; rows carry a 7th field, the image size (synthetic intrinsics scaled
+# to it), and share their rendered frames with the other rows of the same world (parity_util.make_case).
+KITTI_SHAPE = (1241, 376)
+GEOMETRY_CASES = [
+    ("kitti03_shape", "kitti", 30, 1.0, {}, list(range(8)), (1242, 375)),                                 # last cell row 125 rows, last column 242 px
+    ("kitti04_shape", "kitti", 31, 1.0, {}, list(range(8)), (1226, 370)),                                 # 120 / 226
+    ("cells_48", "kitti", 32, 1.0, {"detection_cell_size": 48, "max_keypoints_per_cell": 30}, list(range(8)), (620, 188)),   # compaction path, 52 cells
+    ("cells_64", "kitti", 32, 1.0, {"detection_cell_size": 64}, list(range(8)), (620, 188)),             # smallest size with k_score's segments
+    ("cells_100", "kitti", 33, 1.0, {"detection_cell_size": 100, "max_keypoints_per_cell": 40}, list(range(8)), KITTI_SHAPE),  # 52 cells, 41-px column
+    ("cells_256", "kitti", 33, 1.0, {"detection_cell_size": 256}, list(range(8)), KITTI_SHAPE),           # largest size of the two-workgroup split
+    # smallest size above the split: one workgroup per cell (a world frame's 257-px cells keep to LDS; the strips run in the lock-step row
+    # "strips_257" and the one-frame noise test at this size)
+    ("cells_257", "kitti", 33, 1.0, {"detection_cell_size": 257}, list(range(8)), KITTI_SHAPE),
+    ("cells_1024", "kitti", 33, 1.0, {"detection_cell_size": 1024, "max_keypoints_per_cell": 600}, list(range(8)), KITTI_SHAPE),   # the LDS paths' widest cell
+    ("cells_1025", "kitti", 33, 1.0, {"detection_cell_size": 1025, "max_keypoints_per_cell": 1000}, list(range(8)), KITTI_SHAPE),  # wide global path
+    ("cells_2000", "kitti", 33, 1.0, {"detection_cell_size": 2000, "max_keypoints_per_cell": 1000}, list(range(8)), KITTI_SHAPE),  # one 1241 x 376 cell
+    ("cells_2000_retry", "kitti", 33, 1.0, {"detection_cell_size": 2000, "agast_threshold": 150}, list(range(8)), KITTI_SHAPE),   # retry pass on it
+    ("one_interior_px", "kitti", 34, 1.0, {}, list(range(8)), (757, 507)),                                # 7-px last column, 7-row last row
+    ("no_interior", "kitti", 34, 1.0, {}, list(range(8)), (753, 506)),                                    # 3-px column, 6-row row: skipped cells
+    ("cells_max", "kitti", 35, 1.0, {"detection_cell_size": 100}, list(range(8)), (800, 800)),           # exactly CELLS_MAX cells
+    ("stereo_720p", "kitti", 36, 1.0, {}, list(range(8)), (1280, 720)),                                   # 1 508 hash cells: map lists past LS_BINS
+] + [
+    (f"radius_{r}", "kitti", 32, 1.0, {"tracking_radius": r}, list(range(8)), (620, 188)) for r in (10, 26, 50, 51, 75, 100)   # cell_search_radius 1 2 2 3 3 4
+] + [
+    ("tum_config_720p", "tum", 37, 1.0, {"detection_cell_size": 2000}, list(range(8)), (1280, 720)),     # one 1280 x 720 cell
+    ("tum_config_720p_distorted", "tum", 37, 1.0, dict(TUM_DISTORTION, detection_cell_size=2000), list(range(8)), (1280, 720)),
+    ("tum_config_portrait", "tum", 38, 1.0, {"detection_cell_size": 2000}, list(range(8)), (720, 1280)), # one 720 x 1280 cell
+    ("rgbd_cells_300", "tum", 39, 1.0, {"detection_cell_size": 300}, list(range(8)), None),              # 3 x 2 cells over 256 px (40-px last column)
+]
+CASES = [c + (None,) for c in CASES] + GEOMETRY_CASES
+WIDE_CELL_CASES = ("cells_1025", "cells_2000", "cells_2000_retry", "tum_config_720p", "tum_config_720p_distorted", "tum_config_portrait")
 
 
-@pytest.mark.parametrize("name,kind,seed,scale,overrides,frames", CASES, ids=[c[0] for c in CASES])
-def test_sequence_parity(hip_lib, oracle_lib, name, kind, seed, scale, overrides, frames):
-    world, prm, sensor = make_case(kind, seed, scale, overrides)
+@pytest.mark.parametrize("name,kind,seed,scale,overrides,frames,size", CASES, ids=[c[0] for c in CASES])
+def test_sequence_parity(hip_lib, oracle_lib, name, kind, seed, scale, overrides, frames, size):
+    world, prm, sensor = make_case(kind, seed, scale, overrides, size=size)
     if name.startswith("kitti_hard"):
         world = HardWorld(world, seed)
     res, hip, orc = run_sequence(world, prm, sensor, frames)
@@ -58,6 +95,14 @@ def test_sequence_parity(hip_lib, oracle_lib, name, kind, seed, scale, overrides
         assert hip.get_state() == 2 and c["frame"] == 219
     if name in ("kitti_full_1000", "euroc_300", "tum_rgbd_300"):
         assert hip.get_state() == 2 and c["frame"] == len(frames) - 1, (hip.get_state(), c["frame"])
+    if size is not None or name == "rgbd_cells_300":
+        assert hip.get_state() == 2 and c["n_left"] > 0, (hip.get_state(), c["n_left"])   # (the oracle's shape tracks: parity is not two empty lists)
+    if name in WIDE_CELL_CASES:
+        assert int(hip.debug_stamps()[10]) == 1004, "cell 0 did not take the wide global path"
+    if name == "cells_2000_retry":
+        assert c["retry_left"] == 1, "the <200-corner retry path was not exercised on the wide cell"
+    if name == "tum_rgbd_distorted":
+        assert hip.get_state() == 2 and c["frame"] == len(frames) - 1
     if name == "tum_rgbd":
         assert c["n_right"] == 0
         # (more map points than one resolver super-chunk holds: the compacted query list and several super-chunks were exercised)
@@ -456,6 +501,111 @@ def test_lockstep_batch_equals_the_oracles(hip_lib, oracle_lib):
         co, ch = orc.counts(), batch.counts(s)
         bad = {k: (ch.get(k), v) for k, v in co.items() if ch.get(k) != v}
         assert not bad, f"sequence {s}: counters (hip, oracle) {bad}"
+
+
+LOCKSTEP_GEOMETRY = [
+    # id, world (kind, seed, size), overrides.  strips_257: a noise patch over cell 0 of every image (more raw corners than one workgroup's LDS
+    # holds) sends that cell through k_cells_strip / k_cells_big / radii / select in the batch
+    ("strips_257", ("kitti", 33, KITTI_SHAPE), {"detection_cell_size": 257}),
+    ("stereo_720p", ("kitti", 36, (1280, 720)), {}),                                   # map lists over LS_BINS: the wave-per-query kernels
+    ("stereo_portrait", ("kitti", 40, (720, 1280)), {}),                               # row lists over LS_BINS (H + 1 > 1100)
+    ("radius_75", ("kitti", 32, (620, 188)), {"tracking_radius": 75}),                 # cell_search_radius 3
+    ("cells_100", ("kitti", 33, KITTI_SHAPE), {"detection_cell_size": 100, "max_keypoints_per_cell": 40}),   # 312 k_cells workgroups > CUs: small-LDS instance
+    ("kitti04_shape", ("kitti", 31, (1226, 370)), {}),
+]
+
+
+@pytest.mark.parametrize("name,world_key,overrides", LOCKSTEP_GEOMETRY, ids=[g[0] for g in LOCKSTEP_GEOMETRY])
+def test_lockstep_batch_geometry_equals_the_oracles(hip_lib, oracle_lib, name, world_key, overrides):
+    """the lock-step batch (three sequences, 12 frames, three frames in flight) on shapes that switch its kernels' routes: each sequence against
+    its own oracle on every pose and state and on its counters after the last frame.  The sequences share one world at different frame offsets."""
+    import torch
+    from oracle import pyoracle as O
+    from parity_util import pose_errors
+    B, n, depth = 3, 12, 3
+    kind, seed, size = world_key
+    world, prm, _ = make_case(kind, seed, 1.0, overrides, size=size)
+    W, H = world.W, world.H
+    pitch = ((W + 63) // 64) * 64
+    frames = [[world.render_stereo(2 * s + i) for i in range(n)] for s in range(B)]
+    if name == "strips_257":
+        patch = np.random.default_rng(5).integers(0, 256, size=(257, 257), dtype=np.uint8)
+
+        def patched(img):
+            img = img.copy()
+            img[:257, :257] = patch
+            return img
+        frames = [[(patched(a), patched(b)) for a, b in seq] for seq in frames]
+    dev = torch.zeros((B, n, 2, H, pitch), dtype=torch.uint8, device="cuda")
+    for s in range(B):
+        for i in range(n):
+            dev[s, i, 0, :, :W] = torch.from_numpy(frames[s][i][0]).cuda(); dev[s, i, 1, :, :W] = torch.from_numpy(frames[s][i][1]).cuda()
+    torch.cuda.synchronize()
+    batch = hip_lib.LvtBatch(prm, B)
+    got, inflight = [], 0
+    for i in range(n):
+        batch.track_device_async([dev[s, i, 0].data_ptr() for s in range(B)], [dev[s, i, 1].data_ptr() for s in range(B)], H, W, pitch)
+        inflight += 1
+        if inflight >= depth:
+            got.append(batch.wait()); inflight -= 1
+    while inflight:
+        got.append(batch.wait()); inflight -= 1
+    assert batch.last_error() == "", batch.last_error()
+    if name == "strips_257":   # cell 0 of sequence 0's left image in the last frame: strips (+ three-launch ANMS), as debug_stamps() reports it
+        stamps = np.zeros(32, np.int64)
+        hip_lib.load_library().lvt_amd_get_debug(batch._h, stamps.ctypes.data_as(ctypes.c_void_p))
+        assert int(stamps[10]) in (1001, 1002), int(stamps[10])
+    for s in range(B):
+        orc = O.Oracle(prm, 1)
+        for i in range(n):
+            Ro, to = orc.track(*frames[s][i])
+            Rb, tb, st = got[i]
+            e_t, e_R = pose_errors(Rb[s], tb[s], Ro, to)
+            assert e_t <= POSE_TOL and e_R <= POSE_TOL and st[s] == orc.status, f"sequence {s} frame {i}: {e_t:.2e} {e_R:.2e}"
+        co, ch = orc.counts(), batch.counts(s)
+        bad = {k: (ch.get(k), v) for k, v in co.items() if ch.get(k) != v}
+        assert not bad, f"sequence {s}: counters (hip, oracle) {bad}"
+        assert orc.status == 2
+
+
+def test_grid_limits_are_refused(hip_lib):
+    """lvt_create refuses a detection grid it cannot hold (include/lvt_c.h): 65 cells (1241 x 420 at cell 100), and a cell side over CELL_SIDE_MAX
+    (4096 px); the largest side it takes is created"""
+    _, prm, _ = make_case("kitti", 0, 1.0, {"detection_cell_size": 100})
+    prm.img_width, prm.img_height = 1241, 420
+    with pytest.raises(Exception):
+        hip_lib.LvtSystem.create(prm, 1)
+    prm.img_height = 400                                                   # 13 x 4 = 52 cells
+    assert hip_lib.LvtSystem.create(prm, 1) is not None
+    prm.detection_cell_size = 5000
+    for w, h, ok in ((4097, 300, False), (300, 4097, False), (4096, 300, True)):
+        prm.img_width, prm.img_height = w, h
+        if ok:
+            assert hip_lib.LvtSystem.create(prm, 1) is not None
+        else:
+            with pytest.raises(Exception):
+                hip_lib.LvtSystem.create(prm, 1)
+
+
+def test_more_key_points_than_a_cell_emits(hip_lib, oracle_lib):
+    """a single dense 640 x 480 cell allowed 3 000 key points: more than the CELL_OUT_CAP = 2 048 a cell may emit survive, OVF_CELL_OUT is set
+    and reported, and the features kept are the leading part of the oracle's list (its first 2 048 before BRIEF's border filter)"""
+    from oracle import pyoracle
+    world, prm, _ = make_case("tum", 4, 1.0, {"max_keypoints_per_cell": 3000})
+    rng = np.random.default_rng(3)
+    a = rng.integers(0, 256, size=(world.H + 2, world.W + 2)).astype(np.float32)
+    img = (a[:-2, :-2] + a[:-2, 1:-1] + a[:-2, 2:] + a[1:-1, :-2] + a[1:-1, 1:-1] + a[1:-1, 2:] + a[2:, :-2] + a[2:, 1:-1] + a[2:, 2:]) / 9.0
+    img = np.ascontiguousarray(np.clip((img - 128.0) * 3.0 + 128.0, 0, 255).astype(np.uint8))
+    hip = hip_lib.LvtSystem.create(prm, 2)
+    hip.track(img, np.full((world.H, world.W), 2.0, np.float32))
+    xo, ro, do, _ = pyoracle.compute_features(img, prm)
+    xh, rh, dh = hip.features(0)
+    assert len(xo) > 2048 + 100, len(xo)                                 # (the border filter takes a few of the first 2 048)
+    m = re.search(r"overflow mask (0x[0-9a-f]+)", hip.last_error())
+    assert m and int(m.group(1), 16) == 2 and hip.counts()["overflow"] == 2, (hip.last_error(), hip.counts()["overflow"])
+    n = len(xh)
+    assert 0 < n < len(xo)
+    assert np.array_equal(xh, xo[:n]) and np.array_equal(rh, ro[:n]) and np.array_equal(dh, do[:n])
 
 
 def test_lm_rejections_inside_a_tracked_sequence(hip_lib, oracle_lib):

@@ -18,32 +18,89 @@ def _plane_expected(O, img, prm):
     return out
 
 
-@pytest.mark.parametrize("kind", ["noise", "world"])
-def test_score_and_boxsum_planes(hip_lib, oracle_lib, kind):
-    """k_score: per-cell OAST-9/16 score (incl. the 3-px dead band of every cell) and the 9x9 box sums, every pixel"""
+FEATURE_GEOMETRY = [
+    # id, image size, world seed, cell size, key points per cell (None: KITTI's shape, cell 250, 150 key points; noise fills every cell: at most
+    # NF_MAX = 4 096 features per image)
+    ("kitti", None, 11, None, None),
+    ("cells_48", (620, 188), 32, 48, 30),         # below one k_score tile: pass 0 compacts the score map, a tile holds two cell boundaries
+    ("cells_64", (620, 188), 32, 64, 100),        # smallest size with k_score's segments
+    ("cells_100", (1241, 376), 33, 100, 40),      # 52 cells, 41-px last column, 76-row last row
+    ("cells_257", (1241, 376), 33, 257, 150),     # row strips + three-launch ANMS on cells other than 0 too
+    ("cells_1024", (1241, 376), 33, 1024, 600),   # the widest cell on the LDS paths
+    ("cells_2000", (1241, 376), 33, 2000, 1000),  # one 1241 x 376 cell: the wide global path
+    ("one_interior_px", (757, 507), 34, 250, 150),
+    ("no_interior", (753, 506), 34, 250, 150),
+]
+# cell 0's route through k_cells_big (debug_stamps()[10]): 1001 / 1002 strips, 1003 the whole cell on global scratch; 1004 the wide global path
+ROUTES = {("cells_257", "noise"): (1001, 1002), ("cells_257", "noise_tall_blob"): (1003,), ("cells_1024", "world"): (1001, 1002),
+          ("cells_1024", "noise"): (1003,), ("cells_2000", "world"): (1004,), ("cells_2000", "noise"): (1004,)}
+_GEO_CASES = [(g, k) for g in FEATURE_GEOMETRY for k in ("noise", "world")] + [(FEATURE_GEOMETRY[4], "noise_tall_blob")]
+
+
+@pytest.mark.parametrize("geo,kind", _GEO_CASES, ids=[k if g[1] is None else f"{g[0]}-{k}" for g, k in _GEO_CASES])
+def test_score_and_boxsum_planes(hip_lib, oracle_lib, geo, kind):
+    """k_score: per-cell OAST-9/16 score (incl. the 3-px dead band of every cell) and the 9x9 box sums, every pixel, and both images' features --
+    key points, responses, descriptors, order -- against the oracle; on KITTI's shape and on the shapes where the feature stage changes its route"""
     from parity_util import make_case
-    O = oracle_lib
-    world, prm, _ = make_case("kitti", 11, 1.0)
-    if kind == "noise":
-        rng = np.random.default_rng(0)
-        L = rng.integers(0, 256, size=(world.H, world.W), dtype=np.uint8)      # corner-dense worst case
+    from oracle import pyoracle
+    name, size, seed, cs, max_kp = geo
+    overrides = {} if cs is None else {"detection_cell_size": cs, "max_keypoints_per_cell": max_kp}
+    world, prm, _ = make_case("kitti", seed, 1.0, overrides, size=size)
+    H, W = world.H, world.W
+    rng = np.random.default_rng(0 if cs is None else cs)
+    if kind == "noise":      # corner-dense worst case: the stress for NMS + ANMS + the std::sort emulation
+        L = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
+        R = np.ascontiguousarray(L[:, ::-1])
+    elif kind == "noise_tall_blob":   # enough raw corners for the strips, and a 4-connected corner blob 137 rows tall across them: they cannot vouch
+        L = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
+        L[50:210, 80:120] = 20
+        L[60:200, 96:101] = np.tile(np.array([[128, 128, 128, 128, 20], [128, 235, 128, 235, 128]], np.uint8), (70, 1))
         R = np.ascontiguousarray(L[:, ::-1])
     else:
         L, R = world.render_stereo(0)
     hip = hip_lib.LvtSystem.create(prm, 1)
     hip.track(L, R)
     for eye, img in ((0, L), (1, R)):
-        sp = hip.plane(eye, 0)[:, :world.W].astype(np.int32)
-        assert np.array_equal(sp, _plane_expected(O, img, prm)), f"score plane eye {eye}"
+        sp = hip.plane(eye, 0)[:, :W].astype(np.int32)
+        assert np.array_equal(sp, _plane_expected(oracle_lib, img, prm)), f"score plane eye {eye}"
         a = np.pad(img.astype(np.int64), 4)
-        box = sum(a[dy:dy + world.H, dx:dx + world.W] for dy in range(9) for dx in range(9))
-        assert np.array_equal(hip.plane(eye, 1)[:, :world.W].astype(np.int64), box), f"box sums eye {eye}"
-    if kind == "noise":   # noise is the dense stress for NMS + ANMS + the std::sort emulation: compare features too
-        from oracle import pyoracle
-        for eye, img in ((0, L), (1, R)):
-            xo, ro, do, _ = pyoracle.compute_features(img, prm)
-            xh, rh, dh = hip.features(eye)
-            assert np.array_equal(xh, xo) and np.array_equal(rh, ro) and np.array_equal(dh, do)
+        box = sum(a[dy:dy + H, dx:dx + W] for dy in range(9) for dx in range(9))
+        assert np.array_equal(hip.plane(eye, 1)[:, :W].astype(np.int64), box), f"box sums eye {eye}"
+        xo, ro, do, _ = pyoracle.compute_features(img, prm)
+        xh, rh, dh = hip.features(eye)
+        assert len(xo) > 0
+        assert np.array_equal(xh, xo) and np.array_equal(rh, ro) and np.array_equal(dh, do), (name, kind, eye, len(xh), len(xo))
+    if (name, kind) in ROUTES:
+        assert int(hip.debug_stamps()[10]) in ROUTES[(name, kind)], (name, kind, int(hip.debug_stamps()[10]))
+    assert hip.counts()["overflow"] == 0, hip.counts()["overflow"]
+    # (only noise on a whole-cell path may outlast the early stream's gate waits: reported, results unaffected)
+    err = hip.last_error()
+    assert err == "" or (kind.startswith("noise") and "results unaffected" in err), err
+
+
+def test_anms_decision_across_the_largest_cell(hip_lib, oracle_lib):
+    """one 4096 x 1200 detection cell -- CELL_SIDE_MAX wide, the wide global path -- whose ANMS decision radius is a distance of about 4 100 px:
+    radius^2 over 2^24, past three 8-bit digits of the radix select.  A strong square top left, a weaker one bottom right (its corners' only
+    1.11x-stronger neighbours are the first square's), weaker squares 1 000 px apart between them; six key points per cell put the decision on
+    the bottom-right square's corners.  Key points, responses, descriptors and order against the oracle."""
+    from oracle import pyoracle
+    W, H = 4096, 1200
+    prm = hip_lib.tum_params(width=W, height=H, fx=2000.0, fy=2000.0, cx=W / 2.0, cy=H / 2.0)
+    prm.detection_cell_size = 5000
+    prm.max_keypoints_per_cell = 6
+    img = np.full((H, W), 100, np.uint8)
+    img[40:52, 40:52] = 255
+    img[1130:1142, 4030:4042] = 200
+    for k, v in enumerate((180, 165, 152)):                               # each more than 1.11x weaker than the one before
+        img[500:512, 1000 * (k + 1):1000 * (k + 1) + 12] = v
+    hip = hip_lib.LvtSystem.create(prm, 2)
+    hip.track(img, np.full((H, W), 2.0, np.float32))
+    xo, ro, do, _ = pyoracle.compute_features(img, prm)
+    xh, rh, dh = hip.features(0)
+    assert len(xo) >= 6 and xo[:, 0].max() > 4000 and xo[:, 0].min() < 100, xo
+    assert np.array_equal(xh, xo) and np.array_equal(rh, ro) and np.array_equal(dh, do), (xh, xo)
+    assert int(hip.debug_stamps()[10]) == 1004
+    assert hip.counts()["overflow"] == 0 and hip.last_error() == "", hip.last_error()
 
 
 @pytest.mark.parametrize("kind", ["noise", "blurred_noise", "tall_blobs", "world"])
