@@ -130,6 +130,27 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
 /* oldest un-collected frame: R = B x 9 doubles, t = B x 3 doubles, status = B ints (any may be NULL) */
 LVT_API void lvt_amd_batch_wait(lvt_handle h, double *R, double *t, int *status);
 LVT_API void lvt_amd_batch_get_counts(lvt_handle h, int seq, int out[32]);
+/* ---- MIXED lock-step batch: every sequence with its own parameters ---------------------------------------
+ * The reference gives every lvt_system its own lvt_parameters; KITTI 00 - 07 alone has three calibrations and three image sizes.
+ * B sequences, sequence s with parameters p[s] (any mix of image size, intrinsics, detection grid, radii, thresholds, triangulation
+ * policy).  Shared by the whole batch: the sensor type and the capacities (map / feature / cell limits).  NULL when any p[s] is one
+ * lvt_amd_create would refuse.  The uniform calls above keep their behaviour and their launches; a mixed batch takes its frames through
+ * the _mixed call below (which a uniform batch accepts too). */
+LVT_API lvt_handle lvt_amd_batch_create_mixed(const lvt_amd_params *p /* [n_sequences] */, int sensor_type, int n_sequences);
+/* per-sequence image geometry: arrays of B.  d_left[s] == NULL: sequence s has NO frame in this step -- it is left exactly as it is: no
+ * frame is counted for it, lvt_amd_batch_wait returns its last pose and state, lvt_amd_batch_get_counts its last frame's counters (drives of
+ * different lengths share a chain until the longest one ends).  Returns 0 when the step was enqueued; -1 when it was rejected -- a size that
+ * is not that sequence's, a pitch that is not a multiple of 16, every pointer NULL -- and then NOTHING was enqueued and lvt_amd_last_error
+ * names the sequence. */
+LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *const *d_left, const void *const *d_right,
+                                                   const int *n_rows, const int *n_cols, const int *pitch_bytes);
+/* the parameters sequence `seq` was created with; 1 / 0 (not a batch handle, seq out of range) */
+LVT_API int lvt_amd_batch_get_params(lvt_handle h, int seq, lvt_amd_params *out);
+/* the work tables a mixed batch of these parameters launches its corner-score and corner-cell kernels from (host code, no GPU needed):
+ * cells[i] = sequence << 16 | eye << 8 | cell, by non-increasing cell area; score[g] = (2 sequence + eye) << 22 | tile row << 8 | tile column for
+ * workgroup g.  counts[0 / 1]: entries of the two tables, of which at most cells_cap / score_cap are written.  1 / 0 (refused parameters). */
+LVT_API int lvt_amd_batch_mixed_tables(const lvt_amd_params *p, int sensor_type, int n_sequences, unsigned *cells, int cells_cap,
+                                       unsigned *score, int score_cap, int counts[2]);
 
 /* run all work of this handle on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 LVT_API void lvt_amd_set_stream(lvt_handle h, void *hip_stream);

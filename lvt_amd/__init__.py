@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "lvt_amd_batch_create", "lvt_amd_batch_size", "lvt_amd_batch_track_device_async", "lvt_amd_batch_wait",
     "lvt_amd_batch_get_counts", "lvt_amd_create_on_device", "lvt_amd_get_device", "lvt_amd_wait_status", "lvt_amd_get_host_stats",
     "lvt_amd_track_async", "lvt_amd_track_rgbd_async", "lvt_amd_pnp_trace", "lvt_amd_create_pooled", "lvt_amd_wait_pose",
+    "lvt_amd_batch_create_mixed", "lvt_amd_batch_track_device_async_mixed", "lvt_amd_batch_get_params", "lvt_amd_batch_mixed_tables",
 ]
 
 N_COUNTS = 32
@@ -135,6 +136,15 @@ def load_library():
     L.lvt_amd_batch_track_device_async.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int]
     L.lvt_amd_batch_wait.argtypes = [vp, vp, vp, vp]
     L.lvt_amd_batch_get_counts.argtypes = [vp, C.c_int, vp]
+    L.lvt_amd_batch_create_mixed.restype = vp
+    L.lvt_amd_batch_create_mixed.argtypes = [vp, C.c_int, C.c_int]
+    L.lvt_amd_batch_track_device_async_mixed.restype = C.c_int
+    L.lvt_amd_batch_track_device_async_mixed.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lvt_amd_batch_get_params.restype = C.c_int
+    L.lvt_amd_batch_get_params.argtypes = [vp, C.c_int, vp]
+    L.lvt_amd_batch_mixed_tables.restype = C.c_int
+    L.lvt_amd_batch_mixed_tables.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    L.lvt_amd_batch_size.restype = C.c_int
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -365,13 +375,28 @@ class LvtSystem:
 class LvtBatch:
     """B independent sequences advanced in lock-step by one launch chain on one GPU (include/lvt_amd_ext.h)."""
 
-    def __init__(self, params: LvtParameters, n_sequences: int, sensor_type: int = eSensor_STEREO):
+    def __init__(self, params, n_sequences: int = None, sensor_type: int = eSensor_STEREO):
+        """params: one LvtParameters for all n_sequences sequences -- or a list of them, one per sequence (a MIXED batch: image size, intrinsics,
+        detection grid, radii and thresholds per sequence; frames go through track_device_async_mixed)"""
         L = load_library()
+        if isinstance(params, (list, tuple)):
+            if n_sequences is not None and n_sequences != len(params):
+                raise ValueError("n_sequences differs from the number of parameter sets")
+            pods = (ParamsPOD * len(params))(*[p.to_pod() for p in params])
+            self._h = L.lvt_amd_batch_create_mixed(pods, sensor_type, len(params))
+            if not self._h:
+                raise RuntimeError("lvt_amd_batch_create_mixed failed (a refused parameter set, or no usable HIP device -- no CPU fallback)")
+            self.B, self.mixed = len(params), True
+            return
         pod = params.to_pod()
         self._h = L.lvt_amd_batch_create(C.byref(pod), sensor_type, n_sequences)
         if not self._h:
             raise RuntimeError("lvt_amd_batch_create failed (no usable HIP device -- no CPU fallback)")
-        self.B = n_sequences
+        self.B, self.mixed = n_sequences, False
+
+    @classmethod
+    def create_mixed(cls, params_list, sensor_type: int = eSensor_STEREO) -> "LvtBatch":
+        return cls(list(params_list), None, sensor_type)
 
     def close(self):
         if self._h:
@@ -387,6 +412,22 @@ class LvtBatch:
     def track_device_async(self, d_left, d_right, rows, cols, pitch):
         a = (C.c_void_p * self.B)(*[int(x) for x in d_left]); b = (C.c_void_p * self.B)(*[int(x) for x in d_right])
         load_library().lvt_amd_batch_track_device_async(self._h, a, b, rows, cols, pitch)
+
+    def track_device_async_mixed(self, d_left, d_right, rows, cols, pitch) -> int:
+        """one lock-step step with per-sequence geometry (sequences of length B); d_left[s] None: sequence s has no frame in this step.
+        0: enqueued; -1: rejected, nothing enqueued (last_error() says why)"""
+        vps = C.c_void_p * self.B
+        ints = C.c_int * self.B
+        a = vps(*[None if x is None else int(x) for x in d_left])
+        b = vps(*[None if x is None else int(x) for x in d_right])
+        return load_library().lvt_amd_batch_track_device_async_mixed(self._h, a, b, ints(*[int(x) for x in rows]), ints(*[int(x) for x in cols]),
+                                                                    ints(*[int(x) for x in pitch]))
+
+    def params(self, seq: int) -> LvtParameters:
+        pod = ParamsPOD()
+        if not load_library().lvt_amd_batch_get_params(self._h, seq, C.byref(pod)):
+            raise IndexError(f"no sequence {seq} in this batch")
+        return LvtParameters(**{n: getattr(pod, n) for n, _ in ParamsPOD._fields_ if n in LvtParameters.__dataclass_fields__})
 
     def wait(self):
         R = np.zeros((self.B, 3, 3)); t = np.zeros((self.B, 3)); st = np.zeros(self.B, np.int32)
@@ -408,6 +449,19 @@ class LvtBatch:
     timeline = LvtSystem.timeline   # (sequence 0's stamps)
     host_stats = LvtSystem.host_stats
     debug_stamps = LvtSystem.debug_stamps
+
+
+def mixed_tables(params_list, sensor_type: int = eSensor_STEREO):
+    """(cells, score): the work tables a mixed batch of these parameters launches k_cells_mixed / k_score_mixed from (uint32 arrays, one entry per
+    workgroup; include/lvt_amd_ext.h, lvt_amd_batch_mixed_tables).  Host code: needs the library, not a GPU.  None: refused parameters."""
+    L = load_library()
+    pods = (ParamsPOD * len(params_list))(*[p.to_pod() for p in params_list])
+    n = np.zeros(2, np.int32)
+    if not L.lvt_amd_batch_mixed_tables(pods, sensor_type, len(params_list), None, 0, None, 0, _p(n)):
+        return None
+    cells, score = np.zeros(int(n[0]), np.uint32), np.zeros(int(n[1]), np.uint32)
+    L.lvt_amd_batch_mixed_tables(pods, sensor_type, len(params_list), _p(cells), len(cells), _p(score), len(score), _p(n))
+    return cells, score
 
 
 def pnp(params: LvtParameters, q_in, p_in, pts, obs):

@@ -120,29 +120,11 @@ __device__ __forceinline__ void feat_begin(Seq &S, const FrameArgs &f, int par) 
     if (f.absent) c.poison = 1;
 }
 
-// BEGIN = single sequence: `fa` carries the frame's inputs, block (0, 0, 0) publishes them for the later kernels
+// one TS_W x TS_H tile (bx, by) of image `eye` of sequence S; tiles_x: tiles per tile row of THAT image (the stride of its segment lists).
+// BEGIN = single sequence: `fa` carries the frame's inputs
 template <bool BEGIN>
-__global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par, int z0, int box) {  // z0: first image of this launch (a batch's images may come in several launches); box: 0 = no box-sum plane (k_brief_img builds the sums from the image)
-    const int seq = (blockIdx.z + z0) >> 1, eye = (blockIdx.z + z0) & 1;
-    const Seq &S = seq_const(seqs, seq);  // (read through the constant address space: global, not flat, accesses -- lvt_dev.h; the fields written below are not read here)
-    const FrameBuf &FB = S.fb[par];
-    if (FB.fc->poison) return;
-    if (BEGIN && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) feat_begin(seqs[seq], fa, par);
-    if (eye == 1 && S.prm.sensor == 2) return;
+__device__ __forceinline__ void score_tile(const Seq &S, const FrameBuf &FB, const FrameArgs &fa, int eye, int bx, int by, int tiles_x, int box) {
     const int W = S.prm.W, H = S.prm.H;
-    // workgroups go to the 8 XCDs round-robin by their linear id and every XCD has its own L2: with the plain mapping the four neighbours of a
-    // tile -- which share its halo rows and its 128-byte lines -- sit on other XCDs, and an image was fetched 2.9 times (rocprofv3 FETCH_SIZE
-    // 2.7 MB per stereo pair).  When a plane's tile count is a multiple of 8, XCD x takes the tiles [x n/8, (x + 1) n/8) of the row-major
-    // order: a band of whole tile rows, whose lines are pulled into ONE L2.
-    int bx = blockIdx.x, by = blockIdx.y;
-    {
-        const int n_tiles = gridDim.x * gridDim.y;
-        if ((n_tiles & 7) == 0) {
-            const int lid = blockIdx.x + gridDim.x * blockIdx.y;
-            const int t = (lid & 7) * (n_tiles >> 3) + (lid >> 3);
-            bx = t % gridDim.x, by = t / gridDim.x;
-        }
-    }
     const int x0 = bx * TS_W, y0 = by * TS_H;
     if (x0 >= W || y0 >= H) return;
     const uint8_t *img = BEGIN ? fa.img[eye] : FB.img[eye];
@@ -331,7 +313,7 @@ __global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par,
         const int incl = row16_incl_scan(nc | (ncl << 8));
         const int excl = (incl & 0xFF) - nc;
         if (gy < H) {
-            const size_t seg = (size_t)gy * gridDim.x + bx;
+            const size_t seg = (size_t)gy * tiles_x + bx;
             uint32_t *dst = FB.seg_keys[eye] + seg * TS_W + excl;
 #pragma unroll
             for (int k = 0; k < 4; k++)
@@ -354,6 +336,51 @@ __global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par,
             *reinterpret_cast<uint2 *>(FB.boxsum[eye] + (size_t)gy * pp + x0 + 4 * tx) = o;
         }
     }
+}
+
+// BEGIN = single sequence: block (0, 0, 0) publishes the frame's inputs for the later kernels
+template <bool BEGIN>
+__global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par, int z0, int box) {  // z0: first image of this launch (a batch's images may come in several launches); box: 0 = no box-sum plane (k_brief_img builds the sums from the image)
+    const int seq = (blockIdx.z + z0) >> 1, eye = (blockIdx.z + z0) & 1;
+    const Seq &S = seq_const(seqs, seq);  // (read through the constant address space: global, not flat, accesses -- lvt_dev.h; the fields written below are not read here)
+    const FrameBuf &FB = S.fb[par];
+    if (FB.fc->poison) return;
+    if (BEGIN && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) feat_begin(seqs[seq], fa, par);
+    if (eye == 1 && S.prm.sensor == 2) return;
+    // workgroups go to the 8 XCDs round-robin by their linear id and every XCD has its own L2: with the plain mapping the four neighbours of a
+    // tile -- which share its halo rows and its 128-byte lines -- sit on other XCDs, and an image was fetched 2.9 times (rocprofv3 FETCH_SIZE
+    // 2.7 MB per stereo pair).  When a plane's tile count is a multiple of 8, XCD x takes the tiles [x n/8, (x + 1) n/8) of the row-major
+    // order: a band of whole tile rows, whose lines are pulled into ONE L2.
+    int bx = blockIdx.x, by = blockIdx.y;
+    {
+        const int n_tiles = gridDim.x * gridDim.y;
+        if ((n_tiles & 7) == 0) {
+            const int lid = blockIdx.x + gridDim.x * blockIdx.y;
+            const int t = (lid & 7) * (n_tiles >> 3) + (lid >> 3);
+            bx = t % gridDim.x, by = t / gridDim.x;
+        }
+    }
+    score_tile<BEGIN>(S, FB, fa, eye, bx, by, (int)gridDim.x, box);
+}
+
+// ---- a MIXED lock-step batch (lvt_amd_batch_create_mixed): sequences with their own image sizes and detection grids ------------------
+// The two feature kernels whose work decomposition comes from the image shape take it from tables the host builds once at creation
+// (build_mixed_tables, lvt_host.hip), one 32-bit entry per WORKGROUP, read with one scalar load through the constant address space (the tables
+// are written once, before the first launch).  A per-workgroup table rather than a search in the images' prefix sums: one dependent load at the
+// kernel head instead of nine for 256 sequences, 4 bytes per tile (30 KB for eight KITTI drives), and the host can bake the XCD placement in.
+// score entry: image (2 sequence + eye) << 22 | tile row << 8 | tile column.  The grid holds exactly the tiles that exist.  Workgroup g runs on XCD
+// g & 7; of the workgroups [off, off + n) of an image those of XCD 0 get the first tiles of its row-major order, those of XCD 1 the next ... --
+// k_score's band-per-L2 placement (see above), here for ANY tile count and offset because the table, not a formula, assigns the tiles.
+constexpr int MIXED_TILE_COLS = 256, MIXED_TILE_ROWS = 1 << 14;  // what an entry's fields hold (images up to 16 384 px wide: far beyond the cell-grid limits)
+typedef const __attribute__((address_space(4))) uint32_t *TabConstPtr;
+__global__ __launch_bounds__(256) void k_score_mixed(Seq *seqs, const uint32_t *tab, int par, int box) {
+    const uint32_t e = ((TabConstPtr)tab)[blockIdx.x];
+    const int img = (int)(e >> 22), by = (int)((e >> 8) & (MIXED_TILE_ROWS - 1)), bx = (int)(e & (MIXED_TILE_COLS - 1));
+    const int seq = img >> 1, eye = img & 1;
+    const Seq &S = seq_const(seqs, seq);
+    const FrameBuf &FB = S.fb[par];
+    if (FB.fc->poison) return;  // (absent in this step, or the buffer is not free: feat_begin)
+    score_tile<false>(S, FB, FrameArgs{}, eye, bx, by, (S.prm.W + TS_W - 1) / TS_W, box);
 }
 
 // =================================================================================================
@@ -1607,6 +1634,19 @@ __global__ __launch_bounds__(1024) void k_cells(SeqArg<BV> sa, int pass, int par
 template <>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells<false>(SeqArg<false> sa, int pass, int par, CellOrder ord, int lanes, int raw_cap, NextPull np, int nsplit, unsigned token) {
     cells_entry<false>(sa, pass, par, ord, lanes, raw_cap, np, 0, token);
+}
+// The cells of a MIXED batch (see k_score_mixed): one table entry (sequence << 16 | eye << 8 | cell) per detection cell of every image of the batch,
+// sorted by cell area over ALL sequences, largest first -- what CellOrder does for one grid: the workgroups that start late are the short ones.
+// Same occupancy contract as the batch instance above (64 registers, two 80-KB workgroups per CU under RAW_CAP_SMALL).
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells_mixed(const Seq *seqs, const uint32_t *tab, int pass, int par, int raw_cap) {
+    const uint32_t e = ((TabConstPtr)tab)[blockIdx.x];
+    const int cell = (int)(e & 255u), eye = (int)((e >> 8) & 1u);
+    const Seq &S = seq_const(seqs, e >> 16);
+    const FrameBuf &FB = S.fb[par];
+    if (threadIdx.x == 0 && cell < CELLS_MAX) S.cell_big[eye][cell] = 0;  // (nobody reads it before this launch is over)
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const CellLds L = carve_cell_lds(smem, raw_cap);
+    cells_work(S, FB, eye, cell, pass, L, raw_cap);  // (a sequence that is absent in this step leaves at cell_begin)
 }
 
 // ---- an oversized cell as row strips --------------------------------------------------------------------------------------------

@@ -33,9 +33,11 @@ enum : int { MODE_MAP = 0, MODE_STAGED = 1, MODE_ROW = 2 };
 __device__ __forceinline__ void frame_prologue(const Seq &S, Ctl &c, int par, const Pose &predicted, const double mm_next[14], bool active,
                                                bool first, bool skipped) {
     const bool absent = skipped && S.fb[par].fc->absent != 0;  // (a pooled handle's idle step: nothing may change, not even the frame counter)
-    for (int i = 0; i < N_COUNTS; i++) c.counts[i] = 0;
-    c.counts[C_FRAME] = c.frame_number;
-    if (!absent) c.frame_number++;
+    if (!absent) {  // (an idle step's record repeats the sequence's last frame: counters, overflow mask, pose, state)
+        for (int i = 0; i < N_COUNTS; i++) c.counts[i] = 0;
+        c.counts[C_FRAME] = c.frame_number;
+        c.frame_number++;
+    }
     c.active = active ? 1 : 0;
     c.first_frame = first ? 1 : 0;
     c.do_pass2 = 0;
@@ -47,9 +49,11 @@ __device__ __forceinline__ void frame_prologue(const Seq &S, Ctl &c, int par, co
     c.n_pairs = 0;
     c.mm_pending = 0;
     const FeatCtl &fc = *S.fb[par].fc;
-    c.overflow = fc.overflow;
-    c.counts[C_RETRY_LEFT] = active ? fc.retry[0] : 0;  // (LOST: the reference returns before it detects anything; the feature
-    c.counts[C_RETRY_RIGHT] = active ? fc.retry[1] : 0;  //  stream here has run regardless -- its results are not reported)
+    if (!absent) {
+        c.overflow = fc.overflow;
+        c.counts[C_RETRY_LEFT] = active ? fc.retry[0] : 0;  // (LOST: the reference returns before it detects anything; the feature
+        c.counts[C_RETRY_RIGHT] = active ? fc.retry[1] : 0;  //  stream here has run regardless -- its results are not reported)
+    }
     if (!active) {  // LOST: return the last pose forever (lvt_system.cpp:161-166).  A SKIPPED frame (its features never arrived: a gate
                     // timed out, reported through lvt_amd_last_error) also returns the last pose, but the state stays what it was
         pose_to_Rt(c.last_pose, c.out_R, c.out_t);
@@ -2309,13 +2313,16 @@ __global__ __launch_bounds__(1024) void k_triangulate(SeqArg<BV> sa, int par, se
             ctl.out_status = 2;
         }
         // LOST: no features as far as any caller can see.  (Not for a pooled handle's idle step: the buffer still holds its last real frame's features.)
-        if (!ctl.active && !(ctl.skip && S.fb[par].fc->absent)) *S.fb[par].feat[0].n = *S.fb[par].feat[1].n = 0;
-        ctl.counts[C_N_LEFT] = *S.fb[par].feat[0].n;
-        ctl.counts[C_N_RIGHT] = *S.fb[par].feat[1].n;
-        ctl.counts[C_MAP_SIZE] = *S.map_n;
-        ctl.counts[C_STAGED_SIZE] = *S.staged_n;
-        ctl.overflow |= S.fb[par].fc->overflow;
-        ctl.counts[C_OVERFLOW] = ctl.overflow;
+        const bool idle = ctl.skip && S.fb[par].fc->absent;  // (no frame for this sequence in this step: its counters stay its last frame's, frame_prologue)
+        if (!ctl.active && !idle) *S.fb[par].feat[0].n = *S.fb[par].feat[1].n = 0;
+        if (!idle) {
+            ctl.counts[C_N_LEFT] = *S.fb[par].feat[0].n;
+            ctl.counts[C_N_RIGHT] = *S.fb[par].feat[1].n;
+            ctl.counts[C_MAP_SIZE] = *S.map_n;
+            ctl.counts[C_STAGED_SIZE] = *S.staged_n;
+            ctl.overflow |= S.fb[par].fc->overflow;
+            ctl.counts[C_OVERFLOW] = ctl.overflow;
+        }
         ctl.skip = 0;  // (a skipped frame ends here: every workgroup of k_match_map has read the flag long ago)
         ctl.dbg[46] = (long long)wall_clock64();
         if (run) {  // bring-up stamps of a triangulation frame (tools/cells_phases.py): staged update, row resolution, the rest

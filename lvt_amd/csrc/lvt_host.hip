@@ -130,6 +130,19 @@ struct Context {
     int ring_seqs[8] = {};     // ... and what every un-collected step was launched for
     int sensor = 1;
     Params prm{};
+    // A MIXED batch (lvt_amd_batch_create_mixed): sequence s has its own parameters prms[s] (image size, intrinsics, detection grid, radii, thresholds);
+    // prm and pitch are then sequence 0's (what the sequence-0 read-back calls use).  k_score / k_cells take their work from the two tables
+    // (build_mixed_tables); every other kernel of the chain is per-sequence by blockIdx.z and reads Seq::prm.  A uniform batch has mixed == false,
+    // empty tables and exactly the launches it had before mixed batches existed.
+    bool mixed = false;
+    std::vector<Params> prms;            // mixed: [B]; otherwise empty
+    std::vector<lvt_amd_params> in_prms; // what the caller handed in: [B] (mixed) or [1]
+    uint32_t *d_score_tab = nullptr, *d_cells_tab = nullptr;
+    int n_score_wgs = 0, n_cells_wgs = 0;
+    // per-launch decisions over the batch's sequences (a uniform context: its one parameter set's values)
+    bool any_staged = false, any_strips = false;
+    int max_cells = 0;
+    const Params &seq_prm(int s) const { return mixed ? prms[s] : prm; }
     hipStream_t stream = nullptr;    // tracking chain
     hipStream_t stream_f = nullptr;  // feature stage
     hipStream_t stream_e = nullptr;  // early part of find_matches of the next frame (behind the previous frame's k_pnp)
@@ -465,10 +478,53 @@ static void reset_state(Context *c, int only = -1) {  // lvt_system::reset (lvt_
     HIPCHK(c, hipStreamSynchronize(c->stream));
 }
 
-static Context *create_context(const lvt_amd_params &in, int sensor, int B, int device = -1) {
+// The work tables of a mixed batch (k_score_mixed / k_cells_mixed, k_features.hip), one 32-bit entry per workgroup.  Pure host code.
+//  cells: (sequence << 16 | eye << 8 | cell) for every detection cell of every image (an RGB-D sequence has one image), by NON-INCREASING cell area
+//         over all sequences; ties keep the order (sequence, cell, eye).
+//  score: (image << 22 | tile row << 8 | tile column), image = 2 sequence + eye; image i owns the workgroups [off_i, off_i + n_i) with off the prefix sum of
+//         the images' tile counts n_i = tiles_x tiles_y.  Workgroup g runs on XCD g & 7: the image's workgroups, ordered by (g & 7, g), take its tiles in
+//         row-major order, so every XCD's L2 sees one band of tile rows whatever n_i and off_i are.
+// false: an image has more tile columns / rows than an entry holds.
+static bool build_mixed_tables(const std::vector<Params> &ps, std::vector<uint32_t> &cells, std::vector<uint32_t> &score) {
+    struct Ent {
+        int area;
+        uint32_t v;
+    };
+    std::vector<Ent> es;
+    cells.clear(), score.clear();
+    for (size_t s = 0; s < ps.size(); s++) {
+        const Params &p = ps[s];
+        const int eyes = (p.sensor == 2) ? 1 : 2;
+        for (int cc = 0; cc < p.n_cells; cc++) {
+            const int cx = cc % p.cells_x, cy = cc / p.cells_x;
+            const int area = std::min(p.cell_size, p.W - cx * p.cell_size) * std::min(p.cell_size, p.H - cy * p.cell_size);
+            for (int e = 0; e < eyes; e++) es.push_back({area, (uint32_t)s << 16 | (uint32_t)e << 8 | (uint32_t)cc});
+        }
+        const int tx = (p.W + TS_W - 1) / TS_W, ty = (p.H + TS_H - 1) / TS_H;
+        if (tx > MIXED_TILE_COLS || ty > MIXED_TILE_ROWS) return false;
+        for (int e = 0; e < eyes; e++) {
+            const size_t off = score.size(), n = (size_t)tx * ty;
+            const uint32_t img = (uint32_t)(2 * s + e);
+            score.resize(off + n);
+            uint32_t t = 0;
+            for (size_t x = 0; x < 8; x++)
+                for (size_t g = off + ((x - off) & 7); g < off + n; g += 8, t++) score[g] = img << 22 | (t / (uint32_t)tx) << 8 | (t % (uint32_t)tx);
+        }
+    }
+    std::stable_sort(es.begin(), es.end(), [](const Ent &a, const Ent &b) { return a.area > b.area; });
+    for (const Ent &e : es) cells.push_back(e.v);
+    return true;
+}
+
+// in: ONE parameter set for all B sequences, or -- mixed -- B of them
+static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor, int B, int device) {
     if (sensor != 1 && sensor != 2) return nullptr;
-    Params prm;
-    if (!derive_params(in, sensor, prm)) return nullptr;
+    std::vector<Params> prms(mixed ? B : 1);
+    for (size_t s = 0; s < prms.size(); s++)
+        if (!derive_params(in[s], sensor, prms[s])) return nullptr;
+    const Params prm = prms[0];
+    std::vector<uint32_t> cells_tab, score_tab;
+    if (mixed && !build_mixed_tables(prms, cells_tab, score_tab)) return nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return nullptr;  // no CPU fallback, by design
     int cur = 0;
@@ -483,6 +539,14 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
         c->B = B;
         c->sensor = sensor;
         c->prm = prm;
+        c->mixed = mixed;
+        if (mixed) c->prms = prms;
+        c->in_prms.assign(in, in + prms.size());
+        for (const Params &q : prms) {
+            c->any_staged = c->any_staged || q.staged_th > 0;
+            c->any_strips = c->any_strips || q.big_cell_strips != 0;
+            c->max_cells = std::max(c->max_cells, q.n_cells);
+        }
         HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         {   // A lock-step batch's feature stream is confined to 7/8 of the device's CUs.  k_cells' workgroups (80 KB of LDS each, two per CU, 50 - 90 us)
             // otherwise hold EVERY CU's LDS while they run, and the single-workgroup kernels of the tracking / early chains (50 - 135 KB) -- whose loop
@@ -553,8 +617,10 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
         {
             int n_cu = 256;
             (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-            if (!prm.big_cell_strips && prm.n_cells * 2 * B > n_cu) c->cells_raw_cap = RAW_CAP_SMALL;
+            if (!mixed && !prm.big_cell_strips && prm.n_cells * 2 * B > n_cu) c->cells_raw_cap = RAW_CAP_SMALL;
+            if (mixed && !c->any_strips && (int)cells_tab.size() > n_cu) c->cells_raw_cap = RAW_CAP_SMALL;  // (the same rule: more cell workgroups than CUs)
         }
+        if (mixed) c->score_pieces = 1, c->score_pieces_auto = false;  // a mixed batch's k_score is one launch over its tile table (no pieces)
         if (const char *e = std::getenv("LVT_AMD_CELL_SPLIT")) c->cell_split = std::max(0, std::min(SPLIT_MAX, std::atoi(e)));
         if (const char *e = std::getenv("LVT_AMD_CELLS_RAW_CAP")) c->cells_raw_cap = std::max(RAW_CAP_SMALL, std::min(RAW_CAP, std::atoi(e) & ~1));
         if (const char *e = std::getenv("LVT_AMD_FUSED_PULL")) c->fuse_pull = std::atoi(e) != 0;
@@ -570,25 +636,28 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
         HIPCHK(c, hipHostMalloc((void **)&c->h_fargs, sizeof(FrameArgs) * B * RING, hipHostMallocDefault));
         c->h_seqs.resize(B);
         c->d_ctl.resize(B);
-        const size_t plane = (size_t)c->pitch * prm.H;
         for (int s = 0; s < B; s++) {
+            // every allocation whose size follows the image or the detection grid is sized by THIS sequence's parameters
+            const Params &q = prms[mixed ? s : 0];
+            const int pitch = ((q.W + 63) / 64) * 64;
+            const size_t plane = (size_t)pitch * q.H;
             Seq &S = c->h_seqs[s];
             std::memset(&S, 0, sizeof(S));
-            S.prm = prm;
+            S.prm = q;
             S.ctl = c->d_ctl[s] = c->dalloc<Ctl>(1);
-            S.plane_pitch = c->pitch;
+            S.plane_pitch = pitch;
             {
                 size_t off = 0;
-                for (int cc = 0; cc < prm.n_cells; cc++) {
-                    const int cx = cc % prm.cells_x, cy = cc / prm.cells_x;
-                    const int cw = std::min(prm.cell_size, prm.W - cx * prm.cell_size), ch = std::min(prm.cell_size, prm.H - cy * prm.cell_size);
+                for (int cc = 0; cc < q.n_cells; cc++) {
+                    const int cx = cc % q.cells_x, cy = cc / q.cells_x;
+                    const int cw = std::min(q.cell_size, q.W - cx * q.cell_size), ch = std::min(q.cell_size, q.H - cy * q.cell_size);
                     S.cell_scratch_off[cc] = off;
                     off += (size_t)cw * ch * 6;
                 }
             }
-            for (int e = 0; e < 2; e++) S.cell_scratch[e] = c->dalloc<uint32_t>((size_t)prm.W * prm.H * 6 + 64);
+            for (int e = 0; e < 2; e++) S.cell_scratch[e] = c->dalloc<uint32_t>((size_t)q.W * q.H * 6 + 64);
             for (int e = 0; e < 2; e++) {
-                S.strip_kp[e] = prm.big_cell_strips ? c->dalloc<uint32_t>((size_t)prm.n_cells * STRIPS * RAW_CAP) : c->dalloc_uncached<uint32_t>((size_t)prm.n_cells * SPLIT_MAX * SPLIT_KP_CAP);
+                S.strip_kp[e] = q.big_cell_strips ? c->dalloc<uint32_t>((size_t)q.n_cells * STRIPS * RAW_CAP) : c->dalloc_uncached<uint32_t>((size_t)q.n_cells * SPLIT_MAX * SPLIT_KP_CAP);
                 S.strip_n[e] = c->dalloc_uncached<int>((size_t)CELLS_MAX * STRIPS);
                 S.cell_big[e] = c->dalloc<int>(CELLS_MAX);
             }
@@ -600,9 +669,9 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
                     FB.score[e] = c->dalloc<uint8_t>(plane + 64);
                     FB.boxsum[e] = c->dalloc<uint16_t>(plane + 64);
                     {
-                        const size_t tiles_x = (size_t)(prm.W + TS_W - 1) / TS_W;
-                        FB.seg_keys[e] = c->dalloc<uint32_t>((size_t)prm.H * tiles_x * TS_W);
-                        FB.seg_cnt[e] = c->dalloc<uint16_t>((size_t)prm.H * tiles_x);
+                        const size_t tiles_x = (size_t)(q.W + TS_W - 1) / TS_W;
+                        FB.seg_keys[e] = c->dalloc<uint32_t>((size_t)q.H * tiles_x * TS_W);
+                        FB.seg_cnt[e] = c->dalloc<uint16_t>((size_t)q.H * tiles_x);
                     }
                     FB.cell_kp[e] = c->dalloc<float>((size_t)CELLS_MAX * CELL_OUT_CAP * 3);
                     FB.cell_n[e] = c->dalloc<int>(CELLS_MAX);
@@ -613,7 +682,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
                     }
                     FB.ext_xy[e] = FB.ext_xy_own[e] = c->d_ext[par][e];
                 }
-                if (s == 0 && sensor == 2) c->d_depth[par] = c->dalloc<float>((size_t)prm.W * prm.H + 4);
+                if (s == 0 && sensor == 2) c->d_depth[par] = c->dalloc<float>((size_t)q.W * q.H + 4);
             }
             for (int k = 0; k < 2; k++) {
                 alloc_points(c, S.map[k], MAP_MAX);
@@ -646,6 +715,14 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
         }
         c->d_seqs = c->dalloc<Seq>(B);
         HIPCHK(c, hipMemcpy(c->d_seqs, c->h_seqs.data(), sizeof(Seq) * B, hipMemcpyHostToDevice));
+        if (mixed) {
+            c->n_score_wgs = (int)score_tab.size(), c->n_cells_wgs = (int)cells_tab.size();
+            c->d_score_tab = c->dalloc<uint32_t>(score_tab.size());
+            c->d_cells_tab = c->dalloc<uint32_t>(cells_tab.size());
+            HIPCHK(c, hipMemcpy(c->d_score_tab, score_tab.data(), sizeof(uint32_t) * score_tab.size(), hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(c->d_cells_tab, cells_tab.data(), sizeof(uint32_t) * cells_tab.size(), hipMemcpyHostToDevice));
+            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cells_mixed), hipFuncAttributeMaxDynamicSharedMemorySize, CELLS_LDS_BYTES));
+        }
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cells<true>), hipFuncAttributeMaxDynamicSharedMemorySize, CELLS_LDS_BYTES));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cells<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CELLS_LDS_BYTES));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hamming_batched_lists<MODE_MAP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LS_LDS_BYTES));
@@ -667,6 +744,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
     }
     return c;
 }
+static Context *create_context(const lvt_amd_params &in, int sensor, int B, int device = -1) { return create_context(&in, false, sensor, B, device); }
 
 // ---- the per-frame launch chain -------------------------------------------------------------------
 static const char *kProfNames[Context::PROF_SLOTS] = {
@@ -761,7 +839,9 @@ static void enqueue_frame(Context *c) {
             LAUNCH(0, sf, k_feat_begin_pack, dim3(Bz), dim3(64), 0, S, pk, par, (seq_t)((c->enq >= NPAR && !evo) ? c->enq + 1 - NPAR : 0));
         } else
             LAUNCH(0, sf, k_feat_begin, dim3(Bz), dim3(64), 0, S, fa, par);
-        {   // the batch's images in score_pieces launches: see Context::score_pieces
+        if (c->mixed) {  // exactly the tiles that exist, each image's placed over the XCDs by the table (build_mixed_tables)
+            LAUNCH(2, sf, k_score_mixed, dim3(c->n_score_wgs), dim3(256), 0, S, c->d_score_tab, par, c->brief_from_image ? 0 : 1);
+        } else {   // the batch's images in score_pieces launches: see Context::score_pieces
             const int P = std::max(1, std::min(c->score_pieces, Bz));
             for (int q = 0; q < P; q++) {
                 const int z0 = 2 * (int)((long)Bz * q / P), z1 = 2 * (int)((long)Bz * (q + 1) / P);
@@ -778,12 +858,16 @@ static void enqueue_frame(Context *c) {
             // a single sequence's tall cells run as cell_split co-operating workgroups (cells_work_split); grid: helpers, main workgroups, pull, padded to 8
             const int ns = (B == 1 && !p.big_cell_strips) ? c->cell_split : 0;
             const int gx = (ns >= 2) ? ((((p.n_cells + 7) & ~7) * ns + pull_wgs + 7) & ~7) : p.n_cells + pull_wgs;
-            LAUNCH_S(3, sf, k_cells, (B == 1 ? dim3(gx, 2, 1) : dim3(p.n_cells * 2 * Bz, 1, 1)), dim3(1024), cells_lds_bytes(c->cells_raw_cap), pass, par, c->cell_order, 2 * Bz, c->cells_raw_cap, c->next_pull, ns, (++c->cell_token ? c->cell_token : ++c->cell_token));
-            if (p.big_cell_strips) {  // oversized cells: NMS as row strips on several CUs, then ANMS of the merged survivors in three launches
-                hipLaunchKernelGGL(k_cells_strip, dim3(p.n_cells * STRIPS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_big, dim3(p.n_cells, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_radii, dim3(p.n_cells * RADII_WGS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_select, dim3(p.n_cells, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
+            if (c->mixed) LAUNCH(3, sf, k_cells_mixed, dim3(c->n_cells_wgs), dim3(1024), cells_lds_bytes(c->cells_raw_cap), (const Seq *)S, c->d_cells_tab, pass, par, c->cells_raw_cap);
+            else LAUNCH_S(3, sf, k_cells, (B == 1 ? dim3(gx, 2, 1) : dim3(p.n_cells * 2 * Bz, 1, 1)), dim3(1024), cells_lds_bytes(c->cells_raw_cap), pass, par, c->cell_order, 2 * Bz, c->cells_raw_cap, c->next_pull, ns, (++c->cell_token ? c->cell_token : ++c->cell_token));
+            // (a mixed batch: when ANY sequence has cells tall enough to cut, over the largest grid -- a sequence without such cells leaves at cell_big != 1,
+            //  a cell index beyond a sequence's grid at cell_begin)
+            if (c->any_strips) {  // oversized cells: NMS as row strips on several CUs, then ANMS of the merged survivors in three launches
+                const int nc = c->max_cells;
+                hipLaunchKernelGGL(k_cells_strip, dim3(nc * STRIPS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
+                hipLaunchKernelGGL(k_cells_big, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
+                hipLaunchKernelGGL(k_cells_radii, dim3(nc * RADII_WGS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
+                hipLaunchKernelGGL(k_cells_select, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
                 if (c->prof) (void)hipEventRecord(c->ev[3][1], sf);  // (the slot's time covers the five launches)
             }
         }
@@ -853,7 +937,7 @@ static void enqueue_frame(Context *c) {
         LAUNCH_S(13, st, k_pnp, dim3(1, 1, Bz), dim3(PNP_THREADS), PNP_DYN_BYTES, par, seq, ep ? c->h_pose_dev + (size_t)slot * B : (PoseRec *)nullptr,
                  ep ? c->h_pose_done_dev + (size_t)slot * B : (seq_t *)nullptr);
     }
-    if (p.staged_th > 0)  // (a configuration without staging -- EuRoC, TUM -- never has staged points to list)
+    if (c->any_staged)  // (a configuration without staging -- EuRoC, TUM -- never has staged points to list; in a mixed batch such a sequence leaves at the kernel's head)
         LAUNCH_SM(16, st, k_candidates, MODE_STAGED, dim3(64, 1, Bz), dim3(256), 0, 0, par, (seq_t)0, 0);
     LAUNCH_S(20, st, k_triangulate, dim3(1, 1, Bz), dim3(1024), 0, par, seq, c->h_ctl_dev + (size_t)slot * B,
            c->h_done_dev + (size_t)slot * B, evo ? 0 : (c->force_row_fallback ? 2 : 1), (evo || c->sync_call) ? 1 : 0);
@@ -1391,13 +1475,107 @@ LVT_API lvt_handle lvt_amd_batch_create(const lvt_amd_params *p, int sensor_type
     }
     return nullptr;
 }
-LVT_API int lvt_amd_batch_size(lvt_handle h) { return static_cast<Context *>(h)->B; }
+// B sequences, sequence s with parameters p[s]: see Context::mixed
+LVT_API lvt_handle lvt_amd_batch_create_mixed(const lvt_amd_params *p, int sensor_type, int n_sequences) {
+    try {
+        if (!p || n_sequences < 1 || n_sequences > 256) return nullptr;
+        return static_cast<lvt_handle>(create_context(p, true, sensor_type, n_sequences, -1));
+    } catch (...) {
+    }
+    return nullptr;
+}
+// the work tables a mixed batch of these parameters would launch its k_cells / k_score from (build_mixed_tables; no GPU needed): counts[0 / 1] = entries of the
+// cells / score table, of which min(count, cap) are written.  0: a parameter set lvt_amd_batch_create_mixed refuses.
+LVT_API int lvt_amd_batch_mixed_tables(const lvt_amd_params *p, int sensor_type, int n_sequences, unsigned *cells, int cells_cap, unsigned *score, int score_cap,
+                                       int counts[2]) {
+    try {
+        if (!p || n_sequences < 1 || n_sequences > 256 || (sensor_type != 1 && sensor_type != 2)) return 0;
+        std::vector<Params> ps(n_sequences);
+        for (int s = 0; s < n_sequences; s++)
+            if (!derive_params(p[s], sensor_type, ps[s])) return 0;
+        std::vector<uint32_t> ct, st;
+        if (!build_mixed_tables(ps, ct, st)) return 0;
+        if (counts) counts[0] = (int)ct.size(), counts[1] = (int)st.size();
+        for (int i = 0; cells && i < cells_cap && i < (int)ct.size(); i++) cells[i] = ct[i];
+        for (int i = 0; score && i < score_cap && i < (int)st.size(); i++) score[i] = st[i];
+        return 1;
+    } catch (...) {
+    }
+    return 0;
+}
+LVT_API int lvt_amd_batch_get_params(lvt_handle h, int seq, lvt_amd_params *out) {
+    h = resolve_handle(h, false);
+    if (!is_ctx(h) || !out) return 0;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B || c->in_prms.empty()) return 0;
+    *out = c->in_prms[c->mixed ? seq : 0];
+    return 1;
+}
+LVT_API int lvt_amd_batch_size(lvt_handle h) {
+    h = resolve_handle(h, false);
+    return is_ctx(h) ? static_cast<Context *>(h)->B : 0;
+}
 
-LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d_left, const void *const *d_right, int n_rows, int n_cols,
-                                              int pitch_bytes) {
+// one lock-step step with per-sequence image geometry; d_left[s] == NULL: sequence s has no frame in it (FrameArgs::absent, the pooled seats' mechanism).
+// Everything is checked before anything is enqueued.
+LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *const *d_left, const void *const *d_right, const int *n_rows, const int *n_cols,
+                                                   const int *pitch_bytes) {
+    h = resolve_handle(h);
+    if (!is_ctx(h)) return -1;
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
+        if (!d_left || !d_right || !n_rows || !n_cols || !pitch_bytes) {
+            c->set_error("lvt_amd_batch_track_device_async_mixed: NULL argument");
+            return -1;
+        }
+        int present = 0;
+        for (int s = 0; s < c->B; s++) {
+            if (!d_left[s]) continue;
+            present++;
+            const Params &q = c->seq_prm(s);
+            if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || (pitch_bytes[s] & 15) || pitch_bytes[s] < n_cols[s]) {
+                char buf[200];
+                std::snprintf(buf, sizeof(buf), "lvt_amd_batch_track_device_async_mixed: sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch a multiple of 16)",
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H);
+                c->set_error(buf);
+                return -1;
+            }
+        }
+        if (!present) {
+            c->set_error("lvt_amd_batch_track_device_async_mixed: no sequence has a frame in this step");
+            return -1;
+        }
+        make_room(c);
+        for (int s = 0; s < c->B; s++) {
+            FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B + s];
+            f = FrameArgs{};
+            if (!d_left[s]) {
+                f.absent = 1;
+                continue;
+            }
+            f.img[0] = static_cast<const uint8_t *>(d_left[s]);
+            f.img[1] = static_cast<const uint8_t *>(d_right[s]);
+            f.img_pitch = pitch_bytes[s];
+        }
+        enqueue_frame(c);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+
+LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d_left, const void *const *d_right, int n_rows, int n_cols,
+                                              int pitch_bytes) {
+    h = resolve_handle(h);
+    if (!is_ctx(h)) return;
+    Context *c = static_cast<Context *>(h);
+    DeviceGuard guard(c);
+    try {
+        if (c->mixed) {
+            c->set_error("lvt_amd_batch_track_device: a mixed batch takes its frames through lvt_amd_batch_track_device_async_mixed");
+            return;
+        }
         if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
             c->set_error("lvt_amd_batch_track_device: image size / pitch mismatch");
             return;
@@ -1420,6 +1598,8 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
 }
 // poses of the oldest un-collected batch frame: R = B x 9 doubles (row-major 3x3 each), t = B x 3, status = B ints
 LVT_API void lvt_amd_batch_wait(lvt_handle h, double *R, double *t, int *status) {
+    h = resolve_handle(h);
+    if (!is_ctx(h)) return;
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
@@ -1434,6 +1614,8 @@ LVT_API void lvt_amd_batch_wait(lvt_handle h, double *R, double *t, int *status)
     }
 }
 LVT_API void lvt_amd_batch_get_counts(lvt_handle h, int seq, int out[LVT_AMD_C__COUNT]) {
+    h = resolve_handle(h);
+    if (!is_ctx(h)) return;
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
