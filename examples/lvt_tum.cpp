@@ -3,8 +3,9 @@
 // Same argv, inputs and outputs as the reference's example binary (examples/tum_rgbd/tum_rgbd_example.cpp:49-150 there):
 //     lvt_tum <tum_sequences_root_dir> <associations_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt]
 // reads <associations_dir>/<dataset_name>.txt ("t_rgb rgb/xxx.png t_depth depth/xxx.png" per line), the colour and the 16-bit
-// depth PNGs below <root>/<dataset_name>/, converts colour to gray (cv::cvtColor weights) and depth to metres in float
-// (value * (1.0f / 5000.0f), as cv::Mat::convertTo does), tracks through lvt_amd_track_rgbd and writes <dataset_name>.txt in
+// depth PNGs below <root>/<dataset_name>/, converts colour to gray (cv::cvtColor weights), hands the PNG's 16-bit depth plane to
+// lvt_amd_track_rgbd16_async with 1.0f / 5000.0f metres per unit (the tracker computes value * (1.0f / 5000.0f) in float where it has key
+// points -- what cv::Mat::convertTo gives the reference for every pixel) and writes <dataset_name>.txt in
 // the TUM trajectory format "t x y z qx qy qz qw" with the reference's precision (6 digits for t, 7 for the rest).
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
@@ -71,21 +72,17 @@ int main(int argc, char **argv) {
     std::vector<double> poses;                 // q (w x y z), p per processed frame
     double total_time = 0;
     long n = 0;
-    // frame i is enqueued (lvt_amd_track_rgbd_async: pageable buffers are the library's copy when the call returns), frame i + 1 is read, decoded and
-    // converted to metres while it tracks, then frame i's pose is collected -- the reference's loop (tum_rgbd_example.cpp:83-103) does the two in turn
+    // frame i is enqueued (lvt_amd_track_rgbd16_async: pageable buffers are the library's copy when the call returns), frame i + 1 is read and decoded
+    // while it tracks, then frame i's pose is collected -- the reference's loop (tum_rgbd_example.cpp:83-103) does the two in turn
     struct Frame {
-        Gray rgb;
-        std::vector<float> depth_m;
+        Gray rgb, depth;  // (depth.px16: the PNG's 16-bit plane as it is)
         bool ok = false;
     };
     auto load = [&](long i, Frame &f) {
-        Gray depth;
         std::string err;
         f.ok = i < frame_count && load_image(root_dir + "/" + dataset_name + "/" + rgb_titles[i], f.rgb, err) &&
-               load_image(root_dir + "/" + dataset_name + "/" + depth_titles[i], depth, err) && !depth.px16.empty() && depth.w == f.rgb.w && depth.h == f.rgb.h;
-        if (!f.ok) return;
-        f.depth_m.resize(depth.px16.size());
-        for (size_t k = 0; k < f.depth_m.size(); k++) f.depth_m[k] = (float)depth.px16[k] * depth_scale;
+               load_image(root_dir + "/" + dataset_name + "/" + depth_titles[i], f.depth, err) && !f.depth.px16.empty() && f.depth.w == f.rgb.w &&
+               f.depth.h == f.rgb.h;
     };
     Frame cur, nxt;
     load(0, cur);
@@ -96,7 +93,7 @@ int main(int argc, char **argv) {
             break;
         }
         const auto t0 = std::chrono::steady_clock::now();
-        const int queued = lvt_amd_track_rgbd_async(vo, cur.rgb.px.data(), cur.depth_m.data(), cur.rgb.h, cur.rgb.w);
+        const int queued = lvt_amd_track_rgbd16_async(vo, cur.rgb.px.data(), cur.depth.px16.data(), depth_scale, cur.rgb.h, cur.rgb.w);
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (queued != 0) break;  // (a frame of another size: the reference would throw inside OpenCV)
         load(i + 1, nxt);

@@ -2,7 +2,7 @@
  * lvt_amd_ext.h -- ADDITIVE entry points of the MI355X-native library (nothing here is required of an
  * existing lvt_c caller).  They expose (a) the reference's C++-only API surface over the C-ABI
  * (lvt_system::create with an in-memory lvt_parameters, reset, RGB-D track), (b) zero-copy tracking on
- * images already resident in HBM, (c) read-back of per-frame intermediate results for stage-by-stage
+ * images already resident in HBM -- stereo pairs and RGB-D frames (fp32 or 16-bit depth), one handle or a lock-step batch --, (c) read-back of per-frame intermediate results for stage-by-stage
  * parity tests, (d) the batched Hamming matcher micro-benchmark, (e) the EuRoC rectification pre-step and the odometry
  * accumulator either side of the path.
  *
@@ -118,6 +118,32 @@ LVT_API void lvt_amd_wait(lvt_handle h, double R[3][3], double t[3]);
 LVT_API int lvt_amd_wait_status(lvt_handle h, double R[3][3], double t[3]);
 /* the same with the pose as the tracker holds it (quaternion w x y z + position: what lvt_system::track returns) */
 LVT_API int lvt_amd_wait_pose(lvt_handle h, double q_wxyz[4], double p[3]);
+/* ---- RGB-D: planes already in HBM, 16-bit depth, lock-step batches ------------------------------------------------------------------
+ * The depth element format travels with the frame.  LVT_AMD_DEPTH_F32: metres, as lvt_amd_track_rgbd takes them.  LVT_AMD_DEPTH_U16: what depth cameras
+ * deliver (TUM's PNGs: uint16 at 1/5000 m); the tracker samples the 16-bit plane where it has key points -- depth = (float)raw * depth_scale, one rounded
+ * fp32 multiply, exactly what a caller converting the plane itself computes -- so a 16-bit frame tracks bit for bit like its fp32 conversion at half the
+ * bytes moved, and nobody converts the ~306 000 pixels no key point sits on.  Raw 0 ("no depth") is 0 m: below every near plane, filtered like any other
+ * out-of-range depth.  depth_scale is ignored for F32; for U16 it must be finite and > 0.
+ * All of these return 0 when the frame was enqueued (or tracked) and -1 when it was refused -- then NOTHING was enqueued, frames in flight are unaffected and
+ * lvt_amd_last_error says why (a batch: naming the sequence).  Refused: a stereo or pooled handle (pooled handles are stereo only), a NULL plane, a size that
+ * is not the sequence's own, an unknown format, a bad depth_scale, a misaligned plane.  (The other way round, the stereo device calls -- lvt_amd_track_device[_async],
+ * lvt_amd_batch_track_device_async[_mixed] -- refuse an RGB-D handle: they have no depth plane to hand over.) */
+enum { LVT_AMD_DEPTH_F32 = 0, LVT_AMD_DEPTH_U16 = 1 };
+/* one handle, planes resident in HBM.  Gray: 16-byte aligned pointer, pitch a multiple of 16.  Depth: pointer aligned to its element (4 / 2 bytes), pitch in
+ * BYTES, a multiple of the element size and >= n_cols elements.  The planes must stay valid and unchanged until the frame has been collected. */
+LVT_API int lvt_amd_track_rgbd_device_async(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes,
+                                            int depth_format, float depth_scale, int n_rows, int n_cols);
+LVT_API int lvt_amd_track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
+                                      float depth_scale, int n_rows, int n_cols, double R[3][3], double t[3]);
+/* one handle, HOST buffers (tightly packed, like lvt_amd_track_rgbd[_async]; page-locked ones are read in place), 16-bit depth */
+LVT_API int lvt_amd_track_rgbd16(lvt_handle h, const unsigned char *gray, const uint16_t *depth16, float depth_scale, int n_rows, int n_cols,
+                                 double R[3][3], double t[3]);
+LVT_API int lvt_amd_track_rgbd16_async(lvt_handle h, const unsigned char *gray, const uint16_t *depth16, float depth_scale, int n_rows, int n_cols);
+/* one step of a lock-step RGB-D batch -- lvt_amd_batch_create(p, 2, n) and lvt_amd_batch_create_mixed(p, 2, n) alike: arrays of B; d_gray[s] == NULL: sequence s
+ * sits this step out (exactly as in lvt_amd_batch_track_device_async_mixed); a step with every pointer NULL is refused.  One format and scale per call (they
+ * may change from step to step).  Results: lvt_amd_batch_wait / _get_counts, as for stereo batches. */
+LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *const *d_gray, const void *const *d_depth, const int *n_rows, const int *n_cols,
+                                                  const int *gray_pitch_bytes, const int *depth_pitch_bytes, int depth_format, float depth_scale);
 /* ---- lock-step batch of independent sequences on ONE GPU ----------------------------------------------
  * B sequences (e.g. several KITTI drives) advance frame by frame through a single launch chain (every kernel is
  * launched with gridDim.z = B); the latency-bound serial kernels of the path (pose refinement, greedy resolvers)
@@ -133,7 +159,7 @@ LVT_API void lvt_amd_batch_get_counts(lvt_handle h, int seq, int out[32]);
 /* ---- MIXED lock-step batch: every sequence with its own parameters ---------------------------------------
  * The reference gives every lvt_system its own lvt_parameters; KITTI 00 - 07 alone has three calibrations and three image sizes.
  * B sequences, sequence s with parameters p[s] (any mix of image size, intrinsics, detection grid, radii, thresholds, triangulation
- * policy).  Shared by the whole batch: the sensor type and the capacities (map / feature / cell limits).  NULL when any p[s] is one
+ * policy).  Shared by the whole batch: the sensor type (stereo, or RGB-D: frames then go through lvt_amd_batch_track_rgbd_device_async) and the capacities (map / feature / cell limits).  NULL when any p[s] is one
  * lvt_amd_create would refuse.  The uniform calls above keep their behaviour and their launches; a mixed batch takes its frames through
  * the _mixed call below (which a uniform batch accepts too). */
 LVT_API lvt_handle lvt_amd_batch_create_mixed(const lvt_amd_params *p /* [n_sequences] */, int sensor_type, int n_sequences);

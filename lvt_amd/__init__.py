@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "lvt_amd_batch_get_counts", "lvt_amd_create_on_device", "lvt_amd_get_device", "lvt_amd_wait_status", "lvt_amd_get_host_stats",
     "lvt_amd_track_async", "lvt_amd_track_rgbd_async", "lvt_amd_pnp_trace", "lvt_amd_create_pooled", "lvt_amd_wait_pose",
     "lvt_amd_batch_create_mixed", "lvt_amd_batch_track_device_async_mixed", "lvt_amd_batch_get_params", "lvt_amd_batch_mixed_tables",
+    "lvt_amd_track_rgbd_device", "lvt_amd_track_rgbd_device_async", "lvt_amd_track_rgbd16", "lvt_amd_track_rgbd16_async",
+    "lvt_amd_batch_track_rgbd_device_async",
 ]
 
 N_COUNTS = 32
@@ -44,6 +46,7 @@ COUNT_NAMES = ["n_left", "n_right", "map_size", "staged_size", "n_matches", "sec
 
 eState_NOT_INITIALIZED, eState_TRACKING, eState_LOST = 1, 2, 3
 eSensor_STEREO, eSensor_RGBD = 1, 2
+DEPTH_F32, DEPTH_U16 = 0, 1   # LVT_AMD_DEPTH_F32 (metres) / LVT_AMD_DEPTH_U16 (raw sensor units: metres = raw * depth_scale)
 
 _lib = None
 
@@ -145,6 +148,16 @@ def load_library():
     L.lvt_amd_batch_mixed_tables.restype = C.c_int
     L.lvt_amd_batch_mixed_tables.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     L.lvt_amd_batch_size.restype = C.c_int
+    # RGB-D on device planes / with 16-bit depth / in lock-step batches (a library built before they existed -- LVT_AMD_LIB, kernel A/B runs -- simply lacks them)
+    for name, argtypes in (
+            ("lvt_amd_track_rgbd_device_async", [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]),
+            ("lvt_amd_track_rgbd_device", [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]),
+            ("lvt_amd_track_rgbd16", [vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]),
+            ("lvt_amd_track_rgbd16_async", [vp, vp, vp, C.c_float, C.c_int, C.c_int]),
+            ("lvt_amd_batch_track_rgbd_device_async", [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_float])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -231,12 +244,18 @@ class LvtSystem:
                 "async_host_frames": int(a[4]), "pulls_carried_by_the_previous_frame": int(a[5]), "score_pieces": int(a[6]), "event_ordering": int(a[7])}
 
     # lvt_system::track(img1, img2)  -- lvt_system.cpp:157-207
-    def track(self, img1, img2):
+    def track(self, img1, img2, depth_scale=None):
+        """RGB-D: img2 is the depth image -- floats (metres), or a uint16 array of raw sensor units with depth_scale = metres per unit"""
         R = np.zeros((3, 3)); t = np.zeros(3)
         a = _u8(img1)
         if self._sensor == eSensor_STEREO:
             b = _u8(img2)
             load_library().lvt_track(self._h, _p(a), _p(b), a.shape[0], a.shape[1], _p(R), _p(t))
+        elif isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
+            if depth_scale is None:
+                raise ValueError("a uint16 depth image needs depth_scale (metres per raw unit)")
+            d = np.ascontiguousarray(img2)
+            load_library().lvt_amd_track_rgbd16(self._h, _p(a), _p(d), float(depth_scale), a.shape[0], a.shape[1], _p(R), _p(t))
         else:
             d = np.ascontiguousarray(img2, dtype=np.float32)
             load_library().lvt_amd_track_rgbd(self._h, _p(a), _p(d), a.shape[0], a.shape[1], _p(R), _p(t))
@@ -261,13 +280,32 @@ class LvtSystem:
     def track_device_async(self, d_left: int, d_right: int, rows: int, cols: int, pitch: int):
         load_library().lvt_amd_track_device_async(self._h, C.c_void_p(d_left), C.c_void_p(d_right), rows, cols, pitch)
 
-    def track_async(self, img1, img2) -> int:
+    # RGB-D planes already resident in HBM: gray u8 (16-byte aligned, pitch % 16 == 0) + depth f32 / u16 (pitch in bytes)
+    def track_rgbd_device(self, d_gray: int, d_depth: int, rows: int, cols: int, gray_pitch: int, depth_pitch: int, depth_format: int = DEPTH_F32,
+                          depth_scale: float = 1.0):
+        """(R, t), or None when the frame was refused (last_error() says why; nothing was enqueued)"""
+        R = np.zeros((3, 3)); t = np.zeros(3)
+        rc = load_library().lvt_amd_track_rgbd_device(self._h, C.c_void_p(d_gray), gray_pitch, C.c_void_p(d_depth), depth_pitch, depth_format,
+                                                      float(depth_scale), rows, cols, _p(R), _p(t))
+        return (R, t) if rc == 0 else None
+
+    def track_rgbd_device_async(self, d_gray: int, d_depth: int, rows: int, cols: int, gray_pitch: int, depth_pitch: int, depth_format: int = DEPTH_F32,
+                                depth_scale: float = 1.0) -> int:
+        return load_library().lvt_amd_track_rgbd_device_async(self._h, C.c_void_p(d_gray), gray_pitch, C.c_void_p(d_depth), depth_pitch, depth_format,
+                                                              float(depth_scale), rows, cols)
+
+    def track_async(self, img1, img2, depth_scale=None) -> int:
         """lvt_amd_track_async / lvt_amd_track_rgbd_async: HOST images, the call returns once the frame is enqueued (0) or rejected (-1).
         The arrays are used as they are (no copy here): a page-locked one must stay alive and unchanged until the frame is collected."""
         a = img1 if (isinstance(img1, np.ndarray) and img1.dtype == np.uint8 and img1.flags.c_contiguous) else _u8(img1)
         if self._sensor == eSensor_STEREO:
             b = img2 if (isinstance(img2, np.ndarray) and img2.dtype == np.uint8 and img2.flags.c_contiguous) else _u8(img2)
             return load_library().lvt_amd_track_async(self._h, _p(a), _p(b), a.shape[0], a.shape[1])
+        if isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
+            if depth_scale is None:
+                raise ValueError("a uint16 depth image needs depth_scale (metres per raw unit)")
+            d = img2 if img2.flags.c_contiguous else np.ascontiguousarray(img2)
+            return load_library().lvt_amd_track_rgbd16_async(self._h, _p(a), _p(d), float(depth_scale), a.shape[0], a.shape[1])
         d = img2 if (isinstance(img2, np.ndarray) and img2.dtype == np.float32 and img2.flags.c_contiguous) else np.ascontiguousarray(img2, dtype=np.float32)
         return load_library().lvt_amd_track_rgbd_async(self._h, _p(a), _p(d), a.shape[0], a.shape[1])
 
@@ -422,6 +460,20 @@ class LvtBatch:
         b = vps(*[None if x is None else int(x) for x in d_right])
         return load_library().lvt_amd_batch_track_device_async_mixed(self._h, a, b, ints(*[int(x) for x in rows]), ints(*[int(x) for x in cols]),
                                                                     ints(*[int(x) for x in pitch]))
+
+    def track_rgbd_device_async(self, d_gray, d_depth, rows, cols, gray_pitch, depth_pitch, depth_format: int = DEPTH_F32, depth_scale: float = 1.0) -> int:
+        """one lock-step step of an RGB-D batch (uniform or mixed): d_gray / d_depth are sequences of length B of device pointers, None for a sequence
+        without a frame in this step; rows, cols and the pitches (bytes) are scalars or sequences of length B.  One depth format and scale per call.
+        0: enqueued; -1: refused, nothing enqueued (last_error() says why)"""
+        vps = C.c_void_p * self.B
+        ints = C.c_int * self.B
+
+        def per_seq(v):
+            return ints(*([int(v)] * self.B if np.isscalar(v) else [int(x) for x in v]))
+        a = vps(*[None if x is None else int(x) for x in d_gray])
+        b = vps(*[None if x is None else int(x) for x in d_depth])
+        return load_library().lvt_amd_batch_track_rgbd_device_async(self._h, a, b, per_seq(rows), per_seq(cols), per_seq(gray_pitch), per_seq(depth_pitch),
+                                                                   int(depth_format), float(depth_scale))
 
     def params(self, seq: int) -> LvtParameters:
         pod = ParamsPOD()

@@ -84,14 +84,19 @@ __device__ __forceinline__ uint32_t key_pos(uint32_t k) { return k >> 8; }
 
 // per-frame, per-sequence inputs (pinned host memory read by k_feat_begin for batches; a kernel argument of k_score for
 // a single sequence, which then needs no separate "begin" launch)
+// An all-zero FrameArgs is a frame of today's kind: DEPTH_F32 is 0, so every producer that clears the record or never hands over a depth plane (the stereo
+// calls, the pool's seats) needs no word about the depth format.  The two depth fields sit where the record had padding: it stays at 72 bytes.
 struct FrameArgs {
     const uint8_t *img[2];
-    const float *depth;
-    int img_pitch, depth_pitch;
+    const float *depth;      // RGB-D: the depth plane, float (DEPTH_F32) or uint16_t (DEPTH_U16) elements
+    int img_pitch, depth_pitch;  // bytes / ELEMENTS of the depth format
     int ext_corners, n_ext[2];
+    int depth_format;        // DEPTH_F32 (metres) / DEPTH_U16 (raw sensor units: metres = raw * depth_scale)
     const float *ext_xy[2];  // external corner lists of THIS frame (a pooled handle's: every seat has its own); nullptr: the context's lists (FrameBuf::ext_xy as created)
     int absent;  // (pooled handles, lvt_host.hip) this sequence has no frame in this lock-step step: every kernel of the step leaves it exactly as it is
+    float depth_scale;       // DEPTH_U16 only
 };
+static_assert(sizeof(FrameArgs) == 72, "FrameArgs travels by value (k_score) and 32 at a time (k_feat_begin_pack): keep it at 72 bytes");
 
 // publish this frame's inputs, clear the feature stage's control block
 __device__ __forceinline__ void feat_begin(Seq &S, const FrameArgs &f, int par) {
@@ -101,6 +106,8 @@ __device__ __forceinline__ void feat_begin(Seq &S, const FrameArgs &f, int par) 
     FB.depth_img = f.depth;
     FB.img_pitch = f.img_pitch;
     FB.depth_pitch = f.depth_pitch;
+    FB.depth_format = f.depth_format;
+    FB.depth_scale = f.depth_scale;
     FeatCtl &c = *FB.fc;
     c.absent = f.absent;
     if (c.poison) return;  // (k_gate_buf: the buffer still belongs to an older frame)
@@ -1898,7 +1905,10 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
             oy = y;
             keep = brief_border_keep(x, y, H, W);
             if (keep && rgbd) {  // handler.cpp:255-265 (depth at the distorted pixel), :268-294
-                dep = FBd.depth_img[(size_t)((int)y) * FBd.depth_pitch + (int)x];
+                const size_t di = (size_t)((int)y) * FBd.depth_pitch + (int)x;
+                // DEPTH_U16: one 16-bit load, an exact conversion and ONE rounded fp32 multiply -- what a caller's own `(float)raw * scale` gives, so a
+                // 16-bit frame tracks exactly like its fp32 conversion; raw 0 ("no depth") is 0.0f and falls to the near-plane test below
+                dep = (FBd.depth_format == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(FBd.depth_img)[di], FBd.depth_scale) : FBd.depth_img[di];
                 keep = (dep >= S.prm.near_plane && dep <= S.prm.far_plane);
                 if (keep && S.prm.undistort) {
                     undistort_point(S.prm, x, y, x, y);

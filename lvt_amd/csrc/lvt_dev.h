@@ -139,6 +139,8 @@ struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one
     seq_t feat_seq;  // sequence number of the frame whose features this buffer holds, published by k_feat_done (polled by k_gate)
 };
 
+enum { DEPTH_F32 = 0, DEPTH_U16 = 1 };  // == LVT_AMD_DEPTH_F32 / _U16 (lvt_amd_ext.h)
+
 struct Feat {  // one image's lvt_image_features_struct (lvt_image_features_struct.h:62-80), SoA
     float *x, *y, *resp;   // keypoint coords as the struct stores them (undistorted for RGB-D)
     float *bx, *by;        // coords BRIEF samples at (== x,y except RGB-D with distortion)
@@ -159,8 +161,12 @@ struct MapSoA {            // lvt_local_map.h:64-72 as SoA; two copies for stabl
 // feature extraction of frame t+1 overlaps the tracking chain of frame t on a second HIP stream
 struct FrameBuf {
     const uint8_t *img[2];
-    const float *depth_img;     // RGB-D
+    const float *depth_img;     // RGB-D: float or uint16_t elements (depth_format)
     int img_pitch, depth_pitch; // bytes / elements
+    // element format of depth_img (DEPTH_F32 / DEPTH_U16) and metres per raw unit of a DEPTH_U16 plane.  Per-frame mutable members like depth_img: published by
+    // feat_begin and read ONLY where depth_img is read -- k_gather, on the feature stream, behind the writer (through seq_const: see SeqArg below)
+    int depth_format;
+    float depth_scale;
     uint8_t *score[2];          // OAST-9/16 score map (0 = below the lowered threshold / dead band)
     uint16_t *boxsum[2];        // 9x9 box sums
     uint32_t *seg_keys[2];      // [H][tiles_x][64] raw-corner keys (score >= agast_th) of one 64-px tile row, x-ascending

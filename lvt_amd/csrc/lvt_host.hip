@@ -69,6 +69,7 @@ constexpr int FEAT_PACK = 32;
 struct FrameArgsPack {
     FrameArgs a[FEAT_PACK];
 };
+static_assert(sizeof(Seq *) + sizeof(FrameArgsPack) + sizeof(int) + 2 * sizeof(seq_t) < 4096, "k_feat_begin_pack's arguments must stay under 4096 bytes");
 // ... and with k_gate_buf's wait in front (want != 0: the tracking chain of the frame that used this buffer last must have released it): one launch at the head of a
 // batch's feature stage instead of two
 __global__ void k_feat_begin_pack(Seq *seqs, FrameArgsPack pk, int par, seq_t want) {
@@ -87,19 +88,33 @@ __global__ void k_feat_begin_pack(Seq *seqs, FrameArgsPack pk, int par, seq_t wa
 __global__ __launch_bounds__(256) void k_stage_in(const uint8_t *src0, const uint8_t *src1, uint8_t *dst0, uint8_t *dst1, int W, int H, int pitch) {
     stage_in_body(blockIdx.y ? src1 : src0, blockIdx.y ? dst1 : dst0, W, H, pitch, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
-// the (unpitched) fp32 depth image: 16-byte loads between the first 16-byte boundary of the source and its last whole vector, single
-// floats on either side; the destination is written float by float (it is 16-byte aligned, the source need not be)
-__global__ __launch_bounds__(256) void k_stage_copy(const float *src, float *dst, size_t n) {
-    const size_t head = min((size_t)(((16 - ((uintptr_t)src & 15)) & 15) / 4), n);
-    const size_t nv = (n - head) / 4, tail0 = head + nv * 4;
+// the (unpitched) depth image, T = float (fp32 metres) or uint16_t (raw sensor units; the plane stays 16-bit in HBM): 16-byte loads between the first 16-byte
+// boundary of the source and its last whole vector, single elements on either side -- no load reaches outside [src, src + n); the destination is written
+// element by element (it is 16-byte aligned, the source need only be aligned to its element: head < 16 / sizeof(T), and n - tail0 < 16 / sizeof(T), elements)
+template <typename T>
+__global__ __launch_bounds__(256) void k_stage_copy(const T *src, T *dst, size_t n) {
+    constexpr size_t PER = 16 / sizeof(T);
+    union Vec {
+        uint4 q;
+        T e[PER];
+    };
+    const size_t head = min((size_t)(((16 - ((uintptr_t)src & 15)) & 15) / sizeof(T)), n);
+    const size_t nv = (n - head) / PER, tail0 = head + nv * PER;
     const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     for (size_t v = t0; v < nv; v += stride) {
-        const float4 q = *reinterpret_cast<const float4 *>(src + head + v * 4);
-        float *d = dst + head + v * 4;
-        d[0] = q.x, d[1] = q.y, d[2] = q.z, d[3] = q.w;
+        Vec u;
+        u.q = *reinterpret_cast<const uint4 *>(src + head + v * PER);
+        T *d = dst + head + v * PER;
+#pragma unroll
+        for (size_t k = 0; k < PER; k++) d[k] = u.e[k];
     }
     if (t0 < head) dst[t0] = src[t0];
     if (t0 < n - tail0) dst[tail0 + t0] = src[tail0 + t0];
+}
+// pull a tightly packed depth plane of n elements (format fmt) into d_dst, which is sized for fp32
+static void launch_stage_copy(hipStream_t st, const uint8_t *src, float *d_dst, size_t n, int fmt) {
+    if (fmt == DEPTH_U16) hipLaunchKernelGGL(k_stage_copy<uint16_t>, dim3(256), dim3(256), 0, st, reinterpret_cast<const uint16_t *>(src), reinterpret_cast<uint16_t *>(d_dst), n);
+    else hipLaunchKernelGGL(k_stage_copy<float>, dim3(256), dim3(256), 0, st, reinterpret_cast<const float *>(src), d_dst, n);
 }
 
 // handles alive in this process: a handle whose k_match_map polls for its early stream parks 32 workgroups (50 KB of LDS each)
@@ -634,6 +649,7 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
         }
         if (const char *e = std::getenv("LVT_AMD_MATCH_BLOCKS_BATCH")) c->match_blocks_batch = std::max(1, std::min(256, std::atoi(e)));
         HIPCHK(c, hipHostMalloc((void **)&c->h_fargs, sizeof(FrameArgs) * B * RING, hipHostMallocDefault));
+        std::memset(c->h_fargs, 0, sizeof(FrameArgs) * B * RING);  // (all-zero: fp32 depth, no external corners, present)
         c->h_seqs.resize(B);
         c->d_ctl.resize(B);
         for (int s = 0; s < B; s++) {
@@ -1446,6 +1462,10 @@ LVT_API void lvt_amd_track_device_async(lvt_handle h, const void *d_left, const 
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
+        if (c->sensor != 1) {  // (an RGB-D frame needs a depth plane: lvt_amd_track_rgbd_device[_async])
+            c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
+            return;
+        }
         if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
             c->set_error("lvt_amd_track_device: image size / pitch mismatch");
             return;
@@ -1458,6 +1478,7 @@ LVT_API void lvt_amd_track_device_async(lvt_handle h, const void *d_left, const 
         f.depth = nullptr;
         f.img_pitch = pitch_bytes;
         f.depth_pitch = 0;
+        f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
         f.ext_corners = 0;
         f.absent = 0;
         f.n_ext[0] = f.n_ext[1] = 0;
@@ -1529,6 +1550,10 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             c->set_error("lvt_amd_batch_track_device_async_mixed: NULL argument");
             return -1;
         }
+        if (c->sensor != 1) {
+            c->set_error("lvt_amd_batch_track_device_async_mixed: a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)");
+            return -1;
+        }
         int present = 0;
         for (int s = 0; s < c->B; s++) {
             if (!d_left[s]) continue;
@@ -1572,6 +1597,10 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
+        if (c->sensor != 1) {
+            c->set_error("lvt_amd_batch_track_device: a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)");
+            return;
+        }
         if (c->mixed) {
             c->set_error("lvt_amd_batch_track_device: a mixed batch takes its frames through lvt_amd_batch_track_device_async_mixed");
             return;
@@ -1588,6 +1617,7 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
             f.depth = nullptr;
             f.img_pitch = pitch_bytes;
             f.depth_pitch = 0;
+            f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
             f.ext_corners = 0;
         f.absent = 0;
             f.n_ext[0] = f.n_ext[1] = 0;
@@ -1704,6 +1734,10 @@ LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *
     }
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
+    if (c->sensor != 1) {
+        c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
+        return;
+    }
     if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
         c->set_error("lvt_amd_track_device: image size / pitch mismatch");
         return;  // outputs untouched, like the reference on an exception
@@ -1718,8 +1752,10 @@ LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *
     }
 }
 
+// (dfmt / dscale: element format of an RGB-D frame's depth plane `second` and metres per raw unit of a 16-bit one)
 static void upload_and_track(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols, int ext,
-                             const float *cl, int ncl, const float *cr, int ncr, double R[3][3], double t[3]) {
+                             const float *cl, int ncl, const float *cr, int ncr, double R[3][3], double t[3], int dfmt = DEPTH_F32, float dscale = 0.f) {
+    const size_t desz = (dfmt == DEPTH_U16) ? sizeof(uint16_t) : sizeof(float);
     if (!size_ok(c, n_rows, n_cols)) {
         c->set_error("lvt_track: image size differs from the configured img_width/img_height");
         return;
@@ -1748,7 +1784,7 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
         (void)hipGetLastError();  // (an ordinary malloc'ed pointer is "invalid value" to the query: not an error of this call)
         return nullptr;
     };
-    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? sizeof(float) : 1);
+    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? desz : 1);
     c->planes_in_place += (s0 != nullptr) + (s1 != nullptr);
     c->planes_staged += (s0 == nullptr) + (s1 == nullptr);
     // The pulls are launched BEFORE the previous frame is collected: this frame's image planes (parity `par`) and staging buffer were last used NPAR
@@ -1773,21 +1809,23 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     f.img_pitch = c->pitch;
     f.depth = nullptr;
     f.depth_pitch = 0;
+    f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
     if (rgbd) {
         // The depth plane (1.2 MB: ~60 us of CPU copy into the staging buffer when the caller's buffer is pageable, ~45 us of PCIe pull)
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
         // host while the GPU runs them, the pull on the early stream (idle until this frame's features exist) beside them -- and
-        // the feature stream waits for the pull in front of k_gather.
+        // the feature stream waits for the pull in front of k_gather.  (A 16-bit plane: half those bytes, both ways; it stays 16-bit in d_depth.)
         f.depth = c->d_depth[par];
         f.depth_pitch = n_cols;
-        c->before_gather = [c, s1, second, nbytes, par, sf]() {
+        f.depth_format = dfmt, f.depth_scale = dscale;
+        c->before_gather = [c, s1, second, nbytes, par, sf, dfmt, desz]() {
             const uint8_t *src = s1;
             if (!src) {
-                std::memcpy(c->h_stage[par] + c->stage_img, second, sizeof(float) * nbytes);
+                std::memcpy(c->h_stage[par] + c->stage_img, second, desz * nbytes);
                 src = c->h_stage_dev[par] + c->stage_img;
             }
             hipStream_t sd = c->events_only ? sf : c->stream_e;
-            hipLaunchKernelGGL(k_stage_copy, dim3(256), dim3(256), 0, sd, reinterpret_cast<const float *>(src), reinterpret_cast<float *>(c->d_depth[par]), nbytes);
+            launch_stage_copy(sd, src, c->d_depth[par], nbytes, dfmt);
             if (sd != sf) {
                 (void)hipEventRecord(c->ev_depth, sd);
                 c->depth_wait = true;
@@ -1817,7 +1855,8 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
 // lvt_amd_wait* finds the device about to run dry / any other entry point needs the launch chain.  A frame nobody pulled for pulls its own images at the
 // head of its feature stage (k_stage_in), as every RGB-D frame does.
 // Returns 0 when the frame was enqueued, -1 when it was rejected (nothing enqueued; lvt_amd_last_error says why).
-static int upload_async(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols) {
+static int upload_async(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols, int dfmt = DEPTH_F32, float dscale = 0.f) {
+    const size_t desz = (dfmt == DEPTH_U16) ? sizeof(uint16_t) : sizeof(float);
     if (c->B != 1 || (rgbd ? c->sensor != 2 : c->sensor != 1)) {
         c->set_error("lvt_amd_track_async: wrong sensor type for this entry point (or a batch handle)");
         return -1;
@@ -1845,7 +1884,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
         (void)hipGetLastError();
         return nullptr;
     };
-    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? sizeof(float) : 1);
+    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? desz : 1);
     c->planes_in_place += (s0 != nullptr) + (s1 != nullptr);
     c->planes_staged += (s0 == nullptr) + (s1 == nullptr);
     const size_t img_b = (nbytes + 15) & ~(size_t)15, second_b = rgbd ? ((sizeof(float) * nbytes + 15) & ~(size_t)15) : img_b;
@@ -1887,10 +1926,10 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
         }
         hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, n_cols, n_rows, c->pitch);
         if (!s1) {
-            std::memcpy(c->h_stage_ring[slot] + img_b, second, sizeof(float) * nbytes);
+            std::memcpy(c->h_stage_ring[slot] + img_b, second, desz * nbytes);
             s1 = c->h_stage_ring_dev[slot] + img_b;
         }
-        hipLaunchKernelGGL(k_stage_copy, dim3(256), dim3(256), 0, sp, reinterpret_cast<const float *>(s1), c->d_depth_ring[slot], nbytes);
+        launch_stage_copy(sp, s1, c->d_depth_ring[slot], nbytes, dfmt);
     }
     FrameArgs &f = c->h_fargs[(size_t)slot * c->B];
     f.img[0] = d0;
@@ -1898,6 +1937,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     f.img_pitch = c->pitch;
     f.depth = rgbd ? c->d_depth_ring[slot] : nullptr;
     f.depth_pitch = rgbd ? n_cols : 0;
+    f.depth_format = rgbd ? dfmt : DEPTH_F32, f.depth_scale = rgbd ? dscale : 0.f;
     f.ext_corners = 0;
     f.absent = 0;
     f.n_ext[0] = f.n_ext[1] = 0;
@@ -1969,6 +2009,196 @@ LVT_API void lvt_amd_track_rgbd(lvt_handle h, const unsigned char *gray, const f
         upload_and_track(c, gray, depth, true, n_rows, n_cols, 0, nullptr, 0, nullptr, 0, R, t);
     } catch (...) {
     }
+}
+
+// ---- RGB-D beyond the two host fp32 calls: planes already in HBM, 16-bit depth, lock-step batches -------------------------------------------
+// Every call checks everything before it enqueues anything: 0 = enqueued / tracked, -1 = refused, NOTHING enqueued, the reason in lvt_amd_last_error.
+static int rgbd_refuse(lvt_handle h, const char *who, const std::string &why) {
+    const std::string msg = std::string(who) + ": " + why + " (nothing was enqueued)";
+    if (is_slot(h)) {
+        PoolSlot *S = static_cast<PoolSlot *>(h);
+        std::lock_guard<std::mutex> g(S->pool->mu);
+        S->err = msg;
+    } else if (is_ctx(h))
+        static_cast<Context *>(h)->set_error(msg);
+    return -1;
+}
+// the handle must be a solo (B == 1) or batch (B > 1 or mixed) RGB-D context
+static Context *rgbd_context(lvt_handle h, const char *who, bool batch) {
+    if (is_slot(h)) {
+        rgbd_refuse(h, who, "a pooled handle (pooled handles are stereo only)");
+        return nullptr;
+    }
+    if (!is_ctx(h)) return nullptr;
+    Context *c = static_cast<Context *>(h);
+    if (c->sensor != 2) {
+        rgbd_refuse(h, who, "an RGB-D entry point on a stereo handle");
+        return nullptr;
+    }
+    if (!batch && (c->B != 1 || c->mixed)) {
+        rgbd_refuse(h, who, "a batch handle takes its frames through lvt_amd_batch_track_rgbd_device_async");
+        return nullptr;
+    }
+    return c;
+}
+static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale) {
+    if (fmt != DEPTH_F32 && fmt != DEPTH_U16) {
+        rgbd_refuse(h, who, "unknown depth format " + std::to_string(fmt));
+        return false;
+    }
+    if (fmt == DEPTH_U16 && !(std::isfinite(scale) && scale > 0.f)) {
+        rgbd_refuse(h, who, "depth_scale of a 16-bit depth plane must be finite and > 0");
+        return false;
+    }
+    return true;
+}
+// one sequence's device planes against its parameters; "" when they pass
+static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols) {
+    const int esz = (fmt == DEPTH_U16) ? 2 : 4;
+    char buf[240];
+    if (!d_gray || !d_depth) return "NULL gray or depth plane";
+    if (n_rows != q.H || n_cols != q.W) {
+        std::snprintf(buf, sizeof(buf), "image size %d x %d, expected %d x %d", n_cols, n_rows, q.W, q.H);
+        return buf;
+    }
+    if (((uintptr_t)d_gray & 15) || (gray_pitch & 15) || gray_pitch < n_cols) {
+        std::snprintf(buf, sizeof(buf), "gray plane: pointer and pitch (%d) must be multiples of 16, pitch >= %d", gray_pitch, n_cols);
+        return buf;
+    }
+    if (((uintptr_t)d_depth % esz) || depth_pitch <= 0 || (depth_pitch % esz) || (long long)depth_pitch < (long long)n_cols * esz) {
+        std::snprintf(buf, sizeof(buf), "depth plane: pointer and pitch (%d bytes) must be multiples of the %d-byte element, pitch >= %d", depth_pitch, esz, n_cols * esz);
+        return buf;
+    }
+    return "";
+}
+static void rgbd_fill(FrameArgs &f, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, float scale) {
+    f = FrameArgs{};
+    f.img[0] = f.img[1] = static_cast<const uint8_t *>(d_gray);  // (eye 1 of an RGB-D sequence: every kernel stands down for it)
+    f.img_pitch = gray_pitch;
+    f.depth = static_cast<const float *>(d_depth);
+    f.depth_pitch = depth_pitch / ((fmt == DEPTH_U16) ? 2 : 4);  // elements inside the kernels
+    f.depth_format = fmt;
+    f.depth_scale = (fmt == DEPTH_U16) ? scale : 0.f;
+}
+
+LVT_API int lvt_amd_track_rgbd_device_async(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
+                                            float depth_scale, int n_rows, int n_cols) {
+    static const char *who = "lvt_amd_track_rgbd_device";
+    h = resolve_handle(h);
+    Context *c = rgbd_context(h, who, false);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
+        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols);
+        if (!why.empty()) return rgbd_refuse(h, who, why);
+        if (c->early_pending) drain(c);
+        make_room(c);
+        rgbd_fill(c->h_fargs[(size_t)(c->enq % RING) * c->B], d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale);
+        enqueue_frame(c);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
+                                      float depth_scale, int n_rows, int n_cols, double R[3][3], double t[3]) {
+    static const char *who = "lvt_amd_track_rgbd_device";
+    h = resolve_handle(h);
+    Context *c = rgbd_context(h, who, false);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
+        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols);
+        if (!why.empty()) return rgbd_refuse(h, who, why);
+        drain(c);
+        rgbd_fill(c->h_fargs[(size_t)(c->enq % RING) * c->B], d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale);
+        c->sync_call = true;  // collected right away: k_triangulate delivers the record itself
+        enqueue_frame(c);
+        c->sync_call = false;
+        if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+
+// HOST buffers with 16-bit depth (what the sensor delivers: TUM's PNGs are uint16 at 1/5000 m), tightly packed like lvt_amd_track_rgbd's: the staging copy
+// and the PCIe pull keep their place behind the detection kernels, at half the bytes
+static Context *rgbd16_context(lvt_handle h, const char *who, const void *gray, const void *depth16, float depth_scale, int n_rows, int n_cols) {
+    Context *c = rgbd_context(h, who, false);
+    if (!c) return nullptr;
+    if (!depth_format_ok(h, who, DEPTH_U16, depth_scale)) return nullptr;
+    if (!gray || !depth16 || ((uintptr_t)depth16 & 1)) {
+        rgbd_refuse(h, who, "NULL buffer, or a depth buffer that is not 2-byte aligned");
+        return nullptr;
+    }
+    if (!size_ok(c, n_rows, n_cols)) {
+        rgbd_refuse(h, who, "image size differs from the configured img_width/img_height");
+        return nullptr;
+    }
+    return c;
+}
+LVT_API int lvt_amd_track_rgbd16(lvt_handle h, const unsigned char *gray, const uint16_t *depth16, float depth_scale, int n_rows, int n_cols, double R[3][3],
+                                 double t[3]) {
+    h = resolve_handle(h);
+    Context *c = rgbd16_context(h, "lvt_amd_track_rgbd16", gray, depth16, depth_scale, n_rows, n_cols);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        upload_and_track(c, gray, depth16, true, n_rows, n_cols, 0, nullptr, 0, nullptr, 0, R, t, DEPTH_U16, depth_scale);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_track_rgbd16_async(lvt_handle h, const unsigned char *gray, const uint16_t *depth16, float depth_scale, int n_rows, int n_cols) {
+    h = resolve_handle(h);
+    Context *c = rgbd16_context(h, "lvt_amd_track_rgbd16_async", gray, depth16, depth_scale, n_rows, n_cols);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        return upload_async(c, gray, depth16, true, n_rows, n_cols, DEPTH_U16, depth_scale);
+    } catch (...) {
+    }
+    return -1;
+}
+
+// one lock-step step of an RGB-D batch, uniform or mixed: arrays of B; d_gray[s] == NULL: sequence s sits this step out (FrameArgs::absent)
+LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *const *d_gray, const void *const *d_depth, const int *n_rows, const int *n_cols,
+                                                  const int *gray_pitch_bytes, const int *depth_pitch_bytes, int depth_format, float depth_scale) {
+    static const char *who = "lvt_amd_batch_track_rgbd_device_async";
+    h = resolve_handle(h);
+    Context *c = rgbd_context(h, who, true);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!d_gray || !d_depth || !n_rows || !n_cols || !gray_pitch_bytes || !depth_pitch_bytes) return rgbd_refuse(h, who, "NULL argument");
+        if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
+        int present = 0;
+        for (int s = 0; s < c->B; s++) {
+            if (!d_gray[s]) continue;
+            present++;
+            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s]);
+            if (!why.empty()) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + why);
+        }
+        if (!present) return rgbd_refuse(h, who, "no sequence has a frame in this step");
+        make_room(c);
+        for (int s = 0; s < c->B; s++) {
+            FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B + s];
+            if (!d_gray[s]) {
+                f = FrameArgs{};
+                f.absent = 1;
+                continue;
+            }
+            rgbd_fill(f, d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, depth_scale);
+        }
+        enqueue_frame(c);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
 }
 
 LVT_API void lvt_track_with_external_corners(lvt_handle h, unsigned char *left, unsigned char *right, int n_rows, int n_cols,
