@@ -143,8 +143,8 @@ def diff_frame(hip, orc):
     return msgs
 
 
-def run_sequence(world, prm, sensor, frame_ids, hip=None, orc=None):
-    """track the frames through both systems; returns list of (frame, msgs, e_t, e_R)"""
+def run_sequence(world, prm, sensor, frame_ids, hip=None, orc=None, on_frame=None):
+    """track the frames through both systems; returns list of (frame, msgs, e_t, e_R).  on_frame(i, hip, orc) is called behind every frame's diff."""
     from oracle import pyoracle as O
     orc = orc or O.Oracle(prm, sensor)
     hip = hip or lvt_amd.LvtSystem.create(prm, sensor)
@@ -163,6 +163,8 @@ def run_sequence(world, prm, sensor, frame_ids, hip=None, orc=None):
         if e_t > POSE_TOL or e_R > POSE_TOL:
             msgs.append(f"pose e_t={e_t:.3e} e_R={e_R:.3e}")
         out.append((i, msgs, e_t, e_R))
+        if on_frame:
+            on_frame(i, hip, orc)
     return out, hip, orc
 
 

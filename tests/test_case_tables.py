@@ -1,0 +1,129 @@
+"""CPU tier: the case tables of the k_pnp / k_triangulate edge tests (case_tables.py) cannot rot.  With the oracle alone: the inputs still take the
+branches the GPU tests rely on -- so a GPU test that passes has compared what its docstring says it compares."""
+import numpy as np
+import pytest
+
+import lvt_amd
+from case_tables import (DENSE_MIN_UNSTAGED_FRAMES, KITTI_DENSE_UNSTAGED, PNP_EDGE_COUNTS, PNP_HARD, PNP_HARD_UNSTAGED, PNP_INTRINSICS, PNP_STAGE_MAX,
+                         STAIRCASE, pnp_edge_case, pnp_hard_case, pnp_prior_cases, staircase, staircase_band_counts, staircase_expected, trace_noise)
+
+
+def test_edge_count_cases_take_no_borderline_decision(oracle_lib):
+    """29 edge counts x 3 intrinsics: no gate decision of the oracle within 1e-8 of the threshold (the nearest stays 1.4e-2 away), 10 solve calls
+    for every n >= 3, and the noise-level endings of n = 1, 2 where the GPU test expects them"""
+    assert len(PNP_EDGE_COUNTS) * len(PNP_INTRINSICS) == 87
+    assert {0, 1, 2, 64, 256, 768, PNP_STAGE_MAX, PNP_STAGE_MAX + 1, 4096} <= set(PNP_EDGE_COUNTS)
+    for name in PNP_INTRINSICS:
+        for n in PNP_EDGE_COUNTS:
+            prm, X, uv, q0, p0 = pnp_edge_case(name, n)
+            q, p, marks, tr = oracle_lib.pnp(prm, q0, p0, X, uv)
+            o = oracle_lib.pnp
+            assert o.last_borderline == 0, (name, n)
+            if n == 0:
+                assert o.last_solve_calls == 0 and len(tr) == 0 and np.array_equal(q, [1, 0, 0, 0]) and np.array_equal(p, [0, 0, 0])
+                continue
+            assert o.last_min_margin >= 1.4e-2, (name, n, o.last_min_margin)
+            if n >= 3:
+                assert o.last_solve_calls == 10 and o.last_terminates == 0, (name, n, o.last_solve_calls)
+                assert trace_noise(tr) >= 3, (name, n)
+            if n >= 9:
+                assert 0 < marks.sum() < n, (name, n)           # the gates demote the planted outliers and keep the rest
+    prm = lvt_amd.tum_params()
+    assert prm.fx != prm.fy
+    # n = 1: 5 trials, 2 rejected, both passes Terminate, the first noise-level trial is the fourth
+    prm, X, uv, q0, p0 = pnp_edge_case("kitti", 1)
+    _, _, _, tr = oracle_lib.pnp(prm, q0, p0, X, uv)
+    assert (oracle_lib.pnp.last_trials, oracle_lib.pnp.last_rejections, oracle_lib.pnp.last_terminates, trace_noise(tr)) == (5, 2, 2, 3)
+
+
+def test_prior_cases_are_one_solve(oracle_lib):
+    """q, -q, 3 q and the unnormalised quaternion with w < 0: one pose, the same marks and counters on the oracle; a tenth of the points behind the camera"""
+    prm = lvt_amd.kitti_params()
+    labels = []
+    for label, X, uv, priors, p0 in pnp_prior_cases(prm):
+        labels.append((label, len(X)))
+        ref = None
+        for q0 in priors:
+            q, p, marks, tr = oracle_lib.pnp(prm, q0, p0, X, uv)
+            o = oracle_lib.pnp
+            got = (o.last_solve_calls, o.last_trials, o.last_rejections, o.last_terminates, o.last_borderline)
+            assert o.last_borderline == 0 and o.last_min_margin > 1e-2
+            if ref is None:
+                ref = (q, p, marks, got)
+            assert np.abs(q - ref[0]).max() < 1e-13 and np.abs(p - ref[1]).max() < 1e-13 and np.array_equal(marks, ref[2]) and got == ref[3], label
+        if label.startswith("behind"):
+            assert len(priors) == 4 and priors[3][0] < 0 and abs(np.linalg.norm(priors[2]) - 3) < 1e-12 and (X[:, 2] < 0).sum() >= len(X) // 20
+        else:
+            e2 = (oracle_lib.pnp.last_err ** 2).sum(axis=1)     # outliers over five decades
+            assert e2.max() > 1e10 and sum(((e2 > 10.0 ** (2 * k)) & (e2 < 10.0 ** (2 * k + 2))).any() for k in range(1, 5)) == 4
+    assert labels == [("behind_40", 40), ("behind_300", 300), ("behind_1700", 1700), ("graded_outliers", 600)]
+
+
+def _tally(oracle_lib, table):
+    prm = lvt_amd.kitti_params()
+    rows = []
+    for case in table:
+        X, uv, q0, p0 = pnp_hard_case(prm, *case)
+        _, _, _, tr = oracle_lib.pnp(prm, q0, p0, X, uv)
+        o = oracle_lib.pnp
+        rows.append(dict(case=case, full=trace_noise(tr) == len(tr), rej=o.last_rejections, term=o.last_terminates, nan=bool(np.isnan(tr).any()),
+                         border=o.last_borderline))
+    return rows
+
+
+def test_hard_rows_take_their_branches(oracle_lib):
+    rows = _tally(oracle_lib, PNP_HARD_UNSTAGED)
+    assert all(r["case"][1] > PNP_STAGE_MAX and r["border"] == 0 for r in rows)
+    assert {r["case"][1] for r in rows} == {1600, 2500, 4096}
+    # the closing condition of test_pnp_hard_branches_above_the_staging_limit
+    assert sum(r["full"] for r in rows) >= 3 and sum(r["rej"] for r in rows) > 0 and sum(r["nan"] for r in rows) > 0 and sum(r["term"] for r in rows) > 0
+    # row by row what the table says of them: the first nine are comparable to their last trial and reject 1, 1, 3, 1, 1, 7, 3, 2, 2 trials, two of them
+    # with a NaN step; the last four Terminate behind a noise-level trial
+    assert [r["full"] for r in rows] == [True] * 9 + [False] * 4
+    assert [r["rej"] for r in rows[:9]] == [1, 1, 3, 1, 1, 7, 3, 2, 2] and [r["nan"] for r in rows[:9]] == [False, False, False, True, False, True, False, False, False]
+    assert [r["term"] for r in rows] == [0] * 9 + [1] * 4 and rows[12]["rej"] == 4
+    # ... and the table below the staging limit still meets its test's closing condition
+    old = _tally(oracle_lib, PNP_HARD)
+    full = [r for r in old if r["full"]]
+    assert sum(r["rej"] for r in old) > 0 and sum(r["term"] for r in old) > 0 and sum(r["nan"] for r in old) > 0 and len(full) >= 3
+    assert sum(r["rej"] for r in full) > 0 and sum(r["term"] + r["nan"] for r in full) > 0
+
+
+def test_dense_sequence_stays_above_the_staging_limit(oracle_lib):
+    from parity_util import make_case
+    name, kind, seed, scale, overrides, frames = KITTI_DENSE_UNSTAGED
+    world, prm, sensor = make_case(kind, seed, scale, overrides)
+    orc = oracle_lib.Oracle(prm, sensor)
+    n_matches = []
+    for i in frames:
+        orc.track(*world.render_stereo(i))
+        c = orc.counts()
+        n_matches.append(c["n_matches"])
+        assert orc.status == 2 and c["n_left"] <= 4096 and c["n_right"] <= 4096 and c["overflow"] == 0, (i, orc.status, c)
+    assert n_matches == [0, 1386, 1572, 1667, 1745, 1754, 1750, 1800, 1786, 1810], n_matches
+    assert sum(1 for m in n_matches if m > PNP_STAGE_MAX) >= DENSE_MIN_UNSTAGED_FRAMES
+    # the same world under the defaults, its neighbour in the mixed batch, stays staged
+    _, prm_default, _ = make_case(kind, seed, scale)
+    orc = oracle_lib.Oracle(prm_default, sensor)
+    for i in frames[:3]:
+        orc.track(*world.render_stereo(i))
+    assert 0 < orc.counts()["n_matches"] <= PNP_STAGE_MAX and orc.status == 2
+
+
+@pytest.mark.parametrize("variant", list(STAIRCASE))
+def test_staircase_bands(oracle_lib, variant):
+    prm, L, R, cl, cr, bands = staircase(variant)
+    orc = oracle_lib.Oracle(prm, 1)
+    orc.track_with_external_corners(L, R, cl, cr)
+    c = orc.counts()
+    want = staircase_expected(prm, bands)
+    assert c["n_left"] == c["n_right"] == len(cl) == 114 * len(bands)
+    assert c["n_row_matches"] == sum(w[0] for w in want) and c["n_triangulated"] == c["map_size"] == sum(w[1] for w in want), c
+    assert staircase_band_counts(prm, orc.map()[0], len(bands)) == [w[1] for w in want]
+    if variant == "13_bands":
+        assert (L.shape, c["n_row_matches"], c["map_size"]) == ((1222, 1241), 1482, 570)
+        assert [d for (d, _), w in zip(bands, want) if w[1]] == [9.7, 12, 40, 150, 192.9]
+    if variant == "11_bands":
+        assert L.shape[0] + 1 <= 1100 < 1222 + 1          # LS_BINS (k_lists.hip): this one's row lists fit the binned kernel
+    if variant == "row_band_edge":
+        assert [w[0] for w in want] == [114, 114, 0, 114]

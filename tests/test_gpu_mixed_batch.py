@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from case_tables import KITTI_DENSE_UNSTAGED, PNP_STAGE_MAX
 from parity_util import make_case, pose_errors, POSE_TOL
 
 pytestmark = pytest.mark.gpu
@@ -119,6 +120,21 @@ def test_everything_different_in_one_batch(hip_lib, oracle_lib):
     hip_lib.load_library().lvt_amd_get_debug(batch._h, stamps.ctypes.data_as(ctypes.c_void_p))
     assert int(stamps[10]) in (1001, 1002), int(stamps[10])
     check_against_own_oracles(batch, seqs, schedule, got)
+
+
+def test_staged_and_unstaged_solve_in_one_launch(hip_lib, oracle_lib):
+    """one world twice in a batch: under the dense parameters (more than PNP_STAGE_MAX matches from frame 2 on: k_pnp's edges stay in global
+    memory) and under the defaults (about 600 matches, staged in LDS) -- one k_pnp launch holds both kinds of solve, three steps in flight"""
+    _, kind, seed, scale, overrides, frames = KITTI_DENSE_UNSTAGED
+    world, prm_dense, _ = make_case(kind, seed, scale, overrides)
+    _, prm_default, _ = make_case(kind, seed, scale)
+    seqs = [Seq(world, prm_dense, len(frames)), Seq(world, prm_default, len(frames))]
+    batch = hip_lib.LvtBatch([prm_dense, prm_default])
+    schedule = [[i, i] for i in frames]
+    got = run(batch, seqs, schedule)
+    assert batch.last_error() == "", batch.last_error()
+    check_against_own_oracles(batch, seqs, schedule, got)
+    assert batch.counts(0)["n_matches"] > PNP_STAGE_MAX and 0 < batch.counts(1)["n_matches"] <= PNP_STAGE_MAX, (batch.counts(0), batch.counts(1))
 
 
 def test_sequences_of_different_lengths(hip_lib, oracle_lib):

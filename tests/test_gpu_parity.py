@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from case_tables import (DENSE_MIN_UNSTAGED_FRAMES, KITTI_DENSE_UNSTAGED, PNP_STAGE_MAX, STAIRCASE, staircase, staircase_band_counts,
+                         staircase_expected)
 from parity_util import make_case, run_sequence, diff_frame, sparse_pair, HardWorld, POSE_TOL
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +41,9 @@ CASES = [
     ("euroc", "euroc", 0, 1.0, {}, list(range(10))),                           # configs[2] shape
     ("tum_rgbd", "tum", 0, 1.0, {}, list(range(8))),                           # configs[3] shape (single 640x480 cell)
     ("tum_rgbd_distorted", "tum", 1, 1.0, TUM_DISTORTION, list(range(120))),
+    # ~2 400 features per image, triangulation on every frame: 1 386 matches on frame 1, 1 572 - 1 810 on frames 2 - 9 -- k_pnp above PNP_STAGE_MAX, its
+    # edges in global memory (asserted below: nothing else in this table is sure to reach that path)
+    KITTI_DENSE_UNSTAGED,
 ]
 # geometry: the feature stage picks its route from the image and cell shape alone (k_score's compaction below 64-px cells, the two-workgroup
 # split up to 256, row strips + three-launch ANMS above, the wide global path over 1024 px), the list kernels from the hash grid and the search
@@ -80,11 +85,17 @@ def test_sequence_parity(hip_lib, oracle_lib, name, kind, seed, scale, overrides
     world, prm, sensor = make_case(kind, seed, scale, overrides, size=size)
     if name.startswith("kitti_hard"):
         world = HardWorld(world, seed)
-    res, hip, orc = run_sequence(world, prm, sensor, frames)
+    n_matches = []
+    on_frame = (lambda i, hip, orc: n_matches.append(hip.counts()["n_matches"])) if name == "kitti_dense_unstaged" else None
+    res, hip, orc = run_sequence(world, prm, sensor, frames, on_frame=on_frame)
     bad = [(i, m) for i, m, _, _ in res if m]
     assert not bad, f"{name}: first divergence at frame {bad[0][0]}: {bad[0][1][:6]}"
     assert max(r[2] for r in res) <= POSE_TOL and max(r[3] for r in res) <= POSE_TOL
     c = hip.counts()
+    if name == "kitti_dense_unstaged":
+        unstaged = sum(1 for m in n_matches if m > PNP_STAGE_MAX)
+        print(f"{name}: matches per frame {n_matches}: {unstaged} frames over {PNP_STAGE_MAX}")
+        assert unstaged >= DENSE_MIN_UNSTAGED_FRAMES and hip.get_state() == 2, (n_matches, hip.get_state())
     if name.startswith("kitti_hard"):
         assert hip.get_state() == 2 and c["pnp_inliers"] < 0.9 * c["n_matches"], (c["pnp_inliers"], c["n_matches"])   # the gates really demote edges here
     if name == "kitti_low_corner_retry":
@@ -432,13 +443,11 @@ def test_async_host_rgbd_equals_the_oracle(hip_lib, oracle_lib):
     assert not msgs, msgs[:6]
 
 
-def test_async_device_pipeline_equals_the_oracle(hip_lib, oracle_lib):
-    """lvt_amd_track_device_async, four frames in flight, 200 frames: every pose and state against the ORACLE's, the full frame diff at the end"""
+def _async_device_against_the_oracle(hip_lib, world, prm, n, depth):
+    """lvt_amd_track_device_async, `depth` frames in flight: every pose and state against the ORACLE's, the full frame diff at the end"""
     import torch
     from oracle import pyoracle as O
     from parity_util import pose_errors
-    world, prm, sensor = make_case("kitti", 22, 0.5)
-    n, depth = 200, 4
     pitch = ((world.W + 63) // 64) * 64
     dev = torch.zeros((n, 2, world.H, pitch), dtype=torch.uint8, device="cuda")
     frames = [world.render_stereo(i) for i in range(n)]
@@ -462,6 +471,22 @@ def test_async_device_pipeline_equals_the_oracle(hip_lib, oracle_lib):
         assert e_t <= POSE_TOL and e_R <= POSE_TOL and got[i][2] == orc.status, f"frame {i}: {e_t:.2e} {e_R:.2e}"
     msgs = diff_frame(hip, orc)
     assert not msgs, msgs[:6]
+    return hip, orc
+
+
+def test_async_device_pipeline_equals_the_oracle(hip_lib, oracle_lib):
+    """lvt_amd_track_device_async, four frames in flight, 200 frames: every pose and state against the ORACLE's, the full frame diff at the end"""
+    world, prm, sensor = make_case("kitti", 22, 0.5)
+    _async_device_against_the_oracle(hip_lib, world, prm, 200, 4)
+
+
+def test_async_device_pipeline_above_the_staging_limit(hip_lib, oracle_lib):
+    """the dense sequence (k_pnp's edges in global memory from frame 2 on) with three frames in flight: the early kernels of frame t + 1 run beside
+    the unstaged solve of frame t"""
+    _, kind, seed, scale, overrides, frames = KITTI_DENSE_UNSTAGED
+    world, prm, sensor = make_case(kind, seed, scale, overrides)
+    hip, orc = _async_device_against_the_oracle(hip_lib, world, prm, len(frames), 3)
+    assert hip.counts()["n_matches"] > PNP_STAGE_MAX and hip.get_state() == orc.status == 2, hip.counts()["n_matches"]
 
 
 def test_lockstep_batch_equals_the_oracles(hip_lib, oracle_lib):
@@ -1498,3 +1523,39 @@ def test_many_handles_on_one_gpu(hip_lib, monkeypatch, ordering):
         assert vos[k].last_error() == "", (k, vos[k].last_error())
         for i, ((Ra, ta), (Rb, tb)) in enumerate(zip(ref[k], got[k])):
             assert np.array_equal(ta, tb) and np.array_equal(Ra, Rb), f"handle {k} frame {i}"
+
+
+_STAIR_CASES = [(v, b) for v in STAIRCASE for b in ("0", "1")]
+
+
+@pytest.mark.parametrize("variant,binned", _STAIR_CASES, ids=[f"{v}-{'binned_list_kernel' if b == '1' else 'wave_per_query_lists'}" for v, b in _STAIR_CASES])
+def test_triangulation_gates_on_a_disparity_staircase(hip_lib, oracle_lib, monkeypatch, variant, binned):
+    """k_triangulate's gates decided both ways: a first stereo frame (every triangulated pair goes to the map) of noise in bands of 94 rows, band b
+    planted at disparity d_b with near = 2 m and far = 40 m (9.6536 and 193.07 px): behind the camera (-5), parallel rays into ls_solve_4x3 (0),
+    far beyond far (0.4, 5), either side of the far plane (9.4, 9.6 | 9.7), inside (12, 40, 150), either side of the near plane (192.9 | 193.3), 300.
+    13 bands: 1 482 row pairs, 570 map points; the row lists of its 1 222 rows are past LS_BINS (the binned kernel stands down), the 11-band subset
+    has the binned kernel build them.  row_band_edge: a band whose right eye sits 2 rows lower pairs and triangulates, 3 rows lower does not pair.
+    The full frame diff against the oracle, and per band the count predicted from z = fx b / d."""
+    from oracle import pyoracle as O
+    monkeypatch.setenv("LVT_AMD_BINNED_LISTS", binned)
+    prm, L, R, cl, cr, bands = staircase(variant)
+    hip = hip_lib.LvtSystem.create(prm, 1)
+    orc = O.Oracle(prm, 1)
+    orc.track_with_external_corners(L, R, cl, cr)
+    hip.track_with_external_corners(L, R, cl, cr)
+    msgs = diff_frame(hip, orc)
+    assert not msgs, msgs[:6]
+    want = staircase_expected(prm, bands)
+    pairs, points = sum(w[0] for w in want), sum(w[1] for w in want)
+    c = hip.counts()
+    got = staircase_band_counts(prm, hip.map()[0], len(bands))
+    print(f"staircase {variant}: {c['n_triangulated']} of {c['n_row_matches']} row pairs triangulated, per band {got}")
+    assert c["n_left"] == c["n_right"] == len(cl) and c["n_row_matches"] == pairs and c["n_triangulated"] == c["map_size"] == points, (c, pairs, points)
+    assert got == [w[1] for w in want], (got, want)
+    if variant == "13_bands":
+        assert (pairs, points) == (1482, 570)
+    if variant != "row_band_edge":      # the gates decide both ways, and often
+        assert pairs - points >= 0.5 * pairs and points >= 0.3 * pairs, (pairs, points)
+    else:
+        assert want[1] == (114, 114) and want[2] == (0, 0)
+    assert hip.get_state() == orc.status == 2
