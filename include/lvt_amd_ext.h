@@ -180,7 +180,9 @@ LVT_API int lvt_amd_batch_mixed_tables(const lvt_amd_params *p, int sensor_type,
 
 /* run all work of this handle on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
 LVT_API void lvt_amd_set_stream(lvt_handle h, void *hip_stream);
-/* last HIP error string seen by this handle ("" if none); overflow / capacity diagnostics too.
+/* last HIP error string seen by this handle ("" if none); overflow / capacity diagnostics too.  A capacity report is its frame's own: once it has
+ * been read here, the next frame collected that fits clears it (read after every frame, the string speaks for that frame; read every N frames, a
+ * cut among them is still reported once); lvt_amd_reset clears it as well.  Every other report stays until the next one.
  * BLOCKING: when the last synchronous call returned on its early pose (the frame's tail -- staged update, triangulation -- was still running), this
  * call first collects that frame: its own reports (capacity overflow, a gate that timed out, a skipped frame) arrive with its full record.  A caller
  * that checks the string after EVERY lvt_track therefore gives up the overlap of that tail with its next upload (~30 us per frame); check it every N

@@ -20,9 +20,17 @@
  * image) over 4096 px.  Per frame: 2048 key points one cell may emit after ANMS, 4096 features
  * per image after BRIEF's border filter, 16384 external corners per list, 32768 map points,
  * 16384 staged points.  Exceeding one of these never passes silently: the frame is tracked on
- * what fits -- a cell's first 2048 key points, an image's first 4096 features -- and
- * lvt_amd_last_error() / the `overflow` count (include/lvt_amd_ext.h) say which capacity was
- * hit.  Every shipped configuration of the reference (KITTI, EuRoC, TUM) stays well below them.
+ * what fits -- a cell's first 2048 key points, an image's first 4096 features (the first 4096
+ * survivors of the border filter, in input order), the map's first 32768 points in append order
+ * -- and lvt_amd_last_error() / the `overflow` count (include/lvt_amd_ext.h) say which capacity
+ * was hit, frame by frame: the report covers the frame just tracked, and a map that is culled
+ * back below its capacity reports nothing.  For the map this means: newly triangulated points
+ * and promoted staged points are appended while there is room and dropped behind it; a staged
+ * point whose promotion is dropped leaves the staged set all the same, as every promoted point
+ * does in the reference.  The staged capacity is a bound, not a cut: a staged point that finds
+ * no feature of its own in a frame is erased in that frame, so at most 4096 survive it and at
+ * most 4096 are added behind them -- 8192 at the very most, half the capacity.
+ * Every shipped configuration of the reference (KITTI, EuRoC, TUM) stays well below them.
  */
 #ifndef LVT_C_INTERFACE_H__
 #define LVT_C_INTERFACE_H__

@@ -255,6 +255,11 @@ struct Context {
     long prof_calls[PROF_SLOTS] = {};
 
     void set_error(const std::string &s) { err = s; }
+    // A capacity report is its frame's own (include/lvt_c.h).  It stays until it has been read through lvt_amd_last_error AND a later frame has been collected
+    // that fits: a caller that reads the string every N frames still learns of a cut, one that reads it after every frame sees each frame's own report.
+    // (Every other report -- HIP errors, gate time-outs -- stays until the next one, as before.)
+    long long ovf_done = -1, ovf_read_done = -1;  // `done` behind the frame that set the report / at the last read of it
+    bool capacity_report() const { return err.compare(0, 17, "capacity overflow") == 0; }
 
     template <typename T>
     T *dalloc_uncached(size_t n) {  // device memory no cache holds (MTYPE UC): what one workgroup stores, another of the same launch may read without fences
@@ -466,6 +471,7 @@ static void drain(Context *c);
 static void reset_state(Context *c, int only = -1) {  // lvt_system::reset (lvt_system.cpp:44-68); only >= 0: that sequence of a batch alone
     drain(c);
     if (only < 0) c->gate_timeouts_seen = 0, c->gate_fatal_seen = 0;
+    if (only < 0 && c->capacity_report()) c->err.clear();  // (the frames it spoke of are gone)
     for (int s = 0; s < c->B; s++) {
         if (only >= 0 && s != only) continue;
         Ctl z;
@@ -1014,12 +1020,16 @@ static void collect_oldest(Context *c) {
                 }
             }
     }
+    bool cut = false;
     for (int s = 0; s < Bz; s++)
         if (c->h_ctl[(size_t)slot * c->B + s].overflow) {
             char buf[128];
             std::snprintf(buf, sizeof(buf), "capacity overflow mask 0x%x in sequence %d", c->h_ctl[(size_t)slot * c->B + s].overflow, s);
             c->set_error(buf);
+            cut = true;
         }
+    if (cut) c->ovf_done = (long long)c->done;
+    else if (c->capacity_report() && c->ovf_read_done >= c->ovf_done) c->err.clear();  // an earlier frame's report, read since: this frame fits
     if (c->B > 1 && c->score_pieces_auto && !c->events_only) {  // see Context::score_pieces
         const Ctl &r0 = c->h_ctl[(size_t)slot * c->B];
         const long long t0 = r0.dbg[32], t1 = r0.dbg[35], t2 = r0.dbg[33];
@@ -1403,6 +1413,7 @@ LVT_API const char *lvt_amd_last_error(lvt_handle h) {
         } catch (...) {
         }
     }
+    if (c->capacity_report()) c->ovf_read_done = (long long)c->done;
     return c->err.c_str();
 }
 

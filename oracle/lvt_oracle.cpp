@@ -906,6 +906,14 @@ struct System {
     int state = 1;  // 1 NOT_INITIALIZED, 2 TRACKING, 3 LOST (lvt_system.h:45-50)
     int frame_number = 0;
     int n_threads = 2;
+    // test option (lvto_set_capacities): 0 = unbounded, the reference's behaviour.  With a capacity an append keeps the first `cap` points in
+    // append order and ORs LVTO_OVF_MAP / LVTO_OVF_STAGED into the frame's overflow count: the documented policy of the HIP path (include/lvt_c.h)
+    size_t map_cap = 0, staged_cap = 0;
+    void cut(std::vector<MapPoint> &v, size_t cap, int bit) {
+        if (cap == 0 || v.size() <= cap) return;
+        v.resize(cap);
+        counts[LVTO_C_OVERFLOW] |= bit;
+    }
     std::vector<Rect> rects;
     Bounds bounds;
     MotionModel motion;
@@ -1148,10 +1156,13 @@ struct System {
             triangulate(cam_pose, ls, rs, &nt);
         counts[LVTO_C_TRIANGULATED] = 1;
         counts[LVTO_C_N_TRIANGULATED] = (int)nt.size();
-        if (dont_stage || prm.staged_threshold == 0 || (int)map.size() < kNMapPoints)
+        if (dont_stage || prm.staged_threshold == 0 || (int)map.size() < kNMapPoints) {
             map.insert(map.end(), nt.begin(), nt.end());
-        else
+            cut(map, map_cap, LVTO_OVF_MAP);
+        } else {
             staged.insert(staged.end(), nt.begin(), nt.end());
+            cut(staged, staged_cap, LVTO_OVF_STAGED);
+        }
     }
     // update_staged_map_points -- local_map.cpp:355-391
     void update_staged(const Pose &cam_pose, FeatureStruct *ls) {
@@ -1171,6 +1182,7 @@ struct System {
             mp->counter += 1;
             if (mp->counter == prm.staged_threshold || (int)map.size() < kNMapPoints) {
                 map.push_back(staged[i]);
+                cut(map, map_cap, LVTO_OVF_MAP);  // (a promotion that does not fit is dropped: the staged point is erased all the same)
                 del[i] = 1;
                 counts[LVTO_C_N_STAGED_PROMOTED]++;
             }
@@ -1366,6 +1378,11 @@ lvto_handle lvto_create(const lvto_params *p, int sensor_type) {
 void lvto_destroy(lvto_handle h) { delete static_cast<System *>(h); }
 void lvto_reset(lvto_handle h) { static_cast<System *>(h)->reset(); }
 void lvto_set_threads(lvto_handle h, int n) { static_cast<System *>(h)->n_threads = n; }
+void lvto_set_capacities(lvto_handle h, int map_cap, int staged_cap) {
+    System *s = static_cast<System *>(h);
+    s->map_cap = (size_t)std::max(map_cap, 0);
+    s->staged_cap = (size_t)std::max(staged_cap, 0);
+}
 
 void lvto_track(lvto_handle h, const uint8_t *left, const uint8_t *right, int rows, int cols, double R[9], double t[3]) {
     pose_out(static_cast<System *>(h)->track(left, right, rows, cols), R, t);

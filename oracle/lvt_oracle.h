@@ -53,6 +53,13 @@ lvto_handle lvto_create(const lvto_params *p, int sensor_type); /* lvt_system.cp
 void lvto_destroy(lvto_handle h);
 void lvto_reset(lvto_handle h);                                 /* lvt_system.cpp:44-68 */
 void lvto_set_threads(lvto_handle h, int n);                    /* 2 = reference behaviour (handler.cpp:204-206) */
+/* TEST OPTION.  The reference's map and staged set grow without bound, and so does the oracle by default (0 = unbounded).  With a capacity
+ * the three append sites (new triangulation into the map or the staged set, promotion of a staged point) keep the first `cap` points in
+ * append order and OR LVTO_OVF_MAP / LVTO_OVF_STAGED into the frame's LVTO_C_OVERFLOW count: the HIP path's documented policy
+ * (include/lvt_c.h, "capacities"), stated here as a resize behind the reference's own insert / push_back.  A staged point whose promotion
+ * does not fit is erased from the staged set all the same, as the reference erases every promoted point. */
+enum { LVTO_OVF_MAP = 8, LVTO_OVF_STAGED = 16 };               /* == OVF_MAP, OVF_STAGED of lvt_dev.h */
+void lvto_set_capacities(lvto_handle h, int map_cap, int staged_cap);
 void lvto_track(lvto_handle h, const uint8_t *left, const uint8_t *right, int rows, int cols,
                 double R[9], double t[3]);                      /* lvt_system.cpp:157-207 */
 void lvto_track_rgbd(lvto_handle h, const uint8_t *gray, const float *depth, int rows, int cols,
@@ -82,7 +89,7 @@ enum {
     LVTO_C_N_STAGED_PROMOTED,
     LVTO_C_N_CULLED,
     LVTO_C_FRAME,
-    LVTO_C_OVERFLOW_UNUSED,  /* (slot 18 is the HIP path's capacity-overflow mask; always 0 here) */
+    LVTO_C_OVERFLOW,         /* slot 18 is the HIP path's capacity-overflow mask; here 0 unless lvto_set_capacities set a capacity */
     LVTO_C_PNP_BORDERLINE,   /* chi2-gate decisions (both passes) within 1e-8 of the 5.991 threshold */
     LVTO_C_ROW_FALLBACK_UNUSED, /* (slot 20 is the HIP path's "row lists built on the tracking stream" flag; always 0 here) */
     LVTO_C_PNP_TRIALS,       /* LM trials of both passes (solve + update + chi2 each) */

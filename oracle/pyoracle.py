@@ -39,6 +39,7 @@ def lib():
         L.lvto_destroy.argtypes = [vp]
         L.lvto_reset.argtypes = [vp]
         L.lvto_set_threads.argtypes = [vp, C.c_int]
+        L.lvto_set_capacities.argtypes = [vp, C.c_int, C.c_int]
         L.lvto_track.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
         L.lvto_track_rgbd.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
         L.lvto_track_with_external_corners.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
@@ -103,6 +104,11 @@ class Oracle:
 
     def reset(self):
         lib().lvto_reset(self.h)
+
+    def set_capacities(self, map_cap=0, staged_cap=0):
+        """test option: keep the first `cap` points of the map / the staged set in append order and report the cut in counts()["overflow"]
+        (8 map, 16 staged), as the HIP path does at MAP_MAX / STAGED_MAX; 0 = unbounded, the reference's behaviour and the default"""
+        lib().lvto_set_capacities(self.h, int(map_cap), int(staged_cap))
 
     def track(self, left, right):
         l, r = _u8(left), _u8(right)

@@ -159,3 +159,69 @@ def staircase_band_counts(prm, xyz, n_bands):
     """map points per band, a point's band taken from its row in the (identity-pose) left image"""
     v = prm.fy * xyz[:, 1] / xyz[:, 2] + prm.cy
     return np.bincount(np.floor(v / STAIR_BAND).astype(np.int64), minlength=n_bands)[:n_bands].tolist() if len(xyz) else [0] * n_bands
+
+
+# ---- the map kernels from 10k points to past capacity ----------------------------------------------------------------------------------------------
+# Four recipes that take the per-frame map kernels (bookkeep_cull_large, the super-chunk resolver, staged_body, the two capacity cuts) to the sizes
+# they are written for: MAP_MAX map points, several thousand staged points.  Every frame is noise; columns [0, 300) are the same in all frames (the
+# pose stays solvable on the corners there), the rest is fresh per texture epoch, so old map points find no partner and every fresh corner
+# triangulates.  The right eye is the left one moved 12 px (z ~ 32 m).
+MAP_MAX, STAGED_MAX = 32768, 16384        # lvt_dev.h
+MAPCAP_W, MAPCAP_H, MAPCAP_DISP = 1241, 376, 12
+MAPCAP_KEEP, MAPCAP_FRESH = 300, 3700
+
+# name: (overrides, frames per texture epoch, external corners, frames).  `steady` culls as fast as it appends and plateaus below MAP_MAX; `direct`
+# appends past MAP_MAX by triangulation, `promotion` by promotion of staged points (staged on even frames, promoted on odd ones); `detector` is
+# `direct` through the detector (plain track): the lock-step batch's case; `direct_recover` overflows, then culls its way back below the capacity
+MAPCAP_RECIPES = {
+    "steady": ({"staged_threshold": 0, "untracked_threshold": 8}, 1, True, 14),
+    "direct": ({"staged_threshold": 0, "untracked_threshold": 1000}, 1, True, 12),
+    "direct_recover": ({"staged_threshold": 0, "untracked_threshold": 10}, 1, True, 14),
+    "promotion": ({"staged_threshold": 1, "untracked_threshold": 1000}, 2, True, 22),
+    "detector": ({"staged_threshold": 0, "untracked_threshold": 1000, "max_keypoints_per_cell": 400}, 1, False, 18),
+}
+
+
+def mapcap_params(name):
+    prm = lvt_amd.kitti_params(width=MAPCAP_W, height=MAPCAP_H)
+    prm.triangulation_policy = 2
+    for k, v in MAPCAP_RECIPES[name][0].items():
+        setattr(prm, k, type(getattr(prm, k))(v))
+    return prm
+
+
+def _mapcap_fixed():
+    rng = np.random.default_rng(0)
+    img = rng.integers(0, 256, (MAPCAP_H, MAPCAP_W), dtype=np.uint8)
+    keep = np.column_stack([rng.integers(52, 270, MAPCAP_KEEP), rng.integers(40, MAPCAP_H - 40, MAPCAP_KEEP)])
+    return img, keep
+
+
+def mapcap_frame(epoch):
+    """(L, R, corners_left, corners_right) of one texture epoch"""
+    fixed, keep = _mapcap_fixed()
+    rng = np.random.default_rng(100 + epoch)
+    L = rng.integers(0, 256, (MAPCAP_H, MAPCAP_W), dtype=np.uint8)
+    L[:, :300] = fixed[:, :300]
+    R = np.ascontiguousarray(np.roll(L, -MAPCAP_DISP, axis=1))
+    fresh = np.column_stack([rng.integers(340, MAPCAP_W - 40, MAPCAP_FRESH), rng.integers(40, MAPCAP_H - 40, MAPCAP_FRESH)])
+    cl = np.unique(np.vstack([keep, fresh]), axis=0).astype(np.float64)
+    return L, R, cl, cl - [[float(MAPCAP_DISP), 0.0]]
+
+
+def mapcap_case(name, n_frames=None):
+    """(params, generator of (L, R, corners_left, corners_right)); the corner lists are None for a recipe that runs through the detector.  Frames are
+    made one at a time: a stereo pair is 0.9 MB"""
+    _, per_epoch, ext, n = MAPCAP_RECIPES[name]
+
+    def frames():
+        for i in range(n_frames or n):
+            L, R, cl, cr = mapcap_frame(i // per_epoch)
+            yield (L, R, cl, cr) if ext else (L, R, None, None)
+    return mapcap_params(name), frames()
+
+
+def mapcap_track(system, frame):
+    """one recipe frame through an oracle or a HIP handle (the two share the method names)"""
+    L, R, cl, cr = frame
+    return system.track(L, R) if cl is None else system.track_with_external_corners(L, R, cl, cr)

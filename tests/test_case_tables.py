@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import lvt_amd
+from case_tables import (MAP_MAX, MAPCAP_RECIPES, STAGED_MAX, mapcap_case, mapcap_track)
 from case_tables import (DENSE_MIN_UNSTAGED_FRAMES, KITTI_DENSE_UNSTAGED, PNP_EDGE_COUNTS, PNP_HARD, PNP_HARD_UNSTAGED, PNP_INTRINSICS, PNP_STAGE_MAX,
                          STAIRCASE, pnp_edge_case, pnp_hard_case, pnp_prior_cases, staircase, staircase_band_counts, staircase_expected, trace_noise)
 
@@ -127,3 +128,103 @@ def test_staircase_bands(oracle_lib, variant):
         assert L.shape[0] + 1 <= 1100 < 1222 + 1          # LS_BINS (k_lists.hip): this one's row lists fit the binned kernel
     if variant == "row_band_edge":
         assert [w[0] for w in want] == [114, 114, 0, 114]
+
+
+# ---- the map-capacity recipes (test_gpu_map_capacity.py) -------------------------------------------------------------------------------------------
+def _mapcap_rows(oracle_lib, name, n_frames=None, capped=False):
+    """the recipe through the oracle alone: TRACKING on every frame; one row of counters per frame"""
+    prm, frames = mapcap_case(name, n_frames)
+    orc = oracle_lib.Oracle(prm, 1)
+    if capped:
+        orc.set_capacities(MAP_MAX, STAGED_MAX)
+    rows = []
+    for i, f in enumerate(frames):
+        mapcap_track(orc, f)
+        assert orc.status == 2, (name, i, orc.status)
+        rows.append(orc.counts())
+        assert rows[-1]["staged_size"] <= max(rows[-1]["n_left"], 1), (name, i)      # a staged point owns a feature or goes: far below STAGED_MAX
+    return rows, orc
+
+
+def _first_past_capacity(rows):
+    return next(i for i, c in enumerate(rows) if c["map_size"] > MAP_MAX)
+
+
+def test_mapcap_steady_culls_thousands_above_25000_points(oracle_lib):
+    rows, _ = _mapcap_rows(oracle_lib, "steady")
+    assert len(rows) == MAPCAP_RECIPES["steady"][3] == 14
+    assert [c["map_size"] for c in rows[:8]] == [3985, 7607, 11173, 14679, 18134, 21537, 24861, 28104]
+    assert all(c["n_culled"] > 3000 and c["map_size_at_match"] > 25000 and c["map_size"] > 25000 for c in rows[-6:]), [(c["n_culled"], c["map_size"]) for c in rows]
+    assert max(c["map_size"] for c in rows) <= MAP_MAX and all(c["overflow"] == 0 for c in rows)
+    assert all(c["n_left"] <= 4096 and c["n_right"] <= 4096 for c in rows)
+
+
+def test_mapcap_direct_passes_the_capacity_at_frame_9(oracle_lib):
+    rows, orc = _mapcap_rows(oracle_lib, "direct", 11)
+    assert _first_past_capacity(rows) == 9 and [rows[i]["map_size"] for i in (8, 9, 10)] == [31333, 34508, 37652]
+    assert all(c["overflow"] == 0 and c["n_culled"] == 0 for c in rows)                  # the default: the reference's unbounded growth
+    # the capacity option is the documented cut and nothing else: the same frames, the first MAP_MAX points of the unbounded map in append order
+    capped, orc_c = _mapcap_rows(oracle_lib, "direct", 10, capped=True)
+    assert capped[:9] == rows[:9]
+    assert {k: v for k, v in capped[9].items() if k not in ("map_size", "overflow")} == {k: v for k, v in rows[9].items() if k not in ("map_size", "overflow")}
+    assert capped[9]["map_size"] == MAP_MAX and capped[9]["overflow"] == 8
+    prm, frames = mapcap_case("direct", 10)
+    ref = oracle_lib.Oracle(prm, 1)
+    for f in frames:
+        mapcap_track(ref, f)
+    for a, b in zip(orc_c.map(), ref.map()):
+        assert len(a) == MAP_MAX < len(b) == 34508 and np.array_equal(a, b[:MAP_MAX])
+
+
+def test_mapcap_direct_recovers_from_an_overflow(oracle_lib):
+    """untracked_threshold 10: the first culls at frame 10; the capped oracle overflows, then culls its way back below the capacity"""
+    rows, _ = _mapcap_rows(oracle_lib, "direct_recover", capped=True)
+    assert [i for i, c in enumerate(rows) if c["n_culled"]][0] == 10
+    ovf = [i for i, c in enumerate(rows) if c["overflow"]]
+    assert ovf == [9, 10] and all(rows[i]["overflow"] == 8 and rows[i]["map_size"] == MAP_MAX for i in ovf)
+    assert any(c["overflow"] == 0 and c["n_culled"] > 3000 for c in rows[ovf[0] + 1:])
+    assert all(c["overflow"] == 0 and c["n_culled"] > 3000 and c["map_size"] < MAP_MAX for c in rows[11:]) and len(rows) == 14
+
+
+def test_mapcap_promotion_passes_the_capacity_by_promotion_at_frame_19(oracle_lib):
+    rows, _ = _mapcap_rows(oracle_lib, "promotion", 24)
+    assert _first_past_capacity(rows) == 19 and (rows[18]["map_size"], rows[19]["map_size"], rows[19]["n_staged_promoted"]) == (31106, 34263, 3157)
+    assert rows[19]["n_triangulated"] < 100 and rows[19]["staged_size"] < 100          # ... by promotion: what frame 19 triangulates is staged
+    big = [i for i, c in enumerate(rows) if c["staged_size"] > 2048]
+    assert len(big) >= 5 and big[:3] == [2, 4, 6], big
+    assert sum(1 for c in rows if c["n_staged_promoted"] > 2048) >= 5                    # staged_body's second scan pair: more than RES_THREADS matched
+    capped, orc = _mapcap_rows(oracle_lib, "promotion", capped=True)
+    assert len(capped) == 22 and [i for i, c in enumerate(capped) if c["overflow"]] == [19, 20, 21]
+    assert capped[19]["n_staged_promoted"] == 3157 and capped[19]["map_size"] == MAP_MAX and capped[19]["staged_size"] == rows[19]["staged_size"]
+
+
+def test_mapcap_detector_passes_the_capacity_at_frame_16(oracle_lib):
+    rows, _ = _mapcap_rows(oracle_lib, "detector", 17)
+    assert _first_past_capacity(rows) == 16 and (rows[15]["map_size"], rows[16]["map_size"]) == (32280, 33829)
+    assert all(3000 < c["n_left"] <= 4096 and 3000 < c["n_right"] <= 4096 for c in rows)
+    assert all(1400 <= c["n_triangulated"] <= 2400 for c in rows[1:])
+
+
+def test_oracle_capacity_option_cuts_all_three_append_sites(oracle_lib):
+    """Oracle.set_capacities at small capacities, so that each append site cuts within six frames of `promotion`: triangulation into the map (frame 0),
+    into the staged set (bit 16, frame 2), promotion (frames 2 and 3); the mask is the frame's own, and (0, 0) is the unbounded default again"""
+    prm, frames = mapcap_case("promotion", 6)
+    orc, ref = oracle_lib.Oracle(prm, 1), oracle_lib.Oracle(prm, 1)
+    orc.set_capacities(3000, 2000)
+    ref.set_capacities(3000, 2000); ref.set_capacities(0, 0)
+    rows = []
+    for f in frames:
+        mapcap_track(orc, f); mapcap_track(ref, f)
+        rows.append(orc.counts())
+        assert ref.counts()["overflow"] == 0
+    # (frame 1 stages the ~1 000 corners whose map points frame 0 cut; those of the fixed strip are matched and promoted at frame 2: bit 8 there too)
+    assert [c["overflow"] for c in rows[:4]] == [8, 0, 24, 8] and rows[2]["n_staged_promoted"] > 0, [c["overflow"] for c in rows]
+    assert rows[0]["n_triangulated"] == 3985 and rows[0]["map_size"] == 3000
+    got, first = orc.map(), ref.map()
+    assert all(np.array_equal(got[k][:3000], first[k][:3000]) for k in (0, 3))               # positions, descriptors: the first points in append order
+    assert rows[2]["n_triangulated"] > 2000 == rows[2]["staged_size"] and rows[2]["map_size"] == 3000
+    # frame 3: every matched staged point is promoted and none fits -- dropped, and gone from the staged set all the same
+    # (what is staged behind it is what frame 3 triangulates: the corners whose points frame 2's staged cut had dropped)
+    assert rows[3]["n_staged_promoted"] + rows[3]["n_staged_erased"] == 2000 and rows[3]["n_staged_promoted"] > 1900 and rows[3]["map_size"] == 3000
+    assert rows[3]["staged_size"] == rows[3]["n_triangulated"] < 2000
+    assert ref.counts()["map_size"] > 10000

@@ -273,20 +273,37 @@ def test_more_than_2048_features_per_image(hip_lib, oracle_lib, monkeypatch, bin
     assert 2048 < hip.counts()["n_left"] <= 4096 and hip.get_state() == orc.status == 2
 
 
-def test_more_features_than_capacity_is_reported(hip_lib):
+def test_more_features_than_capacity_is_reported(hip_lib, oracle_lib):
     """4 900 external corners survive the border filter, the feature arrays hold 4 096: the frame is tracked on the first 4 096 and the cut
-    is reported through lvt_amd_last_error (the reference has no such limit: include/lvt_c.h, "capacities") -- never silently"""
+    is reported through lvt_amd_last_error (the reference has no such limit: include/lvt_c.h, "capacities") -- never silently.  What it is tracked
+    on: an oracle fed the first 4 096 survivors of the border filter, in input order, finds the same features, map and pose -- on the cut frame and
+    on the 500-corner frame behind it"""
+    from oracle import pyoracle as O
     world, prm, sensor = make_case("kitti", 12, 1.0)
     hip = hip_lib.LvtSystem.create(prm, 1)
+    orc = O.Oracle(prm, 1)
     gx, gy = np.meshgrid(np.arange(70, dtype=np.float64) * 3 + 40, np.arange(70, dtype=np.float64) * 3 + 40)
     grid = np.stack([gx.ravel(), gy.ravel()], axis=1)
     a, b = world.render_stereo(0)
-    hip.track_with_external_corners(a, b, grid, grid)
+    Rh, th = hip.track_with_external_corners(a, b, grid, grid)
     c = hip.counts()
     assert c["n_left"] == 4096 and c["n_right"] == 4096 and c["overflow"] != 0
     assert "capacity overflow" in hip.last_error()
-    hip.track_with_external_corners(a, b, grid[:500], grid[:500])      # the handle keeps working
+    kept_l, kept_r = O.brief(a, grid)[0], O.brief(b, grid)[0]
+    assert len(kept_l) == len(kept_r) == 4900
+    Ro, to = orc.track_with_external_corners(a, b, grid[kept_l[:4096]], grid[kept_r[:4096]])
+    msgs = diff_frame(hip, orc)
+    for m in (f"hip error: capacity overflow mask 0x{c['overflow']:x} in sequence 0", f"count overflow: hip={c['overflow']} oracle=0", f"overflow mask {c['overflow']}"):
+        assert m in msgs, (m, msgs[:6])
+        msgs.remove(m)
+    assert not msgs, msgs[:6]
+    assert np.allclose(th, to, atol=1e-6) and np.allclose(Rh, Ro, atol=1e-6)
+    Rh, th = hip.track_with_external_corners(a, b, grid[:500], grid[:500])      # the handle keeps working
     assert hip.counts()["n_left"] == 500 and hip.counts()["overflow"] == 0
+    Ro, to = orc.track_with_external_corners(a, b, grid[:500], grid[:500])
+    msgs = diff_frame(hip, orc)
+    assert not msgs, msgs[:6]
+    assert np.allclose(th, to, atol=1e-6) and np.allclose(Rh, Ro, atol=1e-6)
 
 
 def test_create_from_yaml_matches_struct_create(hip_lib, oracle_lib, tmp_path):
