@@ -3,8 +3,9 @@
 // Same argv, inputs and outputs as the reference's example binary (examples/euroc/euroc_example.cpp:49-175 there):
 //     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt]
 // reads <stamps_dir>/<dataset_name>.txt (one nanosecond stamp per line = the image file stem), the cam0 / cam1 PNGs below
-// <root>/<dataset_name>/mav0/, rectifies both on the GPU with the calibration the reference hard-codes
-// (lvt_amd_rectifier_*: cv::initUndistortRectifyMap + cv::remap INTER_LINEAR), tracks, maps the camera pose into the body
+// <root>/<dataset_name>/mav0/, hands the RAW images to lvt_track -- the two rectifiers with the calibration the reference hard-codes
+// (lvt_amd_rectifier_*: cv::initUndistortRectifyMap + cv::remap INTER_LINEAR) are attached to the tracker once, which rectifies
+// every frame at the head of its feature stage (lvt_amd_set_rectifiers) --, maps the camera pose into the body
 // frame (T_BS * T_cam) and writes <dataset_name>.txt in the TUM format "t x y z qx qy qz qw" (6 / 7 digits).
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
@@ -105,10 +106,13 @@ int main(int argc, char **argv) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;
         return -1;
     }
+    if (lvt_amd_set_rectifiers(vo, rect_l, rect_r) != 0) {  // from here on lvt_track takes the camera's raw images
+        std::cout << "failed to attach the rectifiers: " << lvt_amd_last_error(vo) << std::endl;
+        return -1;
+    }
     long frame_count = (long)titles.size();
     if (max_frames >= 0 && max_frames < frame_count) frame_count = max_frames;
     std::vector<double> poses;  // q (w x y z), p of the BODY per processed frame
-    std::vector<unsigned char> rl_img((size_t)W * H), rr_img((size_t)W * H);
     double total_time = 0;
     long n = 0;
     for (long i = 0; i < frame_count; i++) {
@@ -121,12 +125,8 @@ int main(int argc, char **argv) {
             break;
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (lvt_amd_rectify(rect_l, left.px.data(), rl_img.data()) != 0 || lvt_amd_rectify(rect_r, right.px.data(), rr_img.data()) != 0) {
-            std::cout << "rectification failed" << std::endl;
-            break;
-        }
         double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
-        lvt_track(vo, rl_img.data(), rr_img.data(), H, W, R, t);
+        lvt_track(vo, left.px.data(), right.px.data(), H, W, R, t);
         total_time += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         double body[3][4];  // Tbs * [R t; 0 1]
         for (int r = 0; r < 3; r++)

@@ -237,7 +237,8 @@ LVT_API void lvt_amd_get_timeline(lvt_handle h, long long out[16]);
  * polling gate holds up whatever another handle queued behind it) */
 LVT_API int lvt_amd_get_ordering(lvt_handle h);
 /* raw per-pixel intermediates of the last frame: what = 0 score map (u8, rows x pitch),
- * 1 box-sum map (u16, rows x pitch).  returns bytes written, pitch via *pitch_out (in elements). */
+ * 1 box-sum map (u16, rows x pitch), 2 the rectified image of a handle with rectifiers (u8, rows x pitch; 0 bytes without them).
+ * returns bytes written, pitch via *pitch_out (in elements). */
 LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int cap_bytes, int *pitch_out);
 
 /* ---- stage entry points on caller-provided data (differential tests vs the oracle) ---- */
@@ -285,6 +286,24 @@ LVT_API int lvt_amd_rectify_device(lvt_amd_rectifier r, const void *d_src, int s
                                    void *hip_stream);
 LVT_API int lvt_amd_rectify(lvt_amd_rectifier r, const unsigned char *src, unsigned char *dst);
 LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier r, float *map1, float *map2);
+/* RAW stereo frames: rectification inside the tracker's feature stage.  With a pair of rectifiers attached, every stereo frame handed to the handle --
+ * lvt_track, lvt_amd_track_async, lvt_amd_track_device[_async]; a batch: the sequences with rectifiers in lvt_amd_batch_track_device_async[_mixed] -- is a RAW
+ * frame: one launch at the head of the feature stage (k_rectify_frames: both eyes of every such sequence of the step) rectifies it into planes the tracker
+ * owns, byte for byte what lvt_amd_rectify_device writes, and the frame is tracked from those.  No host round trip, no second upload, no launch or stream of the
+ * caller's to order.  A handle or sequence without rectifiers launches exactly what it did before.
+ *  - host entry points pull the raw images where they pulled the rectified ones (the staged planes of the call, the fused pull of lvt_amd_track_async included);
+ *    device entry points read the caller's raw planes in place: any pitch >= n_cols (the pitch % 16 rule applies to rectified planes only); the planes must
+ *    stay valid until the frame has been collected, as always.
+ *  - the rectifiers are BORROWED: they must outlive the handle or be detached first (NULL, NULL detaches; one NULL is refused); several sequences and handles may
+ *    share a pair.
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error): a rectifier whose size is not the sequence's img_width x img_height or that was created on
+ *    another device, an RGB-D handle, a pooled or automatic seat, seq out of range, a handle with frames in flight (attach before the first frame or after every
+ *    frame has been collected).  A successful attach counts as use of an lvt_create handle: it stays on its own chain when a second lvt_create arrives.
+ *  - lvt_track_with_external_corners on such a handle is refused (nothing is tracked, lvt_amd_last_error says so): the corners would be in rectified coordinates.
+ *  - lvt_amd_get_plane(h, eye, 2, ...) reads the rectified image of the last frame back (u8, rows x pitch; 0 for a handle without rectifiers);
+ *    lvt_amd_profile_read reports the launch as "k_rectify_frames". */
+LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right);
+LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right);
 
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "lvt_amd_batch_create_mixed", "lvt_amd_batch_track_device_async_mixed", "lvt_amd_batch_get_params", "lvt_amd_batch_mixed_tables",
     "lvt_amd_track_rgbd_device", "lvt_amd_track_rgbd_device_async", "lvt_amd_track_rgbd16", "lvt_amd_track_rgbd16_async",
     "lvt_amd_batch_track_rgbd_device_async",
+    "lvt_amd_set_rectifiers", "lvt_amd_batch_set_rectifiers",
 ]
 
 N_COUNTS = 32
@@ -155,6 +156,10 @@ def load_library():
             ("lvt_amd_track_rgbd16", [vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]),
             ("lvt_amd_track_rgbd16_async", [vp, vp, vp, C.c_float, C.c_int, C.c_int]),
             ("lvt_amd_batch_track_rgbd_device_async", [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_float])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (("lvt_amd_set_rectifiers", [vp, vp, vp]), ("lvt_amd_batch_set_rectifiers", [vp, C.c_int, vp, vp])):   # (raw frames: likewise)
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
@@ -324,6 +329,14 @@ class LvtSystem:
         st = load_library().lvt_amd_wait_status(self._h, _p(R), _p(t))
         return R, t, st
 
+    def set_rectifiers(self, left, right) -> int:
+        """attach a pair of Rectifier objects (or None, None to detach): every stereo frame handed to this system is then a RAW frame, rectified at the head of
+        its feature stage.  0: done; -1: refused (last_error() says why).  The rectifiers are borrowed: keep them alive while they are attached."""
+        rc = load_library().lvt_amd_set_rectifiers(self._h, left._h if left is not None else None, right._h if right is not None else None)
+        if rc == 0:
+            self._rect = (left, right)
+        return rc
+
     def set_stream(self, hip_stream: int):
         load_library().lvt_amd_set_stream(self._h, C.c_void_p(hip_stream))
 
@@ -398,7 +411,8 @@ class LvtSystem:
         return a
 
     def plane(self, eye=0, what=0):
-        """what=0: corner score map (u8), what=1: 9x9 box sums (u16); returns (rows, pitch) array"""
+        """what=0: corner score map (u8), what=1: 9x9 box sums (u16), what=2: the rectified image of a system with rectifiers (u8; an empty array
+        without them); returns (rows, pitch) array"""
         cap = 64 << 20
         buf = np.zeros(cap // 8, dtype=np.uint64)
         pitch = C.c_int(0)
@@ -406,7 +420,9 @@ class LvtSystem:
         if nbytes < 0:
             raise RuntimeError("lvt_amd_get_plane failed")
         raw = buf.view(np.uint8)[:nbytes]
-        a = raw.view(np.uint8 if what == 0 else np.uint16)
+        if nbytes == 0:
+            return np.zeros((0, 0), np.uint8)
+        a = raw.view(np.uint16 if what == 1 else np.uint8)
         return a.reshape(-1, pitch.value).copy()
 
 
@@ -474,6 +490,13 @@ class LvtBatch:
         b = vps(*[None if x is None else int(x) for x in d_depth])
         return load_library().lvt_amd_batch_track_rgbd_device_async(self._h, a, b, per_seq(rows), per_seq(cols), per_seq(gray_pitch), per_seq(depth_pitch),
                                                                    int(depth_format), float(depth_scale))
+
+    def set_rectifiers(self, seq: int, left, right) -> int:
+        """LvtSystem.set_rectifiers for sequence `seq` of the batch: its frames are raw from then on, the other sequences' are not"""
+        rc = load_library().lvt_amd_batch_set_rectifiers(self._h, int(seq), left._h if left is not None else None, right._h if right is not None else None)
+        if rc == 0:
+            self.__dict__.setdefault("_rect", {})[int(seq)] = (left, right)
+        return rc
 
     def params(self, seq: int) -> LvtParameters:
         pod = ParamsPOD()

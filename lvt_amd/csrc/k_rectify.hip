@@ -8,6 +8,8 @@
 //                   BORDER_CONSTANT 0, 15-bit weights, one 32-bit coalesced store.  8 B of map + 1 B out + <= 4 B of source
 //                   per pixel: HBM-bound by construction, but one 752x480 image is 4.7 MB -- 0.6 us at 8 TB/s -- so a
 //                   single launch is latency-bound like the rest of the single-sequence chain.
+//   k_rectify_fix / k_rectify_frames : the same remap as the first kernel of a tracker's feature stage (raw frames, lvt_amd_set_rectifiers):
+//                   one launch for both eyes of every sequence of a step, from an interleaved fixed-point form of the maps.
 #include "lvt_dev.h"
 
 namespace lvt {
@@ -38,8 +40,8 @@ __global__ __launch_bounds__(64) void k_rectify_map(RectifyArgs a, float *map1, 
     }
 }
 
-__device__ __forceinline__ int remap_one(const uint8_t *src, int sw, int sh, int sstep, float mx, float my) {
-    const int sxf = __float2int_rn(mx * 32.f), syf = __float2int_rn(my * 32.f);  // cvRound: round half to even
+// one output pixel from the map entry in 1/32-px fixed point (sxf, syf): 2x2 gather with BORDER_CONSTANT 0, 15-bit weights
+__device__ __forceinline__ int remap_fixed(const uint8_t *src, int sw, int sh, int sstep, int sxf, int syf) {
     const int sx = min(max(sxf >> 5, -32768), 32767), sy = min(max(syf >> 5, -32768), 32767), ax = sxf & 31, ay = syf & 31;
     int w0 = (32 - ax) * (32 - ay) * 32, w1 = ax * (32 - ay) * 32, w2 = (32 - ax) * ay * 32, w3 = ax * ay * 32;
     if (ax == 0 && ay == 0) w0 = 32767, w3 = 1;  // initInterTab2D: 32768 saturates to short, the sum fix-up lands on the last weight
@@ -59,6 +61,11 @@ __device__ __forceinline__ int remap_one(const uint8_t *src, int sw, int sh, int
     const int r = (v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15;
     return min(max(r, 0), 255);
 }
+// float map -> 1/32-px fixed point: cvRound, round half to even.  A pure function of the map value: k_rectify_fix stores exactly what k_rectify computes per pixel
+__device__ __forceinline__ int map_to_fixed(float m) { return __float2int_rn(m * 32.f); }
+__device__ __forceinline__ int remap_one(const uint8_t *src, int sw, int sh, int sstep, float mx, float my) {
+    return remap_fixed(src, sw, sh, sstep, map_to_fixed(mx), map_to_fixed(my));
+}
 
 // dst_pitch % 4 == 0; the padding columns of dst (if any) are written as zero
 __global__ __launch_bounds__(256) void k_rectify(const uint8_t *src, int sw, int sh, int sstep, const float *map1, const float *map2, int dw, int dh,
@@ -72,6 +79,50 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t *src, int sw, int
         if (x < dw) packed |= (uint32_t)remap_one(src, sw, sh, sstep, map1[(size_t)y * dw + x], map2[(size_t)y * dw + x]) << (8 * k);
     }
     *reinterpret_cast<uint32_t *>(dst + (size_t)y * dst_pitch + x4) = packed;
+}
+
+// the two float maps as ONE interleaved fixed-point map (x, y per pixel): built once per rectifier, one 8-byte load per pixel in k_rectify_frames
+__global__ __launch_bounds__(256) void k_rectify_fix(const float *map1, const float *map2, int2 *fix, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) fix[i] = make_int2(map_to_fixed(map1[i]), map_to_fixed(map2[i]));
+}
+
+// ---- raw frames inside the feature stage: one launch rectifies both eyes of every sequence that brought a raw frame -----------------------
+// One descriptor per image; the table travels BY VALUE in the kernel arguments (like FrameArgsPack): no device read of host memory in front of
+// the frame.  blockIdx.y = image; the grid's x extent is sized by the largest image of the table and an image's surplus workgroups leave at the top.
+// A thread owns one 32-bit word of the destination (4 pixels; words are numbered row after row over the destination PITCH, so the padding
+// columns are written as zero and no lane idles at a row's end); per pixel one 8-byte map load and remap_fixed -- byte for byte k_rectify's output.
+struct RectImg {
+    const uint8_t *src;   // raw image (any pitch >= sw; read byte-wise)
+    const int2 *map;      // dw x dh fixed-point entries (Rectifier::d_fix)
+    uint8_t *dst;         // rectified plane, dst_pitch % 4 == 0
+    int src_pitch, dst_pitch;
+    int sw, sh, dw, dh;
+};
+constexpr int RECT_PACK = 64;   // images per launch (32 stereo sequences); larger batches take several launches
+struct RectTable {
+    RectImg im[RECT_PACK];
+};
+static_assert(sizeof(RectTable) < 4096, "k_rectify_frames' arguments must stay under 4096 bytes");
+
+__global__ __launch_bounds__(256) void k_rectify_frames(RectTable tab) {
+    const RectImg &I = tab.im[blockIdx.y];   // (uniform index: the descriptor stays in scalar registers)
+    const int wpr = I.dst_pitch >> 2;        // words per destination row
+    const unsigned word = blockIdx.x * 256u + threadIdx.x;
+    if (blockIdx.x * 256u >= (unsigned)(wpr * I.dh)) return;   // a workgroup outside this image
+    if (word >= (unsigned)(wpr * I.dh)) return;
+    const int y = (int)(word / (unsigned)wpr), x4 = (int)(word - (unsigned)y * (unsigned)wpr) * 4;
+    const int2 *M = I.map + (size_t)y * I.dw;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x = x4 + k;
+        if (x < I.dw) {
+            const int2 m = M[x];
+            packed |= (uint32_t)remap_fixed(I.src, I.sw, I.sh, I.src_pitch, m.x, m.y) << (8 * k);
+        }
+    }
+    *reinterpret_cast<uint32_t *>(I.dst + (size_t)y * I.dst_pitch + x4) = packed;
 }
 
 }  // namespace lvt

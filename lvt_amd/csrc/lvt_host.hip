@@ -128,6 +128,16 @@ static std::atomic<int> g_live_contexts[MAX_DEVICES];
 // lock-step batch SHARED by the pooled handles of a device); the first word tells them apart.
 constexpr uint64_t CTX_MAGIC = 0x4C56545F43545831ull, SLOT_MAGIC = 0x4C56545F534C5431ull;
 
+// EuRoC pre-step (k_rectify.hip): the maps of one camera.  Stand-alone (lvt_amd_rectify[_device]) or attached to a tracker, whose feature stage then
+// starts with k_rectify_frames (lvt_amd_set_rectifiers)
+struct Rectifier {
+    int w = 0, h = 0, pitch = 0;
+    int device = 0;                              // the HIP device the maps live on
+    float *d_map1 = nullptr, *d_map2 = nullptr;
+    int2 *d_fix = nullptr;                       // both maps interleaved, 1/32-px fixed point (k_rectify_fix): what k_rectify_frames reads
+    uint8_t *d_src = nullptr, *d_dst = nullptr;  // staging for the host-buffer entry point
+};
+
 struct Context {
     uint64_t magic = CTX_MAGIC;
     double host_enq_us = 0, host_wait_us = 0;  // host time spent enqueueing / blocking (LVT_AMD_HOST_TIMING=1 prints it at destroy)
@@ -240,6 +250,14 @@ struct Context {
     long long fused_pulls = 0;
     int feature_cus = 0;    // CUs the feature stream is confined to (0: all; lock-step batches, see create_context)
     float *d_ext[NPAR][2] = {};
+    // RAW stereo frames (lvt_amd_set_rectifiers / lvt_amd_batch_set_rectifiers): a sequence with a pair of rectifiers attached takes raw images through every
+    // stereo entry point.  The entry points work as for rectified frames -- their FrameArgs name the raw planes (the caller's, or the staged ones) --, and
+    // enqueue_frame puts ONE k_rectify_frames launch at the head of the feature stage that writes the sequence's own rectified planes (per feature-buffer
+    // parity) and points the frame at them.  Borrowed: the rectifiers outlive the handle or are detached first.
+    std::vector<Rectifier *> rect;     // [B][2], nullptr: none (empty until the first attach)
+    std::vector<uint8_t *> d_rect;     // [B][NPAR][2] rectified planes, each sequence's own pitch
+    int n_rect = 0;                    // sequences with rectifiers
+    bool has_rect(int s) const { return n_rect > 0 && rect[2 * (size_t)s] != nullptr; }
     int pitch = 0;
     long enq = 0, done = 0;    // frames enqueued / collected
     long delivered = 0;        // frames whose record delivery has been enqueued (k_triangulate, the next frame's k_gate_late, or k_deliver)
@@ -770,7 +788,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
 
 // ---- the per-frame launch chain -------------------------------------------------------------------
 static const char *kProfNames[Context::PROF_SLOTS] = {
-    "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
+    "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "",
     "", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
     "", ""};
@@ -843,6 +861,39 @@ static void enqueue_frame(Context *c) {
     hipStream_t sf = c->stream_f, st = c->stream;
     for (int i = 0; i < Context::PROF_SLOTS; i++) c->ev_used[i] = false;
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
+    // ---- raw frames: both eyes of every sequence that has rectifiers and a frame in this step, in one launch.  The rectified planes (parity `par`) were
+    //      read last by the feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order
+    //      alone covers the hand-over, and the launch needs no gate: it goes out ahead of the buffer gate.
+    if (c->n_rect) {
+        FrameArgs *fw = c->h_fargs + (size_t)slot * B;
+        RectTable tab;
+        std::memset(&tab, 0, sizeof(tab));
+        int n = 0, words = 0;
+        bool timed = false;
+        auto launch = [&]() {
+            const dim3 grid((words + 255) / 256, n);
+            if (!timed) LAUNCH(4, sf, k_rectify_frames, grid, dim3(256), 0, tab);
+            else hipLaunchKernelGGL(k_rectify_frames, grid, dim3(256), 0, sf, tab);
+            timed = true, n = 0, words = 0;
+        };
+        for (int s = 0; s < Bz; s++) {
+            if (!c->has_rect(s) || fw[s].absent) continue;
+            const Params &q = c->seq_prm(s);
+            const int dpitch = c->h_seqs[s].plane_pitch;
+            for (int e = 0; e < 2; e++) {
+                RectImg &I = tab.im[n++];
+                I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
+                I.map = c->rect[2 * (size_t)s + e]->d_fix;
+                I.dst = c->d_rect[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
+                I.sw = I.dw = q.W, I.sh = I.dh = q.H;
+                words = std::max(words, dpitch / 4 * q.H);
+                fw[s].img[e] = I.dst;
+            }
+            fw[s].img_pitch = dpitch;
+            if (n == RECT_PACK) launch();
+        }
+        if (n) launch();
+    }
     const bool evo = c->events_only;
     const bool feat_pack = B > 1 && Bz <= FEAT_PACK && !std::getenv("LVT_AMD_NO_FEAT_PACK");  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
@@ -1125,6 +1176,9 @@ static void result_out(Context *c, int s, double R[3][3], double t[3]) {
 }
 
 static bool size_ok(Context *c, int rows, int cols) { return rows == c->prm.H && cols == c->prm.W; }
+// pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
+// byte-wise by k_rectify_frames: any pitch that holds a row
+static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) { return c->has_rect(s) ? pitch >= cols : (pitch & 15) == 0; }
 
 template <typename T>
 static void d2h(Context *c, T *dst, const T *src, size_t n) {
@@ -1455,6 +1509,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     if (slot < 0 || slot >= Context::PROF_SLOTS || !kProfNames[slot][0]) return 0;
+    if (slot == 4 && c->n_rect == 0 && c->prof_calls[4] == 0) return 0;  // (a handle without rectifiers has no such launch)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1477,7 +1532,7 @@ LVT_API void lvt_amd_track_device_async(lvt_handle h, const void *d_left, const 
             c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
             return;
         }
-        if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
+        if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols)) {
             c->set_error("lvt_amd_track_device: image size / pitch mismatch");
             return;
         }
@@ -1570,10 +1625,10 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             if (!d_left[s]) continue;
             present++;
             const Params &q = c->seq_prm(s);
-            if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || (pitch_bytes[s] & 15) || pitch_bytes[s] < n_cols[s]) {
+            if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
-                std::snprintf(buf, sizeof(buf), "lvt_amd_batch_track_device_async_mixed: sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch a multiple of 16)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H);
+                std::snprintf(buf, sizeof(buf), "lvt_amd_batch_track_device_async_mixed: sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->has_rect(s) ? "at least the width" : "a multiple of 16");
                 c->set_error(buf);
                 return -1;
             }
@@ -1616,7 +1671,9 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
             c->set_error("lvt_amd_batch_track_device: a mixed batch takes its frames through lvt_amd_batch_track_device_async_mixed");
             return;
         }
-        if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
+        bool pitch_ok = true;  // (one pitch for the whole step: it must suit the raw and the rectified sequences alike)
+        for (int s = 0; s < c->B; s++) pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols);
+        if (!size_ok(c, n_rows, n_cols) || !pitch_ok) {
             c->set_error("lvt_amd_batch_track_device: image size / pitch mismatch");
             return;
         }
@@ -1749,7 +1806,7 @@ LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *
         c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
         return;
     }
-    if (!size_ok(c, n_rows, n_cols) || (pitch_bytes & 15)) {
+    if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols)) {
         c->set_error("lvt_amd_track_device: image size / pitch mismatch");
         return;  // outputs untouched, like the reference on an exception
     }
@@ -2250,6 +2307,10 @@ LVT_API void lvt_track_with_external_corners(lvt_handle h, unsigned char *left, 
         Context *c = static_cast<Context *>(h);
         DeviceGuard guard(c);
         if (c->sensor != 1) return;
+        if (c->has_rect(0)) {  // the images would be raw, the corners in rectified coordinates the caller does not have
+            c->set_error("lvt_track_with_external_corners: refused on a handle with rectifiers attached (the frame was NOT tracked; detach them with lvt_amd_set_rectifiers(h, NULL, NULL))");
+            return;
+        }
         if (cut[0]) c->set_error(cut);
         upload_and_track(c, left, right, false, n_rows, n_cols, 1, cl.data(), ncl, cr.data(), ncr, R, t);
     } catch (...) {
@@ -2468,6 +2529,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
         drain(c);
         const FrameBuf &FB = c->h_seqs[0].fb[c->last_par];
         const size_t n = (size_t)c->pitch * c->prm.H;
+        if (what == 2) {  // the rectified image of the last (raw) frame
+            if (!c->has_rect(0) || c->done == 0) return 0;
+            if ((size_t)cap_bytes < n) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_rect[(size_t)c->last_par * 2 + (eye ? 1 : 0)], n, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->pitch;
+            return (int)n;
+        }
         const size_t bytes = n * (what == 0 ? 1 : 2);
         if ((size_t)cap_bytes < bytes) return -1;
         if (what == 0) HIPCHK(c, hipMemcpy(dst, FB.score[eye ? 1 : 0], bytes, hipMemcpyDeviceToHost));
@@ -2641,12 +2709,6 @@ LVT_API float lvt_amd_hamming_match_batched(const void *q_desc, const void *q_xy
 
 
 // ---- EuRoC pre-step: rectification -------------------------------------------------------------------------------------
-struct Rectifier {
-    int w = 0, h = 0, pitch = 0;
-    float *d_map1 = nullptr, *d_map2 = nullptr;
-    uint8_t *d_src = nullptr, *d_dst = nullptr;  // staging for the host-buffer entry point
-};
-
 LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9], const double Pnew[9], int width,
                                                    int height) {
     if (!K || !D || !R || !Pnew || width <= 0 || height <= 0) return nullptr;
@@ -2656,7 +2718,8 @@ LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const doub
     if (!r) return nullptr;
     r->w = width, r->h = height, r->pitch = ((width + 63) / 64) * 64;
     const size_t n = (size_t)width * height;
-    if (hipMalloc((void **)&r->d_map1, n * 4) != hipSuccess || hipMalloc((void **)&r->d_map2, n * 4) != hipSuccess ||
+    if (hipGetDevice(&r->device) != hipSuccess || hipMalloc((void **)&r->d_fix, n * sizeof(int2)) != hipSuccess ||
+        hipMalloc((void **)&r->d_map1, n * 4) != hipSuccess || hipMalloc((void **)&r->d_map2, n * 4) != hipSuccess ||
         hipMalloc((void **)&r->d_src, n) != hipSuccess || hipMalloc((void **)&r->d_dst, (size_t)r->pitch * height) != hipSuccess) {
         lvt_amd_rectifier_destroy(r);
         return nullptr;
@@ -2685,6 +2748,7 @@ LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const doub
     a.k1 = D[0], a.k2 = D[1], a.p1 = D[2], a.p2 = D[3], a.k3 = D[4];
     a.w = width, a.h = height;
     hipLaunchKernelGGL(k_rectify_map, dim3((height + 63) / 64), dim3(64), 0, 0, a, r->d_map1, r->d_map2);
+    hipLaunchKernelGGL(k_rectify_fix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, r->d_map1, r->d_map2, r->d_fix, n);
     if (hipDeviceSynchronize() != hipSuccess) {
         lvt_amd_rectifier_destroy(r);
         return nullptr;
@@ -2695,7 +2759,7 @@ LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const doub
 LVT_API void lvt_amd_rectifier_destroy(lvt_amd_rectifier h) {
     Rectifier *r = static_cast<Rectifier *>(h);
     if (!r) return;
-    (void)hipFree(r->d_map1), (void)hipFree(r->d_map2), (void)hipFree(r->d_src), (void)hipFree(r->d_dst);
+    (void)hipFree(r->d_map1), (void)hipFree(r->d_map2), (void)hipFree(r->d_fix), (void)hipFree(r->d_src), (void)hipFree(r->d_dst);
     delete r;
 }
 
@@ -2721,6 +2785,73 @@ LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier h, float *map1, float *
     if (!r || !map1 || !map2) return -1;
     const size_t n = (size_t)r->w * r->h * 4;
     return (hipMemcpy(map1, r->d_map1, n, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(map2, r->d_map2, n, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -1;
+}
+
+// ---- raw frames: rectifiers attached to a tracker (Context::rect) -------------------------------------------------------------------------
+// Everything is checked before anything changes: 0 = attached / detached, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
+static int rect_refuse(lvt_handle h, const std::string &why) {
+    const std::string msg = "lvt_amd_set_rectifiers: " + why + " (nothing was changed)";
+    if (is_slot(h)) {
+        PoolSlot *S = static_cast<PoolSlot *>(h);
+        std::lock_guard<std::mutex> g(S->pool->mu);
+        S->err = msg;
+    } else if (is_ctx(h))
+        static_cast<Context *>(h)->set_error(msg);
+    return -1;
+}
+static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
+    if (is_slot(h)) return rect_refuse(h, "a pooled handle (its frames ride a chain shared with other handles)");
+    if (!is_ctx(h)) return -1;
+    Context *c = static_cast<Context *>(h);
+    DeviceGuard guard(c);
+    try {
+        if (c->sensor != 1) return rect_refuse(h, "an RGB-D handle (there is one image, and its depth plane is registered to it)");
+        if (!batch_call && (c->B != 1 || c->mixed)) return rect_refuse(h, "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers");
+        if (seq < 0 || seq >= c->B) return rect_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
+        if ((left == nullptr) != (right == nullptr)) return rect_refuse(h, "one rectifier is NULL (both, or NULL, NULL to detach)");
+        Rectifier *rl = static_cast<Rectifier *>(left), *rr = static_cast<Rectifier *>(right);
+        const Params &q = c->seq_prm(seq);
+        for (Rectifier *r : {rl, rr}) {
+            if (!r) continue;
+            if (r->w != q.W || r->h != q.H)
+                return rect_refuse(h, "a rectifier of " + std::to_string(r->w) + " x " + std::to_string(r->h) + " on a sequence of " + std::to_string(q.W) + " x " + std::to_string(q.H));
+            if (r->device != c->device)
+                return rect_refuse(h, "a rectifier created on device " + std::to_string(r->device) + ", the handle owns device " + std::to_string(c->device));
+        }
+        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
+        if (c->done < c->enq || c->pend.valid) return rect_refuse(h, "frames in flight: attach before the first frame or after every frame has been collected");
+        if (c->rect.empty()) {
+            c->rect.assign(2 * (size_t)c->B, nullptr);
+            c->d_rect.assign((size_t)c->B * NPAR * 2, nullptr);
+        }
+        if (rl) {
+            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * q.H;
+            for (int k = 0; k < NPAR * 2; k++) {
+                uint8_t *&d = c->d_rect[(size_t)seq * NPAR * 2 + k];
+                if (!d) d = c->dalloc<uint8_t>(plane + 64);
+            }
+        }
+        c->rect[2 * (size_t)seq] = rl, c->rect[2 * (size_t)seq + 1] = rr;
+        c->n_rect = 0;
+        for (int s = 0; s < c->B; s++) c->n_rect += c->rect[2 * (size_t)s] != nullptr;
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+// an lvt_create handle: decided under its record's lock -- a handle that has not been used yet may be given a seat by another thread's lvt_create at any time --,
+// and a successful attach is a use: the handle keeps its own chain
+static int set_rectifiers_any(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
+    if (!is_auto(h)) return set_rectifiers(h, seq, batch_call, left, right);
+    AutoHandle *A = static_cast<AutoHandle *>(h);
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = set_rectifiers(A->impl, seq, batch_call, left, right);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right) { return set_rectifiers_any(h, 0, false, left, right); }
+LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right) {
+    return set_rectifiers_any(h, seq, true, left, right);
 }
 
 // ---- odometry accumulator (lvt_ros.cpp:215-311 without ROS) -----------------------------------------------
