@@ -127,7 +127,9 @@ LVT_API int lvt_amd_wait_pose(lvt_handle h, double q_wxyz[4], double p[3]);
  * All of these return 0 when the frame was enqueued (or tracked) and -1 when it was refused -- then NOTHING was enqueued, frames in flight are unaffected and
  * lvt_amd_last_error says why (a batch: naming the sequence).  Refused: a stereo or pooled handle (pooled handles are stereo only), a NULL plane, a size that
  * is not the sequence's own, an unknown format, a bad depth_scale, a misaligned plane.  (The other way round, the stereo device calls -- lvt_amd_track_device[_async],
- * lvt_amd_batch_track_device_async[_mixed] -- refuse an RGB-D handle: they have no depth plane to hand over.) */
+ * lvt_amd_batch_track_device_async[_mixed] -- refuse an RGB-D handle: they have no depth plane to hand over.)
+ * Every call of this header and of lvt_c.h that takes a frame or waits for one refuses a handle that is neither a tracker, a pooled seat nor an lvt_create
+ * handle -- NULL included -- before it touches the device: -1 where it returns an int, R and t untouched where it returns nothing. */
 enum { LVT_AMD_DEPTH_F32 = 0, LVT_AMD_DEPTH_U16 = 1 };
 /* one handle, planes resident in HBM.  Gray: 16-byte aligned pointer, pitch a multiple of 16.  Depth: pointer aligned to its element (4 / 2 bytes), pitch in
  * BYTES, a multiple of the element size and >= n_cols elements.  The planes must stay valid and unchanged until the frame has been collected. */

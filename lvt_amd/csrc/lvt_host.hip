@@ -138,6 +138,12 @@ struct Rectifier {
     uint8_t *d_src = nullptr, *d_dst = nullptr;  // staging for the host-buffer entry point
 };
 
+// pinned staging of one frame's host planes, [image | image or depth], each part padded to 16 B: what the host writes and what the device pulls
+struct HostStage {
+    uint8_t *h = nullptr, *dev = nullptr;  // the same memory as the host / the device addresses it
+    size_t second = 0;                     // offset of the second plane (the bytes reserved per 8-bit image, a 16-B multiple)
+};
+
 struct Context {
     uint64_t magic = CTX_MAGIC;
     double host_enq_us = 0, host_wait_us = 0;  // host time spent enqueueing / blocking (LVT_AMD_HOST_TIMING=1 prints it at destroy)
@@ -224,8 +230,7 @@ struct Context {
     std::function<void()> before_gather;  // host work to run once the detection kernels are enqueued (the RGB-D depth upload)
     // owned staging for the host-buffer entry points, per feature buffer
     uint8_t *d_img[NPAR][2] = {};
-    uint8_t *h_stage[NPAR] = {}, *h_stage_dev[NPAR] = {};  // pinned staging of host images (lvt_track): [left | right or depth]
-    size_t stage_img = 0;                                    // bytes reserved per 8-bit image (16-B multiple)
+    HostStage stage[NPAR];  // pinned staging of host images (lvt_track): [left | right or depth]
     float *d_depth[NPAR] = {};
     // asynchronous host-buffer calls (lvt_amd_track_async / lvt_amd_track_rgbd_async): one image set and one staging buffer per RING slot -- frame t's
     // slot was last used by frame t - RING, which make_room() has collected, so neither the pull (a write) nor the CPU copy into the staging
@@ -234,8 +239,7 @@ struct Context {
     // (profiles/r04_async_host.md; the variants are in the history at 7f39175).
     uint8_t *d_img_ring[RING][2] = {};
     float *d_depth_ring[RING] = {};
-    uint8_t *h_stage_ring[RING] = {}, *h_stage_ring_dev[RING] = {};
-    size_t stage_ring_bytes = 0;
+    HostStage stage_ring[RING];
     long long async_frames = 0;
     // A stereo frame handed to lvt_amd_track_async is HELD until the next one arrives (or somebody waits for it): the held frame's k_cells launch then carries
     // the workgroups that pull the NEXT frame's images (k_features.hip, NextPull), and a frame whose images came that way starts without a pull of its own.
@@ -314,7 +318,7 @@ struct Context {
         if (stream_f) (void)hipStreamSynchronize(stream_f);
         if (stream_e) (void)hipStreamSynchronize(stream_e);
         for (void *p : allocs) (void)hipFree(p);
-        for (auto &x : h_stage_ring) if (x) (void)hipHostFree(x);
+        for (auto &x : stage_ring) if (x.h) (void)hipHostFree(x.h);
         for (auto &e : ev)
             for (auto &x : e)
                 if (x) (void)hipEventDestroy(x);
@@ -323,7 +327,7 @@ struct Context {
         if (ev_depth) (void)hipEventDestroy(ev_depth);
         if (ev_switch) (void)hipEventDestroy(ev_switch);
         if (ev_switch_e) (void)hipEventDestroy(ev_switch_e);
-        for (auto &x : h_stage) if (x) (void)hipHostFree(x);
+        for (auto &x : stage) if (x.h) (void)hipHostFree(x.h);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_done) (void)hipHostFree(h_done);
         if (h_pose) (void)hipHostFree(h_pose);
@@ -817,6 +821,42 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
 
 static void collect_oldest(Context *c);
 
+// ---- a frame's inputs ---------------------------------------------------------------------------------
+// Every path BUILDS a FrameArgs -- from FrameArgs{}: fp32 depth, no external corners, present -- and assigns the whole value to its place in the ring:
+// a slot still holds the frame of RING steps ago, and nothing of it may reach the kernels.
+static FrameArgs stereo_args(const void *left, const void *right, int pitch_bytes) {
+    FrameArgs f{};
+    f.img[0] = static_cast<const uint8_t *>(left);
+    f.img[1] = static_cast<const uint8_t *>(right);
+    f.img_pitch = pitch_bytes;
+    return f;
+}
+static FrameArgs with_depth(FrameArgs f, const void *depth, int depth_pitch_bytes, int fmt, float scale) {
+    f.depth = static_cast<const float *>(depth);
+    f.depth_pitch = depth_pitch_bytes / ((fmt == DEPTH_U16) ? 2 : 4);  // elements inside the kernels
+    f.depth_format = fmt;
+    f.depth_scale = (fmt == DEPTH_U16) ? scale : 0.f;
+    return f;
+}
+static FrameArgs rgbd_args(const void *gray, int gray_pitch, const void *depth, int depth_pitch_bytes, int fmt, float scale) {
+    return with_depth(stereo_args(gray, gray, gray_pitch), depth, depth_pitch_bytes, fmt, scale);  // (eye 1 of an RGB-D sequence: every kernel stands down for it)
+}
+static FrameArgs absent_args() {  // the sequence has no frame in this lock-step step
+    FrameArgs f{};
+    f.absent = 1;
+    return f;
+}
+// lvt_track_with_external_corners; xy: the frame's own lists (a pooled seat's), nullptr: the context's (d_ext[par])
+static FrameArgs with_corners(FrameArgs f, int n_left, int n_right, const float *xy_left = nullptr, const float *xy_right = nullptr) {
+    f.ext_corners = 1;
+    f.n_ext[0] = n_left, f.n_ext[1] = n_right;
+    f.ext_xy[0] = xy_left, f.ext_xy[1] = xy_right;
+    return f;
+}
+// sequence s of ring slot `slot`.  The slot is the caller's to name, and to name LATE: make_room / drain / flush_pending may enqueue the held frame and move enq.
+static FrameArgs &frame_args(Context *c, int slot, int s = 0) { return c->h_fargs[(size_t)slot * c->B + s]; }
+static int next_slot(const Context *c) { return (int)(c->enq % RING); }  // the slot the next enqueue_frame reads
+
 // frame inputs must already be in h_fargs[slot] (and any upload enqueued on stream_f)
 struct HostTimer {
     double *acc;
@@ -856,7 +896,7 @@ static void enqueue_frame(Context *c) {
         c->want_events = false;
         c->switched_at = (long)c->enq;
     }
-    const FrameArgs *fa = c->h_fargs + (size_t)slot * B;
+    const FrameArgs *fa = &frame_args(c, slot);
     const int ext = (B == 1) ? fa[0].ext_corners : 0;  // (a pool's step may mix seats with and without external corners: k_cells is launched, cell_begin skips the seats that bring their own)
     hipStream_t sf = c->stream_f, st = c->stream;
     for (int i = 0; i < Context::PROF_SLOTS; i++) c->ev_used[i] = false;
@@ -865,7 +905,7 @@ static void enqueue_frame(Context *c) {
     //      read last by the feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order
     //      alone covers the hand-over, and the launch needs no gate: it goes out ahead of the buffer gate.
     if (c->n_rect) {
-        FrameArgs *fw = c->h_fargs + (size_t)slot * B;
+        FrameArgs *fw = &frame_args(c, slot);
         RectTable tab;
         std::memset(&tab, 0, sizeof(tab));
         int n = 0, words = 0;
@@ -1116,7 +1156,7 @@ static void flush_pending(Context *c, const NextPull *np = nullptr) {
     Context::PendingFrame &q = c->pend;
     q.valid = false;
     if (!q.pulled) hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, q.src[0], q.src[1], q.dst[0], q.dst[1], c->prm.W, c->prm.H, c->pitch);
-    c->h_fargs[(size_t)(c->enq % RING) * c->B] = q.f;
+    frame_args(c, next_slot(c)) = q.f;
     if (np) c->next_pull = *np, c->fused_pulls++;
     enqueue_frame(c);
     c->next_pull = NextPull{};
@@ -1173,6 +1213,20 @@ static void result_out(Context *c, int s, double R[3][3], double t[3]) {
             for (int j = 0; j < 3; j++) R[i][j] = h.out_R[3 * i + j];
     if (t)
         for (int i = 0; i < 3; i++) t[i] = h.out_t[i];
+}
+
+// the tail of every synchronous call: the frame in the ring's next slot is enqueued, collected right away -- k_triangulate delivers its record itself -- and its pose
+// returned.  sync_call goes back to false on every way out: left standing by a HIP error, it would have the handle's next asynchronous frame claim a delivery it does not make.
+static void track_sync(Context *c, double R[3][3], double t[3]) {
+    {
+        struct Scope {
+            bool &flag;
+            explicit Scope(bool &f) : flag(f) { flag = true; }
+            ~Scope() { flag = false; }
+        } sync(c->sync_call);
+        enqueue_frame(c);
+    }
+    if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
 }
 
 static bool size_ok(Context *c, int rows, int cols) { return rows == c->prm.H && cols == c->prm.W; }
@@ -1317,6 +1371,74 @@ static void auto_destroy(AutoHandle *A) {
 static bool pool_wanted(int) {
     const char *e = std::getenv("LVT_AMD_POOL");
     return e && std::atoi(e) != 0;
+}
+
+// ---- refusals -------------------------------------------------------------------------------------------------------------------------------
+// An entry point resolves its handle, checks everything, and only then enqueues.  A refusal is reported as "who: why" on the context or the seat -- the texts are the
+// entry points' own, callers match on them -- and returns -1.  A handle that is neither a context, a seat nor an automatic handle (NULL included) has nowhere to
+// report to: the call returns (-1 where it returns an int), outputs untouched, without a HIP call.
+static int refuse(lvt_handle h, const char *who, const std::string &why) {
+    const std::string msg = std::string(who) + ": " + why;
+    if (is_slot(h)) {
+        PoolSlot *S = static_cast<PoolSlot *>(h);
+        std::lock_guard<std::mutex> g(S->pool->mu);
+        S->err = msg;
+    } else if (is_ctx(h))
+        static_cast<Context *>(h)->set_error(msg);
+    return -1;
+}
+// what an entry point says to a pooled handle / a handle of the other sensor / a batch handle where it takes solo ones (nullptr: refused without a report)
+struct Refusals {
+    const char *pooled, *sensor, *batch;
+};
+// the context behind a (resolved) handle for an entry point of `sensor` (0: either) that takes solo handles (B == 1, not mixed) or, `batch`, any; nullptr: refused
+static Context *frame_context(lvt_handle h, const char *who, int sensor, bool batch, const Refusals &why = {nullptr, nullptr, nullptr}) {
+    if (is_slot(h)) {
+        if (why.pooled) refuse(h, who, why.pooled);
+        return nullptr;
+    }
+    if (!is_ctx(h)) return nullptr;
+    Context *c = static_cast<Context *>(h);
+    if (sensor && c->sensor != sensor) {
+        if (why.sensor) refuse(h, who, why.sensor);
+        return nullptr;
+    }
+    if (!batch && (c->B != 1 || c->mixed)) {
+        if (why.batch) refuse(h, who, why.batch);
+        return nullptr;
+    }
+    return c;
+}
+
+// ---- host planes ----------------------------------------------------------------------------------------------------------------------------
+// the borrowed buffers are copied into pinned memory by the CPU and the GPU pulls them from there -- unless the caller's
+// buffer already IS pinned host memory (hipHostMalloc / hipHostRegister, aligned to `align`): then the GPU reads it in place
+// (k_stage_in / k_stage_copy never load outside [p, p + bytes): any base address and byte count qualify -- 1241 x 376 bytes are
+//  8 mod 16 -- except a depth image that is not even aligned to its element)
+static const uint8_t *device_view(const void *p, size_t align) {
+    hipPointerAttribute_t a;
+    if (((uintptr_t)p & (align - 1)) == 0 && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer)
+        return static_cast<const uint8_t *>(a.devicePointer);
+    (void)hipGetLastError();  // (an ordinary malloc'ed pointer is "invalid value" to the query: not an error of this call)
+    return nullptr;
+}
+// first use of a staging buffer: [image | image] or [image | depth f32] for planes of n pixels
+static void stage_reserve(Context *c, HostStage &st, size_t n, bool rgbd) {
+    if (st.h) return;
+    st.second = (n + 15) & ~(size_t)15;
+    const size_t second_bytes = rgbd ? ((sizeof(float) * n + 15) & ~(size_t)15) : st.second;
+    HIPCHK(c, hipHostMalloc((void **)&st.h, st.second + second_bytes, hipHostMallocDefault));
+    HIPCHK(c, hipHostGetDevicePointer((void **)&st.dev, st.h, 0));
+}
+// a host plane as the device reads it: its view (device_view) when it is page-locked, otherwise its copy at offset `off` of the staging buffer; counted either way
+static const uint8_t *host_plane(Context *c, const uint8_t *view, const void *src, size_t bytes, const HostStage &st, size_t off) {
+    if (view) {
+        c->planes_in_place++;
+        return view;
+    }
+    std::memcpy(st.h + off, src, bytes);
+    c->planes_staged++;
+    return st.dev + off;
 }
 }  // namespace lvt
 
@@ -1516,41 +1638,41 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     return 1;
 }
 
-LVT_API void lvt_amd_track_device_async(lvt_handle h, const void *d_left, const void *d_right, int n_rows, int n_cols, int pitch_bytes) {
+// lvt_amd_track_device (R, t handed back) and lvt_amd_track_device_async
+static void track_device(lvt_handle h, const void *d_left, const void *d_right, int n_rows, int n_cols, int pitch_bytes, bool sync, double R[3][3], double t[3]) {
+    static const char *who = "lvt_amd_track_device";
     h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
-            (void)slot_submit(static_cast<PoolSlot *>(h), static_cast<const uint8_t *>(d_left), static_cast<const uint8_t *>(d_right), n_rows, n_cols, pitch_bytes, false);
-        } catch (...) {
-        }
-        return;
-    }
-    Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
     try {
-        if (c->sensor != 1) {  // (an RGB-D frame needs a depth plane: lvt_amd_track_rgbd_device[_async])
-            c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
+        if (is_slot(h)) {
+            PoolSlot *S = static_cast<PoolSlot *>(h);
+            if (sync) slot_drain(S);
+            if (slot_submit(S, static_cast<const uint8_t *>(d_left), static_cast<const uint8_t *>(d_right), n_rows, n_cols, pitch_bytes, false) != 0 || !sync) return;
+            (void)slot_collect(S);
+            slot_result(S, R, t);
             return;
         }
+        // (an RGB-D frame needs a depth plane: lvt_amd_track_rgbd_device[_async])
+        Context *c = frame_context(h, who, 1, true, {nullptr, "a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)", nullptr});
+        if (!c) return;
+        DeviceGuard guard(c);
         if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols)) {
-            c->set_error("lvt_amd_track_device: image size / pitch mismatch");
-            return;
+            refuse(h, who, "image size / pitch mismatch");
+            return;  // outputs untouched, like the reference on an exception
         }
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has already been returned: not this caller's to collect)
-        make_room(c);
-        FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B];
-        f.img[0] = static_cast<const uint8_t *>(d_left);
-        f.img[1] = static_cast<const uint8_t *>(d_right);
-        f.depth = nullptr;
-        f.img_pitch = pitch_bytes;
-        f.depth_pitch = 0;
-        f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
-        f.ext_corners = 0;
-        f.absent = 0;
-        f.n_ext[0] = f.n_ext[1] = 0;
-        enqueue_frame(c);
+        if (sync) {
+            drain(c);
+        } else {
+            if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has already been returned: not this caller's to collect)
+            make_room(c);
+        }
+        frame_args(c, next_slot(c)) = stereo_args(d_left, d_right, pitch_bytes);
+        if (sync) track_sync(c, R, t);
+        else enqueue_frame(c);
     } catch (...) {
     }
+}
+LVT_API void lvt_amd_track_device_async(lvt_handle h, const void *d_left, const void *d_right, int n_rows, int n_cols, int pitch_bytes) {
+    track_device(h, d_left, d_right, n_rows, n_cols, pitch_bytes, false, nullptr, nullptr);
 }
 
 // ---- lock-step batch: B independent sequences advance through ONE launch chain (gridDim.z = B) ------------
@@ -1607,19 +1729,14 @@ LVT_API int lvt_amd_batch_size(lvt_handle h) {
 // Everything is checked before anything is enqueued.
 LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *const *d_left, const void *const *d_right, const int *n_rows, const int *n_cols,
                                                    const int *pitch_bytes) {
+    static const char *who = "lvt_amd_batch_track_device_async_mixed";
     h = resolve_handle(h);
-    if (!is_ctx(h)) return -1;
-    Context *c = static_cast<Context *>(h);
+    Context *c = frame_context(h, who, 0, true);
+    if (!c) return -1;
     DeviceGuard guard(c);
     try {
-        if (!d_left || !d_right || !n_rows || !n_cols || !pitch_bytes) {
-            c->set_error("lvt_amd_batch_track_device_async_mixed: NULL argument");
-            return -1;
-        }
-        if (c->sensor != 1) {
-            c->set_error("lvt_amd_batch_track_device_async_mixed: a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)");
-            return -1;
-        }
+        if (!d_left || !d_right || !n_rows || !n_cols || !pitch_bytes) return refuse(h, who, "NULL argument");
+        if (c->sensor != 1) return refuse(h, who, "a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)");
         int present = 0;
         for (int s = 0; s < c->B; s++) {
             if (!d_left[s]) continue;
@@ -1627,28 +1744,14 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             const Params &q = c->seq_prm(s);
             if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
-                std::snprintf(buf, sizeof(buf), "lvt_amd_batch_track_device_async_mixed: sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
+                std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
                               s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->has_rect(s) ? "at least the width" : "a multiple of 16");
-                c->set_error(buf);
-                return -1;
+                return refuse(h, who, buf);
             }
         }
-        if (!present) {
-            c->set_error("lvt_amd_batch_track_device_async_mixed: no sequence has a frame in this step");
-            return -1;
-        }
+        if (!present) return refuse(h, who, "no sequence has a frame in this step");
         make_room(c);
-        for (int s = 0; s < c->B; s++) {
-            FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B + s];
-            f = FrameArgs{};
-            if (!d_left[s]) {
-                f.absent = 1;
-                continue;
-            }
-            f.img[0] = static_cast<const uint8_t *>(d_left[s]);
-            f.img[1] = static_cast<const uint8_t *>(d_right[s]);
-            f.img_pitch = pitch_bytes[s];
-        }
+        for (int s = 0; s < c->B; s++) frame_args(c, next_slot(c), s) = d_left[s] ? stereo_args(d_left[s], d_right[s], pitch_bytes[s]) : absent_args();
         enqueue_frame(c);
         return 0;
     } catch (...) {
@@ -1658,38 +1761,24 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
 
 LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d_left, const void *const *d_right, int n_rows, int n_cols,
                                               int pitch_bytes) {
+    static const char *who = "lvt_amd_batch_track_device";
     h = resolve_handle(h);
-    if (!is_ctx(h)) return;
-    Context *c = static_cast<Context *>(h);
+    Context *c = frame_context(h, who, 1, true, {nullptr, "a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)", nullptr});
+    if (!c) return;
     DeviceGuard guard(c);
     try {
-        if (c->sensor != 1) {
-            c->set_error("lvt_amd_batch_track_device: a stereo entry point on an RGB-D batch (nothing was enqueued; use lvt_amd_batch_track_rgbd_device_async)");
-            return;
-        }
         if (c->mixed) {
-            c->set_error("lvt_amd_batch_track_device: a mixed batch takes its frames through lvt_amd_batch_track_device_async_mixed");
+            refuse(h, who, "a mixed batch takes its frames through lvt_amd_batch_track_device_async_mixed");
             return;
         }
         bool pitch_ok = true;  // (one pitch for the whole step: it must suit the raw and the rectified sequences alike)
         for (int s = 0; s < c->B; s++) pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols);
         if (!size_ok(c, n_rows, n_cols) || !pitch_ok) {
-            c->set_error("lvt_amd_batch_track_device: image size / pitch mismatch");
+            refuse(h, who, "image size / pitch mismatch");
             return;
         }
         make_room(c);
-        for (int s = 0; s < c->B; s++) {
-            FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B + s];
-            f.img[0] = static_cast<const uint8_t *>(d_left[s]);
-            f.img[1] = static_cast<const uint8_t *>(d_right[s]);
-            f.depth = nullptr;
-            f.img_pitch = pitch_bytes;
-            f.depth_pitch = 0;
-            f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
-            f.ext_corners = 0;
-        f.absent = 0;
-            f.n_ext[0] = f.n_ext[1] = 0;
-        }
+        for (int s = 0; s < c->B; s++) frame_args(c, next_slot(c), s) = stereo_args(d_left[s], d_right[s], pitch_bytes);
         enqueue_frame(c);
     } catch (...) {
     }
@@ -1724,52 +1813,28 @@ LVT_API void lvt_amd_batch_get_counts(lvt_handle h, int seq, int out[LVT_AMD_C__
     }
 }
 
-LVT_API void lvt_amd_wait(lvt_handle h, double R[3][3], double t[3]) {
-    h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
-            PoolSlot *S = static_cast<PoolSlot *>(h);
-            (void)slot_collect(S);
-            slot_result(S, R, t);
-        } catch (...) {
-        }
-        return;
-    }
-    Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
-    try {
-        if (c->early_pending) drain(c);
-        if (c->enq - c->done <= 1) flush_pending(c);  // (a held host frame: kept back only while the device has other frames to work on)
-        if (c->done < c->enq) collect_oldest(c);  // FIFO: the oldest frame not yet collected
-        result_out(c, 0, R, t);
-    } catch (...) {
-    }
-}
-
 LVT_API int lvt_amd_wait_status(lvt_handle h, double R[3][3], double t[3]) {  // lvt_amd_wait + the tracking state AFTER that frame (1 / 2 / 3; -1: error)
     h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
+    try {
+        if (is_slot(h)) {
             PoolSlot *S = static_cast<PoolSlot *>(h);
             (void)slot_collect(S);
             slot_result(S, R, t);
             return S->last.rec.state;
-        } catch (...) {
         }
-        return -1;
-    }
-    Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
-    try {
+        Context *c = frame_context(h, "lvt_amd_wait", 0, true);
+        if (!c) return -1;
+        DeviceGuard guard(c);
         if (c->early_pending) drain(c);
-        if (c->enq - c->done <= 1) flush_pending(c);
-        if (c->done < c->enq) collect_oldest(c);
+        if (c->enq - c->done <= 1) flush_pending(c);  // (a held host frame: kept back only while the device has other frames to work on)
+        if (c->done < c->enq) collect_oldest(c);  // FIFO: the oldest frame not yet collected
         result_out(c, 0, R, t);
         return last_ctl(c).state;
     } catch (...) {
     }
     return -1;
 }
+LVT_API void lvt_amd_wait(lvt_handle h, double R[3][3], double t[3]) { (void)lvt_amd_wait_status(h, R, t); }
 
 // lvt_amd_wait_status with the pose as the tracker holds it (quaternion w x y z + position) instead of R, t: what lvt_system::track returns
 LVT_API int lvt_amd_wait_pose(lvt_handle h, double q_wxyz[4], double p[3]) {
@@ -1788,44 +1853,15 @@ LVT_API int lvt_amd_wait_pose(lvt_handle h, double q_wxyz[4], double p[3]) {
 
 LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *d_right, int n_rows, int n_cols, int pitch_bytes,
                                   double R[3][3], double t[3]) {
-    h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
-            PoolSlot *S = static_cast<PoolSlot *>(h);
-            slot_drain(S);
-            if (slot_submit(S, static_cast<const uint8_t *>(d_left), static_cast<const uint8_t *>(d_right), n_rows, n_cols, pitch_bytes, false) != 0) return;
-            (void)slot_collect(S);
-            slot_result(S, R, t);
-        } catch (...) {
-        }
-        return;
-    }
-    Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
-    if (c->sensor != 1) {
-        c->set_error("lvt_amd_track_device: a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)");
-        return;
-    }
-    if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols)) {
-        c->set_error("lvt_amd_track_device: image size / pitch mismatch");
-        return;  // outputs untouched, like the reference on an exception
-    }
-    try {
-        drain(c);
-        c->sync_call = true;  // collected right away: k_triangulate delivers the record itself
-        lvt_amd_track_device_async(h, d_left, d_right, n_rows, n_cols, pitch_bytes);
-        c->sync_call = false;
-        if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
-    } catch (...) {
-    }
+    track_device(h, d_left, d_right, n_rows, n_cols, pitch_bytes, true, R, t);
 }
 
-// (dfmt / dscale: element format of an RGB-D frame's depth plane `second` and metres per raw unit of a 16-bit one)
-static void upload_and_track(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols, int ext,
+// (dfmt / dscale: element format of an RGB-D frame's depth plane `second` and metres per raw unit of a 16-bit one; cl / cr: external corner lists, nullptr: none)
+static void upload_and_track(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols,
                              const float *cl, int ncl, const float *cr, int ncr, double R[3][3], double t[3], int dfmt = DEPTH_F32, float dscale = 0.f) {
     const size_t desz = (dfmt == DEPTH_U16) ? sizeof(uint16_t) : sizeof(float);
     if (!size_ok(c, n_rows, n_cols)) {
-        c->set_error("lvt_track: image size differs from the configured img_width/img_height");
+        refuse(c, "lvt_track", "image size differs from the configured img_width/img_height");
         return;
     }
     // (the previous synchronous call may have returned on its early pose: its frame's tail -- staged update, triangulation -- runs
@@ -1834,64 +1870,30 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     const int par = (int)(c->enq % NPAR);
     hipStream_t sf = c->stream_f;
     const size_t nbytes = (size_t)n_rows * n_cols;
-    if (!c->h_stage[par]) {  // first host-buffer call: [image | image] or [image | depth f32], each part padded to 16 B
-        c->stage_img = (nbytes + 15) & ~(size_t)15;
-        const size_t second_bytes = rgbd ? ((sizeof(float) * nbytes + 15) & ~(size_t)15) : c->stage_img;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_stage[par], c->stage_img + second_bytes, hipHostMallocDefault));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_stage_dev[par], c->h_stage[par], 0));
-    }
-    // the borrowed buffers are copied into pinned memory by the CPU and the GPU pulls them from there -- unless the caller's
-    // buffer already IS pinned host memory (hipHostMalloc / hipHostRegister, 16-byte aligned): then the GPU reads it in place
-    // (this call only returns after the frame has been tracked, so the buffer outlives every read)
-    // (k_stage_in / k_stage_copy never load outside [p, p + bytes): any base address and byte count qualify -- 1241 x 376 bytes are
-    //  8 mod 16 -- except a depth image that is not even float-aligned)
-    auto device_view = [](const void *p, size_t align) -> const uint8_t * {
-        hipPointerAttribute_t a;
-        if (((uintptr_t)p & (align - 1)) == 0 && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer)
-            return static_cast<const uint8_t *>(a.devicePointer);
-        (void)hipGetLastError();  // (an ordinary malloc'ed pointer is "invalid value" to the query: not an error of this call)
-        return nullptr;
-    };
-    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? desz : 1);
-    c->planes_in_place += (s0 != nullptr) + (s1 != nullptr);
-    c->planes_staged += (s0 == nullptr) + (s1 == nullptr);
+    const HostStage &stg = c->stage[par];
+    stage_reserve(c, c->stage[par], nbytes, rgbd);
+    // (this call only returns after the frame has been tracked, so a page-locked buffer read in place outlives every read)
+    const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
     // The pulls are launched BEFORE the previous frame is collected: this frame's image planes (parity `par`) and staging buffer were last used NPAR
     // frames ago, and what may still be running -- the tail of the previous synchronous call, which returned on its early pose -- reads neither.
     // Two pageable images: the left one is pulled while the CPU still copies the right one.
-    const bool split = !rgbd && !s0 && !s1;
-    if (!s0) {
-        std::memcpy(c->h_stage[par], left, nbytes);
-        s0 = c->h_stage_dev[par];
-    }
+    const bool split = !rgbd && !v0 && !v1;
+    const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0), *s1 = v1;  // (an RGB-D frame's second plane goes later: before_gather)
     if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s0, s0, c->d_img[par][0], c->d_img[par][0], n_cols, n_rows, c->pitch);
-    if (!s1 && !rgbd) {
-        std::memcpy(c->h_stage[par] + c->stage_img, second, nbytes);
-        s1 = c->h_stage_dev[par] + c->stage_img;
-    }
+    if (!rgbd) s1 = host_plane(c, v1, second, nbytes, stg, stg.second);
     if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s1, s1, c->d_img[par][1], c->d_img[par][1], n_cols, n_rows, c->pitch);
     else hipLaunchKernelGGL(k_stage_in, dim3(128, rgbd ? 1 : 2), dim3(256), 0, sf, s0, s1, c->d_img[par][0], c->d_img[par][1], n_cols, n_rows, c->pitch);
     drain(c);
-    FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B];
-    f.img[0] = c->d_img[par][0];
-    f.img[1] = c->d_img[par][1];
-    f.img_pitch = c->pitch;
-    f.depth = nullptr;
-    f.depth_pitch = 0;
-    f.depth_format = DEPTH_F32, f.depth_scale = 0.f;
+    FrameArgs f = stereo_args(c->d_img[par][0], c->d_img[par][1], c->pitch);
     if (rgbd) {
         // The depth plane (1.2 MB: ~60 us of CPU copy into the staging buffer when the caller's buffer is pageable, ~45 us of PCIe pull)
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
         // host while the GPU runs them, the pull on the early stream (idle until this frame's features exist) beside them -- and
         // the feature stream waits for the pull in front of k_gather.  (A 16-bit plane: half those bytes, both ways; it stays 16-bit in d_depth.)
-        f.depth = c->d_depth[par];
-        f.depth_pitch = n_cols;
-        f.depth_format = dfmt, f.depth_scale = dscale;
-        c->before_gather = [c, s1, second, nbytes, par, sf, dfmt, desz]() {
-            const uint8_t *src = s1;
-            if (!src) {
-                std::memcpy(c->h_stage[par] + c->stage_img, second, desz * nbytes);
-                src = c->h_stage_dev[par] + c->stage_img;
-            }
+        f = with_depth(f, c->d_depth[par], n_cols * (int)desz, dfmt, dscale);
+        // (runs inside enqueue_frame: everything it needs travels by value, nothing is read that enqueue_frame advances)
+        c->before_gather = [c, v1, second, nbytes, par, sf, dfmt, desz]() {
+            const uint8_t *src = host_plane(c, v1, second, desz * nbytes, c->stage[par], c->stage[par].second);
             hipStream_t sd = c->events_only ? sf : c->stream_e;
             launch_stage_copy(sd, src, c->d_depth[par], nbytes, dfmt);
             if (sd != sf) {
@@ -1900,19 +1902,13 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
             }
         };
     }
-    f.ext_corners = ext;
-    f.ext_xy[0] = f.ext_xy[1] = nullptr;  // (the context's own lists, d_ext[par])
-    f.absent = 0;
-    f.n_ext[0] = ncl;
-    f.n_ext[1] = ncr;
-    if (ext) {
+    if (cl) {  // (the context's own lists, d_ext[par])
+        f = with_corners(f, ncl, ncr);
         if (ncl) HIPCHK(c, hipMemcpyAsync(c->d_ext[par][0], cl, sizeof(float) * 2 * (size_t)ncl, hipMemcpyHostToDevice, sf));
         if (ncr) HIPCHK(c, hipMemcpyAsync(c->d_ext[par][1], cr, sizeof(float) * 2 * (size_t)ncr, hipMemcpyHostToDevice, sf));
     }
-    c->sync_call = true;  // collected right away: k_triangulate delivers the record itself
-    enqueue_frame(c);
-    c->sync_call = false;
-    if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
+    frame_args(c, next_slot(c)) = f;
+    track_sync(c, R, t);
 }
 
 // Asynchronous counterpart of upload_and_track (lvt_amd_track_async / lvt_amd_track_rgbd_async): borrowed HOST images, the frame is enqueued and the
@@ -1924,15 +1920,11 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
 // head of its feature stage (k_stage_in), as every RGB-D frame does.
 // Returns 0 when the frame was enqueued, -1 when it was rejected (nothing enqueued; lvt_amd_last_error says why).
 static int upload_async(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols, int dfmt = DEPTH_F32, float dscale = 0.f) {
+    static const char *who = "lvt_amd_track_async";
     const size_t desz = (dfmt == DEPTH_U16) ? sizeof(uint16_t) : sizeof(float);
-    if (c->B != 1 || (rgbd ? c->sensor != 2 : c->sensor != 1)) {
-        c->set_error("lvt_amd_track_async: wrong sensor type for this entry point (or a batch handle)");
-        return -1;
-    }
-    if (!left || !second || !size_ok(c, n_rows, n_cols)) {
-        c->set_error("lvt_amd_track_async: image size differs from the configured img_width/img_height (the frame was NOT enqueued)");
-        return -1;
-    }
+    if (c->B != 1 || (rgbd ? c->sensor != 2 : c->sensor != 1)) return refuse(c, who, "wrong sensor type for this entry point (or a batch handle)");
+    if (!left || !second || !size_ok(c, n_rows, n_cols))
+        return refuse(c, who, "image size differs from the configured img_width/img_height (the frame was NOT enqueued)");
     if (c->early_pending) drain(c);
     if (rgbd) flush_pending(c);
     const int held = c->pend.valid ? 1 : 0;  // (the held frame owns slot enq % RING)
@@ -1945,33 +1937,14 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
             if (rgbd) c->d_depth_ring[r] = c->dalloc<float>(nbytes + 4);
         }
     }
-    auto device_view = [](const void *p, size_t align) -> const uint8_t * {
-        hipPointerAttribute_t a;
-        if (((uintptr_t)p & (align - 1)) == 0 && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer)
-            return static_cast<const uint8_t *>(a.devicePointer);
-        (void)hipGetLastError();
-        return nullptr;
-    };
-    const uint8_t *s0 = device_view(left, 1), *s1 = device_view(second, rgbd ? desz : 1);
-    c->planes_in_place += (s0 != nullptr) + (s1 != nullptr);
-    c->planes_staged += (s0 == nullptr) + (s1 == nullptr);
-    const size_t img_b = (nbytes + 15) & ~(size_t)15, second_b = rgbd ? ((sizeof(float) * nbytes + 15) & ~(size_t)15) : img_b;
-    if ((!s0 || !s1) && !c->h_stage_ring[slot]) {
-        c->stage_ring_bytes = img_b + second_b;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_stage_ring[slot], c->stage_ring_bytes, hipHostMallocDefault));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_stage_ring_dev[slot], c->h_stage_ring[slot], 0));
-    }
+    const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
+    HostStage &stg = c->stage_ring[slot];
+    if (!v0 || !v1) stage_reserve(c, stg, nbytes, rgbd);
     hipStream_t sp = c->stream_f;
     uint8_t *d0 = c->d_img_ring[slot][0], *d1 = c->d_img_ring[slot][1];
+    const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0);
     if (!rgbd) {
-        if (!s0) {
-            std::memcpy(c->h_stage_ring[slot], left, nbytes);
-            s0 = c->h_stage_ring_dev[slot];
-        }
-        if (!s1) {
-            std::memcpy(c->h_stage_ring[slot] + img_b, second, nbytes);
-            s1 = c->h_stage_ring_dev[slot] + img_b;
-        }
+        const uint8_t *s1 = host_plane(c, v1, second, nbytes, stg, stg.second);
         // the frame held so far goes out now, and its k_cells launch pulls THIS frame's images beside its cells
         const bool carried = c->pend.valid && c->fuse_pull;
         if (c->pend.valid) {
@@ -1981,34 +1954,14 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
         Context::PendingFrame &q = c->pend;
         q.valid = true, q.pulled = carried;
         q.src[0] = s0, q.src[1] = s1, q.dst[0] = d0, q.dst[1] = d1;
-        q.f = FrameArgs{};
-        q.f.img[0] = d0, q.f.img[1] = d1;
-        q.f.img_pitch = c->pitch;
+        q.f = stereo_args(d0, d1, c->pitch);
         c->async_frames++;
         if (!c->fuse_pull) flush_pending(c);
         return 0;
-    } else {
-        if (!s0) {
-            std::memcpy(c->h_stage_ring[slot], left, nbytes);
-            s0 = c->h_stage_ring_dev[slot];
-        }
-        hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, n_cols, n_rows, c->pitch);
-        if (!s1) {
-            std::memcpy(c->h_stage_ring[slot] + img_b, second, desz * nbytes);
-            s1 = c->h_stage_ring_dev[slot] + img_b;
-        }
-        launch_stage_copy(sp, s1, c->d_depth_ring[slot], nbytes, dfmt);
     }
-    FrameArgs &f = c->h_fargs[(size_t)slot * c->B];
-    f.img[0] = d0;
-    f.img[1] = rgbd ? d0 : d1;
-    f.img_pitch = c->pitch;
-    f.depth = rgbd ? c->d_depth_ring[slot] : nullptr;
-    f.depth_pitch = rgbd ? n_cols : 0;
-    f.depth_format = rgbd ? dfmt : DEPTH_F32, f.depth_scale = rgbd ? dscale : 0.f;
-    f.ext_corners = 0;
-    f.absent = 0;
-    f.n_ext[0] = f.n_ext[1] = 0;
+    hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, n_cols, n_rows, c->pitch);
+    launch_stage_copy(sp, host_plane(c, v1, second, desz * nbytes, stg, stg.second), c->d_depth_ring[slot], nbytes, dfmt);
+    frame_args(c, slot) = rgbd_args(d0, c->pitch, c->d_depth_ring[slot], n_cols * (int)desz, dfmt, dscale);
     c->async_frames++;
     enqueue_frame(c);
     return 0;
@@ -2016,17 +1969,11 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
 
 LVT_API int lvt_amd_track_async(lvt_handle h, const unsigned char *left, const unsigned char *right, int n_rows, int n_cols) {
     h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
-            return slot_submit(static_cast<PoolSlot *>(h), left, right, n_rows, n_cols, 0, true);
-        } catch (...) {
-        }
-        return -1;
-    }
-    Context *c = static_cast<Context *>(h);
-    if (!c) return -1;
-    DeviceGuard guard(c);
     try {
+        if (is_slot(h)) return slot_submit(static_cast<PoolSlot *>(h), left, right, n_rows, n_cols, 0, true);
+        Context *c = frame_context(h, "lvt_amd_track_async", 0, true);
+        if (!c) return -1;
+        DeviceGuard guard(c);
         return upload_async(c, left, right, false, n_rows, n_cols);
     } catch (...) {
     }
@@ -2034,8 +1981,8 @@ LVT_API int lvt_amd_track_async(lvt_handle h, const unsigned char *left, const u
 }
 LVT_API int lvt_amd_track_rgbd_async(lvt_handle h, const unsigned char *gray, const float *depth, int n_rows, int n_cols) {
     h = resolve_handle(h);
-    Context *c = static_cast<Context *>(h);
-    if (!c || !is_ctx(h)) return -1;
+    Context *c = frame_context(h, "lvt_amd_track_async", 0, true);
+    if (!c) return -1;
     DeviceGuard guard(c);
     try {
         return upload_async(c, gray, depth, true, n_rows, n_cols);
@@ -2046,22 +1993,19 @@ LVT_API int lvt_amd_track_rgbd_async(lvt_handle h, const unsigned char *gray, co
 
 LVT_API void lvt_track(lvt_handle h, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double R[3][3], double t[3]) {
     h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
+    try {
+        if (is_slot(h)) {
             PoolSlot *S = static_cast<PoolSlot *>(h);
             slot_drain(S);
             if (slot_submit(S, left, right, n_rows, n_cols, 0, true) != 0) return;  // outputs untouched, like the reference on an exception
             (void)slot_collect(S);
             slot_result(S, R, t);
-        } catch (...) {
+            return;
         }
-        return;
-    }
-    Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
-    try {
-        if (c->sensor != 1) return;  // the reference cannot run RGB-D through this entry either
-        upload_and_track(c, left, right, false, n_rows, n_cols, 0, nullptr, 0, nullptr, 0, R, t);
+        Context *c = frame_context(h, "lvt_track", 1, true);  // the reference cannot run RGB-D through this entry either
+        if (!c) return;
+        DeviceGuard guard(c);
+        upload_and_track(c, left, right, false, n_rows, n_cols, nullptr, 0, nullptr, 0, R, t);
     } catch (...) {
     }
 }
@@ -2069,45 +2013,22 @@ LVT_API void lvt_track(lvt_handle h, unsigned char *left, unsigned char *right, 
 LVT_API void lvt_amd_track_rgbd(lvt_handle h, const unsigned char *gray, const float *depth, int n_rows, int n_cols, double R[3][3],
                                 double t[3]) {
     h = resolve_handle(h);
-    if (!is_ctx(h)) return;
-    Context *c = static_cast<Context *>(h);
+    Context *c = frame_context(h, "lvt_amd_track_rgbd", 2, true);
+    if (!c) return;
     DeviceGuard guard(c);
     try {
-        if (c->sensor != 2) return;
-        upload_and_track(c, gray, depth, true, n_rows, n_cols, 0, nullptr, 0, nullptr, 0, R, t);
+        upload_and_track(c, gray, depth, true, n_rows, n_cols, nullptr, 0, nullptr, 0, R, t);
     } catch (...) {
     }
 }
 
 // ---- RGB-D beyond the two host fp32 calls: planes already in HBM, 16-bit depth, lock-step batches -------------------------------------------
 // Every call checks everything before it enqueues anything: 0 = enqueued / tracked, -1 = refused, NOTHING enqueued, the reason in lvt_amd_last_error.
-static int rgbd_refuse(lvt_handle h, const char *who, const std::string &why) {
-    const std::string msg = std::string(who) + ": " + why + " (nothing was enqueued)";
-    if (is_slot(h)) {
-        PoolSlot *S = static_cast<PoolSlot *>(h);
-        std::lock_guard<std::mutex> g(S->pool->mu);
-        S->err = msg;
-    } else if (is_ctx(h))
-        static_cast<Context *>(h)->set_error(msg);
-    return -1;
-}
+static int rgbd_refuse(lvt_handle h, const char *who, const std::string &why) { return refuse(h, who, why + " (nothing was enqueued)"); }
 // the handle must be a solo (B == 1) or batch (B > 1 or mixed) RGB-D context
 static Context *rgbd_context(lvt_handle h, const char *who, bool batch) {
-    if (is_slot(h)) {
-        rgbd_refuse(h, who, "a pooled handle (pooled handles are stereo only)");
-        return nullptr;
-    }
-    if (!is_ctx(h)) return nullptr;
-    Context *c = static_cast<Context *>(h);
-    if (c->sensor != 2) {
-        rgbd_refuse(h, who, "an RGB-D entry point on a stereo handle");
-        return nullptr;
-    }
-    if (!batch && (c->B != 1 || c->mixed)) {
-        rgbd_refuse(h, who, "a batch handle takes its frames through lvt_amd_batch_track_rgbd_device_async");
-        return nullptr;
-    }
-    return c;
+    return frame_context(h, who, 2, batch, {"a pooled handle (pooled handles are stereo only) (nothing was enqueued)", "an RGB-D entry point on a stereo handle (nothing was enqueued)",
+                                            "a batch handle takes its frames through lvt_amd_batch_track_rgbd_device_async (nothing was enqueued)"});
 }
 static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale) {
     if (fmt != DEPTH_F32 && fmt != DEPTH_U16) {
@@ -2139,18 +2060,10 @@ static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gr
     }
     return "";
 }
-static void rgbd_fill(FrameArgs &f, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, float scale) {
-    f = FrameArgs{};
-    f.img[0] = f.img[1] = static_cast<const uint8_t *>(d_gray);  // (eye 1 of an RGB-D sequence: every kernel stands down for it)
-    f.img_pitch = gray_pitch;
-    f.depth = static_cast<const float *>(d_depth);
-    f.depth_pitch = depth_pitch / ((fmt == DEPTH_U16) ? 2 : 4);  // elements inside the kernels
-    f.depth_format = fmt;
-    f.depth_scale = (fmt == DEPTH_U16) ? scale : 0.f;
-}
 
-LVT_API int lvt_amd_track_rgbd_device_async(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
-                                            float depth_scale, int n_rows, int n_cols) {
+// lvt_amd_track_rgbd_device (R, t handed back) and lvt_amd_track_rgbd_device_async
+static int track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format, float depth_scale,
+                             int n_rows, int n_cols, bool sync, double R[3][3], double t[3]) {
     static const char *who = "lvt_amd_track_rgbd_device";
     h = resolve_handle(h);
     Context *c = rgbd_context(h, who, false);
@@ -2160,36 +2073,27 @@ LVT_API int lvt_amd_track_rgbd_device_async(lvt_handle h, const void *d_gray, in
         if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
         const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols);
         if (!why.empty()) return rgbd_refuse(h, who, why);
-        if (c->early_pending) drain(c);
-        make_room(c);
-        rgbd_fill(c->h_fargs[(size_t)(c->enq % RING) * c->B], d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale);
-        enqueue_frame(c);
+        if (sync) {
+            drain(c);
+        } else {
+            if (c->early_pending) drain(c);
+            make_room(c);
+        }
+        frame_args(c, next_slot(c)) = rgbd_args(d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale);
+        if (sync) track_sync(c, R, t);
+        else enqueue_frame(c);
         return 0;
     } catch (...) {
     }
     return -1;
+}
+LVT_API int lvt_amd_track_rgbd_device_async(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
+                                            float depth_scale, int n_rows, int n_cols) {
+    return track_rgbd_device(h, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale, n_rows, n_cols, false, nullptr, nullptr);
 }
 LVT_API int lvt_amd_track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_bytes, const void *d_depth, int depth_pitch_bytes, int depth_format,
                                       float depth_scale, int n_rows, int n_cols, double R[3][3], double t[3]) {
-    static const char *who = "lvt_amd_track_rgbd_device";
-    h = resolve_handle(h);
-    Context *c = rgbd_context(h, who, false);
-    if (!c) return -1;
-    DeviceGuard guard(c);
-    try {
-        if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
-        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols);
-        if (!why.empty()) return rgbd_refuse(h, who, why);
-        drain(c);
-        rgbd_fill(c->h_fargs[(size_t)(c->enq % RING) * c->B], d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale);
-        c->sync_call = true;  // collected right away: k_triangulate delivers the record itself
-        enqueue_frame(c);
-        c->sync_call = false;
-        if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
-        return 0;
-    } catch (...) {
-    }
-    return -1;
+    return track_rgbd_device(h, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, depth_scale, n_rows, n_cols, true, R, t);
 }
 
 // HOST buffers with 16-bit depth (what the sensor delivers: TUM's PNGs are uint16 at 1/5000 m), tightly packed like lvt_amd_track_rgbd's: the staging copy
@@ -2215,7 +2119,7 @@ LVT_API int lvt_amd_track_rgbd16(lvt_handle h, const unsigned char *gray, const 
     if (!c) return -1;
     DeviceGuard guard(c);
     try {
-        upload_and_track(c, gray, depth16, true, n_rows, n_cols, 0, nullptr, 0, nullptr, 0, R, t, DEPTH_U16, depth_scale);
+        upload_and_track(c, gray, depth16, true, n_rows, n_cols, nullptr, 0, nullptr, 0, R, t, DEPTH_U16, depth_scale);
         return 0;
     } catch (...) {
     }
@@ -2253,15 +2157,8 @@ LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *cons
         }
         if (!present) return rgbd_refuse(h, who, "no sequence has a frame in this step");
         make_room(c);
-        for (int s = 0; s < c->B; s++) {
-            FrameArgs &f = c->h_fargs[(size_t)(c->enq % RING) * c->B + s];
-            if (!d_gray[s]) {
-                f = FrameArgs{};
-                f.absent = 1;
-                continue;
-            }
-            rgbd_fill(f, d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, depth_scale);
-        }
+        for (int s = 0; s < c->B; s++)
+            frame_args(c, next_slot(c), s) = d_gray[s] ? rgbd_args(d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, depth_scale) : absent_args();
         enqueue_frame(c);
         return 0;
     } catch (...) {
@@ -2304,33 +2201,30 @@ LVT_API void lvt_track_with_external_corners(lvt_handle h, unsigned char *left, 
             slot_result(S, R, t);
             return;
         }
-        Context *c = static_cast<Context *>(h);
+        Context *c = frame_context(h, "lvt_track_with_external_corners", 1, true);
+        if (!c) return;
         DeviceGuard guard(c);
-        if (c->sensor != 1) return;
         if (c->has_rect(0)) {  // the images would be raw, the corners in rectified coordinates the caller does not have
-            c->set_error("lvt_track_with_external_corners: refused on a handle with rectifiers attached (the frame was NOT tracked; detach them with lvt_amd_set_rectifiers(h, NULL, NULL))");
+            refuse(h, "lvt_track_with_external_corners", "refused on a handle with rectifiers attached (the frame was NOT tracked; detach them with lvt_amd_set_rectifiers(h, NULL, NULL))");
             return;
         }
         if (cut[0]) c->set_error(cut);
-        upload_and_track(c, left, right, false, n_rows, n_cols, 1, cl.data(), ncl, cr.data(), ncr, R, t);
+        upload_and_track(c, left, right, false, n_rows, n_cols, cl.data(), ncl, cr.data(), ncr, R, t);
     } catch (...) {
     }
 }
 
 LVT_API int lvt_get_status(lvt_handle h) {
     h = resolve_handle(h);
-    if (is_slot(h)) {
-        try {
+    try {
+        if (is_slot(h)) {
             PoolSlot *S = static_cast<PoolSlot *>(h);
             slot_drain(S);
             return S->last.rec.state;
-        } catch (...) {
         }
-        return -1;
-    }
-    try {
-        Context *c = static_cast<Context *>(h);
-    DeviceGuard guard(c);
+        Context *c = frame_context(h, "lvt_get_status", 0, true);
+        if (!c) return -1;
+        DeviceGuard guard(c);
         drain(c);
         return last_ctl(c).state;
     } catch (...) {
@@ -2789,24 +2683,15 @@ LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier h, float *map1, float *
 
 // ---- raw frames: rectifiers attached to a tracker (Context::rect) -------------------------------------------------------------------------
 // Everything is checked before anything changes: 0 = attached / detached, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
-static int rect_refuse(lvt_handle h, const std::string &why) {
-    const std::string msg = "lvt_amd_set_rectifiers: " + why + " (nothing was changed)";
-    if (is_slot(h)) {
-        PoolSlot *S = static_cast<PoolSlot *>(h);
-        std::lock_guard<std::mutex> g(S->pool->mu);
-        S->err = msg;
-    } else if (is_ctx(h))
-        static_cast<Context *>(h)->set_error(msg);
-    return -1;
-}
+static int rect_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_rectifiers", why + " (nothing was changed)"); }
 static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
-    if (is_slot(h)) return rect_refuse(h, "a pooled handle (its frames ride a chain shared with other handles)");
-    if (!is_ctx(h)) return -1;
-    Context *c = static_cast<Context *>(h);
+    Context *c = frame_context(h, "lvt_amd_set_rectifiers", 1, batch_call,
+                               {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)",
+                                "an RGB-D handle (there is one image, and its depth plane is registered to it) (nothing was changed)",
+                                "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers (nothing was changed)"});
+    if (!c) return -1;
     DeviceGuard guard(c);
     try {
-        if (c->sensor != 1) return rect_refuse(h, "an RGB-D handle (there is one image, and its depth plane is registered to it)");
-        if (!batch_call && (c->B != 1 || c->mixed)) return rect_refuse(h, "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers");
         if (seq < 0 || seq >= c->B) return rect_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
         if ((left == nullptr) != (right == nullptr)) return rect_refuse(h, "one rectifier is NULL (both, or NULL, NULL to detach)");
         Rectifier *rl = static_cast<Rectifier *>(left), *rr = static_cast<Rectifier *>(right);

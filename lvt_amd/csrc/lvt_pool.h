@@ -107,37 +107,24 @@ static void pool_enqueue_step(Pool *P, std::unique_lock<std::mutex> &lk) {
     bool failed = false;
     try {
         make_room(c);  // (POOL_DEPTH < RING - 1: never blocks)
-        const int par_slot = (int)(c->enq % RING);
         for (int s = 0; s < POOL_SLOTS; s++) {
-            FrameArgs &f = c->h_fargs[(size_t)par_slot * c->B + s];
-            std::memset(&f, 0, sizeof(f));
-            if (!(mask & (1u << s))) {
-                f.absent = 1;
-                continue;
-            }
-            const PoolSlot::Pending &p = take[s];
-            if (p.host) {  // pull this slot's staged images over PCIe at the head of the step's feature stage
+            FrameArgs f = absent_args();
+            if (mask & (1u << s)) {
+                const PoolSlot::Pending &p = take[s];
                 PoolSlot *S = P->slots[s];
-                const int rows = c->prm.H, cols = c->prm.W;
-                hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, S->h_stage_dev[p.stage], S->h_stage_dev[p.stage] + S->stage_img,
-                                   S->d_img[p.stage][0], S->d_img[p.stage][1], cols, rows, c->pitch);
-                f.img[0] = S->d_img[p.stage][0], f.img[1] = S->d_img[p.stage][1];
-                f.img_pitch = c->pitch;
-            } else {
-                f.img[0] = p.img[0], f.img[1] = p.img[1];
-                f.img_pitch = p.pitch;
-            }
-            if (p.ext) {  // the corner lists travel with the frame: copied from the slot's pinned list into its device lists in front of the feature stage
-                PoolSlot *S = P->slots[s];
-                f.ext_corners = 1;
-                for (int e = 0; e < 2; e++) {
-                    f.n_ext[e] = p.n_ext[e];
-                    f.ext_xy[e] = S->d_ext[p.stage][e];
-                    if (p.n_ext[e])
-                        HIPCHK(c, hipMemcpyAsync(S->d_ext[p.stage][e], S->h_ext[p.stage] + (size_t)e * 2 * EXT_MAX, sizeof(float) * 2 * (size_t)p.n_ext[e],
-                                                 hipMemcpyHostToDevice, c->stream_f));
+                if (p.host)  // pull this slot's staged images over PCIe at the head of the step's feature stage
+                    hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, S->h_stage_dev[p.stage], S->h_stage_dev[p.stage] + S->stage_img,
+                                       S->d_img[p.stage][0], S->d_img[p.stage][1], c->prm.W, c->prm.H, c->pitch);
+                f = p.host ? stereo_args(S->d_img[p.stage][0], S->d_img[p.stage][1], c->pitch) : stereo_args(p.img[0], p.img[1], p.pitch);
+                if (p.ext) {  // the corner lists travel with the frame: copied from the slot's pinned list into its device lists in front of the feature stage
+                    f = with_corners(f, p.n_ext[0], p.n_ext[1], S->d_ext[p.stage][0], S->d_ext[p.stage][1]);
+                    for (int e = 0; e < 2; e++)
+                        if (p.n_ext[e])
+                            HIPCHK(c, hipMemcpyAsync(S->d_ext[p.stage][e], S->h_ext[p.stage] + (size_t)e * 2 * EXT_MAX, sizeof(float) * 2 * (size_t)p.n_ext[e],
+                                                     hipMemcpyHostToDevice, c->stream_f));
                 }
             }
+            frame_args(c, next_slot(c), s) = f;
         }
         enqueue_frame(c);
     } catch (...) {

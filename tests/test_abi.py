@@ -45,6 +45,56 @@ def test_no_cpu_fallback_without_gpu(hip_lib):
         lvt_amd.LvtSystem.create(lvt_amd.kitti_params(), 1)
 
 
+def test_no_handle_is_refused_by_every_frame_and_wait_entry_point(hip_lib):
+    """a NULL handle, and memory that is neither a context, a seat nor an automatic handle: every entry point that takes a frame or waits for one
+    returns (-1 where it returns an int) with R and t untouched, without a device"""
+    import numpy as np
+    L = hip_lib.load_library()
+    vp = ctypes.c_void_p
+    gray = np.zeros((8, 16), np.uint8); d32 = np.zeros((8, 16), np.float32); d16 = np.zeros((8, 16), np.uint16)
+    corners = np.zeros((4, 2)); q = np.zeros(4)
+    p = lambda a: a.ctypes.data_as(vp)  # noqa: E731  (host addresses stand in for device pointers: the handle is refused before any is looked at)
+    one, ptr1 = (ctypes.c_int * 1), (vp * 1)
+    s = 1.0 / 5000.0
+    not_a_handle = np.zeros(64, np.uint64)
+    for h in (None, p(not_a_handle)):
+        R = np.zeros((3, 3)); t = np.zeros(3); st = np.full(1, 7, np.int32)
+        void_calls = {
+            "lvt_track": lambda: L.lvt_track(h, p(gray), p(gray), 8, 16, p(R), p(t)),
+            "lvt_track_with_external_corners": lambda: L.lvt_track_with_external_corners(h, p(gray), p(gray), 8, 16, p(corners), 4, p(corners), 4, p(R), p(t)),
+            "lvt_amd_track_rgbd": lambda: L.lvt_amd_track_rgbd(h, p(gray), p(d32), 8, 16, p(R), p(t)),
+            "lvt_amd_track_device": lambda: L.lvt_amd_track_device(h, p(gray), p(gray), 8, 16, 16, p(R), p(t)),
+            "lvt_amd_track_device_async": lambda: L.lvt_amd_track_device_async(h, p(gray), p(gray), 8, 16, 16),
+            "lvt_amd_wait": lambda: L.lvt_amd_wait(h, p(R), p(t)),
+            "lvt_amd_batch_track_device_async": lambda: L.lvt_amd_batch_track_device_async(h, ptr1(gray.ctypes.data), ptr1(gray.ctypes.data), 8, 16, 16),
+            "lvt_amd_batch_wait": lambda: L.lvt_amd_batch_wait(h, p(R), p(t), p(st)),
+        }
+        int_calls = {
+            "lvt_get_status": lambda: L.lvt_get_status(h),
+            "lvt_amd_wait_status": lambda: L.lvt_amd_wait_status(h, p(R), p(t)),
+            "lvt_amd_wait_pose": lambda: L.lvt_amd_wait_pose(h, p(q), p(t)),
+            "lvt_amd_track_async": lambda: L.lvt_amd_track_async(h, p(gray), p(gray), 8, 16),
+            "lvt_amd_track_rgbd_async": lambda: L.lvt_amd_track_rgbd_async(h, p(gray), p(d32), 8, 16),
+            "lvt_amd_batch_track_device_async_mixed": lambda: L.lvt_amd_batch_track_device_async_mixed(h, ptr1(gray.ctypes.data), ptr1(gray.ctypes.data), one(8), one(16), one(16)),
+            "lvt_amd_track_rgbd_device_async": lambda: L.lvt_amd_track_rgbd_device_async(h, p(gray), 16, p(d32), 64, 0, 1.0, 8, 16),
+            "lvt_amd_track_rgbd_device": lambda: L.lvt_amd_track_rgbd_device(h, p(gray), 16, p(d16), 32, 1, s, 8, 16, p(R), p(t)),
+            "lvt_amd_track_rgbd16": lambda: L.lvt_amd_track_rgbd16(h, p(gray), p(d16), s, 8, 16, p(R), p(t)),
+            "lvt_amd_track_rgbd16_async": lambda: L.lvt_amd_track_rgbd16_async(h, p(gray), p(d16), s, 8, 16),
+            "lvt_amd_batch_track_rgbd_device_async": lambda: L.lvt_amd_batch_track_rgbd_device_async(h, ptr1(gray.ctypes.data), ptr1(d32.ctypes.data), one(8), one(16), one(16), one(64), 0, 1.0),
+        }
+        assert set(void_calls) | set(int_calls) <= set(lvt_amd.ABI_SYMBOLS)
+        # every symbol that tracks or waits is covered (lvt_amd_odometry_update takes an odometry object, not an lvt_handle)
+        assert {n for n in lvt_amd.ABI_SYMBOLS if ("track" in n or "wait" in n)} == (set(void_calls) | set(int_calls)) - {"lvt_get_status"}
+        L.lvt_get_status.restype = ctypes.c_int
+        L.lvt_amd_wait_pose.restype = ctypes.c_int
+        for name, call in void_calls.items():
+            call()
+            assert not R.any() and not t.any() and st[0] == 7, name
+        for name, call in int_calls.items():
+            assert call() == -1, name
+            assert not R.any() and not t.any() and not q.any(), name
+
+
 def test_product_does_not_reference_the_oracle():
     """the oracle is test infrastructure: only tests/ (incl. tests/tools/), __graft_entry__.smoke() and bench.py's cpu_baseline leg
     touch it -- not the package, not the examples, not the developer tools"""

@@ -184,6 +184,26 @@ def test_sequences_of_different_lengths(hip_lib, oracle_lib):
     assert [batch.counts(s)["frame"] for s in range(3)] == [m - 1 for m in lens]
 
 
+def test_a_sequence_absent_on_alternate_steps(hip_lib, oracle_lib):
+    """three sequences, RING + 2 = 10 steps, sequence 1 sits out every other one: its input record of a ring slot says "absent" where the slot's
+    previous step left planes and the other way round, and each sequence still equals its own oracle"""
+    steps = 8 + 2
+    sizes = ((620, 188), (621, 187), (613, 185))
+    seqs = []
+    for s, size in enumerate(sizes):
+        world, prm, _ = make_case("kitti", 70 + s, 1.0, None, size=size)
+        seqs.append(Seq(world, prm, steps // 2 if s == 1 else steps))
+    schedule = [[k, k // 2 if k % 2 == 0 else None, k] for k in range(steps)]
+    batch = hip_lib.LvtBatch.create_mixed([q.prm for q in seqs])
+    got = run(batch, seqs, schedule)
+    assert batch.last_error() == "", batch.last_error()
+    for k in range(1, steps, 2):   # an absent step returns the previous step's pose and state
+        assert np.allclose(got[k][0][1], got[k - 1][0][1], rtol=0, atol=1e-12) and np.allclose(got[k][1][1], got[k - 1][1][1], rtol=0, atol=1e-12), k
+        assert got[k][2][1] == got[k - 1][2][1], k
+    check_against_own_oracles(batch, seqs, schedule, got)
+    assert [batch.counts(s)["frame"] for s in range(3)] == [steps - 1, steps // 2 - 1, steps - 1]
+
+
 def test_uniform_equals_mixed_bit_for_bit(hip_lib):
     """the same three sequences under one parameter set through LvtBatch(prm, 3) and through the mixed constructor: identical poses, states, counters"""
     n = 12
