@@ -82,8 +82,8 @@ __device__ __forceinline__ int key_x(uint32_t k) { return (int)((k >> 8) & ((1u 
 __device__ __forceinline__ int key_r(uint32_t k) { return (int)(k & 255); }
 __device__ __forceinline__ uint32_t key_pos(uint32_t k) { return k >> 8; }
 
-// per-frame, per-sequence inputs (pinned host memory read by k_feat_begin for batches; a kernel argument of k_score for
-// a single sequence, which then needs no separate "begin" launch)
+// per-frame, per-sequence inputs as the host hands them over (pinned host memory read by k_feat_begin for batches; a kernel argument of k_score for
+// a single sequence, which then needs no separate "begin" launch).  feat_begin turns them into the frame's record on the device, FeatCtl::in.
 // An all-zero FrameArgs is a frame of today's kind: DEPTH_F32 is 0, so every producer that clears the record or never hands over a depth plane (the stereo
 // calls, the pool's seats) needs no word about the depth format.  The two depth fields sit where the record had padding: it stays at 72 bytes.
 struct FrameArgs {
@@ -92,30 +92,29 @@ struct FrameArgs {
     int img_pitch, depth_pitch;  // bytes / ELEMENTS of the depth format
     int ext_corners, n_ext[2];
     int depth_format;        // DEPTH_F32 (metres) / DEPTH_U16 (raw sensor units: metres = raw * depth_scale)
-    const float *ext_xy[2];  // external corner lists of THIS frame (a pooled handle's: every seat has its own); nullptr: the context's lists (FrameBuf::ext_xy as created)
+    const float *ext_xy[2];  // external corner lists of THIS frame (a pooled handle's: every seat has its own); nullptr: the context's lists (FrameBuf::ext_xy_own)
     int absent;  // (pooled handles, lvt_host.hip) this sequence has no frame in this lock-step step: every kernel of the step leaves it exactly as it is
     float depth_scale;       // DEPTH_U16 only
 };
 static_assert(sizeof(FrameArgs) == 72, "FrameArgs travels by value (k_score) and 32 at a time (k_feat_begin_pack): keep it at 72 bytes");
 
-// publish this frame's inputs, clear the feature stage's control block
-__device__ __forceinline__ void feat_begin(Seq &S, const FrameArgs &f, int par) {
-    FrameBuf &FB = S.fb[par];
-    FB.img[0] = f.img[0];
-    FB.img[1] = f.img[1];
-    FB.depth_img = f.depth;
-    FB.img_pitch = f.img_pitch;
-    FB.depth_pitch = f.depth_pitch;
-    FB.depth_format = f.depth_format;
-    FB.depth_scale = f.depth_scale;
+// publish this frame's inputs, clear the feature stage's control block: everything it writes lies in the buffer's FeatCtl, nothing in the descriptor
+__device__ __forceinline__ void feat_begin(const Seq &S, const FrameArgs &f, int par) {
+    const FrameBuf &FB = S.fb[par];
     FeatCtl &c = *FB.fc;
+    c.in.img[0] = f.img[0];
+    c.in.img[1] = f.img[1];
+    c.in.depth_img = f.depth;
+    c.in.img_pitch = f.img_pitch;
+    c.in.depth_pitch = f.depth_pitch;
+    c.in.depth_format = f.depth_format;
+    c.in.depth_scale = f.depth_scale;
     c.absent = f.absent;
     if (c.poison) return;  // (k_gate_buf: the buffer still belongs to an older frame)
     c.ext_corners = f.ext_corners;
-    if (f.ext_corners) {  // a pooled seat's frame brings its own lists (freed with the seat: never kept beyond the frame); any other frame reads the context's
-        FB.ext_xy[0] = f.ext_xy[0] ? f.ext_xy[0] : FB.ext_xy_own[0];
-        FB.ext_xy[1] = f.ext_xy[0] ? f.ext_xy[1] : FB.ext_xy_own[1];
-    }
+    // a pooled seat's frame brings its own lists (freed with the seat: never kept beyond the frame); any other frame reads the context's
+    if (f.ext_xy[0]) c.in.ext_xy[0] = f.ext_xy[0], c.in.ext_xy[1] = f.ext_xy[1];
+    else c.in.ext_xy[0] = FB.ext_xy_own[0], c.in.ext_xy[1] = FB.ext_xy_own[1];
     c.n_ext[0] = f.n_ext[0];
     c.n_ext[1] = f.n_ext[1];
     c.n_detected[0] = c.n_detected[1] = 0;
@@ -127,15 +126,12 @@ __device__ __forceinline__ void feat_begin(Seq &S, const FrameArgs &f, int par) 
     if (f.absent) c.poison = 1;
 }
 
-// one TS_W x TS_H tile (bx, by) of image `eye` of sequence S; tiles_x: tiles per tile row of THAT image (the stride of its segment lists).
-// BEGIN = single sequence: `fa` carries the frame's inputs
-template <bool BEGIN>
-__device__ __forceinline__ void score_tile(const Seq &S, const FrameBuf &FB, const FrameArgs &fa, int eye, int bx, int by, int tiles_x, int box) {
+// one TS_W x TS_H tile (bx, by) of image `eye` of sequence S, the plane `img` at `pitch` bytes (workgroup-uniform: the kernel's head fetched them);
+// tiles_x: tiles per tile row of THAT image (the stride of its segment lists)
+__device__ __forceinline__ void score_tile(const Seq &S, const FrameBuf &FB, const uint8_t *img, int pitch, int eye, int bx, int by, int tiles_x, int box) {
     const int W = S.prm.W, H = S.prm.H;
     const int x0 = bx * TS_W, y0 = by * TS_H;
     if (x0 >= W || y0 >= H) return;
-    const uint8_t *img = BEGIN ? fa.img[eye] : FB.img[eye];
-    const int pitch = BEGIN ? fa.img_pitch : FB.img_pitch;
 
     // every LDS access below is a whole word (a thread owns 4 horizontally adjacent pixels, so a 12-byte row segment = 3 words holds
     // all it needs from one tile row): 35 LDS instructions per thread where byte-wise reads needed 158, and the kernel was LDS-issue-bound
@@ -345,14 +341,20 @@ __device__ __forceinline__ void score_tile(const Seq &S, const FrameBuf &FB, con
     }
 }
 
-// BEGIN = single sequence: block (0, 0, 0) publishes the frame's inputs for the later kernels
+// BEGIN = single sequence: `fa` carries the frame's inputs and block (0, 0, 0) publishes them for the later kernels.  The other workgroups of the launch run
+// beside that store, so this instance takes the image from `fa`, never from the record; a batch's record was written by the launch before (k_feat_begin*).
 template <bool BEGIN>
-__global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par, int z0, int box) {  // z0: first image of this launch (a batch's images may come in several launches); box: 0 = no box-sum plane (k_brief_img builds the sums from the image)
+__global__ __launch_bounds__(256) void k_score(const Seq *seqs, FrameArgs fa, int par, int z0, int box) {  // z0: first image of this launch (a batch's images may come in several launches); box: 0 = no box-sum plane (k_brief_img builds the sums from the image)
     const int seq = (blockIdx.z + z0) >> 1, eye = (blockIdx.z + z0) & 1;
-    const Seq &S = seq_const(seqs, seq);  // (read through the constant address space: global, not flat, accesses -- lvt_dev.h; the fields written below are not read here)
+    const Seq &S = seq_const(seqs, seq);  // (read through the constant address space: global, not flat, accesses -- lvt_dev.h)
     const FrameBuf &FB = S.fb[par];
-    if (FB.fc->poison) return;
-    if (BEGIN && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) feat_begin(seqs[seq], fa, par);
+    const FeatCtl &fc = *FB.fc;
+    const uint8_t *img;
+    int pitch;
+    if constexpr (BEGIN) img = fa.img[eye], pitch = fa.img_pitch;
+    else img = fc.in.img[eye], pitch = fc.in.img_pitch;
+    if (fc.poison) return;
+    if (BEGIN && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) feat_begin(S, fa, par);
     if (eye == 1 && S.prm.sensor == 2) return;
     // workgroups go to the 8 XCDs round-robin by their linear id and every XCD has its own L2: with the plain mapping the four neighbours of a
     // tile -- which share its halo rows and its 128-byte lines -- sit on other XCDs, and an image was fetched 2.9 times (rocprofv3 FETCH_SIZE
@@ -367,7 +369,7 @@ __global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par,
             bx = t % gridDim.x, by = t / gridDim.x;
         }
     }
-    score_tile<BEGIN>(S, FB, fa, eye, bx, by, (int)gridDim.x, box);
+    score_tile(S, FB, img, pitch, eye, bx, by, (int)gridDim.x, box);
 }
 
 // ---- a MIXED lock-step batch (lvt_amd_batch_create_mixed): sequences with their own image sizes and detection grids ------------------
@@ -380,14 +382,17 @@ __global__ __launch_bounds__(256) void k_score(Seq *seqs, FrameArgs fa, int par,
 // k_score's band-per-L2 placement (see above), here for ANY tile count and offset because the table, not a formula, assigns the tiles.
 constexpr int MIXED_TILE_COLS = 256, MIXED_TILE_ROWS = 1 << 14;  // what an entry's fields hold (images up to 16 384 px wide: far beyond the cell-grid limits)
 typedef const __attribute__((address_space(4))) uint32_t *TabConstPtr;
-__global__ __launch_bounds__(256) void k_score_mixed(Seq *seqs, const uint32_t *tab, int par, int box) {
+__global__ __launch_bounds__(256) void k_score_mixed(const Seq *seqs, const uint32_t *tab, int par, int box) {
     const uint32_t e = ((TabConstPtr)tab)[blockIdx.x];
     const int img = (int)(e >> 22), by = (int)((e >> 8) & (MIXED_TILE_ROWS - 1)), bx = (int)(e & (MIXED_TILE_COLS - 1));
     const int seq = img >> 1, eye = img & 1;
     const Seq &S = seq_const(seqs, seq);
     const FrameBuf &FB = S.fb[par];
-    if (FB.fc->poison) return;  // (absent in this step, or the buffer is not free: feat_begin)
-    score_tile<false>(S, FB, FrameArgs{}, eye, bx, by, (S.prm.W + TS_W - 1) / TS_W, box);
+    const FeatCtl &fc = *FB.fc;
+    const uint8_t *plane = fc.in.img[eye];
+    const int pitch = fc.in.img_pitch;
+    if (fc.poison) return;  // (absent in this step, or the buffer is not free: feat_begin)
+    score_tile(S, FB, plane, pitch, eye, bx, by, (S.prm.W + TS_W - 1) / TS_W, box);
 }
 
 // =================================================================================================
@@ -1631,6 +1636,15 @@ __device__ __forceinline__ void cells_entry(const SeqArg<BV> &sa, int pass, int 
     if (strip >= 0) cells_work_split(S, FB, eye, cell, strip, nsplit, token, L, raw_cap);
     else cells_work(S, FB, eye, cell, pass, L, raw_cap);
 }
+struct CellsRest {  // what follows the descriptor in k_cells' arguments, the longest such list of any kernel: held to the room a by-value Seq leaves (lvt_dev.h)
+    int pass, par;
+    CellOrder ord;
+    int lanes, raw_cap;
+    NextPull np;
+    int nsplit;
+    unsigned token;
+};
+static_assert(sizeof(CellsRest) <= BYVAL_REST_MAX, "k_cells' arguments outgrow what SeqArg<true> leaves of the kernel-argument segment");
 // A single sequence runs one workgroup per CU with the 159-KB carve: it may use the 128 registers a 1024-thread workgroup can have.  The batch
 // instance is held to 64 so that TWO of its 80-KB workgroups share a CU (at 66 registers it ran one per CU whatever its LDS) -- an occupancy
 // attribute on the template would cap the single-sequence instance too, where a second workgroup can never fit and the cap can only spill.
@@ -1664,7 +1678,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // vouch (or whose extended rows overflow the LDS) reports -1 and k_cells_big runs the whole cell on the single-workgroup global path
 // instead, as before.  Survivors of the strips, concatenated in strip order, ARE the cell's survivors in raster order.
 constexpr int STRIP_HALO = 16;
-__global__ __launch_bounds__(1024) void k_cells_strip(Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_strip(const Seq *seqs, int pass, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
     const int eye = blockIdx.y, cell = blockIdx.x / STRIPS, strip = blockIdx.x % STRIPS;
     const FrameBuf &FB = S.fb[par];
@@ -1728,7 +1742,7 @@ __global__ __launch_bounds__(1024) void k_cells_strip(Seq *seqs, int pass, int p
 }
 
 // the oversized cell's second half: its strips' survivors, merged in LDS, through LVT's ANMS (or the whole cell on the old path)
-__global__ __launch_bounds__(1024) void k_cells_big(Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int pass, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
     const int eye = blockIdx.y, cell = blockIdx.x;
     const FrameBuf &FB = S.fb[par];
@@ -1785,7 +1799,7 @@ __global__ __launch_bounds__(1024) void k_cells_big(Seq *seqs, int pass, int par
 
 constexpr int RADII_WGS = 16;
 static_assert(STRIPS >= 2, "the ANMS launches pass sorted[] and r2[] through the first two strip buffers");
-__global__ __launch_bounds__(1024) void k_cells_radii(Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_radii(const Seq *seqs, int pass, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
     const int eye = blockIdx.y, cell = blockIdx.x / RADII_WGS, wg = blockIdx.x % RADII_WGS;
     const FrameBuf &FB = S.fb[par];
@@ -1805,7 +1819,7 @@ __global__ __launch_bounds__(1024) void k_cells_radii(Seq *seqs, int pass, int p
     for (int i = wg + tid * RADII_WGS; i < n; i += 1024 * RADII_WGS) gr[i] = L.uf[i];
 }
 
-__global__ __launch_bounds__(1024) void k_cells_select(Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_select(const Seq *seqs, int pass, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
     const int eye = blockIdx.y, cell = blockIdx.x;
     const FrameBuf &FB = S.fb[par];
@@ -1839,14 +1853,12 @@ __device__ __forceinline__ bool brief_border_keep(float x, float y, int rows, in
     return ix >= B && ix < cols - B && iy >= B && iy < rows - B;
 }
 
-// (`seqs` = the descriptors in device memory: the per-frame inputs -- image / depth pointers and pitches -- are published there by the
-//  head of the feature stage and are NOT part of a descriptor that travels by value)
+// (the frame's inputs -- the depth plane, the external corner lists -- come from the buffer's FeatCtl, whichever way the descriptor travelled)
 template <bool BV>
-__global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs, int par) {
+__global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, int par) {
     const Seq &S = sa.get();
     const int eye = blockIdx.y;
     const FrameBuf &FB = S.fb[par];
-    const FrameBuf &FBd = seq_const(seqs, blockIdx.z).fb[par];
     FeatCtl &ctl = *FB.fc;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const CellLds L = carve_cell_lds(smem);
@@ -1871,6 +1883,21 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
         if (tid == 0) *F.n = 0;
         return;
     }
+    // the frame's inputs: workgroup-uniform, one line of the FeatCtl this kernel has just read `poison` from, and fetched only by the frames that use them
+    // (a stereo frame with detected corners waits for none of these loads).  Fetched HERE, behind the retry pass: at the kernel's head they would be held
+    // in scalar registers across it, which the kernel does not have (it sits at its cap of 128 VGPRs, SGPR spills included); behind the retry pass's stores
+    // the compiler no longer takes the loads for scalar ones, hence wave_uniform
+    const FrameIn &in = ctl.in;
+    const bool rgbd = (S.prm.sensor == 2);
+    const float *ext_xy = nullptr, *depth_img = nullptr;
+    int depth_pitch = 0, depth_format = DEPTH_F32;
+    float depth_scale = 0.f;
+    if (ctl.ext_corners) ext_xy = wave_uniform(in.ext_xy[eye]);
+    if (rgbd) {
+        depth_img = wave_uniform(in.depth_img);
+        depth_pitch = wave_uniform(in.depth_pitch), depth_format = wave_uniform(in.depth_format);
+        depth_scale = wave_uniform(in.depth_scale);
+    }
     const int nc = ctl.ext_corners ? 1 : S.prm.n_cells;
     if (tid == 0) {
         int acc = 0;
@@ -1883,7 +1910,6 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
     __syncthreads();
     const int total_in = cell_off[nc];
     const int W = S.prm.W, H = S.prm.H;
-    const bool rgbd = (S.prm.sensor == 2);
     int n_out = 0;
     for (int base = 0; base < total_in; base += 1024) {
         const int g = base + tid;
@@ -1891,8 +1917,8 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
         float x = 0, y = 0, r = 0, ox = 0, oy = 0, dep = 0;
         if (g < total_in) {
             if (ctl.ext_corners) {
-                x = FB.ext_xy[eye][2 * g];
-                y = FB.ext_xy[eye][2 * g + 1];
+                x = ext_xy[2 * g];
+                y = ext_xy[2 * g + 1];
             } else {
                 int c = 0;
                 while (g >= cell_off[c + 1]) c++;
@@ -1905,10 +1931,10 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
             oy = y;
             keep = brief_border_keep(x, y, H, W);
             if (keep && rgbd) {  // handler.cpp:255-265 (depth at the distorted pixel), :268-294
-                const size_t di = (size_t)((int)y) * FBd.depth_pitch + (int)x;
+                const size_t di = (size_t)((int)y) * depth_pitch + (int)x;
                 // DEPTH_U16: one 16-bit load, an exact conversion and ONE rounded fp32 multiply -- what a caller's own `(float)raw * scale` gives, so a
                 // 16-bit frame tracks exactly like its fp32 conversion; raw 0 ("no depth") is 0.0f and falls to the near-plane test below
-                dep = (FBd.depth_format == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(FBd.depth_img)[di], FBd.depth_scale) : FBd.depth_img[di];
+                dep = (depth_format == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(depth_img)[di], depth_scale) : depth_img[di];
                 keep = (dep >= S.prm.near_plane && dep <= S.prm.far_plane);
                 if (keep && S.prm.undistort) {
                     undistort_point(S.prm, x, y, x, y);
@@ -1944,13 +1970,14 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, const Seq *seqs,
 // =================================================================================================
 // k_brief : one wavefront per key point, lane l evaluates tests 4l..4l+3
 // =================================================================================================
-__device__ __forceinline__ int box_at(const Seq &S, const FrameBuf &FB, const FrameBuf &FBd, int eye, int iy, int ix) {
+__device__ __forceinline__ int box_at(const Seq &S, const FrameBuf &FB, int eye, int iy, int ix) {
     const int W = S.prm.W, H = S.prm.H;
     if (ix >= 0 && ix < W && iy >= 0 && iy < H) return FB.boxsum[eye][(size_t)iy * S.plane_pitch + ix];
     // centre outside the image (fractional external corners at the border only): clipped window
+    const FrameIn &in = FB.fc->in;
     int s = 0;
     for (int y = max(iy - 4, 0); y <= min(iy + 4, H - 1); y++)
-        for (int x = max(ix - 4, 0); x <= min(ix + 4, W - 1); x++) s += FBd.img[eye][(size_t)y * FBd.img_pitch + x];
+        for (int x = max(ix - 4, 0); x <= min(ix + 4, W - 1); x++) s += in.img[eye][(size_t)y * in.img_pitch + x];
     return s;
 }
 
@@ -1966,7 +1993,7 @@ constexpr int BR_R = 24, BR_ROWS = 2 * BR_R + 1, BR_DW = 25;      // window rows
 static_assert(brief_max_offset() <= BR_R, "k_brief's window does not cover the test pattern");
 constexpr int BR_WIN_DW = BR_ROWS * BR_DW, BR_LOADS = (BR_WIN_DW + 63) / 64;
 template <bool BV>
-__global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, const Seq *seqs, int par, seq_t publish_seq) {
+__global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t publish_seq) {
     // workgroups go to the 8 XCDs round-robin by their linear id, and every XCD has its own L2: with the plain mapping each L2 sees the
     // box-sum planes of ALL sequences (30 MB for a batch of 16) and every window comes from the Infinity Cache.  When the number of planes
     // is a multiple of 8, XCD x takes planes x, x + 8, ... whole, so a plane is pulled into ONE L2, once.
@@ -1978,8 +2005,7 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, const Seq *seqs, i
         plane = (lid & 7) + 8 * (j / gridDim.x);
         bx = j % gridDim.x;
     }
-    const Seq &S = BV ? sa.get() : seq_const(seqs, plane / gridDim.y);  // (sa.get() indexes by blockIdx.z: the batch form picks its plane's sequence itself)
-    const FrameBuf &FBd = seq_const(seqs, plane / gridDim.y).fb[par];  // per-frame image pointers (border fall-back only)
+    const Seq &S = sa.at(plane / gridDim.y);  // (sa.get() indexes by blockIdx.z: the batch form picks its plane's sequence itself)
     const int eye = plane % gridDim.y;
     const FrameBuf &FB = S.fb[par];
     const Feat &F = FB.feat[eye];
@@ -2063,8 +2089,8 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, const Seq *seqs, i
             if (nfast) fetch(ncy, ncx);
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                const int a = box_at(S, FB, FBd, eye, cy + tq[w][0], cx + tq[w][1]);
-                const int b = box_at(S, FB, FBd, eye, cy + tq[w][2], cx + tq[w][3]);
+                const int a = box_at(S, FB, eye, cy + tq[w][0], cx + tq[w][1]);
+                const int b = box_at(S, FB, eye, cy + tq[w][2], cx + tq[w][3]);
                 word[w] = __ballot(a < b);
             }
         }
@@ -2102,7 +2128,7 @@ constexpr int BI_G = 13;                                // groups of four horizo
 constexpr int BI_PATCH_DW = BI_ROWS * BI_DW, BI_LOADS = (BI_PATCH_DW + 63) / 64;
 constexpr int BI_GROUPS = BI_ROWS * BI_G, BI_GLOOPS = (BI_GROUPS + 63) / 64;
 template <bool BV>
-__global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, const Seq *seqs, int par, seq_t publish_seq) {
+__global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t publish_seq) {
     const int planes = gridDim.y * gridDim.z;
     int lid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     int plane = lid / gridDim.x, bx = lid % gridDim.x;
@@ -2111,8 +2137,7 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, const Seq *seq
         plane = (lid & 7) + 8 * (j / gridDim.x);
         bx = j % gridDim.x;
     }
-    const Seq &S = BV ? sa.get() : seq_const(seqs, plane / gridDim.y);
-    const FrameBuf &FBd = seq_const(seqs, plane / gridDim.y).fb[par];  // per-frame image pointers
+    const Seq &S = sa.at(plane / gridDim.y);
     const int eye = plane % gridDim.y;
     const FrameBuf &FB = S.fb[par];
     const Feat &F = FB.feat[eye];
@@ -2127,8 +2152,8 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, const Seq *seq
     typedef uint16_t __attribute__((may_alias)) u16_alias;
     const u16_alias *hs16 = reinterpret_cast<const u16_alias *>(hs);   // [row][52] horizontal sums
     const int W = S.prm.W, H = S.prm.H;
-    const uint8_t *img = FBd.img[eye];
-    const int pitch = FBd.img_pitch;  // (a multiple of 16: rows are word-aligned)
+    const uint8_t *img = wave_uniform(FB.fc->in.img[eye]);  // the frame's plane, from the buffer's FeatCtl (`eye` is uniform, but computed in vector registers)
+    const int pitch = FB.fc->in.img_pitch;                  // (a multiple of 16: rows are word-aligned)
     int goff[BI_LOADS];
 #pragma unroll
     for (int i = 0; i < BI_LOADS; i++) {

@@ -452,7 +452,7 @@ __device__ __forceinline__ void gate_buf_wait(const Seq &S, seq_t want, int par)
         }
     }
 }
-__global__ __launch_bounds__(64) void k_gate_buf(Seq *seqs, seq_t want, int par) {
+__global__ __launch_bounds__(64) void k_gate_buf(const Seq *seqs, seq_t want, int par) {
     if (threadIdx.x != 0) return;
     gate_buf_wait(seq_const(seqs, blockIdx.z), want, par);
 }
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(64) void k_gate_buf(Seq *seqs, seq_t want, int par)
 // last kernel of the feature stage of a batch (one thread per sequence): this buffer's features are complete.  (A single sequence lets
 // k_brief's last workgroup publish instead -- one launch less on its longest chain.  With a batch's 2048 workgroups that cost 60 us:
 // every workgroup's release fence is an L2 write-back.)
-__global__ void k_feat_done(Seq *seqs, int par, seq_t seq) {
+__global__ void k_feat_done(const Seq *seqs, int par, seq_t seq) {
     if (threadIdx.x != 0) return;
     FeatCtl &fc = *seq_const(seqs, blockIdx.x).fb[par].fc;
     seq_const(seqs, blockIdx.x).ctl->dbg[47] = (long long)wall_clock64();  // (written from the feature stream: the frame it belongs to may differ)
@@ -473,7 +473,7 @@ __global__ void k_feat_done(Seq *seqs, int par, seq_t seq) {
 }
 
 // behind k_candidates<ROW>: this frame's row-match candidate lists are complete (k_triangulate's head polls the word)
-__global__ void k_row_done(Seq *seqs, int par, seq_t seq) {
+__global__ void k_row_done(const Seq *seqs, int par, seq_t seq) {
     if (threadIdx.x != 0) return;
     FeatCtl &fc = *seq_const(seqs, blockIdx.x).fb[par].fc;
     if (__hip_atomic_load(&fc.feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) return;  // (see k_candidates)
@@ -1320,7 +1320,7 @@ __device__ __forceinline__ void deliver_record(const Ctl &ctl, Ctl *rec_out, seq
     if (threadIdx.x == 0) __hip_atomic_store(done_out, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // (the last enqueued frame has no successor: the host launches this when it is asked for that frame's result)
-__global__ __launch_bounds__(64) void k_deliver(Seq *seqs, Ctl *rec_out, seq_t *done_out, seq_t seq) {
+__global__ __launch_bounds__(64) void k_deliver(const Seq *seqs, Ctl *rec_out, seq_t *done_out, seq_t seq) {
     deliver_record(*seq_const(seqs, blockIdx.z).ctl, rec_out + blockIdx.z, done_out + blockIdx.z, seq, 64);
 }
 

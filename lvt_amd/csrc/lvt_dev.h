@@ -125,6 +125,21 @@ struct Ctl {
 // full frame ahead of the tracking stream (with two, the features of frame t+1 only finish when frame t does)
 constexpr int NPAR = 3;
 
+enum { DEPTH_F32 = 0, DEPTH_U16 = 1 };  // == LVT_AMD_DEPTH_F32 / _U16 (lvt_amd_ext.h)
+
+// The inputs of ONE frame: where its planes and corner lists lie.  Their only home is FeatCtl::in, ordinary global memory that feat_begin writes at the head of
+// the frame's feature stage and the feature kernels behind it read with ordinary loads (Seq, which may be read through the constant address space, holds nothing
+// that changes after creation).  k_score<true> is the one reader beside the writer -- workgroup (0, 0, 0) of its own launch -- and takes the image from its
+// FrameArgs argument instead.
+struct FrameIn {
+    const uint8_t *img[2];
+    const float *depth_img;     // RGB-D: float or uint16_t elements (depth_format)
+    int img_pitch, depth_pitch; // bytes / elements
+    int depth_format;           // element format of depth_img (DEPTH_F32 / DEPTH_U16) ...
+    float depth_scale;          // ... and metres per raw unit of a DEPTH_U16 plane
+    const float *ext_xy[2];     // external corners (n_ext x 2, f32) of a track_with_external_corners frame: the frame's own lists, else FrameBuf::ext_xy_own
+};
+
 struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one per feature buffer)
     int ext_corners;    // track_with_external_corners frame
     int n_ext[2];
@@ -137,9 +152,8 @@ struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one
     int poison;         // k_gate_buf gave up waiting for this buffer's previous user: the feature kernels of this frame must not touch it
     seq_t skip_seq;     // ... and this frame (sequence number) has no features: the tracking chain skips it
     seq_t feat_seq;  // sequence number of the frame whose features this buffer holds, published by k_feat_done (polled by k_gate)
+    FrameIn in;      // this frame's inputs (beside `poison`, the word every feature kernel loads first)
 };
-
-enum { DEPTH_F32 = 0, DEPTH_U16 = 1 };  // == LVT_AMD_DEPTH_F32 / _U16 (lvt_amd_ext.h)
 
 struct Feat {  // one image's lvt_image_features_struct (lvt_image_features_struct.h:62-80), SoA
     float *x, *y, *resp;   // keypoint coords as the struct stores them (undistorted for RGB-D)
@@ -157,24 +171,17 @@ struct MapSoA {            // lvt_local_map.h:64-72 as SoA; two copies for stabl
     int *counter, *age, *match_idx;
 };
 
-// everything the feature stage of ONE frame produces / consumes; NPAR copies (frame number mod NPAR) so that the
-// feature extraction of frame t+1 overlaps the tracking chain of frame t on a second HIP stream
+// the buffers the feature stage of ONE frame works in; NPAR copies (frame number mod NPAR) so that the feature extraction of frame t+1 overlaps the
+// tracking chain of frame t on a second HIP stream.  Pointers to fixed allocations only: like all of Seq the record is written by the host at creation and
+// by nobody afterwards.  What changes from frame to frame lies behind `fc` (FeatCtl, with the frame's inputs in FeatCtl::in).
 struct FrameBuf {
-    const uint8_t *img[2];
-    const float *depth_img;     // RGB-D: float or uint16_t elements (depth_format)
-    int img_pitch, depth_pitch; // bytes / elements
-    // element format of depth_img (DEPTH_F32 / DEPTH_U16) and metres per raw unit of a DEPTH_U16 plane.  Per-frame mutable members like depth_img: published by
-    // feat_begin and read ONLY where depth_img is read -- k_gather, on the feature stream, behind the writer (through seq_const: see SeqArg below)
-    int depth_format;
-    float depth_scale;
     uint8_t *score[2];          // OAST-9/16 score map (0 = below the lowered threshold / dead band)
     uint16_t *boxsum[2];        // 9x9 box sums
     uint32_t *seg_keys[2];      // [H][tiles_x][64] raw-corner keys (score >= agast_th) of one 64-px tile row, x-ascending
     uint16_t *seg_cnt[2];       // [H][tiles_x]  count | (count left of the cell boundary inside the tile) << 8
     float *cell_kp[2];          // [CELLS_MAX][CELL_OUT_CAP][3] (x, y, response)
     int *cell_n[2];             // [CELLS_MAX]
-    const float *ext_xy[2];     // external corners (n_ext x 2, f32) for track_with_external_corners
-    const float *ext_xy_own[2]; // the lists the context was created with (ext_xy points at them again whenever a frame brings none of its own)
+    const float *ext_xy_own[2]; // the external-corner lists the context was created with (FrameIn::ext_xy names them whenever a frame brings none of its own)
     Feat feat[2];
     FeatCtl *fc;
 };
@@ -220,6 +227,19 @@ __device__ __forceinline__ int hamming256(const uint64_t a[4], const uint64_t b[
     return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
 }
 
+// a value every lane of the wave holds alike (loaded from one address), moved into scalar registers where the compiler cannot see that for itself
+template <typename T>
+__device__ __forceinline__ T wave_uniform(T v) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two registers");
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+    } else {
+        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+        return __builtin_bit_cast(T, (uint64_t)hi << 32 | lo);
+    }
+}
+
 // inclusive wave scan (64 lanes), all lanes active.  DPP row shifts inside each row of 16 lanes, then the two row
 // broadcasts (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3): six VALU instructions, no LDS crossbar
 // (the __shfl_up form costs six ds_bpermute round trips of ~120 cycles each -- with the barriers around it a block scan
@@ -259,30 +279,35 @@ __device__ __forceinline__ int block_excl_scan(int v, int *scratch, int *total) 
     return base + incl - v;
 }
 
-// A sequence's descriptor reaches the kernels of the early and tracking chains (and k_cells, which touches the feature stage's fixed buffers only) either BY VALUE (single sequence: its fields are
-// kernel arguments, fetched with the kernel's own argument load) or as an element of the device array (lock-step batch: one more
-// dependent memory hop at every kernel head).  These kernels never read the per-frame mutable fields of Seq (FrameBuf::img ...),
-// which only the feature stage writes and reads.
+// A sequence's descriptor is IMMUTABLE: the host writes it at creation (create_context) and nobody writes it afterwards -- every kernel takes it const.  It reaches
+// the kernels either BY VALUE (single sequence: its fields are kernel arguments, fetched with the kernel's own argument load) or as an element of the device array
+// (lock-step batch: one more dependent memory hop at every kernel head).  Whatever changes from frame to frame lies BEHIND its pointers (Ctl, FeatCtl -- the
+// frame's inputs in FeatCtl::in --, the buffers), in ordinary global memory, so both forms always say the same.
 template <bool BYVAL>
 struct SeqArg;
 // Round 6: the element of the device array is read through the CONSTANT address space.  A pointer loaded from generic / global memory is a FLAT pointer to the
 // compiler, and every access through it a flat_load / flat_store: those count on lgkmcnt as well as vmcnt, so each wait for an LDS read also waited for every
 // global load and store in flight (the LDS-latency-bound kernels of a batch -- k_cells, the resolvers, k_triangulate, the list kernels -- paid a memory round trip
 // per LDS access; the by-value form never did: its pointers come out of the kernel arguments).  A pointer loaded from constant memory is taken to be a global one
-// (AMDGPUTargetMachine::getAssumedAddrSpace), the loads of the record's fields become scalar loads.  Valid here: the fields these kernels read are written
-// by the host at creation and by kernels that finished before this one started (never during it).
+// (AMDGPUTargetMachine::getAssumedAddrSpace), the loads of the record's fields become scalar loads that the compiler may hoist anywhere, above an acquire poll
+// included.  Valid because no kernel can write the record: it does not change while a reader can run.
 typedef const __attribute__((address_space(4))) Seq *SeqConstPtr;
 __device__ __forceinline__ const Seq &seq_const(const Seq *p, unsigned i) { return *(const Seq *)((SeqConstPtr)p + i); }
 template <>
 struct SeqArg<false> {
     const Seq *p;
     __device__ __forceinline__ const Seq &get() const { return seq_const(p, blockIdx.z); }
+    __device__ __forceinline__ const Seq &at(unsigned i) const { return seq_const(p, i); }  // (kernels that do not map sequences to blockIdx.z)
 };
 template <>
 struct SeqArg<true> {
     Seq v;
     __device__ __forceinline__ const Seq &get() const { return v; }
+    __device__ __forceinline__ const Seq &at(unsigned) const { return v; }
 };
+// a kernel's arguments end at 4096 bytes: what follows a by-value descriptor may take BYVAL_REST_MAX bytes (the longest list, k_cells', checks itself against it)
+constexpr size_t KERNARG_MAX = 4096, BYVAL_REST_MAX = 256;
+static_assert(sizeof(SeqArg<true>) + BYVAL_REST_MAX <= KERNARG_MAX, "a by-value Seq and the arguments behind it must fit the kernel-argument segment");
 
 
 }  // namespace lvt

@@ -60,9 +60,9 @@ constexpr int MAX_FOLDED_GATES = 4;
 
 // first kernel of the feature stage of a BATCH: publish every sequence's inputs (a single sequence gets them as a kernel
 // argument of k_score)
-__global__ void k_feat_begin(Seq *seqs, const FrameArgs *fa, int par) {
+__global__ void k_feat_begin(const Seq *seqs, const FrameArgs *fa, int par) {
     if (threadIdx.x != 0) return;
-    feat_begin(seqs[blockIdx.x], fa[blockIdx.x], par);
+    feat_begin(seq_const(seqs, blockIdx.x), fa[blockIdx.x], par);
 }
 // the same with the sequences' inputs in the kernel's own arguments (up to FEAT_PACK sequences): no read of pinned host memory over PCIe at the head of the feature stage
 constexpr int FEAT_PACK = 32;
@@ -72,11 +72,12 @@ struct FrameArgsPack {
 static_assert(sizeof(Seq *) + sizeof(FrameArgsPack) + sizeof(int) + 2 * sizeof(seq_t) < 4096, "k_feat_begin_pack's arguments must stay under 4096 bytes");
 // ... and with k_gate_buf's wait in front (want != 0: the tracking chain of the frame that used this buffer last must have released it): one launch at the head of a
 // batch's feature stage instead of two
-__global__ void k_feat_begin_pack(Seq *seqs, FrameArgsPack pk, int par, seq_t want) {
+__global__ void k_feat_begin_pack(const Seq *seqs, FrameArgsPack pk, int par, seq_t want) {
     if (threadIdx.x != 0) return;
-    if (want) gate_buf_wait(seq_const(seqs, blockIdx.x), want, par);
+    const Seq &S = seq_const(seqs, blockIdx.x);
+    if (want) gate_buf_wait(S, want, par);
     const FrameArgs f = pk.a[blockIdx.x];
-    feat_begin(seqs[blockIdx.x], f, par);
+    feat_begin(S, f, par);
 }
 
 // tightly packed host-layout images (stride == cols) -> pitched device images.
@@ -179,7 +180,7 @@ struct Context {
     hipStream_t stream_e = nullptr;  // early part of find_matches of the next frame (behind the previous frame's k_pnp)
     bool own_stream = false;
     std::vector<void *> allocs;
-    Seq *d_seqs = nullptr;
+    const Seq *d_seqs = nullptr;  // written ONCE, by create_context, from h_seqs; no kernel and no later host code writes it (lvt_dev.h: SeqArg)
     std::vector<Seq> h_seqs;   // host mirror (device pointers inside)
     std::vector<Ctl *> d_ctl;
     Ctl *h_ctl = nullptr;          // pinned, RING x B records
@@ -208,6 +209,7 @@ struct Context {
     // In TWO launches the chip drains once in the middle and they get in: +4 .. 8 % for 8 - 24 KITTI-shaped sequences, -6 % from 28 on, where the feature
     // stage is the longer chain and the drain is pure loss.  Which side a batch is on shows in its own early gate (Ctl::dbg[32 / 35 / 33]: start, features
     // seen, pose seen): a gate that mostly waits for the previous pose says the feature stream is ahead.  LVT_AMD_SCORE_PIECES=1 / 2 fixes the choice.
+    bool feat_pack = true;     // LVT_AMD_NO_FEAT_PACK (set to anything): a batch's inputs go through pinned host memory (k_feat_begin) behind a k_gate_buf launch of their own
     int brief_from_image = 0;  // LVT_AMD_BRIEF_FROM_IMAGE=1: no box-sum plane; k_brief_img builds the 9 x 9 sums of a key point's patch in LDS (k_features.hip)
     int score_pieces = 1;
     bool score_pieces_auto = true;
@@ -655,6 +657,7 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
             std::stable_sort(idx, idx + prm.n_cells, [&](int a, int b) { return area[a] > area[b]; });
             for (int cc = 0; cc < CELLS_MAX; cc++) c->cell_order.v[cc] = (uint8_t)(cc < prm.n_cells ? idx[cc] : 0);
         }
+        if (std::getenv("LVT_AMD_NO_FEAT_PACK")) c->feat_pack = false;
         if (const char *e = std::getenv("LVT_AMD_BRIEF_FROM_IMAGE")) c->brief_from_image = std::atoi(e) ? 1 : 0;
         if (const char *e = std::getenv("LVT_AMD_SCORE_PIECES")) c->score_pieces = std::max(1, std::min(8, std::atoi(e))), c->score_pieces_auto = false;
         {
@@ -724,7 +727,7 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
                         c->d_ext[par][e] = c->dalloc<float>((size_t)EXT_MAX * 2);
                         c->d_img[par][e] = c->dalloc<uint8_t>(plane + 64);
                     }
-                    FB.ext_xy[e] = FB.ext_xy_own[e] = c->d_ext[par][e];
+                    FB.ext_xy_own[e] = c->d_ext[par][e];
                 }
                 if (s == 0 && sensor == 2) c->d_depth[par] = c->dalloc<float>((size_t)q.W * q.H + 4);
             }
@@ -757,8 +760,11 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
             S.tri_X = c->dalloc<double>((size_t)NF_MAX * 3);
             S.tri_ok = c->dalloc<int8_t>(NF_MAX);
         }
-        c->d_seqs = c->dalloc<Seq>(B);
-        HIPCHK(c, hipMemcpy(c->d_seqs, c->h_seqs.data(), sizeof(Seq) * B, hipMemcpyHostToDevice));
+        {
+            Seq *d = c->dalloc<Seq>(B);
+            HIPCHK(c, hipMemcpy(d, c->h_seqs.data(), sizeof(Seq) * B, hipMemcpyHostToDevice));
+            c->d_seqs = d;
+        }
         if (mixed) {
             c->n_score_wgs = (int)score_tab.size(), c->n_cells_wgs = (int)cells_tab.size();
             c->d_score_tab = c->dalloc<uint32_t>(score_tab.size());
@@ -873,7 +879,7 @@ static void enqueue_frame(Context *c) {
     const int Bz = (c->launch_seqs > 0 && c->launch_seqs < B) ? c->launch_seqs : B;
     c->ring_seqs[(int)(c->enq % RING)] = Bz;
     const Params &p = c->prm;
-    Seq *S = c->d_seqs;
+    const Seq *S = c->d_seqs;
     const int slot = (int)(c->enq % RING), par = (int)(c->enq % NPAR);
     if (c->want_events && !c->events_only) {
         // polling -> events, between two frames.  The frames already enqueued were ordered by the gates: (i) the last of them expects THIS frame's
@@ -935,12 +941,13 @@ static void enqueue_frame(Context *c) {
         if (n) launch();
     }
     const bool evo = c->events_only;
-    const bool feat_pack = B > 1 && Bz <= FEAT_PACK && !std::getenv("LVT_AMD_NO_FEAT_PACK");  // (k_feat_begin_pack: the buffer gate rides in it)
+    const bool feat_pack = B > 1 && Bz <= FEAT_PACK && c->feat_pack;  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
-        if (!evo && !feat_pack)
-            hipLaunchKernelGGL(k_gate_buf, dim3(1, 1, Bz), dim3(64), 0, sf, S, (seq_t)(c->enq + 1 - NPAR), par);  // polls; see k_gate_buf
-        else if (c->switched_at < 0 || (long)c->enq - NPAR >= c->switched_at)  // (frames from before a switch of the ordering: covered by ev_switch)
+        if (!evo) {  // polls; see k_gate_buf (ev_done is never recorded in this mode)
+            if (!feat_pack) hipLaunchKernelGGL(k_gate_buf, dim3(1, 1, Bz), dim3(64), 0, sf, S, (seq_t)(c->enq + 1 - NPAR), par);
+        } else if (c->switched_at < 0 || (long)c->enq - NPAR >= c->switched_at) {  // (frames from before a switch of the ordering: covered by ev_switch)
             (void)hipStreamWaitEvent(sf, c->ev_done[(int)((c->enq - NPAR) % RING)], 0);
+        }
     }
     if (B == 1) {  // the frame's inputs travel as a kernel argument: no separate "begin" launch, no device read of pinned host memory
         LAUNCH(2, sf, k_score<true>, dim3((p.W + TS_W - 1) / TS_W, (p.H + TS_H - 1) / TS_H, 2), dim3(256), 0, S, c->h_fargs[slot], par, 0, c->brief_from_image ? 0 : 1);
@@ -971,7 +978,7 @@ static void enqueue_frame(Context *c) {
             // a single sequence's tall cells run as cell_split co-operating workgroups (cells_work_split); grid: helpers, main workgroups, pull, padded to 8
             const int ns = (B == 1 && !p.big_cell_strips) ? c->cell_split : 0;
             const int gx = (ns >= 2) ? ((((p.n_cells + 7) & ~7) * ns + pull_wgs + 7) & ~7) : p.n_cells + pull_wgs;
-            if (c->mixed) LAUNCH(3, sf, k_cells_mixed, dim3(c->n_cells_wgs), dim3(1024), cells_lds_bytes(c->cells_raw_cap), (const Seq *)S, c->d_cells_tab, pass, par, c->cells_raw_cap);
+            if (c->mixed) LAUNCH(3, sf, k_cells_mixed, dim3(c->n_cells_wgs), dim3(1024), cells_lds_bytes(c->cells_raw_cap), S, c->d_cells_tab, pass, par, c->cells_raw_cap);
             else LAUNCH_S(3, sf, k_cells, (B == 1 ? dim3(gx, 2, 1) : dim3(p.n_cells * 2 * Bz, 1, 1)), dim3(1024), cells_lds_bytes(c->cells_raw_cap), pass, par, c->cell_order, 2 * Bz, c->cells_raw_cap, c->next_pull, ns, (++c->cell_token ? c->cell_token : ++c->cell_token));
             // (a mixed batch: when ANY sequence has cells tall enough to cut, over the largest grid -- a sequence without such cells leaves at cell_big != 1,
             //  a cell index beyond a sequence's grid at cell_begin)
@@ -993,10 +1000,10 @@ static void enqueue_frame(Context *c) {
         (void)hipStreamWaitEvent(sf, c->ev_depth, 0);
         c->depth_wait = false;
     }
-    LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, (const Seq *)S, par);
+    LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
-    if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, (const Seq *)S, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
-    else LAUNCH_S(6, sf, k_brief, dim3(64, 2, Bz), dim3(256), 0, (const Seq *)S, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
+    if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
+    else LAUNCH_S(6, sf, k_brief, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
     if (!evo && !brief_publishes) hipLaunchKernelGGL(k_feat_done, dim3(Bz), dim3(64), 0, sf, S, par, (seq_t)(c->enq + 1));
     const int bl = c->binned_lists ? 1 : 0;
     if (evo && bl && c->sensor == 1) LAUNCH_SM(19, sf, k_hamming_batched_lists, MODE_ROW, dim3(c->lists_wgs_row, 1, Bz), dim3(LS_THREADS), LS_LDS_BYTES, par, (seq_t)0);
