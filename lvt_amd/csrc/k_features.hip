@@ -564,8 +564,8 @@ __device__ __forceinline__ void wave_introsort_segment(uint32_t *arr, int first,
     }
 }
 
-// LDS carve (bytes): keys 4*RAW | uf 4*RAW | root 2*RAW | abv 2*RAW | nms 2*RAW | row_first/row_end | misc
-constexpr int cells_lds_bytes(int raw_cap) { return raw_cap * 15 + 2 * 1024 * 4 + 64 * 4 + 3 * 64 * 4 + 64; }
+// LDS carve (bytes): keys 4*RAW | uf 4*RAW | root 2*RAW | abv 2*RAW | nms 2*RAW | row_first/row_end | scan | misc | tie RAW
+constexpr int cells_lds_bytes(int raw_cap) { return raw_cap * 15 + 2 * 1024 * 4 + 64 * 4 + 64; }
 constexpr int CELLS_LDS_BYTES = cells_lds_bytes(RAW_CAP);
 constexpr int RAW_CAP_SMALL = 4700;  // 80 KB: two k_cells workgroups per CU (lvt_host.hip, Context::cells_raw_cap)
 
@@ -590,7 +590,7 @@ struct CellGeom {
 // instructions to count and a find-first-set walk over its corners to emit, instead of ~100 + ~160 for the scalar loops
 // -- one CU runs all 16 wavefronts of the cell, so this phase is VALU-bound.
 template <int XB = 10>
-__device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, int cap, int *scan, long long *dbg = nullptr, int ly_off = 0) {
+__device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, int cap, int *scan, long long *dbg = nullptr) {
     const int tid = threadIdx.x;
     const int xa = g.X0 + 3, xb = g.X0 + g.cw - 4;  // inclusive pixel range
     const int c0 = xa >> 4, c1 = xb >> 4;
@@ -653,7 +653,9 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
     }
     int total;
     int off = block_excl_scan(cnt, scan, &total);
-    auto emit16 = [&](const uint4 &v, int ly, int gx0) {
+    int ly = 0;  // cell-local row of the chunk being emitted.  (Through the scope, not as a parameter of emit16: as a parameter k_gather, which inlines this for the retry pass
+    // at its cap of 128 registers, takes 128 VGPRs where it had 126 / 127 -- measured)
+    auto emit16 = [&](const uint4 &v, int gx0) {
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         if ((w[0] | w[1] | w[2] | w[3]) == 0) return;
         if (swar) {
@@ -664,7 +666,7 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
                     const int b = (__ffs((int)m) - 1) >> 3;
                     m &= m - 1;
                     const int s = (w[k] >> (8 * b)) & 255;
-                    if (off < cap) keys[off] = mk_key<XB>(ly + ly_off, gx0 + 4 * k + b - g.X0, s);
+                    if (off < cap) keys[off] = mk_key<XB>(ly, gx0 + 4 * k + b - g.X0, s);
                     off++;
                 }
             }
@@ -675,7 +677,7 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
             const int s = (w[b >> 2] >> (8 * (b & 3))) & 255;
             const int gx = gx0 + b;
             if (s >= g.threshold && gx >= xa && gx <= xb) {
-                if (off < cap) keys[off] = mk_key<XB>(ly + ly_off, gx - g.X0, s);
+                if (off < cap) keys[off] = mk_key<XB>(ly, gx - g.X0, s);
                 off++;
             }
         }
@@ -685,12 +687,16 @@ __device__ __forceinline__ int cell_compact(const CellGeom &g, uint32_t *keys, i
 #pragma unroll
             for (int u = 0; u < KEEP; u++) {
                 const int it = it0 + u;
-                if (it < it1) emit16(kv[u], 3 + it / nchunk, (c0 + it % nchunk) << 4);
+                if (it < it1) {
+                    ly = 3 + it / nchunk;
+                    emit16(kv[u], (c0 + it % nchunk) << 4);
+                }
             }
         } else {
             for (int it = it0; it < it1; it++) {
-                const int ly = 3 + it / nchunk, gx0 = (c0 + it % nchunk) << 4;
-                emit16(*reinterpret_cast<const uint4 *>(g.score + (size_t)(g.Y0 + ly) * g.pp + gx0), ly, gx0);
+                const int gx0 = (c0 + it % nchunk) << 4;
+                ly = 3 + it / nchunk;
+                emit16(*reinterpret_cast<const uint4 *>(g.score + (size_t)(g.Y0 + ly) * g.pp + gx0), gx0);
             }
         }
     }
@@ -742,6 +748,53 @@ __device__ __forceinline__ int cell_gather_segments(const FrameBuf &FB, int eye,
     return total;
 }
 
+// One cell's work arrays: in LDS (I = u16, the workgroup's carve) or in the cell's global scratch (I = u32).  keys / uf / root / abv / nms / tie hold `cap`
+// elements each; row_first / row_end hold an entry per cell row for the NMS and are the ANMS's 256-entry histograms afterwards; scan [64] and misc [16] are
+// always the workgroup's LDS ones.
+template <typename I>
+struct CellArr {
+    uint32_t *keys, *uf;
+    I *root, *abv, *nms;
+    uint8_t *tie;
+    int *row_first, *row_end, *scan, *misc;
+    int cap;
+};
+using CellLds = CellArr<uint16_t>;  // the LDS image of one cell's workgroup
+__device__ __forceinline__ CellLds carve_cell_lds(uint8_t *smem, int raw_cap = RAW_CAP) {  // raw_cap even
+    CellLds L;
+    L.keys = reinterpret_cast<uint32_t *>(smem);
+    L.uf = L.keys + raw_cap;
+    L.root = reinterpret_cast<uint16_t *>(L.uf + raw_cap);
+    L.abv = L.root + raw_cap;
+    L.nms = L.abv + raw_cap;
+    L.row_first = reinterpret_cast<int *>(L.nms + raw_cap);  // [1024]
+    L.row_end = L.row_first + 1024;                          // [1024]
+    L.scan = L.row_end + 1024;                               // [64]
+    L.misc = L.scan + 64;                                    // [16]
+    L.tie = reinterpret_cast<uint8_t *>(L.misc + 16);        // [raw_cap]
+    L.cap = raw_cap;
+    return L;
+}
+// the arrays of a dense / very large cell in its global scratch, sized for every pixel of the cell (the region is cw ch 6 words; this takes 5.25 cw ch, + 2 ch with the
+// row tables).  A cell taller than the LDS row tables (`rows_in_scratch`) keeps its own behind the tie bytes.
+__device__ __forceinline__ CellArr<uint32_t> cell_scratch_arr(const Seq &S, int eye, int cell, const CellGeom &g, const CellLds &L, bool rows_in_scratch) {
+    const size_t cap = (size_t)g.cw * g.ch;
+    CellArr<uint32_t> G;
+    G.keys = S.cell_scratch[eye] + S.cell_scratch_off[cell];
+    G.uf = G.keys + cap;
+    G.root = G.uf + cap;
+    G.abv = G.root + cap;
+    G.nms = G.abv + cap;
+    G.tie = reinterpret_cast<uint8_t *>(G.nms + cap);
+    int *rows = reinterpret_cast<int *>(G.nms + cap + (cap + 3) / 4);  // row_first [ch], row_end [ch]
+    G.row_first = rows_in_scratch ? rows : L.row_first;
+    G.row_end = rows_in_scratch ? rows + g.ch : L.row_end;
+    G.scan = L.scan;
+    G.misc = L.misc;
+    G.cap = (int)cap;
+    return G;
+}
+
 // AGAST NMS + LVT ANMS of one cell on arrays that live either in LDS (I = u16) or in global scratch
 // (I = u32).  Writes the cell's key points to `out` and returns how many.
 #define STAMP(k) do { if (dbg && threadIdx.x == 0) dbg[k] = clock64(); } while (0)
@@ -749,10 +802,13 @@ __device__ __forceinline__ int cell_gather_segments(const FrameBuf &FB, int eye,
 // order, keys / root are intact (root[i] = representative of corner i's 4-connected component).  row_first / row_end: n_rows entries (the cell's height
 // at most).
 template <typename I, int XB = 10>
-__device__ __forceinline__ int cell_nms(uint32_t *keys, uint32_t *uf, I *root, I *abv, I *nms, uint8_t *tie, int n_raw, int *row_first, int *row_end, int *scan,
-                                        long long *dbg, int n_rows = CELL_SIDE_LDS) {
+__device__ __forceinline__ int cell_nms(const CellArr<I> &A, int n_raw, long long *dbg, int n_rows = CELL_SIDE_LDS) {
     constexpr uint32_t NONE = IdxT<I>::NONE, LEFT = IdxT<I>::LEFT, MAXF = IdxT<I>::MAXF;
     const int tid = threadIdx.x;
+    uint32_t *const keys = A.keys, *const uf = A.uf;
+    I *const root = A.root, *const abv = A.abv, *const nms = A.nms;
+    uint8_t *const tie = A.tie;
+    int *const row_first = A.row_first, *const row_end = A.row_end, *const scan = A.scan;
     STAMP(2);
     // ---------------- neighbour links, union-find over 4-connected corner pixels
     for (int i = tid; i < n_rows; i += 1024) {
@@ -935,352 +991,360 @@ __device__ __forceinline__ int cell_nms(uint32_t *keys, uint32_t *uf, I *root, I
     return n_kp;
 }
 
-// second half: LVT's ANMS when the cell is too dense (handler.cpp:140-143, 34-83), else the survivors as they are.  arr = uf[0..n_kp) in
-// raster order; keys / root / abv / nms are scratch of n_cap elements each.
-// `parts`: 1 = std::sort emulation + rank (-> sorted[] in keys), 2 = suppression radii of the key points i_first, i_first + i_stride, ...
-// (sorted[] in keys -> r2[] in uf), 4 = decision radius + emit (sorted[] in keys, r2[] in uf).  7 = the whole thing on one workgroup;
-// the oversized-cell kernels run the parts in three launches, the radii on several workgroups (they are n^2 / 2 distances).
-constexpr int ANMS_SORT = 1, ANMS_RADII = 2, ANMS_SELECT = 4, ANMS_ALL = 7;
-template <typename I, int XB = 10>
-__device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32_t *keys, uint32_t *uf, I *root, I *abv, I *nms, int n_kp, int n_cap, int *row_first,
-                                         int *row_end, int *scan, int *misc, float *out, long long *dbg, int n_raw_dbg, int parts = ANMS_ALL, int i_first = 0,
-                                         int i_stride = 1) {
-    constexpr uint32_t NONE = IdxT<I>::NONE, LEFT = IdxT<I>::LEFT, MAXF = IdxT<I>::MAXF;
-    (void)NONE, (void)LEFT, (void)MAXF;
+// second half: LVT's ANMS when the cell is too dense (handler.cpp:140-143, 34-83), in three parts -- the oversized-cell kernels run them in three launches, the
+// radii on several workgroups (they are n^2 / 2 distances).  uf[0..n_kp) holds the survivors in raster order; keys / root / abv / nms are scratch.
+// part 1: std::sort emulation + rank, uf[] -> sorted[] in keys
+template <typename I>
+__device__ __forceinline__ void anms_sort(const CellArr<I> &A, int n_kp, long long *dbg) {
     const int tid = threadIdx.x;
-    uint32_t *arr = uf;
-    const int n_raw = n_raw_dbg;
-    // ---------------- ANMS when the cell is too dense (handler.cpp:140-143, 34-83)
+    uint32_t *const arr = A.uf, *const sorted = A.keys;  // raw keys no longer needed
+    I *const posL = A.root, *const posR = A.abv, *const nms = A.nms;  // free after NMS
+    int *const row_first = A.row_first, *const row_end = A.row_end, *const misc = A.misc;
+    const int n_cap = A.cap;
+    // ---- std::__introsort_loop.  The segments of one recursion level are disjoint: the first levels run level by level, one
+    // wavefront per segment with a workgroup barrier between levels; as soon as a level holds one segment per wavefront each
+    // wavefront finishes its segments depth-first on its own (no more barriers, nobody waits for the level's largest segment).
+    // Queues and stacks live in the dead nms[] array.
+    {
+        int *q = reinterpret_cast<int *>(nms);
+        constexpr int DFS_AT = 64;  // (also bounds the queues: a level never holds more than 2 * DFS_AT segments)
+        constexpr int qcap = 2 * DFS_AT;  // per level (a level is handed over to the depth-first part at DFS_AT segments)
+        static_assert((6 * qcap + 16 * 96) * sizeof(int) <= (size_t)RAW_CAP_SMALL * sizeof(uint16_t), "queues + stacks must fit the nms[] array of the smallest LDS instance");
+        int *qa = q, *qb = q + 3 * qcap;
+        int *stacks = q + 6 * qcap;  // [16 wavefronts][3 * 32]
+        const int nw = blockDim.x >> 6;
+        if (tid == 0) {
+            int depth0 = 0;
+            for (int v = n_kp; v > 1; v >>= 1) depth0++;
+            qa[0] = 0, qa[1] = n_kp, qa[2] = 2 * depth0;
+            misc[1] = (n_kp > 16) ? 1 : 0;
+            misc[2] = 0;
+        }
+        __syncthreads();
+        int levels = 0;
+        while (true) {
+            const int cnt = misc[1];
+            if (cnt == 0) break;
+            levels++;
+            if (cnt >= DFS_AT) {  // depth-first from here
+                for (int sgi = wave_id(); sgi < cnt; sgi += nw)
+                    wave_introsort_segment<I>(arr, qa[3 * sgi], qa[3 * sgi + 1], qa[3 * sgi + 2], posL, posR, stacks + 96 * wave_id());
+                break;
+            }
+            for (int sgi = wave_id(); sgi < cnt; sgi += nw) {
+                const int first = qa[3 * sgi], last = qa[3 * sgi + 1], depth = qa[3 * sgi + 2];
+                if (depth == 0) {
+                    if (lane_id() == 0) heap_sort_seq(arr + first, last - first);
+                    continue;
+                }
+                const int cut = wave_partition_pivot<I>(arr, first, last, posL, posR);
+                if (lane_id() == 0) {
+                    if (last - cut > 16) {
+                        const int o = atomicAdd(&misc[2], 1);
+                        qb[3 * o] = cut, qb[3 * o + 1] = last, qb[3 * o + 2] = depth - 1;
+                    }
+                    if (cut - first > 16) {
+                        const int o = atomicAdd(&misc[2], 1);
+                        qb[3 * o] = first, qb[3 * o + 1] = cut, qb[3 * o + 2] = depth - 1;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                misc[1] = misc[2];
+                misc[2] = 0;
+            }
+            int *t = qa;
+            qa = qb;
+            qb = t;
+            __syncthreads();
+        }
+        __syncthreads();
+        if (dbg && tid == 0) dbg[41] = levels;
+    }
+    STAMP(6);
+    // ---- final insertion sort == stable sort by response (descending).  rank = #(greater response) +
+    // #(equal response earlier in the array); the second term comes from one wavefront walking the array in
+    // 64-element steps with a running 256-bin histogram, equal keys inside a step grouped by 8 ballots.
+    // More than 512 key points: every wavefront walks ITS block of the array with a histogram of its own (in the dead nms[] area), the
+    // blocks' counts are prefix-summed per key afterwards -- the single-wavefront walk over 1 650 key points took 17k cycles.
+    int *hist = row_first;    // [256] (row tables are dead)
+    int *gtab = row_end;      // [256] #elements with a strictly greater response
+    const int nwv = blockDim.x >> 6;
+    // (the per-wavefront histograms live in the dead nms[] array: [nwv][256] ints -- with the small LDS instance of a batch, RAW_CAP_SMALL, that array is too short)
+    const bool par_rank = n_kp > 512 && (size_t)n_cap * sizeof(I) >= (size_t)nwv * 256 * sizeof(int);
+    const int blk = par_rank ? (((n_kp + nwv - 1) / nwv + 63) & ~63) : n_kp;  // elements per wavefront (a multiple of 64)
+    int *hw = par_rank ? reinterpret_cast<int *>(nms) : hist;                  // [nwv][256] | [256]
+    if (par_rank) {
+        for (int k = tid; k < nwv * 256; k += 1024) hw[k] = 0;
+        __syncthreads();
+    }
+    if (par_rank || wave_id() == 0) {
+        const int lane = lane_id();
+        const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+        int *myh = par_rank ? hw + 256 * wave_id() : hist;
+        if (!par_rank) {
+            for (int k = lane; k < 256; k += 64) hist[k] = 0;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        }
+        const int b_lo = par_rank ? wave_id() * blk : 0, b_hi = min(n_kp, b_lo + blk);
+        for (int base = b_lo; base < b_hi; base += 64) {
+            const int i = base + lane;
+            const bool valid = i < b_hi;
+            const int key = valid ? key_r(arr[i]) : 0;
+            uint64_t m = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                const uint64_t bb = __ballot((key >> b) & 1);
+                m &= ((key >> b) & 1) ? bb : ~bb;
+            }
+            if (valid) {
+                const int hb = myh[key];
+                posL[i] = (I)(hb + __popcll(m & lt_mask));
+                if ((m & lt_mask) == 0ull) myh[key] = hb + __popcll(m);  // group leader
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        }
+    }
+    if (par_rank) {  // per key: the blocks' counts -> exclusive prefix over the blocks (in place), total -> hist
+        __syncthreads();
+        if (tid < 256) {
+            int run = 0;
+            for (int w = 0; w < nwv; w++) {
+                const int t = hw[256 * w + tid];
+                hw[256 * w + tid] = run;
+                run += t;
+            }
+            hist[tid] = run;
+        }
+        __syncthreads();
+    }
+    if (wave_id() == 0) {
+        const int lane = lane_id();
+        // suffix sums: gtab[k] = sum_{k' > k} hist[k']
+        int h[4], tot = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            h[q] = hist[4 * lane + q];
+            tot += h[q];
+        }
+        int incl = tot;  // inclusive suffix scan over lanes
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_down(incl, d, 64);
+            if (lane + d < 64) incl += t;
+        }
+        int above = incl - tot;
+#pragma unroll
+        for (int q = 3; q >= 0; q--) {
+            gtab[4 * lane + q] = above;
+            above += h[q];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_kp; i += 1024) {
+        const uint32_t k = arr[i];
+        const int kr = key_r(k);
+        sorted[gtab[kr] + (par_rank ? hw[256 * (i / blk) + kr] : 0) + (int)posL[i]] = k;
+    }
+    __syncthreads();
+    STAMP(7);
+}
+
+// part 2: suppression radii of the key points i_first, i_first + i_stride, ... (sorted[] in keys -> r2[] in uf)
+template <typename I, int XB = 10>
+__device__ __forceinline__ void anms_radii(const CellArr<I> &A, int n_kp, int i_first, int i_stride) {
+    const int tid = threadIdx.x;
+    uint32_t *const sorted = A.keys;
+    // ---- suppression radius^2 (integers: exact in the reference's float arithmetic too).  sorted[] is descending, so the points
+    // stronger than 1.11 * response are a prefix [0, lo) whose length a binary search finds, and lo never decreases along the
+    // array.  One lane per key point; the lanes of a wave walk the prefix TOGETHER (every lane reads the same word: an LDS
+    // broadcast), coordinates packed as two 16-bit halves so that a distance is one packed subtract and one dot product.  The
+    // phase is VALU-bound on the cell's single CU (n^2 / 2 distances): 3 instructions per distance where the scalar form had 8.
+    uint32_t *const r2 = A.uf;  // arr consumed
+    uint32_t *sxy = reinterpret_cast<uint32_t *>(A.root);  // posL (and, with 16-bit indices, the adjacent posR) are dead: x | y << 16
+    for (int i = tid; i < n_kp; i += 1024) {
+        const uint32_t k = sorted[i];
+        sxy[i] = (uint32_t)key_x<XB>(k) | ((uint32_t)key_y<XB>(k) << 16);
+    }
+    __syncthreads();
+    // this workgroup's key points: i_first + k * i_stride, k = 0 .. n_pts - 1 (all of them when the cell has one workgroup)
+    const int n_pts = (n_kp > i_first) ? (n_kp - i_first + i_stride - 1) / i_stride : 0;
+    // few key points: 2, 4 or 8 lanes share one (its prefix in interleaved groups of four), so that all 16 wavefronts have work
+    auto radii = [&](auto lpp_log_c) {
+        constexpr int lpp_log = decltype(lpp_log_c)::value, lpp = 1 << lpp_log, ppp = 1024 >> lpp_log, step = 4 * lpp;
+        for (int base = 0; base < n_pts; base += ppp) {
+            const int k = base + (tid >> lpp_log), sub = tid & (lpp - 1);
+            const int i = i_first + k * i_stride;
+            const bool valid = k < n_pts;
+            int lo = 0;
+            if (valid) {
+                const float response = (float)key_r(sorted[i]) * 1.11f;
+                int hi = i;  // first index in [0,i) whose response is NOT > `response`
+                while (lo < hi) {
+                    const int m = (lo + hi) >> 1;
+                    if ((float)key_r(sorted[m]) > response) lo = m + 1;
+                    else hi = m;
+                }
+            }
+            const int wave_first = base + ((tid & ~63) >> lpp_log);
+            if (wave_first < n_pts) {  // (wave-uniform)
+                const int n_valid = min(64 >> lpp_log, n_pts - wave_first);
+                const int lo_min = __shfl(lo, 0, 64), lo_max = __shfl(lo, (n_valid << lpp_log) - 1, 64);
+                const s16x2 pi = __builtin_bit_cast(s16x2, sxy[min(i, n_kp - 1)]);
+                uint32_t best = 0xFFFFFFFFu;
+                int j = 4 * sub;
+                for (; j + 4 <= lo_min; j += step) {  // every lane's prefix covers these
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const s16x2 d = pi - __builtin_bit_cast(s16x2, sxy[j + c]);
+                        best = min(best, (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false));
+                    }
+                }
+                for (; j < lo_max; j += step) {
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const s16x2 d = pi - __builtin_bit_cast(s16x2, sxy[j + c]);  // (reads at most 3 words past the prefix: inside the arrays)
+                        const uint32_t d2 = (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);
+                        best = (j + c < lo) ? min(best, d2) : best;
+                    }
+                }
+                if (lpp > 1) best = min(best, (uint32_t)__shfl_xor((int)best, 1, 64));
+                if (lpp > 2) best = min(best, (uint32_t)__shfl_xor((int)best, 2, 64));
+                if (lpp > 4) best = min(best, (uint32_t)__shfl_xor((int)best, 4, 64));
+                if (valid && sub == 0) r2[i] = best;
+            }
+        }
+    };
+    if (n_pts <= 128) radii(std::integral_constant<int, 3>{});
+    else if (n_pts <= 512) radii(std::integral_constant<int, 2>{});
+    else if (n_pts <= 1024) radii(std::integral_constant<int, 1>{});
+    else radii(std::integral_constant<int, 0>{});
+    __syncthreads();
+}
+
+// part 3: decision radius + emit (sorted[] in keys, r2[] in uf); returns the number of key points kept
+template <typename I, int XB = 10>
+__device__ __forceinline__ int anms_select(const Seq &S, const CellGeom &g, const CellArr<I> &A, int n_kp, float *out, long long *dbg) {
+    const int tid = threadIdx.x;
+    uint32_t *const sorted = A.keys, *const r2 = A.uf;
+    int *const row_first = A.row_first, *const scan = A.scan, *const misc = A.misc;
     const int max_kp = S.prm.max_kp_cell;
     const float fX0 = (float)g.X0, fY0 = (float)g.Y0;
     int n_out = 0;
-    if (n_kp > max_kp) {
-        I *posL = root;  // free after NMS
-        I *posR = abv;
-        uint32_t *sorted = keys;  // raw keys no longer needed
-        if (parts & ANMS_SORT) {
-        // ---- std::__introsort_loop.  The segments of one recursion level are disjoint: the first levels run level by level, one
-        // wavefront per segment with a workgroup barrier between levels; as soon as a level holds one segment per wavefront each
-        // wavefront finishes its segments depth-first on its own (no more barriers, nobody waits for the level's largest segment).
-        // Queues and stacks live in the dead nms[] array.
-        {
-            int *q = reinterpret_cast<int *>(nms);
-            constexpr int DFS_AT = 64;  // (also bounds the queues: a level never holds more than 2 * DFS_AT segments)
-            constexpr int qcap = 2 * DFS_AT;  // per level (a level is handed over to the depth-first part at DFS_AT segments)
-            static_assert((6 * qcap + 16 * 96) * sizeof(int) <= (size_t)RAW_CAP_SMALL * sizeof(uint16_t), "queues + stacks must fit the nms[] array of the smallest LDS instance");
-            int *qa = q, *qb = q + 3 * qcap;
-            int *stacks = q + 6 * qcap;  // [16 wavefronts][3 * 32]
-            const int nw = blockDim.x >> 6;
-            if (tid == 0) {
-                int depth0 = 0;
-                for (int v = n_kp; v > 1; v >>= 1) depth0++;
-                qa[0] = 0, qa[1] = n_kp, qa[2] = 2 * depth0;
-                misc[1] = (n_kp > 16) ? 1 : 0;
-                misc[2] = 0;
-            }
-            __syncthreads();
-            int levels = 0;
-            while (true) {
-                const int cnt = misc[1];
-                if (cnt == 0) break;
-                levels++;
-                if (cnt >= DFS_AT) {  // depth-first from here
-                    for (int sgi = wave_id(); sgi < cnt; sgi += nw)
-                        wave_introsort_segment<I>(arr, qa[3 * sgi], qa[3 * sgi + 1], qa[3 * sgi + 2], posL, posR, stacks + 96 * wave_id());
-                    break;
+    STAMP(8);
+    // ---- decisionRadius = (max_kp)-th element (0-based) of the radii sorted descending: radix select over
+    // three 8-bit digits (finite radii^2 < 2^24 in a cell of at most CELL_SIDE_LDS px; 0xFFFFFFFF stands for sqrt(FLT_MAX)).  The wide
+    // path's radii^2 reach 2 (CELL_SIDE_MAX - 7)^2 > 2^24: a fourth digit.
+    constexpr int TOP_SHIFT = (XB > 10) ? 24 : 16;
+    constexpr uint32_t VAL_MASK = (XB > 10) ? 0xFFFFFFFFu : 0xFFFFFFu;
+    static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 24), "three digits hold every finite radius^2 of an LDS-path cell");
+    {
+        int *h = row_first;  // [256]
+        if (tid == 0) {
+            misc[0] = 0;      // selected prefix
+            misc[3] = max_kp; // remaining rank
+            misc[4] = 0;      // #infinite
+            misc[5] = 0;      // done flag
+        }
+        __syncthreads();
+        int ninf = 0;
+        for (int i = tid; i < n_kp; i += 1024) ninf += (r2[i] == 0xFFFFFFFFu) ? 1 : 0;
+        if (ninf) atomicAdd(&misc[4], ninf);
+        __syncthreads();
+        if (tid == 0) {
+            if (misc[3] < misc[4]) {
+                misc[0] = (int)0xFFFFFFFFu;
+                misc[5] = 1;
+            } else
+                misc[3] -= misc[4];
+        }
+        __syncthreads();
+        if (!misc[5]) {
+            for (int shift = TOP_SHIFT; shift >= 0; shift -= 8) {
+                for (int k = tid; k < 256; k += 1024) h[k] = 0;
+                __syncthreads();
+                const uint32_t prefix = (uint32_t)misc[0];
+                const uint32_t himask = (shift == TOP_SHIFT) ? 0u : (VAL_MASK & ~((1u << (shift + 8)) - 1u));
+                for (int i = tid; i < n_kp; i += 1024) {
+                    const uint32_t v = r2[i];
+                    if (v != 0xFFFFFFFFu && (v & himask) == (prefix & himask)) atomicAdd(&h[(v >> shift) & 255u], 1);
                 }
-                for (int sgi = wave_id(); sgi < cnt; sgi += nw) {
-                    const int first = qa[3 * sgi], last = qa[3 * sgi + 1], depth = qa[3 * sgi + 2];
-                    if (depth == 0) {
-                        if (lane_id() == 0) heap_sort_seq(arr + first, last - first);
-                        continue;
+                __syncthreads();
+                if (wave_id() == 0) {  // digit d with #(digit > d) <= rem < #(digit >= d): suffix scan over 256 bins
+                    const int lane = lane_id();
+                    const int rem = misc[3];
+                    int hh[4], tot = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        hh[q] = h[4 * lane + q];
+                        tot += hh[q];
                     }
-                    const int cut = wave_partition_pivot<I>(arr, first, last, posL, posR);
-                    if (lane_id() == 0) {
-                        if (last - cut > 16) {
-                            const int o = atomicAdd(&misc[2], 1);
-                            qb[3 * o] = cut, qb[3 * o + 1] = last, qb[3 * o + 2] = depth - 1;
+                    int incl = tot;
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const int t = __shfl_down(incl, d, 64);
+                        if (lane + d < 64) incl += t;
+                    }
+                    int above = incl - tot;
+                    int found_d = -1, found_above = 0;
+#pragma unroll
+                    for (int q = 3; q >= 0; q--) {
+                        if (found_d < 0 && above <= rem && rem < above + hh[q]) {
+                            found_d = 4 * lane + q;
+                            found_above = above;
                         }
-                        if (cut - first > 16) {
-                            const int o = atomicAdd(&misc[2], 1);
-                            qb[3 * o] = first, qb[3 * o + 1] = cut, qb[3 * o + 2] = depth - 1;
-                        }
+                        above += hh[q];
+                    }
+                    const uint64_t fm = __ballot(found_d >= 0);
+                    if (fm == 0ull) {  // rem >= total (cannot happen: n_kp > max_kp): fall to digit 0
+                        if (lane == 0) misc[0] = (int)prefix;
+                    } else if (found_d >= 0) {
+                        misc[3] = rem - found_above;
+                        misc[0] = (int)(prefix | ((uint32_t)found_d << shift));
                     }
                 }
                 __syncthreads();
-                if (tid == 0) {
-                    misc[1] = misc[2];
-                    misc[2] = 0;
-                }
-                int *t = qa;
-                qa = qb;
-                qb = t;
-                __syncthreads();
-            }
-            __syncthreads();
-            if (dbg && tid == 0) dbg[41] = levels;
-        }
-        STAMP(6);
-        // ---- final insertion sort == stable sort by response (descending).  rank = #(greater response) +
-        // #(equal response earlier in the array); the second term comes from one wavefront walking the array in
-        // 64-element steps with a running 256-bin histogram, equal keys inside a step grouped by 8 ballots.
-        // More than 512 key points: every wavefront walks ITS block of the array with a histogram of its own (in the dead nms[] area), the
-        // blocks' counts are prefix-summed per key afterwards -- the single-wavefront walk over 1 650 key points took 17k cycles.
-        int *hist = row_first;    // [256] (row tables are dead)
-        int *gtab = row_end;      // [256] #elements with a strictly greater response
-        const int nwv = blockDim.x >> 6;
-        // (the per-wavefront histograms live in the dead nms[] array: [nwv][256] ints -- with the small LDS instance of a batch, RAW_CAP_SMALL, that array is too short)
-        const bool par_rank = n_kp > 512 && (size_t)n_cap * sizeof(I) >= (size_t)nwv * 256 * sizeof(int);
-        const int blk = par_rank ? (((n_kp + nwv - 1) / nwv + 63) & ~63) : n_kp;  // elements per wavefront (a multiple of 64)
-        int *hw = par_rank ? reinterpret_cast<int *>(nms) : hist;                  // [nwv][256] | [256]
-        if (par_rank) {
-            for (int k = tid; k < nwv * 256; k += 1024) hw[k] = 0;
-            __syncthreads();
-        }
-        if (par_rank || wave_id() == 0) {
-            const int lane = lane_id();
-            const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-            int *myh = par_rank ? hw + 256 * wave_id() : hist;
-            if (!par_rank) {
-                for (int k = lane; k < 256; k += 64) hist[k] = 0;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            }
-            const int b_lo = par_rank ? wave_id() * blk : 0, b_hi = min(n_kp, b_lo + blk);
-            for (int base = b_lo; base < b_hi; base += 64) {
-                const int i = base + lane;
-                const bool valid = i < b_hi;
-                const int key = valid ? key_r(arr[i]) : 0;
-                uint64_t m = __ballot(valid);
-#pragma unroll
-                for (int b = 0; b < 8; b++) {
-                    const uint64_t bb = __ballot((key >> b) & 1);
-                    m &= ((key >> b) & 1) ? bb : ~bb;
-                }
-                if (valid) {
-                    const int hb = myh[key];
-                    posL[i] = (I)(hb + __popcll(m & lt_mask));
-                    if ((m & lt_mask) == 0ull) myh[key] = hb + __popcll(m);  // group leader
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             }
         }
-        if (par_rank) {  // per key: the blocks' counts -> exclusive prefix over the blocks (in place), total -> hist
-            __syncthreads();
-            if (tid < 256) {
-                int run = 0;
-                for (int w = 0; w < nwv; w++) {
-                    const int t = hw[256 * w + tid];
-                    hw[256 * w + tid] = run;
-                    run += t;
-                }
-                hist[tid] = run;
-            }
-            __syncthreads();
+    }
+    STAMP(9);
+    const uint32_t decision = (uint32_t)misc[0];
+    __syncthreads();
+    // the reference keeps sqrtf(radius^2) >= sqrtf(decision^2) on float radii^2 (handler.cpp:64-77).  Below 2^22 distinct integers have distinct
+    // square roots and the integer test is the same test -- every cell of at most CELL_SIDE_LDS px; above, neighbouring integers can share one,
+    // so the wide path also keeps a radius^2 below a decision of 2^22 or more whose square root equals the decision's (the float of the exact
+    // integer is the reference's once-rounded dx^2 + dy^2).  Infinite radii (0xFFFFFFFF) only ever take the integer test.
+    static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 22), "integer radius test exact");
+    auto keep_r2 = [&](uint32_t v) -> bool {
+        if constexpr (XB > 10) {
+            return v >= decision || (decision >= (1u << 22) && decision != 0xFFFFFFFFu && __fsqrt_rn((float)v) == __fsqrt_rn((float)decision));
+        } else {
+            return v >= decision;
         }
-        if (wave_id() == 0) {
-            const int lane = lane_id();
-            // suffix sums: gtab[k] = sum_{k' > k} hist[k']
-            int h[4], tot = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                h[q] = hist[4 * lane + q];
-                tot += h[q];
-            }
-            int incl = tot;  // inclusive suffix scan over lanes
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_down(incl, d, 64);
-                if (lane + d < 64) incl += t;
-            }
-            int above = incl - tot;
-#pragma unroll
-            for (int q = 3; q >= 0; q--) {
-                gtab[4 * lane + q] = above;
-                above += h[q];
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < n_kp; i += 1024) {
-            const uint32_t k = arr[i];
-            const int kr = key_r(k);
-            sorted[gtab[kr] + (par_rank ? hw[256 * (i / blk) + kr] : 0) + (int)posL[i]] = k;
-        }
-        __syncthreads();
-        }
-        STAMP(7);
-        if (!(parts & (ANMS_RADII | ANMS_SELECT))) return n_kp;
-        // ---- suppression radius^2 (integers: exact in the reference's float arithmetic too).  sorted[] is descending, so the points
-        // stronger than 1.11 * response are a prefix [0, lo) whose length a binary search finds, and lo never decreases along the
-        // array.  One lane per key point; the lanes of a wave walk the prefix TOGETHER (every lane reads the same word: an LDS
-        // broadcast), coordinates packed as two 16-bit halves so that a distance is one packed subtract and one dot product.  The
-        // phase is VALU-bound on the cell's single CU (n^2 / 2 distances): 3 instructions per distance where the scalar form had 8.
-        uint32_t *r2 = arr;  // arr consumed
-        if (parts & ANMS_RADII) {
-        uint32_t *sxy = reinterpret_cast<uint32_t *>(root);  // posL (and, with 16-bit indices, the adjacent posR) are dead: x | y << 16
-        for (int i = tid; i < n_kp; i += 1024) {
+    };
+    for (int base = 0; base < n_kp; base += 1024) {
+        const int i = base + tid;
+        const bool keep = (i < n_kp) && keep_r2(r2[i]);
+        int total;
+        const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);
+        if (keep && off < CELL_OUT_CAP) {
             const uint32_t k = sorted[i];
-            sxy[i] = (uint32_t)key_x<XB>(k) | ((uint32_t)key_y<XB>(k) << 16);
+            out[3 * off] = (float)key_x<XB>(k) + fX0;
+            out[3 * off + 1] = (float)key_y<XB>(k) + fY0;
+            out[3 * off + 2] = (float)key_r(k);
         }
-        __syncthreads();
-        // this workgroup's key points: i_first + k * i_stride, k = 0 .. n_pts - 1 (all of them when the cell has one workgroup)
-        const int n_pts = (n_kp > i_first) ? (n_kp - i_first + i_stride - 1) / i_stride : 0;
-        // few key points: 2, 4 or 8 lanes share one (its prefix in interleaved groups of four), so that all 16 wavefronts have work
-        auto radii = [&](auto lpp_log_c) {
-            constexpr int lpp_log = decltype(lpp_log_c)::value, lpp = 1 << lpp_log, ppp = 1024 >> lpp_log, step = 4 * lpp;
-            for (int base = 0; base < n_pts; base += ppp) {
-                const int k = base + (tid >> lpp_log), sub = tid & (lpp - 1);
-                const int i = i_first + k * i_stride;
-                const bool valid = k < n_pts;
-                int lo = 0;
-                if (valid) {
-                    const float response = (float)key_r(sorted[i]) * 1.11f;
-                    int hi = i;  // first index in [0,i) whose response is NOT > `response`
-                    while (lo < hi) {
-                        const int m = (lo + hi) >> 1;
-                        if ((float)key_r(sorted[m]) > response) lo = m + 1;
-                        else hi = m;
-                    }
-                }
-                const int wave_first = base + ((tid & ~63) >> lpp_log);
-                if (wave_first < n_pts) {  // (wave-uniform)
-                    const int n_valid = min(64 >> lpp_log, n_pts - wave_first);
-                    const int lo_min = __shfl(lo, 0, 64), lo_max = __shfl(lo, (n_valid << lpp_log) - 1, 64);
-                    const s16x2 pi = __builtin_bit_cast(s16x2, sxy[min(i, n_kp - 1)]);
-                    uint32_t best = 0xFFFFFFFFu;
-                    int j = 4 * sub;
-                    for (; j + 4 <= lo_min; j += step) {  // every lane's prefix covers these
-#pragma unroll
-                        for (int c = 0; c < 4; c++) {
-                            const s16x2 d = pi - __builtin_bit_cast(s16x2, sxy[j + c]);
-                            best = min(best, (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false));
-                        }
-                    }
-                    for (; j < lo_max; j += step) {
-#pragma unroll
-                        for (int c = 0; c < 4; c++) {
-                            const s16x2 d = pi - __builtin_bit_cast(s16x2, sxy[j + c]);  // (reads at most 3 words past the prefix: inside the arrays)
-                            const uint32_t d2 = (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);
-                            best = (j + c < lo) ? min(best, d2) : best;
-                        }
-                    }
-                    if (lpp > 1) best = min(best, (uint32_t)__shfl_xor((int)best, 1, 64));
-                    if (lpp > 2) best = min(best, (uint32_t)__shfl_xor((int)best, 2, 64));
-                    if (lpp > 4) best = min(best, (uint32_t)__shfl_xor((int)best, 4, 64));
-                    if (valid && sub == 0) r2[i] = best;
-                }
-            }
-        };
-        if (n_pts <= 128) radii(std::integral_constant<int, 3>{});
-        else if (n_pts <= 512) radii(std::integral_constant<int, 2>{});
-        else if (n_pts <= 1024) radii(std::integral_constant<int, 1>{});
-        else radii(std::integral_constant<int, 0>{});
-        __syncthreads();
-        }
-        if (!(parts & ANMS_SELECT)) return n_kp;
-        STAMP(8);
-        // ---- decisionRadius = (max_kp)-th element (0-based) of the radii sorted descending: radix select over
-        // three 8-bit digits (finite radii^2 < 2^24 in a cell of at most CELL_SIDE_LDS px; 0xFFFFFFFF stands for sqrt(FLT_MAX)).  The wide
-        // path's radii^2 reach 2 (CELL_SIDE_MAX - 7)^2 > 2^24: a fourth digit.
-        constexpr int TOP_SHIFT = (XB > 10) ? 24 : 16;
-        constexpr uint32_t VAL_MASK = (XB > 10) ? 0xFFFFFFFFu : 0xFFFFFFu;
-        static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 24), "three digits hold every finite radius^2 of an LDS-path cell");
-        {
-            int *h = row_first;  // [256]
-            if (tid == 0) {
-                misc[0] = 0;      // selected prefix
-                misc[3] = max_kp; // remaining rank
-                misc[4] = 0;      // #infinite
-                misc[5] = 0;      // done flag
-            }
-            __syncthreads();
-            int ninf = 0;
-            for (int i = tid; i < n_kp; i += 1024) ninf += (r2[i] == 0xFFFFFFFFu) ? 1 : 0;
-            if (ninf) atomicAdd(&misc[4], ninf);
-            __syncthreads();
-            if (tid == 0) {
-                if (misc[3] < misc[4]) {
-                    misc[0] = (int)0xFFFFFFFFu;
-                    misc[5] = 1;
-                } else
-                    misc[3] -= misc[4];
-            }
-            __syncthreads();
-            if (!misc[5]) {
-                for (int shift = TOP_SHIFT; shift >= 0; shift -= 8) {
-                    for (int k = tid; k < 256; k += 1024) h[k] = 0;
-                    __syncthreads();
-                    const uint32_t prefix = (uint32_t)misc[0];
-                    const uint32_t himask = (shift == TOP_SHIFT) ? 0u : (VAL_MASK & ~((1u << (shift + 8)) - 1u));
-                    for (int i = tid; i < n_kp; i += 1024) {
-                        const uint32_t v = r2[i];
-                        if (v != 0xFFFFFFFFu && (v & himask) == (prefix & himask)) atomicAdd(&h[(v >> shift) & 255u], 1);
-                    }
-                    __syncthreads();
-                    if (wave_id() == 0) {  // digit d with #(digit > d) <= rem < #(digit >= d): suffix scan over 256 bins
-                        const int lane = lane_id();
-                        const int rem = misc[3];
-                        int hh[4], tot = 0;
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            hh[q] = h[4 * lane + q];
-                            tot += hh[q];
-                        }
-                        int incl = tot;
-                        for (int d = 1; d < 64; d <<= 1) {
-                            const int t = __shfl_down(incl, d, 64);
-                            if (lane + d < 64) incl += t;
-                        }
-                        int above = incl - tot;
-                        int found_d = -1, found_above = 0;
-#pragma unroll
-                        for (int q = 3; q >= 0; q--) {
-                            if (found_d < 0 && above <= rem && rem < above + hh[q]) {
-                                found_d = 4 * lane + q;
-                                found_above = above;
-                            }
-                            above += hh[q];
-                        }
-                        const uint64_t fm = __ballot(found_d >= 0);
-                        if (fm == 0ull) {  // rem >= total (cannot happen: n_kp > max_kp): fall to digit 0
-                            if (lane == 0) misc[0] = (int)prefix;
-                        } else if (found_d >= 0) {
-                            misc[3] = rem - found_above;
-                            misc[0] = (int)(prefix | ((uint32_t)found_d << shift));
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-        STAMP(9);
-        const uint32_t decision = (uint32_t)misc[0];
-        __syncthreads();
-        // the reference keeps sqrtf(radius^2) >= sqrtf(decision^2) on float radii^2 (handler.cpp:64-77).  Below 2^22 distinct integers have distinct
-        // square roots and the integer test is the same test -- every cell of at most CELL_SIDE_LDS px; above, neighbouring integers can share one,
-        // so the wide path also keeps a radius^2 below a decision of 2^22 or more whose square root equals the decision's (the float of the exact
-        // integer is the reference's once-rounded dx^2 + dy^2).  Infinite radii (0xFFFFFFFF) only ever take the integer test.
-        static_assert(XB > 10 || 2 * (CELL_SIDE_LDS - 7) * (CELL_SIDE_LDS - 7) < (1 << 22), "integer radius test exact");
-        auto keep_r2 = [&](uint32_t v) -> bool {
-            if constexpr (XB > 10) {
-                return v >= decision || (decision >= (1u << 22) && decision != 0xFFFFFFFFu && __fsqrt_rn((float)v) == __fsqrt_rn((float)decision));
-            } else {
-                return v >= decision;
-            }
-        };
-        for (int base = 0; base < n_kp; base += 1024) {
-            const int i = base + tid;
-            const bool keep = (i < n_kp) && keep_r2(r2[i]);
-            int total;
-            const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);
-            if (keep && off < CELL_OUT_CAP) {
-                const uint32_t k = sorted[i];
-                out[3 * off] = (float)key_x<XB>(k) + fX0;
-                out[3 * off + 1] = (float)key_y<XB>(k) + fY0;
-                out[3 * off + 2] = (float)key_r(k);
-            }
-            n_out += total;
-        }
-    } else {
-        for (int i = tid; i < n_kp; i += 1024) {
+        n_out += total;
+    }
+    return n_out;
+}
+
+// the survivors as they are, or through the ANMS when the cell is too dense; writes the cell's key points to `out` and returns how many
+template <typename I, int XB = 10>
+__device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, const CellArr<I> &A, int n_kp, int n_raw, float *out, long long *dbg) {
+    int n_out;
+    if (n_kp <= S.prm.max_kp_cell) {
+        const uint32_t *arr = A.uf;
+        const float fX0 = (float)g.X0, fY0 = (float)g.Y0;
+        for (int i = threadIdx.x; i < n_kp; i += 1024) {
             if (i < CELL_OUT_CAP) {
                 const uint32_t k = arr[i];
                 out[3 * i] = (float)key_x<XB>(k) + fX0;
@@ -1289,6 +1353,10 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
             }
         }
         n_out = n_kp;
+    } else {
+        anms_sort<I>(A, n_kp, dbg);
+        anms_radii<I, XB>(A, n_kp, 0, 1);
+        n_out = anms_select<I, XB>(S, g, A, n_kp, out, dbg);
     }
     STAMP(10);
     if (dbg && threadIdx.x == 0) dbg[39] = (long long)n_raw | ((long long)n_kp << 16) | ((long long)n_out << 32);  // (one free slot)
@@ -1296,37 +1364,13 @@ __device__ __forceinline__ int cell_anms(const Seq &S, const CellGeom &g, uint32
 }
 #undef STAMP
 
-// AGAST NMS + LVT ANMS of one cell on arrays that live either in LDS (I = u16) or in global scratch (I = u32).
+// AGAST NMS + LVT ANMS of one cell
 template <typename I>
-__device__ __forceinline__ int cell_nms_anms(const Seq &S, const CellGeom &g, uint32_t *keys, uint32_t *uf, I *root, I *abv, I *nms, uint8_t *tie,
-                                             int n_raw, int n_cap, int *row_first, int *row_end, int *scan, int *stack, int *misc, float *out, long long *dbg) {
-    (void)stack;
-    const int n_kp = cell_nms<I>(keys, uf, root, abv, nms, tie, n_raw, row_first, row_end, scan, dbg);
-    return cell_anms<I>(S, g, keys, uf, root, abv, nms, n_kp, n_cap, row_first, row_end, scan, misc, out, dbg, n_raw);
+__device__ __forceinline__ int cell_nms_anms(const Seq &S, const CellGeom &g, const CellArr<I> &A, int n_raw, float *out, long long *dbg) {
+    const int n_kp = cell_nms<I>(A, n_raw, dbg);
+    return cell_anms<I>(S, g, A, n_kp, n_raw, out, dbg);
 }
 
-// the LDS image of one cell's workgroup
-struct CellLds {
-    uint32_t *keys, *uf;
-    uint16_t *root16, *abv16, *nms16;
-    int *row_first, *row_end, *scan, *stack, *misc;
-    uint8_t *tie8;
-};
-__device__ __forceinline__ CellLds carve_cell_lds(uint8_t *smem, int raw_cap = RAW_CAP) {  // raw_cap even
-    CellLds L;
-    L.keys = reinterpret_cast<uint32_t *>(smem);
-    L.uf = L.keys + raw_cap;
-    L.root16 = reinterpret_cast<uint16_t *>(L.uf + raw_cap);
-    L.abv16 = L.root16 + raw_cap;
-    L.nms16 = L.abv16 + raw_cap;
-    L.row_first = reinterpret_cast<int *>(L.nms16 + raw_cap);  // [1024]
-    L.row_end = L.row_first + 1024;                            // [1024]
-    L.scan = L.row_end + 1024;                                 // [64]
-    L.stack = L.scan + 64;                                     // [192]
-    L.misc = L.stack + 192;                                    // [16]
-    L.tie8 = reinterpret_cast<uint8_t *>(L.misc + 16);          // [RAW_CAP]
-    return L;
-}
 // shared prologue of the three cell kernels: false = nothing to do for this (cell, eye, pass)
 __device__ __forceinline__ bool cell_begin(const Seq &S, const FrameBuf &FB, int eye, int cell, int pass, CellGeom &g, int &cxi) {
     const FeatCtl &ctl = *FB.fc;
@@ -1364,35 +1408,27 @@ __device__ __forceinline__ void cell_finish(const FrameBuf &FB, int eye, int cel
 // dense / very large cell on ONE workgroup: the same algorithm on global scratch sized for every pixel of the cell
 __device__ __forceinline__ int cell_global_path(const Seq &S, const FrameBuf &FB, int eye, int cell, int cxi, bool segs, const CellGeom &g, const CellLds &L, float *out,
                                                 long long *dbg) {
-    const size_t cap = (size_t)g.cw * g.ch;
-    uint32_t *gk = S.cell_scratch[eye] + S.cell_scratch_off[cell];
-    uint32_t *guf = gk + cap, *groot = guf + cap, *gabv = groot + cap, *gnms = gabv + cap;
-    const int n_raw = segs ? cell_gather_segments(FB, eye, g, S.prm.cell_size, cxi, (S.prm.W + TS_W - 1) / TS_W, gk, (int)cap, L.scan) : cell_compact(g, gk, (int)cap, L.scan);
-    return cell_nms_anms<uint32_t>(S, g, gk, guf, groot, gabv, gnms, reinterpret_cast<uint8_t *>(gnms + cap), n_raw, (int)cap, L.row_first, L.row_end, L.scan, L.stack, L.misc, out,
-                                   dbg);
+    const CellArr<uint32_t> G = cell_scratch_arr(S, eye, cell, g, L, false);
+    const int n_raw = segs ? cell_gather_segments(FB, eye, g, S.prm.cell_size, cxi, (S.prm.W + TS_W - 1) / TS_W, G.keys, G.cap, G.scan) : cell_compact(g, G.keys, G.cap, G.scan);
+    return cell_nms_anms<uint32_t>(S, g, G, n_raw, out, dbg);
 }
 
 // a cell with a side over CELL_SIDE_LDS (a camera wider or taller than 1024 px under a cell size that large, e.g. the reference's TUM config on a
 // 1280 x 720 camera): the global-memory path in both passes, on 12-bit keys that k_score's segments do not carry -- the score map is compacted
-// here -- and with the row tables in the cell's own scratch, behind the tie bytes (the region is cw ch 6 words; this takes 5.25 cw ch + 2 ch).
-// The ANMS reuses the LDS row tables as its histograms (256 entries each), as on every other path.
-__device__ __forceinline__ int cell_global_path_wide(const Seq &S, const FrameBuf &FB, int eye, int cell, const CellGeom &g, const CellLds &L, float *out,
-                                                     long long *dbg) {
+// here -- and with the row tables in the cell's own scratch (cell_scratch_arr).  The ANMS takes the LDS row tables as its histograms (256 entries each), as on every other path.
+__device__ __forceinline__ int cell_global_path_wide(const Seq &S, int eye, int cell, const CellGeom &g, const CellLds &L, float *out, long long *dbg) {
     constexpr int XB = 12;
     static_assert(CELL_SIDE_MAX <= (1 << XB) && (CELL_SIDE_MAX - 6) * (CELL_SIDE_MAX - 6) < (1 << 24), "12-bit cell-local coordinates; 24-bit corner indices");
     static_assert(2ll * (CELL_SIDE_MAX - 7) * (CELL_SIDE_MAX - 7) < (1ll << 31), "radius^2 as sdot2's int32 and below cell_anms' 0xFFFFFFFF (its four-digit select)");
-    const size_t cap = (size_t)g.cw * g.ch;
-    uint32_t *gk = S.cell_scratch[eye] + S.cell_scratch_off[cell];
-    uint32_t *guf = gk + cap, *groot = guf + cap, *gabv = groot + cap, *gnms = gabv + cap;
-    uint8_t *gtie = reinterpret_cast<uint8_t *>(gnms + cap);
-    int *grow = reinterpret_cast<int *>(gnms + cap + (cap + 3) / 4);  // row_first [ch], row_end [ch]
-    const int n_raw = cell_compact<XB>(g, gk, (int)cap, L.scan);
-    const int n_kp = cell_nms<uint32_t, XB>(gk, guf, groot, gabv, gnms, gtie, n_raw, grow, grow + g.ch, L.scan, dbg, g.ch);
-    return cell_anms<uint32_t, XB>(S, g, gk, guf, groot, gabv, gnms, n_kp, (int)cap, L.row_first, L.row_end, L.scan, L.misc, out, dbg, n_raw);
+    CellArr<uint32_t> G = cell_scratch_arr(S, eye, cell, g, L, true);
+    const int n_raw = cell_compact<XB>(g, G.keys, G.cap, G.scan);
+    const int n_kp = cell_nms<uint32_t, XB>(G, n_raw, dbg, g.ch);
+    G.row_first = L.row_first, G.row_end = L.row_end;  // the NMS needed a table entry per cell row (scratch); the ANMS needs 256-entry histograms: the LDS tables
+    return cell_anms<uint32_t, XB>(S, g, G, n_kp, n_raw, out, dbg);
 }
 
 // one detection cell of one image: AGAST NMS + LVT's ANMS (or the hand-over of an oversized cell to the strip kernels)
-__device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int eye, int cell, int pass, const CellLds &L, int raw_cap = RAW_CAP) {
+__device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int eye, int cell, int pass, const CellLds &L) {
     FeatCtl &ctl = *FB.fc;
     const int tid = threadIdx.x;
     CellGeom g;
@@ -1407,16 +1443,16 @@ __device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int
     if (g.cw > CELL_SIDE_MAX || g.ch > CELL_SIDE_MAX) {  // (lvt_create refuses such a grid)
         if (tid == 0) atomicOr(&ctl.overflow, OVF_CELL_DIM);
     } else if ((g.cw > CELL_SIDE_LDS || g.ch > CELL_SIDE_LDS) && g.cw >= 7 && g.ch >= 7) {
-        n_out = cell_global_path_wide(S, FB, eye, cell, g, L, out, dbg);
+        n_out = cell_global_path_wide(S, eye, cell, g, L, out, dbg);
         if (dbg && tid == 0) dbg[10] = 1004;  // (tests: the wide global path -- in place of cell_anms' last phase stamp)
     } else if (g.cw >= 7 && g.ch >= 7) {
         // pass 0 with cells of at least one tile width: gather k_score's segments; otherwise compact the score map here
         const bool segs = (pass == 0) && (cs >= TS_W);
-        const int n_raw = segs ? cell_gather_segments(FB, eye, g, cs, cxi, (S.prm.W + TS_W - 1) / TS_W, L.keys, raw_cap, L.scan)
-                               : cell_compact(g, L.keys, raw_cap, L.scan, dbg);
+        const int n_raw = segs ? cell_gather_segments(FB, eye, g, cs, cxi, (S.prm.W + TS_W - 1) / TS_W, L.keys, L.cap, L.scan)
+                               : cell_compact(g, L.keys, L.cap, L.scan, dbg);
         if (dbg && tid == 0) dbg[1] = clock64();
-        if (n_raw <= raw_cap) {
-            n_out = cell_nms_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, L.tie8, n_raw, raw_cap, L.row_first, L.row_end, L.scan, L.stack, L.misc, out, dbg);
+        if (n_raw <= L.cap) {
+            n_out = cell_nms_anms<uint16_t>(S, g, L, n_raw, out, dbg);
         } else if (S.prm.big_cell_strips && pass == 0) {
             // more raw corners than this workgroup's LDS holds, in a cell tall enough to cut: k_cells_strip (NMS of row strips on several
             // CUs) and the kernels behind it take over; they also write cell_n / n_detected
@@ -1430,74 +1466,89 @@ __device__ __forceinline__ void cells_work(const Seq &S, const FrameBuf &FB, int
     cell_finish(FB, eye, cell, pass, n_out);
 }
 
+// ---- AGAST's NMS of a cell by row strips -------------------------------------------------------------------------------------------
+// AGAST's NMS keeps one corner per 4-connected blob of corner pixels, decided by the blob's pixels alone, so the rows of a cell can be
+// cut: strip s of n decides the corners of its CORE rows from the raw corners of core + STRIP_HALO rows on either side (the LDS path, one workgroup per
+// strip), and every decision is exact as long as no blob reaches from a core row to the outermost halo row of the extended strip -- such a blob might
+// continue outside.  That is checked per blob.  Survivors of the strips, concatenated in strip order, ARE the cell's survivors in raster order.
+// Returns the number of survivors in the strip's core rows, each handed to sink(position, key) in raster order, or -1 when the strip cannot vouch or
+// its extended rows overflow the arrays (the caller then runs the whole cell on one workgroup).  Both users cut cells of at least one k_score tile
+// width -- a single sequence's tall cells in ONE launch (cells_work_split), the oversized cells in a launch of their own (k_cells_strip) -- so the raw
+// corners always come from k_score's segments.
+constexpr int STRIP_HALO = 16;
+static_assert(BIG_CELL_SIDE >= TS_W, "an oversized cell (k_cells_strip) spans whole k_score tiles: its strips gather segments");
+template <typename Sink>
+__device__ __forceinline__ int strip_nms(const Seq &S, const FrameBuf &FB, int eye, const CellGeom &g, int cxi, int strip, int nstrips, const CellLds &L, long long *dbg, Sink sink) {
+    const int tid = threadIdx.x;
+    // interior rows of the cell: ly in [3, ch - 3)
+    const int per = (g.ch - 6 + nstrips - 1) / nstrips;
+    const int c0 = 3 + strip * per, c1 = min(c0 + per, g.ch - 3);
+    if (c0 >= c1) return 0;
+    const int e0 = max(3, c0 - STRIP_HALO), e1 = min(g.ch - 3, c1 + STRIP_HALO);
+    CellGeom g2 = g;  // the extended strip as a "cell" whose interior rows are [e0, e1)
+    g2.Y0 = g.Y0 + e0 - 3;
+    g2.ch = (e1 - e0) + 6;
+    const int n_raw = cell_gather_segments(FB, eye, g2, S.prm.cell_size, cxi, (S.prm.W + TS_W - 1) / TS_W, L.keys, L.cap, L.scan);
+    if (dbg && tid == 0) dbg[1] = clock64();
+    if (n_raw > L.cap) return -1;
+    const int n_kp = cell_nms<uint16_t>(L, n_raw, dbg);
+    // a blob with a pixel in an outermost extended row (that is not the cell's own first / last interior row) AND one in a core row?
+    for (int i = tid; i < n_raw; i += 1024) L.tie[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < n_raw; i += 1024) {
+        const int y = key_y(L.keys[i]);
+        if ((e0 > 3 && y == e0) || (e1 < g.ch - 3 && y == e1 - 1)) L.tie[L.root[i]] = 1;
+    }
+    __syncthreads();
+    int unsafe = 0;
+    for (int i = tid; i < n_raw; i += 1024) {
+        const int y = key_y(L.keys[i]);
+        if (y >= c0 && y < c1 && L.tie[L.root[i]]) unsafe = 1;
+    }
+    if (__syncthreads_or(unsafe)) return -1;
+    // survivors of the core rows, raster order
+    int n_out = 0;
+    for (int base = 0; base < n_kp; base += 1024) {
+        const int i = base + tid;
+        const uint32_t k = (i < n_kp) ? L.uf[i] : 0u;
+        const bool keep = (i < n_kp) && key_y(k) >= c0 && key_y(k) < c1;
+        int total;
+        const int off = n_out + block_excl_scan(keep ? 1 : 0, L.scan, &total);
+        if (keep) sink(off, k);
+        n_out += total;
+    }
+    return n_out;
+}
+
 // ---- a single sequence's tall cells as TWO (or three) co-operating workgroups of the same launch --------------------------------------
-// k_cells is the longest kernel of the feature stage (66 us of one CU per cell) and half of it is AGAST's NMS, which can be cut by rows exactly as
-// for the oversized cells below (one survivor per 4-connected blob, decided by the blob's pixels alone): workgroup "strip s" gathers the raw corners of
-// its core rows + SPLIT_HALO rows on either side, runs the same cell_nms, vouches that no blob reaches from a core row to the outermost halo row, and
-// keeps the survivors of its core rows.  Strips 1.. ("helpers") put theirs into global memory and publish a count + this launch's token; strip 0
+// k_cells is the longest kernel of the feature stage (66 us of one CU per cell) and half of it is AGAST's NMS, which can be cut by rows (strip_nms):
+// workgroup "strip s" decides the corners of its core rows.  Strips 1.. ("helpers") put theirs into global memory and publish a count + this launch's token; strip 0
 // ("main") appends them behind its own -- strip order IS raster order -- and runs LVT's ANMS on the merged list as before.  A strip that cannot vouch
 // (or overflows) reports -1 and the main workgroup runs the whole cell alone, as before.
 // No deadlock: the helpers have the LOWER workgroup ids and the same id modulo 8 as their main workgroup (cells_entry), i.e. they sit in the same XCD's
 // dispatch order in front of it: when a main workgroup runs, its helpers are resident or done.  The wait is bounded all the same (2 ms -> whole cell alone).
 constexpr int STRIPS = 8;  // (row strips of an oversized cell, k_cells_strip below; the per-cell stride of Seq::strip_n)
-constexpr int SPLIT_HALO = 16, SPLIT_MIN_ROWS = 160, SPLIT_MAX = 3, SPLIT_KP_CAP = 2048;
-__device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &FB, int eye, int cell, int strip, int nsplit, unsigned token, const CellLds &L, int raw_cap) {
+constexpr int SPLIT_MIN_ROWS = 160, SPLIT_MAX = 3, SPLIT_KP_CAP = 2048;
+__device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &FB, int eye, int cell, int strip, int nsplit, unsigned token, const CellLds &L) {
     const int tid = threadIdx.x;
     CellGeom g;
     int cxi;
     if (!cell_begin(S, FB, eye, cell, 0, g, cxi)) return;
-    const int cs = S.prm.cell_size;
-    const bool splittable = g.cw >= 7 && g.ch >= SPLIT_MIN_ROWS && g.cw <= CELL_SIDE_LDS && g.ch <= CELL_SIDE_LDS && cs >= TS_W && !S.prm.big_cell_strips;
+    const bool splittable = g.cw >= 7 && g.ch >= SPLIT_MIN_ROWS && g.cw <= CELL_SIDE_LDS && g.ch <= CELL_SIDE_LDS && S.prm.cell_size >= TS_W && !S.prm.big_cell_strips;
     if (!splittable) {
-        if (strip == 0) cells_work(S, FB, eye, cell, 0, L, raw_cap);
+        if (strip == 0) cells_work(S, FB, eye, cell, 0, L);
         return;
     }
     long long *dbg = (cell == 0 && eye == 0 && strip == 0) ? S.ctl->dbg : nullptr;
     if (dbg && tid == 0) dbg[0] = clock64();
     int *cnt_all = S.strip_n[eye] + cell * STRIPS;          // [1, nsplit): the helpers' counts; [4 + s]: their tokens
-    const int per = (g.ch - 6 + nsplit - 1) / nsplit;
-    const int c0 = 3 + strip * per, c1 = min(c0 + per, g.ch - 3);
-    const int e0 = max(3, c0 - SPLIT_HALO), e1 = min(g.ch - 3, c1 + SPLIT_HALO);
-    CellGeom g2 = g;  // the extended strip as a "cell" whose interior rows are [e0, e1)
-    g2.Y0 = g.Y0 + e0 - 3;
-    g2.ch = (e1 - e0) + 6;
-    int n_core = -1;
-    const int n_raw = (c0 < c1) ? cell_gather_segments(FB, eye, g2, cs, cxi, (S.prm.W + TS_W - 1) / TS_W, L.keys, raw_cap, L.scan) : 0;
-    if (dbg && tid == 0) dbg[1] = clock64();
     uint32_t *dst = S.strip_kp[eye] + ((size_t)cell * SPLIT_MAX + strip) * SPLIT_KP_CAP;  // (helpers)
-    if (n_raw <= raw_cap) {
-        const int n_kp = cell_nms<uint16_t>(L.keys, L.uf, L.root16, L.abv16, L.nms16, L.tie8, n_raw, L.row_first, L.row_end, L.scan, dbg);
-        // a blob with a pixel in an outermost extended row (that is not the cell's own first / last interior row) AND one in a core row?
-        for (int i = tid; i < n_raw; i += 1024) L.tie8[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < n_raw; i += 1024) {
-            const int y = key_y(L.keys[i]);
-            if ((e0 > 3 && y == e0) || (e1 < g.ch - 3 && y == e1 - 1)) L.tie8[L.root16[i]] = 1;
-        }
-        __syncthreads();
-        int unsafe = 0;
-        for (int i = tid; i < n_raw; i += 1024) {
-            const int y = key_y(L.keys[i]);
-            if (y >= c0 && y < c1 && L.tie8[L.root16[i]]) unsafe = 1;
-        }
-        if (!__syncthreads_or(unsafe)) {
-            // survivors of the core rows, raster order: the main workgroup keeps them where they are (uf[0 ..): off <= i), a helper sends them out
-            int n_out = 0;
-            for (int base = 0; base < n_kp; base += 1024) {
-                const int i = base + tid;
-                const uint32_t k = (i < n_kp) ? L.uf[i] : 0u;
-                const bool keep = (i < n_kp) && key_y(k) >= c0 && key_y(k) < c1;
-                int total;
-                const int off = n_out + block_excl_scan(keep ? 1 : 0, L.scan, &total);
-                if (keep) {
-                    if (strip == 0) L.uf[off] = k;
-                    else if (off < SPLIT_KP_CAP) dst[off] = k;
-                }
-                n_out += total;
-            }
-            n_core = (strip != 0 && n_out > SPLIT_KP_CAP) ? -1 : n_out;
-        }
-    }
+    // the main workgroup keeps its survivors where they are (uf[0 ..): off <= i), a helper sends them out
+    int n_core = strip_nms(S, FB, eye, g, cxi, strip, nsplit, L, dbg, [&](int off, uint32_t k) {
+        if (strip == 0) L.uf[off] = k;
+        else if (off < SPLIT_KP_CAP) dst[off] = k;
+    });
+    if (strip != 0 && n_core > SPLIT_KP_CAP) n_core = -1;
     if (strip != 0) {  // helper: the survivors, then the count, then the token.  strip_kp / strip_n are UNCACHED device memory (lvt_host.hip): a store is
         // performed when its wave's vmcnt says so -- no release fence, whose L2 write-back costs ~13 us behind k_score's planes (measured)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1535,9 +1586,9 @@ __device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &F
         bad = bad || s_helper[h] < 0;
         total += max(s_helper[h], 0);
     }
-    if (bad || total > raw_cap) {
+    if (bad || total > L.cap) {
         __syncthreads();
-        cells_work(S, FB, eye, cell, 0, L, raw_cap);
+        cells_work(S, FB, eye, cell, 0, L);
         if (dbg && tid == 0) dbg[10] = 2003;  // (tests: a strip could not vouch or overflowed -- the whole cell on this workgroup, as without the split)
         return;
     }
@@ -1552,7 +1603,7 @@ __device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &F
     __syncthreads();
     if (dbg && tid == 0) dbg[5] = clock64();
     float *out = FB.cell_kp[eye] + (size_t)cell * CELL_OUT_CAP * 3;
-    const int n_out = cell_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, total, raw_cap, L.row_first, L.row_end, L.scan, L.misc, out, dbg, total);
+    const int n_out = cell_anms<uint16_t>(S, g, L, total, total, out, dbg);
     if (dbg && tid == 0) dbg[11] = clock64();
     cell_finish(FB, eye, cell, 0, n_out);
 }
@@ -1599,7 +1650,7 @@ struct CellOrder {
     uint8_t v[CELLS_MAX];
 };
 template <bool BV>  // (a single sequence's descriptor travels in the kernel arguments: one dependent memory hop less at the head of the longest kernel)
-__device__ __forceinline__ void cells_entry(const SeqArg<BV> &sa, int pass, int par, const CellOrder &ord, int lanes, int raw_cap, const NextPull &np, int nsplit, unsigned token) {
+__device__ __forceinline__ void cells_entry(const SeqArg<BV> &sa, int par, const CellOrder &ord, int lanes, int raw_cap, const NextPull &np, int nsplit, unsigned token) {
     int eye = blockIdx.y, cell = blockIdx.x;
     int strip = -1;  // >= 0: this workgroup is one row strip of a split cell (cells_work_split)
     if constexpr (BV) {
@@ -1633,11 +1684,11 @@ __device__ __forceinline__ void cells_entry(const SeqArg<BV> &sa, int pass, int 
     if (threadIdx.x == 0 && cell < CELLS_MAX && strip <= 0) S.cell_big[eye][cell] = 0;  // (nobody reads it before this launch is over)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const CellLds L = carve_cell_lds(smem, raw_cap);
-    if (strip >= 0) cells_work_split(S, FB, eye, cell, strip, nsplit, token, L, raw_cap);
-    else cells_work(S, FB, eye, cell, pass, L, raw_cap);
+    if (strip >= 0) cells_work_split(S, FB, eye, cell, strip, nsplit, token, L);
+    else cells_work(S, FB, eye, cell, 0, L);
 }
 struct CellsRest {  // what follows the descriptor in k_cells' arguments, the longest such list of any kernel: held to the room a by-value Seq leaves (lvt_dev.h)
-    int pass, par;
+    int par;
     CellOrder ord;
     int lanes, raw_cap;
     NextPull np;
@@ -1649,17 +1700,17 @@ static_assert(sizeof(CellsRest) <= BYVAL_REST_MAX, "k_cells' arguments outgrow w
 // instance is held to 64 so that TWO of its 80-KB workgroups share a CU (at 66 registers it ran one per CU whatever its LDS) -- an occupancy
 // attribute on the template would cap the single-sequence instance too, where a second workgroup can never fit and the cap can only spill.
 template <bool BV>
-__global__ __launch_bounds__(1024) void k_cells(SeqArg<BV> sa, int pass, int par, CellOrder ord, int lanes, int raw_cap, NextPull np, int nsplit, unsigned token) {
-    cells_entry<BV>(sa, pass, par, ord, lanes, raw_cap, np, nsplit, token);
+__global__ __launch_bounds__(1024) void k_cells(SeqArg<BV> sa, int par, CellOrder ord, int lanes, int raw_cap, NextPull np, int nsplit, unsigned token) {
+    cells_entry<BV>(sa, par, ord, lanes, raw_cap, np, nsplit, token);
 }
 template <>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells<false>(SeqArg<false> sa, int pass, int par, CellOrder ord, int lanes, int raw_cap, NextPull np, int nsplit, unsigned token) {
-    cells_entry<false>(sa, pass, par, ord, lanes, raw_cap, np, 0, token);
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells<false>(SeqArg<false> sa, int par, CellOrder ord, int lanes, int raw_cap, NextPull np, int nsplit, unsigned token) {
+    cells_entry<false>(sa, par, ord, lanes, raw_cap, np, 0, token);
 }
 // The cells of a MIXED batch (see k_score_mixed): one table entry (sequence << 16 | eye << 8 | cell) per detection cell of every image of the batch,
 // sorted by cell area over ALL sequences, largest first -- what CellOrder does for one grid: the workgroups that start late are the short ones.
 // Same occupancy contract as the batch instance above (64 registers, two 80-KB workgroups per CU under RAW_CAP_SMALL).
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells_mixed(const Seq *seqs, const uint32_t *tab, int pass, int par, int raw_cap) {
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cells_mixed(const Seq *seqs, const uint32_t *tab, int par, int raw_cap) {
     const uint32_t e = ((TabConstPtr)tab)[blockIdx.x];
     const int cell = (int)(e & 255u), eye = (int)((e >> 8) & 1u);
     const Seq &S = seq_const(seqs, e >> 16);
@@ -1667,92 +1718,48 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     if (threadIdx.x == 0 && cell < CELLS_MAX) S.cell_big[eye][cell] = 0;  // (nobody reads it before this launch is over)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const CellLds L = carve_cell_lds(smem, raw_cap);
-    cells_work(S, FB, eye, cell, pass, L, raw_cap);  // (a sequence that is absent in this step leaves at cell_begin)
+    cells_work(S, FB, eye, cell, 0, L);  // (a sequence that is absent in this step leaves at cell_begin)
 }
 
 // ---- an oversized cell as row strips --------------------------------------------------------------------------------------------
-// AGAST's NMS keeps one corner per 4-connected blob of corner pixels, decided by the blob's pixels alone, so the rows
-// of a cell can be cut: strip s decides the corners of its CORE rows from the raw corners of core + STRIP_HALO rows on either side
-// (the fast LDS path of k_cells, one CU per strip), and every decision is exact as long as no blob reaches from a core row to the
-// outermost halo row of the extended strip -- such a blob might continue outside.  That is checked per blob; a strip that cannot
-// vouch (or whose extended rows overflow the LDS) reports -1 and k_cells_big runs the whole cell on the single-workgroup global path
-// instead, as before.  Survivors of the strips, concatenated in strip order, ARE the cell's survivors in raster order.
-constexpr int STRIP_HALO = 16;
-__global__ __launch_bounds__(1024) void k_cells_strip(const Seq *seqs, int pass, int par) {
-    const Seq &S = seq_const(seqs, blockIdx.z);
-    const int eye = blockIdx.y, cell = blockIdx.x / STRIPS, strip = blockIdx.x % STRIPS;
-    const FrameBuf &FB = S.fb[par];
+// k_cells leaves a cell with more raw corners than its LDS holds (cell_big = 1) to four launches: k_cells_strip, strip_nms on STRIPS strips, one CU each; k_cells_big,
+// their survivors merged in LDS and through LVT's ANMS -- or, when a strip reported -1, the whole cell on the single-workgroup global path; and, for a merged list too dense
+// (cell_big = 2), the ANMS's radii on RADII_WGS workgroups (k_cells_radii) and its selection (k_cells_select).  Detection pass 0 only (cells_work).
+struct BigCell {
+    int eye, cell, part;  // part: which of the cell's workgroups in this launch
     CellGeom g;
     int cxi;
-    if (!cell_begin(S, FB, eye, cell, pass, g, cxi)) return;
-    if (S.cell_big[eye][cell] != 1) return;
+    CellLds L;
+};
+// shared prologue of the four kernels: eye and (cell, part) from the block indices, per_cell workgroups a cell, then cell_begin, the cell_big state the kernel is for and the
+// LDS carve; false = nothing to do.  (S and FB stay references of the kernel, which takes the sequence from blockIdx.z: carried in the record they cost k_cells_big two registers)
+__device__ __forceinline__ bool big_cell_begin(const Seq &S, const FrameBuf &FB, int per_cell, int state, BigCell &c) {
+    c.eye = blockIdx.y, c.cell = blockIdx.x / per_cell, c.part = blockIdx.x % per_cell;
+    if (!cell_begin(S, FB, c.eye, c.cell, 0, c.g, c.cxi)) return false;
+    if (S.cell_big[c.eye][c.cell] != state) return false;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellLds L = carve_cell_lds(smem);
-    const int tid = threadIdx.x, cs = S.prm.cell_size;
-    int *cnt = S.strip_n[eye] + cell * STRIPS + strip;
-    uint32_t *dst = S.strip_kp[eye] + ((size_t)cell * STRIPS + strip) * RAW_CAP;
-    // interior rows of the cell: ly in [3, ch - 3)
-    const int per = (g.ch - 6 + STRIPS - 1) / STRIPS;
-    const int c0 = 3 + strip * per, c1 = min(c0 + per, g.ch - 3);
-    if (c0 >= c1) {
-        if (tid == 0) *cnt = 0;
-        return;
-    }
-    const int e0 = max(3, c0 - STRIP_HALO), e1 = min(g.ch - 3, c1 + STRIP_HALO);
-    CellGeom g2 = g;  // the extended strip as a "cell" whose interior rows are [e0, e1)
-    g2.Y0 = g.Y0 + e0 - 3;
-    g2.ch = (e1 - e0) + 6;
-    const bool segs = (pass == 0) && (cs >= TS_W);
-    const int n_raw = segs ? cell_gather_segments(FB, eye, g2, cs, cxi, (S.prm.W + TS_W - 1) / TS_W, L.keys, RAW_CAP, L.scan)
-                           : cell_compact(g2, L.keys, RAW_CAP, L.scan, nullptr, e0 - 3);
-    if (n_raw > RAW_CAP) {
-        if (tid == 0) *cnt = -1;
-        return;
-    }
-    const int n_kp = cell_nms<uint16_t>(L.keys, L.uf, L.root16, L.abv16, L.nms16, L.tie8, n_raw, L.row_first, L.row_end, L.scan, nullptr);
-    // a blob with a pixel in an outermost extended row (that is not the cell's own first / last interior row) AND one in a core row?
-    for (int i = tid; i < n_raw; i += 1024) L.tie8[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < n_raw; i += 1024) {
-        const int y = key_y(L.keys[i]);
-        if ((e0 > 3 && y == e0) || (e1 < g.ch - 3 && y == e1 - 1)) L.tie8[L.root16[i]] = 1;
-    }
-    __syncthreads();
-    int unsafe = 0;
-    for (int i = tid; i < n_raw; i += 1024) {
-        const int y = key_y(L.keys[i]);
-        if (y >= c0 && y < c1 && L.tie8[L.root16[i]]) unsafe = 1;
-    }
-    if (__syncthreads_or(unsafe)) {
-        if (tid == 0) *cnt = -1;
-        return;
-    }
-    // survivors of the core rows, raster order
-    int n_out = 0;
-    for (int base = 0; base < n_kp; base += 1024) {
-        const int i = base + tid;
-        const uint32_t k = (i < n_kp) ? L.uf[i] : 0u;
-        const bool keep = (i < n_kp) && key_y(k) >= c0 && key_y(k) < c1;
-        int total;
-        const int off = n_out + block_excl_scan(keep ? 1 : 0, L.scan, &total);
-        if (keep) dst[off] = k;  // (at most n_raw <= RAW_CAP)
-        n_out += total;
-    }
-    if (tid == 0) *cnt = n_out;
+    c.L = carve_cell_lds(smem);
+    return true;
+}
+
+__global__ __launch_bounds__(1024) void k_cells_strip(const Seq *seqs, int par) {
+    const Seq &S = seq_const(seqs, blockIdx.z);
+    const FrameBuf &FB = S.fb[par];
+    BigCell c;
+    if (!big_cell_begin(S, FB, STRIPS, 1, c)) return;
+    uint32_t *dst = S.strip_kp[c.eye] + ((size_t)c.cell * STRIPS + c.part) * RAW_CAP;
+    const int n = strip_nms(S, FB, c.eye, c.g, c.cxi, c.part, STRIPS, c.L, nullptr, [&](int off, uint32_t k) { dst[off] = k; });  // (at most n_raw <= RAW_CAP)
+    if (threadIdx.x == 0) S.strip_n[c.eye][c.cell * STRIPS + c.part] = n;
 }
 
 // the oversized cell's second half: its strips' survivors, merged in LDS, through LVT's ANMS (or the whole cell on the old path)
-__global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
-    const int eye = blockIdx.y, cell = blockIdx.x;
     const FrameBuf &FB = S.fb[par];
-    CellGeom g;
-    int cxi;
-    if (!cell_begin(S, FB, eye, cell, pass, g, cxi)) return;
-    if (S.cell_big[eye][cell] != 1) return;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellLds L = carve_cell_lds(smem);
-    const int tid = threadIdx.x;
+    BigCell c;
+    if (!big_cell_begin(S, FB, 1, 1, c)) return;
+    const CellLds &L = c.L;
+    const int eye = c.eye, cell = c.cell, tid = threadIdx.x;
     float *out = FB.cell_kp[eye] + (size_t)cell * CELL_OUT_CAP * 3;
     const int *cnt = S.strip_n[eye] + cell * STRIPS;
     int total = 0;
@@ -1763,10 +1770,10 @@ __global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int pass, i
         total += max(n, 0);
     }
     int n_out;
-    long long *route = (cell == 0 && eye == 0 && pass == 0 && tid == 0) ? S.ctl->dbg + 10 : nullptr;  // (tests: which way the cell went)
+    long long *route = (cell == 0 && eye == 0 && tid == 0) ? S.ctl->dbg + 10 : nullptr;  // (tests: which way the cell went)
     if (bad || total > RAW_CAP) {
         if (route) *route = 1003;  // a strip could not vouch or overflowed: the whole cell on one workgroup
-        n_out = cell_global_path(S, FB, eye, cell, cxi, (pass == 0) && (S.prm.cell_size >= TS_W), g, L, out, nullptr);
+        n_out = cell_global_path(S, FB, eye, cell, c.cxi, true, c.g, L, out, nullptr);
     } else {
         if (route) *route = (total > S.prm.max_kp_cell) ? 1001 : 1002;  // strips + three-launch ANMS / strips, no ANMS needed
         int off = 0;
@@ -1776,12 +1783,12 @@ __global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int pass, i
             off += cnt[s];
         }
         __syncthreads();
-        long long *dbg = (cell == 0 && eye == 0 && pass == 0) ? S.ctl->dbg : nullptr;  // (phase stamps 5 .. 10: tools/cells_phases.py)
+        long long *dbg = (cell == 0 && eye == 0) ? S.ctl->dbg : nullptr;  // (phase stamps 5 .. 10: tools/cells_phases.py)
         if (dbg && tid == 0) dbg[5] = clock64();
         if (total > S.prm.max_kp_cell) {
             // ANMS in three launches: the sort here, the radii (n^2 / 2 distances: VALU-bound on one CU) on RADII_WGS workgroups, the
             // selection on one again.  sorted[] travels through strip 0's (now dead) buffer, the radii through strip 1's.
-            cell_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, total, RAW_CAP, L.row_first, L.row_end, L.scan, L.misc, out, dbg, total, ANMS_SORT);
+            anms_sort<uint16_t>(L, total, dbg);
             uint32_t *gs = S.strip_kp[eye] + (size_t)cell * STRIPS * RAW_CAP;
             for (int i = tid; i < total; i += 1024) gs[i] = L.keys[i];
             if (tid == 0) {
@@ -1791,56 +1798,49 @@ __global__ __launch_bounds__(1024) void k_cells_big(const Seq *seqs, int pass, i
             if (dbg && tid == 0) dbg[11] = clock64();
             return;
         }
-        n_out = cell_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, total, RAW_CAP, L.row_first, L.row_end, L.scan, L.misc, out, dbg, total);
+        n_out = cell_anms<uint16_t>(S, c.g, L, total, total, out, dbg);
         if (dbg && tid == 0) dbg[11] = clock64();
     }
-    cell_finish(FB, eye, cell, pass, n_out);
+    cell_finish(FB, eye, cell, 0, n_out);
 }
 
 constexpr int RADII_WGS = 16;
 static_assert(STRIPS >= 2, "the ANMS launches pass sorted[] and r2[] through the first two strip buffers");
-__global__ __launch_bounds__(1024) void k_cells_radii(const Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_radii(const Seq *seqs, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
-    const int eye = blockIdx.y, cell = blockIdx.x / RADII_WGS, wg = blockIdx.x % RADII_WGS;
     const FrameBuf &FB = S.fb[par];
-    CellGeom g;
-    int cxi;
-    if (!cell_begin(S, FB, eye, cell, pass, g, cxi)) return;
-    if (S.cell_big[eye][cell] != 2) return;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellLds L = carve_cell_lds(smem);
-    const int tid = threadIdx.x;
+    BigCell c;
+    if (!big_cell_begin(S, FB, RADII_WGS, 2, c)) return;
+    const CellLds &L = c.L;
+    const int eye = c.eye, cell = c.cell, wg = c.part, tid = threadIdx.x;
     const int n = S.strip_n[eye][cell * STRIPS];
     const uint32_t *gs = S.strip_kp[eye] + (size_t)cell * STRIPS * RAW_CAP;
     uint32_t *gr = S.strip_kp[eye] + ((size_t)cell * STRIPS + 1) * RAW_CAP;
     for (int i = tid; i < n; i += 1024) L.keys[i] = gs[i];
     __syncthreads();
-    cell_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, n, RAW_CAP, L.row_first, L.row_end, L.scan, L.misc, nullptr, nullptr, n, ANMS_RADII, wg, RADII_WGS);
+    anms_radii<uint16_t>(L, n, wg, RADII_WGS);
     for (int i = wg + tid * RADII_WGS; i < n; i += 1024 * RADII_WGS) gr[i] = L.uf[i];
 }
 
-__global__ __launch_bounds__(1024) void k_cells_select(const Seq *seqs, int pass, int par) {
+__global__ __launch_bounds__(1024) void k_cells_select(const Seq *seqs, int par) {
     const Seq &S = seq_const(seqs, blockIdx.z);
-    const int eye = blockIdx.y, cell = blockIdx.x;
     const FrameBuf &FB = S.fb[par];
-    CellGeom g;
-    int cxi;
-    if (!cell_begin(S, FB, eye, cell, pass, g, cxi)) return;
-    if (S.cell_big[eye][cell] != 2) return;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellLds L = carve_cell_lds(smem);
-    const int tid = threadIdx.x;
+    BigCell c;
+    if (!big_cell_begin(S, FB, 1, 2, c)) return;
+    const CellLds &L = c.L;
+    const int eye = c.eye, cell = c.cell, tid = threadIdx.x;
     const int n = S.strip_n[eye][cell * STRIPS];
     const uint32_t *gs = S.strip_kp[eye] + (size_t)cell * STRIPS * RAW_CAP;
     const uint32_t *gr = S.strip_kp[eye] + ((size_t)cell * STRIPS + 1) * RAW_CAP;
+#pragma unroll 4  // (eight loads in flight; left to itself the compiler unrolls further and the kernel's register count is this loop's)
     for (int i = tid; i < n; i += 1024) {
         L.keys[i] = gs[i];
         L.uf[i] = gr[i];
     }
     __syncthreads();
     float *out = FB.cell_kp[eye] + (size_t)cell * CELL_OUT_CAP * 3;
-    const int n_out = cell_anms<uint16_t>(S, g, L.keys, L.uf, L.root16, L.abv16, L.nms16, n, RAW_CAP, L.row_first, L.row_end, L.scan, L.misc, out, nullptr, n, ANMS_SELECT);
-    cell_finish(FB, eye, cell, pass, n_out);
+    const int n_out = anms_select<uint16_t>(S, c.g, L, n, out, nullptr);
+    cell_finish(FB, eye, cell, 0, n_out);
 }
 
 // =================================================================================================

@@ -19,6 +19,7 @@ constexpr int RAW_CAP = 10240;     // raw (pre-NMS) corners one cell may hold in
 constexpr int CELL_SIDE_LDS = 1024;  // longest side of a detection cell on the LDS paths (10-bit cell-local x of a raw-corner key)
 constexpr int CELL_SIDE_MAX = 4096;  // longest side of a detection cell at all (a longer side: the 12-bit keys of the wide global path; lvt_create refuses more).
                                      // Its ANMS radii^2 reach 2 (4089)^2 > 2^24: a four-digit select and the reference's sqrtf test (cell_anms)
+constexpr int BIG_CELL_SIDE = 256;   // a detection grid of larger cells sends a cell whose raw corners overflow the LDS through the strip kernels (Params::big_cell_strips)
 constexpr int MAP_MAX = 32768;     // local map points
 constexpr int STAGED_MAX = 16384;  // staged points
 constexpr int KC = 128;            // candidate-list capacity per query (overflow -> exact slow path)
@@ -61,7 +62,7 @@ struct Params {  // lvt_parameters.h:29-64 + derived values
     int sensor;                             // 1 stereo, 2 rgbd
     int undistort;                          // |k1| > 1e-5 (handler.cpp:268)
     unsigned cell_magic;                    // ceil(2^32 / cell_size): x / cell_size == __umulhi(x, cell_magic) for x * cell_size < 2^32 (pixel coordinates)
-    int big_cell_strips;                    // detection cells taller than 256 px: an oversized cell's NMS runs as row strips on several CUs (k_cells_strip)
+    int big_cell_strips;                    // detection cells larger than BIG_CELL_SIDE px: an oversized cell's NMS runs as row strips on several CUs (k_cells_strip)
 };
 
 struct Pose {  // camera-to-world, quaternion (w,x,y,z) + position

@@ -405,7 +405,7 @@ static bool derive_params(const lvt_amd_params &in, int sensor, Params &p) {
     }
     p.undistort = (std::fabs(p.k1) > 1e-5) ? 1 : 0;
     p.cell_magic = (unsigned)((0x100000000ull + (unsigned long long)p.cell_size - 1) / (unsigned long long)p.cell_size);
-    p.big_cell_strips = (p.cell_size > 256) ? 1 : 0;  // (TUM's single 2000-px cell; the 250-px cells of KITTI / EuRoC keep the two-launch feature chain)
+    p.big_cell_strips = (p.cell_size > BIG_CELL_SIDE) ? 1 : 0;  // (TUM's single 2000-px cell; the 250-px cells of KITTI / EuRoC keep the two-launch feature chain)
     return true;
 }
 
@@ -972,22 +972,22 @@ static void enqueue_frame(Context *c) {
     }
     if (!ext) {
         {
-            const int pass = 0;  // (the <200-corner retry pass runs inside k_gather: it is almost never taken)
+            // detection pass 0 (the <200-corner retry pass runs inside k_gather: it is almost never taken)
             // (a single sequence: + the workgroups that pull the next asynchronous host frame, one 16-byte vector per thread)
             const int pull_wgs = (B == 1 && c->next_pull.src[0]) ? std::min(64, (int)(((size_t)p.W * p.H / 16 + 1023) / 1024)) : 0;
             // a single sequence's tall cells run as cell_split co-operating workgroups (cells_work_split); grid: helpers, main workgroups, pull, padded to 8
             const int ns = (B == 1 && !p.big_cell_strips) ? c->cell_split : 0;
             const int gx = (ns >= 2) ? ((((p.n_cells + 7) & ~7) * ns + pull_wgs + 7) & ~7) : p.n_cells + pull_wgs;
-            if (c->mixed) LAUNCH(3, sf, k_cells_mixed, dim3(c->n_cells_wgs), dim3(1024), cells_lds_bytes(c->cells_raw_cap), S, c->d_cells_tab, pass, par, c->cells_raw_cap);
-            else LAUNCH_S(3, sf, k_cells, (B == 1 ? dim3(gx, 2, 1) : dim3(p.n_cells * 2 * Bz, 1, 1)), dim3(1024), cells_lds_bytes(c->cells_raw_cap), pass, par, c->cell_order, 2 * Bz, c->cells_raw_cap, c->next_pull, ns, (++c->cell_token ? c->cell_token : ++c->cell_token));
+            if (c->mixed) LAUNCH(3, sf, k_cells_mixed, dim3(c->n_cells_wgs), dim3(1024), cells_lds_bytes(c->cells_raw_cap), S, c->d_cells_tab, par, c->cells_raw_cap);
+            else LAUNCH_S(3, sf, k_cells, (B == 1 ? dim3(gx, 2, 1) : dim3(p.n_cells * 2 * Bz, 1, 1)), dim3(1024), cells_lds_bytes(c->cells_raw_cap), par, c->cell_order, 2 * Bz, c->cells_raw_cap, c->next_pull, ns, (++c->cell_token ? c->cell_token : ++c->cell_token));
             // (a mixed batch: when ANY sequence has cells tall enough to cut, over the largest grid -- a sequence without such cells leaves at cell_big != 1,
             //  a cell index beyond a sequence's grid at cell_begin)
             if (c->any_strips) {  // oversized cells: NMS as row strips on several CUs, then ANMS of the merged survivors in three launches
                 const int nc = c->max_cells;
-                hipLaunchKernelGGL(k_cells_strip, dim3(nc * STRIPS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_big, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_radii, dim3(nc * RADII_WGS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
-                hipLaunchKernelGGL(k_cells_select, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, pass, par);
+                hipLaunchKernelGGL(k_cells_strip, dim3(nc * STRIPS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, par);
+                hipLaunchKernelGGL(k_cells_big, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, par);
+                hipLaunchKernelGGL(k_cells_radii, dim3(nc * RADII_WGS, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, par);
+                hipLaunchKernelGGL(k_cells_select, dim3(nc, 2, Bz), dim3(1024), CELLS_LDS_BYTES, sf, S, par);
                 if (c->prof) (void)hipEventRecord(c->ev[3][1], sf);  // (the slot's time covers the five launches)
             }
         }

@@ -145,14 +145,22 @@ def test_oversized_cell_paths(hip_lib, oracle_lib, kind):
     assert err == "" or "results unaffected" in err, err
 
 
-@pytest.mark.parametrize("kind", ["world", "tall_blobs", "blurred_noise"])
-def test_split_cell_routes(hip_lib, oracle_lib, kind):
+# (LVT_AMD_CELL_SPLIT, input): None = the default of two strips.  The strip arithmetic (strip_nms) is shared by 2, 3 and -- the oversized cells -- 8 strips
+_SPLIT_CASES = [(None, "world"), (None, "tall_blobs"), (None, "blurred_noise"), ("3", "world"), ("3", "tall_blobs"), ("0", "world")]
+
+
+@pytest.mark.parametrize("split,kind", _SPLIT_CASES, ids=[k if s is None else f"split{s}-{k}" for s, k in _SPLIT_CASES])
+def test_split_cell_routes(hip_lib, oracle_lib, monkeypatch, split, kind):
     """a single sequence's 250-row detection cells run as TWO co-operating workgroups of one k_cells launch (cells_work_split: AGAST's NMS of the
     upper and the lower half with a 16-row halo, survivors merged, ANMS on the merged list).  An ordinary frame takes the split; noise stretched
     a constructed corner blob 137 rows tall crosses the cut and both halos -- the strips cannot vouch and the main workgroup runs the whole cell alone (route 2003).
-    Key points, responses, descriptors and their ORDER against the oracle either way."""
+    Key points, responses, descriptors and their ORDER against the oracle either way.
+    LVT_AMD_CELL_SPLIT=3: three strips -- the middle one's core rows are [85, 167) of the 250-row cell and its extended rows [69, 183); the planted blob (rows
+    60 - 200) touches both outer rows and the core, so that strip cannot vouch either.  =0: no split, the whole cell on one workgroup from the start."""
     from parity_util import make_case
     from oracle import pyoracle
+    if split is not None:
+        monkeypatch.setenv("LVT_AMD_CELL_SPLIT", split)   # (read when the handle is created)
     world, prm, _ = make_case("kitti", 4, 1.0)
     H, W = world.H, world.W
     rng = np.random.default_rng(11)
