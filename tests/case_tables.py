@@ -1,6 +1,8 @@
 """The inputs of the edge-case tests of k_pnp and k_triangulate, in one place: the GPU tests (test_gpu_primitives.py, test_gpu_parity.py,
 test_gpu_mixed_batch.py) drive the HIP path with them, the CPU tier (test_case_tables.py) asserts with the oracle alone that they still take
 the branches they were chosen for.  Nothing here needs a GPU."""
+import functools
+
 import numpy as np
 
 import lvt_amd
@@ -225,3 +227,265 @@ def mapcap_track(system, frame):
     """one recipe frame through an oracle or a HIP handle (the two share the method names)"""
     L, R, cl, cr = frame
     return system.track(L, R) if cl is None else system.track_with_external_corners(L, R, cl, cr)
+
+
+# ---- the greedy match resolvers on deep dependency chains: the "domino" scenes ---------------------------------------------------------------------
+# The resolvers (resolve_super and its callers, k_track.hip) replace the reference's serial accept / mark scans by a synchronous fixpoint that needs
+# one iteration more than the longest chain "query q's best candidate is taken by an earlier query" is long.  Random texture gives chains of 2 - 4.
+# A domino scene builds one of any length out of image content alone: BRIEF reads 9 x 9 box sums at offsets <= 24, so the descriptor of a corner is
+# a function of its own 57 x 57 patch.
+#   nodes      integer positions on a lattice of pitch 58, numbered boustrophedon: consecutive nodes are lattice neighbours
+#   frame 0    left eye: node i carries its own noise patch P_i.  Right eye: node j, moved DOMINO_DISP px to the left, carries the blend
+#              a P_(j+1) + (1 - a) P_j: its descriptor is nearest to desc(P_(j+1)), second nearest to desc(P_j), far from every other patch
+#   frame >= 1 left eye: the blends at the nodes' own positions (static camera); right eye: the same image moved DOMINO_DISP px
+# row_match (frame 0) and find_matches (frame >= 1, tracking radius 60: a map point sees its four lattice neighbours and itself) then meet the same
+# preference: query i takes target i - 1 before target i before anything else.  Serially query 0 takes target 0 (target -1 does not exist) and every
+# later query is pushed to its own target; in the fixpoint query i cannot settle before iteration i + 1.  row_match offers a query the targets of
+# its own lattice row only (+-2 rows, any x), so there every lattice row is a chain of its own, all running at once.
+# Fillers are plain corners on the scene's noise background, identical in every frame and eye: each matches itself at distance 0.
+#
+# Noise patches drawn blindly spread too far for a chain of a hundred (at a = 0.6 best 26 .. 60, second 54 .. 114, unrelated pairs down to 82 were
+# measured: some node always breaks the chain), so the patches are drawn until they meet fixed windows (domino_patches).  Measured with the oracle's
+# BRIEF on `map_chain` (test_case_tables.py asserts these figures), per chain query behind the head (best, second, third) as min / median / max:
+#   find_matches, frames 1 and 2   best 36 / 47 / 54     second 70 / 77 / 86     third 101 / 117 / 152
+#   row_match, frame 0             best 36 / 47 / 54     second 70 / 77 / 86     third 100 / 108 / 118
+# so best / second <= 0.78 and second / third <= 0.86 at the worst node.  Both ratio thresholds are set to 0.9: the chain conditions hold with room
+# (at the reference's defaults, 0.8 and 0.6, a query pushed off its best candidate would be left unmatched and its successor let through).
+# Measured depths (synchronous fixpoint on the oracle's own candidate lists, counting the last iteration, which changes nothing):
+#   map_chain                    96 (95 queries in one chain)          row_chain   20 (five chains of 19, one per lattice row)
+#   chain_across_super_chunks    super-chunk 0: 48, super-chunk 1: 49  staged_chain 96 (update_staged's scan over the 95 staged chain points)
+DOMINO_PITCH, DOMINO_HALF, DOMINO_DISP, DOMINO_RADIUS, DOMINO_ALPHA, DOMINO_RATIO = 58, 28, 20, 60, 0.6, 0.9
+DOMINO_BEST, DOMINO_SECOND, DOMINO_OTHER = (36, 54), (70, 86), 100      # Hamming distances the chain's patches are drawn for (domino_patches)
+RES_QCAP, RES_LCAP, RES_KC, RES_THREADS = 2048, 24576, 128, 1024        # k_track.hip / lvt_dev.h: queries and packed list entries of a super-chunk
+
+
+def boustrophedon(cols, rows, x0, y0, pitch=DOMINO_PITCH):
+    """integer lattice positions, row by row, every second row from right to left"""
+    out = []
+    for r in range(rows):
+        cs = range(cols) if r % 2 == 0 else range(cols - 1, -1, -1)
+        out += [(x0 + pitch * c, y0 + pitch * r) for c in cs]
+    return np.array(out, dtype=np.int64)
+
+
+# name: (width, height, lattice (cols, rows, x0, y0), dense fillers (cols, rows, x0, y0, pitch) or None, sparse fillers (cols, x0, y0, pitch) or None,
+#        staged_threshold, frames)
+DOMINO_SCENES = {
+    "map_chain": (1241, 376, (19, 5, 70, 60), None, None, 0, 3),
+    "chain_across_super_chunks": (2048, 1040, (19, 5, 70, 60), (48, 16, 60, 400, 16), (39, 930, 400, 28), 0, 3),
+    # the same scene and corner order, staged_threshold 1.  Frame 0 is given the fillers alone: they are the 250 map points without which every staged
+    # point is promoted at once.  Frame 1 adds the chain's corners on frame 0's images: the fillers match the map, the chain's pairs are staged (in
+    # corner order: the whole chain, then the spares).  Frame 2 shows the blends: the chain runs through update_staged's resolver and is promoted; the
+    # spares of the first three lattice rows are left out of its corners, so their staged points are erased
+    "staged_chain": (2048, 1040, (19, 5, 70, 60), (48, 16, 60, 400, 16), (39, 930, 400, 28), 1, 3),
+}
+STAGED_CHAIN_DROPPED = 3
+DOMINO_MIN_DEPTH = {"map_chain": 64, "row_chain": 16, "chain_across_super_chunks": 32}
+
+
+def super_chunks(n_cand):
+    """the resolver's cut of a query list into super-chunks (resolve_super): at most QCAP queries, the longest prefix whose lists (lengths rounded
+    up to 4 entries) fit LCAP packed entries; a query with more than KC candidates ends the chunk in front of it and is decided alone (length 1)"""
+    out, b0, M = [], 0, len(n_cand)
+    while b0 < M:
+        if n_cand[b0] > RES_KC:
+            out.append((b0, 1)); b0 += 1
+            continue
+        used, ent = 0, 0
+        while b0 + used < M and used < RES_QCAP and n_cand[b0 + used] <= RES_KC and ent + ((n_cand[b0 + used] + 3) & ~3) <= RES_LCAP:
+            ent += (n_cand[b0 + used] + 3) & ~3
+            used += 1
+        out.append((b0, used)); b0 += used
+    return out
+
+
+def _neighbour_counts(xy, radius):
+    d2 = ((xy[:, None, :] - xy[None, :, :]) ** 2).sum(-1)
+    return (d2 < radius * radius).sum(1)
+
+
+def _blend(a, b):
+    return np.rint(DOMINO_ALPHA * a.astype(np.float64) + (1.0 - DOMINO_ALPHA) * b.astype(np.float64)).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def domino_patches(n, n_spare):
+    """(P, blend, spare): n + 1 noise patches of 57 x 57, the n blends a P_(i+1) + (1 - a) P_i, and n_spare patches for the spare corners.  P_(i+1) is
+    drawn, seeded, until blend_i lies within DOMINO_BEST of desc(P_(i+1)) and within DOMINO_SECOND of desc(P_i), and every unrelated pair (a blend, a
+    patch) of the chain so far is at least DOMINO_OTHER apart; a spare is at least DOMINO_OTHER from every patch and blend.  The descriptor of a patch
+    is the oracle's BRIEF at its centre (it reads nothing outside the patch)."""
+    from oracle import pyoracle as O
+    side, batch = 2 * DOMINO_HALF + 1, 32
+    centres = np.array([[DOMINO_HALF + side * k, DOMINO_HALF] for k in range(batch)], dtype=np.float32)
+
+    def desc(patches):
+        kept, d = O.brief(np.ascontiguousarray(np.hstack(list(patches))), centres[:len(patches)])
+        assert len(kept) == len(patches)
+        return d
+
+    rng = np.random.default_rng(20)
+    P = [rng.integers(0, 256, (side, side), dtype=np.uint8)]
+    dP, B, dB = [desc(P)[0]], [], []
+    while len(B) < n:
+        cand = rng.integers(0, 256, (batch, side, side), dtype=np.uint8)
+        bl = [_blend(c, P[-1]) for c in cand]
+        dc, db = desc(cand), desc(bl)
+        for k in range(batch):
+            best, second = _hamming(db[k:k + 1], dc[k:k + 1])[0, 0], _hamming(db[k:k + 1], dP[-1][None])[0, 0]
+            if not (DOMINO_BEST[0] <= best <= DOMINO_BEST[1] and DOMINO_SECOND[0] <= second <= DOMINO_SECOND[1]):
+                continue
+            if len(dP) > 1 and _hamming(db[k:k + 1], np.array(dP[:-1])).min() < DOMINO_OTHER:
+                continue
+            if dB and _hamming(dc[k:k + 1], np.array(dB)).min() < DOMINO_OTHER:
+                continue
+            P.append(cand[k]); dP.append(dc[k]); B.append(bl[k]); dB.append(db[k])
+            break
+    spare = []
+    while len(spare) < n_spare:
+        cand = rng.integers(0, 256, (batch, side, side), dtype=np.uint8)
+        dc = desc(cand)
+        far = (_hamming(dc, np.array(dP)).min(1) >= DOMINO_OTHER) & (_hamming(dc, np.array(dB)).min(1) >= DOMINO_OTHER)
+        spare += [cand[k] for k in np.flatnonzero(far)][:n_spare - len(spare)]
+    return np.array(P), np.array(B), np.array(spare)
+
+
+@functools.lru_cache(maxsize=None)
+def domino_scene(name):
+    """(params, frames, info): frames = [(L, R, corners_left, corners_right)] for track_with_external_corners; info = dict(n_chain, chain = corner
+    indices of the chain's nodes in chain order, n_corners).
+
+    `chain_across_super_chunks` orders its corners: first half of the chain, dense fillers (pitch 16: ~44 candidates each within the radius), sparse
+    fillers (pitch 28: ~14), second half of the chain, spares.  The dense fillers fill the 24 576-entry list area, so super-chunk 0 ends among them and
+    the head of the second half prefers a target that carries super-chunk 0's permanent mark, not a claim.  The number of sparse fillers is chosen from
+    the geometry alone so that the second half starts 24 queries in front of local index 1 024 of super-chunk 1: the chain runs out of the threads'
+    first queries (threads 1000 .. 1023) into their second ones (threads 0 .. 23).  2048 x 1040 px is what the 843 sparse fillers need; one detection
+    cell of 4096 px, the largest a handle takes."""
+    W, H, (lc, lr, lx, ly), dense, sparse, staged, n_frames = DOMINO_SCENES[name]
+    nodes = boustrophedon(lc, lr, lx, ly)
+    n = len(nodes)
+    prm = lvt_amd.kitti_params(width=W, height=H)
+    prm.tracking_radius, prm.staged_threshold, prm.triangulation_policy = DOMINO_RADIUS, staged, 2
+    prm.tracking_ratio_test_threshold = prm.triangulation_ratio_test_threshold = DOMINO_RATIO
+    if W > 1241:          # detection is unused: one cell for the large image (the KITTI-sized scene keeps KITTI's grid: its parameters serve the ordinary
+        prm.detection_cell_size = 4096          # world that shares the lock-step pool with it)
+    # one spare corner behind every lattice row, on the background and last in the corner order: the last query of a chain still has two candidates to
+    # choose from (with one left, the absolute threshold would decide, and reject)
+    spare = np.array([(lx + DOMINO_PITCH * lc, ly + DOMINO_PITCH * r) for r in range(lr)], dtype=np.int64)
+    if dense is None:
+        corners, chain = np.vstack([nodes, spare]), np.arange(n)
+    else:
+        dc, dr, dx, dy, dp = dense
+        D = np.array([(dx + dp * c, dy + dp * r) for r in range(dr) for c in range(dc)], dtype=np.int64)
+        sc, sx, sy, sp = sparse
+        half = n // 2
+        head = np.vstack([nodes[:half], D])
+        # the cut of super-chunk 0 from the geometry: candidates of a map point = corners closer than the radius (fillers and nodes are > radius apart)
+        cnt = np.concatenate([_neighbour_counts(nodes.astype(np.float64), DOMINO_RADIUS)[:half], _neighbour_counts(D.astype(np.float64), DOMINO_RADIUS)])
+        first = super_chunks(cnt)[0][1]
+        assert half < first < len(head), (first, len(head))
+        n_sparse = RES_THREADS - 24 - (len(head) - first)
+        S = np.array([(sx + sp * (k % sc), sy + sp * (k // sc)) for k in range(n_sparse)], dtype=np.int64)
+        assert S[:, 1].max() < H - DOMINO_HALF - 1 and S[:, 0].max() < W - DOMINO_HALF - 1
+        corners = np.vstack([head, S, nodes[half:], spare])
+        chain = np.concatenate([np.arange(half), len(head) + n_sparse + np.arange(n - half)])
+    P, blend, spare_patches = domino_patches(n, lr)
+    back = np.random.default_rng(21).integers(0, 256, (H, W), dtype=np.uint8)
+
+    def paste(img, patches, shift):
+        for (x, y), p in list(zip(nodes, patches)) + list(zip(spare, spare_patches)):
+            img[y - DOMINO_HALF:y + DOMINO_HALF + 1, x - shift - DOMINO_HALF:x - shift + DOMINO_HALF + 1] = p
+        return np.ascontiguousarray(img)
+
+    L0 = paste(back.copy(), P[:-1], 0)
+    R0 = paste(np.roll(back, -DOMINO_DISP, axis=1), blend, DOMINO_DISP)
+    L1 = paste(back.copy(), blend, 0)
+    R1 = np.ascontiguousarray(np.roll(L1, -DOMINO_DISP, axis=1))
+    cl = corners.astype(np.float64)
+    cr = cl - [[float(DOMINO_DISP), 0.0]]
+    frames = [(L0, R0, cl, cr)] + [(L1, R1, cl, cr)] * (n_frames - 1)
+    if name == "staged_chain":
+        fill = cl[half:len(head) + n_sparse]
+        keep = np.r_[0:len(cl) - lr, len(cl) - lr + STAGED_CHAIN_DROPPED:len(cl)]
+        frames = [(L0, R0, fill, fill - [[float(DOMINO_DISP), 0.0]]), (L0, R0, cl, cr), (L1, R1, cl[keep], cr[keep])]
+    return prm, frames, dict(n_chain=n, chain=chain, n_corners=len(corners))
+
+
+# ---- the two procedures over explicit candidate lists ------------------------------------------------------------------------------------------------
+# A list holds a query's candidates as (distance, target index) sorted ascending; accept is accept_match's rule (k_track.hip; find_match_index and
+# row_match in the oracle): with two or more candidates available the ratio of the best two distances decides (in fp32, 0 / 0 rejects), with exactly
+# one the absolute threshold.
+def _accept(avail, ratio, desc_th):
+    if len(avail) > 1:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return bool(np.float32(avail[0][0]) / np.float32(avail[1][0]) < np.float32(ratio))
+    return len(avail) == 1 and np.float32(avail[0][0]) <= np.float32(desc_th)
+
+
+def greedy_serial(lists, ratio, desc_th, marked=()):
+    """(a) the reference's scan: query q takes the best of its still unmarked candidates if the rule accepts it, and marks it.  Returns the
+    decisions (target or -1)."""
+    marked = set(marked)
+    out = []
+    for lst in lists:
+        avail = [c for c in lst if c[1] not in marked][:2]
+        out.append(avail[0][1] if _accept(avail, ratio, desc_th) else -1)
+        if out[-1] >= 0:
+            marked.add(out[-1])
+    return out
+
+
+def greedy_fixpoint(lists, ratio, desc_th, marked=()):
+    """(b) the synchronous fixpoint: in iteration t every query decides at once; a candidate is unavailable when it is marked or when a query with a
+    smaller index accepted it in iteration t - 1.  Ends with the first iteration that changes no decision.  Returns (decisions, iterations)."""
+    marked = set(marked)
+    prev, claim, it = [-2] * len(lists), {}, 0
+    while True:
+        it += 1
+        cur, new_claim = [], {}
+        for q, lst in enumerate(lists):
+            avail = [c for c in lst if c[1] not in marked and claim.get(c[1], q) >= q][:2]
+            d = avail[0][1] if _accept(avail, ratio, desc_th) else -1
+            cur.append(d)
+            if d >= 0 and d not in new_claim:
+                new_claim[d] = q            # (queries come in ascending order: the first claim is the earliest query's)
+        if cur == prev:
+            return cur, it
+        prev, claim = cur, new_claim
+
+
+def _hamming(a, b):
+    return np.unpackbits(a[:, None, :] ^ b[None, :, :], axis=2).sum(2).astype(np.int64)
+
+
+def map_lists(prm, map_xyz, map_desc, q, p, feat_xy, feat_desc):
+    """find_matches' candidate lists: map points projected with the pose (q = w x y z, p: camera to world), features closer than the tracking radius
+    (find_match_index's fp32 test; its hash cells cover the circle).  Returns (lists, visible)."""
+    w, x, y, z = q
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    Xc = (map_xyz - p) @ R
+    vis = (Xc[:, 2] >= prm.near_plane_distance) & (Xc[:, 2] <= prm.far_plane_distance)
+    zc = np.where(vis, Xc[:, 2], 1.0)
+    u, v = prm.fx * Xc[:, 0] / zc + prm.cx, prm.fy * Xc[:, 1] / zc + prm.cy
+    vis &= (u >= 0) & (u <= prm.img_width) & (v >= 0) & (v <= prm.img_height)
+    dx = feat_xy[None, :, 0] - u.astype(np.float32)[:, None]
+    dy = feat_xy[None, :, 1] - v.astype(np.float32)[:, None]
+    near = (dx * dx + dy * dy) < np.float32(prm.tracking_radius * prm.tracking_radius)
+    lists = []
+    for i in range(len(map_xyz)):
+        idx = np.flatnonzero(near[i]) if vis[i] else np.zeros(0, np.int64)
+        d = _hamming(map_desc[i:i + 1], feat_desc[idx])[0] if len(idx) else []
+        lists.append(sorted(zip((int(k) for k in d), (int(k) for k in idx))))
+    return lists, vis
+
+
+def row_lists(left_xy, left_desc, right_xy, right_desc, img_rows):
+    """row_match's candidate lists: every right feature of the query's +-2 row band, whatever its x"""
+    lists = []
+    for i in range(len(left_xy)):
+        y0, y1 = max(int(left_xy[i, 1]) - 2, 0), min(int(left_xy[i, 1]) + 2, img_rows)
+        idx = np.flatnonzero((right_xy[:, 1] >= y0) & (right_xy[:, 1] <= y1))
+        d = _hamming(left_desc[i:i + 1], right_desc[idx])[0] if len(idx) else []
+        lists.append(sorted(zip((int(k) for k in d), (int(k) for k in idx))))
+    return lists

@@ -228,3 +228,180 @@ def test_oracle_capacity_option_cuts_all_three_append_sites(oracle_lib):
     assert rows[3]["n_staged_promoted"] + rows[3]["n_staged_erased"] == 2000 and rows[3]["n_staged_promoted"] > 1900 and rows[3]["map_size"] == 3000
     assert rows[3]["staged_size"] == rows[3]["n_triangulated"] < 2000
     assert ref.counts()["map_size"] > 10000
+
+
+# ---- the domino scenes (test_gpu_resolver_chains.py) ----------------------------------------------------------------------------------------------
+from case_tables import (DOMINO_BEST, DOMINO_MIN_DEPTH, DOMINO_OTHER, DOMINO_RATIO, DOMINO_SECOND, RES_LCAP, RES_THREADS, STAGED_CHAIN_DROPPED,
+                         domino_scene, greedy_fixpoint, greedy_serial, map_lists, row_lists, super_chunks)
+
+
+def test_fixpoint_equals_the_serial_scan_on_random_lists():
+    """(a) == (b) on 400 random instances: few targets and distances from a small set (ties, contested targets, both branches of the accept rule,
+    0 / 0), marks from before the call; and on a planted chain of n queries (b) needs exactly n + 1 iterations"""
+    rng = np.random.default_rng(7)
+    deep = 0
+    for _ in range(400):
+        nq, nt = int(rng.integers(1, 40)), int(rng.integers(1, 25))
+        lists = []
+        for q in range(nq):
+            t = rng.choice(nt, size=int(rng.integers(0, min(nt, 6) + 1)), replace=False)
+            lists.append(sorted((int(rng.choice([0, 10, 20, 24, 25, 30, 31, 60, 100])), int(k)) for k in t))
+        marked = [int(k) for k in np.flatnonzero(rng.random(nt) < 0.15)]
+        ratio = float(rng.choice([0.6, 0.8, 0.9]))
+        a = greedy_serial(lists, ratio, 30.0, marked)
+        b, it = greedy_fixpoint(lists, ratio, 30.0, marked)
+        assert a == b and 1 <= it <= nq + 1, (lists, marked, ratio, a, b, it)
+        assert len({d for d in a if d >= 0}) == sum(d >= 0 for d in a) and not set(a) & set(marked)
+        deep = max(deep, it)
+    assert deep >= 4
+    for n in (1, 2, 17, 100):
+        chain = [[(80, 0), (110, n)]] + [[(45, q - 1), (80, q), (110, n)] for q in range(1, n)]
+        b, it = greedy_fixpoint(chain, 0.9, 30.0)
+        assert b == list(range(n)) == greedy_serial(chain, 0.9, 30.0) and it == n + 1, (n, it)
+
+
+def test_super_chunk_cut_is_the_resolvers():
+    """the restated cut: QCAP queries, LCAP entries in lists rounded up to four, a list over KC alone"""
+    assert super_chunks([5] * 5000) == [(0, 2048), (2048, 2048), (4096, 904)]
+    assert super_chunks([45] * 600) == [(0, RES_LCAP // 48), (RES_LCAP // 48, 600 - RES_LCAP // 48)] and RES_LCAP // 48 == 512
+    assert super_chunks([3, 129, 3, 0, 200]) == [(0, 1), (1, 1), (2, 2), (4, 1)]
+
+
+def _triples(lists, chain):
+    """(best, second, third) distances of the chain's queries behind its head, each as (min, median, max)"""
+    a = np.array([[c[0] for c in lists[k][:3]] for k in chain[1:]])
+    return [(int(a[:, j].min()), int(np.median(a[:, j])), int(a[:, j].max())) for j in range(3)]
+
+
+_DOMINO = {}
+
+
+def _domino_run(O, name):
+    """the scene through the oracle alone, once per session: per frame its counts, status, row lists (frame 0) or map lists, the oracle's decisions and,
+    for staged_chain's last frame, the staged lists with the marks find_matches left behind"""
+    if name in _DOMINO:
+        return _DOMINO[name]
+    prm, frames, info = domino_scene(name)
+    orc = O.Oracle(prm, 1)
+    rows = []
+    for i, f in enumerate(frames):
+        (mxyz, _, _, mdesc), (sxyz, _, sdesc) = orc.map(), orc.staged()
+        orc.track_with_external_corners(*f)
+        fl, fr = orc.features(0), orc.features(1)
+        row = dict(counts=orc.counts(), status=orc.status, row_pairs=orc.row_matches(), matches=orc.matches()[0])
+        if i == 0:
+            row["row_lists"] = row_lists(fl[0], fl[2], fr[0], fr[2], prm.img_height)
+        else:
+            row["map_lists"], vis = map_lists(prm, mxyz, mdesc, *orc.predicted_pose(), fl[0], fl[2])
+            assert vis.all()
+        if len(sxyz):
+            row["staged_lists"], vis = map_lists(prm, sxyz, sdesc, *orc.pose(), fl[0], fl[2])
+            assert vis.all()
+        rows.append(row)
+    _DOMINO[name] = (prm, info, rows)
+    return _DOMINO[name]
+
+
+def _map_conditions(prm, info, rows, frame):
+    """find_matches of a frame: the oracle's matches are simulation (a)'s on lists built from its own features, map and predicted pose, every map point
+    takes the feature of its own corner, and the oracle keeps tracking with all of them.  Returns the lists and (a)'s decisions."""
+    r = rows[frame]
+    lists = r["map_lists"]
+    a = greedy_serial(lists, prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold)
+    assert [d for d in a if d >= 0] == r["matches"].tolist()
+    assert a == list(range(len(lists)))
+    assert r["status"] == 2 and r["counts"]["n_matches"] == len(lists) >= info["n_chain"] and r["counts"]["second_pass"] == 0
+    return lists, a
+
+
+def test_map_chain_conditions(oracle_lib):
+    """`map_chain`: 95 nodes + 5 spares, nothing lost at the border; frames 1 and 2 are one chain of 95 queries in one super-chunk, depth 96"""
+    prm, info, rows = _domino_run(oracle_lib, "map_chain")
+    n = info["n_chain"]
+    assert n == 95 and info["n_corners"] == 100 and rows[0]["counts"]["n_triangulated"] == rows[0]["counts"]["map_size"] == 100
+    for frame in (1, 2):
+        lists, a = _map_conditions(prm, info, rows, frame)
+        assert super_chunks([len(l) for l in lists]) == [(0, 100)] and max(len(l) for l in lists) == 5
+        b, it = greedy_fixpoint(lists, prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold)
+        assert b == a and it == 96 >= DOMINO_MIN_DEPTH["map_chain"] == 64
+        # the chain itself: query i sees target i - 1, then target i, then an unrelated one, at the distances the patches were drawn for
+        for k in range(1, n):
+            (d1, t1), (d2, t2), (d3, _) = lists[k][:3]
+            assert (t1, t2) == (k - 1, k) and DOMINO_BEST[0] <= d1 <= DOMINO_BEST[1] and DOMINO_SECOND[0] <= d2 <= DOMINO_SECOND[1] and d3 >= DOMINO_OTHER
+        assert lists[0][0][1] == 0 and lists[0][1][0] >= DOMINO_OTHER
+        assert _triples(lists, info["chain"]) == [(36, 47, 54), (70, 77, 86), (101, 117, 152)]
+    # with room: the worst node stays 0.13 below the ratio threshold on the way in (best / second) and 0.04 on the way out (second / third)
+    assert DOMINO_BEST[1] / DOMINO_SECOND[0] < 0.78 and DOMINO_SECOND[1] / DOMINO_OTHER <= 0.86 < DOMINO_RATIO == prm.tracking_ratio_test_threshold
+
+
+def test_row_chain_conditions(oracle_lib):
+    """`row_chain` = frame 0 of `map_chain`: row_match offers a query the 20 right features of its lattice row (19 nodes and the spare): five chains of
+    19 running at once, depth 20; every left corner pairs with its own partner and triangulates"""
+    prm, info, rows = _domino_run(oracle_lib, "map_chain")
+    lists = rows[0]["row_lists"]
+    assert [len(l) for l in lists] == [20] * 100
+    a = greedy_serial(lists, prm.triangulation_ratio_test_threshold, prm.descriptor_matching_threshold)
+    b, it = greedy_fixpoint(lists, prm.triangulation_ratio_test_threshold, prm.descriptor_matching_threshold)
+    assert a == b == list(range(100)) and it == 20 >= DOMINO_MIN_DEPTH["row_chain"] == 16
+    assert np.array_equal(rows[0]["row_pairs"], np.column_stack([np.arange(100), a]))
+    heads = set(range(0, 95, 19))
+    for k in range(95):
+        if k not in heads:
+            assert [t for _, t in lists[k][:2]] == [k - 1, k] and lists[k][2][0] >= DOMINO_OTHER
+        else:
+            assert lists[k][0][1] == k and lists[k][1][0] >= DOMINO_OTHER
+    body = [k for k in range(95) if k not in heads]
+    assert _triples(lists, [0] + body) == [(36, 47, 54), (70, 77, 86), (100, 108, 118)]
+
+
+def test_chain_across_super_chunks_conditions(oracle_lib):
+    """`chain_across_super_chunks`: 47 chain queries, 768 dense and 843 sparse fillers, 48 chain queries, 5 spares.  The dense fillers end super-chunk 0
+    on the list area at query 610; the second half of the chain holds local queries 1000 .. 1047 of super-chunk 1, across local index 1 024; its head
+    prefers the target of query 46, which carries super-chunk 0's permanent mark.  Depths 48 and 49."""
+    prm, info, rows = _domino_run(oracle_lib, "chain_across_super_chunks")
+    n, chain = info["n_chain"], info["chain"]
+    half = n // 2
+    assert (n, half, info["n_corners"]) == (95, 47, 1663) and rows[0]["counts"]["map_size"] == 1663
+    for frame in (1, 2):
+        lists, a = _map_conditions(prm, info, rows, frame)
+        ncand = [len(l) for l in lists]
+        chunks = super_chunks(ncand)
+        assert chunks == [(0, 610), (610, 1053)] and max(ncand) == 45 <= 128
+        assert sum((c + 3) & ~3 for c in ncand[:610]) <= RES_LCAP < sum((c + 3) & ~3 for c in ncand[:611])        # cut by the list area, among the dense fillers
+        assert half < 610 < half + 768
+        local = chain[half:] - 610
+        assert local[0] == 1000 and local[-1] == 1047 and local[0] < RES_THREADS < local[-1] and np.array_equal(np.diff(local), np.ones(47))
+        marked, depth = set(), []
+        for b0, used in chunks:
+            sub = lists[b0:b0 + used]
+            b, it = greedy_fixpoint(sub, prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold, marked)
+            assert b == a[b0:b0 + used]
+            marked |= set(b)
+            depth.append(it)
+        assert depth == [48, 49] and depth[1] >= DOMINO_MIN_DEPTH["chain_across_super_chunks"] == 32
+        head = lists[chain[half]]
+        assert head[0][1] == chain[half - 1] < 610 and head[1][1] == chain[half]        # its best target was taken in super-chunk 0
+        # without that mark the head would take it: the second half is decided wrongly from its first query on if the mark goes stale
+        assert greedy_serial(lists[610:], prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold)[local[0]] == chain[half - 1]
+        for j, k in enumerate(chain):
+            if j:
+                assert [t for _, t in lists[k][:2]] == [chain[j - 1], k] and lists[k][2][0] >= DOMINO_OTHER
+    assert prm.img_width <= 4096 and prm.img_height <= 4096 and prm.detection_cell_size >= max(prm.img_width, prm.img_height)    # one detection cell
+
+
+def test_staged_chain_conditions(oracle_lib):
+    """`staged_chain`: frame 0 maps the 1 563 fillers, frame 1 stages the chain and the spares (100 points, in corner order), frame 2 runs them through
+    update_staged: 97 promoted, the three spares whose corners are gone erased; the staged scan is one chain of 95, depth 96"""
+    prm, info, rows = _domino_run(oracle_lib, "staged_chain")
+    c = [r["counts"] for r in rows]
+    assert prm.staged_threshold == 1 and all(r["status"] == 2 for r in rows)
+    assert (c[0]["map_size"], c[0]["staged_size"]) == (1563, 0) and (c[1]["map_size"], c[1]["staged_size"], c[1]["n_matches"]) == (1563, 100, 1563)
+    assert (c[2]["n_staged_promoted"], c[2]["n_staged_erased"], c[2]["staged_size"], c[2]["map_size"]) == (97, STAGED_CHAIN_DROPPED, 0, 1660)
+    lists = rows[2]["staged_lists"]
+    marks = rows[2]["matches"].tolist()              # what find_matches marked; nothing was culled
+    assert len(lists) == 100 and c[2]["n_culled"] == 0 and len(marks) == 1563
+    a = greedy_serial(lists, prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold, marks)
+    b, it = greedy_fixpoint(lists, prm.tracking_ratio_test_threshold, prm.descriptor_matching_threshold, marks)
+    assert a == b and it == 96 >= 16
+    assert sum(d >= 0 for d in a) == c[2]["n_staged_promoted"] and sum(d < 0 for d in a) == c[2]["n_staged_erased"]
+    assert a[:95] == info["chain"].tolist() and [d >= 0 for d in a[95:]] == [False] * STAGED_CHAIN_DROPPED + [True] * (5 - STAGED_CHAIN_DROPPED)
