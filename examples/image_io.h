@@ -1,6 +1,7 @@
 // image_io.h -- the image readers of the dataset harnesses (no OpenCV: zlib only).
 // PNG: 8/16-bit gray, gray+alpha, RGB, RGBA, non-interlaced; PGM: binary P5.  Colour is reduced to gray with
-// cv::cvtColor's fixed-point weights; 16-bit samples are kept (depth maps) and also narrowed to their high byte.
+// cv::cvtColor's fixed-point weights -- and kept, interleaved R G B, for callers that hand the tracker colour frames (LVT_AMD_PIX_RGB8);
+// 16-bit samples are kept (depth maps) and also narrowed to their high byte.
 #pragma once
 #include <zlib.h>
 
@@ -19,6 +20,7 @@ struct Gray {
     int w = 0, h = 0;
     std::vector<unsigned char> px;   // 8-bit gray (16-bit files: the high byte)
     std::vector<uint16_t> px16;      // filled for 16-bit gray files only (TUM depth maps)
+    std::vector<unsigned char> rgb;  // filled for colour PNGs only: interleaved R G B, 3 bytes per pixel (px is to_gray of these)
 };
 
 inline bool read_file(const std::string &path, std::vector<unsigned char> &out) {
@@ -75,7 +77,9 @@ inline bool decode_png(const std::vector<unsigned char> &buf, Gray &img, std::st
     img.w = w, img.h = h;
     img.px.resize((size_t)w * h);
     img.px16.clear();
+    img.rgb.clear();
     if (depth == 16 && ch <= 2) img.px16.resize((size_t)w * h);
+    if (ch >= 3) img.rgb.resize((size_t)w * h * 3);
     for (int y = 0; y < h; y++) {
         const unsigned char *line = &raw[(stride + 1) * (size_t)y];
         const int ft = line[0];
@@ -102,8 +106,11 @@ inline bool decode_png(const std::vector<unsigned char> &buf, Gray &img, std::st
             if (ch <= 2) {
                 img.px[(size_t)y * w + x] = p[0];
                 if (!img.px16.empty()) img.px16[(size_t)y * w + x] = (uint16_t)((p[0] << 8) | p[1]);  // PNG samples are big-endian
-            } else
-                img.px[(size_t)y * w + x] = to_gray(p[0], p[bps], p[2 * bps]);
+            } else {
+                unsigned char *c = &img.rgb[((size_t)y * w + x) * 3];
+                c[0] = p[0], c[1] = p[bps], c[2] = p[2 * bps];
+                img.px[(size_t)y * w + x] = to_gray(c[0], c[1], c[2]);
+            }
         }
         std::swap(cur, prev);
     }
@@ -131,6 +138,7 @@ inline bool decode_pgm(const std::vector<unsigned char> &buf, Gray &img, std::st
     if (w <= 0 || h <= 0 || mx <= 0 || mx > 255 || pos + (size_t)w * h > buf.size()) return err = "unsupported PGM", false;
     img.w = w, img.h = h;
     img.px.assign(buf.begin() + (long)pos, buf.begin() + (long)(pos + (size_t)w * h));
+    img.px16.clear(), img.rgb.clear();
     return true;
 }
 

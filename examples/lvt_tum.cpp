@@ -3,7 +3,8 @@
 // Same argv, inputs and outputs as the reference's example binary (examples/tum_rgbd/tum_rgbd_example.cpp:49-150 there):
 //     lvt_tum <tum_sequences_root_dir> <associations_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt]
 // reads <associations_dir>/<dataset_name>.txt ("t_rgb rgb/xxx.png t_depth depth/xxx.png" per line), the colour and the 16-bit
-// depth PNGs below <root>/<dataset_name>/, converts colour to gray (cv::cvtColor weights), hands the PNG's 16-bit depth plane to
+// depth PNGs below <root>/<dataset_name>/, hands the decoded RGB to the tracker as it is (LVT_AMD_PIX_RGB8: the conversion to gray, cv::cvtColor's
+// weights, is the first launch of the frame's feature stage; a dataset of gray PNGs goes in as gray) and the PNG's 16-bit depth plane to
 // lvt_amd_track_rgbd16_async with 1.0f / 5000.0f metres per unit (the tracker computes value * (1.0f / 5000.0f) in float where it has key
 // points -- what cv::Mat::convertTo gives the reference for every pixel) and writes <dataset_name>.txt in
 // the TUM trajectory format "t x y z qx qy qz qw" with the reference's precision (6 digits for t, 7 for the rest).
@@ -86,14 +87,23 @@ int main(int argc, char **argv) {
     };
     Frame cur, nxt;
     load(0, cur);
+    const bool colour = cur.ok && !cur.rgb.rgb.empty();  // colour PNGs: the tracker takes the interleaved RGB; every later frame must be colour too
+    if (colour && lvt_amd_set_pixel_format(vo, LVT_AMD_PIX_RGB8) != 0) {
+        std::cout << "failed to set the pixel format: " << lvt_amd_last_error(vo) << std::endl;
+        return -1;
+    }
     for (long i = 0; i < frame_count; i++) {
         std::cout << "Frame number: " << i << "/" << frame_count << "\r" << std::flush;
         if (!cur.ok) {
             std::cout << "Failed to load image " << std::endl;
             break;
         }
+        if (!cur.rgb.rgb.empty() != colour) {  // the pixel format was set from the first frame
+            std::cout << "Frame " << i << " is a " << (colour ? "gray" : "colour") << " image in a dataset that began with " << (colour ? "colour" : "gray") << " images" << std::endl;
+            break;
+        }
         const auto t0 = std::chrono::steady_clock::now();
-        const int queued = lvt_amd_track_rgbd16_async(vo, cur.rgb.px.data(), cur.depth.px16.data(), depth_scale, cur.rgb.h, cur.rgb.w);
+        const int queued = lvt_amd_track_rgbd16_async(vo, colour ? cur.rgb.rgb.data() : cur.rgb.px.data(), cur.depth.px16.data(), depth_scale, cur.rgb.h, cur.rgb.w);
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (queued != 0) break;  // (a frame of another size: the reference would throw inside OpenCV)
         load(i + 1, nxt);

@@ -239,7 +239,9 @@ LVT_API void lvt_amd_get_timeline(lvt_handle h, long long out[16]);
  * polling gate holds up whatever another handle queued behind it) */
 LVT_API int lvt_amd_get_ordering(lvt_handle h);
 /* raw per-pixel intermediates of the last frame: what = 0 score map (u8, rows x pitch),
- * 1 box-sum map (u16, rows x pitch), 2 the rectified image of a handle with rectifiers (u8, rows x pitch; 0 bytes without them).
+ * 1 box-sum map (u16, rows x pitch), 2 the rectified image of a handle with rectifiers (u8, rows x pitch; 0 bytes without them),
+ * 3 the converted gray image of a handle with a colour pixel format (u8, rows x pitch, before rectification; 0 bytes on a gray handle, and when the
+ *   last frame was handed in before the colour format was set: nothing was converted for it).
  * returns bytes written, pitch via *pitch_out (in elements). */
 LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int cap_bytes, int *pitch_out);
 
@@ -306,6 +308,27 @@ LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier r, float *map1, float *
  *    lvt_amd_profile_read reports the launch as "k_rectify_frames". */
 LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right);
 LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right);
+
+/* COLOUR frames: gray conversion inside the tracker's feature stage.  The pixel format is a property of the handle, or of one sequence of a batch, like the
+ * rectifiers.  Once a colour format is set, EVERY frame-taking call on that handle or sequence -- lvt_track, lvt_track_with_external_corners,
+ * lvt_amd_track_async, lvt_amd_track_device[_async], lvt_amd_track_rgbd[_async], lvt_amd_track_rgbd16[_async], lvt_amd_track_rgbd_device[_async], the
+ * batch calls (sit-outs included) -- takes its image(s) interleaved in that format.  One launch at the head of the feature stage (k_gray_frames: every
+ * colour image of the step) converts them into planes the tracker owns,
+ *     gray = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14        (cv::cvtColor's 8-bit BGR2GRAY; (255,0,0) -> 76, (0,255,0) -> 150, (0,0,255) -> 29)
+ * and the frame is tracked from those; with rectifiers attached the order is the reference's: convert, then remap.  The alpha byte of the 4-byte formats
+ * is ignored.  A handle or sequence that never sets a format launches exactly what it did before; LVT_AMD_PIX_GRAY8 returns a handle to that path.
+ *  - n_rows / n_cols stay in PIXELS.  Host buffers are tightly packed, n_cols * bpp bytes per row; page-locked ones are read in place as before.
+ *  - device planes: any base address and any pitch_bytes >= n_cols * bpp (a smaller pitch is refused); the pitch % 16 / 16-byte alignment rules belong to gray
+ *    planes.  For RGB-D the `gray` argument is the colour image; the depth plane and its format are untouched.
+ *  - external corners are in the same coordinates: lvt_track_with_external_corners stays allowed.
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error): an unknown format, a pooled or automatic seat, seq out of range, the batch call on a
+ *    handle that is not a batch and the other way round, a handle with frames in flight (set the format before the first frame or after every frame has
+ *    been collected).  A successful set counts as use of an lvt_create handle.
+ *  - lvt_amd_get_plane(h, eye, 3, ...) reads the converted gray plane of the last frame back; lvt_amd_profile_read reports the launch as "k_gray_frames". */
+enum { LVT_AMD_PIX_GRAY8 = 0, LVT_AMD_PIX_BGR8 = 1, LVT_AMD_PIX_RGB8 = 2, LVT_AMD_PIX_BGRA8 = 3, LVT_AMD_PIX_RGBA8 = 4 };
+LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format);                 /* 0 / -1 */
+LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format);  /* 0 / -1 */
+LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq);                    /* format, -1: bad handle / seq */
 
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without

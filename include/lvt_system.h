@@ -207,7 +207,8 @@ typedef std::vector<lvt_pose, Eigen::aligned_allocator<lvt_pose>> lvt_pose_array
 typedef std::vector<lvt_pose> lvt_pose_array;
 #endif
 
-/* a borrowed image plane: 8-bit gray (elem_size 1) or 32-bit float depth in metres (elem_size 4); rows `step` bytes apart */
+/* a borrowed image plane: 8-bit gray (elem_size 1), 32-bit float depth in metres (elem_size 4) or -- for a system with a colour pixel format,
+ * lvt_system::set_pixel_format -- interleaved 8-bit colour (elem_size 3 or 4 bytes per pixel); rows `step` bytes apart */
 struct lvt_image_view {
     const void *data;
     int rows, cols;
@@ -215,9 +216,10 @@ struct lvt_image_view {
     int elem_size;
     lvt_image_view() : data(nullptr), rows(0), cols(0), step(0), elem_size(1) {}
     lvt_image_view(const unsigned char *p, int rows_, int cols_, size_t step_ = 0) : data(p), rows(rows_), cols(cols_), step(step_ ? step_ : (size_t)cols_), elem_size(1) {}
+    lvt_image_view(const unsigned char *p, int rows_, int cols_, int bytes_per_pixel, size_t step_) : data(p), rows(rows_), cols(cols_), step(step_ ? step_ : (size_t)cols_ * (size_t)bytes_per_pixel), elem_size(bytes_per_pixel) {}
     lvt_image_view(const float *p, int rows_, int cols_, size_t step_ = 0) : data(p), rows(rows_), cols(cols_), step(step_ ? step_ : sizeof(float) * (size_t)cols_), elem_size(4) {}
 #if defined(LVT_SYSTEM_HAVE_OPENCV)
-    lvt_image_view(const cv::Mat &m) : data(m.data), rows(m.rows), cols(m.cols), step(m.step[0]), elem_size((int)m.elemSize()) {} /* CV_8UC1 / CV_32FC1 */
+    lvt_image_view(const cv::Mat &m) : data(m.data), rows(m.rows), cols(m.cols), step(m.step[0]), elem_size((int)m.elemSize()) {} /* CV_8UC1 / CV_32FC1; CV_8UC3 / CV_8UC4 on a colour system */
 #endif
 };
 
@@ -251,7 +253,7 @@ class lvt_system {
      * Returns the camera-to-world pose of the left camera in the first frame's left-camera frame; after LOST, the last pose. */
     lvt_pose track(const lvt_image_view &img1, const lvt_image_view &img2) {
         double R[3][3], t[3];
-        if (img2.rows != img1.rows || img2.cols != img1.cols || img1.elem_size != 1 || img2.elem_size != (m_sensor == eSensor_STEREO ? 1 : 4)) {
+        if (img2.rows != img1.rows || img2.cols != img1.cols || img1.elem_size != m_bpp || img2.elem_size != (m_sensor == eSensor_STEREO ? m_bpp : 4)) {
             /* the C-ABI is told ONE size for both planes: a second plane of another size (or element type) would be read out of bounds.
                The reference would throw inside OpenCV here and lvt_c.cpp:85-87 swallows that: same outcome, the last pose */
             return current_pose();
@@ -266,11 +268,19 @@ class lvt_system {
      * t tracks (kitti_example.cpp:113-138 does both in turn); wait_pose() returns the poses in the order of the track_async() calls.  false: the
      * frame was rejected (size / element type), nothing was enqueued. */
     bool track_async(const lvt_image_view &img1, const lvt_image_view &img2) {
-        if (img2.rows != img1.rows || img2.cols != img1.cols || img1.elem_size != 1 || img2.elem_size != (m_sensor == eSensor_STEREO ? 1 : 4)) return false;
+        if (img2.rows != img1.rows || img2.cols != img1.cols || img1.elem_size != m_bpp || img2.elem_size != (m_sensor == eSensor_STEREO ? m_bpp : 4)) return false;
         const unsigned char *a = static_cast<const unsigned char *>(packed(img1, m_buf1));
         if (m_sensor == eSensor_STEREO)
             return lvt_amd_track_async(m_handle, a, static_cast<const unsigned char *>(packed(img2, m_buf2)), img1.rows, img1.cols) == 0;
         return lvt_amd_track_rgbd_async(m_handle, a, static_cast<const float *>(packed(img2, m_buf2)), img1.rows, img1.cols) == 0;
+    }
+    /* ADDITIVE: the pixel format of every image handed to this system from now on (LVT_AMD_PIX_GRAY8 ... LVT_AMD_PIX_RGBA8, include/lvt_amd_ext.h): colour
+     * frames are converted to gray (cv::cvtColor's weights) by the first launch of their feature stage.  Views then have elem_size 3 or 4.  false: refused
+     * (last_error() says why), nothing changed. */
+    bool set_pixel_format(int format) {
+        if (lvt_amd_set_pixel_format(m_handle, format) != 0) return false;
+        m_bpp = (format == LVT_AMD_PIX_GRAY8) ? 1 : (format >= LVT_AMD_PIX_BGRA8 ? 4 : 3);
+        return true;
     }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
@@ -331,6 +341,7 @@ class lvt_system {
 
     lvt_handle m_handle;
     int m_state = -1;
+    int m_bpp = 1; /* bytes per pixel of the image views (set_pixel_format) */
     eSensor m_sensor;
     lvt_parameters m_params;
     std::vector<unsigned char> m_buf1, m_buf2;

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "lvt_amd_track_rgbd_device", "lvt_amd_track_rgbd_device_async", "lvt_amd_track_rgbd16", "lvt_amd_track_rgbd16_async",
     "lvt_amd_batch_track_rgbd_device_async",
     "lvt_amd_set_rectifiers", "lvt_amd_batch_set_rectifiers",
+    "lvt_amd_set_pixel_format", "lvt_amd_batch_set_pixel_format", "lvt_amd_get_pixel_format",
 ]
 
 N_COUNTS = 32
@@ -47,6 +48,8 @@ COUNT_NAMES = ["n_left", "n_right", "map_size", "staged_size", "n_matches", "sec
 
 eState_NOT_INITIALIZED, eState_TRACKING, eState_LOST = 1, 2, 3
 eSensor_STEREO, eSensor_RGBD = 1, 2
+PIX_GRAY8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8 = 0, 1, 2, 3, 4   # LVT_AMD_PIX_*: interleaved 8-bit formats a handle / a batch sequence takes its frames in
+PIX_BPP = {PIX_GRAY8: 1, PIX_BGR8: 3, PIX_RGB8: 3, PIX_BGRA8: 4, PIX_RGBA8: 4}
 DEPTH_F32, DEPTH_U16 = 0, 1   # LVT_AMD_DEPTH_F32 (metres) / LVT_AMD_DEPTH_U16 (raw sensor units: metres = raw * depth_scale)
 
 _lib = None
@@ -163,6 +166,11 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (("lvt_amd_set_pixel_format", [vp, C.c_int]), ("lvt_amd_batch_set_pixel_format", [vp, C.c_int, C.c_int]),
+                           ("lvt_amd_get_pixel_format", [vp, C.c_int])):   # (colour frames: likewise)
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -174,9 +182,13 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-def _u8(img):
-    a = np.ascontiguousarray(img, dtype=np.uint8)
-    assert a.ndim == 2
+def _u8(img, bpp=1):
+    """a contiguous uint8 image of bpp bytes per pixel: (H, W) for gray, (H, W, bpp) for a colour format -- anything else raises"""
+    a = img if (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags.c_contiguous) else np.ascontiguousarray(img, dtype=np.uint8)
+    if bpp == 1:
+        assert a.ndim == 2
+    elif a.ndim != 3 or a.shape[2] != bpp:
+        raise ValueError(f"an image of shape {a.shape} on a handle whose pixel format has {bpp} bytes per pixel: expected (H, W, {bpp})")
     return a
 
 
@@ -186,6 +198,7 @@ class LvtSystem:
     def __init__(self, handle, sensor_type):
         self._h = handle
         self._sensor = sensor_type
+        self._bpp = 1   # bytes per pixel of the handle's pixel format (set_pixel_format)
 
     # lvt_system::create(const lvt_parameters&, eSensor)  -- lvt_system.cpp:70-127
     @classmethod
@@ -252,9 +265,9 @@ class LvtSystem:
     def track(self, img1, img2, depth_scale=None):
         """RGB-D: img2 is the depth image -- floats (metres), or a uint16 array of raw sensor units with depth_scale = metres per unit"""
         R = np.zeros((3, 3)); t = np.zeros(3)
-        a = _u8(img1)
+        a = _u8(img1, self._bpp)
         if self._sensor == eSensor_STEREO:
-            b = _u8(img2)
+            b = _u8(img2, self._bpp)
             load_library().lvt_track(self._h, _p(a), _p(b), a.shape[0], a.shape[1], _p(R), _p(t))
         elif isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
@@ -269,7 +282,7 @@ class LvtSystem:
     # lvt_system::track_with_external_corners  -- lvt_system.cpp:209-250
     def track_with_external_corners(self, left, right, corners_left, corners_right):
         R = np.zeros((3, 3)); t = np.zeros(3)
-        a, b = _u8(left), _u8(right)
+        a, b = _u8(left, self._bpp), _u8(right, self._bpp)
         cl = np.ascontiguousarray(corners_left, dtype=np.float64).reshape(-1, 2)
         cr = np.ascontiguousarray(corners_right, dtype=np.float64).reshape(-1, 2)
         load_library().lvt_track_with_external_corners(self._h, _p(a), _p(b), a.shape[0], a.shape[1], _p(cl), len(cl),
@@ -302,9 +315,9 @@ class LvtSystem:
     def track_async(self, img1, img2, depth_scale=None) -> int:
         """lvt_amd_track_async / lvt_amd_track_rgbd_async: HOST images, the call returns once the frame is enqueued (0) or rejected (-1).
         The arrays are used as they are (no copy here): a page-locked one must stay alive and unchanged until the frame is collected."""
-        a = img1 if (isinstance(img1, np.ndarray) and img1.dtype == np.uint8 and img1.flags.c_contiguous) else _u8(img1)
+        a = _u8(img1, self._bpp)   # (a contiguous uint8 array passes through as it is)
         if self._sensor == eSensor_STEREO:
-            b = img2 if (isinstance(img2, np.ndarray) and img2.dtype == np.uint8 and img2.flags.c_contiguous) else _u8(img2)
+            b = _u8(img2, self._bpp)
             return load_library().lvt_amd_track_async(self._h, _p(a), _p(b), a.shape[0], a.shape[1])
         if isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
@@ -336,6 +349,17 @@ class LvtSystem:
         if rc == 0:
             self._rect = (left, right)
         return rc
+
+    def set_pixel_format(self, fmt: int) -> int:
+        """PIX_GRAY8 ... PIX_RGBA8: every frame handed to this system from now on is in that format -- host images (H, W, bpp) uint8, device planes with any
+        base address and any pitch >= W * bpp; the conversion to gray is the first launch of the frame's feature stage.  0: done; -1: refused (last_error())."""
+        rc = load_library().lvt_amd_set_pixel_format(self._h, int(fmt))
+        if rc == 0:
+            self._bpp = PIX_BPP[int(fmt)]
+        return rc
+
+    def pixel_format(self) -> int:
+        return load_library().lvt_amd_get_pixel_format(self._h, 0)
 
     def set_stream(self, hip_stream: int):
         load_library().lvt_amd_set_stream(self._h, C.c_void_p(hip_stream))
@@ -412,7 +436,8 @@ class LvtSystem:
 
     def plane(self, eye=0, what=0):
         """what=0: corner score map (u8), what=1: 9x9 box sums (u16), what=2: the rectified image of a system with rectifiers (u8; an empty array
-        without them); returns (rows, pitch) array"""
+        without them), what=3: the converted gray image of a system with a colour pixel format (u8, before rectification; empty on a gray system);
+        returns (rows, pitch) array"""
         cap = 64 << 20
         buf = np.zeros(cap // 8, dtype=np.uint64)
         pitch = C.c_int(0)
@@ -497,6 +522,13 @@ class LvtBatch:
         if rc == 0:
             self.__dict__.setdefault("_rect", {})[int(seq)] = (left, right)
         return rc
+
+    def set_pixel_format(self, seq: int, fmt: int) -> int:
+        """LvtSystem.set_pixel_format for sequence `seq` of the batch: its planes are colour from then on, the other sequences' are not"""
+        return load_library().lvt_amd_batch_set_pixel_format(self._h, int(seq), int(fmt))
+
+    def pixel_format(self, seq: int) -> int:
+        return load_library().lvt_amd_get_pixel_format(self._h, int(seq))
 
     def params(self, seq: int) -> LvtParameters:
         pod = ParamsPOD()

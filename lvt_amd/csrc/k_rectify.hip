@@ -10,6 +10,7 @@
 //                   single launch is latency-bound like the rest of the single-sequence chain.
 //   k_rectify_fix / k_rectify_frames : the same remap as the first kernel of a tracker's feature stage (raw frames, lvt_amd_set_rectifiers):
 //                   one launch for both eyes of every sequence of a step, from an interleaved fixed-point form of the maps.
+//   k_gray_frames : in front of it, colour frames (lvt_amd_set_pixel_format): one launch converts every colour image of a step to gray.
 #include "lvt_dev.h"
 
 namespace lvt {
@@ -120,6 +121,48 @@ __global__ __launch_bounds__(256) void k_rectify_frames(RectTable tab) {
         if (x < I.dw) {
             const int2 m = M[x];
             packed |= (uint32_t)remap_fixed(I.src, I.sw, I.sh, I.src_pitch, m.x, m.y) << (8 * k);
+        }
+    }
+    *reinterpret_cast<uint32_t *>(I.dst + (size_t)y * I.dst_pitch + x4) = packed;
+}
+
+// ---- colour frames inside the feature stage: one launch converts every colour image of a step to gray (lvt_amd_set_pixel_format) ---------------
+// gray = (R 4899 + G 9617 + B 1868 + 8192) >> 14: cv::cvtColor's 8-bit BGR2GRAY, the weights examples/image_io.h uses.  The table travels BY VALUE like
+// RectTable; blockIdx.y = image, the grid's x extent follows the largest image and a smaller image's surplus workgroups leave at the top.  A thread owns one
+// 32-bit word of the destination (4 pixels; words are numbered row after row over the destination PITCH: the padding columns are written as zero, no lane
+// idles at a row's end).  The source is read byte by byte, three bytes per pixel that exists: it may start at any address and have any pitch, and no load
+// reaches outside [row start, row start + W bpp) of a source row -- what lies behind a row's last pixel may be the caller's next allocation, or nobody's.
+// The format enters through the pixel stride and the byte offsets of R and B only (G is byte 1 of every format; an alpha byte is never loaded).
+constexpr int PIX_GRAY8 = 0, PIX_BGR8 = 1, PIX_RGB8 = 2, PIX_BGRA8 = 3, PIX_RGBA8 = 4;   // LVT_AMD_PIX_* (include/lvt_amd_ext.h)
+__host__ __device__ constexpr int pix_bpp(int fmt) { return fmt == PIX_GRAY8 ? 1 : (fmt >= PIX_BGRA8 ? 4 : 3); }
+struct GrayImg {
+    const uint8_t *src;   // interleaved colour image (any address, any pitch >= w * bpp; read byte-wise)
+    uint8_t *dst;         // gray plane, dst_pitch % 4 == 0
+    int src_pitch, dst_pitch;
+    int w, h, fmt;
+};
+constexpr int GRAY_PACK = 64;   // images per launch; a step with more colour images takes several launches
+struct GrayTable {
+    GrayImg im[GRAY_PACK];
+};
+static_assert(sizeof(GrayTable) < 4096, "k_gray_frames' arguments must stay under 4096 bytes");
+
+__global__ __launch_bounds__(256) void k_gray_frames(GrayTable tab) {
+    const GrayImg &I = tab.im[blockIdx.y];   // (uniform index: the descriptor stays in scalar registers)
+    const int wpr = I.dst_pitch >> 2;        // words per destination row
+    const unsigned word = blockIdx.x * 256u + threadIdx.x;
+    if (word >= (unsigned)(wpr * I.h)) return;   // (a smaller image's surplus workgroups leave here as a whole)
+    const int y = (int)(word / (unsigned)wpr), x4 = (int)(word - (unsigned)y * (unsigned)wpr) * 4;
+    const int bpp = pix_bpp(I.fmt);
+    const int ro = (I.fmt == PIX_BGR8 || I.fmt == PIX_BGRA8) ? 2 : 0, bo = 2 - ro;
+    const uint8_t *P = I.src + (size_t)y * I.src_pitch + (size_t)x4 * bpp;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (x4 + k < I.w) {   // (the last byte read is byte (x4 + k) bpp + 2 < w bpp of the row)
+            const uint8_t *p = P + k * bpp;
+            const uint32_t r = p[ro], g = p[1], b = p[bo];
+            packed |= ((r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14) << (8 * k);
         }
     }
     *reinterpret_cast<uint32_t *>(I.dst + (size_t)y * I.dst_pitch + x4) = packed;

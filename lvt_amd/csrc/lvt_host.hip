@@ -250,6 +250,7 @@ struct Context {
         FrameArgs f{};
         const uint8_t *src[2] = {nullptr, nullptr};
         uint8_t *dst[2] = {nullptr, nullptr};
+        int row_bytes = 0, pitch = 0;  // the pulled planes: bytes per row (n_cols, times bpp on a colour handle) and their pitch
     } pend;
     NextPull next_pull{};   // what this enqueue_frame's k_cells pulls (src[0] == nullptr: nothing)
     bool fuse_pull = true;  // LVT_AMD_FUSED_PULL=0: every frame pulls its own images at the head of its feature stage
@@ -264,6 +265,20 @@ struct Context {
     std::vector<uint8_t *> d_rect;     // [B][NPAR][2] rectified planes, each sequence's own pitch
     int n_rect = 0;                    // sequences with rectifiers
     bool has_rect(int s) const { return n_rect > 0 && rect[2 * (size_t)s] != nullptr; }
+    // COLOUR frames (lvt_amd_set_pixel_format / lvt_amd_batch_set_pixel_format): a sequence with a colour format takes interleaved colour images through every
+    // frame-taking entry point.  As for raw frames the FrameArgs name the colour planes (the caller's, or the context's own pulled ones), and enqueue_frame puts
+    // ONE k_gray_frames launch at the head of the feature stage -- ahead of the rectify block -- that writes the sequence's own gray planes and points the frame at them.
+    std::vector<int> pixfmt;           // [B] LVT_AMD_PIX_* (empty until the first colour set: every sequence gray)
+    std::vector<uint8_t *> d_gray;     // [B][NPAR][2] converted planes, each sequence's own pitch (an RGB-D sequence: eye 0 only)
+    int n_colour = 0;                  // sequences with a colour format
+    bool ring_converted[RING] = {};    // per un-collected / last frame: sequence 0's image went through k_gray_frames (what lvt_amd_get_plane(.., 3, ..) may read back)
+    int fmt_of(int s) const { return n_colour > 0 ? pixfmt[(size_t)s] : PIX_GRAY8; }
+    int bpp_of(int s) const { return pix_bpp(fmt_of(s)); }
+    // host entry points of a colour handle pull the colour bytes -- a byte image n_cols * bpp wide -- into these planes (allocated when first needed, sized for
+    // 4 bytes per pixel): per feature buffer for the synchronous calls, per RING slot for the asynchronous ones
+    uint8_t *d_col[NPAR][2] = {};
+    uint8_t *d_col_ring[RING][2] = {};
+    int colour_pitch() const { return (prm.W * bpp_of(0) + 63) / 64 * 64; }
     int pitch = 0;
     long enq = 0, done = 0;    // frames enqueued / collected
     long delivered = 0;        // frames whose record delivery has been enqueued (k_triangulate, the next frame's k_gate_late, or k_deliver)
@@ -799,7 +814,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
 // ---- the per-frame launch chain -------------------------------------------------------------------
 static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
-    "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "",
+    "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
     "", ""};
 
@@ -907,6 +922,42 @@ static void enqueue_frame(Context *c) {
     hipStream_t sf = c->stream_f, st = c->stream;
     for (int i = 0; i < Context::PROF_SLOTS; i++) c->ev_used[i] = false;
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
+    // ---- colour frames: every colour image of the step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in one launch, AHEAD of the
+    //      rectify block (convert, then remap: the reference's order).  The gray planes (parity `par`) were read last by the feature stage of frame enq - NPAR
+    //      (k_rectify_frames or k_score, k_gather, k_brief_img: all on this stream, all enqueued before), and the source was written by a pull on this stream
+    //      or belongs to the caller: stream order alone covers the hand-over, no gate.
+    c->ring_converted[slot] = false;
+    if (c->n_colour) {
+        FrameArgs *fw = &frame_args(c, slot);
+        GrayTable tab;
+        std::memset(&tab, 0, sizeof(tab));
+        int n = 0, words = 0;
+        bool timed = false;
+        auto launch = [&]() {
+            const dim3 grid((words + 255) / 256, n);
+            if (!timed) LAUNCH(14, sf, k_gray_frames, grid, dim3(256), 0, tab);
+            else hipLaunchKernelGGL(k_gray_frames, grid, dim3(256), 0, sf, tab);
+            timed = true, n = 0, words = 0;
+        };
+        for (int s = 0; s < Bz; s++) {
+            if (c->fmt_of(s) == PIX_GRAY8 || fw[s].absent) continue;
+            const Params &q = c->seq_prm(s);
+            const int dpitch = c->h_seqs[s].plane_pitch, eyes = (c->sensor == 2) ? 1 : 2;
+            if (n + eyes > GRAY_PACK) launch();
+            for (int e = 0; e < eyes; e++) {
+                GrayImg &I = tab.im[n++];
+                I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
+                I.dst = c->d_gray[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
+                I.w = q.W, I.h = q.H, I.fmt = c->fmt_of(s);
+                words = std::max(words, dpitch / 4 * q.H);
+                fw[s].img[e] = I.dst;
+            }
+            if (eyes == 1) fw[s].img[1] = fw[s].img[0];
+            fw[s].img_pitch = dpitch;
+            if (s == 0) c->ring_converted[slot] = true;
+        }
+        if (n) launch();
+    }
     // ---- raw frames: both eyes of every sequence that has rectifiers and a frame in this step, in one launch.  The rectified planes (parity `par`) were
     //      read last by the feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order
     //      alone covers the hand-over, and the launch needs no gate: it goes out ahead of the buffer gate.
@@ -974,7 +1025,7 @@ static void enqueue_frame(Context *c) {
         {
             // detection pass 0 (the <200-corner retry pass runs inside k_gather: it is almost never taken)
             // (a single sequence: + the workgroups that pull the next asynchronous host frame, one 16-byte vector per thread)
-            const int pull_wgs = (B == 1 && c->next_pull.src[0]) ? std::min(64, (int)(((size_t)p.W * p.H / 16 + 1023) / 1024)) : 0;
+            const int pull_wgs = (B == 1 && c->next_pull.src[0]) ? std::min(64, (int)(((size_t)c->next_pull.W * c->next_pull.H / 16 + 1023) / 1024)) : 0;  // (W: bytes per row, n_cols * bpp on a colour handle)
             // a single sequence's tall cells run as cell_split co-operating workgroups (cells_work_split); grid: helpers, main workgroups, pull, padded to 8
             const int ns = (B == 1 && !p.big_cell_strips) ? c->cell_split : 0;
             const int gx = (ns >= 2) ? ((((p.n_cells + 7) & ~7) * ns + pull_wgs + 7) & ~7) : p.n_cells + pull_wgs;
@@ -1162,7 +1213,7 @@ static void flush_pending(Context *c, const NextPull *np = nullptr) {
     if (!c->pend.valid) return;
     Context::PendingFrame &q = c->pend;
     q.valid = false;
-    if (!q.pulled) hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, q.src[0], q.src[1], q.dst[0], q.dst[1], c->prm.W, c->prm.H, c->pitch);
+    if (!q.pulled) hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, q.src[0], q.src[1], q.dst[0], q.dst[1], q.row_bytes, c->prm.H, q.pitch);
     frame_args(c, next_slot(c)) = q.f;
     if (np) c->next_pull = *np, c->fused_pulls++;
     enqueue_frame(c);
@@ -1238,8 +1289,11 @@ static void track_sync(Context *c, double R[3][3], double t[3]) {
 
 static bool size_ok(Context *c, int rows, int cols) { return rows == c->prm.H && cols == c->prm.W; }
 // pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
-// byte-wise by k_rectify_frames: any pitch that holds a row
-static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) { return c->has_rect(s) ? pitch >= cols : (pitch & 15) == 0; }
+// byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes)
+static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) {
+    if (c->fmt_of(s) != PIX_GRAY8) return (long long)pitch >= (long long)cols * c->bpp_of(s);
+    return c->has_rect(s) ? pitch >= cols : (pitch & 15) == 0;
+}
 
 template <typename T>
 static void d2h(Context *c, T *dst, const T *src, size_t n) {
@@ -1429,13 +1483,22 @@ static const uint8_t *device_view(const void *p, size_t align) {
     (void)hipGetLastError();  // (an ordinary malloc'ed pointer is "invalid value" to the query: not an error of this call)
     return nullptr;
 }
-// first use of a staging buffer: [image | image] or [image | depth f32] for planes of n pixels
-static void stage_reserve(Context *c, HostStage &st, size_t n, bool rgbd) {
+// first use of a staging buffer: [image | image] or [image | depth f32] for images of img_bytes (n_rows * n_cols * bpp) and, RGB-D, depth planes of depth_px pixels
+// (a change of the pixel format releases the buffers: stage_release)
+static void stage_reserve(Context *c, HostStage &st, size_t img_bytes, size_t depth_px) {
     if (st.h) return;
-    st.second = (n + 15) & ~(size_t)15;
-    const size_t second_bytes = rgbd ? ((sizeof(float) * n + 15) & ~(size_t)15) : st.second;
+    st.second = (img_bytes + 15) & ~(size_t)15;
+    const size_t second_bytes = depth_px ? ((sizeof(float) * depth_px + 15) & ~(size_t)15) : st.second;
     HIPCHK(c, hipHostMalloc((void **)&st.h, st.second + second_bytes, hipHostMallocDefault));
     HIPCHK(c, hipHostGetDevicePointer((void **)&st.dev, st.h, 0));
+}
+static void stage_release(Context *c) {  // (no frame in flight: nothing reads them)
+    for (HostStage *st : {&c->stage[0], &c->stage_ring[0]})
+        for (int i = 0, n = (st == &c->stage[0]) ? NPAR : RING; i < n; i++)
+            if (st[i].h) {
+                (void)hipHostFree(st[i].h);
+                st[i] = HostStage{};
+            }
 }
 // a host plane as the device reads it: its view (device_view) when it is page-locked, otherwise its copy at offset `off` of the staging buffer; counted either way
 static const uint8_t *host_plane(Context *c, const uint8_t *view, const void *src, size_t bytes, const HostStage &st, size_t off) {
@@ -1639,6 +1702,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     DeviceGuard guard(c);
     if (slot < 0 || slot >= Context::PROF_SLOTS || !kProfNames[slot][0]) return 0;
     if (slot == 4 && c->n_rect == 0 && c->prof_calls[4] == 0) return 0;  // (a handle without rectifiers has no such launch)
+    if (slot == 14 && c->n_colour == 0 && c->prof_calls[14] == 0) return 0;  // (... and one without a colour sequence no k_gray_frames)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1752,7 +1816,7 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
                 std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->has_rect(s) ? "at least the width" : "a multiple of 16");
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : c->has_rect(s) ? "at least the width" : "a multiple of 16");
                 return refuse(h, who, buf);
             }
         }
@@ -1863,6 +1927,11 @@ LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *
     track_device(h, d_left, d_right, n_rows, n_cols, pitch_bytes, true, R, t);
 }
 
+// the context's own colour planes (Context::d_col / d_col_ring), allocated when first needed and sized for 4 bytes per pixel: the format may change later
+static void colour_planes(Context *c, uint8_t *(&d)[2], int eyes) {
+    for (int e = 0; e < eyes; e++)
+        if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)((c->prm.W * 4 + 63) / 64 * 64) * c->prm.H + 64);
+}
 // (dfmt / dscale: element format of an RGB-D frame's depth plane `second` and metres per raw unit of a 16-bit one; cl / cr: external corner lists, nullptr: none)
 static void upload_and_track(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols,
                              const float *cl, int ncl, const float *cr, int ncr, double R[3][3], double t[3], int dfmt = DEPTH_F32, float dscale = 0.f) {
@@ -1876,9 +1945,14 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     flush_pending(c);  // a held lvt_amd_track_async frame goes out FIRST: it takes a frame number, and this frame's buffers (images, corner lists) are chosen by number
     const int par = (int)(c->enq % NPAR);
     hipStream_t sf = c->stream_f;
-    const size_t nbytes = (size_t)n_rows * n_cols;
+    // a COLOUR handle: the image is a byte image n_cols * bpp wide; it is pulled into the context's colour planes and enqueue_frame converts it from there
+    const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
+    const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp;
+    if (bpp > 1) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
+    uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : c->d_img[par];
+    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
     const HostStage &stg = c->stage[par];
-    stage_reserve(c, c->stage[par], nbytes, rgbd);
+    stage_reserve(c, c->stage[par], nbytes, rgbd ? npix : 0);
     // (this call only returns after the frame has been tracked, so a page-locked buffer read in place outlives every read)
     const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
     // The pulls are launched BEFORE the previous frame is collected: this frame's image planes (parity `par`) and staging buffer were last used NPAR
@@ -1886,12 +1960,12 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     // Two pageable images: the left one is pulled while the CPU still copies the right one.
     const bool split = !rgbd && !v0 && !v1;
     const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0), *s1 = v1;  // (an RGB-D frame's second plane goes later: before_gather)
-    if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s0, s0, c->d_img[par][0], c->d_img[par][0], n_cols, n_rows, c->pitch);
+    if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s0, s0, dimg[0], dimg[0], row_bytes, n_rows, ipitch);
     if (!rgbd) s1 = host_plane(c, v1, second, nbytes, stg, stg.second);
-    if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s1, s1, c->d_img[par][1], c->d_img[par][1], n_cols, n_rows, c->pitch);
-    else hipLaunchKernelGGL(k_stage_in, dim3(128, rgbd ? 1 : 2), dim3(256), 0, sf, s0, s1, c->d_img[par][0], c->d_img[par][1], n_cols, n_rows, c->pitch);
+    if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s1, s1, dimg[1], dimg[1], row_bytes, n_rows, ipitch);
+    else hipLaunchKernelGGL(k_stage_in, dim3(128, rgbd ? 1 : 2), dim3(256), 0, sf, s0, s1, dimg[0], dimg[1], row_bytes, n_rows, ipitch);
     drain(c);
-    FrameArgs f = stereo_args(c->d_img[par][0], c->d_img[par][1], c->pitch);
+    FrameArgs f = stereo_args(dimg[0], dimg[(bpp > 1 && rgbd) ? 0 : 1], ipitch);  // (an RGB-D handle has one colour plane)
     if (rgbd) {
         // The depth plane (1.2 MB: ~60 us of CPU copy into the staging buffer when the caller's buffer is pageable, ~45 us of PCIe pull)
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
@@ -1899,10 +1973,10 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
         // the feature stream waits for the pull in front of k_gather.  (A 16-bit plane: half those bytes, both ways; it stays 16-bit in d_depth.)
         f = with_depth(f, c->d_depth[par], n_cols * (int)desz, dfmt, dscale);
         // (runs inside enqueue_frame: everything it needs travels by value, nothing is read that enqueue_frame advances)
-        c->before_gather = [c, v1, second, nbytes, par, sf, dfmt, desz]() {
-            const uint8_t *src = host_plane(c, v1, second, desz * nbytes, c->stage[par], c->stage[par].second);
+        c->before_gather = [c, v1, second, npix, par, sf, dfmt, desz]() {
+            const uint8_t *src = host_plane(c, v1, second, desz * npix, c->stage[par], c->stage[par].second);
             hipStream_t sd = c->events_only ? sf : c->stream_e;
-            launch_stage_copy(sd, src, c->d_depth[par], nbytes, dfmt);
+            launch_stage_copy(sd, src, c->d_depth[par], npix, dfmt);
             if (sd != sf) {
                 (void)hipEventRecord(c->ev_depth, sd);
                 c->depth_wait = true;
@@ -1937,38 +2011,43 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     const int held = c->pend.valid ? 1 : 0;  // (the held frame owns slot enq % RING)
     while (c->enq + held - c->done >= RING - 1) collect_oldest(c);
     const int slot = (int)((c->enq + held) % RING);
-    const size_t nbytes = (size_t)n_rows * n_cols, plane = (size_t)c->pitch * c->prm.H;
+    // (a COLOUR handle: byte images n_cols * bpp wide into the context's colour planes, as in upload_and_track; the fused pull carries them like gray ones)
+    const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
+    const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp, plane = (size_t)c->pitch * c->prm.H;
+    if (bpp > 1) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
+    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
     if (!c->d_img_ring[0][0]) {  // first asynchronous host-buffer call
         for (int r = 0; r < RING; r++) {
             for (int e = 0; e < (rgbd ? 1 : 2); e++) c->d_img_ring[r][e] = c->dalloc<uint8_t>(plane + 64);
-            if (rgbd) c->d_depth_ring[r] = c->dalloc<float>(nbytes + 4);
+            if (rgbd) c->d_depth_ring[r] = c->dalloc<float>(npix + 4);
         }
     }
     const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
     HostStage &stg = c->stage_ring[slot];
-    if (!v0 || !v1) stage_reserve(c, stg, nbytes, rgbd);
+    if (!v0 || !v1) stage_reserve(c, stg, nbytes, rgbd ? npix : 0);
     hipStream_t sp = c->stream_f;
-    uint8_t *d0 = c->d_img_ring[slot][0], *d1 = c->d_img_ring[slot][1];
+    uint8_t *d0 = (bpp > 1) ? c->d_col_ring[slot][0] : c->d_img_ring[slot][0], *d1 = (bpp > 1) ? c->d_col_ring[slot][1] : c->d_img_ring[slot][1];
     const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0);
     if (!rgbd) {
         const uint8_t *s1 = host_plane(c, v1, second, nbytes, stg, stg.second);
         // the frame held so far goes out now, and its k_cells launch pulls THIS frame's images beside its cells
         const bool carried = c->pend.valid && c->fuse_pull;
         if (c->pend.valid) {
-            const NextPull np{{s0, s1}, {d0, d1}, n_cols, n_rows, c->pitch};
+            const NextPull np{{s0, s1}, {d0, d1}, row_bytes, n_rows, ipitch};
             flush_pending(c, carried ? &np : nullptr);
         }
         Context::PendingFrame &q = c->pend;
         q.valid = true, q.pulled = carried;
         q.src[0] = s0, q.src[1] = s1, q.dst[0] = d0, q.dst[1] = d1;
-        q.f = stereo_args(d0, d1, c->pitch);
+        q.row_bytes = row_bytes, q.pitch = ipitch;
+        q.f = stereo_args(d0, d1, ipitch);
         c->async_frames++;
         if (!c->fuse_pull) flush_pending(c);
         return 0;
     }
-    hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, n_cols, n_rows, c->pitch);
-    launch_stage_copy(sp, host_plane(c, v1, second, desz * nbytes, stg, stg.second), c->d_depth_ring[slot], nbytes, dfmt);
-    frame_args(c, slot) = rgbd_args(d0, c->pitch, c->d_depth_ring[slot], n_cols * (int)desz, dfmt, dscale);
+    hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, row_bytes, n_rows, ipitch);
+    launch_stage_copy(sp, host_plane(c, v1, second, desz * npix, stg, stg.second), c->d_depth_ring[slot], npix, dfmt);
+    frame_args(c, slot) = rgbd_args(d0, ipitch, c->d_depth_ring[slot], n_cols * (int)desz, dfmt, dscale);
     c->async_frames++;
     enqueue_frame(c);
     return 0;
@@ -2049,7 +2128,7 @@ static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale)
     return true;
 }
 // one sequence's device planes against its parameters; "" when they pass
-static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols) {
+static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp) {
     const int esz = (fmt == DEPTH_U16) ? 2 : 4;
     char buf[240];
     if (!d_gray || !d_depth) return "NULL gray or depth plane";
@@ -2057,7 +2136,12 @@ static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gr
         std::snprintf(buf, sizeof(buf), "image size %d x %d, expected %d x %d", n_cols, n_rows, q.W, q.H);
         return buf;
     }
-    if (((uintptr_t)d_gray & 15) || (gray_pitch & 15) || gray_pitch < n_cols) {
+    if (bpp > 1) {  // a colour sequence: k_gray_frames reads the plane byte-wise -- any address, any pitch that holds a row
+        if ((long long)gray_pitch < (long long)n_cols * bpp) {
+            std::snprintf(buf, sizeof(buf), "colour plane: pitch (%d) must hold a row of %d bytes", gray_pitch, n_cols * bpp);
+            return buf;
+        }
+    } else if (((uintptr_t)d_gray & 15) || (gray_pitch & 15) || gray_pitch < n_cols) {
         std::snprintf(buf, sizeof(buf), "gray plane: pointer and pitch (%d) must be multiples of 16, pitch >= %d", gray_pitch, n_cols);
         return buf;
     }
@@ -2078,7 +2162,7 @@ static int track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_by
     DeviceGuard guard(c);
     try {
         if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
-        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols);
+        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0));
         if (!why.empty()) return rgbd_refuse(h, who, why);
         if (sync) {
             drain(c);
@@ -2159,7 +2243,7 @@ LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *cons
         for (int s = 0; s < c->B; s++) {
             if (!d_gray[s]) continue;
             present++;
-            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s]);
+            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s));
             if (!why.empty()) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + why);
         }
         if (!present) return rgbd_refuse(h, who, "no sequence has a frame in this step");
@@ -2434,6 +2518,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             if (!c->has_rect(0) || c->done == 0) return 0;
             if ((size_t)cap_bytes < n) return -1;
             HIPCHK(c, hipMemcpy(dst, c->d_rect[(size_t)c->last_par * 2 + (eye ? 1 : 0)], n, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->pitch;
+            return (int)n;
+        }
+        if (what == 3) {  // the converted gray image of the last (colour) frame, before rectification
+            if (c->fmt_of(0) == PIX_GRAY8 || c->done == 0 || !c->ring_converted[c->last_slot]) return 0;  // (the last frame must have been a colour frame)
+            if ((size_t)cap_bytes < n) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_gray[(size_t)c->last_par * 2 + ((eye && c->sensor == 1) ? 1 : 0)], n, hipMemcpyDeviceToHost));
             if (pitch_out) *pitch_out = c->pitch;
             return (int)n;
         }
@@ -2744,6 +2835,62 @@ static int set_rectifiers_any(lvt_handle h, int seq, bool batch_call, lvt_amd_re
 LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right) { return set_rectifiers_any(h, 0, false, left, right); }
 LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right) {
     return set_rectifiers_any(h, seq, true, left, right);
+}
+
+// ---- colour frames: a pixel format per handle / per sequence of a batch (Context::pixfmt) ----------------------------------------------------
+// Everything is checked before anything changes: 0 = set, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
+static int pix_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_pixel_format", why + " (nothing was changed)"); }
+static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) {
+    Context *c = frame_context(h, "lvt_amd_set_pixel_format", 0, batch_call,
+                               {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                "a batch handle takes its pixel formats per sequence through lvt_amd_batch_set_pixel_format (nothing was changed)"});
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (batch_call && c->B == 1 && !c->mixed) return pix_refuse(h, "lvt_amd_batch_set_pixel_format on a handle that is not a batch (use lvt_amd_set_pixel_format)");
+        if (seq < 0 || seq >= c->B) return pix_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
+        if (format < PIX_GRAY8 || format > PIX_RGBA8) return pix_refuse(h, "unknown pixel format " + std::to_string(format));
+        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
+        if (c->done < c->enq || c->pend.valid) return pix_refuse(h, "frames in flight: set the format before the first frame or after every frame has been collected");
+        if (format == c->fmt_of(seq)) return 0;
+        if (c->pixfmt.empty()) {
+            c->pixfmt.assign((size_t)c->B, PIX_GRAY8);
+            c->d_gray.assign((size_t)c->B * NPAR * 2, nullptr);
+        }
+        if (format != PIX_GRAY8) {
+            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
+            for (int par = 0; par < NPAR; par++)
+                for (int e = 0; e < (c->sensor == 2 ? 1 : 2); e++) {
+                    uint8_t *&d = c->d_gray[((size_t)seq * NPAR + par) * 2 + e];
+                    if (!d) d = c->dalloc<uint8_t>(plane + 64);
+                }
+        }
+        if (seq == 0 && pix_bpp(format) != c->bpp_of(0)) stage_release(c);  // (the pinned staging of the host entry points is sized by bpp: reserved again at the next frame)
+        c->pixfmt[(size_t)seq] = format;
+        c->n_colour = 0;
+        for (int s = 0; s < c->B; s++) c->n_colour += c->pixfmt[(size_t)s] != PIX_GRAY8;
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+// (an lvt_create handle: as for rectifiers, decided under its record's lock, and a successful set is a use)
+static int set_pixel_format_any(lvt_handle h, int seq, bool batch_call, int format) {
+    if (!is_auto(h)) return set_pixel_format(h, seq, batch_call, format);
+    AutoHandle *A = static_cast<AutoHandle *>(h);
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = set_pixel_format(A->impl, seq, batch_call, format);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format) { return set_pixel_format_any(h, 0, false, format); }
+LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format) { return set_pixel_format_any(h, seq, true, format); }
+LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? PIX_GRAY8 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
 }
 
 // ---- odometry accumulator (lvt_ros.cpp:215-311 without ROS) -----------------------------------------------
