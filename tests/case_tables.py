@@ -1,6 +1,7 @@
 """The inputs of the edge-case tests of k_pnp and k_triangulate, in one place: the GPU tests (test_gpu_primitives.py, test_gpu_parity.py,
 test_gpu_mixed_batch.py) drive the HIP path with them, the CPU tier (test_case_tables.py) asserts with the oracle alone that they still take
-the branches they were chosen for.  Nothing here needs a GPU."""
+the branches they were chosen for.  Further down: the planted scenes of the triangulation gates, the map capacity, the resolver chains and the RGB-D
+depth and lens edges (test_gpu_rgbd_edges.py), held the same way.  Nothing here needs a GPU."""
 import functools
 
 import numpy as np
@@ -489,3 +490,127 @@ def row_lists(left_xy, left_desc, right_xy, right_desc, img_rows):
         d = _hamming(left_desc[i:i + 1], right_desc[idx])[0] if len(idx) else []
         lists.append(sorted(zip((int(k) for k in d), (int(k) for k in idx))))
     return lists
+
+
+# ---- RGB-D at its depth and lens edges ---------------------------------------------------------------------------------------------------------------
+# What only an RGB-D frame reaches: the depth lookup and the near / far filter of k_gather, its 16-bit conversion, undistort_point with the "left the
+# hash grid -> drop" rule, the fp32 back-projection of k_triangulate.  All cases are the synthetic TUM world of seed 1 at 640 x 480.
+RGBD_EDGE_SEED = 1
+RGBD_NEAR, RGBD_FAR = 0.5, 5.0
+RGBD_GATES = {"near_plane_distance": RGBD_NEAR, "far_plane_distance": RGBD_FAR}
+RGBD_PLANT_FRAMES = 4           # frame 0 with the planted plane, frames 1 - 3 with the world's own depth
+# 16-bit sets: (depth_scale, raw classes).  Each decides one gate by the rounding of the fp32 product alone (checked over all 65536 raws: the fp32 and
+# the float64 product disagree about the gates at raw 2500 of set A and at raw 5000 of set B, nowhere else):
+#   A  raw 2500: fp32 product exactly 0.5 = near, kept; the exact product of the two fp32 operands is 0.49999998..., below near
+#   B  raw 5000: fp32 product exactly 5.0 = far, kept; the exact product is 5.0000002..., above far (and raw / (1f / scale) = 5.0000005)
+#      raw 500: fp32 product exactly 0.5 = near; the exact product lies above it, so the gate keeps it either way -- what raw 500 pins is the value:
+#      raw / (1f / scale) gives 0.50000006, another map point
+RGBD16_SETS = {
+    "A": (np.float32(1) / np.float32(5000), (0, 1, 2499, 2500, 2501, 12345, 24999, 25000, 25001, 65535)),
+    "B": (np.float32(0.001), (0, 499, 500, 501, 4999, 5000, 5001, 65535)),
+}
+RGBD16_FRAMES = 3
+# barrel distortion (k1 < 0: the sign of RealSense / Kinect-class colour cameras; these are the EuRoC cam0 coefficients).  Measured with the oracle on
+# seed 1, frames 0 - 7 (test_case_tables.py asserts the conditions): TRACKING throughout, 683 - 798 matches from frame 1, 7 - 11 features kept outside
+# the image per frame (x up to 649.7), 10 - 22 corners dropped for leaving the hash grid, and 3 - 7 find_matches matches per frame from frame 1 (36 in
+# all) that land on a feature outside the image -- so seed 1 serves, no other seed was needed
+RGBD_BARREL = dict(k1=-0.28340811, k2=0.07395907, p1=0.00019359, p2=1.76187114e-05, k3=0.0)
+RGBD_BARREL_FRAMES = 8
+RGBD_RETRY = {"agast_threshold": 150}       # 159 - 181 corners per frame: below the 200 that send the image through the detector again
+RGBD_RETRY_FRAMES = 4
+# scripts of frames without valid depth: name -> (depth kinds per frame, the oracle's status per frame).  "world": the world's depth; "nan": an
+# all-NaN fp32 plane; "zero": an all-zero fp32 plane; "zero16": a uint16 plane of raw 0 (the oracle gets fp32 zeros)
+RGBD_NODEPTH = {
+    "nan_first": (("nan", "world", "world"), (2, 3, 3)),
+    "zero_mid": (("world", "world", "zero", "world"), (2, 2, 3, 3)),
+    "zero16_mid": (("world", "world", "zero16", "world"), (2, 2, 3, 3)),
+}
+
+
+def rgbd_depth_classes(near=RGBD_NEAR, far=RGBD_FAR):
+    """the 15 fp32 depth values planted at the corners: what no rendered depth plane holds.  Kept by `near <= d <= far` in fp32: classes 8 - 12."""
+    n, f, lo, hi = np.float32(near), np.float32(far), np.float32(-np.inf), np.float32(np.inf)
+    return np.array([np.nan, np.inf, -np.inf, -1.0, -0.0, 0.0, 1e-45, np.nextafter(n, lo), n, np.nextafter(n, hi), 1.5,
+                     np.nextafter(f, lo), f, np.nextafter(f, hi), 3.4e38], dtype=np.float32)
+
+
+def rgbd_world(overrides=None):
+    from parity_util import make_case
+    world, prm, sensor = make_case("tum", RGBD_EDGE_SEED, 1.0, overrides)
+    assert sensor == 2 and (world.W, world.H) == (640, 480)
+    return world, prm
+
+
+@functools.lru_cache(maxsize=None)
+def rgbd_planted(kind):
+    """kind "f32": frame 0 of the world under RGBD_GATES with class i % 15 of rgbd_depth_classes() written into the depth plane at corner i of
+    O.compute_features(gray) (list order; the corners are integer and distinct); kind "A" / "B": a uint16 plane (the world's depth in raw units) with
+    raw class i % len(raws) of that 16-bit set.  Returns a dict: prm, scale (None for f32), frames = [(gray, depth plane as handed in, its fp32 value
+    as the oracle gets it)] -- the planted frame, then the world's own frames --, xy / desc = the corner list, val = the fp32 depth at every corner,
+    keep = near <= val <= far in numpy float32."""
+    from oracle import pyoracle as O
+    world, prm = rgbd_world(RGBD_GATES)
+    n_frames = RGBD_PLANT_FRAMES if kind == "f32" else RGBD16_FRAMES
+    rendered = [world.render_rgbd(i) for i in range(n_frames)]
+    gray = np.ascontiguousarray(rendered[0][0])
+    xy, _, desc, retry = O.compute_features(gray, prm)
+    assert retry == 0 and np.array_equal(xy, np.rint(xy)) and len(np.unique(xy, axis=0)) == len(xy)
+    ix, iy = xy[:, 0].astype(np.int64), xy[:, 1].astype(np.int64)
+    if kind == "f32":
+        scale = None
+        cls = rgbd_depth_classes()
+        val = cls[np.arange(len(xy)) % len(cls)]
+        plane = np.array(rendered[0][1], dtype=np.float32)
+        plane[iy, ix] = val
+        frames = [(gray, plane, plane)] + [(np.ascontiguousarray(g), np.ascontiguousarray(d, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32))
+                                           for g, d in rendered[1:]]
+    else:
+        scale, raws = RGBD16_SETS[kind]
+        raws = np.array(raws, dtype=np.uint16)
+
+        def to_raw(d):
+            return np.clip(np.rint(d.astype(np.float64) / np.float64(scale)), 0, 65535).astype(np.uint16)
+        u = to_raw(rendered[0][1])
+        u[iy, ix] = raws[np.arange(len(xy)) % len(raws)]
+        us = [u] + [to_raw(d) for _, d in rendered[1:]]
+        frames = []
+        for (g, _), uu in zip(rendered, us):
+            f = uu.astype(np.float32) * scale           # ONE rounded fp32 multiply
+            assert f.dtype == np.float32
+            frames.append((np.ascontiguousarray(g), uu, f))
+        val = frames[0][2][iy, ix]
+    with np.errstate(invalid="ignore"):
+        keep = (val >= np.float32(prm.near_plane_distance)) & (val <= np.float32(prm.far_plane_distance))
+    return dict(prm=prm, scale=scale, frames=frames, xy=xy, desc=desc, val=val, keep=keep)
+
+
+def rgbd_backproject(prm, uv, z):
+    """k_triangulate's RGB-D branch (lvt_local_map.cpp:231-256) under the identity pose, restated in numpy float32 and widened: x = (u - cx) z (1f / fx),
+    y = (v - cy) z (1f / fy), z.  The fp64 rotation of the first frame multiplies by exact ones and adds exact zeros."""
+    f = np.float32
+    u, v, z = uv[:, 0].astype(f), uv[:, 1].astype(f), z.astype(f)
+    x = (u - f(prm.cx)) * z * (f(1) / f(prm.fx))
+    y = (v - f(prm.cy)) * z * (f(1) / f(prm.fy))
+    assert x.dtype == np.float32 and y.dtype == np.float32
+    return np.column_stack([x, y, z]).astype(np.float64)
+
+
+def rgbd_outside(xy, W=640, H=480):
+    """features kept although they left the image: the hash grid reaches to 25 ceil(W / 25) x 25 ceil(H / 25)"""
+    return (xy[:, 0] >= W) | (xy[:, 1] >= H) | (xy[:, 0] < 0) | (xy[:, 1] < 0)
+
+
+def rgbd_nodepth_script(name):
+    """(prm, [(gray, depth plane as handed in, its fp32 value), ...], the oracle's status per frame) of one RGBD_NODEPTH script"""
+    world, prm = rgbd_world()
+    kinds, status = RGBD_NODEPTH[name]
+    frames = []
+    for i, kind in enumerate(kinds):
+        g, d = world.render_rgbd(i)
+        g, d = np.ascontiguousarray(g), np.ascontiguousarray(d, dtype=np.float32)
+        if kind == "nan":
+            d = np.full_like(d, np.nan)
+        elif kind in ("zero", "zero16"):
+            d = np.zeros_like(d)
+        frames.append((g, np.zeros(d.shape, np.uint16) if kind == "zero16" else d, d))
+    return prm, frames, status

@@ -5,6 +5,8 @@ import pytest
 
 import lvt_amd
 from case_tables import (MAP_MAX, MAPCAP_RECIPES, STAGED_MAX, mapcap_case, mapcap_track)
+from case_tables import (RGBD16_SETS, RGBD_BARREL, RGBD_BARREL_FRAMES, RGBD_FAR, RGBD_NEAR, RGBD_NODEPTH, RGBD_PLANT_FRAMES, RGBD_RETRY, RGBD_RETRY_FRAMES,
+                         rgbd_backproject, rgbd_depth_classes, rgbd_nodepth_script, rgbd_outside, rgbd_planted, rgbd_world)
 from case_tables import (DENSE_MIN_UNSTAGED_FRAMES, KITTI_DENSE_UNSTAGED, PNP_EDGE_COUNTS, PNP_HARD, PNP_HARD_UNSTAGED, PNP_INTRINSICS, PNP_STAGE_MAX,
                          STAIRCASE, pnp_edge_case, pnp_hard_case, pnp_prior_cases, staircase, staircase_band_counts, staircase_expected, trace_noise)
 
@@ -405,3 +407,153 @@ def test_staged_chain_conditions(oracle_lib):
     assert a == b and it == 96 >= 16
     assert sum(d >= 0 for d in a) == c[2]["n_staged_promoted"] and sum(d < 0 for d in a) == c[2]["n_staged_erased"]
     assert a[:95] == info["chain"].tolist() and [d >= 0 for d in a[95:]] == [False] * STAGED_CHAIN_DROPPED + [True] * (5 - STAGED_CHAIN_DROPPED)
+
+
+# ---- RGB-D at its depth and lens edges (test_gpu_rgbd_edges.py) ---------------------------------------------------------------------------------------
+def _oracle_frame0(oracle_lib, case):
+    orc = oracle_lib.Oracle(case["prm"], 2)
+    g, _, f = case["frames"][0]
+    orc.track_rgbd(g, f)
+    return orc
+
+
+def _assert_planted(oracle_lib, case, n_corners, n_kept):
+    """the oracle keeps exactly the corners numpy float32 keeps, in list order, with their compute_features descriptors, and its map after frame 0 EQUALS
+    the fp32 restatement of the back-projection"""
+    assert len(case["xy"]) == n_corners and int(case["keep"].sum()) == n_kept
+    orc = _oracle_frame0(oracle_lib, case)
+    xy, _, desc = orc.features(0)
+    k = case["keep"]
+    assert orc.status == 2 and orc.counts()["n_left"] == n_kept and orc.counts()["n_right"] == 0
+    assert np.array_equal(xy, case["xy"][k]) and np.array_equal(desc, case["desc"][k])
+    mx, _, _, md = orc.map()
+    assert np.array_equal(mx, rgbd_backproject(case["prm"], case["xy"][k], case["val"][k])) and np.array_equal(md, case["desc"][k])
+
+
+def test_rgbd_planted_depth_classes(oracle_lib):
+    """804 integer corners at distinct pixels, 15 classes of fp32 depth: NaN, the infinities, negatives, both zeros, a denormal and 3.4e38 are dropped,
+    the two planes themselves are kept, one ulp outside them is dropped"""
+    cls = rgbd_depth_classes()
+    near, far = np.float32(RGBD_NEAR), np.float32(RGBD_FAR)
+    assert cls.dtype == np.float32 and len(cls) == 15
+    assert np.isnan(cls[0]) and cls[1] == np.inf and cls[2] == -np.inf and cls[3] == -1 and np.signbit(cls[4]) and cls[4] == 0 and not np.signbit(cls[5])
+    assert 0 < cls[6] < np.finfo(np.float32).tiny and cls[14] > 3e38 and np.isfinite(cls[14])
+    assert cls[7] < near == cls[8] < cls[9] and cls[11] < far == cls[12] < cls[13]
+    assert np.nextafter(cls[7], far) == near and np.nextafter(cls[9], -far) == near and np.nextafter(cls[11], 2 * far) == far and np.nextafter(cls[13], near) == far
+    case = rgbd_planted("f32")
+    assert case["prm"].k1 == 0 and case["prm"].near_plane_distance == near and case["prm"].far_plane_distance == far
+    plane = case["frames"][0][1]
+    assert plane.dtype == np.float32 and np.array_equal(plane[case["xy"][:, 1].astype(int), case["xy"][:, 0].astype(int)], case["val"], equal_nan=True)
+    which = np.arange(len(case["xy"])) % 15
+    assert np.array_equal(case["keep"], (which >= 8) & (which <= 12)) and np.bincount(which, minlength=15).min() >= 53
+    _assert_planted(oracle_lib, case, 804, 266)
+    # the NaN class is what tells `d >= near && d <= far` from !(d < near) && !(d > far): the second form keeps every NaN corner
+    with np.errstate(invalid="ignore"):
+        assert int((~(case["val"] < near) & ~(case["val"] > far)).sum()) == 266 + int((which == 0).sum())
+    # frames 1 - 3 (the world's own depth) go on TRACKING on the 266-point map
+    orc = oracle_lib.Oracle(case["prm"], 2)
+    for i, (g, _, f) in enumerate(case["frames"]):
+        orc.track_rgbd(g, f)
+        assert orc.status == 2 and (i == 0 or orc.counts()["n_matches"] > 150), (i, orc.counts())
+    assert len(case["frames"]) == RGBD_PLANT_FRAMES == 4
+
+
+@pytest.mark.parametrize("name", sorted(RGBD16_SETS))
+def test_rgbd_planted_raws_decide_a_gate_by_rounding(oracle_lib, name):
+    """a 16-bit set is worth its test only while ONE rounded fp32 multiply and a wider one fall on different sides of a plane at its pinned raw"""
+    scale, raws = RGBD16_SETS[name]
+    near, far = np.float32(RGBD_NEAR), np.float32(RGBD_FAR)
+    assert scale.dtype == np.float32
+    allr = np.arange(65536, dtype=np.uint16)
+    p32 = allr.astype(np.float32) * scale
+    p64 = allr.astype(np.float64) * np.float64(scale)         # exact: 16 x 24 significant bits
+    assert p32.dtype == np.float32
+    differ = np.flatnonzero(((p32 >= near) & (p32 <= far)) != ((p64 >= near) & (p64 <= far)))
+    if name == "A":
+        assert differ.tolist() == [2500] and p32[2500] == near and p64[2500] < near
+        assert p32[25000] == far and p64[25000] < far and p32[2499] < near < p32[2501] and p32[24999] < far < p32[25001]
+        kept = {2500, 2501, 12345, 24999, 25000}
+    else:
+        assert differ.tolist() == [5000] and p32[5000] == far and p64[5000] > far
+        assert p32[500] == near and p64[500] > near and p32[499] < near < p32[501] and p32[4999] < far < p32[5001]
+        # a division by the reciprocal scale, the other plausible conversion, moves raw 500 off the plane and raw 5000 beyond it
+        div = allr.astype(np.float32) / (np.float32(1) / scale)
+        assert div.dtype == np.float32 and div[500] > near and div[5000] > far
+        kept = {500, 501, 4999, 5000}
+    assert set(raws) >= kept | {0, 65535} and all((near <= p32[r] <= far) == (r in kept) for r in raws)
+    # some kept raw's metres differ between the multiply and a division by the reciprocal scale: the map's exact z tells them apart
+    dv = np.array(sorted(kept), np.float32) / (np.float32(1) / scale)
+    assert (dv != p32[sorted(kept)]).any()
+    case = rgbd_planted(name)
+    u = case["frames"][0][1]
+    ix, iy = case["xy"][:, 0].astype(int), case["xy"][:, 1].astype(int)
+    assert u.dtype == np.uint16 and np.array_equal(u[iy, ix], np.array(raws, np.uint16)[np.arange(len(ix)) % len(raws)])
+    assert np.array_equal(case["val"], u[iy, ix].astype(np.float32) * scale)
+    n_kept = sum(len(range(j, 804, len(raws))) for j, r in enumerate(raws) if r in kept)
+    _assert_planted(oracle_lib, case, 804, n_kept)
+    orc = oracle_lib.Oracle(case["prm"], 2)
+    for i, (g, _, f) in enumerate(case["frames"]):
+        orc.track_rgbd(g, f)
+        assert orc.status == 2, i
+
+
+def test_rgbd_barrel_case_leaves_the_image(oracle_lib):
+    """k1 < 0 on every frame: features kept outside [0, W) x [0, H), corners dropped for leaving the hash grid, and matches that land on the former"""
+    world, prm = rgbd_world(RGBD_BARREL)
+    assert prm.k1 < -1e-5
+    all_valid = rgbd_world(dict(RGBD_BARREL, near_plane_distance=0.0, far_plane_distance=1e30))[1]
+    orc = oracle_lib.Oracle(prm, 2)
+    outside_matched, rows = 0, []
+    for i in range(RGBD_BARREL_FRAMES):
+        g, d = world.render_rgbd(i)
+        orc.track_rgbd(g, d)
+        c = orc.counts()
+        xy = orc.features(0)[0]
+        out = rgbd_outside(xy)
+        # dropped by the grid rule: all corners minus the features of a frame whose depth is valid everywhere
+        full = oracle_lib.Oracle(all_valid, 2)
+        full.track_rgbd(g, np.ones_like(d))
+        drops = len(oracle_lib.compute_features(g, prm)[0]) - full.counts()["n_left"]
+        assert full.counts()["n_left"] == c["n_left"]          # (the world's depth is valid everywhere too)
+        fi, _ = orc.matches()
+        rows.append((c["n_matches"], int(out.sum()), drops, int(out[fi].sum()), float(xy[:, 0].max())))
+        outside_matched += int(out[fi].sum())
+        assert orc.status == 2 and (i == 0 or c["n_matches"] > 600), (i, c)
+        assert out.sum() >= 5 and drops >= 5, (i, rows[-1])
+        assert (xy[out, 0] < 650).all() and (xy[out, 1] < 500).all() and (xy >= 0).all()
+    print(rows)
+    assert outside_matched >= 1
+    assert max(r[4] for r in rows) > 649
+
+
+def test_rgbd_retry_case_runs_the_second_detection_pass(oracle_lib):
+    world, prm = rgbd_world(RGBD_RETRY)
+    orc = oracle_lib.Oracle(prm, 2)
+    for i in range(RGBD_RETRY_FRAMES):
+        orc.track_rgbd(*world.render_rgbd(i))
+        c = orc.counts()
+        assert c["retry_left"] == 1 and c["n_right"] == 0 and orc.status == 2 and 100 < c["n_left"] < 200, (i, c)
+        assert i == 0 or c["n_matches"] > 100, (i, c)
+
+
+@pytest.mark.parametrize("name", sorted(RGBD_NODEPTH))
+def test_rgbd_frames_without_valid_depth(oracle_lib, name):
+    prm, frames, status = rgbd_nodepth_script(name)
+    orc = oracle_lib.Oracle(prm, 2)
+    kinds = RGBD_NODEPTH[name][0]
+    assert len(frames) == len(kinds) == len(status)
+    for i, (g, handed, f) in enumerate(frames):
+        assert f.dtype == np.float32 and handed.dtype == (np.uint16 if kinds[i] == "zero16" else np.float32)
+        if kinds[i] != "world":
+            with np.errstate(invalid="ignore"):
+                assert not ((f >= np.float32(prm.near_plane_distance)) & (f <= np.float32(prm.far_plane_distance))).any()
+            assert np.isnan(handed).all() if kinds[i] == "nan" else not handed.any()
+        orc.track_rgbd(g, f)
+        c = orc.counts()
+        assert orc.status == status[i], (i, orc.status)
+        if kinds[i] != "world":
+            assert c["n_left"] == 0 and c["n_matches"] == 0, (i, c)
+    if name == "nan_first":
+        assert orc.counts()["map_size"] == 0
+    else:
+        assert orc.counts()["map_size"] > 1000

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from parity_util import make_case, pose_errors, diff_frame, POSE_TOL
-from test_gpu_rgbd_batch import quantise, SCALE
+from rgbd_util import quantise, SCALE
 
 pytestmark = pytest.mark.gpu
 
