@@ -262,6 +262,10 @@ LVT_API int lvt_amd_pnp_detail(const lvt_amd_params *p, const double q_in[4], co
 LVT_API int lvt_amd_pnp_trace(const lvt_amd_params *p, const double q_in[4], const double p_in[3], const double *pts,
                               const float *obs, int n, double q_out[4], double p_out[3], int *n_solve_calls,
                               double *err_out, int *level_out, int *borderline, double *trace, int trace_cap, int stats[3]);
+/* the constant-velocity motion model alone (reference lvt_motion_model.cpp:42-65), run by one device thread through the frame path's own code: state =
+ * {last_q[4] (w x y z), ang_vel[4], last_p[3], lin_vel[3]} on entry, the model's next state on return; q, p = the current pose; q_out, p_out = the
+ * predicted one.  Host pointers; runs on the current device.  0 on success, -1 on a NULL argument or a HIP failure. */
+LVT_API int lvt_amd_motion_predict(double state[14], const double q[4], const double p[3], double q_out[4], double p_out[3]);
 /* batched masked 2-NN Hamming (reference lvt_image_features_struct.cpp:68-120 + cv::BFMatcher knnMatch k=2):
  * B independent problems; per problem M queries (desc 32 B, xy f32) against N train (desc, xy, flag u8);
  * candidate iff !flag && dx*dx+dy*dy < r2 (f32, strict) [mode 0] or |band| row test [mode 1].

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "lvt_amd_batch_track_rgbd_device_async",
     "lvt_amd_set_rectifiers", "lvt_amd_batch_set_rectifiers",
     "lvt_amd_set_pixel_format", "lvt_amd_batch_set_pixel_format", "lvt_amd_get_pixel_format",
+    "lvt_amd_motion_predict",
 ]
 
 N_COUNTS = 32
@@ -115,6 +116,8 @@ def load_library():
     L.lvt_amd_pnp.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.lvt_amd_pnp_detail.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.lvt_amd_pnp_trace.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.lvt_amd_motion_predict.argtypes = [vp, vp, vp, vp, vp]
+    L.lvt_amd_motion_predict.restype = C.c_int
     L.lvt_amd_hamming_match_batched.restype = C.c_float
     L.lvt_amd_hamming_match_batched.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp]
     L.lvt_amd_get_timeline.argtypes = [vp, vp]
@@ -614,6 +617,17 @@ def pnp_trace(params: LvtParameters, q_in, p_in, pts, obs, trace_cap=256):
     if inl < 0:
         raise RuntimeError("lvt_amd_pnp_trace failed")
     return q, p, inl, calls.value, tr[:min(int(st[0]), trace_cap)].copy(), tuple(int(x) for x in st)
+
+
+def motion_predict(state, q, p):
+    """stage entry: the constant-velocity motion model on caller data (reference lvt_motion_model.cpp:42-65), one device thread through the frame path's own
+    motion_predict.  state = last_q[4] (w x y z), ang_vel[4], last_p[3], lin_vel[3]; returns (next state[14], predicted q, predicted p)"""
+    st = np.ascontiguousarray(state, np.float64).reshape(14).copy()
+    q = np.ascontiguousarray(q, np.float64).reshape(4); p = np.ascontiguousarray(p, np.float64).reshape(3)
+    qo = np.zeros(4); po = np.zeros(3)
+    if load_library().lvt_amd_motion_predict(_p(st), _p(q), _p(p), _p(qo), _p(po)) != 0:
+        raise RuntimeError("lvt_amd_motion_predict failed")
+    return st, qo, po
 
 
 def hamming_match_batched(q_desc, q_xy, t_desc, t_xy, t_flag, r2: float, mode: int, img_rows: int, img_cols: int, out, stream: int = 0,

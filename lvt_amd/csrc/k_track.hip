@@ -1955,6 +1955,23 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_standalone(Params prm, Pose
     }
 }
 
+// stand-alone entry for differential tests (lvt_amd_motion_predict): one thread fills the model state of a Ctl in device memory and calls the frame
+// path's own motion_predict.  io = {last_q[4], ang_vel[4], last_p[3], lin_vel[3], cur.q[4], cur.p[3]} in, {next[14], out.q[4], out.p[3]} out
+__global__ __launch_bounds__(64) void k_motion_predict_standalone(Ctl *ctl, double *io) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Ctl &c = *ctl;
+    for (int k = 0; k < 4; k++) c.mm_last_q[k] = io[k], c.mm_ang_vel[k] = io[4 + k];
+    for (int k = 0; k < 3; k++) c.mm_last_p[k] = io[8 + k], c.mm_lin_vel[k] = io[11 + k];
+    Pose cur, out;
+    for (int k = 0; k < 4; k++) cur.q[k] = io[14 + k];
+    for (int k = 0; k < 3; k++) cur.p[k] = io[18 + k];
+    double next[14];
+    motion_predict(c, cur, out, next);
+    for (int k = 0; k < 14; k++) io[k] = next[k];
+    for (int k = 0; k < 4; k++) io[14 + k] = out.q[k];
+    for (int k = 0; k < 3; k++) io[18 + k] = out.p[k];
+}
+
 // =================================================================================================
 // staged_body : update_staged_map_points (lvt_local_map.cpp:355-391) then the triangulation policy.
 // Matching = the same block-wide fixpoint; the promotion rule "counter == staged_threshold || map_size < 250"

@@ -2604,6 +2604,31 @@ LVT_API int lvt_amd_pnp(const lvt_amd_params *pin, const double q_in[4], const d
     return lvt_amd_pnp_detail(pin, q_in, p_in, pts, obs, n, q_out, p_out, n_solve_calls, nullptr, nullptr, nullptr);
 }
 
+// ---- stage entry: the constant-velocity motion model on caller data (the contract of the oracle's lvto_motion_predict) -------------
+// state = {last_q[4], ang_vel[4], last_p[3], lin_vel[3]} in, the model's next state out; (q, p) the current pose; runs on the current device.  0 / -1
+LVT_API int lvt_amd_motion_predict(double state[14], const double q[4], const double p[3], double q_out[4], double p_out[3]) {
+    if (!state || !q || !p || !q_out || !p_out) return -1;
+    Ctl *dCtl = nullptr;
+    double *dIo = nullptr;
+    double io[21];
+    for (int k = 0; k < 14; k++) io[k] = state[k];
+    for (int k = 0; k < 4; k++) io[14 + k] = q[k];
+    for (int k = 0; k < 3; k++) io[18 + k] = p[k];
+    int rc = -1;
+    if (hipMalloc((void **)&dCtl, sizeof(Ctl)) == hipSuccess && hipMalloc((void **)&dIo, sizeof(io)) == hipSuccess &&
+        hipMemset(dCtl, 0, sizeof(Ctl)) == hipSuccess && hipMemcpy(dIo, io, sizeof(io), hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_motion_predict_standalone, dim3(1), dim3(64), 0, 0, dCtl, dIo);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(io, dIo, sizeof(io), hipMemcpyDeviceToHost) == hipSuccess) {
+            for (int k = 0; k < 14; k++) state[k] = io[k];
+            for (int k = 0; k < 4; k++) q_out[k] = io[14 + k];
+            for (int k = 0; k < 3; k++) p_out[k] = io[18 + k];
+            rc = 0;
+        }
+    }
+    (void)hipFree(dCtl), (void)hipFree(dIo);
+    return rc;
+}
+
 
 // ---- stage entry: batched masked 2-NN Hamming matcher on device-resident problems --------------------
 LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_xy, const void *t_desc, const void *t_xy, const void *t_flag,

@@ -614,3 +614,162 @@ def rgbd_nodepth_script(name):
             d = np.zeros_like(d)
         frames.append((g, np.zeros(d.shape, np.uint16) if kind == "zero16" else d, d))
     return prm, frames, status
+
+
+# ---- turns past 180 degrees --------------------------------------------------------------------------------------------------------------------------
+# The synthetic worlds of lvt_amd/synth.py turn by a few degrees, so every other sequence keeps its pose quaternion at w > 0.99.  These cases drive the
+# tracker through half a turn and more (turn_worlds.py): the published pose flips from q to -q between two frames (k_pnp keeps w >= 0), motion_predict takes
+# the d < 0 arm of its slerp and predicts a pose with w < 0, the rotation matrices leave the identity (R[0] < 0: the right camera towards the world's -x),
+# and -- in the room with culling switched off -- hundreds of map points lie behind the camera and project inside the image with a negative depth.
+# Measured with the oracle (test_case_tables.py asserts the conditions; half-size KITTI is 620 x 188, half-size TUM 320 x 240):
+#   roll_past_180    TRACKING on all 76 frames, pose w down to 0.0092 at frame 60, predicted w < 0 at frames 60 and 61 (-0.0094, -0.0348)
+#   room_loop        TRACKING on all 150 frames, |w| down to 0.0044 at frame 73, predicted w < 0 at frames 73 and 74, at most 1 point behind the camera
+#   room_loop_keep   TRACKING on all 150 frames, |w| down to 0.0021, the map grows to 2 040 points, up to 1 008 of them behind the camera, up to 518 of those
+#                    inside the image; 100 or more of them on 108 frames
+#   room_rgbd        (3 m room, radius 0.8 m, 2 degrees per frame, 0.01 m texels) TRACKING on all 100 frames, |w| down to 0.0081 at frame 91
+# name: (world kind, world parameters, parameter overrides, frames, sensor)
+TURN_CASES = {
+    "roll_past_180": ("roll", dict(deg_per_frame=3.0), {}, 76, 1),
+    "room_loop": ("room", dict(deg_per_frame=2.5, radius=3.0), {}, 150, 1),
+    "room_loop_keep": ("room", dict(deg_per_frame=2.5, radius=3.0), {"untracked_threshold": 1000}, 150, 1),
+    "room_rgbd": ("room", dict(deg_per_frame=2.0, radius=0.8, half_side=3.0, texel=0.01), {}, 100, 2),
+}
+TURN_MIN_ABS_W = 1e-3             # below it the sign of w would be a matter of rounding
+TURN_KEEP_FRAMES, TURN_KEEP_POINTS = 100, 100     # room_loop_keep: on so many frames so many points are kept out by the near plane alone
+TURN_CULLED_POINTS = 5            # room_loop (default culling): never more than this handful
+
+_TURN_WORLDS = {}
+
+
+def turn_case(name):
+    """(world, params, sensor, frames) of one TURN_CASES entry.  Worlds are kept (and keep their frames): room_loop and room_loop_keep share one."""
+    from parity_util import make_case
+    from turn_worlds import RolledWorld, RoomWorld
+    kind, wkw, overrides, n, sensor = TURN_CASES[name]
+    base, prm, s = make_case("kitti" if sensor == 1 else "tum", 0, 0.5, overrides)
+    assert s == sensor
+    key = (kind, sensor, tuple(sorted(wkw.items())))
+    if key not in _TURN_WORLDS:
+        if kind == "roll":
+            _TURN_WORLDS[key] = RolledWorld(base, **wkw)
+        else:
+            _TURN_WORLDS[key] = RoomWorld(base.W, base.H, base.fx, base.fy, base.cx, base.cy, base.baseline, seed=0, **wkw)
+    return _TURN_WORLDS[key], prm, sensor, n
+
+
+def quat_to_R(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def behind_camera_in_image(prm, xyz, q, p, near_gate=True):
+    """the number of map points that is_point_visible's `cz < near_plane` ALONE keeps out of the match lists, with cz < 0: under the pose (q = w x y z, p:
+    camera to world) they lie behind the camera, yet projected with inv_z = 1 / cz they land inside [0, W) x [0, H), and the far plane passes every negative
+    depth.  near_gate=False restates the gate without that comparison: nothing is kept out then, the count is zero."""
+    if not len(xyz):
+        return 0
+    Xc = (np.asarray(xyz) - p) @ quat_to_R(q)
+    cz = Xc[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = prm.fx * Xc[:, 0] / cz + prm.cx, prm.fy * Xc[:, 1] / cz + prm.cy
+        inside = (u >= 0) & (u < prm.img_width) & (v >= 0) & (v < prm.img_height)
+    without = inside & ~(cz > prm.far_plane_distance)
+    with_gate = without & ~(cz < prm.near_plane_distance) if near_gate else without
+    return int((without & ~with_gate & (cz < 0)).sum())
+
+
+# ---- the motion model alone: the branches of motion_predict (lvt_math.h) / MotionModel::predict (the oracle) no sequence reaches ------------------------
+MOTION_ONE = 1.0 - 2.0 ** -52       # Eigen's slerp: at |d| >= 1 - epsilon the weights are (1 - t, t)
+MOTION_SMALL_ANGLES = (1e-9, 3e-9, 1e-8, 1.5e-8, 2e-8, 5e-8, 1e-7, 1e-6, 1e-4, 1e-2)     # cos a walks through MOTION_ONE between 2e-8 and 5e-8
+MOTION_RANDOM = 200
+
+
+def _axis_angle(axis, a):
+    axis = np.asarray(axis, float)
+    return np.array([np.cos(a / 2), *(np.sin(a / 2) * axis / np.linalg.norm(axis))])
+
+
+def _qmul(a, b):
+    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                     a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3], a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1]])
+
+
+def motion_edge_cases():
+    """[(label, state[14] = last_q, ang_vel, last_p, lin_vel, q[4], p[3])].  last_q is the identity unless the label says otherwise, so diff = cur.q * last_q^-1
+    is cur.q exactly and d = diff . ang_vel is known in advance."""
+    ident = np.array([1.0, 0, 0, 0])
+    rows = []
+
+    def add(label, q, last_q=ident, ang_vel=ident, p=(0.3, -0.2, 1.5), last_p=(0.1, 0.1, 1.0), lin_vel=(0.15, -0.25, 0.45)):
+        rows.append((label, np.concatenate([last_q, ang_vel, last_p, lin_vel]).astype(np.float64), np.asarray(q, np.float64), np.asarray(p, np.float64)))
+    add("stationary", ident, p=(1.0, 2.0, 3.0), last_p=(1.0, 2.0, 3.0), lin_vel=(0, 0, 0))                    # d = 1 exactly, nothing moves
+    for a in MOTION_SMALL_ANGLES:
+        q = np.array([np.cos(a), np.sin(a), 0, 0])
+        add(f"small_{a:g}", q)
+        add(f"small_{a:g}_negated_velocity", q, ang_vel=-ident)                                              # d < 0
+        add(f"small_{a:g}_negated_pose", -q)                                                                 # d < 0
+    add("orthogonal_axes", [0.0, 1, 0, 0])                                                                   # d = +0.0, theta = pi / 2
+    c, s = np.cos(0.3), np.sin(0.3)
+    add("orthogonal_cancelling", [c, s, 0, 0], ang_vel=np.array([-s, c, 0, 0]))                              # d = -cs + sc = +0.0
+    for deg in (90.0, 179.0, 179.999):                                                                      # the angle between diff and ang_vel as 4-vectors
+        f = np.deg2rad(deg)
+        add(f"wide_{deg:g}", ident, ang_vel=np.array([np.cos(f), 0, np.sin(f), 0]))
+        add(f"wide_{deg:g}_rotated", _axis_angle([1, 2, 3], 0.7), ang_vel=_qmul(_axis_angle([1, 2, 3], 0.7), np.array([np.cos(f), 0, np.sin(f), 0])))
+    g = _axis_angle([0.2, -1.0, 0.4], 1.1)
+    add("zero_last_q", g, last_q=np.zeros(4), ang_vel=_axis_angle([0, 1, 0], 0.2))                          # inv = 0, diff = 0
+    add("last_q_norm_3", g, last_q=3.0 * _axis_angle([0.5, 1.0, 0.1], 0.9), ang_vel=_axis_angle([0, 1, 0], 0.2))
+    add("last_q_norm_1e-3", g, last_q=1e-3 * _axis_angle([0.5, 1.0, 0.1], 0.9), ang_vel=_axis_angle([0, 1, 0], 0.2))
+    add("cur_q_norm_2", 2.0 * g, last_q=_axis_angle([0.5, 1.0, 0.1], 0.9), ang_vel=_axis_angle([0, 1, 0], 0.2))
+    add("large_positions", g, p=(1e6, -2e6, 3e6), last_p=(1e6 - 0.5, -2e6 + 0.25, 3e6 - 1.0), lin_vel=(1e6, 1e6, -1e6))
+    add("tiny_positions", g, p=(1e-12, -2e-12, 3e-12), last_p=(2e-12, 1e-12, -1e-12), lin_vel=(1e-12, -1e-12, 1e-12))
+    rng = np.random.default_rng(20260)
+    for k in range(MOTION_RANDOM):
+        last_q = _axis_angle(rng.normal(size=3), rng.uniform(0, 2 * np.pi))
+        q = _qmul(_axis_angle(rng.normal(size=3), np.deg2rad(rng.uniform(0, 170))), last_q) * rng.choice([-1.0, 1.0])
+        av = _axis_angle(rng.normal(size=3), np.deg2rad(rng.uniform(0, 170))) * rng.choice([-1.0, 1.0])
+        last_p = rng.normal(0, 10, 3)
+        add(f"random_{k}", q, last_q=last_q, ang_vel=av, p=last_p + rng.normal(0, 1, 3), last_p=last_p, lin_vel=rng.normal(0, 1, 3))
+    return rows
+
+
+MOTION_EDGE_CASES = motion_edge_cases()
+
+
+def motion_slerp_dot(state, q):
+    """(d, |diff|): the dot product motion_predict's slerp branches on, in the code's own operation order (fp64)"""
+    lq, b = state[0:4], state[4:8]
+    n2 = lq[0] * lq[0] + lq[1] * lq[1] + lq[2] * lq[2] + lq[3] * lq[3]
+    inv = np.array([lq[0] / n2, -lq[1] / n2, -lq[2] / n2, -lq[3] / n2]) if n2 > 0 else np.zeros(4)
+    diff = _qmul(q, inv)
+    return diff[0] * b[0] + diff[1] * b[1] + diff[2] * b[2] + diff[3] * b[3], float(np.linalg.norm(diff))
+
+
+def motion_predict_longdouble(state, q, p):
+    """lvt_motion_model.cpp:42-65 with Eigen 3.3's inverse / slerp / normalize, restated in numpy.longdouble from the fp64 inputs: (next[14], q_out, p_out).
+    The slerp's `one` is the fp64 constant of the code, whatever the precision of the arithmetic."""
+    L = np.longdouble
+    st, q, p = np.asarray(state, L), np.asarray(q, L), np.asarray(p, L)
+    lq, b, lp, lv = st[0:4], st[4:8], st[8:11], st[11:14]
+    half = L(0.5)
+    nv = ((p - lp) + lv) * half
+    n2 = (lq * lq).sum()
+    inv = np.array([lq[0], -lq[1], -lq[2], -lq[3]], L) / n2 if n2 > 0 else np.zeros(4, L)
+    diff = _qmul(q, inv)
+    d = (diff * b).sum()
+    if abs(d) >= L(MOTION_ONE):
+        s0 = s1 = half
+    else:
+        th = np.arccos(abs(d))
+        s0, s1 = np.sin(half * th) / np.sin(th), np.sin(half * th) / np.sin(th)
+    if d < 0:
+        s1 = -s1
+    nav = s0 * diff + s1 * b
+
+    def normalized(x):
+        z = (x * x).sum()
+        return x / np.sqrt(z) if z > 0 else x
+    nav = normalized(nav)
+    out_q = normalized(_qmul(q, nav))
+    return np.concatenate([q, nav, p, nv]), out_q, p + nv

@@ -20,6 +20,7 @@ def declared_symbols():
 def test_library_exports_every_declared_symbol(hip_lib):
     decl = declared_symbols()
     assert {"lvt_create", "lvt_destroy", "lvt_track", "lvt_track_with_external_corners", "lvt_get_status"} <= set(decl)
+    assert {"lvt_amd_pnp", "lvt_amd_pnp_detail", "lvt_amd_pnp_trace", "lvt_amd_motion_predict"} <= set(decl)     # the stage entry points on caller data
     assert sorted(decl) == sorted(lvt_amd.ABI_SYMBOLS)
     lib = ctypes.CDLL(lvt_amd.LIB_PATH)
     for s in decl:
@@ -93,6 +94,18 @@ def test_no_handle_is_refused_by_every_frame_and_wait_entry_point(hip_lib):
         for name, call in int_calls.items():
             assert call() == -1, name
             assert not R.any() and not t.any() and not q.any(), name
+
+
+def test_motion_predict_refuses_a_null_argument_without_a_device(hip_lib):
+    """lvt_amd_motion_predict: -1 for any NULL pointer before the device is touched, the other arrays unchanged"""
+    import numpy as np
+    L = hip_lib.load_library()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    for missing in range(5):
+        arrs = [np.full(14, 7.0), np.full(4, 7.0), np.full(3, 7.0), np.full(4, 7.0), np.full(3, 7.0)]
+        args = [None if k == missing else p(a) for k, a in enumerate(arrs)]
+        assert L.lvt_amd_motion_predict(*args) == -1, missing
+        assert all((a == 7.0).all() for a in arrs)
 
 
 def test_product_does_not_reference_the_oracle():

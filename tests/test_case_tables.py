@@ -557,3 +557,131 @@ def test_rgbd_frames_without_valid_depth(oracle_lib, name):
         assert orc.counts()["map_size"] == 0
     else:
         assert orc.counts()["map_size"] > 1000
+
+
+# ---- turns past 180 degrees: conditions on the inputs, the oracle alone ------------------------------------------------------------------------------
+from case_tables import (MOTION_EDGE_CASES, MOTION_ONE, MOTION_RANDOM, MOTION_SMALL_ANGLES, TURN_CASES, TURN_CULLED_POINTS, TURN_KEEP_FRAMES,  # noqa: E402
+                         TURN_KEEP_POINTS, TURN_MIN_ABS_W, behind_camera_in_image, motion_predict_longdouble, motion_slerp_dot, quat_to_R, turn_case)
+
+_TURNS = {}
+
+
+def _turn_run(name):
+    """one oracle run per case, shared by the guards: per frame the status, the pose, the predicted pose (None for a frame that made none) and the number
+    of map points at match time that the near plane alone keeps out (with the gate as it is, and restated without the comparison)"""
+    if name not in _TURNS:
+        from oracle import pyoracle as O
+        world, prm, sensor, n = turn_case(name)
+        orc = O.Oracle(prm, sensor)
+        rows = []
+        for i in range(n):
+            at_match = orc.map()[0]
+            if sensor == 1:
+                orc.track(*world.render_stereo(i))
+            else:
+                orc.track_rgbd(*world.render_rgbd(i))
+            q, p = orc.pose()
+            pred, behind, ungated = None, 0, 0
+            if orc.counts()["map_size_at_match"] > 0:
+                assert orc.counts()["map_size_at_match"] == len(at_match)
+                pred = orc.predicted_pose()
+                behind = behind_camera_in_image(prm, at_match, pred[0], pred[1])
+                ungated = behind_camera_in_image(prm, at_match, pred[0], pred[1], near_gate=False)
+            rows.append(dict(status=orc.status, q=q, p=p, pred=pred, behind=behind, ungated=ungated))
+        _TURNS[name] = (world, prm, rows)
+    return _TURNS[name]
+
+
+def test_turn_worlds_are_functions_of_their_seed():
+    """the same frame from two instances, another one from another seed; the room's depth is the planar depth of what the gray image shows"""
+    from parity_util import make_case
+    from turn_worlds import RolledWorld, RoomWorld
+    base, _, _ = make_case("kitti", 0, 0.25)
+    cam = (base.W, base.H, base.fx, base.fy, base.cx, base.cy, base.baseline)
+    a, b, c = RoomWorld(*cam, seed=3), RoomWorld(*cam, seed=3), RoomWorld(*cam, seed=4)
+    for i in (0, 40, 77):
+        assert all(np.array_equal(x, y) for x, y in zip(a.render_stereo(i), b.render_stereo(i)))
+        assert not np.array_equal(a.render_stereo(i)[0], c.render_stereo(i)[0])
+    g, d = a.render_rgbd(40)
+    assert np.array_equal(g, a.render_stereo(40)[0]) and d.dtype == np.float32 and d.min() > 1.0 and d.max() < 30.0
+    assert a.render_stereo(40) is a.render_stereo(40)                                        # frames are kept
+    R, t = a.pose(72)                                                                        # 180 degrees of yaw: the far side of the circle, looking back
+    assert np.allclose(R, np.diag([-1.0, 1, -1]), atol=1e-12) and np.allclose(t[[0, 2]], [6.0, 0.0], atol=1e-12)
+    r1, r2 = RolledWorld(base, 3.0), RolledWorld(base, 3.0)
+    assert all(np.array_equal(x, y) for x, y in zip(r1.render_stereo(30), r2.render_stereo(30)))
+    R30, t30 = r1.pose(30)
+    Rb, tb = base.pose(30)                                                                   # (the wrapped world keeps its own trajectory)
+    c90 = np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 1]])
+    assert np.allclose(R30, Rb @ c90, atol=1e-12) and np.array_equal(t30, tb)
+
+
+@pytest.mark.parametrize("name", sorted(TURN_CASES))
+def test_turn_case_conditions(oracle_lib, name):
+    """every frame TRACKING; |w| of every pose at least 1e-3 (the sign k_pnp publishes is then no matter of rounding); the pose flips (q . previous q < 0) and a
+    prediction with w < 0 follows a pose with w >= 0; the rotation leaves the identity far enough for R[0] < 0"""
+    _, prm, rows = _turn_run(name)
+    assert [r["status"] for r in rows] == [2] * len(rows), [i for i, r in enumerate(rows) if r["status"] != 2]
+    w = np.array([r["q"][0] for r in rows])
+    print(f"{name}: min |w| {np.abs(w).min():.4f} at frame {int(np.abs(w).argmin())}")
+    assert np.abs(w).min() >= TURN_MIN_ABS_W and w.min() >= 0.0
+    neg = [(i, float(r["pred"][0][0])) for i, r in enumerate(rows) if r["pred"] is not None and r["pred"][0][0] < 0 and r["q"][0] >= 0]
+    flips = [i for i in range(1, len(rows)) if rows[i]["q"] @ rows[i - 1]["q"] < 0]
+    print(f"{name}: predicted w < 0 at {neg}, pose flips at {flips}")
+    assert neg and flips
+    assert min(quat_to_R(r["q"])[0, 0] for r in rows) < -0.9
+
+
+def test_room_loop_keep_has_points_behind_the_camera_inside_the_image(oracle_lib):
+    """with culling off, on at least 100 frames at least 100 map points at match time lie behind the camera under the predicted pose and project inside the
+    image: is_point_visible's `cz < near_plane` alone keeps them out of the lists.  Restated without that comparison the count is zero on every frame; under
+    the default culling (room_loop) there is never more than a handful."""
+    _, _, rows = _turn_run("room_loop_keep")
+    behind = np.array([r["behind"] for r in rows])
+    print(f"room_loop_keep: {int((behind >= TURN_KEEP_POINTS).sum())} frames with {TURN_KEEP_POINTS}+ such points, peak {behind.max()}")
+    assert (behind >= TURN_KEEP_POINTS).sum() >= TURN_KEEP_FRAMES
+    assert not any(r["ungated"] for r in rows)
+    _, _, rows = _turn_run("room_loop")
+    assert max(r["behind"] for r in rows) <= TURN_CULLED_POINTS, max(r["behind"] for r in rows)
+
+
+def test_motion_table_takes_every_branch():
+    """MOTION_EDGE_CASES: both arms of |d| >= one among the small angles (and the threshold between 2e-8 and 5e-8), d < 0, d = +0.0, a zero inverse, scaled
+    and unnormalised quaternions, and the random rows' d of both signs"""
+    d = {lab: motion_slerp_dot(st, q) for lab, st, q, _ in MOTION_EDGE_CASES}
+    assert len(d) == len(MOTION_EDGE_CASES) and sum(lab.startswith("random_") for lab in d) == MOTION_RANDOM
+    assert d["stationary"][0] == 1.0
+    small = [d[f"small_{a:g}"][0] for a in MOTION_SMALL_ANGLES]
+    assert any(x >= MOTION_ONE for x in small) and any(x < MOTION_ONE for x in small)
+    assert d["small_2e-08"][0] >= MOTION_ONE > d["small_5e-08"][0]
+    for a in MOTION_SMALL_ANGLES:
+        assert d[f"small_{a:g}_negated_velocity"][0] == -d[f"small_{a:g}"][0] == d[f"small_{a:g}_negated_pose"][0]
+    for lab in ("orthogonal_axes", "orthogonal_cancelling"):
+        assert d[lab][0] == 0.0 and not np.signbit(d[lab][0])
+    assert abs(d["wide_90"][0]) < 1e-15 and -1.0 < d["wide_179"][0] < -0.999 and d["wide_179.999"][0] < -0.9999999 and d["wide_179.999"][0] > -MOTION_ONE
+    assert d["zero_last_q"] == (0.0, 0.0)
+    assert abs(d["last_q_norm_3"][1] - 1 / 3) < 1e-12 and abs(d["last_q_norm_1e-3"][1] - 1e3) < 1e-9 and abs(d["cur_q_norm_2"][1] - 2) < 1e-12
+    rnd = np.array([d[f"random_{k}"][0] for k in range(MOTION_RANDOM)])
+    assert (rnd < 0).sum() > 50 and (rnd > 0).sum() > 50 and (np.abs(rnd) < MOTION_ONE).all()
+
+
+def test_oracle_motion_model_equals_the_longdouble_restatement(oracle_lib):
+    """the oracle's lvto_motion_predict on the whole table against lvt_motion_model.cpp:42-65 restated in numpy.longdouble (64-bit significand): the reference
+    is pinned before the GPU tier uses it as one.
+      copies (next[0..3] = q, next[8..10] = p): bit-equal.
+      quaternions (next[4..7], q_out; components <= 1): the path is about 20 roundings of 1.1e-16 on quantities <= 1 (2.3e-15) plus acos and two sin within an
+      ulp; 1e-14 leaves a factor of four.
+      positions (next[11..13], p_out): three roundings on quantities up to 2 M, M = the largest position / velocity component: 4 eps M."""
+    assert np.finfo(np.longdouble).eps < 1e-18, "numpy.longdouble is no wider than double here: the restatement would pin nothing"
+    worst_q = worst_p = 0.0
+    for lab, st, q, p in MOTION_EDGE_CASES:
+        nx, qo, po = oracle_lib.motion_predict(st, q, p)
+        ln, lq, lp = motion_predict_longdouble(st, q, p)
+        assert np.array_equal(nx[0:4], q) and np.array_equal(nx[8:11], p), lab
+        eq = float(max(np.abs(qo - lq).max(), np.abs(nx[4:8] - ln[4:8]).max()))
+        M = float(np.abs(np.concatenate([st[8:14], p])).max())
+        ep = float(max(np.abs(po - lp).max(), np.abs(nx[11:14] - ln[11:14]).max())) / M
+        worst_q, worst_p = max(worst_q, eq), max(worst_p, ep)
+        assert eq <= 1e-14, f"{lab}: quaternion differs by {eq:.3e}"
+        assert ep <= 4 * np.finfo(np.float64).eps, f"{lab}: position differs by {ep:.3e} relative"
+        assert abs(float((qo * qo).sum()) - 1) < 1e-15 and abs(float((nx[4:8] * nx[4:8]).sum()) - 1) < 1e-15, lab
+    print(f"oracle vs longdouble: quaternions {worst_q:.3e}, positions {worst_p:.3e} relative")

@@ -118,3 +118,60 @@ def test_bad_arguments():
     L = lvt_amd.load_library()
     assert L.lvt_amd_odometry_push_pose(od._h, None, None, 2, 0.0, None, None) == -1
     assert L.lvt_amd_odometry_update(od._h, None, None, 1, 1, 0.0, None, None) == -1   # no tracker attached
+
+
+# ---- turns past 180 degrees: all four arms of mat3_to_quat -------------------------------------------------------------------------------------------
+# The random walk above stays within a few degrees of the identity: only the `tr > 0` arm of mat3_to_quat (lvt_odometry.h) runs.  The ground-truth
+# trajectories of the turning worlds (TURN_CASES) and a pitch loop take the accumulated rotation through half a turn about each axis of the odom frame: the
+# roll about the optical axis is a rotation about odom x (largest diagonal element 0), the pitch loop about odom y (1), the yaw of the room about odom z (2).
+# The rooms and the pitch loop turn by an exact multiple of their step, so frame 72 / 90 would be a rotation by pi exactly, where the model's _quat_xyzw
+# divides by sin(angle) = 0: their frames are taken 0.3 of a step late.
+TURN_PHASE = {"roll_past_180": 0.0, "room_loop": 0.3, "room_rgbd": 0.3, "pitch_loop": 0.3}
+
+
+def _turn_trajectory(name):
+    if name == "pitch_loop":     # rotation about the camera's x axis through 360 degrees at 2.5 degrees per frame, driving the circle that goes with it
+        return [(_rot("x", np.deg2rad(2.5) * (i + TURN_PHASE[name])), 3.0 * np.array([0.05 * np.sin(i / 7.0), np.cos(np.deg2rad(2.5) * i) - 1, np.sin(np.deg2rad(2.5) * i)]))
+                for i in range(146)]
+    from case_tables import turn_case
+    world, _, _, n = turn_case(name)
+    return [world.pose(i + TURN_PHASE[name]) for i in range(n)]
+
+
+def _arm(R):
+    """the arm mat3_to_quat takes on R: "tr", or the index of the largest diagonal element by its own comparisons"""
+    if R[0, 0] + R[1, 1] + R[2, 2] > 0:
+        return "tr"
+    i = 1 if R[1, 1] > R[0, 0] else 0
+    return 2 if R[2, 2] > R[i, i] else i
+
+
+def _angle(R):
+    return float(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1)))
+
+
+@pytest.mark.parametrize("with_base", [False, True])
+def test_accumulation_through_turns_past_180_degrees(with_base):
+    b2s = None
+    if with_base:
+        b2s = np.eye(4); b2s[:3, :3] = _rot("z", 0.3) @ _rot("y", -0.2); b2s[:3, 3] = [0.4, -0.1, 1.2]
+    arms = {}
+    for name in TURN_PHASE:
+        od = lvt_amd.Odometry(None, None if b2s is None else b2s[:3, :], True)
+        ref = NodeModel(b2s, True)
+        seen = set()
+        for i, (R, t) in enumerate(_turn_trajectory(name)):
+            before = ref.acc.copy()
+            got, exp = od.push_pose(R, t, 2, 0.1 * i), ref.push(R, t, 2, 0.1 * i)
+            assert got is not None and exp is not None
+            # condition on the model (its _quat_xyzw divides by sin(angle)): the accumulated and the delta rotation stay 1e-3 rad away from pi
+            delta = np.linalg.inv(before) @ ref.acc
+            assert np.pi - _angle(ref.acc[:3, :3]) >= 1e-3 and np.pi - _angle(delta[:3, :3]) >= 1e-3, (name, i)
+            seen.add(_arm(ref.acc[:3, :3]))
+            assert np.allclose(got[0][:3], exp[0][:3], atol=1e-9), (name, i)
+            assert _same_rotation(got[0][3:], exp[0][3:]), (name, i, got[0][3:], exp[0][3:])
+            assert np.allclose(got[1], exp[1], atol=1e-7), (name, i)
+            assert abs(np.linalg.norm(got[0][3:]) - 1) < 1e-12
+        arms[name] = seen
+    if not with_base:    # (a base frame conjugates the rotation onto other axes)
+        assert arms["roll_past_180"] == {"tr", 0} and arms["pitch_loop"] == {"tr", 1} and arms["room_loop"] == {"tr", 2} and arms["room_rgbd"] == {"tr", 2}, arms
