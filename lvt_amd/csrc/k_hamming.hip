@@ -269,7 +269,9 @@ __global__ __launch_bounds__(HB_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
                 // starts, 6-bit lengths): neither stage recomputes hash cells, window clamps or bin lookups
                 const Ranges R = ranges(qp[k]);
                 qkey[k] = HB_HIST - 1 - min(R.l0 + R.l1 + R.l2, HB_HIST - 1);
-                const bool fits = (N <= 2048) && (R.l0 < 64) && (R.l1 < 64) && (R.l2 < 64);
+                // (a start is a count of unflagged features: with N = 2048 and no flag set, the start of a range behind the last populated
+                //  bin IS 2048, one bit more than its field -- the test is on the starts themselves, N = 2048 with flags stays packed)
+                const bool fits = (N <= 2048) && ((R.s0 | R.s1 | R.s2) < 2048) && (R.l0 < 64) && (R.l1 < 64) && (R.l2 < 64);
                 s_q[3 * q] = fits ? ((uint32_t)R.s0 | ((uint32_t)R.s1 << 11) | ((uint32_t)R.l0 << 22)) : 0xFFFFFFFFu;
                 s_q[3 * q + 1] = (uint32_t)R.s2 | ((uint32_t)R.l1 << 11) | ((uint32_t)R.l2 << 17);
             } else {

@@ -2661,21 +2661,6 @@ LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_
         a.nbx = (int)std::ceil(img_cols / (float)HASH_CELL), a.nby = (int)std::ceil(img_rows / (float)HASH_CELL);
         a.csr = std::max(1, (int)std::ceil(std::sqrt(r2) / (float)HASH_CELL));
     }
-    const size_t lds = hamming_lds_bytes(N, M, a.nbx * a.nby);
-    if (lds > 160 * 1024) {
-        std::fprintf(stderr, "lvt_amd_hamming_match_batched: %zu bytes of LDS needed\n", lds);
-        return -1.0f;
-    }
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    hipEvent_t e0, e1;
-    {
-        const hipError_t c0 = hipEventCreate(&e0), c1 = hipEventCreate(&e1);
-        if (c0 != hipSuccess || c1 != hipSuccess) {
-            std::fprintf(stderr, "lvt_amd_hamming_match_batched: hipEventCreate failed: %s / %s\n", hipGetErrorString(c0), hipGetErrorString(c1));
-            return -1.0f;
-        }
-    }
-    float ms = -1.0f;
     // the variant fixes how many candidate ranges a query keeps in registers (k_hamming.hip)
     void (*kern)(HammingArgs) = nullptr;
     {
@@ -2694,6 +2679,28 @@ LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_
 #undef LVT_PICK_T
 #undef LVT_PICK
     }
+    // a workgroup's 160 KiB hold the carve-up AND the kernel's static arrays (s_scan, s_hist, s_recheck): a size that leaves them no room is refused
+    // here, not at the launch
+    const size_t lds = hamming_lds_bytes(N, M, a.nbx * a.nby);
+    hipFuncAttributes fattr;
+    if (hipFuncGetAttributes(&fattr, reinterpret_cast<const void *>(kern)) != hipSuccess) {
+        std::fprintf(stderr, "lvt_amd_hamming_match_batched: hipFuncGetAttributes failed\n");
+        return -1.0f;
+    }
+    if (lds + fattr.sharedSizeBytes > 160 * 1024) {
+        std::fprintf(stderr, "lvt_amd_hamming_match_batched: %zu + %zu bytes of LDS needed\n", lds, (size_t)fattr.sharedSizeBytes);
+        return -1.0f;
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    hipEvent_t e0, e1;
+    {
+        const hipError_t c0 = hipEventCreate(&e0), c1 = hipEventCreate(&e1);
+        if (c0 != hipSuccess || c1 != hipSuccess) {
+            std::fprintf(stderr, "lvt_amd_hamming_match_batched: hipEventCreate failed: %s / %s\n", hipGetErrorString(c0), hipGetErrorString(c1));
+            return -1.0f;
+        }
+    }
+    float ms = -1.0f;
     const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipEventRecord(e0, st);
     for (int l = 0; l < launches; l++) hipLaunchKernelGGL(kern, dim3(B), dim3(HB_THREADS), lds, st, a);

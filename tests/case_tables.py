@@ -773,3 +773,481 @@ def motion_predict_longdouble(state, q, p):
     nav = normalized(nav)
     out_q = normalized(_qmul(q, nav))
     return np.concatenate([q, nav, p, nv]), out_q, p + nv
+
+
+# ---- the batched Hamming matcher: every template instance, its overflow bounds, its dispatch boundaries (test_gpu_hamming_instances.py) ----------------
+# The host's dispatch rule and LDS formula, restated (tools/hamming_sweep.py states the picker as well, but imports torch and opens the device, and keys
+# the family by the name of a mask instead of r2).  Restated from lvt_amd/csrc:
+#   lvt_host.hip  lvt_amd_hamming_match_batched_n: the size caps (N <= HB_NMAX, M <= HB_MMAX), nbx / nby / csr, the LDS check (the carve-up plus the
+#                 kernel's static arrays within a workgroup's 160 KiB), and the picker
+#                 (qpt, tpt = ceil(M / HB_THREADS), ceil(N / HB_THREADS); row mode <1,1>, csr 1 <0,3>, csr 2 <0,5>, any other csr <0,0>)
+#   k_hamming.hip hamming_lds_bytes, HB_THREADS, HB_TPT, HB_QPT; the chunk of the chunked bin scan (step 2); MASK_BITS and the 64-candidate masks
+HB_THREADS = 1024
+HB_MMAX = HB_NMAX = 4 * HB_THREADS
+HB_LDS_MAX = 160 * 1024
+HB_STATIC_LDS = 400                 # s_scan (128 B) + s_hist (256 B) + s_recheck (4 B) as every instance's code object lays them out: the host asks the runtime
+HB_MASK_BITS = 41                   # packed csr-1 family: window candidates a query's slot words hold a radius bit for
+HB_RANGE_MAX = 63                   # ... and the longest range its 6-bit length fields hold
+HB_TWO_STAGE_MAX = 64               # unpacked two-stage family (csr 2): window candidates of the two mask words
+HASH_CELL = 25
+HAMMING_GEOMETRY = (376, 1241)      # rows, cols of test_every_instance
+# family -> (mode, NSP, r2 of test_every_instance)
+HAMMING_FAMILIES = {"row": (1, 1, 0.0), "csr1": (0, 3, 625.0), "csr2": (0, 5, 2500.0), "any": (0, 0, 5625.0)}
+
+
+def hamming_csr(r2):
+    """max(1, ceil(sqrt(r2) / 25)) in fp32, as the host computes it"""
+    return max(1, int(np.ceil(np.sqrt(np.float32(r2)) / np.float32(HASH_CELL))))
+
+
+def hamming_grid(mode, rows, cols):
+    """(nbx, nby): hash cells in radius mode, one bin per image row 0 .. rows in row mode"""
+    if mode == 1:
+        return 1, rows + 1
+    return int(np.ceil(np.float32(cols) / np.float32(HASH_CELL))), int(np.ceil(np.float32(rows) / np.float32(HASH_CELL)))
+
+
+def hamming_nbins(mode, rows, cols):
+    nbx, nby = hamming_grid(mode, rows, cols)
+    return nbx * nby
+
+
+def hamming_lds_bytes(N, M, nbins):
+    """hamming_lds_bytes of k_hamming.hip: 42 N + 14 M (the u16 arrays rounded up to an even count) + 4 (nbins + 1) + 16"""
+    return N * 32 + N * 8 + M * 12 + (nbins + 1) * 4 + ((N + 1) & ~1) * 2 + ((M + 1) & ~1) * 2 + 16
+
+
+def hamming_lds_fits(N, M, nbins):
+    return hamming_lds_bytes(N, M, nbins) + HB_STATIC_LDS <= HB_LDS_MAX
+
+
+def hamming_instance(mode, r2, M, N):
+    """<MODE, NSP, QPT, TPT> of the launch"""
+    qpt, tpt = -(-M // HB_THREADS), -(-N // HB_THREADS)
+    if mode == 1:
+        return (1, 1, qpt, tpt)
+    csr = hamming_csr(r2)
+    return (0, {1: 3, 2: 5}.get(csr, 0), qpt, tpt)
+
+
+def hamming_admitted(mode, M, N, rows, cols):
+    """the entry launches: sizes within the caps and the LDS need within 160 KiB"""
+    return 0 < M <= HB_MMAX and 0 < N <= HB_NMAX and hamming_lds_fits(N, M, hamming_nbins(mode, rows, cols))
+
+
+def hamming_scan_chunk(nbins):
+    """entries per thread of the bin scan: 0 = one entry per thread (nbins + 1 <= HB_THREADS), else the chunked scan's ceil((nbins + 1) / HB_THREADS)"""
+    return 0 if nbins + 1 <= HB_THREADS else -(-(nbins + 1) // HB_THREADS)
+
+
+def _hamming_instance_table():
+    """per family and (QPT, TPT) class the smallest member (M, N) = (1024 (q - 1) + 1, 1024 (t - 1) + 1) and the largest one: M = 1024 q with N = 1024 t
+    lowered to the largest the LDS bound admits; where that N would leave the class (the bound is 42 N + 14 M: only at (3, 4)), N stays the smallest of
+    the class and M is lowered instead.  A class whose smallest member the bound refuses has no member at all."""
+    rows, cols = HAMMING_GEOMETRY
+    table = []
+    for fam, (mode, _, r2) in HAMMING_FAMILIES.items():
+        nb = hamming_nbins(mode, rows, cols)
+        fits = lambda M, N: hamming_lds_fits(N, M, nb)
+        for q in range(1, 5):
+            for t in range(1, 5):
+                m0, n0 = HB_THREADS * (q - 1) + 1, HB_THREADS * (t - 1) + 1
+                if not fits(m0, n0):
+                    continue
+                table.append((fam, q, t, "smallest", m0, n0))
+                m1 = HB_THREADS * q
+                if fits(m1, n0):
+                    n1 = max(n for n in range(n0, HB_THREADS * t + 1) if fits(m1, n))
+                else:
+                    n1 = n0
+                    m1 = max(m for m in range(m0, m1 + 1) if fits(m, n0))
+                table.append((fam, q, t, "largest", m1, n1))
+    return table
+
+
+HAMMING_INSTANCE_CASES = _hamming_instance_table()
+
+
+def hamming_window_counts(qxy, txy, tf, csr, rows, cols):
+    """(M, 2 csr + 1) int: unflagged train features in each row of a query's window of hash cells -- the kernel's candidate ranges (l_0 .. l_2csr).
+    Cells are floor(x / 25) in fp32, clamped into the grid for a feature, the window clipped to the grid for a query (struct.cpp:71-83)."""
+    nbx, nby = hamming_grid(0, rows, cols)
+    cell = lambda v: np.floor(v.astype(np.float32) / np.float32(HASH_CELL)).astype(np.int64)
+    keep = tf == 0
+    tcx, tcy = np.clip(cell(txy[keep, 0]), 0, nbx - 1), np.clip(cell(txy[keep, 1]), 0, nby - 1)
+    grid = np.zeros((nby, nbx + 1), np.int64)
+    np.add.at(grid, (tcy, tcx + 1), 1)
+    cum = np.cumsum(grid, axis=1)                                         # cum[y, x] = features of row y in cells < x
+    hx, hy = cell(qxy[:, 0]), cell(qxy[:, 1])
+    x0, x1 = np.maximum(hx - csr, 0), np.minimum(hx + csr, nbx - 1)
+    y0, y1 = np.maximum(hy - csr, 0), np.minimum(hy + csr, nby - 1)
+    out = np.zeros((len(qxy), 2 * csr + 1), np.int64)
+    for k in range(2 * csr + 1):
+        ok = (y0 + k <= y1) & (x0 <= x1)
+        yy = np.where(ok, y0 + k, 0)
+        out[:, k] = np.where(ok, cum[yy, np.where(ok, x1 + 1, 0)] - cum[yy, np.where(ok, x0, 0)], 0)
+    return out
+
+
+@functools.lru_cache(maxsize=4)
+def hamming_instance_problem(fam, M, N):
+    """the two problems of one case of test_every_instance: (qd, qxy, td, txy, tf), B = 2.
+    0: uniform integer features and a strip of graded density, about 15 % flagged, descriptors from 8 prototypes (ties resolve by the lowest index),
+       queries outside the image on all four sides;
+    1: half the features and queries in a dense 120 x 90 cluster (windows past 64 candidates, ranges past 63: the in-place match_all fallbacks); in row
+       mode fractional / out-of-range / NaN rows, which send this problem -- and not the other -- through the comparing walk."""
+    mode = HAMMING_FAMILIES[fam][0]
+    rows, cols = HAMMING_GEOMETRY
+    rng = np.random.default_rng([M, N, mode, HAMMING_FAMILIES[fam][1]])
+    B = 2
+    td = rng.integers(0, 256, (B, N, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (B, M, 32), dtype=np.uint8)
+    proto = rng.integers(0, 256, (8, 32), dtype=np.uint8)
+    td[0], qd[0] = proto[rng.integers(0, 8, N)], proto[rng.integers(0, 8, M)]
+    txy = np.floor(rng.uniform(0, 1, (B, N, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    qxy = (rng.uniform(0, 1, (B, M, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    outside = np.array([[-30.5, 100.25], [cols + 40.0, 100.0], [300.0, -30.5], [300.5, rows + 30.0], [-3.0, -3.0], [cols + 1.0, rows + 1.0],
+                        [cols - 0.5, rows - 0.5], [0.0, 0.0], [-200.0, 50.0], [cols + 200.0, 300.0], [600.0, -150.0], [600.0, rows + 150.0]], np.float32)
+    k = min(M, len(outside))
+    qxy[0, M - k:] = outside[:k]
+    ng, mg = N // 8, M // 4             # a strip whose density grows to the right: windows of every size up to the fallbacks'
+    txy[0, :ng] = np.floor(np.column_stack([700 + 250 * np.sqrt(rng.uniform(0, 1, ng)), 200 + 75 * rng.uniform(0, 1, ng)])).astype(np.float32)
+    qxy[0, :mg] = np.column_stack([rng.uniform(700, 950, mg), rng.uniform(200, 275, mg)]).astype(np.float32)
+    nc, mc = N // 2, M // 2
+    txy[1, :nc] = np.floor(rng.uniform(0, 1, (nc, 2)) * [120, 90] + [300, 100]).astype(np.float32)
+    qxy[1, :mc] = (rng.uniform(0, 1, (mc, 2)) * [120, 90] + [300, 100]).astype(np.float32)
+    if mode == 1 and N >= 8:
+        j = rng.permutation(N)
+        n8 = max(N // 8, 1)
+        txy[1, j[:n8], 1] += rng.uniform(0.01, 0.99, n8).astype(np.float32)                    # fractional
+        txy[1, j[n8:n8 + 3], 1] = np.array([-4.5, rows + 0.5, rows + 7.0], np.float32)         # above the image (bin 0), below it (last bin)
+        txy[1, j[n8 + 3], 1] = np.float32(np.nan)
+        txy[1, j[n8 + 4], 1] = np.float32(rows)                                                # the row `end_y` may reach
+    tf = (rng.uniform(0, 1, (B, N)) < 0.15).astype(np.uint8)
+    for a in (qd, qxy, td, txy, tf):
+        a.setflags(write=False)
+    return qd, qxy, td, txy, tf
+
+
+# -- the overflow bounds of the two-stage families: populations with an exact number of window candidates
+HAMMING_COUNT_KS = (31, 32, 33, 40, 41, 42, 63, 64, 65)      # the lo | hi mask words, MASK_BITS, the 6-bit range length and the two-word mask
+HAMMING_COUNT_GEOMETRY = (350, 1750)                          # 14 x 70 cells = 980 bins: the scan's one-entry-per-thread arm
+_COUNT_QUERY_OFFSETS = np.array([[0.0, 0.0], [2.0, -1.5], [-2.5, 1.0], [1.5, 2.5]])      # inside the centre cell; the first is the cell's centre
+_COUNT_MARGIN = 3.0                                           # a "robust" feature lies this far inside / outside the circle of EVERY query of its population
+
+
+def _count_rows(csr, k, layout):
+    """{window row j: features}: 'one' = all k in the centre row (one range); 'split' = over all 2 csr + 1 rows -- evenly below 63, and from 63 on one in
+    each outer row and the rest in the centre, so that a single range holds k - 2 csr (csr 1: 61 .. 64 for k = 63 .. 66)"""
+    if layout == "one":
+        return {0: k}
+    rows = list(range(-csr, csr + 1))
+    if k >= 63:
+        per = {j: 1 for j in rows}
+        per[0] = k - 2 * csr
+    else:
+        per = {j: k // len(rows) for j in rows}
+        per[0] += k - sum(per.values())
+    return per
+
+
+@functools.lru_cache(maxsize=4)
+def hamming_count_case(csr):
+    """test_candidate_count_bounds, radius 25 csr: B = 2 problems of the same populations (other descriptors, other positions drawn).  A population owns
+    the (2 csr + 1)^2 cells around its centre cell, two empty cells wide all round; its queries sit in the centre cell and see exactly k window
+    candidates, about half of them inside the circle, some at distance^2 == r2 exactly from the query at the cell's centre (coordinates are multiples of
+    0.5: every square and sum is exact in fp32).  The LAST populated cell of every window row holds one feature, inside the circle of all the population's
+    queries: the last candidate of a range is a hit whatever order a cell's features took.  Every feature has a query with its descriptor, one bit flipped.
+    Returns (qd, qxy, td, txy, tf, pops): pops = [(k, layout, {row: count}, query indices)]."""
+    rows_img, cols_img = HAMMING_COUNT_GEOMETRY
+    nbx, nby = hamming_grid(0, rows_img, cols_img)
+    r = 25.0 * csr
+    pitch = 2 * csr + 3
+    slots = [(csr + pitch * i, csr + pitch * j) for j in range((nby - 2 * csr - 1) // pitch + 1) for i in range((nbx - 2 * csr - 1) // pitch + 1)]
+    plan = [(k, "one") for k in HAMMING_COUNT_KS] + [(k, "split") for k in HAMMING_COUNT_KS + (66,)]
+    assert len(plan) <= len(slots)
+    exact = {(a * csr * s, b * csr * t) for a, b in ((25, 0), (0, 25), (7, 24), (24, 7), (15, 20), (20, 15)) for s in (1, -1) for t in (1, -1)}
+    out = []
+    for b in range(2):
+        rng = np.random.default_rng([csr, b, 77])
+        txy, qxy, owner = [], [], []
+        pops = []
+        for (k, layout), (cx, cy) in zip(plan, slots):
+            centre = np.array([cx * 25 + 12.5, cy * 25 + 12.5])
+            per = _count_rows(csr, k, layout)
+            first_q = len(qxy)
+            for j, n in per.items():
+                dx, dy = np.meshgrid(np.arange(-(r + 12), r + 12.5, 0.5), 25 * j + np.arange(-12, 12.5, 0.5))
+                dx, dy = dx.ravel(), dy.ravel()
+                d2 = dx * dx + dy * dy
+                col = np.floor((12.5 + dx) / 25)
+                rin, rout = d2 <= (r - _COUNT_MARGIN) ** 2, d2 >= (r + _COUNT_MARGIN) ** 2
+                ex = np.array([(x, y) in exact for x, y in zip(dx, dy)]) & (d2 == r * r)
+                cl = col[rin].max()
+                pick = [int(rng.choice(np.flatnonzero(rin & (col == cl))))]                     # the last cell's one feature
+                rest = n - 1
+                e = np.flatnonzero(ex & (col < cl))
+                e = rng.permutation(e)[:min(len(e), rest // 4)]
+                n_in = (rest - len(e)) // 2
+                pick += list(e) + list(rng.choice(np.flatnonzero(rin & (col < cl)), n_in, replace=False))
+                pick += list(rng.choice(np.flatnonzero(rout & (col < cl)), rest - len(e) - n_in, replace=False))
+                assert len(set(pick)) == n
+                for i in pick:
+                    txy.append(centre + [dx[i], dy[i]])
+                    qxy.append(centre + _COUNT_QUERY_OFFSETS[(len(qxy) - first_q) % 4])
+            pops.append((k, layout, per, np.arange(first_q, len(qxy))))
+        N = len(txy)
+        order = rng.permutation(N)                                                              # train index != construction order
+        td = rng.integers(0, 256, (N, 32), dtype=np.uint8)
+        qd = np.empty((N, 32), np.uint8)
+        t_arr = np.empty((N, 2), np.float32)
+        for i, slot in enumerate(order):
+            t_arr[slot] = txy[i]
+            qd[i] = td[slot]
+            qd[i, i % 32] ^= np.uint8(1 << (i % 8))
+        out.append((qd, np.array(qxy, np.float32), td, t_arr, np.zeros(N, np.uint8), pops))
+    assert [p[:3] for p in out[0][5]] == [p[:3] for p in out[1][5]]
+    stack = lambda i: np.stack([out[0][i], out[1][i]])
+    return stack(0), stack(1), stack(2), stack(3), stack(4), out[0][5]
+
+
+# -- the dispatch boundaries in r2
+_F32 = np.float32
+HAMMING_R2_BOUNDARIES = [(_F32(0.0), "csr1"), (_F32(1e-3), "csr1"), (_F32(625.0), "csr1"), (np.nextafter(_F32(625.0), _F32(np.inf)), "csr2"),
+                         (_F32(2500.0), "csr2"), (np.nextafter(_F32(2500.0), _F32(np.inf)), "any"), (_F32(40000.0), "any")]
+HAMMING_RING_OFFSETS = [(0, 0), (25, 0), (0, 25), (-25, 0), (0, -25), (7, 24), (-24, 7), (15, -20), (-20, -15),
+                        (50, 0), (0, -50), (14, 48), (-48, 14), (30, 40), (-40, -30)]
+HAMMING_RING_QUERIES = 60
+
+
+@functools.lru_cache(maxsize=1)
+def hamming_boundary_problem():
+    """one problem pair (M, N) = (600, 1200) on 1241 x 376 for every r2 of HAMMING_R2_BOUNDARIES: random integer features, and around each of the first 60
+    queries (at multiples of 0.5 px) one feature ON the query, eight at distance 25 exactly and six at 50 exactly (axes, 7-24-25, 15-20-25 and their
+    doubles): the strict `<` decides them while the family switches.  A ring feature's descriptor is its query's with 3, 6, 9 .. bits flipped in an order
+    drawn per query, so the record names exactly the accepted ones."""
+    rows, cols = HAMMING_GEOMETRY
+    B, M, N = 2, 600, 1200
+    rng = np.random.default_rng(2500)
+    td = rng.integers(0, 256, (B, N, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (B, M, 32), dtype=np.uint8)
+    txy = np.floor(rng.uniform(0, 1, (B, N, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    qxy = (rng.uniform(0, 1, (B, M, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    nr = len(HAMMING_RING_OFFSETS)
+    for b in range(B):
+        slots = rng.permutation(N)[:HAMMING_RING_QUERIES * nr].reshape(HAMMING_RING_QUERIES, nr)
+        for i in range(HAMMING_RING_QUERIES):
+            q = np.floor(rng.uniform([70, 70], [cols - 70, rows - 70]) * 2) / 2
+            qxy[b, i] = q
+            for rank, j in enumerate(rng.permutation(nr)):
+                txy[b, slots[i, j]] = q + HAMMING_RING_OFFSETS[j]
+                bits = np.zeros(256, np.uint8)
+                bits[rng.permutation(256)[:3 * (rank + 1)]] = 1
+                td[b, slots[i, j]] = qd[b, i] ^ np.packbits(bits)
+    tf = (rng.uniform(0, 1, (B, N)) < 0.05).astype(np.uint8)
+    return qd, qxy, td, txy, tf
+
+
+# -- the chunked bin scan
+HAMMING_CHUNKED_ROW = (1022, 1023, 1024, 2160)        # nbins + 1 = 1024 (the last size of the one-entry arm), 1025, 1026, 2162
+HAMMING_CHUNKED_GRID = ((1200, 4096, 625.0), (1000, 2600, 625.0), (1000, 2600, 2500.0), (1200, 4096, 5625.0))    # rows, cols, r2: 7 873 and 4 161 entries
+
+
+@functools.lru_cache(maxsize=2)
+def hamming_chunked_row_case(rows):
+    """row mode on an image of `rows` rows: 1 200 features over all rows 0 .. rows (every scan chunk populated; the first row, the last, and row `rows`
+    itself, which end_y may reach), 500 queries, 30 at either border.  Problem 0 keeps integer rows (the lean walk) and no flag, problem 1 has fractional
+    rows and a tenth of its features flagged."""
+    B, M, N = 2, 500, 1200
+    cols = 3840 if rows > 2000 else 1241
+    rng = np.random.default_rng(rows)
+    td = rng.integers(0, 256, (B, N, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (B, M, 32), dtype=np.uint8)
+    txy = np.floor(rng.uniform(0, 1, (B, N, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    qxy = (rng.uniform(0, 1, (B, M, 2)) * [cols - 1, rows]).astype(np.float32)
+    for b in range(B):
+        ys = np.concatenate([np.floor(np.arange(N - 6) * (rows + 1) / (N - 6)), [0, 0, rows, rows, rows - 1, 1]])
+        txy[b, :, 1] = rng.permutation(ys).astype(np.float32)
+        qxy[b, :30, 1] = rng.uniform(0, 4, 30).astype(np.float32)
+        qxy[b, 30:60, 1] = rng.uniform(rows - 4, rows + 3, 30).astype(np.float32)
+    txy[1, ::7, 1] += rng.uniform(0.01, 0.99, len(txy[1, ::7])).astype(np.float32)
+    tf = (rng.uniform(0, 1, (B, N)) < 0.1).astype(np.uint8)
+    tf[0] = 0                                              # (problem 0: every chunk keeps its feature)
+    return qd, qxy, td, txy, tf, cols
+
+
+@functools.lru_cache(maxsize=2)
+def hamming_chunked_grid_case(rows, cols):
+    """radius mode on a grid of more than 1 023 hash cells: one feature in every chunk of the scan (at a different place of the chunk from chunk to chunk),
+    more along the last cell column, the last cell row and the first column (a window at the end of a cell row must not run into the next row's first
+    cells); queries beside features and across all four image borders.  Sparse: about 1 400 features."""
+    nbx, nby = hamming_grid(0, rows, cols)
+    nbins = nbx * nby
+    chunk = hamming_scan_chunk(nbins)
+    assert chunk > 1 and (nbins + 1) % chunk != 0
+    B, M = 2, 700
+    rng = np.random.default_rng([rows, cols])
+    out_t, out_q = [], []
+    for b in range(B):
+        c = np.arange(-(-(nbins + 1) // chunk))
+        bins = np.minimum(c * chunk + (c + b) % chunk, nbins - 1)
+        pts = np.column_stack([bins % nbx, bins // nbx]) * 25.0 + rng.uniform(0.5, 24.5, (len(bins), 2))
+        extra = [np.column_stack([rng.uniform(cols - 30, cols - 0.5, 150), rng.uniform(0, rows - 1, 150)]),
+                 np.column_stack([rng.uniform(0, cols - 1, 100), rng.uniform(rows - 30, rows - 0.5, 100)]),
+                 np.column_stack([rng.uniform(0, 30, 100), rng.uniform(0, rows - 1, 100)]),
+                 rng.uniform(0, 1, (50, 2)) * [cols - 1, rows - 1]]
+        t = np.vstack([pts] + extra)
+        t = np.minimum(t, [cols - 0.25, rows - 0.25])
+        t = t[rng.permutation(len(t))]
+        near = t[rng.integers(0, len(t), 300)] + rng.uniform(-20, 20, (300, 2))
+        q = np.vstack([near,
+                       np.column_stack([rng.uniform(cols - 40, cols + 30, 100), rng.uniform(-10, rows + 10, 100)]),
+                       np.column_stack([rng.uniform(-10, cols + 10, 100), rng.uniform(rows - 40, rows + 30, 100)]),
+                       np.column_stack([rng.uniform(-30, 40, 100), rng.uniform(-10, rows + 10, 100)]),
+                       rng.uniform(0, 1, (100, 2)) * [cols - 1, rows - 1]])
+        out_t.append(t.astype(np.float32))
+        out_q.append(q.astype(np.float32))
+    txy, qxy = np.stack(out_t), np.stack(out_q)
+    N = txy.shape[1]
+    td = rng.integers(0, 256, (B, N, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (B, M, 32), dtype=np.uint8)
+    tf = (rng.uniform(0, 1, (B, N)) < 0.1).astype(np.uint8)
+    return qd, qxy, td, txy, tf
+
+
+# -- range starts of exactly 2048 in the packed family (N = 2048, no feature flagged)
+HAMMING_PACKED_LAYOUTS = ("behind", "tail", "control")
+
+
+@functools.lru_cache(maxsize=3)
+def hamming_packed_starts_case(layout):
+    """N = 2048 unflagged features on 1241 x 376 (50 x 16 cells), r2 = 625, M = 300, B = 2.
+    behind : every feature in cell rows 0 .. 3; 100 queries from cell row 6 down (all three range starts are 2048), 100 in cell rows 4 and 5 (the first
+             window row may still hold features), 100 among the features
+    tail   : cell rows 0 .. 4 full, and the last features in bin order in cells (5, 10 .. 12): 2 + 2 + 2 in problem 0 (even counts), 2 + 2 + 3 in problem 1
+             (odd); 100 queries in cell row 6 above them -- their first range ends at feature 2048, the two behind it start there -- the rest anywhere
+    control: `tail` with N = 2047"""
+    rows, cols = HAMMING_GEOMETRY
+    B, M = 2, 300
+    N = 2047 if layout == "control" else 2048
+    rng = np.random.default_rng(["behind", "tail", "control"].index(layout) + 2048)
+    td = rng.integers(0, 256, (B, N, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (B, M, 32), dtype=np.uint8)
+    txy = np.empty((B, N, 2), np.float32)
+    qxy = (rng.uniform(0, 1, (B, M, 2)) * [cols - 1, rows - 1]).astype(np.float32)
+    for b in range(B):
+        if layout == "behind":
+            txy[b] = rng.uniform([0, 0], [cols - 1, 99.5], (N, 2))
+            qxy[b, :100] = rng.uniform([0, 150], [cols - 1, rows + 20], (100, 2))
+            qxy[b, 100:200] = rng.uniform([0, 100], [cols - 1, 149.5], (100, 2))
+            qxy[b, 200:] = rng.uniform([0, 0], [cols - 1, 99.5], (100, 2))
+        else:
+            tail = [2, 2, 2 + b]
+            n_tail = sum(tail)
+            txy[b, :N - n_tail] = rng.uniform([0, 0], [cols - 1, 124.5], (N - n_tail, 2))
+            cells = np.repeat([10, 11, 12], tail)
+            txy[b, N - n_tail:] = np.column_stack([cells * 25 + rng.uniform(1, 24, n_tail), rng.uniform(140, 149.5, n_tail)])
+            txy[b] = txy[b, rng.permutation(N)]
+            qxy[b, :100] = np.column_stack([rng.uniform(265, 349, 100), rng.uniform(150, 174.5, 100)])
+    return qd, qxy, td, txy, np.zeros((B, N), np.uint8)
+
+
+# -- the constructed input of the 11-bit overflow: a phantom candidate that IS inside a circle
+def hamming_phantom_case():
+    """N = 2048 unflagged features, M = 1099, r2 = 625 on 1241 x 376: built so that the start fields' overflow, unguarded, changes a record.
+    Every feature lies in cell rows 0 .. 3 but two, in cell (4, 1).  Query Q = (3, 128) (the last but ten) has those two as its first range -- an even
+    length that ends at feature 2048 -- and nothing behind: starts 2048, 2048.  Packed into 11-bit fields the first of them turns length 2 into 3, and
+    the third candidate is LDS position 2048: s_xy[N], the slot words of query 0 read as coordinates (x, y).
+      x: word 0 = s0 | s1 << 11 | l0 << 22, a float with exponent field l0 >> 1 <= 31: below 1e-28, whatever query 0 is.
+      y: word 1 = s2 | l1 << 11 | l2 << 17 | hi << 23 once stage 4a has stored query 0's mask: exponent field = bits 32 .. 39 of the in-circle mask.
+    Query 0 = (262.5, 37.5) sees 40 window candidates in cell order (0,9) (0,10) (0,11) | (1,9) (1,10) (1,11) | (2,10): 20 | 13 outside its circle, 2
+    inside, 4 outside | 1 inside.  Candidates 32 .. 39 are out, in, in, out x 4, in whatever order each cell's features took: hi = 0b10000110 = 134,
+    y = 2^7 (1 + (19 << 11 | 1 << 17) / 2^23) = 130.6, inside Q's circle, where the reference has no candidate at all.
+    For Q to read the word AFTER query 0's mask is stored: 960 queries with 60 or more window candidates each (matched in place in stage 4a) fill the
+    first fifteen wavefronts of round 0, query 0 leads the sixteenth, followed by 127 queries of 30 candidates; Q is the 1089th in sorted order and
+    falls to round 1 of a wavefront that spent round 0 on descriptor walks.  (No barrier orders the two: the unguarded kernel gives the wrong record
+    when the wavefronts run as described, the right one otherwise.)
+    Returns (qd, qxy, td, txy, tf, info)."""
+    rows, cols = HAMMING_GEOMETRY
+    nbx, nby = hamming_grid(0, rows, cols)
+    rng = np.random.default_rng(134)
+    q0 = np.array([262.5, 37.5])
+    in_cell = lambda cy, cx, n: np.column_stack([cx * 25 + rng.uniform(1, 24, n), cy * 25 + rng.uniform(1, 24, n)])
+    feats = {}                                                     # (cy, cx) -> points
+    feats[(0, 9)], feats[(0, 10)], feats[(0, 11)] = in_cell(0, 9, 7), in_cell(0, 10, 7), in_cell(0, 11, 6)
+    feats[(1, 9)] = np.column_stack([rng.uniform(226, 236, 13), rng.uniform(26, 49, 13)])
+    feats[(1, 10)] = np.array([[262.0, 38.0], [263.0, 37.0]])
+    feats[(1, 11)] = np.column_stack([rng.uniform(290, 299, 4), rng.uniform(26, 49, 4)])
+    feats[(2, 10)] = np.array([[262.0, 52.0]])
+    feats[(2, 9)] = feats[(2, 11)] = np.zeros((0, 2))
+    spot2 = [(cy, cx) for cy in (0, 1, 2) for cx in (29, 30, 31)]
+    for (cy, cx), n in zip(spot2, (4, 3, 3, 4, 3, 3, 4, 3, 3)):
+        feats[(cy, cx)] = in_cell(cy, cx, n)
+    feats[(4, 1)] = np.array([[45.0, 101.0], [46.0, 102.0]])
+    dense = [(cy, cx) for cy in range(4) for cx in range(nbx) if (cy, cx) not in feats]
+    left = 2048 - sum(len(v) for v in feats.values())
+    base, more = divmod(left, len(dense))
+    for i, (cy, cx) in enumerate(dense):
+        feats[(cy, cx)] = in_cell(cy, cx, base + (i < more))
+    txy = np.vstack([feats[k] for k in sorted(feats)])
+    assert len(txy) == 2048
+    txy = txy[rng.permutation(2048)].astype(np.float32)
+    heavy_cols = [c for c in range(3, 47) if min(abs(c - 10), abs(c - 30)) > 3]
+    heavy = np.column_stack([rng.choice(heavy_cols, 960) * 25 + rng.uniform(1, 24, 960), rng.uniform(1, 74, 960)])
+    medium = np.column_stack([30 * 25 + rng.uniform(1, 24, 127), 25 + rng.uniform(1, 24, 127)])
+    Q = np.array([[3.0, 128.0]])
+    light = np.column_stack([rng.uniform(0, cols - 1, 10), rng.uniform(210, rows - 1, 10)])
+    qxy = np.vstack([q0[None], heavy, medium, Q, light]).astype(np.float32)
+    M = len(qxy)
+    td = rng.integers(0, 256, (2048, 32), dtype=np.uint8)
+    qd = rng.integers(0, 256, (M, 32), dtype=np.uint8)
+    info = dict(q0=0, heavy=np.arange(1, 961), medium=np.arange(961, 1088), Q=1088, light=np.arange(1089, M))
+    return qd[None], qxy[None], td[None], txy[None], np.zeros((1, 2048), np.uint8), info
+
+
+def hamming_packed_words(qxy, txy, rows, cols):
+    """the packed family's slot words of every query as stage 3 would store them WITHOUT a guard on the starts (N <= 2048, no flags), and the ranges:
+    (W0, W1, s (M, 3), l (M, 3)); W0 = 0xFFFFFFFF where a length reaches 64.  Bin order is (cell row, cell column); starts are counts of features in
+    earlier bins."""
+    nbx, nby = hamming_grid(0, rows, cols)
+    cell = lambda v: np.floor(v.astype(np.float32) / np.float32(HASH_CELL)).astype(np.int64)
+    tb = np.clip(cell(txy[:, 1]), 0, nby - 1) * nbx + np.clip(cell(txy[:, 0]), 0, nbx - 1)
+    start = np.concatenate([[0], np.cumsum(np.bincount(tb, minlength=nbx * nby))])
+    hx, hy = cell(qxy[:, 0]), cell(qxy[:, 1])
+    x0, x1 = np.maximum(hx - 1, 0), np.minimum(hx + 1, nbx - 1)
+    y0, y1 = np.maximum(hy - 1, 0), np.minimum(hy + 1, nby - 1)
+    s, l = np.zeros((len(qxy), 3), np.int64), np.zeros((len(qxy), 3), np.int64)
+    for k in range(3):
+        ok = (y0 + k <= y1) & (x0 <= x1)
+        row = np.where(ok, (y0 + k) * nbx, 0)
+        s[:, k] = start[row + np.where(ok, x0, 0)]
+        l[:, k] = start[row + np.where(ok, x1 + 1, 0)] - s[:, k]
+    fits = (l < 64).all(axis=1)
+    W0 = np.where(fits, (s[:, 0] | (s[:, 1] << 11) | (l[:, 0] << 22)) & 0xFFFFFFFF, 0xFFFFFFFF).astype(np.uint32)
+    W1 = ((s[:, 2] | (l[:, 1] << 11) | (l[:, 2] << 17)) & 0xFFFFFFFF).astype(np.uint32)
+    return W0, W1, s, l
+
+
+def hamming_count_check(csr):
+    """asserts that every query of hamming_count_case(csr) sees its population's counts range by range, and that about half of them lie inside the
+    circle; returns [(k, layout, longest range, features at distance^2 == r2 from the cell's centre)]"""
+    from hamming_util import radius_mask
+    rows, cols = HAMMING_COUNT_GEOMETRY
+    qd, qxy, td, txy, tf, pops = hamming_count_case(csr)
+    r2 = np.float32(625.0 * csr * csr)
+    stats = []
+    for b in range(2):
+        assert not tf[b].any()
+        wc = hamming_window_counts(qxy[b], txy[b], tf[b], csr, rows, cols)
+        inside = radius_mask(qxy[b], txy[b], r2)
+        for k, layout, per, qi in pops:
+            want = [per.get(j, 0) for j in range(-csr, csr + 1)]
+            assert sum(want) == k and (wc[qi] == want).all(), (csr, b, k, layout)
+            n_in = inside[qi].sum(axis=1)
+            assert (n_in >= k // 4).all() and (n_in <= k - k // 4).all(), (csr, b, k, layout, n_in.min(), n_in.max())
+            main = qi[::4][0]
+            d = txy[b] - qxy[b, main]
+            n_exact = int(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).astype(np.float32) == r2).sum())
+            if b == 0:
+                stats.append((k, layout, max(want), n_exact))
+    return stats

@@ -685,3 +685,218 @@ def test_oracle_motion_model_equals_the_longdouble_restatement(oracle_lib):
         assert ep <= 4 * np.finfo(np.float64).eps, f"{lab}: position differs by {ep:.3e} relative"
         assert abs(float((qo * qo).sum()) - 1) < 1e-15 and abs(float((nx[4:8] * nx[4:8]).sum()) - 1) < 1e-15, lab
     print(f"oracle vs longdouble: quaternions {worst_q:.3e}, positions {worst_p:.3e} relative")
+
+
+# ---- the batched Hamming matcher's instances and bounds (test_gpu_hamming_instances.py): the table and the constructed inputs, no GPU ---------------------
+from case_tables import (HAMMING_CHUNKED_GRID, HAMMING_CHUNKED_ROW, HAMMING_COUNT_GEOMETRY, HAMMING_COUNT_KS, HAMMING_FAMILIES, HAMMING_GEOMETRY,  # noqa: E402
+                         HAMMING_INSTANCE_CASES, HAMMING_PACKED_LAYOUTS, HAMMING_R2_BOUNDARIES, HAMMING_RING_OFFSETS, HAMMING_RING_QUERIES, HB_LDS_MAX,
+                         HB_MASK_BITS, HB_MMAX, HB_NMAX, HB_RANGE_MAX, HB_STATIC_LDS, HB_THREADS, HB_TWO_STAGE_MAX, hamming_admitted,
+                         hamming_boundary_problem, hamming_chunked_grid_case, hamming_chunked_row_case, hamming_count_case, hamming_count_check,
+                         hamming_csr, hamming_grid, hamming_instance, hamming_instance_problem, hamming_lds_bytes, hamming_nbins, hamming_packed_starts_case,
+                         hamming_packed_words, hamming_phantom_case, hamming_scan_chunk, hamming_window_counts)
+
+
+def test_hamming_table_reaches_every_admissible_instance():
+    """the table's instances are ALL the instances a launch can reach on its geometry: 4 families x 15 (QPT, TPT) classes; (4, 4) is out because its
+    smallest member, M = N = 3073, needs 42 N + 14 M = 172 088 bytes of LDS, more than a workgroup's 163 840 -- and for no other reason"""
+    rows, cols = HAMMING_GEOMETRY
+    reached = set()
+    for fam, q, t, member, M, N in HAMMING_INSTANCE_CASES:
+        mode, nsp, r2 = HAMMING_FAMILIES[fam]
+        assert hamming_admitted(mode, M, N, rows, cols), (fam, M, N)
+        assert hamming_instance(mode, r2, M, N) == (mode, nsp, q, t), (fam, M, N)
+        reached.add((mode, nsp, q, t))
+        if member == "smallest":
+            assert (M, N) == (HB_THREADS * (q - 1) + 1, HB_THREADS * (t - 1) + 1)
+        else:        # nothing larger in its class launches: M or N is at the class's end, or one more of it is refused
+            assert M == HB_THREADS * q or not hamming_admitted(mode, M + 1, N, rows, cols)
+            assert N == HB_THREADS * t or not hamming_admitted(mode, M, N + 1, rows, cols)
+            assert M == HB_THREADS * q or N == HB_THREADS * (t - 1) + 1
+    admissible = set()
+    for fam, (mode, nsp, r2) in HAMMING_FAMILIES.items():
+        for q in range(1, 5):
+            for t in range(1, 5):
+                if hamming_admitted(mode, HB_THREADS * (q - 1) + 1, HB_THREADS * (t - 1) + 1, rows, cols):      # the class's cheapest member
+                    admissible.add((mode, nsp, q, t))
+    assert reached == admissible and len(reached) == 60 and len(HAMMING_INSTANCE_CASES) == 120
+    assert {(1, 1), (0, 3), (0, 5), (0, 0)} == {i[:2] for i in reached}
+    for fam, (mode, nsp, r2) in HAMMING_FAMILIES.items():
+        assert (mode, nsp, 4, 4) not in reached
+        assert HB_MMAX >= 3073 and HB_NMAX >= 3073                                    # not the caps ...
+        assert hamming_lds_bytes(3073, 3073, 0) == 42 * 3074 + 14 * 3074 - 40 * 1 - 12 * 1 + 4 + 16 > HB_LDS_MAX   # ... the carve-up alone, without a single bin
+    assert [hamming_csr(HAMMING_FAMILIES[f][2]) for f in ("csr1", "csr2", "any")] == [1, 2, 3]
+    assert hamming_lds_bytes(1500, 1000, 800) == 42 * 1500 + 14 * 1000 + 4 * 801 + 16 and HB_STATIC_LDS == 128 + 256 + 4 + 12
+
+
+def test_hamming_instance_problems_take_their_branches():
+    """the largest member of every class: problem 1's cluster pushes windows past 64 candidates and ranges past 63 (the in-place fallbacks), problem 0
+    has windows the masks hold, flags, ties and queries outside the image; in row mode only problem 1 has rows that are no in-range integers"""
+    rows, cols = HAMMING_GEOMETRY
+    for fam, q, t, member, M, N in HAMMING_INSTANCE_CASES:
+        if member != "largest":
+            continue
+        mode, nsp, r2 = HAMMING_FAMILIES[fam]
+        qd, qxy, td, txy, tf = hamming_instance_problem(fam, M, N)
+        assert qd.shape == (2, M, 32) and td.shape == (2, N, 32) and 0.1 < tf.mean() < 0.2
+        assert len(np.unique(td[0], axis=0)) == 8 and len(np.unique(td[1], axis=0)) > N // 2
+        o = qxy[0]
+        assert (o[:, 0] < 0).any() and (o[:, 0] > cols).any() and (o[:, 1] < 0).any() and (o[:, 1] > rows).any()
+        if mode == 1:
+            is_row = lambda y: (y == np.floor(y)) & (y >= 0) & (y <= rows)
+            assert is_row(txy[0, :, 1]).all() and (~is_row(txy[1, tf[1] == 0, 1])).sum() >= 5 and np.isnan(txy[1, :, 1]).sum() == 1
+            continue
+        csr = hamming_csr(r2)
+        w0, w1 = (hamming_window_counts(qxy[b], txy[b], tf[b], csr, rows, cols) for b in (0, 1))
+        assert (w1.sum(axis=1) > HB_TWO_STAGE_MAX).sum() >= 10 and (w1.max(axis=1) > HB_RANGE_MAX).sum() >= 10, (fam, M, N)
+        w = np.vstack([w0, w1])
+        total = w.sum(axis=1)
+        if nsp == 3:       # both mask words, the in-place walk of a packed query (total past MASK_BITS), and of one whose ranges do not fit
+            fits = w.max(axis=1) <= HB_RANGE_MAX
+            assert (fits & (total <= 32)).sum() >= 10 and (fits & (total > 32) & (total <= HB_MASK_BITS)).sum() >= 3 and (fits & (total > HB_MASK_BITS)).sum() >= 3, (fam, M, N)
+        if nsp == 5:
+            assert (total <= 32).sum() >= 10 and ((total > 32) & (total <= HB_TWO_STAGE_MAX)).sum() >= 10, (fam, M, N)
+
+
+@pytest.mark.parametrize("csr", [1, 2])
+def test_hamming_count_populations_hold_their_counts(csr):
+    """binned with floor(x / 25) in fp32, every query of a population sees exactly its k window candidates, range by range"""
+    stats = hamming_count_check(csr)
+    ks = sorted({k for k, _, _, _ in stats})
+    assert ks == sorted(HAMMING_COUNT_KS + (66,)) and {31, 32, 33, 40, 41, 42, 63, 64, 65} <= set(ks)
+    assert {HB_MASK_BITS, HB_MASK_BITS + 1, HB_RANGE_MAX, HB_RANGE_MAX + 1, HB_TWO_STAGE_MAX, HB_TWO_STAGE_MAX + 1, 32, 33} <= set(ks)
+    if csr == 1:     # a single range of 63 and of 64, in either layout
+        longest = {(layout, longest) for _, layout, longest, _ in stats}
+        assert {("one", 63), ("one", 64), ("split", 63), ("split", 64)} <= longest
+    assert sum(n_exact for _, _, _, n_exact in stats) >= 20
+    assert hamming_nbins(0, *HAMMING_COUNT_GEOMETRY) + 1 <= HB_THREADS
+
+
+def test_hamming_boundary_problem_sits_on_the_circles():
+    """the r2 list switches the family where it says, and the ring features lie at distance^2 0, 625 and 2500 EXACTLY in fp32: accepted or rejected by
+    the strict comparison alone"""
+    from hamming_util import radius_mask
+    assert [f for _, f in HAMMING_R2_BOUNDARIES] == ["csr1", "csr1", "csr1", "csr2", "csr2", "any", "any"]
+    r2s = [r for r, _ in HAMMING_R2_BOUNDARIES]
+    assert all(r.dtype == np.float32 for r in r2s) and r2s[3] > np.float32(625) and r2s[3] - np.float32(625) < 1e-4 and r2s[5] - np.float32(2500) < 3e-4
+    for r2, fam in HAMMING_R2_BOUNDARIES:
+        assert hamming_instance(0, r2, 600, 1200)[:2] == HAMMING_FAMILIES[fam][:2]
+    assert [hamming_csr(r) for r in r2s] == [1, 1, 1, 2, 2, 3, 8]
+    qd, qxy, td, txy, tf = hamming_boundary_problem()
+    n25 = sum(1 for x, y in HAMMING_RING_OFFSETS if x * x + y * y == 625)
+    n50 = sum(1 for x, y in HAMMING_RING_OFFSETS if x * x + y * y == 2500)
+    assert (n25, n50, len(HAMMING_RING_OFFSETS)) == (8, 6, 15)
+    for b in range(2):
+        q, t = qxy[b, :HAMMING_RING_QUERIES], txy[b]
+        dx, dy = t[None, :, 0] - q[:, None, 0], t[None, :, 1] - q[:, None, 1]
+        d2 = (dx * dx + dy * dy).astype(np.float32)
+        assert d2.dtype == np.float32
+        assert ((d2 == 0).sum(axis=1) >= 1).all() and ((d2 == 625).sum(axis=1) >= n25).all() and ((d2 == 2500).sum(axis=1) >= n50).all()
+        # what the switch of the family must not change: 625 admits nothing new at distance 25, its successor admits all eight
+        m = [radius_mask(q, t, r) for r in r2s]
+        assert not (m[0] & (d2 == 0)).any() and (m[1] & (d2 == 0)).sum() >= HAMMING_RING_QUERIES
+        assert not (m[2] & (d2 == 625)).any() and ((m[3] & (d2 == 625)).sum(axis=1) >= n25).all()
+        assert not (m[4] & (d2 == 2500)).any() and ((m[5] & (d2 == 2500)).sum(axis=1) >= n50).all()
+
+
+def test_hamming_chunked_cases_fill_every_chunk():
+    """the sizes sit on either side of the scan's threshold, and every chunk of the chunked scan that holds a bin holds a feature"""
+    assert [hamming_scan_chunk(r + 1) for r in HAMMING_CHUNKED_ROW] == [0, 2, 2, 3]
+    assert [hamming_nbins(1, r, 0) + 1 for r in HAMMING_CHUNKED_ROW] == [1024, 1025, 1026, 2162]
+    for rows in HAMMING_CHUNKED_ROW:
+        qd, qxy, td, txy, tf, cols = hamming_chunked_row_case(rows)
+        chunk = max(hamming_scan_chunk(rows + 1), 1)
+        assert not tf[0].any() and 0.05 < tf[1].mean() < 0.15
+        for b in range(2):
+            y = txy[b, tf[b] == 0, 1]
+            if b == 0:
+                assert {0, 1, rows - 1, rows} <= set(y.tolist())
+                assert set(range(-(-(rows + 1) // chunk))) == set((y.astype(int) // chunk).tolist())
+            assert (qxy[b, :, 1] < 2).any() and (qxy[b, :, 1] > rows).any()
+        assert (txy[0, :, 1] == np.floor(txy[0, :, 1])).all() and (txy[1, :, 1] != np.floor(txy[1, :, 1])).sum() > 100
+        assert hamming_admitted(1, qd.shape[1], td.shape[1], rows, cols)
+    assert {(r, c) for r, c, _ in HAMMING_CHUNKED_GRID} == {(1200, 4096), (1000, 2600)}
+    assert [HAMMING_FAMILIES[f][1] for f in ("csr1", "csr2", "any")] == [3, 5, 0]
+    assert sorted({hamming_instance(0, r2, 700, 1300)[1] for _, _, r2 in HAMMING_CHUNKED_GRID}) == [0, 3, 5]
+    for rows, cols in ((1200, 4096), (1000, 2600)):
+        nbx, nby = hamming_grid(0, rows, cols)
+        nbins = nbx * nby
+        chunk = hamming_scan_chunk(nbins)
+        assert (nbx, nby) in ((164, 48), (104, 40)) and chunk in (8, 5) and (nbins + 1) % chunk == 1
+        qd, qxy, td, txy, tf = hamming_chunked_grid_case(rows, cols)
+        assert 1000 < td.shape[1] <= 1500 and hamming_admitted(0, qd.shape[1], td.shape[1], rows, cols)
+        for b in range(2):
+            t = txy[b]
+            bins = np.floor(t[:, 1] / np.float32(25)).astype(int) * nbx + np.floor(t[:, 0] / np.float32(25)).astype(int)
+            assert bins.min() >= 0 and bins.max() == nbins - 1
+            assert set(range(-(-nbins // chunk))) == set((bins // chunk).tolist())              # (flagged or not: the scan adds every chunk's counts)
+            assert len({int(x) % chunk for x in bins}) == chunk                                 # ... at every place inside a chunk
+            last_col = np.floor(qxy[b, :, 0] / np.float32(25)) >= nbx - 2
+            assert last_col.sum() >= 50 and (qxy[b, :, 0] > cols).any() and (qxy[b, :, 1] > rows).any() and (qxy[b] < 0).any()
+            w = hamming_window_counts(qxy[b], txy[b], tf[b], 1, rows, cols)
+            assert (w[last_col].sum(axis=1) > 0).sum() >= 30                                    # windows at the end of a cell row that hold candidates
+
+
+def test_hamming_packed_start_layouts_reach_2048():
+    """without a flag and with N = 2048 the layouts hold queries whose range starts ARE 2048: all three (`behind`), or the two behind a first range that
+    ends at the last feature, of even length in problem 0 and odd in problem 1 (`tail`); the control has none"""
+    rows, cols = HAMMING_GEOMETRY
+    assert HAMMING_PACKED_LAYOUTS == ("behind", "tail", "control")
+    for layout in HAMMING_PACKED_LAYOUTS:
+        qd, qxy, td, txy, tf = hamming_packed_starts_case(layout)
+        assert not tf.any() and td.shape[1] == (2047 if layout == "control" else 2048) and hamming_instance(0, 625.0, qd.shape[1], td.shape[1]) == (0, 3, 1, 2)
+        for b in range(2):
+            W0, W1, s, l = hamming_packed_words(qxy[b], txy[b], rows, cols)
+            packed = W0 != 0xFFFFFFFF
+            if layout == "control":
+                assert s.max() == 2047
+                continue
+            if layout == "behind":
+                assert (packed & (s == 2048).all(axis=1)).sum() >= 100
+                assert (packed & (s[:, 0] < 2048) & (l[:, 0] > 0) & (s[:, 1] == 2048)).sum() >= 10
+            else:
+                at_end = packed[:100] & (s[:100, 0] + l[:100, 0] == 2048) & (l[:100, 0] > 0) & (s[:100, 1] == 2048) & (s[:100, 2] == 2048)
+                assert at_end.sum() >= 60
+                assert set((l[:100, 0][at_end] % 2).tolist()) == {b}
+            # what the 11-bit fields make of such a start: the decoded ranges differ from the true ones
+            dec_l0 = W0[packed] >> 22
+            assert (dec_l0 != l[packed, 0]).any() or (((W1[packed] >> 11) & 63) != l[packed, 1]).any()
+
+
+def test_hamming_phantom_case_decodes_inside_a_circle():
+    """the slot words of the constructed input, modelled: query 0's words, read as coordinates once its mask is stored, lie inside Q's circle; Q's first
+    range ends at feature 2048 with an even length and the starts behind it are 2048; the sorted order puts query 0 at slot 960 and Q at slot 1088"""
+    rows, cols = HAMMING_GEOMETRY
+    qd, qxy, td, txy, tf, info = hamming_phantom_case()
+    qxy, txy = qxy[0], txy[0]
+    assert txy.shape == (2048, 2) and not tf.any() and hamming_instance(0, 625.0, len(qxy), 2048) == (0, 3, 2, 2)
+    W0, W1, s, l = hamming_packed_words(qxy, txy, rows, cols)
+    Q = info["Q"]
+    assert s[Q].tolist() == [2046, 2048, 2048] and l[Q].tolist() == [2, 0, 0] and W0[Q] != 0xFFFFFFFF
+    assert (int(W0[Q]) >> 22, int(W0[Q]) & 2047) == (3, 2046)                           # decoded: one candidate more, at position 2046 + 2 = N
+    assert s[0].max() < 2048 and l[0].tolist() == [20, 19, 1]
+    # query 0's candidates in flattened order, cell by cell; inside a cell the order is the scatter's, so a cell must be all in or all out
+    from hamming_util import radius_mask
+    nbx = hamming_grid(0, rows, cols)[0]
+    cell = np.floor(txy[:, 1] / np.float32(25)).astype(int) * nbx + np.floor(txy[:, 0] / np.float32(25)).astype(int)
+    inside = radius_mask(qxy[:1], txy, 625.0)[0]
+    bits = []
+    for cy, cx in [(0, 9), (0, 10), (0, 11), (1, 9), (1, 10), (1, 11), (2, 9), (2, 10), (2, 11)]:
+        k = np.flatnonzero(cell == cy * nbx + cx)
+        if cy > 0:
+            assert len(set(inside[k].tolist())) <= 1
+        bits += inside[k].tolist()
+    assert len(bits) == 40 <= HB_MASK_BITS
+    hi = sum(int(v) << i for i, v in enumerate(bits[32:]))
+    assert hi == 0b10000110
+    W1_after = (int(W1[0]) & 0x7FFFFF) | (hi << 23)
+    phantom = np.array([W0[0], W1_after], np.uint32).view(np.float32)
+    assert 0 <= phantom[0] < 1e-28 and 130.0 < phantom[1] < 131.0
+    assert radius_mask(qxy[Q:Q + 1], phantom[None, :], 625.0)[0, 0] and not radius_mask(qxy[Q:Q + 1], txy, 625.0).any()
+    # the order of stage 4a: classes by min(window candidates, 63), heaviest first
+    total = l.sum(axis=1)
+    assert (total[info["heavy"]] > 41).all() and len(info["heavy"]) == 960 and (total[info["medium"]] == 30).all() and len(info["medium"]) == 127
+    assert total[0] == 40 and total[Q] == 2 and (total[info["light"]] == 0).all()
+    assert (total > total[0]).sum() == 960 and (total > total[Q]).sum() == 1088 >= HB_THREADS + 64
+    # no other query's own words are touched by a start of 2048, except the ten far below (their extra candidates are features of rows 0: out of reach)
+    others = np.concatenate([info["heavy"], info["medium"]])
+    assert s[others].max() < 2048

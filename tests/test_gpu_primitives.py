@@ -4,6 +4,7 @@ import pytest
 
 from case_tables import (PNP_EDGE_COUNTS, PNP_HARD, PNP_HARD_UNSTAGED, PNP_INTRINSICS, PNP_STAGE_MAX, pnp_case as _pnp_case,
                          pnp_edge_case, pnp_hard_case as _pnp_hard_case, pnp_prior_cases, trace_noise)
+from hamming_util import NO_NEIGHBOUR, problem_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -194,15 +195,9 @@ def _hamming_ref(O, qd, qxy, td, txy, tf, r2, mode, rows, cols):
     B, M = qd.shape[:2]
     out = np.zeros((B, M, 4), np.int32)
     for b in range(B):
+        mask = problem_mask(qxy[b], txy[b], tf[b], r2, mode, rows).astype(np.uint8)
         for m in range(M):
-            if mode == 0:
-                d = txy[b] - qxy[b, m]
-                mask = (tf[b] == 0) & ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).astype(np.float32) < np.float32(r2))
-            else:
-                y = qxy[b, m, 1]
-                s = max(int(y) - 2, 0); e = min(int(y) + 2, rows)
-                mask = (tf[b] == 0) & (txy[b, :, 1] >= s) & (txy[b, :, 1] <= e)
-            out[b, m] = O.hamming_top2(qd[b, m], td[b], mask.astype(np.uint8))
+            out[b, m] = O.hamming_top2(qd[b, m], td[b], mask[m])
     return out
 
 
@@ -242,34 +237,25 @@ def test_hamming_match_batched(hip_lib, oracle_lib, mode, variant):
 
 def _hamming_ref_np(qd, qxy, td, txy, tf, r2, mode, rows):
     """vectorised restatement of the same semantics (masked top-2, ties -> lowest index) for sizes the scalar oracle loop
-    would take minutes on; checked against the oracle on the small cases above by construction of the same masks"""
+    would take minutes on; checked against the oracle on the small cases above by construction of the same masks (hamming_util.py, which
+    also holds the cheap reference of the sizes this one's (M, N, 32) table cannot reach: test_hamming_reference.py holds the two together)"""
     B, M = qd.shape[:2]
     N = td.shape[1]
     out = np.zeros((B, M, 4), np.int32)
     pop = np.array([bin(i).count("1") for i in range(256)], np.int32)
     for b in range(B):
         d = pop[qd[b][:, None, :] ^ td[b][None, :, :]].sum(axis=2).astype(np.int64)      # (M, N)
-        if mode == 0:
-            dx = (txy[b][None, :, 0] - qxy[b][:, None, 0]).astype(np.float32)
-            dy = (txy[b][None, :, 1] - qxy[b][:, None, 1]).astype(np.float32)
-            mask = ((dx * dx).astype(np.float32) + (dy * dy).astype(np.float32)).astype(np.float32) < np.float32(r2)
-        else:
-            y = qxy[b][:, 1]
-            s = np.maximum(y.astype(np.int64) - 2, 0)[:, None]
-            e = np.minimum(y.astype(np.int64) + 2, rows)[:, None]
-            ty = txy[b][None, :, 1]
-            mask = (ty >= s) & (ty <= e)
-        mask &= (tf[b] == 0)[None, :]
+        mask = problem_mask(qxy[b], txy[b], tf[b], r2, mode, rows)
         key = np.where(mask, d * 65536 + np.arange(N)[None, :], np.int64(1) << 40)
         key = np.concatenate([key, np.full((M, 2), np.int64(1) << 40)], axis=1)   # (a single train feature still has a "second")
         order = np.argsort(key, axis=1, kind="stable")[:, :2]
         k1 = np.take_along_axis(key, order[:, :1], 1)[:, 0]
         k2 = np.take_along_axis(key, order[:, 1:2], 1)[:, 0]
         big = np.int64(1) << 40
-        out[b, :, 0] = np.where(k1 < big, k1 % 65536, -1)
-        out[b, :, 1] = np.where(k1 < big, k1 // 65536, 0x7FFFFFFF)
-        out[b, :, 2] = np.where(k2 < big, k2 % 65536, -1)
-        out[b, :, 3] = np.where(k2 < big, k2 // 65536, 0x7FFFFFFF)
+        out[b, :, 0] = np.where(k1 < big, k1 % 65536, NO_NEIGHBOUR[0])
+        out[b, :, 1] = np.where(k1 < big, k1 // 65536, NO_NEIGHBOUR[1])
+        out[b, :, 2] = np.where(k2 < big, k2 % 65536, NO_NEIGHBOUR[0])
+        out[b, :, 3] = np.where(k2 < big, k2 // 65536, NO_NEIGHBOUR[1])
     return out
 
 
