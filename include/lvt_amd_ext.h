@@ -334,6 +334,52 @@ LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format);                 
 LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format);  /* 0 / -1 */
 LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq);                    /* format, -1: bad handle / seq */
 
+/* ---- SNAPSHOTS: one sequence's state saved, restored, moved between handles and seats -------------------------------------------------
+ * A tracker's state lives in HBM: its control record, the local map, the staged points and the motion model.  A snapshot is a copy of it, device-resident and
+ * owned by the library: ONE contiguous allocation (header | control record | the live map and staged arrays, the first map_n / staged_n points in storage
+ * order), gathered by one kernel launch (k_state_pack) and scattered back by one (k_state_unpack).  Its exported form is the same bytes, headed by magic,
+ * version, the sizes and capacities of the build, sensor type, the sequence's lvt_amd_params, point counts, section offsets, total size and a 64-bit checksum
+ * of everything behind the header.  The words of the control record that belong to a launch chain, not to the tracker (stream hand-over sequence numbers, gate
+ * counters, debug stamps), are zero in a snapshot: two snapshots of one state export identical bytes whatever route the frames took, and a snapshot taken
+ * right after an apply exports the bytes that were applied.  `seq` is 0 for a solo handle.
+ *  - take: drains the handle as the introspection calls do; the snapshot is the state after the last frame enqueued; the source is untouched and goes on
+ *    tracking.  Allowed in every state: NOT_INITIALIZED (an empty map), TRACKING, LOST.  The batch call takes every sequence with ONE drain and ONE launch
+ *    (16 sequences per launch), out[s] = sequence s.
+ *  - apply: replaces the WHOLE state of the target sequence; the next frame handed in continues the snapshot's trajectory as if the source had tracked it, bit
+ *    for bit.  lvt_amd_get_pose, lvt_amd_get_counts, lvt_get_status, lvt_amd_get_map, lvt_amd_get_staged and lvt_amd_batch_get_counts answer from the snapshot
+ *    as soon as apply returns.  The other per-frame read-backs (features, matches, row matches, planes) stay those of the TARGET's own last frame -- their
+ *    buffers are per-frame scratch, not state -- and speak of the snapshot's trajectory from the next frame on.  A snapshot may be applied any number of times
+ *    (a clone) and stays valid until it is destroyed.  The batch call applies s[i] to sequence i, NULL = leave alone.  A successful apply counts as use of an
+ *    lvt_create handle.
+ *  - export / import: the route to a file, another process or another device.  export copies the blob to host memory and writes the checksum (the bytes
+ *    written, -1: cap is too small; lvt_amd_snapshot_get_info says how many are needed); import checks the bytes and uploads them to `device`
+ *    (-1: the current one).  lvt_amd_snapshot_describe does the checks alone: host code, no GPU needed.
+ *  - lvt_amd_batch_reset: lvt_system::reset for ONE sequence of a lock-step batch (lvt_amd_reset on a batch handle resets them all); drains first.
+ *  - refused (-1 or NULL, nothing changed, the reason in lvt_amd_last_error; a batch names the sequence): seq out of range (a solo handle: seq != 0); a batch
+ *    call on a solo handle; apply of a snapshot whose lvt_amd_params differ from the target sequence's (compared byte for byte, as the pool compares them), of
+ *    another sensor type, or living on another device (between devices: export, then import); apply with frames in flight (apply after every frame has been
+ *    collected); pooled and automatic seats, both ways; import or describe of bytes that are too short or have a wrong magic, version, recorded record size,
+ *    capacities, section offsets or checksum -- those two have no handle: lvt_amd_last_error(NULL) gives the reason of the calling thread's last refusal.
+ *  - out of scope: pooled and automatic seats (moving a tracked handle into the pool needs the pool's quiesce and its per-seat host records); a reset or
+ *    restore without draining the pipeline; applying across different parameters or capacities.
+ *  - lvt_amd_profile_read reports the launches as "k_state_pack" / "k_state_unpack" (time between HIP events on the handle's stream). */
+typedef void *lvt_amd_snapshot;            /* one sequence's state, device-resident, owned by the library */
+typedef struct lvt_amd_snapshot_info {     /* all int / long long, no padding surprises */
+    int version, sensor_type, state, frame_number, map_n, staged_n, src_map_cur, src_staged_cur, device;   /* device: -1 from lvt_amd_snapshot_describe */
+    long long bytes;                       /* size of the exported form */
+} lvt_amd_snapshot_info;
+LVT_API lvt_amd_snapshot lvt_amd_snapshot_take(lvt_handle h, int seq);                         /* NULL on refusal */
+LVT_API int lvt_amd_snapshot_apply(lvt_handle h, int seq, lvt_amd_snapshot s);                 /* 0 / -1 */
+LVT_API int lvt_amd_batch_snapshot_take(lvt_handle h, lvt_amd_snapshot *out /* [B] */);        /* 0 / -1 */
+LVT_API int lvt_amd_batch_snapshot_apply(lvt_handle h, const lvt_amd_snapshot *s /* [B], NULL = leave alone */);
+LVT_API int lvt_amd_snapshot_get_info(lvt_amd_snapshot s, lvt_amd_snapshot_info *out);         /* 0 / -1 */
+LVT_API int lvt_amd_snapshot_get_params(lvt_amd_snapshot s, lvt_amd_params *out);              /* 0 / -1 */
+LVT_API long long lvt_amd_snapshot_export(lvt_amd_snapshot s, void *host_buf, long long cap);  /* bytes written, -1 */
+LVT_API lvt_amd_snapshot lvt_amd_snapshot_import(const void *bytes, long long n, int device /* -1: current */);
+LVT_API int lvt_amd_snapshot_describe(const void *bytes, long long n, lvt_amd_snapshot_info *out, lvt_amd_params *p);  /* 0 / -1 */
+LVT_API void lvt_amd_snapshot_destroy(lvt_amd_snapshot s);
+LVT_API int lvt_amd_batch_reset(lvt_handle h, int seq);                                        /* 0 / -1 */
+
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without
  * ROS: poses are re-expressed in an x-forward / z-up frame (rot_fix = Rz(-pi/2) Rx(-pi/2)), the frame-to-frame delta is moved

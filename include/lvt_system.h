@@ -247,6 +247,28 @@ class lvt_system {
         delete s;
     }
     void reset() { lvt_amd_reset(m_handle); m_state = -1; } /* lvt_system.cpp:44-68 */
+    /* snapshots (lvt_amd_snapshot_*, include/lvt_amd_ext.h).  save_state(): the state after the last frame handed in, as bytes -- a checkpoint file, another
+     * process, another device; this system goes on tracking; empty when refused.  load_state(): replaces this system's WHOLE state by the bytes': the next
+     * track() continues their trajectory.  false when refused -- other parameters or sensor type, damaged bytes, frames in flight -- and then nothing has
+     * changed (last_error(), or lvt_amd_last_error(NULL) for bytes that are no snapshot). */
+    std::vector<unsigned char> save_state() {
+        std::vector<unsigned char> out;
+        lvt_amd_snapshot s = lvt_amd_snapshot_take(m_handle, 0);
+        lvt_amd_snapshot_info info;
+        if (s && lvt_amd_snapshot_get_info(s, &info) == 0) {
+            out.resize((size_t)info.bytes);
+            if (lvt_amd_snapshot_export(s, out.data(), info.bytes) != info.bytes) out.clear();
+        }
+        lvt_amd_snapshot_destroy(s);
+        return out;
+    }
+    bool load_state(const std::vector<unsigned char> &bytes) {
+        lvt_amd_snapshot s = lvt_amd_snapshot_import(bytes.data(), (long long)bytes.size(), lvt_amd_get_device(m_handle));
+        const bool ok = s && lvt_amd_snapshot_apply(m_handle, 0, s) == 0;
+        lvt_amd_snapshot_destroy(s);
+        if (ok) m_state = -1;
+        return ok;
+    }
 
     /* stereo: two rectified 8-bit gray images -- or the camera's RAW images, once a pair of rectifiers has been attached with
      * lvt_amd_set_rectifiers(native_handle(), left, right) (include/lvt_amd_ext.h); RGB-D: gray + 32-bit float depth in metres (lvt_system.cpp:157-207).

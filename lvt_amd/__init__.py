@@ -40,6 +40,9 @@ ABI_SYMBOLS = [
     "lvt_amd_set_rectifiers", "lvt_amd_batch_set_rectifiers",
     "lvt_amd_set_pixel_format", "lvt_amd_batch_set_pixel_format", "lvt_amd_get_pixel_format",
     "lvt_amd_motion_predict",
+    "lvt_amd_snapshot_take", "lvt_amd_snapshot_apply", "lvt_amd_batch_snapshot_take", "lvt_amd_batch_snapshot_apply", "lvt_amd_snapshot_get_info",
+    "lvt_amd_snapshot_get_params", "lvt_amd_snapshot_export", "lvt_amd_snapshot_import", "lvt_amd_snapshot_describe", "lvt_amd_snapshot_destroy",
+    "lvt_amd_batch_reset",
 ]
 
 N_COUNTS = 32
@@ -174,6 +177,16 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes, restype in (   # (snapshots: likewise)
+            ("lvt_amd_snapshot_take", [vp, C.c_int], vp), ("lvt_amd_snapshot_apply", [vp, C.c_int, vp], C.c_int),
+            ("lvt_amd_batch_snapshot_take", [vp, vp], C.c_int), ("lvt_amd_batch_snapshot_apply", [vp, vp], C.c_int),
+            ("lvt_amd_snapshot_get_info", [vp, vp], C.c_int), ("lvt_amd_snapshot_get_params", [vp, vp], C.c_int),
+            ("lvt_amd_snapshot_export", [vp, vp, C.c_longlong], C.c_longlong), ("lvt_amd_snapshot_import", [vp, C.c_longlong, C.c_int], vp),
+            ("lvt_amd_snapshot_describe", [vp, C.c_longlong, vp, vp], C.c_int), ("lvt_amd_snapshot_destroy", [vp], None),
+            ("lvt_amd_batch_reset", [vp, C.c_int], C.c_int)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -193,6 +206,80 @@ def _u8(img, bpp=1):
     elif a.ndim != 3 or a.shape[2] != bpp:
         raise ValueError(f"an image of shape {a.shape} on a handle whose pixel format has {bpp} bytes per pixel: expected (H, W, {bpp})")
     return a
+
+
+class SnapshotInfo(C.Structure):
+    """lvt_amd_snapshot_info"""
+    _fields_ = [(n, C.c_int) for n in ("version", "sensor_type", "state", "frame_number", "map_n", "staged_n", "src_map_cur", "src_staged_cur", "device")] + \
+               [("bytes", C.c_longlong)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def _params_of(pod):
+    return LvtParameters(**{n: getattr(pod, n) for n, _ in ParamsPOD._fields_ if n in LvtParameters.__dataclass_fields__})
+
+
+class Snapshot:
+    """One sequence's tracker state (control record, map, staged points, motion model), device-resident and owned by the library (lvt_amd_snapshot_*):
+    taken from a system or a batch sequence, applied to any number of them, exported to bytes and imported again -- on another device, in another process."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def info(self) -> dict:
+        """version, sensor_type, state, frame_number, map_n, staged_n, src_map_cur, src_staged_cur, device, bytes (the size of to_bytes())"""
+        i = SnapshotInfo()
+        if load_library().lvt_amd_snapshot_get_info(self._h, C.byref(i)) != 0:
+            raise RuntimeError("lvt_amd_snapshot_get_info failed")
+        return i.as_dict()
+
+    @property
+    def params(self) -> LvtParameters:
+        pod = ParamsPOD()
+        if load_library().lvt_amd_snapshot_get_params(self._h, C.byref(pod)) != 0:
+            raise RuntimeError("lvt_amd_snapshot_get_params failed")
+        return _params_of(pod)
+
+    def to_bytes(self) -> bytes:
+        n = self.info["bytes"]
+        buf = np.zeros(n, np.uint8)
+        if load_library().lvt_amd_snapshot_export(self._h, _p(buf), n) != n:
+            raise RuntimeError("lvt_amd_snapshot_export failed")
+        return buf.tobytes()
+
+    @classmethod
+    def from_bytes(cls, b, device: int = -1) -> "Snapshot":
+        """the snapshot these bytes hold, uploaded to `device` (-1: the current one); ValueError with the reason when they are refused"""
+        L = load_library()
+        a = np.frombuffer(bytes(b), np.uint8)
+        h = L.lvt_amd_snapshot_import(_p(a) if a.size else None, a.size, device)
+        if not h:
+            raise ValueError(L.lvt_amd_last_error(None).decode())
+        return cls(h)
+
+    @staticmethod
+    def describe(b):
+        """(info dict, LvtParameters) of exported bytes -- host code, no GPU needed; ValueError with the reason when they are no snapshot"""
+        L = load_library()
+        a = np.frombuffer(bytes(b), np.uint8)
+        i, pod = SnapshotInfo(), ParamsPOD()
+        if L.lvt_amd_snapshot_describe(_p(a) if a.size else None, a.size, C.byref(i), C.byref(pod)) != 0:
+            raise ValueError(L.lvt_amd_last_error(None).decode())
+        return i.as_dict(), _params_of(pod)
+
+    def close(self):
+        if self._h:
+            load_library().lvt_amd_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 class LvtSystem:
@@ -244,6 +331,17 @@ class LvtSystem:
 
     def reset(self):
         load_library().lvt_amd_reset(self._h)
+
+    def snapshot(self) -> Snapshot:
+        """the state after the last frame handed in (drains first); this system goes on tracking.  RuntimeError with the reason when refused"""
+        h = load_library().lvt_amd_snapshot_take(self._h, 0)
+        if not h:
+            raise RuntimeError(self.last_error() or "lvt_amd_snapshot_take failed")
+        return Snapshot(h)
+
+    def restore(self, snap: Snapshot) -> int:
+        """replace this system's whole state by the snapshot's: the next frame continues the snapshot's trajectory.  0: done; -1: refused (last_error())"""
+        return load_library().lvt_amd_snapshot_apply(self._h, 0, snap._h if snap is not None else None)
 
     def get_sensor_type(self):
         return self._sensor
@@ -537,7 +635,35 @@ class LvtBatch:
         pod = ParamsPOD()
         if not load_library().lvt_amd_batch_get_params(self._h, seq, C.byref(pod)):
             raise IndexError(f"no sequence {seq} in this batch")
-        return LvtParameters(**{n: getattr(pod, n) for n, _ in ParamsPOD._fields_ if n in LvtParameters.__dataclass_fields__})
+        return _params_of(pod)
+
+    def snapshot(self, seq: int = None):
+        """the state of sequence `seq` -- or, None, of every sequence through one drain and one launch: a list.  RuntimeError with the reason when refused"""
+        L = load_library()
+        if seq is not None:
+            h = L.lvt_amd_snapshot_take(self._h, int(seq))
+            if not h:
+                raise RuntimeError(self.last_error() or "lvt_amd_snapshot_take failed")
+            return Snapshot(h)
+        out = (C.c_void_p * self.B)()
+        if L.lvt_amd_batch_snapshot_take(self._h, out) != 0:
+            raise RuntimeError(self.last_error() or "lvt_amd_batch_snapshot_take failed")
+        return [Snapshot(out[s]) for s in range(self.B)]
+
+    def restore(self, seq: int, snap: Snapshot) -> int:
+        """LvtSystem.restore for sequence `seq`; the other sequences are untouched.  0: done; -1: refused (last_error())"""
+        return load_library().lvt_amd_snapshot_apply(self._h, int(seq), snap._h if snap is not None else None)
+
+    def restore_all(self, snaps) -> int:
+        """one snapshot per sequence (None: leave that sequence alone) through one launch.  0: done; -1: refused, nothing changed (last_error())"""
+        if len(snaps) != self.B:
+            raise ValueError("one entry per sequence")
+        arr = (C.c_void_p * self.B)(*[None if x is None else x._h for x in snaps])
+        return load_library().lvt_amd_batch_snapshot_apply(self._h, arr)
+
+    def reset(self, seq: int) -> int:
+        """lvt_system::reset for sequence `seq` alone (drains first).  0: done; -1: refused (last_error())"""
+        return load_library().lvt_amd_batch_reset(self._h, int(seq))
 
     def wait(self):
         R = np.zeros((self.B, 3, 3)); t = np.zeros((self.B, 3)); st = np.zeros(self.B, np.int32)

@@ -19,6 +19,7 @@
 #include "k_hamming.hip"
 #include "k_lists.hip"
 #include "k_rectify.hip"
+#include "k_state.hip"
 #include "lvt_odometry.h"
 
 #include <atomic>
@@ -124,6 +125,8 @@ static void launch_stage_copy(hipStream_t st, const uint8_t *src, float *d_dst, 
 // Counted PER DEVICE: handles on different GPUs of one process share no hardware queue and no CU.
 constexpr int MAX_DEVICES = 64;
 static std::atomic<int> g_live_contexts[MAX_DEVICES];
+// snapshots: why the calling thread's last lvt_amd_snapshot_import / _describe was refused (they have no handle to report to: lvt_amd_last_error(NULL))
+static thread_local std::string g_snap_err;
 
 // An lvt_handle is either a Context (a sequence, or a lock-step batch, with its own launch chain) or a PoolSlot (lvt_pool.h: one sequence of a
 // lock-step batch SHARED by the pooled handles of a device); the first word tells them apart.
@@ -280,6 +283,7 @@ struct Context {
     uint8_t *d_col_ring[RING][2] = {};
     int colour_pitch() const { return (prm.W * bpp_of(0) + 63) / 64 * 64; }
     int pitch = 0;
+    int *d_snap_status = nullptr;  // snapshots: [B][4] map_cur, map_n, staged_cur, staged_n as k_state_pack found them (allocated by the first take)
     long enq = 0, done = 0;    // frames enqueued / collected
     long delivered = 0;        // frames whose record delivery has been enqueued (k_triangulate, the next frame's k_gate_late, or k_deliver)
     bool sync_call = false;    // the frame being enqueued is collected right away: k_triangulate delivers its record itself
@@ -507,27 +511,33 @@ static void alloc_points(Context *c, MapSoA &P, int cap) {
 
 static void drain(Context *c);
 
+// the record of a sequence that has not tracked yet, with the chain words this context's next frame expects (nothing pending): what lvt_system::reset leaves,
+// and what an applied snapshot takes its chain words from (k_state.hip)
+static Ctl fresh_ctl(const Context *c) {
+    Ctl z;
+    std::memset(&z, 0, sizeof(z));
+    z.state = 1;
+    z.last_matches[0] = z.last_matches[1] = z.last_matches[2] = 0x7FFFFFFF;
+    z.last_pose.q[0] = 1.0;
+    z.mm_last_q[0] = 1.0;
+    z.mm_ang_vel[0] = 1.0;
+    z.optimized.q[0] = z.predicted.q[0] = 1.0;
+    z.out_R[0] = z.out_R[4] = z.out_R[8] = 1.0;
+    z.out_status = 1;
+    z.pnp_seq = (seq_t)c->enq;  // the next frame's gate waits for this value: nothing is pending
+    z.early_state = 4u * (seq_t)c->enq + 3u;
+    z.track_done_seq = (seq_t)c->enq;
+    z.late_gate_seq = (seq_t)c->enq;
+    z.gate_timeouts = c->gate_timeouts_seen, z.gate_fatal = c->gate_fatal_seen;  // (the host compares these running counters with what it has seen)
+    return z;
+}
 static void reset_state(Context *c, int only = -1) {  // lvt_system::reset (lvt_system.cpp:44-68); only >= 0: that sequence of a batch alone
     drain(c);
     if (only < 0) c->gate_timeouts_seen = 0, c->gate_fatal_seen = 0;
     if (only < 0 && c->capacity_report()) c->err.clear();  // (the frames it spoke of are gone)
     for (int s = 0; s < c->B; s++) {
         if (only >= 0 && s != only) continue;
-        Ctl z;
-        std::memset(&z, 0, sizeof(z));
-        z.state = 1;
-        z.last_matches[0] = z.last_matches[1] = z.last_matches[2] = 0x7FFFFFFF;
-        z.last_pose.q[0] = 1.0;
-        z.mm_last_q[0] = 1.0;
-        z.mm_ang_vel[0] = 1.0;
-        z.optimized.q[0] = z.predicted.q[0] = 1.0;
-        z.out_R[0] = z.out_R[4] = z.out_R[8] = 1.0;
-        z.out_status = 1;
-        z.pnp_seq = (seq_t)c->enq;  // the next frame's gate waits for this value: nothing is pending
-        z.early_state = 4u * (seq_t)c->enq + 3u;
-        z.track_done_seq = (seq_t)c->enq;
-        z.late_gate_seq = (seq_t)c->enq;
-        z.gate_timeouts = c->gate_timeouts_seen, z.gate_fatal = c->gate_fatal_seen;  // (the host compares these running counters with what it has seen)
+        const Ctl z = fresh_ctl(c);
         HIPCHK(c, hipMemcpyAsync(c->d_ctl[s], &z, sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(c->h_seqs[s].map_n, 0, sizeof(int), c->stream));
         HIPCHK(c, hipMemsetAsync(c->h_seqs[s].map_cur, 0, sizeof(int), c->stream));
@@ -816,7 +826,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
-    "", ""};
+    "k_state_pack", "k_state_unpack"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -1642,7 +1652,7 @@ LVT_API const char *lvt_amd_last_error(lvt_handle h) {
         acopy = lvt_amd_last_error(A->impl);
         return acopy.c_str();
     }
-    if (!h) return "no handle (creation failed: bad parameters, or no HIP device -- there is no CPU fallback)";
+    if (!h) return g_snap_err.empty() ? "no handle (creation failed: bad parameters, or no HIP device -- there is no CPU fallback)" : g_snap_err.c_str();
     if (is_slot(h)) {
         PoolSlot *S = static_cast<PoolSlot *>(h);
         std::lock_guard<std::mutex> g(S->pool->mu);
@@ -1703,6 +1713,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot < 0 || slot >= Context::PROF_SLOTS || !kProfNames[slot][0]) return 0;
     if (slot == 4 && c->n_rect == 0 && c->prof_calls[4] == 0) return 0;  // (a handle without rectifiers has no such launch)
     if (slot == 14 && c->n_colour == 0 && c->prof_calls[14] == 0) return 0;  // (... and one without a colour sequence no k_gray_frames)
+    if (slot >= 22 && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -2924,6 +2935,363 @@ LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
     const Context *c = static_cast<const Context *>(h);
     return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
 }
+
+// ---- snapshots: one sequence's state saved, restored, moved between handles and seats (k_state.hip) -------------------------------------------
+// Everything is checked before anything changes: a refusal returns -1 / NULL, leaves handle and snapshot as they were and says why in lvt_amd_last_error
+// (lvt_amd_snapshot_import / _describe have no handle: lvt_amd_last_error(NULL) then speaks of the calling thread's last refused import or describe).
+}  // extern "C"
+namespace lvt {
+constexpr uint64_t SNAPOBJ_MAGIC = 0x4C56545F534E4150ull;
+struct Snapshot {
+    uint64_t magic = SNAPOBJ_MAGIC;
+    int device = 0;
+    uint8_t *d_blob = nullptr;  // SnapHeader::total bytes
+    SnapHeader hdr{};           // host copy of the blob's header
+    Ctl ctl;                    // host copy of its Ctl section (chain words zero), fetched when first needed
+    bool have_ctl = false;
+};
+struct DevScope {  // DeviceGuard for an object that is no Context
+    int prev = -1;
+    explicit DevScope(int dev) {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
+    }
+    ~DevScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+static Snapshot *snap_of(lvt_amd_snapshot s) {
+    Snapshot *p = static_cast<Snapshot *>(s);
+    return (p && p->magic == SNAPOBJ_MAGIC) ? p : nullptr;
+}
+static void snap_free(Snapshot *p) {
+    if (!p) return;
+    if (p->d_blob) {
+        DevScope g(p->device);
+        (void)hipFree(p->d_blob);
+    }
+    p->magic = 0;
+    delete p;
+}
+static bool snap_fetch_ctl(Snapshot *p) {
+    if (p->have_ctl) return true;
+    DevScope g(p->device);
+    if (hipMemcpy(&p->ctl, p->d_blob + p->hdr.off[SEC_CTL], sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return p->have_ctl = true;
+}
+// a header (and, with_payload, the n bytes it heads) this library can take; "" or the reason
+static std::string snap_validate(const void *bytes, long long n, bool with_payload) {
+    if (!bytes || n < (long long)sizeof(SnapHeader)) return "too short for a snapshot header (" + std::to_string(bytes ? n : 0) + " bytes)";
+    SnapHeader h;
+    std::memcpy(&h, bytes, sizeof(h));
+    if (h.magic != SNAP_MAGIC) return "not a snapshot (wrong magic)";
+    if (h.version != SNAP_VERSION) return "snapshot version " + std::to_string(h.version) + ", this library reads version " + std::to_string(SNAP_VERSION);
+    if (h.header_bytes != (int)sizeof(SnapHeader) || h.ctl_bytes != (int)sizeof(Ctl))
+        return "a snapshot of another build (header / Ctl of " + std::to_string(h.header_bytes) + " / " + std::to_string(h.ctl_bytes) + " bytes, here " +
+               std::to_string(sizeof(SnapHeader)) + " / " + std::to_string(sizeof(Ctl)) + ")";
+    if (h.nf_max != NF_MAX || h.map_max != MAP_MAX || h.staged_max != STAGED_MAX) return "a snapshot of a build with other capacities";
+    if (h.sensor != 1 && h.sensor != 2) return "unknown sensor type " + std::to_string(h.sensor);
+    if (h.map_n < 0 || h.map_n > MAP_MAX || h.staged_n < 0 || h.staged_n > STAGED_MAX || (h.map_cur & ~1) || (h.staged_cur & ~1)) return "point counts out of range";
+    int off[SNAP_SECTIONS];
+    const long long total = snap_layout(h.map_n, h.staged_n, off);
+    if (std::memcmp(off, h.off, sizeof(off)) != 0 || h.total != total) return "section offsets that do not belong to its point counts";
+    if (!with_payload) return "";
+    if (n < total) return "truncated: " + std::to_string(n) + " bytes of " + std::to_string(total);
+    if (snap_checksum(static_cast<const uint8_t *>(bytes) + sizeof(SnapHeader), (size_t)(total - (long long)sizeof(SnapHeader))) != h.checksum) return "checksum mismatch (damaged payload)";
+    return "";
+}
+static void snap_info(const SnapHeader &h, const Ctl &k, int device, lvt_amd_snapshot_info *out) {
+    out->version = h.version, out->sensor_type = h.sensor, out->state = k.state, out->frame_number = k.frame_number;
+    out->map_n = h.map_n, out->staged_n = h.staged_n, out->src_map_cur = h.map_cur, out->src_staged_cur = h.staged_cur, out->device = device, out->bytes = h.total;
+}
+
+static int snap_refuse(lvt_handle h, const char *who, const std::string &why) { return refuse(h, who, why + " (nothing was changed)"); }
+// the context behind a (resolved) handle for a snapshot call; batch_call: the calls that take every sequence / name one of a batch.  nullptr: refused
+static Context *snap_context(lvt_handle h, const char *who, bool batch_call) {
+    Context *c = frame_context(h, who, 0, true, {"a pooled or automatic seat (its state lives in a chain shared with other handles) (nothing was changed)", nullptr, nullptr});
+    if (!c) return nullptr;
+    if (batch_call && c->B == 1 && !c->mixed) {
+        snap_refuse(h, who, "a batch call on a handle that is not a batch");
+        return nullptr;
+    }
+    return c;
+}
+static bool snap_seq_ok(Context *c, const char *who, int seq) {
+    if (seq >= 0 && seq < c->B) return true;
+    snap_refuse(c, who, "no sequence " + std::to_string(seq) + " in this handle" + (c->B == 1 ? " (seq is 0 for a solo handle)" : ""));
+    return false;
+}
+static StateSeq state_desc(Context *c, int s, uint8_t *blob, const SnapHeader &h) {
+    const Seq &S = c->h_seqs[s];
+    StateSeq d{};
+    d.ctl = c->d_ctl[s];
+    for (int k = 0; k < 2; k++) {
+        d.map[k] = PointsRef{S.map[k].pos, S.map[k].desc, S.map[k].counter, S.map[k].age};
+        d.staged[k] = PointsRef{S.staged[k].pos, S.staged[k].desc, S.staged[k].counter, S.staged[k].age};
+    }
+    d.map_cur = S.map_cur, d.map_n = S.map_n, d.staged_cur = S.staged_cur, d.staged_n = S.staged_n;
+    d.blob = blob;
+    std::memcpy(d.off, h.off, sizeof(d.off));
+    d.map_n_blob = h.map_n, d.staged_n_blob = h.staged_n, d.map_cur_blob = h.map_cur, d.staged_cur_blob = h.staged_cur;
+    uintptr_t bits = (uintptr_t)blob;  // sections move as 16-byte vectors: both ends of every copy lie on 16-byte boundaries
+    for (int k = 0; k < 2; k++)
+        for (const PointsRef &r : {d.map[k], d.staged[k]}) bits |= (uintptr_t)r.pos | (uintptr_t)r.desc | (uintptr_t)r.counter | (uintptr_t)r.age;
+    if (bits & 15) {
+        c->set_error("snapshot: a state array that is not 16-byte aligned");
+        throw std::runtime_error(c->err);
+    }
+    return d;
+}
+// one launch per STATE_PACK sequences on the handle's stream, then the stream is synchronised (profiling: the launches' time between two events)
+static void state_launch(Context *c, bool pack, const std::vector<StateSeq> &ds, const ChainWords &cw) {
+    const int slot = pack ? 22 : 23;
+    if (c->prof) (void)hipEventRecord(c->ev[slot][0], c->stream);
+    for (size_t i0 = 0; i0 < ds.size(); i0 += STATE_PACK) {
+        const int n = (int)std::min(ds.size() - i0, (size_t)STATE_PACK);
+        StateTable tab{};
+        unsigned work = 0;
+        for (int i = 0; i < n; i++) tab.s[i] = ds[i0 + i], work = std::max(work, state_work(tab.s[i].map_n_blob, tab.s[i].staged_n_blob));
+        const dim3 grid(std::min((work + 255u) / 256u, 256u), n);
+        if (pack) hipLaunchKernelGGL(k_state_pack, grid, dim3(256), 0, c->stream, tab, c->d_snap_status + 4 * i0);
+        else hipLaunchKernelGGL(k_state_unpack, grid, dim3(256), 0, c->stream, tab, chain_arg(cw));
+    }
+    if (c->prof) (void)hipEventRecord(c->ev[slot][1], c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    float ms = 0;
+    if (c->prof && hipEventElapsedTime(&ms, c->ev[slot][0], c->ev[slot][1]) == hipSuccess) c->prof_ms[slot] += ms, c->prof_calls[slot]++;
+}
+// snapshots of the sequences `seqs` of a drained context: one pack launch (per STATE_PACK sequences) and ONE small read-back for all of them.  The blobs are sized
+// from the host's record of the last frame (its map / staged counters); the kernel reports what it found on the device, and the read-back confirms the sizes --
+// should they ever differ, the blobs are sized again from the device's figures.
+static void take_snapshots(Context *c, const std::vector<int> &seqs, std::vector<Snapshot *> &out) {
+    if (!c->d_snap_status) c->d_snap_status = c->dalloc<int>(4 * (size_t)c->B);
+    const size_t n = seqs.size();
+    std::vector<int> found(4 * n, 0);
+    out.assign(n, nullptr);
+    try {
+        for (int attempt = 0; attempt < 2; attempt++) {
+            std::vector<StateSeq> ds;
+            for (size_t i = 0; i < n; i++) {
+                const int s = seqs[i];
+                Snapshot *p = out[i] = new Snapshot();
+                SnapHeader &h = p->hdr;
+                std::memset(&h, 0, sizeof(h));
+                h.magic = SNAP_MAGIC, h.version = SNAP_VERSION, h.header_bytes = (int)sizeof(SnapHeader), h.ctl_bytes = (int)sizeof(Ctl);
+                h.nf_max = NF_MAX, h.map_max = MAP_MAX, h.staged_max = STAGED_MAX, h.sensor = c->sensor;
+                const int mn = attempt ? found[4 * i + 1] : last_ctl(c, s).counts[C_MAP_SIZE], sn = attempt ? found[4 * i + 3] : last_ctl(c, s).counts[C_STAGED_SIZE];
+                h.map_n = std::min(std::max(mn, 0), MAP_MAX), h.staged_n = std::min(std::max(sn, 0), STAGED_MAX);
+                h.prm = c->in_prms[c->mixed ? s : 0];
+                h.total = snap_layout(h.map_n, h.staged_n, h.off);
+                p->device = c->device;
+                HIPCHK(c, hipMalloc((void **)&p->d_blob, (size_t)h.total));
+                ds.push_back(state_desc(c, s, p->d_blob, h));
+            }
+            state_launch(c, true, ds, ChainWords{});
+            HIPCHK(c, hipMemcpy(found.data(), c->d_snap_status, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
+            bool fits = true;
+            for (size_t i = 0; i < n; i++) {
+                SnapHeader &h = out[i]->hdr;
+                h.map_cur = found[4 * i] & 1, h.staged_cur = found[4 * i + 2] & 1;
+                fits = fits && h.map_n == std::min(std::max(found[4 * i + 1], 0), MAP_MAX) && h.staged_n == std::min(std::max(found[4 * i + 3], 0), STAGED_MAX);
+            }
+            if (fits) break;
+            if (attempt) {
+                c->set_error("snapshot: the sequence's point counts changed while it was packed");
+                throw std::runtime_error(c->err);
+            }
+            for (Snapshot *&p : out) snap_free(p), p = nullptr;
+        }
+        for (Snapshot *p : out) HIPCHK(c, hipMemcpy(p->d_blob, &p->hdr, sizeof(SnapHeader), hipMemcpyHostToDevice));
+    } catch (...) {
+        for (Snapshot *&p : out) snap_free(p), p = nullptr;
+        throw;
+    }
+}
+// why snapshot p cannot become sequence s of c; "": it can
+static std::string apply_objection(Context *c, int s, const Snapshot *p) {
+    if (p->device != c->device)
+        return "a snapshot on device " + std::to_string(p->device) + ", the handle owns device " + std::to_string(c->device) + " (between devices: export, then import)";
+    if (p->hdr.sensor != c->sensor) return "a snapshot of sensor type " + std::to_string(p->hdr.sensor) + " on a handle of sensor type " + std::to_string(c->sensor);
+    if (!same_params(p->hdr.prm, c->in_prms[c->mixed ? s : 0])) return "the snapshot's parameters differ from the sequence's";
+    return "";
+}
+// snaps[i] != nullptr becomes sequence seqs[i]; everything has been checked
+static void apply_snapshots(Context *c, const std::vector<int> &seqs, const std::vector<Snapshot *> &snaps) {
+    const ChainWords cw = chain_of(fresh_ctl(c));
+    std::vector<StateSeq> ds;
+    for (size_t i = 0; i < seqs.size(); i++) {
+        if (!snap_fetch_ctl(snaps[i])) {
+            c->set_error("snapshot: its record could not be read back");
+            throw std::runtime_error(c->err);
+        }
+        ds.push_back(state_desc(c, seqs[i], snaps[i]->d_blob, snaps[i]->hdr));
+    }
+    state_launch(c, false, ds, cw);
+    for (size_t i = 0; i < seqs.size(); i++) {  // the host ring answers from the snapshot at once, as it answers from a fresh record after a reset
+        Ctl k = snaps[i]->ctl;
+        set_chain(k, cw);
+        for (int r = 0; r < RING; r++) c->h_ctl[r * c->B + seqs[i]] = k;
+    }
+}
+static int snapshot_apply(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_snapshot *list) {
+    Context *c = snap_context(h, who, batch_call);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        std::vector<int> seqs;
+        std::vector<Snapshot *> snaps;
+        if (!batch_call && !snap_seq_ok(c, who, seq)) return -1;
+        if (!list) return snap_refuse(h, who, "no snapshot");
+        for (int i = 0; i < (batch_call ? c->B : 1); i++) {
+            const int s = batch_call ? i : seq;
+            if (batch_call && !list[i]) continue;  // (left alone)
+            Snapshot *p = snap_of(list[i]);
+            const std::string tag = c->B > 1 ? "sequence " + std::to_string(s) + ": " : "";
+            if (!p) return snap_refuse(h, who, tag + "not a snapshot");
+            const std::string why = apply_objection(c, s, p);
+            if (!why.empty()) return snap_refuse(h, who, tag + why);
+            seqs.push_back(s), snaps.push_back(p);
+        }
+        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
+        if (c->done < c->enq || c->pend.valid) return snap_refuse(h, who, "frames in flight: apply after every frame has been collected");
+        if (!seqs.empty()) apply_snapshots(c, seqs, snaps);
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+// (an lvt_create handle: as for rectifiers, decided under its record's lock, and a successful apply is a use)
+static int snapshot_apply_any(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_snapshot *list) {
+    if (!is_auto(h)) return snapshot_apply(h, who, batch_call, seq, list);
+    AutoHandle *A = static_cast<AutoHandle *>(h);
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = snapshot_apply(A->impl, who, batch_call, seq, list);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+}  // namespace lvt
+extern "C" {
+
+LVT_API lvt_amd_snapshot lvt_amd_snapshot_take(lvt_handle h, int seq) {
+    static const char *who = "lvt_amd_snapshot_take";
+    h = resolve_handle(h);
+    Context *c = snap_context(h, who, false);
+    if (!c) return nullptr;
+    DeviceGuard guard(c);
+    try {
+        if (!snap_seq_ok(c, who, seq)) return nullptr;
+        drain(c);
+        std::vector<Snapshot *> out;
+        take_snapshots(c, {seq}, out);
+        return out[0];
+    } catch (...) {
+    }
+    return nullptr;
+}
+LVT_API int lvt_amd_batch_snapshot_take(lvt_handle h, lvt_amd_snapshot *out) {
+    static const char *who = "lvt_amd_batch_snapshot_take";
+    h = resolve_handle(h);
+    Context *c = snap_context(h, who, true);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!out) return snap_refuse(h, who, "no array to return the snapshots in");
+        drain(c);
+        std::vector<int> seqs(c->B);
+        for (int s = 0; s < c->B; s++) seqs[s] = s;
+        std::vector<Snapshot *> got;
+        take_snapshots(c, seqs, got);
+        for (int s = 0; s < c->B; s++) out[s] = got[s];
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_snapshot_apply(lvt_handle h, int seq, lvt_amd_snapshot s) { return snapshot_apply_any(h, "lvt_amd_snapshot_apply", false, seq, &s); }
+LVT_API int lvt_amd_batch_snapshot_apply(lvt_handle h, const lvt_amd_snapshot *s) { return snapshot_apply_any(h, "lvt_amd_batch_snapshot_apply", true, 0, s); }
+LVT_API int lvt_amd_batch_reset(lvt_handle h, int seq) {
+    static const char *who = "lvt_amd_batch_reset";
+    h = resolve_handle(h);
+    Context *c = snap_context(h, who, true);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!snap_seq_ok(c, who, seq)) return -1;
+        reset_state(c, seq);  // (drains first)
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_snapshot_get_info(lvt_amd_snapshot s, lvt_amd_snapshot_info *out) {
+    Snapshot *p = snap_of(s);
+    if (!p || !out || !snap_fetch_ctl(p)) return -1;
+    snap_info(p->hdr, p->ctl, p->device, out);
+    return 0;
+}
+LVT_API int lvt_amd_snapshot_get_params(lvt_amd_snapshot s, lvt_amd_params *out) {
+    Snapshot *p = snap_of(s);
+    if (!p || !out) return -1;
+    *out = p->hdr.prm;
+    return 0;
+}
+LVT_API long long lvt_amd_snapshot_export(lvt_amd_snapshot s, void *host_buf, long long cap) {
+    Snapshot *p = snap_of(s);
+    if (!p || !host_buf || cap < p->hdr.total) return -1;
+    DevScope g(p->device);
+    if (hipMemcpy(host_buf, p->d_blob, (size_t)p->hdr.total, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    SnapHeader h;
+    std::memcpy(&h, host_buf, sizeof(h));
+    h.checksum = p->hdr.checksum = 0;
+    if (std::memcmp(&h, &p->hdr, sizeof(h)) != 0 || !snap_validate(&h, sizeof(h), false).empty()) return -1;  // (the blob's header is not the one it was given)
+    h.checksum = snap_checksum(static_cast<const uint8_t *>(host_buf) + sizeof(SnapHeader), (size_t)(h.total - (long long)sizeof(SnapHeader)));
+    std::memcpy(host_buf, &h, sizeof(h));
+    return h.total;
+}
+LVT_API lvt_amd_snapshot lvt_amd_snapshot_import(const void *bytes, long long n, int device) {
+    const std::string why = snap_validate(bytes, n, true);
+    if (!why.empty()) {
+        g_snap_err = "lvt_amd_snapshot_import: " + why;
+        return nullptr;
+    }
+    int cur = 0;
+    if (device < 0 && hipGetDevice(&cur) == hipSuccess) device = cur;
+    Snapshot *p = new Snapshot();
+    std::memcpy(&p->hdr, bytes, sizeof(SnapHeader));
+    std::memcpy(&p->ctl, static_cast<const uint8_t *>(bytes) + p->hdr.off[SEC_CTL], sizeof(Ctl));
+    p->have_ctl = true, p->device = device;
+    p->hdr.checksum = 0;  // (a blob in device memory carries none: export writes it)
+    bool ok;
+    {
+        DevScope g(device);
+        ok = hipMalloc((void **)&p->d_blob, (size_t)p->hdr.total) == hipSuccess && hipMemcpy(p->d_blob, bytes, (size_t)p->hdr.total, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(p->d_blob, &p->hdr, sizeof(SnapHeader), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (!ok) {
+        g_snap_err = std::string("lvt_amd_snapshot_import: ") + hipGetErrorString(hipGetLastError());
+        snap_free(p);
+        return nullptr;
+    }
+    g_snap_err.clear();
+    return p;
+}
+LVT_API int lvt_amd_snapshot_describe(const void *bytes, long long n, lvt_amd_snapshot_info *out, lvt_amd_params *prm) {  // host code only
+    const std::string why = snap_validate(bytes, n, true);
+    if (!why.empty()) {
+        g_snap_err = "lvt_amd_snapshot_describe: " + why;
+        return -1;
+    }
+    SnapHeader h;
+    Ctl k;
+    std::memcpy(&h, bytes, sizeof(h));
+    std::memcpy(&k, static_cast<const uint8_t *>(bytes) + h.off[SEC_CTL], sizeof(Ctl));
+    if (out) snap_info(h, k, -1, out);
+    if (prm) *prm = h.prm;
+    g_snap_err.clear();
+    return 0;
+}
+LVT_API void lvt_amd_snapshot_destroy(lvt_amd_snapshot s) { snap_free(snap_of(s)); }
 
 // ---- odometry accumulator (lvt_ros.cpp:215-311 without ROS) -----------------------------------------------
 LVT_API lvt_amd_odometry lvt_amd_odometry_create(lvt_handle h, const double base_to_sensor[12], int reset_pose_on_lost) {
