@@ -3,12 +3,15 @@
 // lvt_system::create, vo->track, lvt_pose::get_position / get_orientation_matrix), with lvt_image_view where it has cv::Mat.
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/kitti/kitti_example.cpp:49-152 there):
-//     lvt_kitti <sequences_dir> <seq_number> [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt]
+//     lvt_kitti <sequences_dir> <seq_number> [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--covariance FILE]
 // reads <sequences_dir>/NN/image_0/%06d.{png,pgm} and image_1/..., the OpenCV-YAML calibration (camera_matrix, baseline)
 // and vo_config.yaml, tracks every frame until the sequence ends or the tracker is LOST, writes NN.txt in the KITTI
 // 3x4 row format with the reference's precision (fixed, 9 digits) and prints the mean per-frame track() time.
 // No OpenCV: the PNG reader below handles what KITTI ships (8-bit gray / RGB / RGBA / gray+alpha, non-interlaced), colour
 // is reduced to gray with cv::cvtColor's fixed-point weights, and PGM (P5) is accepted for pre-converted data.
+// --covariance FILE (not in the reference): the tracker also evaluates every frame's pose uncertainty (lvt_system::enable_pose_info) and FILE receives one
+// line per tracked frame: frame, status, n_inliers and the six sigmas (square roots of the covariance's diagonal: metres x y z, radians x y z; zeros
+// unless the status is 1).  Without the option nothing of this runs.
 #include "../include/lvt_system.h"
 
 #include "image_io.h"
@@ -63,7 +66,7 @@ int main(int argc, char **argv) {
     char seq_cstr[16];
     std::snprintf(seq_cstr, sizeof seq_cstr, "%02d", std::atoi(argv[2]));
     const std::string seq_str(seq_cstr), dir_prefix = std::string(argv[1]) + "/" + seq_str;
-    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt";
+    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name;
     long max_frames = -1;
     for (int i = 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -71,6 +74,7 @@ int main(int argc, char **argv) {
         else if (k == "--calib") calib = argv[i + 1];
         else if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
+        else if (k == "--covariance") cov_name = argv[i + 1];
     }
     double K[9], baseline = 0;
     if (!read_calib(calib, K, baseline)) {
@@ -101,6 +105,16 @@ int main(int argc, char **argv) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;
         return -1;
     }
+    std::ofstream cov_file;
+    if (!cov_name.empty()) {
+        cov_file.open(cov_name.c_str());
+        if (!cov_file || !vo->enable_pose_info()) {
+            std::cout << "failed to set up the covariance output: " << (cov_file ? vo->last_error() : "cannot open the file") << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
+        cov_file << std::scientific << std::setprecision(9);
+    }
     // like the reference, the trajectory has one row per frame of the sequence; frames after a LOST keep the default pose
     long frame_count = 0;
     for (;; frame_count++) {
@@ -130,6 +144,13 @@ int main(int argc, char **argv) {
         const lvt_pose pose = vo->wait_pose();
         dt += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
         total_time += dt;  // (time spent inside the tracker's calls, as the reference reports it)
+        if (cov_file.is_open()) {
+            lvt_amd_pose_info info;
+            vo->get_pose_info(info);
+            cov_file << i << " " << info.status << " " << info.n_inliers;
+            for (int k = 0; k < 6; k++) cov_file << " " << (info.status == 1 ? std::sqrt(info.cov[7 * k]) : 0.0);
+            cov_file << std::endl;
+        }
         const lvt_vector3 pos = pose.get_position();  // kitti_example.cpp:40-47
         const lvt_matrix33 R = pose.get_orientation_matrix();
         for (int r = 0; r < 3; r++) {

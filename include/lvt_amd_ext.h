@@ -380,6 +380,54 @@ LVT_API int lvt_amd_snapshot_describe(const void *bytes, long long n, lvt_amd_sn
 LVT_API void lvt_amd_snapshot_destroy(lvt_amd_snapshot s);
 LVT_API int lvt_amd_batch_reset(lvt_handle h, int seq);                                        /* 0 / -1 */
 
+/* ---- POSE UNCERTAINTY: a per-frame 6x6 covariance from the solver's edges -----------------------------------------------------------------
+ * The reference publishes its odometry with both covariance blocks at zero (lvt_ros.cpp:268-299).  A handle that asks for it gets, per frame and per
+ * sequence, the information matrix of the frame's 2D-3D edges at the PUBLISHED pose and its inverse.  Opt-in: one launch of its own (k_pose_info, one
+ * workgroup per sequence, on the tracking stream directly behind k_pnp); a handle that never asks launches exactly what it did.
+ *  Pose convention.  Pose (R, p) is camera-to-world, as lvt_track returns it.  The perturbation is xi = (dp, dtheta): p <- p + dp in metres on world axes,
+ *    R <- R Exp([dtheta]x) in radians on camera axes -- the pose solver's own parametrisation (t += dx[0..2], q <- q (sqrt(1 - |v|^2), v)) with dtheta = 2 v.
+ *  Edge quantities.  For edge i with its map point X and its observation (u, v) -- what lvt_amd_get_matches / lvt_amd_get_features(0) return for the frame:
+ *    pc = R^T (X - p);  e = (fx pcx / pcz + cx - u, fy pcy / pcz + cy - v);
+ *    the edge is an INLIER iff pcz > 0 and e.e <= 5.991, with comparisons false for NaN;
+ *    weight w = 1 / (1 + e.e / 5.991): the Cauchy kernel of the solver, rho' only, no second-order term;  J = de/dxi, 2 x 6.
+ *  Outputs.  info = sum over inliers of w J^T J;  cov = info^-1.  Both 6 x 6, row-major, in the order (px, py, pz, thetax, thetay, thetaz) and exactly symmetric.
+ *    Unit pixel noise: cov is NOT scaled by the residual -- chi2, sq_err and n_inliers are what a caller needs to scale it.
+ *  status: 0 = none (not enabled, first frame, LOST at or before this frame, skipped or absent frame, or just reset / restored); 1 = valid;
+ *    2 = degenerate: n_inliers < 3, or an LDL^T pivot d_k <= 1e-12 info[k][k] (a sum of <= 4096 fp64 terms carries that much relative noise: a pivot below it
+ *    is not information) -- info is still delivered, cov is all zero.
+ *  - lvt_amd_enable_pose_info: a property of the handle, all sequences of a batch together; 0 / -1.  Refused (-1, nothing changed, the reason in
+ *    lvt_amd_last_error): frames in flight (enable before the first frame or after every frame has been collected), a pooled or automatic seat, a bad handle.
+ *    A successful call counts as use of an lvt_create handle.  Enabling is not state: it is neither in snapshots nor restored by them.
+ *  - lvt_amd_get_pose_info: the record of the frame lvt_amd_get_pose / lvt_amd_get_counts answer for, waiting where they wait (`seq` is 0 for a solo handle).
+ *    1 = record copied, 0 = not enabled (the record is zero-filled), -1 = bad handle or seq.  lvt_amd_reset, lvt_amd_batch_reset and lvt_amd_snapshot_apply
+ *    leave status 0 until the next tracked frame.
+ *  - lvt_amd_pose_info_eval: the same evaluation on caller data (host pointers: pts n x 3 f64, obs n x 2 f32, 0 <= n <= 4096; q unit, either sign),
+ *    for differential tests; 0 / -1.
+ *  - lvt_amd_pose_info_to_ros: host only.  cov with its rotation part on FIXED WORLD axes (dphi = R dtheta), i.e. M cov M^T with M = blockdiag(I, R): the
+ *    convention of geometry_msgs/PoseWithCovariance for the camera pose itself.  (The odometry accumulator below has its own, for base_link in odom.)
+ *  - lvt_amd_profile_read reports the launch as "k_pose_info" (an enabled handle only). */
+typedef struct lvt_amd_pose_info {
+    double cov[36], info[36];
+    double chi2;        /* sum of 5.991 log(1 + e.e / 5.991) over inliers */
+    double sq_err;      /* sum of e.e over inliers */
+    int n_edges, n_inliers;
+    int n_borderline;   /* edges with |e.e - 5.991| < 1e-6 */
+    int status;
+    int frame;          /* LVT_AMD_C_FRAME of the frame the record belongs to */
+    int reserved;
+} lvt_amd_pose_info;
+#define LVT_AMD_POSE_INFO_SIZE 616
+#ifdef __cplusplus
+static_assert(sizeof(lvt_amd_pose_info) == LVT_AMD_POSE_INFO_SIZE, "lvt_amd_pose_info is part of the ABI");
+#else
+_Static_assert(sizeof(lvt_amd_pose_info) == LVT_AMD_POSE_INFO_SIZE, "lvt_amd_pose_info is part of the ABI");
+#endif
+LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable);                               /* 0 / -1 */
+LVT_API int lvt_amd_get_pose_info(lvt_handle h, int seq, lvt_amd_pose_info *out);             /* 1 / 0 / -1 */
+LVT_API int lvt_amd_pose_info_eval(const lvt_amd_params *p, const double q_wxyz[4], const double pos[3], const double *pts, const float *obs, int n,
+                                   lvt_amd_pose_info *out);
+LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3], double cov_ros[36]);
+
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without
  * ROS: poses are re-expressed in an x-forward / z-up frame (rot_fix = Rz(-pi/2) Rx(-pi/2)), the frame-to-frame delta is moved
@@ -399,6 +447,21 @@ LVT_API int lvt_amd_odometry_push_pose(lvt_amd_odometry o, const double R[3][3],
                                        double pose_out[7], double twist_out[6]);
 LVT_API int lvt_amd_odometry_update(lvt_amd_odometry o, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double stamp_sec,
                                     double pose_out[7], double twist_out[6]);
+/* ... with the covariance of the published pose.  cov_in: the frame's lvt_amd_pose_info::cov in the convention above; NULL when there is none (hand in
+ * NULL unless the record's status is 1: a degenerate record's cov is all zero and says nothing).
+ * cov_out: the 6 x 6 row-major covariance of the published base_link-in-odom pose in ROS's order and axes -- position, then rotation about the FIXED axes of
+ * odom (geometry_msgs/PoseWithCovariance) --, obtained by pushing xi through the accumulator's own arithmetic.  With (R_po, .) the accumulated pose BEFORE this
+ * frame, R_B the rotation of base_to_sensor, (., p_C) = base_to_sensor^-1, F = rot_fix, L the previous frame's fixed rotation (F R_prev; F before the first
+ * frame and after a restart) and Q = R_po R_B F R:
+ *     dp_ob = Q R^T dp - Q [L^T p_C]x dtheta,      dphi_ob = Q dtheta
+ * so cov_out = M cov_in M^T with M = [Q R^T, -Q [L^T p_C]x; 0, Q].  It is the uncertainty of THIS frame's localisation against the local map, not
+ * accumulated drift: the poses before it are taken as exact.  cov_out is all zero when cov_in is NULL or nothing was published (LOST, stale stamp).
+ * pose_out, twist_out and the return value are exactly those of the functions above.  lvt_amd_odometry_update_cov tracks, fetches the record
+ * (lvt_amd_get_pose_info; a record whose status is not 1 -- a handle that never enabled it included -- gives zeros) and pushes. */
+LVT_API int lvt_amd_odometry_push_pose_cov(lvt_amd_odometry o, const double R[3][3], const double t[3], int status, double stamp_sec,
+                                           const double cov_in[36], double pose_out[7], double twist_out[6], double cov_out[36]);
+LVT_API int lvt_amd_odometry_update_cov(lvt_amd_odometry o, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double stamp_sec,
+                                        double pose_out[7], double twist_out[6], double cov_out[36]);
 
 #ifdef __cplusplus
 }

@@ -304,6 +304,13 @@ class lvt_system {
         m_bpp = (format == LVT_AMD_PIX_GRAY8) ? 1 : (format >= LVT_AMD_PIX_BGRA8 ? 4 : 3);
         return true;
     }
+    /* ADDITIVE: pose uncertainty (include/lvt_amd_ext.h, POSE UNCERTAINTY).  enable_pose_info(): from the next frame on every tracked frame carries an
+     * lvt_amd_pose_info -- the information matrix of its 2D-3D edges at the returned pose and its inverse, a 6 x 6 covariance for unit pixel noise in
+     * the order (position on world axes, rotation on camera axes).  false: refused (frames in flight; last_error() says why), nothing changed.
+     * get_pose_info(): the record of the last frame handed in (waits for its tail, as lvt_get_status does); false when the system never enabled it -- the
+     * record is then zero-filled, status 0. */
+    bool enable_pose_info(bool enable = true) { return lvt_amd_enable_pose_info(m_handle, enable ? 1 : 0) == 0; }
+    bool get_pose_info(lvt_amd_pose_info &out) { return lvt_amd_get_pose_info(m_handle, 0, &out) == 1; }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
         m_state = lvt_amd_wait_pose(m_handle, q, p);

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "lvt_amd_snapshot_take", "lvt_amd_snapshot_apply", "lvt_amd_batch_snapshot_take", "lvt_amd_batch_snapshot_apply", "lvt_amd_snapshot_get_info",
     "lvt_amd_snapshot_get_params", "lvt_amd_snapshot_export", "lvt_amd_snapshot_import", "lvt_amd_snapshot_describe", "lvt_amd_snapshot_destroy",
     "lvt_amd_batch_reset",
+    "lvt_amd_enable_pose_info", "lvt_amd_get_pose_info", "lvt_amd_pose_info_eval", "lvt_amd_pose_info_to_ros",
+    "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
 ]
 
 N_COUNTS = 32
@@ -187,6 +189,14 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, restype
+    for name, argtypes, restype in (   # (pose uncertainty: likewise)
+            ("lvt_amd_enable_pose_info", [vp, C.c_int], C.c_int), ("lvt_amd_get_pose_info", [vp, C.c_int, vp], C.c_int),
+            ("lvt_amd_pose_info_eval", [vp, vp, vp, vp, vp, C.c_int, vp], C.c_int), ("lvt_amd_pose_info_to_ros", [vp, vp, vp], None),
+            ("lvt_amd_odometry_push_pose_cov", [vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp], C.c_int),
+            ("lvt_amd_odometry_update_cov", [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp], C.c_int)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -215,6 +225,64 @@ class SnapshotInfo(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+POSE_INFO_NONE, POSE_INFO_VALID, POSE_INFO_DEGENERATE = 0, 1, 2
+POSE_INFO_SIZE = 616   # sizeof(lvt_amd_pose_info), LVT_AMD_POSE_INFO_SIZE: pinned in the header too
+
+
+class PoseInfo(C.Structure):
+    """lvt_amd_pose_info: the information matrix of a frame's 2D-3D edges at the published pose and its inverse (include/lvt_amd_ext.h, POSE UNCERTAINTY).
+    Perturbation (dp on world axes, dtheta on camera axes), order px py pz thetax thetay thetaz, unit pixel noise."""
+    _fields_ = [("_cov", C.c_double * 36), ("_info", C.c_double * 36), ("chi2", C.c_double), ("sq_err", C.c_double),
+                ("n_edges", C.c_int), ("n_inliers", C.c_int), ("n_borderline", C.c_int), ("status", C.c_int), ("frame", C.c_int), ("reserved", C.c_int)]
+
+    @property
+    def cov(self) -> np.ndarray:
+        return np.array(self._cov, dtype=np.float64).reshape(6, 6)
+
+    @property
+    def info(self) -> np.ndarray:
+        return np.array(self._info, dtype=np.float64).reshape(6, 6)
+
+    def sigmas(self) -> np.ndarray:
+        """square roots of cov's diagonal: metres (3), radians (3)"""
+        return np.sqrt(np.diag(self.cov))
+
+    def to_bytes(self) -> bytes:
+        return bytes(memoryview(self))
+
+
+assert C.sizeof(PoseInfo) == POSE_INFO_SIZE
+
+
+def _pose_info_of(handle, seq):
+    rec = PoseInfo()
+    rc = load_library().lvt_amd_get_pose_info(handle, int(seq), C.byref(rec))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_pose_info: bad handle or no sequence {seq}")
+    return rec
+
+
+def pose_info_eval(params: LvtParameters, q, p, pts, obs) -> PoseInfo:
+    """stage entry: the pose-uncertainty evaluation on caller data (q w x y z unit, either sign; pts n x 3; obs n x 2 float32; n <= 4096)"""
+    pod = params.to_pod()
+    q = np.ascontiguousarray(q, np.float64).reshape(4); p = np.ascontiguousarray(p, np.float64).reshape(3)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3); obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 2)
+    if len(pts) != len(obs):
+        raise ValueError("one observation per point")
+    rec = PoseInfo()
+    if load_library().lvt_amd_pose_info_eval(C.byref(pod), _p(q), _p(p), _p(pts) if len(pts) else None, _p(obs) if len(pts) else None, len(pts), C.byref(rec)) != 0:
+        raise RuntimeError("lvt_amd_pose_info_eval failed")
+    return rec
+
+
+def pose_info_to_ros(cov, R) -> np.ndarray:
+    """cov with its rotation part on fixed world axes: M cov M^T, M = blockdiag(I, R) (host code: needs the library, not a GPU)"""
+    c = np.ascontiguousarray(cov, np.float64).reshape(36); Rm = np.ascontiguousarray(R, np.float64).reshape(9)
+    out = np.zeros(36)
+    load_library().lvt_amd_pose_info_to_ros(_p(c), _p(Rm), _p(out))
+    return out.reshape(6, 6)
 
 
 def _params_of(pod):
@@ -462,6 +530,14 @@ class LvtSystem:
     def pixel_format(self) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, 0)
 
+    def enable_pose_info(self, on: bool = True) -> int:
+        """from the next frame on every tracked frame carries a PoseInfo (one more launch per frame, k_pose_info).  0: done; -1: refused (last_error())"""
+        return load_library().lvt_amd_enable_pose_info(self._h, 1 if on else 0)
+
+    def pose_info(self) -> PoseInfo:
+        """the record of the frame pose() / counts() answer for; status 0 when there is none (not enabled, first frame, LOST, just reset / restored)"""
+        return _pose_info_of(self._h, 0)
+
     def set_stream(self, hip_stream: int):
         load_library().lvt_amd_set_stream(self._h, C.c_void_p(hip_stream))
 
@@ -630,6 +706,14 @@ class LvtBatch:
 
     def pixel_format(self, seq: int) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, int(seq))
+
+    def enable_pose_info(self, on: bool = True) -> int:
+        """LvtSystem.enable_pose_info for all sequences of the batch together"""
+        return load_library().lvt_amd_enable_pose_info(self._h, 1 if on else 0)
+
+    def pose_info(self, seq: int) -> PoseInfo:
+        """sequence `seq`'s record of the last collected step (IndexError: no such sequence)"""
+        return _pose_info_of(self._h, seq)
 
     def params(self, seq: int) -> LvtParameters:
         pod = ParamsPOD()
@@ -835,6 +919,29 @@ class Odometry:
     def update(self, left, right, stamp):
         a, b = _u8(left), _u8(right)
         return self._call(load_library().lvt_amd_odometry_update, _p(a), _p(b), a.shape[0], a.shape[1], float(stamp))
+
+    def _call_cov(self, fn, *args):
+        pose = np.zeros(7); twist = np.zeros(6); cov = np.zeros(36)
+        rc = fn(self._h, *args, _p(pose), _p(twist), _p(cov))
+        if rc < 0:
+            raise ValueError("bad arguments")
+        return (pose, twist, cov.reshape(6, 6)) if rc == 1 else None
+
+    def push_pose_cov(self, R, t, status, stamp, cov=None):
+        """push_pose with the 6 x 6 covariance of the published pose (ROS order, rotation about odom's fixed axes): (pose, twist, cov_out) or None.
+        cov: the frame's PoseInfo.cov (hand in None unless its status is 1); None gives zeros"""
+        Rm = np.ascontiguousarray(R, dtype=np.float64).reshape(3, 3); tv = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        c = None if cov is None else np.ascontiguousarray(cov, dtype=np.float64).reshape(36)
+        pose = np.zeros(7); twist = np.zeros(6); out = np.zeros(36)
+        rc = load_library().lvt_amd_odometry_push_pose_cov(self._h, _p(Rm), _p(tv), int(status), float(stamp), _p(c), _p(pose), _p(twist), _p(out))
+        if rc < 0:
+            raise ValueError("bad arguments")
+        return (pose, twist, out.reshape(6, 6)) if rc == 1 else None
+
+    def update_cov(self, left, right, stamp):
+        """update with the covariance of the published pose (zeros unless the system has pose info enabled and the frame's record is valid)"""
+        a, b = _u8(left), _u8(right)
+        return self._call_cov(load_library().lvt_amd_odometry_update_cov, _p(a), _p(b), a.shape[0], a.shape[1], float(stamp))
 
     def reset(self):
         load_library().lvt_amd_odometry_reset(self._h)

@@ -20,6 +20,7 @@
 #include "k_lists.hip"
 #include "k_rectify.hip"
 #include "k_state.hip"
+#include "k_poseinfo.hip"
 #include "lvt_odometry.h"
 
 #include <atomic>
@@ -200,6 +201,11 @@ struct Context {
     bool early_pose = true;    // LVT_AMD_SYNC_TAIL=wait: synchronous calls return only when the whole frame is done
     bool early_pending = false;  // the last synchronous call returned on its early pose: its frame is still un-collected (and is nobody's to wait for)
     FrameArgs *h_fargs = nullptr;  // pinned, RING x B
+    // POSE UNCERTAINTY (lvt_amd_enable_pose_info): an enabled handle launches k_pose_info behind k_pnp, which writes every sequence's record of the frame into
+    // its slot of this ring (pinned + coherent, RING x B, beside h_ctl; allocated by the first enable).  The frame's completion flag is released by a later
+    // kernel of the same stream, so a collected frame's record is complete.  Not state: snapshots neither hold nor restore it.
+    bool pose_info = false;
+    lvt_amd_pose_info *h_pinfo = nullptr, *h_pinfo_dev = nullptr;
     hipEvent_t ev_done[RING] = {};  // the only events of the normal mode: the streams hand over through polling gates (k_gate*)
     // LVT_AMD_ORDERING=events: the streams are ordered by event barriers only and the early stream is not used (the tracking chain
     // does all the matching).  Slower (~6 300 instead of ~7 000 frames/s), but free of kernels that wait for another queue's
@@ -354,6 +360,7 @@ struct Context {
         if (h_pose) (void)hipHostFree(h_pose);
         if (h_pose_done) (void)hipHostFree(h_pose_done);
         if (h_fargs) (void)hipHostFree(h_fargs);
+        if (h_pinfo) (void)hipHostFree(h_pinfo);
         if (stream && own_stream) (void)hipStreamDestroy(stream);
         if (stream_f) (void)hipStreamDestroy(stream_f);
         if (stream_e) (void)hipStreamDestroy(stream_e);
@@ -513,6 +520,11 @@ static void drain(Context *c);
 
 // the record of a sequence that has not tracked yet, with the chain words this context's next frame expects (nothing pending): what lvt_system::reset leaves,
 // and what an applied snapshot takes its chain words from (k_state.hip)
+// the pose-uncertainty records of sequence s: status 0 until the next tracked frame (reset, restore, enable)
+static void pose_info_clear(Context *c, int s) {
+    if (!c->h_pinfo) return;
+    for (int r = 0; r < RING; r++) std::memset(&c->h_pinfo[(size_t)r * c->B + s], 0, sizeof(lvt_amd_pose_info));
+}
 static Ctl fresh_ctl(const Context *c) {
     Ctl z;
     std::memset(&z, 0, sizeof(z));
@@ -544,6 +556,7 @@ static void reset_state(Context *c, int only = -1) {  // lvt_system::reset (lvt_
         HIPCHK(c, hipMemsetAsync(c->h_seqs[s].staged_n, 0, sizeof(int), c->stream));
         HIPCHK(c, hipMemsetAsync(c->h_seqs[s].staged_cur, 0, sizeof(int), c->stream));
         for (int r = 0; r < RING; r++) c->h_ctl[r * c->B + s] = z;
+        pose_info_clear(c, s);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
 }
@@ -825,7 +838,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
 static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
-    "", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
+    "k_pose_info", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
     "k_state_pack", "k_state_unpack"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
@@ -1118,6 +1131,7 @@ static void enqueue_frame(Context *c) {
         LAUNCH_S(13, st, k_pnp, dim3(1, 1, Bz), dim3(PNP_THREADS), PNP_DYN_BYTES, par, seq, ep ? c->h_pose_dev + (size_t)slot * B : (PoseRec *)nullptr,
                  ep ? c->h_pose_done_dev + (size_t)slot * B : (seq_t *)nullptr);
     }
+    if (c->pose_info) LAUNCH_S(15, st, k_pose_info, dim3(1, 1, Bz), dim3(PI_THREADS), 0, c->h_pinfo_dev + (size_t)slot * B);
     if (c->any_staged)  // (a configuration without staging -- EuRoC, TUM -- never has staged points to list; in a mixed batch such a sequence leaves at the kernel's head)
         LAUNCH_SM(16, st, k_candidates, MODE_STAGED, dim3(64, 1, Bz), dim3(256), 0, 0, par, (seq_t)0, 0);
     LAUNCH_S(20, st, k_triangulate, dim3(1, 1, Bz), dim3(1024), 0, par, seq, c->h_ctl_dev + (size_t)slot * B,
@@ -1713,6 +1727,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot < 0 || slot >= Context::PROF_SLOTS || !kProfNames[slot][0]) return 0;
     if (slot == 4 && c->n_rect == 0 && c->prof_calls[4] == 0) return 0;  // (a handle without rectifiers has no such launch)
     if (slot == 14 && c->n_colour == 0 && c->prof_calls[14] == 0) return 0;  // (... and one without a colour sequence no k_gray_frames)
+    if (slot == 15 && !c->pose_info && c->prof_calls[15] == 0) return 0;  // (... one that never enabled pose uncertainty no k_pose_info)
     if (slot >= 22 && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
@@ -2936,6 +2951,89 @@ LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
     return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
 }
 
+// ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ------------------------------
+static int enable_pose_info(lvt_handle h, int enable) {
+    static const char *who = "lvt_amd_enable_pose_info";
+    Context *c = frame_context(h, who, 0, true, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr, nullptr});
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
+        if (c->done < c->enq || c->pend.valid) return refuse(h, who, "frames in flight: enable before the first frame or after every frame has been collected (nothing was changed)");
+        if ((enable != 0) == c->pose_info) return 0;
+        if (enable && !c->h_pinfo) {
+            HIPCHK(c, hipHostMalloc((void **)&c->h_pinfo, sizeof(lvt_amd_pose_info) * c->B * RING, hipHostMallocCoherent));
+            HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinfo_dev, c->h_pinfo, 0));
+        }
+        for (int s = 0; s < c->B; s++) pose_info_clear(c, s);  // (either way: the last frame has no record)
+        c->pose_info = enable != 0;
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) {
+    if (!is_auto(h)) return enable_pose_info(h, enable);
+    AutoHandle *A = static_cast<AutoHandle *>(h);  // (an lvt_create handle: decided under its record's lock, and a successful call is a use)
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = enable_pose_info(A->impl, enable);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+LVT_API int lvt_amd_get_pose_info(lvt_handle h, int seq, lvt_amd_pose_info *out) {
+    h = resolve_handle(h);
+    if (!out) return -1;
+    std::memset(out, 0, sizeof(*out));
+    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has it enabled)
+    if (!is_ctx(h)) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->pose_info) return 0;
+    DeviceGuard guard(c);
+    try {
+        drain(c);  // (as lvt_amd_get_pose / lvt_amd_get_counts: the last frame enqueued, collected)
+        *out = c->h_pinfo[(size_t)c->last_slot * c->B + seq];
+        return 1;
+    } catch (...) {
+    }
+    return -1;
+}
+LVT_API int lvt_amd_pose_info_eval(const lvt_amd_params *pin, const double q_wxyz[4], const double pos[3], const double *pts, const float *obs, int n,
+                                   lvt_amd_pose_info *out) {
+    if (!pin || !q_wxyz || !pos || !out || n < 0 || n > NF_MAX || (n > 0 && (!pts || !obs))) return -1;
+    Params prm;
+    lvt_amd_params tmp = *pin;
+    if (tmp.img_width <= 0) tmp.img_width = 64;
+    if (tmp.img_height <= 0) tmp.img_height = 64;
+    if (!derive_params(tmp, 1, prm)) return -1;
+    double *dX = nullptr;
+    float *dObs = nullptr;
+    lvt_amd_pose_info *dOut = nullptr;
+    int rc = -1;
+    const size_t nn = (size_t)std::max(n, 1);
+    if (hipMalloc((void **)&dX, nn * 24) == hipSuccess && hipMalloc((void **)&dObs, nn * 8) == hipSuccess &&
+        hipMalloc((void **)&dOut, sizeof(lvt_amd_pose_info)) == hipSuccess &&
+        (n == 0 || (hipMemcpy(dX, pts, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dObs, obs, (size_t)n * 8, hipMemcpyHostToDevice) == hipSuccess))) {
+        Pose pose;
+        for (int k = 0; k < 4; k++) pose.q[k] = q_wxyz[k];
+        for (int k = 0; k < 3; k++) pose.p[k] = pos[k];
+        hipLaunchKernelGGL(k_pose_info_standalone, dim3(1), dim3(PI_THREADS), 0, 0, prm, pose, dX, dObs, n, dOut);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dOut, sizeof(lvt_amd_pose_info), hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    (void)hipFree(dX), (void)hipFree(dObs), (void)hipFree(dOut);
+    return rc;
+}
+// host only: the rotation part moved from camera axes to fixed world axes, M cov M^T with M = blockdiag(I, R)
+LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3], double cov_ros[36]) {
+    if (!cov || !R || !cov_ros) return;
+    double M[36] = {};
+    for (int i = 0; i < 3; i++) {
+        M[6 * i + i] = 1.0;
+        for (int j = 0; j < 3; j++) M[6 * (3 + i) + 3 + j] = R[i][j];
+    }
+    sandwich6(M, cov, cov_ros);
+}
+
 // ---- snapshots: one sequence's state saved, restored, moved between handles and seats (k_state.hip) -------------------------------------------
 // Everything is checked before anything changes: a refusal returns -1 / NULL, leaves handle and snapshot as they were and says why in lvt_amd_last_error
 // (lvt_amd_snapshot_import / _describe have no handle: lvt_amd_last_error(NULL) then speaks of the calling thread's last refused import or describe).
@@ -3132,6 +3230,7 @@ static void apply_snapshots(Context *c, const std::vector<int> &seqs, const std:
         Ctl k = snaps[i]->ctl;
         set_chain(k, cw);
         for (int r = 0; r < RING; r++) c->h_ctl[r * c->B + seqs[i]] = k;
+        pose_info_clear(c, seqs[i]);
     }
 }
 static int snapshot_apply(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_snapshot *list) {
@@ -3341,6 +3440,34 @@ LVT_API int lvt_amd_odometry_update(lvt_amd_odometry op, unsigned char *left, un
     double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
     lvt_track(o->tracker, left, right, n_rows, n_cols, R, t);
     return lvt_amd_odometry_push_pose(op, R, t, lvt_get_status(o->tracker), stamp_sec, pose_out, twist_out);
+}
+// ... with the covariance of the published pose: the perturbation map is taken from the accumulator's state BEFORE the push (lvt_odometry.h), the push itself is
+// lvt_amd_odometry_push_pose's
+LVT_API int lvt_amd_odometry_push_pose_cov(lvt_amd_odometry op, const double R[3][3], const double t[3], int status, double stamp_sec,
+                                           const double cov_in[36], double pose_out[7], double twist_out[6], double cov_out[36]) {
+    Odometry *o = static_cast<Odometry *>(op);
+    if (cov_out)
+        for (int k = 0; k < 36; k++) cov_out[k] = 0.0;
+    if (!o || !R || !t) return -1;
+    double M[36];
+    o->perturbation_map(&R[0][0], M);
+    const int rc = lvt_amd_odometry_push_pose(op, R, t, status, stamp_sec, pose_out, twist_out);
+    if (rc == 1 && cov_in && cov_out) sandwich6(M, cov_in, cov_out);
+    return rc;
+}
+LVT_API int lvt_amd_odometry_update_cov(lvt_amd_odometry op, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double stamp_sec,
+                                        double pose_out[7], double twist_out[6], double cov_out[36]) {
+    Odometry *o = static_cast<Odometry *>(op);
+    if (cov_out)
+        for (int k = 0; k < 36; k++) cov_out[k] = 0.0;
+    if (!o || !o->tracker || !left || !right) return -1;
+    if (o->have_time && o->last_time > stamp_sec) return 0;  // (checked before tracking, like the node)
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
+    lvt_track(o->tracker, left, right, n_rows, n_cols, R, t);
+    const int status = lvt_get_status(o->tracker);
+    lvt_amd_pose_info rec;
+    const bool have = lvt_amd_get_pose_info(o->tracker, 0, &rec) == 1 && rec.status == 1;
+    return lvt_amd_odometry_push_pose_cov(op, R, t, status, stamp_sec, have ? rec.cov : nullptr, pose_out, twist_out, cov_out);
 }
 
 }  // extern "C"

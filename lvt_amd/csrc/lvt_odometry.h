@@ -59,6 +59,23 @@ static inline void mat3_to_quat(const double R[9], double q[4]) {
     }
 }
 
+// out = M S M^T for 6 x 6 row-major matrices (S symmetric); the upper triangle is computed and mirrored, so out is exactly symmetric
+static inline void sandwich6(const double M[36], const double S[36], double out[36]) {
+    double MS[36];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0;
+            for (int k = 0; k < 6; k++) v += M[6 * i + k] * S[6 * k + j];
+            MS[6 * i + j] = v;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++) {
+            double v = 0;
+            for (int k = 0; k < 6; k++) v += MS[6 * i + k] * M[6 * j + k];
+            out[6 * i + j] = out[6 * j + i] = v;
+        }
+}
+
 struct Odometry {
     void *tracker = nullptr;  // lvt_handle or NULL (push_pose only)
     bool reset_pose_on_lost = true;
@@ -78,6 +95,32 @@ struct Odometry {
     void restart_deltas() {
         std::memcpy(last_R, rot_fix, sizeof(rot_fix));
         last_p[0] = last_p[1] = last_p[2] = 0;
+    }
+    // The 6 x 6 map M of a perturbation xi = (dp on world axes, dtheta on camera axes) of the pose (R, t) ABOUT TO BE PUSHED onto the pose push() will publish
+    // for it (position, rotation about the fixed axes of odom), from the state BEFORE that push.  push() forms base_to_odom' = base_to_odom * B d B^-1 with
+    // d.R = F R L^T, d.p = F t - last_p (F = rot_fix, L = last_R, B = base_to_sensor, (R_C, p_C) = B^-1), so with P = R_po R_B:
+    //   R_ob' = P F R Exp(dtheta) L^T R_B^T = Exp(P F R dtheta) R_ob                                  -> dphi_ob = Q dtheta, Q = P F R
+    //   p_ob' = p_po + R_po (R_B d.R p_C + R_B d.p + p_B),  d(d.R p_C) = F R [dtheta]x L^T p_C         -> dp_ob = P F dp - Q [L^T p_C]x dtheta
+    void perturbation_map(const double R[9], double M[36]) const {
+        double P[9], PF[9], Q[9];
+        mat3_mul(base_to_odom.R, base_to_sensor.R, P);
+        mat3_mul(P, rot_fix, PF);
+        mat3_mul(PF, R, Q);
+        const Rigid C = rigid_inv(base_to_sensor);
+        double LT[9], a[3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) LT[3 * i + j] = last_R[3 * j + i];
+        mat3_vec(LT, C.p, a);
+        const double ax[9] = {0, -a[2], a[1], a[2], 0, -a[0], -a[1], a[0], 0};
+        double Qa[9];
+        mat3_mul(Q, ax, Qa);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                M[6 * i + j] = PF[3 * i + j];
+                M[6 * i + 3 + j] = -Qa[3 * i + j];
+                M[6 * (3 + i) + j] = 0;
+                M[6 * (3 + i) + 3 + j] = Q[3 * i + j];
+            }
     }
     // returns true when a pose was published
     bool push(const double R[9], const double t[3], double stamp, double pose_out[7], double twist_out[6]) {
