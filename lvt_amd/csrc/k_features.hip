@@ -5,6 +5,7 @@
 //   k_brief   : BRIEF-256, one wavefront per key point
 // Integer stages are bit-exact restatements; see DESIGN.md for the layout and roofline of each kernel.
 #include "lvt_dev.h"
+#include "lvt_handover.h"
 #include "lvt_math.h"
 #include <type_traits>
 
@@ -1572,7 +1573,7 @@ __device__ __forceinline__ void cells_work_split(const Seq &S, const FrameBuf &F
                     n = __hip_atomic_load(cnt_all + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     break;
                 }
-                if (wall_clock64() - t0 > 200000) break;  // 2 ms of the 100-MHz clock: the whole cell on this workgroup
+                if (wall_clock64() - t0 > SPLIT_HELPER) break;  // the whole cell on this workgroup
                 __builtin_amdgcn_s_sleep(2);
             }
             s_helper[h] = n;
@@ -2104,13 +2105,7 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t pub
             __threadfence();  // ... and visible before this workgroup counts itself
             if (atomicAdd(&fc.done_blocks, 1u) == gridDim.x * gridDim.y - 1) {
                 fc.done_blocks = 0;
-                if (poison) {  // the frame has no features: say so to the gates of the other streams, then release the flag
-                    fc.skip_seq = publish_seq;
-                    fc.poison = 0;
-                }
-                S.ctl->dbg[47] = (long long)wall_clock64();  // (written from the feature stream: the frame it belongs to may differ)
-                __threadfence();
-                atomicExch(&fc.feat_seq, publish_seq);
+                publish_features(S, fc, publish_seq);
             }
         }
     }
@@ -2260,13 +2255,7 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t
             __threadfence();
             if (atomicAdd(&fc.done_blocks, 1u) == gridDim.x * gridDim.y - 1) {
                 fc.done_blocks = 0;
-                if (poison) {
-                    fc.skip_seq = publish_seq;
-                    fc.poison = 0;
-                }
-                S.ctl->dbg[47] = (long long)wall_clock64();
-                __threadfence();
-                atomicExch(&fc.feat_seq, publish_seq);
+                publish_features(S, fc, publish_seq);
             }
         }
     }

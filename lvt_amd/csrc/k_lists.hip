@@ -25,6 +25,7 @@
 // Capacity: 1536 train features and 1100 bins per LDS image (94 KB of LDS per 512-thread workgroup); beyond that (or for a cell search radius above 2) the kernel does
 // NOTHING and raises Seq::lists_fb, and the wave-per-query kernel launched behind it does the work as before.
 #include "lvt_dev.h"
+#include "lvt_handover.h"
 #include "lvt_math.h"
 
 namespace lvt {
@@ -56,12 +57,12 @@ __global__ __launch_bounds__(LS_THREADS) void k_hamming_batched_lists(SeqArg<BV>
     // ---- what there is to do (block-uniform), exactly as the kernel this one stands in for decides it
     int q_end = 0;
     if (MODE == MODE_MAP) {
-        const int n_early = (ctl.gate_ok == seq) ? ctl.early_done : 0;  // k_early_map
+        const int n_early = early_points_claimed(&ctl, seq);  // k_early_map
         if (n_early <= 0) return;
         q_end = min(*S.map_n, n_early);
     } else {
         if (S.prm.sensor != 1) return;
-        if (seq && __hip_atomic_load(&S.fb[par].fc->feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) return;  // k_candidates<ROW>
+        if (seq && !seq_reached(S.fb[par].fc->feat_seq, seq)) return;  // k_candidates<ROW>
         q_end = *S.fb[par].feat[0].n;
     }
     const Feat &T = (MODE == MODE_ROW) ? S.fb[par].feat[1] : S.fb[par].feat[0];

@@ -19,6 +19,7 @@
 // The Hamming distance evaluation is parallel (k_candidates); only the accept/mark scan is sequential,
 // and it walks pre-sorted candidate lists so it touches a few words per query.
 #include "lvt_dev.h"
+#include "lvt_handover.h"
 #include "wave_reduce.h"
 #include "lvt_math.h"
 
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void k_candidates(SeqArg<BV> sa, int pass2, in
         if (MODE == MODE_STAGED && (ctl.lost_now || S.prm.staged_th <= 0)) return;
     } else {
         if (S.prm.sensor != 1) return;
-        if (need_seq && __hip_atomic_load(&S.fb[par].fc->feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < need_seq) return;
+        if (need_seq && !seq_reached(S.fb[par].fc->feat_seq, need_seq)) return;
     }
     __shared__ uint32_t lbuf[4 * KC];
     __shared__ float s_tx[NF_MAX], s_ty[NF_MAX];
@@ -355,7 +356,6 @@ __global__ __launch_bounds__(256) void k_candidates(SeqArg<BV> sa, int pass2, in
 }
 
 __device__ __forceinline__ void deliver_record(const Ctl &ctl, Ctl *rec_out, seq_t *done_out, seq_t seq, int nthreads);
-__device__ __forceinline__ void gate_late_poll(Ctl &ctl, FeatCtl &fc, seq_t seq);
 // k_match_map : frame prologue + projection of the map points + their candidate lists (find_matches pass 1).  Every block
 // derives the per-frame facts it needs (active / first frame / predicted pose) from the PERSISTENT part of Ctl, which
 // nobody writes during this kernel; block 0 additionally publishes them for the rest of the chain.
@@ -379,9 +379,8 @@ __global__ __launch_bounds__(256) void k_match_map(SeqArg<BV> sa, int par, seq_t
             if (blockIdx.x == 0) {
                 gate_late_poll(ctl, *S.fb[par].fc, seq);
                 __hip_atomic_store(&ctl.late_gate_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                while (__hip_atomic_load(&ctl.late_gate_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) __builtin_amdgcn_s_sleep(8);
-            }
+            } else
+                wait_seq_unbounded(ctl.late_gate_seq, seq);
         }
     }
     if (threadIdx.x == 0 && blockIdx.x == 0) ctl.dbg[40] = (long long)wall_clock64();  // (timeline: the frame's work starts)
@@ -390,7 +389,7 @@ __global__ __launch_bounds__(256) void k_match_map(SeqArg<BV> sa, int par, seq_t
         int sk = ctl.skip;  // state: persistent, not written by this kernel; skip: set by this frame's gate (above / k_gate_late)
         // event ordering runs no gate at all: a frame published WITHOUT features (a pooled seat that had no frame in this step, a buffer given up on) is found
         // here -- the feature stream's k_feat_done, ordered in front of this kernel by the event, wrote the word.  (Behind k_gate_late the flag is set already.)
-        if (!gated && __hip_atomic_load(&S.fb[par].fc->skip_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == seq) {
+        if (!gated && frame_without_features(*S.fb[par].fc, seq)) {
             sk = 1;
             if (blockIdx.x == 0) ctl.skip = 1;  // (every workgroup decides from skip_seq itself: nobody waits for this store; the epilogue reads and clears it)
         }
@@ -421,37 +420,13 @@ __global__ __launch_bounds__(256) void k_match_map(SeqArg<BV> sa, int par, seq_t
     CandLds C;
     C.lbuf = lbuf, C.tx = s_tx, C.ty = s_ty, C.tc = s_tc, C.w2c = w2c;
     // the points [0, early_done) were projected and listed by k_early_map while the previous frame finished
-    candidates_body<MODE_MAP, true>(S, 0, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256, (ctl.early_ran_seq == seq) ? max(ctl.early_done, 0) : 0, -1);
+    candidates_body<MODE_MAP, true>(S, 0, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256, early_points_ran(&ctl, seq), -1);
 }
 
-// k_early_map : projection + candidate lists of the map points that survived the PREVIOUS frame's clean-up, launched on its own
-// stream as soon as that frame's pose is known (after its k_pnp) -- k_triangulate of that frame (staged update, triangulation) only appends points
-// behind early_done.  Nothing of the per-frame state is published here (k_match_map does that when the previous frame is
-// complete); the prediction is recomputed from the same persistent inputs, so both kernels see the same pose.
-// k_gate : one wavefront per sequence at the head of the early stream; returns when the previous frame's k_pnp has published
-// its sequence number (or after 20 ms of wall clock: then the early kernels stand down and the late ones do all the work)
-// head of the feature stage: returns when the tracking chain of the frame that used this feature buffer last (NPAR frames ago)
-// is finished.  Polled: a feature stream parked on an event barrier stalls the queues that share its hardware pipe -- with
+// k_gate_buf : head of the feature stage: returns when the tracking chain of the frame that used this feature buffer last (NPAR frames ago)
+// is finished (gate_buf_wait).  Polled: a feature stream parked on an event barrier stalls the queues that share its hardware pipe -- with
 // the barrier, SHORTENING the feature chain made the whole pipeline slower -- and the event record costs the tracking stream
 // 3-4 us per frame.  (LVT_AMD_ORDERING=events uses the barrier instead of this kernel.)
-// the wait of k_gate_buf for one sequence (one thread): the tracking chain of frame `want` has released feature buffer `par`
-__device__ __forceinline__ void gate_buf_wait(const Seq &S, seq_t want, int par) {
-    Ctl &ctl = *S.ctl;
-    const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load(&ctl.track_done_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
-        __builtin_amdgcn_s_sleep(8);
-        if (wall_clock64() - t0 > 200000000ull) {  // 2 s: the tracking stream is wedged, or a tool serialises the dispatches and this
-            // kernel holds the slot.  The buffer still belongs to an older frame: this frame's feature kernels leave it alone
-            // (FeatCtl::poison), k_brief publishes "no features" (skip_seq) and the tracking chain SKIPS the frame -- last pose
-            // returned, state kept, reported through lvt_amd_last_error.  Never LOST: that state is sticky and, in the reference,
-            // a matter of match counts only.
-            S.fb[par].fc->poison = 1;
-            atomicAdd(&ctl.gate_fatal, 1);
-            __threadfence();
-            break;
-        }
-    }
-}
 __global__ __launch_bounds__(64) void k_gate_buf(const Seq *seqs, seq_t want, int par) {
     if (threadIdx.x != 0) return;
     gate_buf_wait(seq_const(seqs, blockIdx.z), want, par);
@@ -462,25 +437,20 @@ __global__ __launch_bounds__(64) void k_gate_buf(const Seq *seqs, seq_t want, in
 // every workgroup's release fence is an L2 write-back.)
 __global__ void k_feat_done(const Seq *seqs, int par, seq_t seq) {
     if (threadIdx.x != 0) return;
-    FeatCtl &fc = *seq_const(seqs, blockIdx.x).fb[par].fc;
-    seq_const(seqs, blockIdx.x).ctl->dbg[47] = (long long)wall_clock64();  // (written from the feature stream: the frame it belongs to may differ)
-    if (fc.poison) {  // the frame has no features (k_gate_buf timed out): say so to the gates of the other streams, then release the flag
-        fc.skip_seq = seq;
-        fc.poison = 0;
-    }
-    __threadfence();
-    atomicExch(&fc.feat_seq, seq);
+    const Seq &S = seq_const(seqs, blockIdx.x);
+    publish_features(S, *S.fb[par].fc, seq);
 }
 
 // behind k_candidates<ROW>: this frame's row-match candidate lists are complete (k_triangulate's head polls the word)
 __global__ void k_row_done(const Seq *seqs, int par, seq_t seq) {
     if (threadIdx.x != 0) return;
     FeatCtl &fc = *seq_const(seqs, blockIdx.x).fb[par].fc;
-    if (__hip_atomic_load(&fc.feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) return;  // (see k_candidates)
-    __threadfence();
-    atomicExch(&fc.row_seq, seq);
+    if (!seq_reached(fc.feat_seq, seq)) return;  // (see k_candidates)
+    publish_seq(fc.row_seq, seq);
 }
 
+// k_gate : one wavefront per sequence at the head of the early stream; returns when this frame's features are there and the previous frame's
+// k_pnp has published its sequence number (or after GATE_STAND_DOWN on either: then the early kernels stand down and the late ones do all the work)
 template <bool BV>
 __global__ __launch_bounds__(64) void k_gate(SeqArg<BV> sa, int par, seq_t want, seq_t seq, int test_timeout) {
     if (threadIdx.x == 0 && blockIdx.x == 0) sa.get().ctl->dbg[32] = (long long)wall_clock64();
@@ -493,56 +463,34 @@ __global__ __launch_bounds__(64) void k_gate(SeqArg<BV> sa, int par, seq_t want,
         ok = false;
     } else {
         // both conditions are polled: a stream parked on an event barrier stalls the other queues of its hardware pipe until
-        // a time slice expires (the feature stream did not advance while this stream waited for the NEXT frame's features).
-        // After 20 ms of wall clock (100 MHz) on either, the early kernels stand down and the late ones do all the work --
-        // that happens when a tool serialises the dispatches of all queues (rocprofv3 --pmc): this kernel then holds the only
-        // dispatch slot and what it waits for cannot start.
-        const unsigned long long t0 = wall_clock64();
-        // (a) this frame's features
-        while (__hip_atomic_load(&fc.feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) {
-            __builtin_amdgcn_s_sleep(8);
-            if (wall_clock64() - t0 > 2000000ull) {
-                atomicAdd(&ctl.gate_timeouts, 1);
-                ok = false;
-                break;
-            }
-        }
-        if (ok && __hip_atomic_load(&fc.skip_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == seq) ok = false;  // published, but empty (k_gate_buf)
-        // (b) the previous frame's k_pnp
-        const unsigned long long t1 = wall_clock64();
+        // a time slice expires (the feature stream did not advance while this stream waited for the NEXT frame's features)
+        ok = wait_seq(fc.feat_seq, seq, GATE_STAND_DOWN);  // (a) this frame's features
+        if (!ok) atomicAdd(&ctl.gate_timeouts, 1);
+        if (ok && frame_without_features(fc, seq)) ok = false;  // published, but empty (k_gate_buf)
+        const unsigned long long t1 = wall_clock64();  // (b) the previous frame's k_pnp
         ctl.dbg[35] = (long long)t1;  // (tools/timeline.py: when this frame's features were seen)
-        while (ok && __hip_atomic_load(&ctl.pnp_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(8);
-            if (wall_clock64() - t1 > 2000000ull) {
-                atomicAdd(&ctl.gate_timeouts, 1);
-                ok = false;
-                break;
-            }
+        if (ok && !wait_seq(ctl.pnp_seq, want, GATE_STAND_DOWN, t1)) {
+            atomicAdd(&ctl.gate_timeouts, 1);
+            ok = false;
         }
     }
     // claim the frame (or record that nothing will be done); if the tracking stream has cancelled it meanwhile, stand down
-    const seq_t mine = 4u * seq + (ok ? 1u : 3u);
-    seq_t cur = __hip_atomic_load(&ctl.early_state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    for (;;) {
-        if (cur >= 4u * seq + 1u) {
-            ok = false;
-            break;
-        }
-        const seq_t seen = atomicCAS(&ctl.early_state, cur, mine);
-        if (seen == cur) break;
-        cur = seen;
-    }
+    ok = early_claim(ctl, seq, ok);
     ctl.gate_ok = ok ? seq : (seq_t)0;
     ctl.dbg[33] = (long long)wall_clock64();
 }
 
+// k_early_map : projection + candidate lists of the map points that survived the PREVIOUS frame's clean-up, launched on its own
+// stream as soon as that frame's pose is known (after its k_pnp) -- k_triangulate of that frame (staged update, triangulation) only appends points
+// behind early_done.  Nothing of the per-frame state is published here (k_match_map does that when the previous frame is
+// complete); the prediction is recomputed from the same persistent inputs, so both kernels see the same pose.
 template <bool BV>
 __global__ __launch_bounds__(256) void k_early_map(SeqArg<BV> sa, int par, seq_t seq, int only_fb) {
     if (threadIdx.x == 0 && blockIdx.x == 0) sa.get().ctl->dbg[34] = (long long)wall_clock64();
     const Seq &S = sa.get();
     if (only_fb && !S.lists_fb[0]) return;  // (k_hamming_batched_lists<MODE_MAP> has projected and listed these points)
     Ctl &ctl = *S.ctl;
-    const int n_early = (ctl.gate_ok == seq) ? ctl.early_done : 0;
+    const int n_early = early_points_claimed(&ctl, seq);
     if (n_early <= 0) return;  // first frame, LOST, the previous frame did not reach its pose refinement, or the gate timed out
     __shared__ double w2c[12];
     if (threadIdx.x == 0) {
@@ -1255,7 +1203,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_track_mid(SeqArg<BV> sa, int pa
     if (ctl.first_frame) return;
     RESOLVE_LDS_DECL
     {   // find_matches pass 1: the points [0, early_done) were resolved by k_early_mid; the greedy scan continues behind them
-        const int n_early = (ctl.early_ran_seq == seq) ? max(ctl.early_done, 0) : 0;
+        const int n_early = early_points_ran(&ctl, seq);
         resolve_body<MODE_MAP>(S, ctl, 0, par, L, r_tab, n_early > 0 ? 2 : 0, n_early);
         __syncthreads();
         if (threadIdx.x == 0) ctl.early_done = 0;  // consumed; this frame's k_pnp publishes the next one
@@ -1288,7 +1236,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_early_mid(SeqArg<BV> sa, int pa
     if (threadIdx.x == 0 && blockIdx.x == 0) sa.get().ctl->dbg[36] = (long long)wall_clock64();
     const Seq &S = sa.get();
     Ctl &ctl = *S.ctl;
-    const int n_early = (ctl.gate_ok == seq) ? ctl.early_done : 0;
+    const int n_early = early_points_claimed(&ctl, seq);
     if (n_early > 0) {
         RESOLVE_LDS_DECL
         resolve_body<MODE_MAP>(S, ctl, 0, par, L, r_tab, 1, n_early);
@@ -1298,7 +1246,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_early_mid(SeqArg<BV> sa, int pa
     if (threadIdx.x == 0) {  // the tracking stream's gate polls this: the early stream has finished what it claimed
         ctl.dbg[37] = (long long)wall_clock64();
         __threadfence();
-        if (n_early > 0 || ctl.gate_ok == seq) atomicCAS(&ctl.early_state, 4u * seq + 1u, 4u * seq + 2u);
+        if (n_early > 0 || ctl.gate_ok == seq) early_finish(ctl, seq);
     }
 }
 
@@ -1322,33 +1270,6 @@ __device__ __forceinline__ void deliver_record(const Ctl &ctl, Ctl *rec_out, seq
 // (the last enqueued frame has no successor: the host launches this when it is asked for that frame's result)
 __global__ __launch_bounds__(64) void k_deliver(const Seq *seqs, Ctl *rec_out, seq_t *done_out, seq_t seq) {
     deliver_record(*seq_const(seqs, blockIdx.z).ctl, rec_out + blockIdx.z, done_out + blockIdx.z, seq, 64);
-}
-
-// the tracking stream's wait for the early stream (one thread; see k_gate_late / k_match_map)
-__device__ __forceinline__ void gate_late_poll(Ctl &ctl, FeatCtl &fc, seq_t seq) {
-    unsigned long long t0 = wall_clock64();
-    for (;;) {
-        const seq_t cur = __hip_atomic_load(&ctl.early_state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur >= 4u * seq + 2u) break;  // finished, stood down or cancelled
-        __builtin_amdgcn_s_sleep(8);
-        if (wall_clock64() - t0 > 6000000ull) {  // 60 ms: the early stream's own gate gives up after 2 x 20
-            atomicAdd(&ctl.gate_timeouts, 1);
-            // not claimed yet: cancel it (an early kernel arriving later does nothing).  Claimed: its kernels are running, wait on.
-            if (cur < 4u * seq + 1u && atomicCAS(&ctl.early_state, cur, 4u * seq + 3u) == cur) break;
-            t0 = wall_clock64();
-        }
-    }
-    // this stream has no barrier of its own on the frame's features (the early stream normally vouches for them): make sure
-    t0 = wall_clock64();
-    while (__hip_atomic_load(&fc.feat_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) {
-        __builtin_amdgcn_s_sleep(8);
-        if (wall_clock64() - t0 > 200000000ull) {  // 2 s: the feature stream is wedged -- nothing valid to track on: the frame is
-            ctl.skip = 1;                           // skipped (last pose, state kept), reported through lvt_amd_last_error
-            atomicAdd(&ctl.gate_fatal, 1);
-            break;
-        }
-    }
-    if (__hip_atomic_load(&fc.skip_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == seq) ctl.skip = 1;  // published without features (k_gate_buf gave up)
 }
 
 template <bool BV>
@@ -1892,8 +1813,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp(SeqArg<BV> sa, int par, seq
     Ctl &ctl = *S.ctl;
     if (!ctl.active || ctl.first_frame || ctl.lost_now) {
         if (threadIdx.x == 0) {  // nothing for the next frame to start on (early_done is 0), but its gate must not wait
-            __threadfence();
-            atomicExch(&ctl.pnp_seq, seq);
+            publish_seq(ctl.pnp_seq, seq);
         }
         return;
     }
@@ -1917,8 +1837,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp(SeqArg<BV> sa, int par, seq
         ctl.early_done = *S.map_n;  // the map after clean_untracked_points: the next frame may start on these points now
         ctl.early_accepted = 0;
         ctl.dbg[45] = (long long)wall_clock64();
-        __threadfence();
-        atomicExch(&ctl.pnp_seq, seq);  // release: everything the next frame's early kernels read is final
+        publish_seq(ctl.pnp_seq, seq);  // everything the next frame's early kernels read is final
         if (pose_out) {  // synchronous call: hand the pose to the waiting host now (no later kernel of this frame changes it or the state)
             PoseRec &o = pose_out[blockIdx.z];
             for (int k = 0; k < 9; k++) o.R[k] = ctl.out_R[k];
@@ -2208,25 +2127,19 @@ __global__ __launch_bounds__(1024) void k_triangulate(SeqArg<BV> sa, int par, se
     if (run) {
     int n_pairs = 0;
     if (S.prm.sensor == 1) {  // row_match (lvt_image_features_handler.cpp:299-326): greedy resolution of the lists k_candidates<ROW> built
-        // (on the early stream behind k_early_mid: normally finished ~70 us ago.  One workgroup polling holds one CU.  2 s without
-        //  the lists: nothing valid to triangulate from -> LOST, reported)
+        // on the early stream behind k_early_mid.  One workgroup polling holds one CU.
         if (row_gated) {
-            // (the lists are normally ~70 us old by now.  5 ms without them -- the early stream's gate stood down, or the stream is
+            // (the lists are normally ~70 us old by now.  ROW_LISTS_FALLBACK without them -- the early stream's gate stood down, or the stream is
             //  held up -- and this workgroup builds them itself: the features are complete (this frame's gate has seen them), the lists
             //  are a function of the two feature sets only, so a late k_candidates<ROW> writing the same words is harmless.  A
             //  time-out costs time, never the track.)
             __shared__ int s_row_fallback;
             if (tid == 0) {
                 FeatCtl &fc = *S.fb[par].fc;
-                const unsigned long long t0 = wall_clock64();
                 int fb = (row_gated == 2) ? 1 : 0;  // (2: tests force the fallback -- it then runs beside the early stream's list kernel)
-                while (!fb && __hip_atomic_load(&fc.row_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (wall_clock64() - t0 > 500000ull) {
-                        atomicAdd(&ctl.gate_timeouts, 1);
-                        fb = 1;
-                        break;
-                    }
+                if (!fb && !wait_seq(fc.row_seq, seq, ROW_LISTS_FALLBACK)) {
+                    atomicAdd(&ctl.gate_timeouts, 1);
+                    fb = 1;
                 }
                 if (fb) ctl.counts[C_ROW_FALLBACK] = 1;
                 s_row_fallback = fb;
@@ -2345,8 +2258,7 @@ __global__ __launch_bounds__(1024) void k_triangulate(SeqArg<BV> sa, int par, se
         if (run) {  // bring-up stamps of a triangulation frame (tools/cells_phases.py): staged update, row resolution, the rest
             ctl.dbg[20] = tq1 - tq0, ctl.dbg[21] = tq2 - tq1, ctl.dbg[22] = clock64() - tq2;
         }
-        __threadfence();
-        atomicExch(&ctl.track_done_seq, seq);  // this frame's feature buffer may be refilled (k_gate_buf polls this)
+        publish_seq(ctl.track_done_seq, seq);  // this frame's feature buffer may be refilled (k_gate_buf polls this)
     }
     // ---- the frame's result record (synchronous calls and the events-only ordering: here; otherwise by the next frame's k_gate_late)
     __syncthreads();

@@ -91,10 +91,7 @@ struct Ctl {
     // for an in-stream boundary): k_pnp publishes its frame's sequence number, a one-wave gate kernel at the head of the early
     // stream polls it (with a wall-clock time-out), k_early_mid confirms that the early part really ran
     seq_t pnp_seq, gate_ok, early_ran_seq;
-    // ownership of frame seq's early work, 4 * seq + phase, only ever increasing: 1 = the early stream has claimed it (running),
-    // 2 = it has finished with results, 3 = nothing was done (it stood down, or the tracking stream cancelled it after a
-    // time-out: an early kernel that arrives later finds the claim taken and does nothing)
-    seq_t early_state;
+    seq_t early_state;     // ownership of frame seq's early work, early_word(seq, phase), only ever increasing (lvt_handover.h, which has the whole protocol of these words)
     seq_t track_done_seq;  // last frame whose tracking chain has finished with its feature buffer (polled by k_gate_buf)
     seq_t late_gate_seq;   // k_match_map's folded gate: workgroup 0 ALONE waits, decides (skip / time-outs) and publishes the frame here; the others poll it
     int gate_timeouts;  // a gate gave up waiting and its stream stood down / cancelled (results unaffected)

@@ -537,7 +537,7 @@ static Ctl fresh_ctl(const Context *c) {
     z.out_R[0] = z.out_R[4] = z.out_R[8] = 1.0;
     z.out_status = 1;
     z.pnp_seq = (seq_t)c->enq;  // the next frame's gate waits for this value: nothing is pending
-    z.early_state = 4u * (seq_t)c->enq + 3u;
+    z.early_state = early_word((seq_t)c->enq, EARLY_NOTHING);
     z.track_done_seq = (seq_t)c->enq;
     z.late_gate_seq = (seq_t)c->enq;
     z.gate_timeouts = c->gate_timeouts_seen, z.gate_fatal = c->gate_fatal_seen;  // (the host compares these running counters with what it has seen)
@@ -908,6 +908,8 @@ struct HostTimer {
     explicit HostTimer(double *a) : acc(a), t0(std::chrono::steady_clock::now()) {}
     ~HostTimer() { *acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 };
+// the frame (sequence number) that used the feature buffer of the frame about to be enqueued last: gate_buf_wait's `want` (only from frame NPAR on)
+static seq_t buffer_last_user(const Context *c) { return (seq_t)(c->enq + 1 - NPAR); }
 static void enqueue_frame(Context *c) {
     HostTimer ht(&c->host_enq_us);
     c->host_enq_n++;
@@ -1018,7 +1020,7 @@ static void enqueue_frame(Context *c) {
     const bool feat_pack = B > 1 && Bz <= FEAT_PACK && c->feat_pack;  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
         if (!evo) {  // polls; see k_gate_buf (ev_done is never recorded in this mode)
-            if (!feat_pack) hipLaunchKernelGGL(k_gate_buf, dim3(1, 1, Bz), dim3(64), 0, sf, S, (seq_t)(c->enq + 1 - NPAR), par);
+            if (!feat_pack) hipLaunchKernelGGL(k_gate_buf, dim3(1, 1, Bz), dim3(64), 0, sf, S, buffer_last_user(c), par);
         } else if (c->switched_at < 0 || (long)c->enq - NPAR >= c->switched_at) {  // (frames from before a switch of the ordering: covered by ev_switch)
             (void)hipStreamWaitEvent(sf, c->ev_done[(int)((c->enq - NPAR) % RING)], 0);
         }
@@ -1030,7 +1032,7 @@ static void enqueue_frame(Context *c) {
             FrameArgsPack pk;
             std::memset(&pk, 0, sizeof(pk));
             for (int s = 0; s < Bz; s++) pk.a[s] = fa[s];
-            LAUNCH(0, sf, k_feat_begin_pack, dim3(Bz), dim3(64), 0, S, pk, par, (seq_t)((c->enq >= NPAR && !evo) ? c->enq + 1 - NPAR : 0));
+            LAUNCH(0, sf, k_feat_begin_pack, dim3(Bz), dim3(64), 0, S, pk, par, (c->enq >= NPAR && !evo) ? buffer_last_user(c) : (seq_t)0);
         } else
             LAUNCH(0, sf, k_feat_begin, dim3(Bz), dim3(64), 0, S, fa, par);
         if (c->mixed) {  // exactly the tiles that exist, each image's placed over the XCDs by the table (build_mixed_tables)
@@ -1141,6 +1143,19 @@ static void enqueue_frame(Context *c) {
     c->enq++;
 }
 
+// spin until pinned flag `a` (or `b`, if given) carries `want`; every 2^20 spins (~10 ms) the tracking stream is asked (*q): a dead stream must not hang the caller
+enum class SpinStop { FLAG_A, FLAG_B, STREAM_ERROR, STREAM_IDLE };
+static SpinStop spin_on_flags(Context *c, seq_t want, volatile seq_t *a, volatile seq_t *b, unsigned &spins, hipError_t *q) {
+    for (;;) {
+        if (__atomic_load_n(a, __ATOMIC_ACQUIRE) == want) return SpinStop::FLAG_A;
+        if (b && __atomic_load_n(b, __ATOMIC_ACQUIRE) == want) return SpinStop::FLAG_B;
+        __builtin_ia32_pause();
+        if ((++spins & 0xFFFFF) == 0) {
+            *q = hipStreamQuery(c->stream);
+            if (*q != hipErrorNotReady) return *q == hipSuccess ? SpinStop::STREAM_IDLE : SpinStop::STREAM_ERROR;
+        }
+    }
+}
 // wait for the oldest un-collected frame; its record becomes "last"
 static void collect_oldest(Context *c) {
     HostTimer ht(&c->host_wait_us);
@@ -1159,21 +1174,15 @@ static void collect_oldest(Context *c) {
         unsigned spins = 0;
         for (int s = 0; s < Bz; s++) {
             volatile seq_t *f = c->h_done + (size_t)slot * c->B + s;
-            while (__atomic_load_n(f, __ATOMIC_ACQUIRE) != want) {
-                __builtin_ia32_pause();
-                if ((++spins & 0xFFFFF) == 0) {  // every ~10 ms: a dead stream must not hang the caller
-                    const hipError_t q = hipStreamQuery(c->stream);
-                    if (q != hipSuccess && q != hipErrorNotReady) {
-                        c->set_error(std::string("tracking stream: ") + hipGetErrorString(q));
-                        s = c->B;
-                        break;
-                    }
-                    if (q == hipSuccess && __atomic_load_n(f, __ATOMIC_ACQUIRE) != want) {  // stream empty but no flag: cannot happen
-                        c->set_error("tracking stream finished without a result record");
-                        s = c->B;
-                        break;
-                    }
-                }
+            hipError_t q = hipSuccess;
+            const SpinStop why = spin_on_flags(c, want, f, nullptr, spins, &q);
+            if (why == SpinStop::STREAM_ERROR) {
+                c->set_error(std::string("tracking stream: ") + hipGetErrorString(q));
+                break;
+            }
+            if (why == SpinStop::STREAM_IDLE && __atomic_load_n(f, __ATOMIC_ACQUIRE) != want) {  // stream empty but no flag: cannot happen
+                c->set_error("tracking stream finished without a result record");
+                break;
             }
         }
         if (c->prof) HIPCHK(c, hipStreamSynchronize(c->stream));  // the per-kernel timing events are read below
@@ -1261,25 +1270,18 @@ static bool wait_pose_or_frame(Context *c, double R[3][3], double t[3]) {
         return false;
     }
     unsigned spins = 0;
-    for (;;) {
-        if (__atomic_load_n(fp, __ATOMIC_ACQUIRE) == want) {
-            const PoseRec &p = c->h_pose[(size_t)slot * c->B];
-            if (R)
-                for (int i = 0; i < 3; i++)
-                    for (int j = 0; j < 3; j++) R[i][j] = p.R[3 * i + j];
-            if (t)
-                for (int i = 0; i < 3; i++) t[i] = p.t[i];
-            c->early_pending = true;
-            return true;
-        }
-        if (__atomic_load_n(fd, __ATOMIC_ACQUIRE) == want) break;
-        __builtin_ia32_pause();
-        if ((++spins & 0xFFFFF) == 0) {  // a dead stream must not hang the caller: collect_oldest diagnoses it
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q != hipErrorNotReady) break;
-        }
+    hipError_t q = hipSuccess;
+    if (spin_on_flags(c, want, fp, fd, spins, &q) == SpinStop::FLAG_A) {
+        const PoseRec &p = c->h_pose[(size_t)slot * c->B];
+        if (R)
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) R[i][j] = p.R[3 * i + j];
+        if (t)
+            for (int i = 0; i < 3; i++) t[i] = p.t[i];
+        c->early_pending = true;
+        return true;
     }
-    drain(c);
+    drain(c);  // the full record is there, or the stream has stopped: collect_oldest diagnoses it
     return false;
 }
 static void make_room(Context *c) {  // at most RING-1 frames un-collected before a new one is enqueued
