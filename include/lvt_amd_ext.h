@@ -241,7 +241,9 @@ LVT_API int lvt_amd_get_ordering(lvt_handle h);
 /* raw per-pixel intermediates of the last frame: what = 0 score map (u8, rows x pitch),
  * 1 box-sum map (u16, rows x pitch), 2 the rectified image of a handle with rectifiers (u8, rows x pitch; 0 bytes without them),
  * 3 the converted gray image of a handle with a colour pixel format (u8, rows x pitch, before rectification; 0 bytes on a gray handle, and when the
- *   last frame was handed in before the colour format was set: nothing was converted for it).
+ *   last frame was handed in before the colour format was set: nothing was converted for it),
+ * 4 the registered depth plane of a handle with a depth camera (fp32, rows x pitch; 0 bytes without one, and when the last frame was handed in before
+ *   the camera was set).
  * returns bytes written, pitch via *pitch_out (in elements). */
 LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int cap_bytes, int *pitch_out);
 
@@ -333,6 +335,49 @@ enum { LVT_AMD_PIX_GRAY8 = 0, LVT_AMD_PIX_BGR8 = 1, LVT_AMD_PIX_RGB8 = 2, LVT_AM
 LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format);                 /* 0 / -1 */
 LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format);  /* 0 / -1 */
 LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq);                    /* format, -1: bad handle / seq */
+
+/* UNREGISTERED DEPTH: depth registration inside the tracker's feature stage.  Without a depth camera the depth plane of an RGB-D frame is taken as registered
+ * to the gray image (TUM's files, sensors that register in hardware).  A depth camera says that the plane is delivered in ANOTHER camera -- its own size,
+ * its own pinhole, a rigid offset from the colour camera (RealSense D4xx: the left infrared camera; Azure Kinect, Orbbec: a second camera a few centimetres
+ * away).  It is a property of the handle, or of one sequence of a batch, like the pixel format; the record is copied.  It is not state: it is neither in
+ * snapshots nor restored by them.  Once it is set, EVERY RGB-D frame-taking call on that handle or sequence -- lvt_amd_track_rgbd[_async],
+ * lvt_amd_track_rgbd16[_async], lvt_amd_track_rgbd_device[_async], lvt_amd_batch_track_rgbd_device_async (uniform and mixed, sit-outs included) -- takes the depth
+ * plane as the sensor delivers it, cam.width x cam.height, in either depth format.  Two launches of the feature stage (k_depth_clear at its head,
+ * k_depth_register directly in front of the feature gather) build the registered fp32 plane the tracker samples; a handle or sequence that never sets a
+ * camera launches exactly what it did before, and NULL returns a handle to that path.
+ *  The definition -- fp32 throughout, one IEEE operation per written operation.  K_c, k1 k2 p1 p2 k3, W, H are the sequence's own lvt_amd_params; the
+ *  registered plane lives on the raw, distorted colour pixel grid (where the feature gather samples it).  For depth pixel (i, j), column i, row j:
+ *   1. z = the fp32 element, or (float)raw16 * depth_scale.  Skipped unless z is finite and > 0.
+ *   2. proj(a, b):  X = ((a - cx_d) / fx_d) * z,  Y = ((b - cy_d) / fy_d) * z;  Xc = (R00 X + R01 Y) + R02 z + t0, likewise Yc, Zc, left to right;
+ *      x = Xc / Zc, y = Yc / Zc;  r2 = x x + y y;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3));  xd = x rad + (2 p1 x y + p2 (r2 + 2 x x));
+ *      yd = y rad + (p1 (r2 + 2 y y) + 2 p2 x y);  u = xd fx + cx,  v = yd fy + cy.
+ *   3. (u0, v0) = proj(i - 0.5, j - 0.5), (u1, v1) = proj(i + 0.5, j + 0.5), Zc of proj(i, j).  Skipped unless that Zc is finite and > 0 and u0, v0, u1, v1
+ *      are finite with magnitude < 1e6.
+ *   4. the footprint is the pixel centres of the half-open box (the top-left rule): x0 = ceil(u0), x1 = ceil(u1) - 1, y0 = ceil(v0), y1 = ceil(v1) - 1;
+ *      skipped when x1 - x0 >= 16 or y1 - y0 >= 16 (a calibration error); then clipped to [0, W-1] x [0, H-1].
+ *   5. every covered pixel takes min(current, Zc); the plane starts at +inf, and a pixel nothing lands on stays +inf: beyond every far plane, filtered like
+ *      any other out-of-range depth.  No hole filling, no smoothing.
+ *  - n_rows / n_cols stay the GRAY image's.  Host depth buffers are tightly packed at the camera's size; page-locked ones are read in place as before.
+ *  - device depth planes: a pitch of at least cam.width elements; pointer and pitch aligned to the element, as before.
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error): a stereo handle, a pooled or automatic seat, seq out of range, the batch call on a handle
+ *    that is not a batch and the other way round, a handle with frames in flight (set the camera before the first frame or after every frame has been
+ *    collected), a bad record -- width or height outside 1 ... 8192, a non-finite field, fx or fy <= 0.  A successful set counts as use of an lvt_create handle.
+ *  - lvt_amd_get_depth_camera: 1 = a camera is set (copied to *out), 0 = none, -1 = bad handle / seq.
+ *  - lvt_amd_get_plane(h, 0, 4, ...) reads the registered plane of the last frame back (fp32, rows x pitch; 0 bytes on a handle without a camera);
+ *    lvt_amd_profile_read reports the launches as "k_depth_clear" and "k_depth_register" (a handle with a camera only).
+ *  - lvt_amd_register_depth_device: the stage alone on caller data (device pointers; `colour`: fx fy cx cy, k1 k2 p1 p2 k3, img_width, img_height are read),
+ *    for differential tests: d_out, out_pitch_bytes / 4 >= img_width words per row, every word of img_height rows is written.  0 / -1. */
+typedef struct lvt_amd_depth_camera {   /* the camera the depth plane is delivered in */
+    int   width, height;                 /* of the depth plane, pixels */
+    float fx, fy, cx, cy;                /* pinhole, no distortion */
+    float R[9], t[3];                    /* row-major; p_colour = R p_depth + t, metres */
+} lvt_amd_depth_camera;
+LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam);                /* NULL: registered frames again; 0 / -1 */
+LVT_API int lvt_amd_batch_set_depth_camera(lvt_handle h, int seq, const lvt_amd_depth_camera *cam);
+LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out);             /* 1 set, 0 none, -1 bad handle / seq */
+LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour,
+                                          const void *d_depth, int depth_pitch_bytes, int depth_format, float depth_scale,
+                                          void *d_out /* fp32 */, int out_pitch_bytes, void *hip_stream);
 
 /* ---- SNAPSHOTS: one sequence's state saved, restored, moved between handles and seats -------------------------------------------------
  * A tracker's state lives in HBM: its control record, the local map, the staged points and the motion model.  A snapshot is a copy of it, device-resident and

@@ -311,6 +311,11 @@ class lvt_system {
      * record is then zero-filled, status 0. */
     bool enable_pose_info(bool enable = true) { return lvt_amd_enable_pose_info(m_handle, enable ? 1 : 0) == 0; }
     bool get_pose_info(lvt_amd_pose_info &out) { return lvt_amd_get_pose_info(m_handle, 0, &out) == 1; }
+    /* ADDITIVE: the camera an RGB-D sensor delivers its depth plane in (lvt_amd_depth_camera, include/lvt_amd_ext.h).  From now on the depth plane handed to the
+     * C-ABI's RGB-D calls on native_handle() is the sensor's own, cam->width x cam->height, and the feature stage registers it to the gray image; nullptr: registered
+     * frames again.  (track() / track_async() take ONE size for both views: a sensor whose depth image has another size goes through lvt_amd_track_rgbd*.)
+     * false: refused (last_error() says why), nothing changed. */
+    bool set_depth_camera(const lvt_amd_depth_camera *cam) { return lvt_amd_set_depth_camera(m_handle, cam) == 0; }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
         m_state = lvt_amd_wait_pose(m_handle, q, p);

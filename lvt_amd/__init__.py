@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "lvt_amd_batch_reset",
     "lvt_amd_enable_pose_info", "lvt_amd_get_pose_info", "lvt_amd_pose_info_eval", "lvt_amd_pose_info_to_ros",
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
+    "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
 ]
 
 N_COUNTS = 32
@@ -197,6 +198,12 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, restype
+    for name, argtypes in (   # (unregistered depth: likewise)
+            ("lvt_amd_set_depth_camera", [vp, vp]), ("lvt_amd_batch_set_depth_camera", [vp, C.c_int, vp]), ("lvt_amd_get_depth_camera", [vp, C.c_int, vp]),
+            ("lvt_amd_register_depth_device", [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -216,6 +223,54 @@ def _u8(img, bpp=1):
     elif a.ndim != 3 or a.shape[2] != bpp:
         raise ValueError(f"an image of shape {a.shape} on a handle whose pixel format has {bpp} bytes per pixel: expected (H, W, {bpp})")
     return a
+
+
+class DepthCamera(C.Structure):
+    """lvt_amd_depth_camera: the camera an RGB-D sensor delivers its depth plane in (include/lvt_amd_ext.h, UNREGISTERED DEPTH) -- its image size, its pinhole
+    (no distortion) and p_colour = R p_depth + t in metres"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("_R", C.c_float * 9), ("_t", C.c_float * 3)]
+
+    def __init__(self, width=0, height=0, fx=0.0, fy=0.0, cx=0.0, cy=0.0, R=None, t=None):
+        super().__init__(int(width), int(height), float(fx), float(fy), float(cx), float(cy))
+        self.R = np.eye(3) if R is None else R
+        self.t = np.zeros(3) if t is None else t
+
+    @property
+    def R(self) -> np.ndarray:
+        return np.array(self._R, dtype=np.float32).reshape(3, 3)
+
+    @R.setter
+    def R(self, v):
+        self._R = (C.c_float * 9)(*[float(x) for x in np.asarray(v, dtype=np.float64).reshape(9)])
+
+    @property
+    def t(self) -> np.ndarray:
+        return np.array(self._t, dtype=np.float32)
+
+    @t.setter
+    def t(self, v):
+        self._t = (C.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float64).reshape(3)])
+
+    def to_bytes(self) -> bytes:
+        return bytes(memoryview(self))
+
+
+def _depth_camera_of(handle, seq):
+    cam = DepthCamera()
+    rc = load_library().lvt_amd_get_depth_camera(handle, int(seq), C.byref(cam))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_depth_camera: bad handle or no sequence {seq}")
+    return cam if rc == 1 else None
+
+
+def register_depth_device(cam: DepthCamera, params: LvtParameters, d_depth: int, depth_pitch: int, depth_format: int, depth_scale: float, d_out: int,
+                          out_pitch: int, stream: int = 0) -> int:
+    """stage entry: the depth registration alone on device planes (pitches in bytes; d_out fp32, out_pitch / 4 >= img_width words per row, img_height rows, every
+    word written); 0 / -1"""
+    pod = params.to_pod()
+    return load_library().lvt_amd_register_depth_device(C.byref(cam), C.byref(pod), C.c_void_p(d_depth), int(depth_pitch), int(depth_format), float(depth_scale),
+                                                        C.c_void_p(d_out), int(out_pitch), C.c_void_p(stream))
 
 
 class SnapshotInfo(C.Structure):
@@ -441,10 +496,10 @@ class LvtSystem:
         elif isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
                 raise ValueError("a uint16 depth image needs depth_scale (metres per raw unit)")
-            d = np.ascontiguousarray(img2)
+            d = self._depth(np.ascontiguousarray(img2))
             load_library().lvt_amd_track_rgbd16(self._h, _p(a), _p(d), float(depth_scale), a.shape[0], a.shape[1], _p(R), _p(t))
         else:
-            d = np.ascontiguousarray(img2, dtype=np.float32)
+            d = self._depth(np.ascontiguousarray(img2, dtype=np.float32))
             load_library().lvt_amd_track_rgbd(self._h, _p(a), _p(d), a.shape[0], a.shape[1], _p(R), _p(t))
         return R, t
 
@@ -491,9 +546,9 @@ class LvtSystem:
         if isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
                 raise ValueError("a uint16 depth image needs depth_scale (metres per raw unit)")
-            d = img2 if img2.flags.c_contiguous else np.ascontiguousarray(img2)
+            d = self._depth(img2 if img2.flags.c_contiguous else np.ascontiguousarray(img2))
             return load_library().lvt_amd_track_rgbd16_async(self._h, _p(a), _p(d), float(depth_scale), a.shape[0], a.shape[1])
-        d = img2 if (isinstance(img2, np.ndarray) and img2.dtype == np.float32 and img2.flags.c_contiguous) else np.ascontiguousarray(img2, dtype=np.float32)
+        d = self._depth(img2 if (isinstance(img2, np.ndarray) and img2.dtype == np.float32 and img2.flags.c_contiguous) else np.ascontiguousarray(img2, dtype=np.float32))
         return load_library().lvt_amd_track_rgbd_async(self._h, _p(a), _p(d), a.shape[0], a.shape[1])
 
     def track_async_ptr(self, p_left: int, p_right: int, rows: int, cols: int) -> int:
@@ -529,6 +584,26 @@ class LvtSystem:
 
     def pixel_format(self) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, 0)
+
+    def set_depth_camera(self, cam) -> int:
+        """a DepthCamera: every RGB-D frame handed to this system from now on brings its depth plane as the sensor delivers it -- (cam.height, cam.width),
+        float32 or uint16 -- and the feature stage registers it to the gray image; None: registered frames again.  0: done; -1: refused (last_error())."""
+        rc = load_library().lvt_amd_set_depth_camera(self._h, C.byref(cam) if cam is not None else None)
+        if rc == 0:
+            self._depth_shape = (int(cam.height), int(cam.width)) if cam is not None else None
+        return rc
+
+    def _depth(self, d):
+        """the depth array of a host call: with a depth camera set the library reads cam.height x cam.width elements, and the C-ABI has no size argument for
+        them -- an array of any other shape would be read past its end"""
+        want = getattr(self, "_depth_shape", None)
+        if want is not None and tuple(d.shape) != want:
+            raise ValueError(f"a depth image of shape {tuple(d.shape)} on a system whose depth camera delivers {want}")
+        return d
+
+    def depth_camera(self):
+        """the DepthCamera that is set, or None"""
+        return _depth_camera_of(self._h, 0)
 
     def enable_pose_info(self, on: bool = True) -> int:
         """from the next frame on every tracked frame carries a PoseInfo (one more launch per frame, k_pose_info).  0: done; -1: refused (last_error())"""
@@ -613,7 +688,8 @@ class LvtSystem:
 
     def plane(self, eye=0, what=0):
         """what=0: corner score map (u8), what=1: 9x9 box sums (u16), what=2: the rectified image of a system with rectifiers (u8; an empty array
-        without them), what=3: the converted gray image of a system with a colour pixel format (u8, before rectification; empty on a gray system);
+        without them), what=3: the converted gray image of a system with a colour pixel format (u8, before rectification; empty on a gray system),
+        what=4: the registered depth plane of a system with a depth camera (float32, +inf where nothing landed; empty without one);
         returns (rows, pitch) array"""
         cap = 64 << 20
         buf = np.zeros(cap // 8, dtype=np.uint64)
@@ -624,7 +700,7 @@ class LvtSystem:
         raw = buf.view(np.uint8)[:nbytes]
         if nbytes == 0:
             return np.zeros((0, 0), np.uint8)
-        a = raw.view(np.uint16 if what == 1 else np.uint8)
+        a = raw.view(np.float32 if what == 4 else np.uint16 if what == 1 else np.uint8)
         return a.reshape(-1, pitch.value).copy()
 
 
@@ -706,6 +782,13 @@ class LvtBatch:
 
     def pixel_format(self, seq: int) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, int(seq))
+
+    def set_depth_camera(self, seq: int, cam) -> int:
+        """LvtSystem.set_depth_camera for sequence `seq` of the batch: its depth planes are the sensor's from then on, the other sequences' are not"""
+        return load_library().lvt_amd_batch_set_depth_camera(self._h, int(seq), C.byref(cam) if cam is not None else None)
+
+    def depth_camera(self, seq: int):
+        return _depth_camera_of(self._h, seq)
 
     def enable_pose_info(self, on: bool = True) -> int:
         """LvtSystem.enable_pose_info for all sequences of the batch together"""

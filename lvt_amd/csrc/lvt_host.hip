@@ -19,6 +19,7 @@
 #include "k_hamming.hip"
 #include "k_lists.hip"
 #include "k_rectify.hip"
+#include "k_depthreg.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
 #include "lvt_odometry.h"
@@ -288,6 +289,19 @@ struct Context {
     uint8_t *d_col[NPAR][2] = {};
     uint8_t *d_col_ring[RING][2] = {};
     int colour_pitch() const { return (prm.W * bpp_of(0) + 63) / 64 * 64; }
+    // UNREGISTERED DEPTH (lvt_amd_set_depth_camera / lvt_amd_batch_set_depth_camera): a sequence with a depth camera takes its depth plane as the sensor
+    // delivers it -- the camera's size, either format -- through every RGB-D entry point.  As for colour frames the FrameArgs name the sensor's plane (the
+    // caller's, or the context's own pulled one), and enqueue_frame registers it into the sequence's own fp32 plane (k_depth_clear at the head of the feature
+    // stage, k_depth_register in front of k_gather) and points the frame at that.  A property of the handle, not state: snapshots neither hold nor restore it.
+    std::vector<lvt_amd_depth_camera> depth_cam;  // [B] (empty until the first set); width == 0: none
+    std::vector<float *> d_reg;                   // [B][NPAR] registered planes, fp32, plane_pitch words per row
+    int n_depth_cam = 0;                          // sequences with a depth camera
+    bool ring_registered[RING] = {};              // per un-collected / last frame: sequence 0's depth went through k_depth_register (lvt_amd_get_plane(.., 4, ..))
+    bool has_depth_cam(int s) const { return n_depth_cam > 0 && depth_cam[(size_t)s].width > 0; }
+    // the depth plane the host entry points of sequence 0 take: the camera's size where one is set, else the image's
+    size_t depth_px() const { return has_depth_cam(0) ? (size_t)depth_cam[0].width * depth_cam[0].height : (size_t)prm.W * prm.H; }
+    int depth_cols() const { return has_depth_cam(0) ? depth_cam[0].width : prm.W; }
+    size_t depth_cap = 0, depth_ring_cap = 0;     // pixels d_depth[] / d_depth_ring[] hold
     int pitch = 0;
     int *d_snap_status = nullptr;  // snapshots: [B][4] map_cur, map_n, staged_cur, staged_n as k_state_pack found them (allocated by the first take)
     long enq = 0, done = 0;    // frames enqueued / collected
@@ -329,6 +343,16 @@ struct Context {
         HIPCHK(this, hipMemset(p, 0, bytes));
         allocs.push_back(p);
         return static_cast<T *>(p);
+    }
+
+    void dfree(void *p) {  // give a dalloc'ed buffer back before the context ends (nullptr: nothing)
+        if (!p) return;
+        for (size_t i = 0; i < allocs.size(); i++)
+            if (allocs[i] == p) {
+                allocs.erase(allocs.begin() + (long)i);
+                (void)hipFree(p);
+                return;
+            }
     }
 
     bool counted = false;
@@ -767,7 +791,7 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
                     }
                     FB.ext_xy_own[e] = c->d_ext[par][e];
                 }
-                if (s == 0 && sensor == 2) c->d_depth[par] = c->dalloc<float>((size_t)q.W * q.H + 4);
+                if (s == 0 && sensor == 2) c->d_depth[par] = c->dalloc<float>((size_t)q.W * q.H + 4), c->depth_cap = (size_t)q.W * q.H;
             }
             for (int k = 0; k < 2; k++) {
                 alloc_points(c, S.map[k], MAP_MAX);
@@ -838,7 +862,7 @@ static Context *create_context(const lvt_amd_params &in, int sensor, int B, int 
 static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
-    "k_pose_info", "k_candidates(staged)", "", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "",
+    "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
     "k_state_pack", "k_state_unpack"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
@@ -1016,6 +1040,51 @@ static void enqueue_frame(Context *c) {
         }
         if (n) launch();
     }
+    // ---- unregistered depth: every sequence that has a depth camera and a frame in this step.  The descriptors are built HERE, on the host, and the frame is
+    //      pointed at the sequence's registered plane before k_score<true> / k_feat_begin* carries the record into FeatCtl::in; k_depth_clear goes out now,
+    //      k_depth_register directly in front of k_gather (a host call's depth plane arrives on the early stream: behind the wait for ev_depth).  The registered
+    //      plane (parity `par`) was read last by k_gather of frame enq - NPAR -- on this stream, enqueued before -- and the source was written by a pull this
+    //      stream waits for or belongs to the caller: stream order alone covers the hand-over, no gate.
+    c->ring_registered[slot] = false;
+    // (one table on the stack, as the colour and rectify blocks have; only a step with more than DEPTHREG_PACK registered sequences takes tables from the heap)
+    struct DepthRegStep {
+        DepthRegTable tab;
+        int n, px, words;  // descriptors, the largest depth image (pixels) and the largest registered plane (fp32 words) among them
+    };
+    DepthRegStep dreg_first;  // (written only when a sequence registers)
+    std::vector<DepthRegStep> dreg_more;
+    int n_dreg = 0;
+    auto dreg = [&](int k) -> DepthRegStep & { return k == 0 ? dreg_first : dreg_more[(size_t)k - 1]; };
+    if (c->n_depth_cam) {
+        FrameArgs *fw = &frame_args(c, slot);
+        for (int s = 0; s < Bz; s++) {
+            if (!c->has_depth_cam(s) || fw[s].absent) continue;
+            if (n_dreg == 0 || dreg(n_dreg - 1).n == DEPTHREG_PACK) {
+                if (n_dreg > 0) dreg_more.emplace_back();
+                std::memset(&dreg(n_dreg), 0, sizeof(DepthRegStep));
+                n_dreg++;
+            }
+            DepthRegStep &T = dreg(n_dreg - 1);
+            const lvt_amd_depth_camera &dc = c->depth_cam[(size_t)s];
+            const lvt_amd_params &q = c->in_prms[c->mixed ? (size_t)s : 0];
+            DepthRegImg &I = T.tab.im[T.n++];
+            I.src = fw[s].depth, I.src_pitch = fw[s].depth_pitch, I.fmt = fw[s].depth_format, I.scale = fw[s].depth_scale;
+            I.dst = c->d_reg[(size_t)s * NPAR + par], I.dst_pitch = c->h_seqs[s].plane_pitch;
+            I.dw = dc.width, I.dh = dc.height, I.fx = dc.fx, I.fy = dc.fy, I.cx = dc.cx, I.cy = dc.cy;
+            std::memcpy(I.R, dc.R, sizeof(I.R)), std::memcpy(I.t, dc.t, sizeof(I.t));
+            I.cfx = q.fx, I.cfy = q.fy, I.ccx = q.cx, I.ccy = q.cy, I.k1 = q.k1, I.k2 = q.k2, I.p1 = q.p1, I.p2 = q.p2, I.k3 = q.k3;
+            I.W = q.img_width, I.H = q.img_height;
+            T.px = std::max(T.px, dc.width * dc.height), T.words = std::max(T.words, I.dst_pitch * I.H);
+            fw[s].depth = I.dst, fw[s].depth_pitch = I.dst_pitch, fw[s].depth_format = DEPTH_F32, fw[s].depth_scale = 0.f;
+            if (s == 0) c->ring_registered[slot] = true;
+        }
+        for (int k = 0; k < n_dreg; k++) {
+            const DepthRegStep &T = dreg(k);
+            const dim3 grid(((T.words + 3) / 4 + 255) / 256, T.n);
+            if (k == 0) LAUNCH(17, sf, k_depth_clear, grid, dim3(256), 0, T.tab);
+            else hipLaunchKernelGGL(k_depth_clear, grid, dim3(256), 0, sf, T.tab);
+        }
+    }
     const bool evo = c->events_only;
     const bool feat_pack = B > 1 && Bz <= FEAT_PACK && c->feat_pack;  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
@@ -1075,6 +1144,12 @@ static void enqueue_frame(Context *c) {
     if (c->depth_wait) {
         (void)hipStreamWaitEvent(sf, c->ev_depth, 0);
         c->depth_wait = false;
+    }
+    for (int k = 0; k < n_dreg; k++) {  // the z-buffered scatter of the step's unregistered depth planes (descriptors: the head of this function)
+        const DepthRegStep &T = dreg(k);
+        const dim3 grid((T.px + 255) / 256, T.n);
+        if (k == 0) LAUNCH(21, sf, k_depth_register, grid, dim3(256), 0, T.tab);
+        else hipLaunchKernelGGL(k_depth_register, grid, dim3(256), 0, sf, T.tab);
     }
     LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
@@ -1731,6 +1806,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot == 14 && c->n_colour == 0 && c->prof_calls[14] == 0) return 0;  // (... and one without a colour sequence no k_gray_frames)
     if (slot == 15 && !c->pose_info && c->prof_calls[15] == 0) return 0;  // (... one that never enabled pose uncertainty no k_pose_info)
     if (slot >= 22 && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
+    if ((slot == 17 || slot == 21) && c->n_depth_cam == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without a depth camera no registration launches)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1960,6 +2036,17 @@ static void colour_planes(Context *c, uint8_t *(&d)[2], int eyes) {
     for (int e = 0; e < eyes; e++)
         if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)((c->prm.W * 4 + 63) / 64 * 64) * c->prm.H + 64);
 }
+// the context's own depth planes of the synchronous host calls (Context::d_depth) hold dpix pixels: allocated at creation for the image's size, again when a
+// depth camera with a larger plane has been set (no frame is in flight then)
+static void depth_planes(Context *c, size_t dpix) {
+    if (c->depth_cap >= dpix) return;
+    drain(c);  // (once per larger camera)
+    for (int par = 0; par < NPAR; par++) {
+        c->dfree(c->d_depth[par]);  // (the smaller planes: nothing in flight reads them)
+        c->d_depth[par] = c->dalloc<float>(dpix + 4);
+    }
+    c->depth_cap = dpix;
+}
 // (dfmt / dscale: element format of an RGB-D frame's depth plane `second` and metres per raw unit of a 16-bit one; cl / cr: external corner lists, nullptr: none)
 static void upload_and_track(Context *c, const unsigned char *left, const void *second, bool rgbd, int n_rows, int n_cols,
                              const float *cl, int ncl, const float *cr, int ncr, double R[3][3], double t[3], int dfmt = DEPTH_F32, float dscale = 0.f) {
@@ -1979,8 +2066,12 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     if (bpp > 1) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
     uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : c->d_img[par];
     const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
+    // (a handle with a depth camera: the depth plane is the sensor's, the camera's size -- staged, pulled and handed on unchanged)
+    const size_t dpix = rgbd ? c->depth_px() : 0;
+    const int dcols = c->depth_cols();
+    if (rgbd) depth_planes(c, dpix);
     const HostStage &stg = c->stage[par];
-    stage_reserve(c, c->stage[par], nbytes, rgbd ? npix : 0);
+    stage_reserve(c, c->stage[par], nbytes, dpix);
     // (this call only returns after the frame has been tracked, so a page-locked buffer read in place outlives every read)
     const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
     // The pulls are launched BEFORE the previous frame is collected: this frame's image planes (parity `par`) and staging buffer were last used NPAR
@@ -1999,12 +2090,12 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
         // host while the GPU runs them, the pull on the early stream (idle until this frame's features exist) beside them -- and
         // the feature stream waits for the pull in front of k_gather.  (A 16-bit plane: half those bytes, both ways; it stays 16-bit in d_depth.)
-        f = with_depth(f, c->d_depth[par], n_cols * (int)desz, dfmt, dscale);
+        f = with_depth(f, c->d_depth[par], dcols * (int)desz, dfmt, dscale);
         // (runs inside enqueue_frame: everything it needs travels by value, nothing is read that enqueue_frame advances)
-        c->before_gather = [c, v1, second, npix, par, sf, dfmt, desz]() {
-            const uint8_t *src = host_plane(c, v1, second, desz * npix, c->stage[par], c->stage[par].second);
+        c->before_gather = [c, v1, second, dpix, par, sf, dfmt, desz]() {
+            const uint8_t *src = host_plane(c, v1, second, desz * dpix, c->stage[par], c->stage[par].second);
             hipStream_t sd = c->events_only ? sf : c->stream_e;
-            launch_stage_copy(sd, src, c->d_depth[par], npix, dfmt);
+            launch_stage_copy(sd, src, c->d_depth[par], dpix, dfmt);
             if (sd != sf) {
                 (void)hipEventRecord(c->ev_depth, sd);
                 c->depth_wait = true;
@@ -2044,15 +2135,23 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp, plane = (size_t)c->pitch * c->prm.H;
     if (bpp > 1) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
     const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
+    const size_t dpix = rgbd ? c->depth_px() : 0;  // (a handle with a depth camera: the sensor's plane, the camera's size)
+    const int dcols = c->depth_cols();
     if (!c->d_img_ring[0][0]) {  // first asynchronous host-buffer call
-        for (int r = 0; r < RING; r++) {
+        for (int r = 0; r < RING; r++)
             for (int e = 0; e < (rgbd ? 1 : 2); e++) c->d_img_ring[r][e] = c->dalloc<uint8_t>(plane + 64);
-            if (rgbd) c->d_depth_ring[r] = c->dalloc<float>(npix + 4);
+    }
+    if (rgbd && c->depth_ring_cap < dpix) {  // (first call, or a depth camera with a larger plane was set since: no frame is in flight then)
+        drain(c);  // (once per larger camera; enq stays: an RGB-D handle holds no frame back)
+        for (int r = 0; r < RING; r++) {
+            c->dfree(c->d_depth_ring[r]);
+            c->d_depth_ring[r] = c->dalloc<float>(dpix + 4);
         }
+        c->depth_ring_cap = dpix;
     }
     const uint8_t *v0 = device_view(left, 1), *v1 = device_view(second, rgbd ? desz : 1);
     HostStage &stg = c->stage_ring[slot];
-    if (!v0 || !v1) stage_reserve(c, stg, nbytes, rgbd ? npix : 0);
+    if (!v0 || !v1) stage_reserve(c, stg, nbytes, dpix);
     hipStream_t sp = c->stream_f;
     uint8_t *d0 = (bpp > 1) ? c->d_col_ring[slot][0] : c->d_img_ring[slot][0], *d1 = (bpp > 1) ? c->d_col_ring[slot][1] : c->d_img_ring[slot][1];
     const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0);
@@ -2074,8 +2173,8 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
         return 0;
     }
     hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sp, s0, s0, d0, d0, row_bytes, n_rows, ipitch);
-    launch_stage_copy(sp, host_plane(c, v1, second, desz * npix, stg, stg.second), c->d_depth_ring[slot], npix, dfmt);
-    frame_args(c, slot) = rgbd_args(d0, ipitch, c->d_depth_ring[slot], n_cols * (int)desz, dfmt, dscale);
+    launch_stage_copy(sp, host_plane(c, v1, second, desz * dpix, stg, stg.second), c->d_depth_ring[slot], dpix, dfmt);
+    frame_args(c, slot) = rgbd_args(d0, ipitch, c->d_depth_ring[slot], dcols * (int)desz, dfmt, dscale);
     c->async_frames++;
     enqueue_frame(c);
     return 0;
@@ -2155,8 +2254,8 @@ static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale)
     }
     return true;
 }
-// one sequence's device planes against its parameters; "" when they pass
-static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp) {
+// one sequence's device planes against its parameters; "" when they pass (dcols: the width of its depth plane -- its depth camera's, else the image's)
+static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp, int dcols) {
     const int esz = (fmt == DEPTH_U16) ? 2 : 4;
     char buf[240];
     if (!d_gray || !d_depth) return "NULL gray or depth plane";
@@ -2173,8 +2272,8 @@ static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gr
         std::snprintf(buf, sizeof(buf), "gray plane: pointer and pitch (%d) must be multiples of 16, pitch >= %d", gray_pitch, n_cols);
         return buf;
     }
-    if (((uintptr_t)d_depth % esz) || depth_pitch <= 0 || (depth_pitch % esz) || (long long)depth_pitch < (long long)n_cols * esz) {
-        std::snprintf(buf, sizeof(buf), "depth plane: pointer and pitch (%d bytes) must be multiples of the %d-byte element, pitch >= %d", depth_pitch, esz, n_cols * esz);
+    if (((uintptr_t)d_depth % esz) || depth_pitch <= 0 || (depth_pitch % esz) || (long long)depth_pitch < (long long)dcols * esz) {
+        std::snprintf(buf, sizeof(buf), "depth plane: pointer and pitch (%d bytes) must be multiples of the %d-byte element, pitch >= %d", depth_pitch, esz, dcols * esz);
         return buf;
     }
     return "";
@@ -2190,7 +2289,7 @@ static int track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_by
     DeviceGuard guard(c);
     try {
         if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
-        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0));
+        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0), c->depth_cols());
         if (!why.empty()) return rgbd_refuse(h, who, why);
         if (sync) {
             drain(c);
@@ -2271,7 +2370,8 @@ LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *cons
         for (int s = 0; s < c->B; s++) {
             if (!d_gray[s]) continue;
             present++;
-            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s));
+            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s),
+                                                      c->has_depth_cam(s) ? c->depth_cam[(size_t)s].width : n_cols[s]);
             if (!why.empty()) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + why);
         }
         if (!present) return rgbd_refuse(h, who, "no sequence has a frame in this step");
@@ -2555,6 +2655,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             HIPCHK(c, hipMemcpy(dst, c->d_gray[(size_t)c->last_par * 2 + ((eye && c->sensor == 1) ? 1 : 0)], n, hipMemcpyDeviceToHost));
             if (pitch_out) *pitch_out = c->pitch;
             return (int)n;
+        }
+        if (what == 4) {  // the registered depth plane of the last frame (fp32, pitch words per row)
+            if (!c->has_depth_cam(0) || c->done == 0 || !c->ring_registered[c->last_slot]) return 0;  // (the last frame's depth must have been registered)
+            if ((size_t)cap_bytes < n * sizeof(float)) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_reg[(size_t)c->last_par], n * sizeof(float), hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->pitch;
+            return (int)(n * sizeof(float));
         }
         const size_t bytes = n * (what == 0 ? 1 : 2);
         if ((size_t)cap_bytes < bytes) return -1;
@@ -2951,6 +3058,106 @@ LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
     if (!is_ctx(h)) return -1;
     const Context *c = static_cast<const Context *>(h);
     return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
+}
+
+// ---- unregistered depth: a depth camera per handle / per sequence of a batch (Context::depth_cam, k_depthreg.hip) ----------------------------------
+// Everything is checked before anything changes: 0 = set / cleared, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
+static int dcam_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_depth_camera", why + " (nothing was changed)"); }
+// "" when the record passes
+static std::string depth_camera_check(const lvt_amd_depth_camera &d) {
+    if (d.width < 1 || d.width > 8192 || d.height < 1 || d.height > 8192)
+        return "a depth camera of " + std::to_string(d.width) + " x " + std::to_string(d.height) + " pixels (1 ... 8192 each way)";
+    bool finite = std::isfinite(d.fx) && std::isfinite(d.fy) && std::isfinite(d.cx) && std::isfinite(d.cy);
+    for (float v : d.R) finite = finite && std::isfinite(v);
+    for (float v : d.t) finite = finite && std::isfinite(v);
+    if (!finite) return "a depth camera with a non-finite field";
+    if (!(d.fx > 0.f && d.fy > 0.f)) return "a depth camera whose fx or fy is not > 0";
+    return "";
+}
+static int set_depth_camera(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_camera *cam) {
+    Context *c = frame_context(h, "lvt_amd_set_depth_camera", 2, batch_call,
+                               {"a pooled handle (pooled handles are stereo only) (nothing was changed)",
+                                "a stereo handle (it has no depth plane to register) (nothing was changed)",
+                                "a batch handle takes its depth cameras per sequence through lvt_amd_batch_set_depth_camera (nothing was changed)"});
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (batch_call && c->B == 1 && !c->mixed) return dcam_refuse(h, "lvt_amd_batch_set_depth_camera on a handle that is not a batch (use lvt_amd_set_depth_camera)");
+        if (seq < 0 || seq >= c->B) return dcam_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
+        if (cam) {
+            const std::string why = depth_camera_check(*cam);
+            if (!why.empty()) return dcam_refuse(h, why);
+        }
+        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
+        if (c->done < c->enq || c->pend.valid) return dcam_refuse(h, "frames in flight: set the camera before the first frame or after every frame has been collected");
+        if (!cam && !c->has_depth_cam(seq)) return 0;
+        if (c->depth_cam.empty()) {
+            c->depth_cam.assign((size_t)c->B, lvt_amd_depth_camera{});
+            c->d_reg.assign((size_t)c->B * NPAR, nullptr);
+        }
+        if (cam) {
+            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
+            for (int par = 0; par < NPAR; par++) {
+                float *&d = c->d_reg[(size_t)seq * NPAR + par];
+                if (!d) d = c->dalloc<float>(plane + 16);
+            }
+        }
+        if (seq == 0) stage_release(c);  // (the pinned staging of the host entry points is sized by the depth plane: reserved again at the next frame)
+        c->depth_cam[(size_t)seq] = cam ? *cam : lvt_amd_depth_camera{};
+        c->n_depth_cam = 0;
+        for (int s = 0; s < c->B; s++) c->n_depth_cam += c->depth_cam[(size_t)s].width > 0;
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
+// (an lvt_create handle is a stereo handle: refused like one, under its record's lock, and a refusal is no use)
+static int set_depth_camera_any(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_camera *cam) {
+    if (!is_auto(h)) return set_depth_camera(h, seq, batch_call, cam);
+    AutoHandle *A = static_cast<AutoHandle *>(h);
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = set_depth_camera(A->impl, seq, batch_call, cam);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam) { return set_depth_camera_any(h, 0, false, cam); }
+LVT_API int lvt_amd_batch_set_depth_camera(lvt_handle h, int seq, const lvt_amd_depth_camera *cam) { return set_depth_camera_any(h, seq, true, cam); }
+LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->has_depth_cam(seq)) return 0;
+    if (out) *out = c->depth_cam[(size_t)seq];
+    return 1;
+}
+// the stage alone on caller data: clear, then scatter, on the caller's stream
+LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour, const void *d_depth, int depth_pitch_bytes,
+                                          int depth_format, float depth_scale, void *d_out, int out_pitch_bytes, void *hip_stream) {
+    if (!cam || !colour || !d_depth || !d_out || !depth_camera_check(*cam).empty()) return -1;
+    if (depth_format != DEPTH_F32 && depth_format != DEPTH_U16) return -1;
+    if (depth_format == DEPTH_U16 && !(std::isfinite(depth_scale) && depth_scale > 0.f)) return -1;
+    const int esz = (depth_format == DEPTH_U16) ? 2 : 4;
+    if (((uintptr_t)d_depth % esz) || depth_pitch_bytes <= 0 || (depth_pitch_bytes % esz) || (long long)depth_pitch_bytes < (long long)cam->width * esz) return -1;
+    if (colour->img_width < 1 || colour->img_width > 8192 || colour->img_height < 1 || colour->img_height > 8192) return -1;
+    if (((uintptr_t)d_out & 3) || (out_pitch_bytes & 3) || (long long)out_pitch_bytes < (long long)colour->img_width * 4) return -1;
+    DepthRegTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    DepthRegImg &I = tab.im[0];
+    I.src = d_depth, I.src_pitch = depth_pitch_bytes / esz, I.fmt = depth_format, I.scale = (depth_format == DEPTH_U16) ? depth_scale : 0.f;
+    I.dst = static_cast<float *>(d_out), I.dst_pitch = out_pitch_bytes / 4;
+    I.dw = cam->width, I.dh = cam->height, I.fx = cam->fx, I.fy = cam->fy, I.cx = cam->cx, I.cy = cam->cy;
+    std::memcpy(I.R, cam->R, sizeof(I.R)), std::memcpy(I.t, cam->t, sizeof(I.t));
+    I.cfx = colour->fx, I.cfy = colour->fy, I.ccx = colour->cx, I.ccy = colour->cy;
+    I.k1 = colour->k1, I.k2 = colour->k2, I.p1 = colour->p1, I.p2 = colour->p2, I.k3 = colour->k3;
+    I.W = colour->img_width, I.H = colour->img_height;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const size_t words = (size_t)I.dst_pitch * I.H;
+    if ((words + 3) / 4 / 256 + 1 > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(k_depth_clear, dim3((unsigned)(((words + 3) / 4 + 255) / 256), 1), dim3(256), 0, st, tab);
+    hipLaunchKernelGGL(k_depth_register, dim3((unsigned)((I.dw * I.dh + 255) / 256), 1), dim3(256), 0, st, tab);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ------------------------------
