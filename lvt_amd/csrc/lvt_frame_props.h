@@ -1,0 +1,371 @@
+// lvt_frame_props.h -- the properties a handle, or one sequence of a batch, has besides its parameters (included by lvt_host.hip): rectifiers for raw frames,
+// a pixel format for colour frames, a depth camera for unregistered depth, the pose-uncertainty record.
+//
+// THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
+// was, lvt_amd_last_error says why); it needs a quiet handle (no frame in flight); an lvt_create handle is decided under its record's lock; a property is
+// configuration, not state (reset and snapshots leave it alone); and a context without the property launches what it always did.
+// Here: the one path every such call takes (frames_in_flight, with_auto_handle, set_property), the one packer of the by-value descriptor tables, the
+// setters and getters, and the launches the properties add to the head of a frame's feature stage (enqueue_frame calls them in this file's order).
+#pragma once
+
+namespace lvt {
+
+// ---- one path for "change a property of a quiet handle" ---------------------------------------------------------------------------------------------
+static int refuse_unchanged(lvt_handle h, const char *who, const std::string &why) { return refuse(h, who, why + " (nothing was changed)"); }
+// a synchronous call's frame whose pose has been returned is nobody's to collect: it is drained; any other un-collected or held frame is in flight
+static bool frames_in_flight(Context *c) {
+    if (c->early_pending) drain(c);
+    return c->done < c->enq || c->pend.valid;
+}
+// fn(handle) on the tracker behind h.  An lvt_create handle: decided under its record's lock -- a handle that has not been used yet may be given a seat by
+// another thread's lvt_create at any time --, and a successful call is a use: the handle keeps its own chain (a refusal is no use)
+template <typename Fn>
+static int with_auto_handle(lvt_handle h, Fn fn) {
+    if (!is_auto(h)) return fn(h);
+    AutoHandle *A = static_cast<AutoHandle *>(h);
+    std::lock_guard<std::mutex> g(A->mu);
+    const int rc = fn(A->impl);
+    if (rc == 0) A->started = true;
+    return rc;
+}
+// what distinguishes one property call from another before its own checks begin
+struct PropertyCall {
+    const char *who;
+    int sensor;                 // the sensor the property belongs to (0: either)
+    Refusals why;               // to a pooled handle / a handle of the other sensor / a batch handle in the solo spelling
+    const char *batch_on_solo;  // to the batch spelling on a solo handle; nullptr: accepted (for seq == 0, by the range check)
+};
+// The preamble: the handle's kind, the spelling, the sequence -- in this order, then body(h, c), which makes the call's own validity checks, then asks
+// frames_in_flight, then changes the context.  The order of objections is behaviour: callers see the first one.
+template <typename Body>
+static int set_property(lvt_handle h, const PropertyCall &k, int seq, bool batch_call, Body body) {
+    return with_auto_handle(h, [&](lvt_handle t) -> int {
+        Context *c = frame_context(t, k.who, k.sensor, batch_call, k.why);
+        if (!c) return -1;
+        DeviceGuard guard(c);
+        try {
+            if (batch_call && k.batch_on_solo && c->B == 1 && !c->mixed) return refuse_unchanged(t, k.who, k.batch_on_solo);
+            if (seq < 0 || seq >= c->B) return refuse_unchanged(t, k.who, "no sequence " + std::to_string(seq) + " in this handle");
+            return body(t, c);
+        } catch (...) {
+        }
+        return -1;
+    });
+}
+// sequence seq's planes (each of its own plane_pitch x H elements + pad) in a [B][NPAR][stride] vector: sized at its first use, `eyes` <= stride planes per
+// parity allocated where they do not exist yet
+template <typename T>
+static void give_planes(Context *c, std::vector<T *> &planes, int stride, int seq, int eyes, size_t pad) {
+    if (planes.empty()) planes.assign((size_t)c->B * NPAR * stride, nullptr);
+    const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
+    for (int par = 0; par < NPAR; par++)
+        for (int e = 0; e < eyes; e++) {
+            T *&d = planes[((size_t)seq * NPAR + par) * stride + e];
+            if (!d) d = c->dalloc<T>(plane + pad);
+        }
+}
+// the per-sequence values live in vectors that are empty until the first set; the count of sequences that have the property is what the frame path tests
+template <typename T, typename Has>
+static int put_seq_value(Context *c, std::vector<T> &v, int per_seq, const T &none, int seq, std::initializer_list<T> vals, Has has) {
+    if (v.empty()) v.assign((size_t)c->B * per_seq, none);
+    std::copy(vals.begin(), vals.end(), v.begin() + (size_t)seq * per_seq);
+    int n = 0;
+    for (int s = 0; s < c->B; s++) n += has(v[(size_t)s * per_seq]) ? 1 : 0;
+    return n;
+}
+
+// ---- one packer for the by-value descriptor tables (GrayTable, RectTable, DepthRegTable, StateTable) ------------------------------------------------
+// blockIdx.y is the descriptor and the grid's x extent follows the largest one (the caller keeps that maximum and clears it in `launch`).
+// THE RULE: add(k) flushes first when the next sequence's k descriptors do not fit; flush() sends what is left; launch(tab, n, first) is told whether it
+// is the step's first launch -- the one its profile slot times, later ones go out untimed.  The launches are the ones four hand-written loops made:
+// colour flushed before adding (n + eyes > GRAY_PACK), as here; rectify flushed after adding at n == RECT_PACK, and with n always even and k == 2 that is
+// "the next pair does not fit", sent one add later or by flush(); depth (k == 1) opened a table at n == DEPTHREG_PACK and state cut chunks of STATE_PACK.
+template <typename Table, typename Desc, int CAP, typename Launch>
+struct TablePacker {
+    Table tab;
+    Desc (Table::*slots)[CAP];
+    Launch launch;
+    int n = 0;
+    bool first = true;
+    TablePacker(Desc (Table::*a)[CAP], Launch l) : slots(a), launch(l) { std::memset(&tab, 0, sizeof(tab)); }
+    Desc *add(int k) {
+        if (n + k > CAP) flush();
+        Desc *d = &(tab.*slots)[n];
+        n += k;
+        return d;
+    }
+    void flush() {
+        if (n) launch(tab, n, first), first = false, n = 0;
+    }
+};
+// a table's launch on the feature stream: timed by `slot` when it is the step's first
+#define LAUNCH_TABLE(first, slot, kern, grid, tab)                          \
+    do {                                                                    \
+        if (first) LAUNCH(slot, c->stream_f, kern, grid, dim3(256), 0, tab); \
+        else hipLaunchKernelGGL(kern, grid, dim3(256), 0, c->stream_f, tab); \
+    } while (0)
+
+// ---- colour frames: a pixel format per handle / per sequence of a batch (Context::pixfmt) ------------------------------------------------------------
+// Every colour image of the step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in one launch, AHEAD of the rectify block
+// (convert, then remap: the reference's order).  The gray planes (parity `par`) were read last by the feature stage of frame enq - NPAR (k_rectify_frames or
+// k_score, k_gather, k_brief_img: all on this stream, all enqueued before), and the source was written by a pull on this stream or belongs to the
+// caller: stream order alone covers the hand-over, no gate.
+static void convert_colour_frames(Context *c, int slot, int par, int Bz) {
+    FrameArgs *fw = &frame_args(c, slot);
+    int words = 0;
+    TablePacker pk(&GrayTable::im, [&](const GrayTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 14, k_gray_frames, dim3((words + 255) / 256, n), tab);
+        words = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (c->fmt_of(s) == PIX_GRAY8 || fw[s].absent) continue;
+        const Params &q = c->seq_prm(s);
+        const int dpitch = c->h_seqs[s].plane_pitch, eyes = (c->sensor == 2) ? 1 : 2;
+        GrayImg *im = pk.add(eyes);
+        for (int e = 0; e < eyes; e++) {
+            GrayImg &I = im[e];
+            I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
+            I.dst = c->d_gray[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
+            I.w = q.W, I.h = q.H, I.fmt = c->fmt_of(s);
+            words = std::max(words, dpitch / 4 * q.H);
+            fw[s].img[e] = I.dst;
+        }
+        if (eyes == 1) fw[s].img[1] = fw[s].img[0];
+        fw[s].img_pitch = dpitch;
+        if (s == 0) c->ring_converted[slot] = true;
+    }
+    pk.flush();
+}
+static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) {
+    static const PropertyCall call = {"lvt_amd_set_pixel_format", 0,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                       "a batch handle takes its pixel formats per sequence through lvt_amd_batch_set_pixel_format (nothing was changed)"},
+                                      "lvt_amd_batch_set_pixel_format on a handle that is not a batch (use lvt_amd_set_pixel_format)"};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (format < PIX_GRAY8 || format > PIX_RGBA8) return refuse_unchanged(t, call.who, "unknown pixel format " + std::to_string(format));
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the format before the first frame or after every frame has been collected");
+        if (format == c->fmt_of(seq)) return 0;
+        if (format != PIX_GRAY8) give_planes(c, c->d_gray, 2, seq, c->sensor == 2 ? 1 : 2, 64);
+        if (seq == 0 && pix_bpp(format) != c->bpp_of(0)) stage_release(c);  // (the pinned staging of the host entry points is sized by bpp: reserved again at the next frame)
+        c->n_colour = put_seq_value(c, c->pixfmt, 1, (int)PIX_GRAY8, seq, {format}, [](int f) { return f != PIX_GRAY8; });
+        return 0;
+    });
+}
+
+// ---- raw frames: rectifiers attached to a tracker (Context::rect) -----------------------------------------------------------------------------------
+// Both eyes of every sequence that has rectifiers and a frame in this step, in one launch.  The rectified planes (parity `par`) were read last by the
+// feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order alone covers the
+// hand-over, and the launch needs no gate: it goes out ahead of the buffer gate.
+static void rectify_raw_frames(Context *c, int slot, int par, int Bz) {
+    FrameArgs *fw = &frame_args(c, slot);
+    int words = 0;
+    TablePacker pk(&RectTable::im, [&](const RectTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 4, k_rectify_frames, dim3((words + 255) / 256, n), tab);
+        words = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (!c->has_rect(s) || fw[s].absent) continue;
+        const Params &q = c->seq_prm(s);
+        const int dpitch = c->h_seqs[s].plane_pitch;
+        RectImg *im = pk.add(2);
+        for (int e = 0; e < 2; e++) {
+            RectImg &I = im[e];
+            I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
+            I.map = c->rect[2 * (size_t)s + e]->d_fix;
+            I.dst = c->d_rect[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
+            I.sw = I.dw = q.W, I.sh = I.dh = q.H;
+            words = std::max(words, dpitch / 4 * q.H);
+            fw[s].img[e] = I.dst;
+        }
+        fw[s].img_pitch = dpitch;
+    }
+    pk.flush();
+}
+// (the batch spelling on a solo handle is accepted for seq == 0)
+static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
+    static const PropertyCall call = {"lvt_amd_set_rectifiers", 1,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)",
+                                       "an RGB-D handle (there is one image, and its depth plane is registered to it) (nothing was changed)",
+                                       "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers (nothing was changed)"},
+                                      nullptr};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if ((left == nullptr) != (right == nullptr)) return refuse_unchanged(t, call.who, "one rectifier is NULL (both, or NULL, NULL to detach)");
+        Rectifier *rl = static_cast<Rectifier *>(left), *rr = static_cast<Rectifier *>(right);
+        const Params &q = c->seq_prm(seq);
+        for (Rectifier *r : {rl, rr}) {
+            if (!r) continue;
+            if (r->w != q.W || r->h != q.H)
+                return refuse_unchanged(t, call.who, "a rectifier of " + std::to_string(r->w) + " x " + std::to_string(r->h) + " on a sequence of " + std::to_string(q.W) + " x " + std::to_string(q.H));
+            if (r->device != c->device)
+                return refuse_unchanged(t, call.who, "a rectifier created on device " + std::to_string(r->device) + ", the handle owns device " + std::to_string(c->device));
+        }
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: attach before the first frame or after every frame has been collected");
+        if (rl) give_planes(c, c->d_rect, 2, seq, 2, 64);
+        c->n_rect = put_seq_value(c, c->rect, 2, (Rectifier *)nullptr, seq, {rl, rr}, [](const Rectifier *r) { return r != nullptr; });
+        return 0;
+    });
+}
+
+// ---- unregistered depth: a depth camera per handle / per sequence of a batch (Context::depth_cam, k_depthreg.hip) --------------------------------------
+// "" when the record passes
+static std::string depth_camera_check(const lvt_amd_depth_camera &d) {
+    if (d.width < 1 || d.width > 8192 || d.height < 1 || d.height > 8192)
+        return "a depth camera of " + std::to_string(d.width) + " x " + std::to_string(d.height) + " pixels (1 ... 8192 each way)";
+    bool finite = std::isfinite(d.fx) && std::isfinite(d.fy) && std::isfinite(d.cx) && std::isfinite(d.cy);
+    for (float v : d.R) finite = finite && std::isfinite(v);
+    for (float v : d.t) finite = finite && std::isfinite(v);
+    if (!finite) return "a depth camera with a non-finite field";
+    if (!(d.fx > 0.f && d.fy > 0.f)) return "a depth camera whose fx or fy is not > 0";
+    return "";
+}
+// one depth plane's descriptor: the sensor's plane (src_pitch in ELEMENTS of fmt; scale only for DEPTH_U16) registered to the colour camera's pixel grid in dst
+static DepthRegImg depth_reg_img(const lvt_amd_depth_camera &dc, const lvt_amd_params &q, const void *src, int src_pitch, int fmt, float scale, float *dst, int dst_pitch) {
+    DepthRegImg I{};
+    I.src = src, I.src_pitch = src_pitch, I.fmt = fmt, I.scale = (fmt == DEPTH_U16) ? scale : 0.f;
+    I.dst = dst, I.dst_pitch = dst_pitch;
+    I.dw = dc.width, I.dh = dc.height, I.fx = dc.fx, I.fy = dc.fy, I.cx = dc.cx, I.cy = dc.cy;
+    std::memcpy(I.R, dc.R, sizeof(I.R)), std::memcpy(I.t, dc.t, sizeof(I.t));
+    I.cfx = q.fx, I.cfy = q.fy, I.ccx = q.cx, I.ccy = q.cy, I.k1 = q.k1, I.k2 = q.k2, I.p1 = q.p1, I.p2 = q.p2, I.k3 = q.k3;
+    I.W = q.img_width, I.H = q.img_height;
+    return I;
+}
+// Every sequence that has a depth camera and a frame in this step.  The descriptors are built HERE, on the host, and the frame is pointed at the sequence's
+// registered plane before k_score<true> / k_feat_begin* carries the record into FeatCtl::in; k_depth_clear goes out now, k_depth_register directly in front
+// of k_gather (scatter_depth_planes).  The registered plane (parity `par`) was read last by k_gather of frame enq - NPAR -- on this stream, enqueued before --
+// and the source was written by a pull this stream waits for or belongs to the caller: stream order alone covers the hand-over, no gate.
+// Both kernels take each table, so the step keeps them (DepthRegPlan: the first in place, only a step with more than DEPTHREG_PACK registered sequences
+// takes tables from the heap).
+static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan) {
+    FrameArgs *fw = &frame_args(c, slot);
+    int px = 0, words = 0;
+    TablePacker pk(&DepthRegTable::im, [&](const DepthRegTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 17, k_depth_clear, dim3(((words + 3) / 4 + 255) / 256, n), tab);
+        DepthRegStep &T = first ? plan.first : (plan.more.emplace_back(), plan.more.back());
+        T.tab = tab, T.n = n, T.px = px;
+        plan.n++, px = 0, words = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (!c->has_depth_cam(s) || fw[s].absent) continue;
+        const lvt_amd_depth_camera &dc = c->depth_cam[(size_t)s];
+        DepthRegImg &I = *pk.add(1);
+        I = depth_reg_img(dc, c->in_prms[c->mixed ? (size_t)s : 0], fw[s].depth, fw[s].depth_pitch, fw[s].depth_format, fw[s].depth_scale, c->d_reg[(size_t)s * NPAR + par],
+                          c->h_seqs[s].plane_pitch);
+        px = std::max(px, dc.width * dc.height), words = std::max(words, I.dst_pitch * I.H);
+        fw[s].depth = I.dst, fw[s].depth_pitch = I.dst_pitch, fw[s].depth_format = DEPTH_F32, fw[s].depth_scale = 0.f;
+        if (s == 0) c->ring_registered[slot] = true;
+    }
+    pk.flush();
+}
+// the z-buffered scatter of the step's unregistered depth planes (a host call's depth plane arrives on the early stream: the caller has waited for ev_depth)
+static void scatter_depth_planes(Context *c, const DepthRegPlan &plan) {
+    for (int k = 0; k < plan.n; k++) {
+        const DepthRegStep &T = k == 0 ? plan.first : plan.more[(size_t)k - 1];
+        LAUNCH_TABLE(k == 0, 21, k_depth_register, dim3((T.px + 255) / 256, T.n), T.tab);
+    }
+}
+static int set_depth_camera(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_camera *cam) {
+    static const PropertyCall call = {"lvt_amd_set_depth_camera", 2,
+                                      {"a pooled handle (pooled handles are stereo only) (nothing was changed)",
+                                       "a stereo handle (it has no depth plane to register) (nothing was changed)",
+                                       "a batch handle takes its depth cameras per sequence through lvt_amd_batch_set_depth_camera (nothing was changed)"},
+                                      "lvt_amd_batch_set_depth_camera on a handle that is not a batch (use lvt_amd_set_depth_camera)"};
+    // (an lvt_create handle is a stereo handle: refused like one)
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (cam) {
+            const std::string why = depth_camera_check(*cam);
+            if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        }
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the camera before the first frame or after every frame has been collected");
+        if (!cam && !c->has_depth_cam(seq)) return 0;
+        if (cam) give_planes(c, c->d_reg, 1, seq, 1, 16);
+        if (seq == 0) stage_release(c);  // (the pinned staging of the host entry points is sized by the depth plane: reserved again at the next frame)
+        c->n_depth_cam = put_seq_value(c, c->depth_cam, 1, lvt_amd_depth_camera{}, seq, {cam ? *cam : lvt_amd_depth_camera{}}, [](const lvt_amd_depth_camera &d) { return d.width > 0; });
+        return 0;
+    });
+}
+
+// ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ----------------------------------
+static int enable_pose_info(lvt_handle h, int enable) {
+    static const PropertyCall call = {"lvt_amd_enable_pose_info", 0, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr, nullptr}, nullptr};
+    return set_property(h, call, 0, true, [&](lvt_handle t, Context *c) -> int {
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: enable before the first frame or after every frame has been collected");
+        if ((enable != 0) == c->pose_info) return 0;
+        if (enable && !c->h_pinfo) {
+            HIPCHK(c, hipHostMalloc((void **)&c->h_pinfo, sizeof(lvt_amd_pose_info) * c->B * RING, hipHostMallocCoherent));
+            HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinfo_dev, c->h_pinfo, 0));
+        }
+        for (int s = 0; s < c->B; s++) pose_info_clear(c, s);  // (either way: the last frame has no record)
+        c->pose_info = enable != 0;
+        return 0;
+    });
+}
+}  // namespace lvt
+
+// ---- the properties' C-ABI ----------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right) { return set_rectifiers(h, 0, false, left, right); }
+LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right) { return set_rectifiers(h, seq, true, left, right); }
+
+LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format) { return set_pixel_format(h, 0, false, format); }
+LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format) { return set_pixel_format(h, seq, true, format); }
+LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? PIX_GRAY8 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
+}
+
+LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam) { return set_depth_camera(h, 0, false, cam); }
+LVT_API int lvt_amd_batch_set_depth_camera(lvt_handle h, int seq, const lvt_amd_depth_camera *cam) { return set_depth_camera(h, seq, true, cam); }
+LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->has_depth_cam(seq)) return 0;
+    if (out) *out = c->depth_cam[(size_t)seq];
+    return 1;
+}
+// the stage alone on caller data: clear, then scatter, on the caller's stream
+LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour, const void *d_depth, int depth_pitch_bytes,
+                                          int depth_format, float depth_scale, void *d_out, int out_pitch_bytes, void *hip_stream) {
+    if (!cam || !colour || !d_depth || !d_out || !depth_camera_check(*cam).empty()) return -1;
+    if (depth_format != DEPTH_F32 && depth_format != DEPTH_U16) return -1;
+    if (depth_format == DEPTH_U16 && !(std::isfinite(depth_scale) && depth_scale > 0.f)) return -1;
+    const int esz = (depth_format == DEPTH_U16) ? 2 : 4;
+    if (((uintptr_t)d_depth % esz) || depth_pitch_bytes <= 0 || (depth_pitch_bytes % esz) || (long long)depth_pitch_bytes < (long long)cam->width * esz) return -1;
+    if (colour->img_width < 1 || colour->img_width > 8192 || colour->img_height < 1 || colour->img_height > 8192) return -1;
+    if (((uintptr_t)d_out & 3) || (out_pitch_bytes & 3) || (long long)out_pitch_bytes < (long long)colour->img_width * 4) return -1;
+    DepthRegTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    const DepthRegImg &I = tab.im[0] = depth_reg_img(*cam, *colour, d_depth, depth_pitch_bytes / esz, depth_format, depth_scale, static_cast<float *>(d_out), out_pitch_bytes / 4);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const size_t words = (size_t)I.dst_pitch * I.H;
+    if ((words + 3) / 4 / 256 + 1 > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL(k_depth_clear, dim3((unsigned)(((words + 3) / 4 + 255) / 256), 1), dim3(256), 0, st, tab);
+    hipLaunchKernelGGL(k_depth_register, dim3((unsigned)((I.dw * I.dh + 255) / 256), 1), dim3(256), 0, st, tab);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) { return enable_pose_info(h, enable); }
+LVT_API int lvt_amd_get_pose_info(lvt_handle h, int seq, lvt_amd_pose_info *out) {
+    h = resolve_handle(h);
+    if (!out) return -1;
+    std::memset(out, 0, sizeof(*out));
+    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has it enabled)
+    if (!is_ctx(h)) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->pose_info) return 0;
+    DeviceGuard guard(c);
+    try {
+        drain(c);  // (as lvt_amd_get_pose / lvt_amd_get_counts: the last frame enqueued, collected)
+        *out = c->h_pinfo[(size_t)c->last_slot * c->B + seq];
+        return 1;
+    } catch (...) {
+    }
+    return -1;
+}
+}  // extern "C"

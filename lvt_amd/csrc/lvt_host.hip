@@ -934,6 +934,21 @@ struct HostTimer {
 };
 // the frame (sequence number) that used the feature buffer of the frame about to be enqueued last: gate_buf_wait's `want` (only from frame NPAR on)
 static seq_t buffer_last_user(const Context *c) { return (seq_t)(c->enq + 1 - NPAR); }
+// the frame properties' part of the chain (lvt_frame_props.h, which needs the refusal path further down: declared here for enqueue_frame).  The depth tables of
+// a step are kept between its two launches: the first in place, further ones on the heap; `first` is written only when a sequence registers
+struct DepthRegStep {
+    DepthRegTable tab;
+    int n, px;  // descriptors, and the largest depth image (pixels) among them
+};
+struct DepthRegPlan {
+    DepthRegStep first;
+    std::vector<DepthRegStep> more;
+    int n = 0;  // tables
+};
+static void convert_colour_frames(Context *c, int slot, int par, int Bz);
+static void rectify_raw_frames(Context *c, int slot, int par, int Bz);
+static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
+static void scatter_depth_planes(Context *c, const DepthRegPlan &plan);
 static void enqueue_frame(Context *c) {
     HostTimer ht(&c->host_enq_us);
     c->host_enq_n++;
@@ -971,120 +986,14 @@ static void enqueue_frame(Context *c) {
     hipStream_t sf = c->stream_f, st = c->stream;
     for (int i = 0; i < Context::PROF_SLOTS; i++) c->ev_used[i] = false;
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
-    // ---- colour frames: every colour image of the step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in one launch, AHEAD of the
-    //      rectify block (convert, then remap: the reference's order).  The gray planes (parity `par`) were read last by the feature stage of frame enq - NPAR
-    //      (k_rectify_frames or k_score, k_gather, k_brief_img: all on this stream, all enqueued before), and the source was written by a pull on this stream
-    //      or belongs to the caller: stream order alone covers the hand-over, no gate.
-    c->ring_converted[slot] = false;
-    if (c->n_colour) {
-        FrameArgs *fw = &frame_args(c, slot);
-        GrayTable tab;
-        std::memset(&tab, 0, sizeof(tab));
-        int n = 0, words = 0;
-        bool timed = false;
-        auto launch = [&]() {
-            const dim3 grid((words + 255) / 256, n);
-            if (!timed) LAUNCH(14, sf, k_gray_frames, grid, dim3(256), 0, tab);
-            else hipLaunchKernelGGL(k_gray_frames, grid, dim3(256), 0, sf, tab);
-            timed = true, n = 0, words = 0;
-        };
-        for (int s = 0; s < Bz; s++) {
-            if (c->fmt_of(s) == PIX_GRAY8 || fw[s].absent) continue;
-            const Params &q = c->seq_prm(s);
-            const int dpitch = c->h_seqs[s].plane_pitch, eyes = (c->sensor == 2) ? 1 : 2;
-            if (n + eyes > GRAY_PACK) launch();
-            for (int e = 0; e < eyes; e++) {
-                GrayImg &I = tab.im[n++];
-                I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
-                I.dst = c->d_gray[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
-                I.w = q.W, I.h = q.H, I.fmt = c->fmt_of(s);
-                words = std::max(words, dpitch / 4 * q.H);
-                fw[s].img[e] = I.dst;
-            }
-            if (eyes == 1) fw[s].img[1] = fw[s].img[0];
-            fw[s].img_pitch = dpitch;
-            if (s == 0) c->ring_converted[slot] = true;
-        }
-        if (n) launch();
-    }
-    // ---- raw frames: both eyes of every sequence that has rectifiers and a frame in this step, in one launch.  The rectified planes (parity `par`) were
-    //      read last by the feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order
-    //      alone covers the hand-over, and the launch needs no gate: it goes out ahead of the buffer gate.
-    if (c->n_rect) {
-        FrameArgs *fw = &frame_args(c, slot);
-        RectTable tab;
-        std::memset(&tab, 0, sizeof(tab));
-        int n = 0, words = 0;
-        bool timed = false;
-        auto launch = [&]() {
-            const dim3 grid((words + 255) / 256, n);
-            if (!timed) LAUNCH(4, sf, k_rectify_frames, grid, dim3(256), 0, tab);
-            else hipLaunchKernelGGL(k_rectify_frames, grid, dim3(256), 0, sf, tab);
-            timed = true, n = 0, words = 0;
-        };
-        for (int s = 0; s < Bz; s++) {
-            if (!c->has_rect(s) || fw[s].absent) continue;
-            const Params &q = c->seq_prm(s);
-            const int dpitch = c->h_seqs[s].plane_pitch;
-            for (int e = 0; e < 2; e++) {
-                RectImg &I = tab.im[n++];
-                I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
-                I.map = c->rect[2 * (size_t)s + e]->d_fix;
-                I.dst = c->d_rect[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
-                I.sw = I.dw = q.W, I.sh = I.dh = q.H;
-                words = std::max(words, dpitch / 4 * q.H);
-                fw[s].img[e] = I.dst;
-            }
-            fw[s].img_pitch = dpitch;
-            if (n == RECT_PACK) launch();
-        }
-        if (n) launch();
-    }
-    // ---- unregistered depth: every sequence that has a depth camera and a frame in this step.  The descriptors are built HERE, on the host, and the frame is
-    //      pointed at the sequence's registered plane before k_score<true> / k_feat_begin* carries the record into FeatCtl::in; k_depth_clear goes out now,
-    //      k_depth_register directly in front of k_gather (a host call's depth plane arrives on the early stream: behind the wait for ev_depth).  The registered
-    //      plane (parity `par`) was read last by k_gather of frame enq - NPAR -- on this stream, enqueued before -- and the source was written by a pull this
-    //      stream waits for or belongs to the caller: stream order alone covers the hand-over, no gate.
-    c->ring_registered[slot] = false;
-    // (one table on the stack, as the colour and rectify blocks have; only a step with more than DEPTHREG_PACK registered sequences takes tables from the heap)
-    struct DepthRegStep {
-        DepthRegTable tab;
-        int n, px, words;  // descriptors, the largest depth image (pixels) and the largest registered plane (fp32 words) among them
-    };
-    DepthRegStep dreg_first;  // (written only when a sequence registers)
-    std::vector<DepthRegStep> dreg_more;
-    int n_dreg = 0;
-    auto dreg = [&](int k) -> DepthRegStep & { return k == 0 ? dreg_first : dreg_more[(size_t)k - 1]; };
-    if (c->n_depth_cam) {
-        FrameArgs *fw = &frame_args(c, slot);
-        for (int s = 0; s < Bz; s++) {
-            if (!c->has_depth_cam(s) || fw[s].absent) continue;
-            if (n_dreg == 0 || dreg(n_dreg - 1).n == DEPTHREG_PACK) {
-                if (n_dreg > 0) dreg_more.emplace_back();
-                std::memset(&dreg(n_dreg), 0, sizeof(DepthRegStep));
-                n_dreg++;
-            }
-            DepthRegStep &T = dreg(n_dreg - 1);
-            const lvt_amd_depth_camera &dc = c->depth_cam[(size_t)s];
-            const lvt_amd_params &q = c->in_prms[c->mixed ? (size_t)s : 0];
-            DepthRegImg &I = T.tab.im[T.n++];
-            I.src = fw[s].depth, I.src_pitch = fw[s].depth_pitch, I.fmt = fw[s].depth_format, I.scale = fw[s].depth_scale;
-            I.dst = c->d_reg[(size_t)s * NPAR + par], I.dst_pitch = c->h_seqs[s].plane_pitch;
-            I.dw = dc.width, I.dh = dc.height, I.fx = dc.fx, I.fy = dc.fy, I.cx = dc.cx, I.cy = dc.cy;
-            std::memcpy(I.R, dc.R, sizeof(I.R)), std::memcpy(I.t, dc.t, sizeof(I.t));
-            I.cfx = q.fx, I.cfy = q.fy, I.ccx = q.cx, I.ccy = q.cy, I.k1 = q.k1, I.k2 = q.k2, I.p1 = q.p1, I.p2 = q.p2, I.k3 = q.k3;
-            I.W = q.img_width, I.H = q.img_height;
-            T.px = std::max(T.px, dc.width * dc.height), T.words = std::max(T.words, I.dst_pitch * I.H);
-            fw[s].depth = I.dst, fw[s].depth_pitch = I.dst_pitch, fw[s].depth_format = DEPTH_F32, fw[s].depth_scale = 0.f;
-            if (s == 0) c->ring_registered[slot] = true;
-        }
-        for (int k = 0; k < n_dreg; k++) {
-            const DepthRegStep &T = dreg(k);
-            const dim3 grid(((T.words + 3) / 4 + 255) / 256, T.n);
-            if (k == 0) LAUNCH(17, sf, k_depth_clear, grid, dim3(256), 0, T.tab);
-            else hipLaunchKernelGGL(k_depth_clear, grid, dim3(256), 0, sf, T.tab);
-        }
-    }
+    // ---- the frame properties' launches at its head, ahead of the buffer gate (lvt_frame_props.h: why stream order alone covers each hand-over).  They point the
+    //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
+    //      (the reference's order), then the clear of the registered depth planes, whose scatter goes out in front of k_gather.
+    c->ring_converted[slot] = c->ring_registered[slot] = false;
+    if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
+    if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
+    DepthRegPlan dreg;
+    if (c->n_depth_cam) begin_depth_registration(c, slot, par, Bz, dreg);
     const bool evo = c->events_only;
     const bool feat_pack = B > 1 && Bz <= FEAT_PACK && c->feat_pack;  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
@@ -1145,12 +1054,7 @@ static void enqueue_frame(Context *c) {
         (void)hipStreamWaitEvent(sf, c->ev_depth, 0);
         c->depth_wait = false;
     }
-    for (int k = 0; k < n_dreg; k++) {  // the z-buffered scatter of the step's unregistered depth planes (descriptors: the head of this function)
-        const DepthRegStep &T = dreg(k);
-        const dim3 grid((T.px + 255) / 256, T.n);
-        if (k == 0) LAUNCH(21, sf, k_depth_register, grid, dim3(256), 0, T.tab);
-        else hipLaunchKernelGGL(k_depth_register, grid, dim3(256), 0, sf, T.tab);
-    }
+    scatter_depth_planes(c, dreg);  // (behind the wait for ev_depth: a host call's depth plane arrives on the early stream)
     LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
     if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
@@ -1614,6 +1518,8 @@ static const uint8_t *host_plane(Context *c, const uint8_t *view, const void *sr
 }  // namespace lvt
 
 using namespace lvt;
+
+#include "lvt_frame_props.h"
 
 // =================================================================================================
 // C-ABI
@@ -2642,31 +2548,25 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
         drain(c);
         const FrameBuf &FB = c->h_seqs[0].fb[c->last_par];
         const size_t n = (size_t)c->pitch * c->prm.H;
-        if (what == 2) {  // the rectified image of the last (raw) frame
-            if (!c->has_rect(0) || c->done == 0) return 0;
-            if ((size_t)cap_bytes < n) return -1;
-            HIPCHK(c, hipMemcpy(dst, c->d_rect[(size_t)c->last_par * 2 + (eye ? 1 : 0)], n, hipMemcpyDeviceToHost));
-            if (pitch_out) *pitch_out = c->pitch;
-            return (int)n;
+        const int e = eye ? 1 : 0;
+        const void *src = (what == 0) ? (const void *)FB.score[e] : (const void *)FB.boxsum[e];
+        size_t esz = (what == 0) ? 1 : 2;
+        if (what >= 2 && what <= 4) {  // a frame property's plane: 0 bytes unless the last frame went through that stage
+            if (c->done == 0) return 0;
+            if (what == 2) {  // the rectified image of the last (raw) frame
+                if (!c->has_rect(0)) return 0;
+                src = c->d_rect[(size_t)c->last_par * 2 + e], esz = 1;
+            } else if (what == 3) {  // the converted gray image of the last (colour) frame, before rectification
+                if (c->fmt_of(0) == PIX_GRAY8 || !c->ring_converted[c->last_slot]) return 0;
+                src = c->d_gray[(size_t)c->last_par * 2 + (c->sensor == 1 ? e : 0)], esz = 1;
+            } else {  // the registered depth plane of the last frame (fp32, pitch words per row)
+                if (!c->has_depth_cam(0) || !c->ring_registered[c->last_slot]) return 0;
+                src = c->d_reg[(size_t)c->last_par], esz = sizeof(float);
+            }
         }
-        if (what == 3) {  // the converted gray image of the last (colour) frame, before rectification
-            if (c->fmt_of(0) == PIX_GRAY8 || c->done == 0 || !c->ring_converted[c->last_slot]) return 0;  // (the last frame must have been a colour frame)
-            if ((size_t)cap_bytes < n) return -1;
-            HIPCHK(c, hipMemcpy(dst, c->d_gray[(size_t)c->last_par * 2 + ((eye && c->sensor == 1) ? 1 : 0)], n, hipMemcpyDeviceToHost));
-            if (pitch_out) *pitch_out = c->pitch;
-            return (int)n;
-        }
-        if (what == 4) {  // the registered depth plane of the last frame (fp32, pitch words per row)
-            if (!c->has_depth_cam(0) || c->done == 0 || !c->ring_registered[c->last_slot]) return 0;  // (the last frame's depth must have been registered)
-            if ((size_t)cap_bytes < n * sizeof(float)) return -1;
-            HIPCHK(c, hipMemcpy(dst, c->d_reg[(size_t)c->last_par], n * sizeof(float), hipMemcpyDeviceToHost));
-            if (pitch_out) *pitch_out = c->pitch;
-            return (int)(n * sizeof(float));
-        }
-        const size_t bytes = n * (what == 0 ? 1 : 2);
+        const size_t bytes = n * esz;
         if ((size_t)cap_bytes < bytes) return -1;
-        if (what == 0) HIPCHK(c, hipMemcpy(dst, FB.score[eye ? 1 : 0], bytes, hipMemcpyDeviceToHost));
-        else HIPCHK(c, hipMemcpy(dst, FB.boxsum[eye ? 1 : 0], bytes, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
         if (pitch_out) *pitch_out = c->pitch;
         return (int)bytes;
     } catch (...) {
@@ -2946,267 +2846,8 @@ LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier h, float *map1, float *
     return (hipMemcpy(map1, r->d_map1, n, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(map2, r->d_map2, n, hipMemcpyDeviceToHost) == hipSuccess) ? 0 : -1;
 }
 
-// ---- raw frames: rectifiers attached to a tracker (Context::rect) -------------------------------------------------------------------------
-// Everything is checked before anything changes: 0 = attached / detached, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
-static int rect_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_rectifiers", why + " (nothing was changed)"); }
-static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
-    Context *c = frame_context(h, "lvt_amd_set_rectifiers", 1, batch_call,
-                               {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)",
-                                "an RGB-D handle (there is one image, and its depth plane is registered to it) (nothing was changed)",
-                                "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers (nothing was changed)"});
-    if (!c) return -1;
-    DeviceGuard guard(c);
-    try {
-        if (seq < 0 || seq >= c->B) return rect_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
-        if ((left == nullptr) != (right == nullptr)) return rect_refuse(h, "one rectifier is NULL (both, or NULL, NULL to detach)");
-        Rectifier *rl = static_cast<Rectifier *>(left), *rr = static_cast<Rectifier *>(right);
-        const Params &q = c->seq_prm(seq);
-        for (Rectifier *r : {rl, rr}) {
-            if (!r) continue;
-            if (r->w != q.W || r->h != q.H)
-                return rect_refuse(h, "a rectifier of " + std::to_string(r->w) + " x " + std::to_string(r->h) + " on a sequence of " + std::to_string(q.W) + " x " + std::to_string(q.H));
-            if (r->device != c->device)
-                return rect_refuse(h, "a rectifier created on device " + std::to_string(r->device) + ", the handle owns device " + std::to_string(c->device));
-        }
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
-        if (c->done < c->enq || c->pend.valid) return rect_refuse(h, "frames in flight: attach before the first frame or after every frame has been collected");
-        if (c->rect.empty()) {
-            c->rect.assign(2 * (size_t)c->B, nullptr);
-            c->d_rect.assign((size_t)c->B * NPAR * 2, nullptr);
-        }
-        if (rl) {
-            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * q.H;
-            for (int k = 0; k < NPAR * 2; k++) {
-                uint8_t *&d = c->d_rect[(size_t)seq * NPAR * 2 + k];
-                if (!d) d = c->dalloc<uint8_t>(plane + 64);
-            }
-        }
-        c->rect[2 * (size_t)seq] = rl, c->rect[2 * (size_t)seq + 1] = rr;
-        c->n_rect = 0;
-        for (int s = 0; s < c->B; s++) c->n_rect += c->rect[2 * (size_t)s] != nullptr;
-        return 0;
-    } catch (...) {
-    }
-    return -1;
-}
-// an lvt_create handle: decided under its record's lock -- a handle that has not been used yet may be given a seat by another thread's lvt_create at any time --,
-// and a successful attach is a use: the handle keeps its own chain
-static int set_rectifiers_any(lvt_handle h, int seq, bool batch_call, lvt_amd_rectifier left, lvt_amd_rectifier right) {
-    if (!is_auto(h)) return set_rectifiers(h, seq, batch_call, left, right);
-    AutoHandle *A = static_cast<AutoHandle *>(h);
-    std::lock_guard<std::mutex> g(A->mu);
-    const int rc = set_rectifiers(A->impl, seq, batch_call, left, right);
-    if (rc == 0) A->started = true;
-    return rc;
-}
-LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right) { return set_rectifiers_any(h, 0, false, left, right); }
-LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right) {
-    return set_rectifiers_any(h, seq, true, left, right);
-}
-
-// ---- colour frames: a pixel format per handle / per sequence of a batch (Context::pixfmt) ----------------------------------------------------
-// Everything is checked before anything changes: 0 = set, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
-static int pix_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_pixel_format", why + " (nothing was changed)"); }
-static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) {
-    Context *c = frame_context(h, "lvt_amd_set_pixel_format", 0, batch_call,
-                               {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
-                                "a batch handle takes its pixel formats per sequence through lvt_amd_batch_set_pixel_format (nothing was changed)"});
-    if (!c) return -1;
-    DeviceGuard guard(c);
-    try {
-        if (batch_call && c->B == 1 && !c->mixed) return pix_refuse(h, "lvt_amd_batch_set_pixel_format on a handle that is not a batch (use lvt_amd_set_pixel_format)");
-        if (seq < 0 || seq >= c->B) return pix_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
-        if (format < PIX_GRAY8 || format > PIX_RGBA8) return pix_refuse(h, "unknown pixel format " + std::to_string(format));
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
-        if (c->done < c->enq || c->pend.valid) return pix_refuse(h, "frames in flight: set the format before the first frame or after every frame has been collected");
-        if (format == c->fmt_of(seq)) return 0;
-        if (c->pixfmt.empty()) {
-            c->pixfmt.assign((size_t)c->B, PIX_GRAY8);
-            c->d_gray.assign((size_t)c->B * NPAR * 2, nullptr);
-        }
-        if (format != PIX_GRAY8) {
-            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
-            for (int par = 0; par < NPAR; par++)
-                for (int e = 0; e < (c->sensor == 2 ? 1 : 2); e++) {
-                    uint8_t *&d = c->d_gray[((size_t)seq * NPAR + par) * 2 + e];
-                    if (!d) d = c->dalloc<uint8_t>(plane + 64);
-                }
-        }
-        if (seq == 0 && pix_bpp(format) != c->bpp_of(0)) stage_release(c);  // (the pinned staging of the host entry points is sized by bpp: reserved again at the next frame)
-        c->pixfmt[(size_t)seq] = format;
-        c->n_colour = 0;
-        for (int s = 0; s < c->B; s++) c->n_colour += c->pixfmt[(size_t)s] != PIX_GRAY8;
-        return 0;
-    } catch (...) {
-    }
-    return -1;
-}
-// (an lvt_create handle: as for rectifiers, decided under its record's lock, and a successful set is a use)
-static int set_pixel_format_any(lvt_handle h, int seq, bool batch_call, int format) {
-    if (!is_auto(h)) return set_pixel_format(h, seq, batch_call, format);
-    AutoHandle *A = static_cast<AutoHandle *>(h);
-    std::lock_guard<std::mutex> g(A->mu);
-    const int rc = set_pixel_format(A->impl, seq, batch_call, format);
-    if (rc == 0) A->started = true;
-    return rc;
-}
-LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format) { return set_pixel_format_any(h, 0, false, format); }
-LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format) { return set_pixel_format_any(h, seq, true, format); }
-LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
-    h = resolve_handle(h, false);
-    if (is_slot(h)) return seq == 0 ? PIX_GRAY8 : -1;
-    if (!is_ctx(h)) return -1;
-    const Context *c = static_cast<const Context *>(h);
-    return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
-}
-
-// ---- unregistered depth: a depth camera per handle / per sequence of a batch (Context::depth_cam, k_depthreg.hip) ----------------------------------
-// Everything is checked before anything changes: 0 = set / cleared, -1 = refused, the handle is as it was and lvt_amd_last_error says why.
-static int dcam_refuse(lvt_handle h, const std::string &why) { return refuse(h, "lvt_amd_set_depth_camera", why + " (nothing was changed)"); }
-// "" when the record passes
-static std::string depth_camera_check(const lvt_amd_depth_camera &d) {
-    if (d.width < 1 || d.width > 8192 || d.height < 1 || d.height > 8192)
-        return "a depth camera of " + std::to_string(d.width) + " x " + std::to_string(d.height) + " pixels (1 ... 8192 each way)";
-    bool finite = std::isfinite(d.fx) && std::isfinite(d.fy) && std::isfinite(d.cx) && std::isfinite(d.cy);
-    for (float v : d.R) finite = finite && std::isfinite(v);
-    for (float v : d.t) finite = finite && std::isfinite(v);
-    if (!finite) return "a depth camera with a non-finite field";
-    if (!(d.fx > 0.f && d.fy > 0.f)) return "a depth camera whose fx or fy is not > 0";
-    return "";
-}
-static int set_depth_camera(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_camera *cam) {
-    Context *c = frame_context(h, "lvt_amd_set_depth_camera", 2, batch_call,
-                               {"a pooled handle (pooled handles are stereo only) (nothing was changed)",
-                                "a stereo handle (it has no depth plane to register) (nothing was changed)",
-                                "a batch handle takes its depth cameras per sequence through lvt_amd_batch_set_depth_camera (nothing was changed)"});
-    if (!c) return -1;
-    DeviceGuard guard(c);
-    try {
-        if (batch_call && c->B == 1 && !c->mixed) return dcam_refuse(h, "lvt_amd_batch_set_depth_camera on a handle that is not a batch (use lvt_amd_set_depth_camera)");
-        if (seq < 0 || seq >= c->B) return dcam_refuse(h, "no sequence " + std::to_string(seq) + " in this handle");
-        if (cam) {
-            const std::string why = depth_camera_check(*cam);
-            if (!why.empty()) return dcam_refuse(h, why);
-        }
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
-        if (c->done < c->enq || c->pend.valid) return dcam_refuse(h, "frames in flight: set the camera before the first frame or after every frame has been collected");
-        if (!cam && !c->has_depth_cam(seq)) return 0;
-        if (c->depth_cam.empty()) {
-            c->depth_cam.assign((size_t)c->B, lvt_amd_depth_camera{});
-            c->d_reg.assign((size_t)c->B * NPAR, nullptr);
-        }
-        if (cam) {
-            const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
-            for (int par = 0; par < NPAR; par++) {
-                float *&d = c->d_reg[(size_t)seq * NPAR + par];
-                if (!d) d = c->dalloc<float>(plane + 16);
-            }
-        }
-        if (seq == 0) stage_release(c);  // (the pinned staging of the host entry points is sized by the depth plane: reserved again at the next frame)
-        c->depth_cam[(size_t)seq] = cam ? *cam : lvt_amd_depth_camera{};
-        c->n_depth_cam = 0;
-        for (int s = 0; s < c->B; s++) c->n_depth_cam += c->depth_cam[(size_t)s].width > 0;
-        return 0;
-    } catch (...) {
-    }
-    return -1;
-}
-// (an lvt_create handle is a stereo handle: refused like one, under its record's lock, and a refusal is no use)
-static int set_depth_camera_any(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_camera *cam) {
-    if (!is_auto(h)) return set_depth_camera(h, seq, batch_call, cam);
-    AutoHandle *A = static_cast<AutoHandle *>(h);
-    std::lock_guard<std::mutex> g(A->mu);
-    const int rc = set_depth_camera(A->impl, seq, batch_call, cam);
-    if (rc == 0) A->started = true;
-    return rc;
-}
-LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam) { return set_depth_camera_any(h, 0, false, cam); }
-LVT_API int lvt_amd_batch_set_depth_camera(lvt_handle h, int seq, const lvt_amd_depth_camera *cam) { return set_depth_camera_any(h, seq, true, cam); }
-LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out) {
-    h = resolve_handle(h, false);
-    if (is_slot(h)) return seq == 0 ? 0 : -1;
-    if (!is_ctx(h)) return -1;
-    const Context *c = static_cast<const Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    if (!c->has_depth_cam(seq)) return 0;
-    if (out) *out = c->depth_cam[(size_t)seq];
-    return 1;
-}
-// the stage alone on caller data: clear, then scatter, on the caller's stream
-LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour, const void *d_depth, int depth_pitch_bytes,
-                                          int depth_format, float depth_scale, void *d_out, int out_pitch_bytes, void *hip_stream) {
-    if (!cam || !colour || !d_depth || !d_out || !depth_camera_check(*cam).empty()) return -1;
-    if (depth_format != DEPTH_F32 && depth_format != DEPTH_U16) return -1;
-    if (depth_format == DEPTH_U16 && !(std::isfinite(depth_scale) && depth_scale > 0.f)) return -1;
-    const int esz = (depth_format == DEPTH_U16) ? 2 : 4;
-    if (((uintptr_t)d_depth % esz) || depth_pitch_bytes <= 0 || (depth_pitch_bytes % esz) || (long long)depth_pitch_bytes < (long long)cam->width * esz) return -1;
-    if (colour->img_width < 1 || colour->img_width > 8192 || colour->img_height < 1 || colour->img_height > 8192) return -1;
-    if (((uintptr_t)d_out & 3) || (out_pitch_bytes & 3) || (long long)out_pitch_bytes < (long long)colour->img_width * 4) return -1;
-    DepthRegTable tab;
-    std::memset(&tab, 0, sizeof(tab));
-    DepthRegImg &I = tab.im[0];
-    I.src = d_depth, I.src_pitch = depth_pitch_bytes / esz, I.fmt = depth_format, I.scale = (depth_format == DEPTH_U16) ? depth_scale : 0.f;
-    I.dst = static_cast<float *>(d_out), I.dst_pitch = out_pitch_bytes / 4;
-    I.dw = cam->width, I.dh = cam->height, I.fx = cam->fx, I.fy = cam->fy, I.cx = cam->cx, I.cy = cam->cy;
-    std::memcpy(I.R, cam->R, sizeof(I.R)), std::memcpy(I.t, cam->t, sizeof(I.t));
-    I.cfx = colour->fx, I.cfy = colour->fy, I.ccx = colour->cx, I.ccy = colour->cy;
-    I.k1 = colour->k1, I.k2 = colour->k2, I.p1 = colour->p1, I.p2 = colour->p2, I.k3 = colour->k3;
-    I.W = colour->img_width, I.H = colour->img_height;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const size_t words = (size_t)I.dst_pitch * I.H;
-    if ((words + 3) / 4 / 256 + 1 > 0x7FFFFFFFull) return -1;
-    hipLaunchKernelGGL(k_depth_clear, dim3((unsigned)(((words + 3) / 4 + 255) / 256), 1), dim3(256), 0, st, tab);
-    hipLaunchKernelGGL(k_depth_register, dim3((unsigned)((I.dw * I.dh + 255) / 256), 1), dim3(256), 0, st, tab);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ------------------------------
-static int enable_pose_info(lvt_handle h, int enable) {
-    static const char *who = "lvt_amd_enable_pose_info";
-    Context *c = frame_context(h, who, 0, true, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr, nullptr});
-    if (!c) return -1;
-    DeviceGuard guard(c);
-    try {
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
-        if (c->done < c->enq || c->pend.valid) return refuse(h, who, "frames in flight: enable before the first frame or after every frame has been collected (nothing was changed)");
-        if ((enable != 0) == c->pose_info) return 0;
-        if (enable && !c->h_pinfo) {
-            HIPCHK(c, hipHostMalloc((void **)&c->h_pinfo, sizeof(lvt_amd_pose_info) * c->B * RING, hipHostMallocCoherent));
-            HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinfo_dev, c->h_pinfo, 0));
-        }
-        for (int s = 0; s < c->B; s++) pose_info_clear(c, s);  // (either way: the last frame has no record)
-        c->pose_info = enable != 0;
-        return 0;
-    } catch (...) {
-    }
-    return -1;
-}
-LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) {
-    if (!is_auto(h)) return enable_pose_info(h, enable);
-    AutoHandle *A = static_cast<AutoHandle *>(h);  // (an lvt_create handle: decided under its record's lock, and a successful call is a use)
-    std::lock_guard<std::mutex> g(A->mu);
-    const int rc = enable_pose_info(A->impl, enable);
-    if (rc == 0) A->started = true;
-    return rc;
-}
-LVT_API int lvt_amd_get_pose_info(lvt_handle h, int seq, lvt_amd_pose_info *out) {
-    h = resolve_handle(h);
-    if (!out) return -1;
-    std::memset(out, 0, sizeof(*out));
-    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has it enabled)
-    if (!is_ctx(h)) return -1;
-    Context *c = static_cast<Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    if (!c->pose_info) return 0;
-    DeviceGuard guard(c);
-    try {
-        drain(c);  // (as lvt_amd_get_pose / lvt_amd_get_counts: the last frame enqueued, collected)
-        *out = c->h_pinfo[(size_t)c->last_slot * c->B + seq];
-        return 1;
-    } catch (...) {
-    }
-    return -1;
-}
+// (the properties of a handle -- rectifiers, pixel format, depth camera, pose info -- and their entry points: lvt_frame_props.h)
+// ---- stage entry: the pose-uncertainty record on caller data (k_poseinfo.hip) ---------------------------------------------------------------------
 LVT_API int lvt_amd_pose_info_eval(const lvt_amd_params *pin, const double q_wxyz[4], const double pos[3], const double *pts, const float *obs, int n,
                                    lvt_amd_pose_info *out) {
     if (!pin || !q_wxyz || !pos || !out || n < 0 || n > NF_MAX || (n > 0 && (!pts || !obs))) return -1;
@@ -3312,20 +2953,19 @@ static void snap_info(const SnapHeader &h, const Ctl &k, int device, lvt_amd_sna
     out->map_n = h.map_n, out->staged_n = h.staged_n, out->src_map_cur = h.map_cur, out->src_staged_cur = h.staged_cur, out->device = device, out->bytes = h.total;
 }
 
-static int snap_refuse(lvt_handle h, const char *who, const std::string &why) { return refuse(h, who, why + " (nothing was changed)"); }
 // the context behind a (resolved) handle for a snapshot call; batch_call: the calls that take every sequence / name one of a batch.  nullptr: refused
 static Context *snap_context(lvt_handle h, const char *who, bool batch_call) {
     Context *c = frame_context(h, who, 0, true, {"a pooled or automatic seat (its state lives in a chain shared with other handles) (nothing was changed)", nullptr, nullptr});
     if (!c) return nullptr;
     if (batch_call && c->B == 1 && !c->mixed) {
-        snap_refuse(h, who, "a batch call on a handle that is not a batch");
+        refuse_unchanged(h, who, "a batch call on a handle that is not a batch");
         return nullptr;
     }
     return c;
 }
 static bool snap_seq_ok(Context *c, const char *who, int seq) {
     if (seq >= 0 && seq < c->B) return true;
-    snap_refuse(c, who, "no sequence " + std::to_string(seq) + " in this handle" + (c->B == 1 ? " (seq is 0 for a solo handle)" : ""));
+    refuse_unchanged(c, who, "no sequence " + std::to_string(seq) + " in this handle" + (c->B == 1 ? " (seq is 0 for a solo handle)" : ""));
     return false;
 }
 static StateSeq state_desc(Context *c, int s, uint8_t *blob, const SnapHeader &h) {
@@ -3353,15 +2993,16 @@ static StateSeq state_desc(Context *c, int s, uint8_t *blob, const SnapHeader &h
 static void state_launch(Context *c, bool pack, const std::vector<StateSeq> &ds, const ChainWords &cw) {
     const int slot = pack ? 22 : 23;
     if (c->prof) (void)hipEventRecord(c->ev[slot][0], c->stream);
-    for (size_t i0 = 0; i0 < ds.size(); i0 += STATE_PACK) {
-        const int n = (int)std::min(ds.size() - i0, (size_t)STATE_PACK);
-        StateTable tab{};
-        unsigned work = 0;
-        for (int i = 0; i < n; i++) tab.s[i] = ds[i0 + i], work = std::max(work, state_work(tab.s[i].map_n_blob, tab.s[i].staged_n_blob));
+    size_t i0 = 0;  // sequences sent so far
+    unsigned work = 0;
+    TablePacker pk(&StateTable::s, [&](const StateTable &tab, int n, bool) {
         const dim3 grid(std::min((work + 255u) / 256u, 256u), n);
         if (pack) hipLaunchKernelGGL(k_state_pack, grid, dim3(256), 0, c->stream, tab, c->d_snap_status + 4 * i0);
         else hipLaunchKernelGGL(k_state_unpack, grid, dim3(256), 0, c->stream, tab, chain_arg(cw));
-    }
+        i0 += (size_t)n, work = 0;
+    });
+    for (const StateSeq &d : ds) *pk.add(1) = d, work = std::max(work, state_work(d.map_n_blob, d.staged_n_blob));
+    pk.flush();
     if (c->prof) (void)hipEventRecord(c->ev[slot][1], c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
@@ -3372,7 +3013,12 @@ static void state_launch(Context *c, bool pack, const std::vector<StateSeq> &ds,
 // from the host's record of the last frame (its map / staged counters); the kernel reports what it found on the device, and the read-back confirms the sizes --
 // should they ever differ, the blobs are sized again from the device's figures.
 static void take_snapshots(Context *c, const std::vector<int> &seqs, std::vector<Snapshot *> &out) {
-    if (!c->d_snap_status) c->d_snap_status = c->dalloc<int>(4 * (size_t)c->B);
+    if (!c->d_snap_status) {
+        c->d_snap_status = c->dalloc<int>(4 * (size_t)c->B);
+        // dalloc clears on the null stream, which the (non-blocking) tracking stream does not wait for: a clear that lands behind the first pack launch
+        // would wipe what it reported, and both sizing attempts would fail ("point counts changed")
+        HIPCHK(c, hipStreamSynchronize(nullptr));
+    }
     const size_t n = seqs.size();
     std::vector<int> found(4 * n, 0);
     out.assign(n, nullptr);
@@ -3442,6 +3088,7 @@ static void apply_snapshots(Context *c, const std::vector<int> &seqs, const std:
         pose_info_clear(c, seqs[i]);
     }
 }
+// (h: resolved; the entry points below come through with_auto_handle)
 static int snapshot_apply(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_snapshot *list) {
     Context *c = snap_context(h, who, batch_call);
     if (!c) return -1;
@@ -3450,33 +3097,23 @@ static int snapshot_apply(lvt_handle h, const char *who, bool batch_call, int se
         std::vector<int> seqs;
         std::vector<Snapshot *> snaps;
         if (!batch_call && !snap_seq_ok(c, who, seq)) return -1;
-        if (!list) return snap_refuse(h, who, "no snapshot");
+        if (!list) return refuse_unchanged(h, who, "no snapshot");
         for (int i = 0; i < (batch_call ? c->B : 1); i++) {
             const int s = batch_call ? i : seq;
             if (batch_call && !list[i]) continue;  // (left alone)
             Snapshot *p = snap_of(list[i]);
             const std::string tag = c->B > 1 ? "sequence " + std::to_string(s) + ": " : "";
-            if (!p) return snap_refuse(h, who, tag + "not a snapshot");
+            if (!p) return refuse_unchanged(h, who, tag + "not a snapshot");
             const std::string why = apply_objection(c, s, p);
-            if (!why.empty()) return snap_refuse(h, who, tag + why);
+            if (!why.empty()) return refuse_unchanged(h, who, tag + why);
             seqs.push_back(s), snaps.push_back(p);
         }
-        if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: nobody's to collect)
-        if (c->done < c->enq || c->pend.valid) return snap_refuse(h, who, "frames in flight: apply after every frame has been collected");
+        if (frames_in_flight(c)) return refuse_unchanged(h, who, "frames in flight: apply after every frame has been collected");
         if (!seqs.empty()) apply_snapshots(c, seqs, snaps);
         return 0;
     } catch (...) {
     }
     return -1;
-}
-// (an lvt_create handle: as for rectifiers, decided under its record's lock, and a successful apply is a use)
-static int snapshot_apply_any(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_snapshot *list) {
-    if (!is_auto(h)) return snapshot_apply(h, who, batch_call, seq, list);
-    AutoHandle *A = static_cast<AutoHandle *>(h);
-    std::lock_guard<std::mutex> g(A->mu);
-    const int rc = snapshot_apply(A->impl, who, batch_call, seq, list);
-    if (rc == 0) A->started = true;
-    return rc;
 }
 }  // namespace lvt
 extern "C" {
@@ -3504,7 +3141,7 @@ LVT_API int lvt_amd_batch_snapshot_take(lvt_handle h, lvt_amd_snapshot *out) {
     if (!c) return -1;
     DeviceGuard guard(c);
     try {
-        if (!out) return snap_refuse(h, who, "no array to return the snapshots in");
+        if (!out) return refuse_unchanged(h, who, "no array to return the snapshots in");
         drain(c);
         std::vector<int> seqs(c->B);
         for (int s = 0; s < c->B; s++) seqs[s] = s;
@@ -3516,8 +3153,12 @@ LVT_API int lvt_amd_batch_snapshot_take(lvt_handle h, lvt_amd_snapshot *out) {
     }
     return -1;
 }
-LVT_API int lvt_amd_snapshot_apply(lvt_handle h, int seq, lvt_amd_snapshot s) { return snapshot_apply_any(h, "lvt_amd_snapshot_apply", false, seq, &s); }
-LVT_API int lvt_amd_batch_snapshot_apply(lvt_handle h, const lvt_amd_snapshot *s) { return snapshot_apply_any(h, "lvt_amd_batch_snapshot_apply", true, 0, s); }
+LVT_API int lvt_amd_snapshot_apply(lvt_handle h, int seq, lvt_amd_snapshot s) {
+    return with_auto_handle(h, [&](lvt_handle t) { return snapshot_apply(t, "lvt_amd_snapshot_apply", false, seq, &s); });
+}
+LVT_API int lvt_amd_batch_snapshot_apply(lvt_handle h, const lvt_amd_snapshot *s) {
+    return with_auto_handle(h, [&](lvt_handle t) { return snapshot_apply(t, "lvt_amd_batch_snapshot_apply", true, 0, s); });
+}
 LVT_API int lvt_amd_batch_reset(lvt_handle h, int seq) {
     static const char *who = "lvt_amd_batch_reset";
     h = resolve_handle(h);

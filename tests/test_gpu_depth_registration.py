@@ -404,6 +404,48 @@ def test_mixed_batch(hip_lib, oracle_lib):
     batch.close()
 
 
+def test_a_batch_with_more_depth_cameras_than_one_table_holds(hip_lib, oracle_lib):
+    """25 RGB-D sequences with the half-size depth camera: each step takes a second k_depth_clear and a second k_depth_register launch, whose table holds
+    sequence 24's descriptor alone.  Sequence s starts at frame s % 3; three steps, one at a time; sequences 0, 23 and 24 against oracle chains fed the
+    numpy-registered planes (state, pose, all counters), every sequence TRACKING; each profile slot counts a step once.  (plane(0, 4) answers for sequence 0:
+    the stage alone is held to numpy on sequence 24's last input instead.)"""
+    need(hip_lib, *NEW)
+    q, P = D.sequence("half"), planes("half")
+    B, steps = 25, 3
+    batch = hip_lib.LvtBatch(q.prm, B, 2)
+    for s in range(B):
+        assert batch.set_depth_camera(s, q.cam) == 0, batch.last_error()
+    refs = []
+    for o in range(3):
+        orc, out = oracle_lib.Oracle(q.prm, 2), []
+        for i in range(o, o + steps):
+            Ro, to = orc.track_rgbd(q.gray[i], q.f32[i])
+            out.append((np.array(Ro), np.array(to), orc.status, orc.counts()))
+        assert [r[2] for r in out] == [2] * steps, "the oracle is not TRACKING on every frame"
+        refs.append(out)
+    batch.profile_enable(True)
+    for k in range(steps):
+        fr = [k + s % 3 for s in range(B)]
+        dd = [P.depth(i, hip_lib.DEPTH_U16) for i in fr]
+        assert batch.track_rgbd_device_async([P.gray(i) for i in fr], [x[0] for x in dd], q.H, q.W, P.gpitch, [x[1] for x in dd], hip_lib.DEPTH_U16, SCALE) == 0, \
+            batch.last_error()
+        R, t, st = batch.wait()
+        assert batch.last_error() == "", batch.last_error()
+        assert list(st) == [2] * B, (k, list(st))
+        for s in (0, 23, 24):
+            ref = refs[s % 3][k]
+            e_t, e_R = pose_errors(R[s], t[s], ref[0], ref[1])
+            print(f"sequence {s} step {k}: e_t {e_t:.2e} e_R {e_R:.2e}")
+            assert e_t <= POSE_TOL and e_R <= POSE_TOL, f"sequence {s} step {k}: {e_t:.2e} {e_R:.2e}"
+            ch = batch.counts(s)
+            wrong = {n: (ch.get(n), v) for n, v in ref[3].items() if ch.get(n) != v}
+            assert not wrong, f"sequence {s} step {k}: counters (hip, oracle) {wrong}"
+    prof = dict(_profile_of(batch))
+    assert prof["k_depth_clear"] == steps and prof["k_depth_register"] == steps, prof   # (a slot times a step's first launch)
+    batch.close()
+    check_stage(hip_lib, q.cam, q.prm, q.s_u16[steps - 1 + 24 % 3], SCALE)
+
+
 def test_colour_handle_with_a_depth_camera(hip_lib, oracle_lib):
     """a colour (LVT_AMD_PIX_RGB8) handle with a depth camera: convert, register, track -- held to the oracle on the gray frames and the numpy planes"""
     q = D.sequence("half")

@@ -347,6 +347,33 @@ def test_launch_accounting(hip_lib, oracle_lib):
     assert batch.last_error() == "", batch.last_error()
 
 
+def test_a_batch_with_more_raw_sequences_than_one_table_holds(hip_lib, oracle_lib):
+    """33 raw stereo sequences on ONE rectifier pair = 66 images: the step takes a second k_rectify_frames launch (sequence 32's two images).  Sequence s
+    starts at frame s % 3 of case A; three steps; sequences 0, 1, 31 and 32 against their oracle chains (state, pose, all counters), every sequence TRACKING"""
+    c = get_case("A")
+    B, steps = 33, 3
+    batch = hip_lib.LvtBatch(c.prm, B)
+    rl, rr = c.rectifiers(hip_lib)
+    for s in range(B):
+        assert batch.set_rectifiers(s, rl, rr) == 0, batch.last_error()
+    dev = device_planes(c.raw[:steps + 2], c.W, c.H, 624)
+    refs = [c.chain(o, steps) for o in range(3)]
+    assert all(r[2] == 2 for ref in refs for r in ref), "the oracle is not TRACKING on every frame: an early LOST would hide a difference"
+    batch.profile_enable(True)
+    for k in range(steps):
+        fr = [k + s % 3 for s in range(B)]
+        batch.track_device_async([dev[i, 0].data_ptr() for i in fr], [dev[i, 1].data_ptr() for i in fr], c.H, c.W, 624)
+        R, t, st = batch.wait()
+        assert batch.last_error() == "", batch.last_error()
+        assert list(st) == [2] * B, (k, list(st))
+        for s in (0, 1, 31, 32):
+            ref = refs[s % 3][k]
+            assert st[s] == ref[2]
+            close_to(R[s], t[s], ref, f"sequence {s} step {k}")
+            counts_equal(batch.counts(s), ref[3], f"sequence {s} step {k}")
+    assert dict(_profile_of(batch))["k_rectify_frames"] == steps   # (the slot times a step's first launch)
+
+
 # ---- 6. refusals and detach ------------------------------------------------------------------------------------------------------------
 def test_refused_attachments(hip_lib, oracle_lib, tmp_path):
     """every refusal returns -1 with a reason and leaves the handle as it was"""

@@ -222,6 +222,56 @@ def test_into_and_out_of_a_mixed_batch(hip_lib, oracle_lib):
         x.close()
 
 
+def test_a_batch_with_more_snapshots_than_one_table_holds(hip_lib):
+    """a uniform batch of 17 (sequence s starts at frame s % 3 of the half-size world) is snapshot after two steps -- a second k_state_pack launch, whose table
+    holds sequence 16 alone --, exported, imported and applied to a second batch of 17 -- a second k_state_unpack launch.  Sequences 0, 15 and 16 export the bytes
+    a solo handle on the same frames exports, and continue in the second batch with the solo handle's poses bit for bit, as every sequence does with the first batch's"""
+    world, prm, _ = make_case("kitti", 0, 0.5)
+    B, cut, n = 17, 2, 4
+    q = Seq(world, prm, n + 2)
+    solo = {}
+    for o in (0, 1):                                             # (sequences 0 and 15 start at frame 0, sequence 16 at frame 1)
+        h = hip_lib.LvtSystem.create(prm, 1)
+        for i in range(cut):
+            h.track(*q.frames[o + i])
+        snap = h.snapshot()
+        solo[o] = (snap.to_bytes(), [h.track(*q.frames[o + i]) for i in range(cut, n)])
+        assert h.last_error() == "" and h.get_state() == 2, h.last_error()
+        snap.close(); h.close()
+
+    def steps(batch, ks):
+        out = []
+        for k in ks:
+            fr = [q.ptrs(k + s % 3) for s in range(B)]
+            batch.track_device_async([f[0] for f in fr], [f[1] for f in fr], q.H, q.W, q.pitch)
+            out.append(batch.wait())
+            assert batch.last_error() == "", batch.last_error()
+        return out
+
+    first = hip_lib.LvtBatch(prm, B)
+    steps(first, range(cut))
+    snaps = first.snapshot()
+    raw = [x.to_bytes() for x in snaps]
+    for s in (0, 15, 16):
+        want = solo[s % 3][0]
+        assert raw[s] == want, (s, [i for i in range(0, len(want), 4) if raw[s][i:i + 4] != want[i:i + 4]][:16])
+    second = hip_lib.LvtBatch(prm, B)
+    imported = [hip_lib.Snapshot.from_bytes(b) for b in raw]
+    assert second.restore_all(imported) == 0, second.last_error()
+    for s in (0, 15, 16):
+        assert second.counts(s) == first.counts(s), s              # (the seats answer from the snapshots at once)
+    a, b = steps(first, range(cut, n)), steps(second, range(cut, n))
+    for k in range(n - cut):
+        assert list(b[k][2]) == [2] * B, (k, list(b[k][2]))
+        assert np.array_equal(a[k][0], b[k][0]) and np.array_equal(a[k][1], b[k][1]), f"step {cut + k}: the restored batch's poses differ from the source's"
+        for s in (0, 15, 16):
+            R, t = solo[s % 3][1][k]
+            assert np.array_equal(b[k][0][s], R) and np.array_equal(b[k][1][s], t), f"sequence {s} step {cut + k}: not the solo handle's pose"
+    for x in snaps + imported:
+        x.close()
+    first.close(); second.close()
+
+
 def test_rgbd(hip_lib, oracle_lib):
     world, prm, sensor = make_case("tum", 0, 1.0)
     assert sensor == 2
