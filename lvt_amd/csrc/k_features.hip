@@ -1982,6 +1982,54 @@ __device__ __forceinline__ int box_at(const Seq &S, const FrameBuf &FB, int eye,
     return s;
 }
 
+// ---- what k_brief and k_brief_img share beside their loop: where a workgroup works, which key points a wave takes, where a key point's tests are centred, and
+//      who publishes the frame ----
+// workgroups go to the 8 XCDs round-robin by their linear id, and every XCD has its own L2: with the plain mapping each L2 sees the
+// box-sum planes of ALL sequences (30 MB for a batch of 16) and every window comes from the Infinity Cache.  When the number of planes
+// is a multiple of 8, XCD x takes planes x, x + 8, ... whole, so a plane is pulled into ONE L2, once.  Returns the number of planes.
+__device__ __forceinline__ int brief_plane_of_block(int &plane, int &bx) {
+    const int planes = gridDim.y * gridDim.z;
+    int lid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    plane = lid / gridDim.x, bx = lid % gridDim.x;
+    if ((planes & 7) == 0) {
+        const int j = lid >> 3;
+        plane = (lid & 7) + 8 * (j / gridDim.x);
+        bx = j % gridDim.x;
+    }
+    return planes;
+}
+// the key points i, i + stride, ... < i_end of this wave (wpb waves per workgroup, n key points in the plane); returns the stride
+// (a single sequence: 2 planes, so the plane-per-XCD mapping above does not apply and every XCD would sample windows all over both
+//  planes -- 5.4 MB fetched for 1.9 MB of box sums.  The key points are stored in detection-cell order: XCD x takes the x-th EIGHTH of
+//  them, i.e. the windows of about one cell and a quarter, and its L2 pulls that part of the plane only.)
+__device__ __forceinline__ int brief_key_points_of_wave(int planes, int bx, int wpb, int n, int &i, int &i_end) {
+    int stride = gridDim.x * wpb;
+    i = bx * wpb + wave_id();
+    i_end = n;
+    if ((planes & 7) != 0 && (gridDim.x & 7) == 0) {
+        const int eighth = (n + 7) >> 3, x = bx & 7;   // (planes are whole multiples of gridDim.x workgroups: bx & 7 is this workgroup's XCD)
+        stride = (gridDim.x >> 3) * wpb;
+        i = x * eighth + (bx >> 3) * wpb + wave_id();
+        i_end = min(n, (x + 1) * eighth);
+    }
+    return stride;
+}
+__device__ __forceinline__ void brief_centre(const Feat &F, int i, int &cy, int &cx) {
+    cy = (int)((double)F.by[i] + 0.5), cx = (int)((double)F.bx[i] + 0.5);
+}
+// the workgroup that finishes last publishes the frame's features (every workgroup calls this behind its last descriptor)
+__device__ __forceinline__ void last_block_publishes(const Seq &S, const FrameBuf &FB, seq_t publish_seq) {
+    __syncthreads();  // every wave's descriptors are written ...
+    if (threadIdx.x == 0) {
+        FeatCtl &fc = *FB.fc;
+        __threadfence();  // ... and visible before this workgroup counts itself
+        if (atomicAdd(&fc.done_blocks, 1u) == gridDim.x * gridDim.y - 1) {
+            fc.done_blocks = 0;
+            publish_features(S, fc, publish_seq);
+        }
+    }
+}
+
 // publish_seq != 0: k_brief is the last kernel of the feature stage and its last workgroup publishes the frame's sequence number
 // for the gates of the other streams (a one-thread kernel behind it cost the feature chain a launch and a boundary)
 // The 512 box sums of a key point lie in the 49x49 window around it (|offset| <= 24: a 48-px patch).  Fetching them one by one made every wave touch
@@ -1995,17 +2043,8 @@ static_assert(brief_max_offset() <= BR_R, "k_brief's window does not cover the t
 constexpr int BR_WIN_DW = BR_ROWS * BR_DW, BR_LOADS = (BR_WIN_DW + 63) / 64;
 template <bool BV>
 __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t publish_seq) {
-    // workgroups go to the 8 XCDs round-robin by their linear id, and every XCD has its own L2: with the plain mapping each L2 sees the
-    // box-sum planes of ALL sequences (30 MB for a batch of 16) and every window comes from the Infinity Cache.  When the number of planes
-    // is a multiple of 8, XCD x takes planes x, x + 8, ... whole, so a plane is pulled into ONE L2, once.
-    const int planes = gridDim.y * gridDim.z;
-    int lid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    int plane = lid / gridDim.x, bx = lid % gridDim.x;
-    if ((planes & 7) == 0) {
-        const int j = lid >> 3;
-        plane = (lid & 7) + 8 * (j / gridDim.x);
-        bx = j % gridDim.x;
-    }
+    int plane, bx;
+    const int planes = brief_plane_of_block(plane, bx);
     const Seq &S = sa.at(plane / gridDim.y);  // (sa.get() indexes by blockIdx.z: the batch form picks its plane's sequence itself)
     const int eye = plane % gridDim.y;
     const FrameBuf &FB = S.fb[par];
@@ -2036,22 +2075,9 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t pub
         ta[w] = (t[0] + BR_R) * (2 * BR_DW) + t[1] + BR_R;
         tb[w] = (t[2] + BR_R) * (2 * BR_DW) + t[3] + BR_R;
     }
-    auto centre = [&](int i, int &cy, int &cx) {
-        cy = (int)((double)F.by[i] + 0.5), cx = (int)((double)F.bx[i] + 0.5);
-    };
     auto inside = [&](int cy, int cx) { return cx - BR_R >= 0 && cx + BR_R < W && cy - BR_R >= 0 && cy + BR_R < H; };
-    // (a single sequence: 2 planes, so the plane-per-XCD mapping above does not apply and every XCD would sample windows all over both
-    //  planes -- 5.4 MB fetched for 1.9 MB of box sums.  The key points are stored in detection-cell order: XCD x takes the x-th EIGHTH of
-    //  them, i.e. the windows of about one cell and a quarter, and its L2 pulls that part of the plane only.)
-    int stride = gridDim.x * wpb;
-    int i = bx * wpb + wave_id();
-    int i_end = n;
-    if ((planes & 7) != 0 && (gridDim.x & 7) == 0) {
-        const int eighth = (n + 7) >> 3, x = bx & 7;   // (planes are whole multiples of gridDim.x workgroups: bx & 7 is this workgroup's XCD)
-        stride = (gridDim.x >> 3) * wpb;
-        i = x * eighth + (bx >> 3) * wpb + wave_id();
-        i_end = min(n, (x + 1) * eighth);
-    }
+    int i, i_end;
+    const int stride = brief_key_points_of_wave(planes, bx, wpb, n, i, i_end);
     uint32_t v[BR_LOADS];
     int cy = 0, cx = 0;
     bool fast = false;
@@ -2063,7 +2089,7 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t pub
         for (int k = 0; k < BR_LOADS; k++) v[k] = src[goff[k]];
     };
     if (i < i_end) {
-        centre(i, cy, cx);
+        brief_centre(F, i, cy, cx);
         fast = inside(cy, cx);
         if (fast) fetch(cy, cx);
     }
@@ -2073,7 +2099,7 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t pub
         int ncy = 0, ncx = 0;
         bool nfast = false;
         if (inext < i_end) {
-            centre(inext, ncy, ncx);
+            brief_centre(F, inext, ncy, ncx);
             nfast = inside(ncy, ncx);
         }
         if (fast) {
@@ -2098,17 +2124,7 @@ __global__ __launch_bounds__(256) void k_brief(SeqArg<BV> sa, int par, seq_t pub
         if (lane < 4) F.desc[(size_t)i * 4 + lane] = (lane == 0) ? word[0] : (lane == 1) ? word[1] : (lane == 2) ? word[2] : word[3];
         cy = ncy, cx = ncx, fast = nfast;
     }
-    if (publish_seq) {
-        __syncthreads();  // every wave's descriptors are written ...
-        if (threadIdx.x == 0) {
-            FeatCtl &fc = *FB.fc;
-            __threadfence();  // ... and visible before this workgroup counts itself
-            if (atomicAdd(&fc.done_blocks, 1u) == gridDim.x * gridDim.y - 1) {
-                fc.done_blocks = 0;
-                publish_features(S, fc, publish_seq);
-            }
-        }
-    }
+    if (publish_seq) last_block_publishes(S, FB, publish_seq);
 }
 
 
@@ -2124,14 +2140,8 @@ constexpr int BI_PATCH_DW = BI_ROWS * BI_DW, BI_LOADS = (BI_PATCH_DW + 63) / 64;
 constexpr int BI_GROUPS = BI_ROWS * BI_G, BI_GLOOPS = (BI_GROUPS + 63) / 64;
 template <bool BV>
 __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t publish_seq) {
-    const int planes = gridDim.y * gridDim.z;
-    int lid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    int plane = lid / gridDim.x, bx = lid % gridDim.x;
-    if ((planes & 7) == 0) {
-        const int j = lid >> 3;
-        plane = (lid & 7) + 8 * (j / gridDim.x);
-        bx = j % gridDim.x;
-    }
+    int plane, bx;
+    const int planes = brief_plane_of_block(plane, bx);
     const Seq &S = sa.at(plane / gridDim.y);
     const int eye = plane % gridDim.y;
     const FrameBuf &FB = S.fb[par];
@@ -2165,20 +2175,10 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t
         ta[w] = (t[0] + BR_R) * (4 * BI_G) + t[1] + BR_R;
         tb[w] = (t[2] + BR_R) * (4 * BI_G) + t[3] + BR_R;
     }
-    auto centre = [&](int i, int &cy, int &cx) {
-        cy = (int)((double)F.by[i] + 0.5), cx = (int)((double)F.bx[i] + 0.5);
-    };
     // the patch's 64 columns must lie inside the row pitch and its rows inside the image
     auto inside = [&](int cy, int cx) { return cx - BI_R >= 0 && ((cx - BI_R) & ~3) + 64 <= pitch && cx + BI_R < W && cy - BI_R >= 0 && cy + BI_R < H; };
-    int stride = gridDim.x * wpb;
-    int i = bx * wpb + wave_id();
-    int i_end = n;
-    if ((planes & 7) != 0 && (gridDim.x & 7) == 0) {
-        const int eighth = (n + 7) >> 3, x = bx & 7;
-        stride = (gridDim.x >> 3) * wpb;
-        i = x * eighth + (bx >> 3) * wpb + wave_id();
-        i_end = min(n, (x + 1) * eighth);
-    }
+    int i, i_end;
+    const int stride = brief_key_points_of_wave(planes, bx, wpb, n, i, i_end);
     uint32_t v[BI_LOADS];
     int cy = 0, cx = 0;
     bool fast = false;
@@ -2196,7 +2196,7 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t
         return sum;
     };
     if (i < i_end) {
-        centre(i, cy, cx);
+        brief_centre(F, i, cy, cx);
         fast = inside(cy, cx);
         if (fast) fetch(cy, cx);
     }
@@ -2206,7 +2206,7 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t
         int ncy = 0, ncx = 0;
         bool nfast = false;
         if (inext < i_end) {
-            centre(inext, ncy, ncx);
+            brief_centre(F, inext, ncy, ncx);
             nfast = inside(ncy, ncx);
         }
         if (fast) {
@@ -2248,17 +2248,7 @@ __global__ __launch_bounds__(256) void k_brief_img(SeqArg<BV> sa, int par, seq_t
         if (lane < 4) F.desc[(size_t)i * 4 + lane] = (lane == 0) ? word[0] : (lane == 1) ? word[1] : (lane == 2) ? word[2] : word[3];
         cy = ncy, cx = ncx, fast = nfast;
     }
-    if (publish_seq) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            FeatCtl &fc = *FB.fc;
-            __threadfence();
-            if (atomicAdd(&fc.done_blocks, 1u) == gridDim.x * gridDim.y - 1) {
-                fc.done_blocks = 0;
-                publish_features(S, fc, publish_seq);
-            }
-        }
-    }
+    if (publish_seq) last_block_publishes(S, FB, publish_seq);
 }
 
 }  // namespace lvt

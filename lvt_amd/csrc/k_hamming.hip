@@ -62,14 +62,6 @@ __device__ __forceinline__ void push_bit(uint32_t &mask, float d2, float r2) {
     asm("v_cmp_gt_f32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(d2), "v"(r2) : "vcc");
 }
 
-// 256-bit Hamming distance as ONE chain of accumulating popcounts (v_bcnt_u32_b32 adds its third operand): 8 xor + 8 bcnt.  Left to itself the
-// compiler splits the sum of eight popcounts into four chains and adds them up again (8 + 8 + 3 instructions), and bcnt / add3 / min / lshl_or issue at
-// HALF the rate of xor / add / fma on this machine (4.2 against 2.3 cycles per wave64 instruction and SIMD: tools/lab/int_issue.hip)
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 // the running top-2 (k1 <= k2) takes a new key: k2' is the MEDIAN of (k1, k2, key) -- one v_med3_u32 where min(k2, max(k1, key)) is two half-rate instructions
 __device__ __forceinline__ void top2_insert(uint32_t &k1, uint32_t &k2, uint32_t key) {
     uint32_t m;

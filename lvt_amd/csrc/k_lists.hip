@@ -42,12 +42,6 @@ constexpr int LS_LDS_BYTES = LS_NMAX * 42 + LS_STARTS * 4 + LS_QCH * 64 + LS_WAV
 static_assert(KC + 64 <= LS_SEG, "the long-window path shares the wavefront's segment words");
 typedef unsigned int ls_u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t ls_bcnt(uint32_t x, uint32_t acc) {  // acc + popcount(x): one instruction
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-
 template <int MODE, bool BV>
 __global__ __launch_bounds__(LS_THREADS) void k_hamming_batched_lists(SeqArg<BV> sa, int par, seq_t seq) {
     const Seq &S = sa.get();
@@ -108,8 +102,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_hamming_batched_lists(SeqArg<BV>
     if (MODE == MODE_MAP && tid == 0) {  // the prediction, recomputed from the persistent state (k_early_map does the same)
         Pose predicted;
         double mmn[14];
-        motion_predict(ctl, ctl.last_pose, predicted, mmn);
-        world_to_camera(predicted, w2c);
+        predicted_w2c(ctl, w2c, &predicted, mmn);
     }
     for (int i = tid; i <= nbins; i += LS_THREADS) s_start[i] = 0;
     __syncthreads();
@@ -248,9 +241,9 @@ __global__ __launch_bounds__(LS_THREADS) void k_hamming_batched_lists(SeqArg<BV>
                     ok = (dx * dx + dy * dy) < r2;
                 }
                 ok = ok && in;
-                uint32_t d = ls_bcnt(d0.x ^ a0.x, 0u);
-                d = ls_bcnt(d0.y ^ a0.y, d), d = ls_bcnt(d0.z ^ a0.z, d), d = ls_bcnt(d0.w ^ a0.w, d);
-                d = ls_bcnt(d1.x ^ a1.x, d), d = ls_bcnt(d1.y ^ a1.y, d), d = ls_bcnt(d1.z ^ a1.z, d), d = ls_bcnt(d1.w ^ a1.w, d);
+                uint32_t d = bcnt_acc(d0.x ^ a0.x, 0u);
+                d = bcnt_acc(d0.y ^ a0.y, d), d = bcnt_acc(d0.z ^ a0.z, d), d = bcnt_acc(d0.w ^ a0.w, d);
+                d = bcnt_acc(d1.x ^ a1.x, d), d = bcnt_acc(d1.y ^ a1.y, d), d = bcnt_acc(d1.z ^ a1.z, d), d = bcnt_acc(d1.w ^ a1.w, d);
                 const uint64_t bal = __ballot(ok);
                 const int slot = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
                 if (ok && slot < KC + 64) s_seg[slot] = (d << 16) | id;
@@ -323,9 +316,9 @@ __global__ __launch_bounds__(LS_THREADS) void k_hamming_batched_lists(SeqArg<BV>
                         ok = (dx * dx + dy * dy) < r2;  // struct.cpp:95-99
                     }
                     ok = ok && in;
-                    uint32_t d = ls_bcnt(d0.x ^ a0.x, 0u);
-                    d = ls_bcnt(d0.y ^ a0.y, d), d = ls_bcnt(d0.z ^ a0.z, d), d = ls_bcnt(d0.w ^ a0.w, d);
-                    d = ls_bcnt(d1.x ^ a1.x, d), d = ls_bcnt(d1.y ^ a1.y, d), d = ls_bcnt(d1.z ^ a1.z, d), d = ls_bcnt(d1.w ^ a1.w, d);
+                    uint32_t d = bcnt_acc(d0.x ^ a0.x, 0u);
+                    d = bcnt_acc(d0.y ^ a0.y, d), d = bcnt_acc(d0.z ^ a0.z, d), d = bcnt_acc(d0.w ^ a0.w, d);
+                    d = bcnt_acc(d1.x ^ a1.x, d), d = bcnt_acc(d1.y ^ a1.y, d), d = bcnt_acc(d1.z ^ a1.z, d), d = bcnt_acc(d1.w ^ a1.w, d);
                     const uint32_t key = (d << 16) | id;
                     const uint32_t brow = (uint32_t)(__ballot(ok) >> (row * 16)) & 0xFFFFu;  // this row's candidates that passed
                     if (ok) {

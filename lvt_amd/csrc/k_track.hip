@@ -153,6 +153,23 @@ struct CandLds {
     uint32_t *tc;            // [NF_MAX] packed hash cell (cy << 16 | cx)
     const double *w2c;       // PROJECT: world -> camera of the predicted pose (LDS)
 };
+// a candidate kernel's own LDS (k_candidates, k_match_map, k_early_map): 50 KB, filled into `C`
+#define CAND_LDS_DECL                                       \
+    __shared__ uint32_t lbuf[4 * KC];                       \
+    __shared__ float s_tx[NF_MAX], s_ty[NF_MAX];            \
+    __shared__ uint32_t s_tc[NF_MAX];                       \
+    CandLds C;                                              \
+    C.lbuf = lbuf, C.tx = s_tx, C.ty = s_ty, C.tc = s_tc;
+// ... and the same record carved out of the (not yet used) list area of a resolver kernel: 16 waves x KC list words, then the three NF_MAX arrays
+__device__ __forceinline__ CandLds cand_lds_from_lists(uint32_t *r_lists) {
+    CandLds C;
+    C.lbuf = r_lists;
+    C.tx = reinterpret_cast<float *>(r_lists + 16 * KC);
+    C.ty = C.tx + NF_MAX;
+    C.tc = reinterpret_cast<uint32_t *>(C.ty + NF_MAX);
+    C.w2c = nullptr;
+    return C;
+}
 
 // wave `wave0 + k * wave_stride` handles query wave0 + k * wave_stride; all `nthreads` threads of the block stage the
 // train data.  MODE_ROW lists are built for EVERY left feature (they depend on the two feature sets only, so the
@@ -165,7 +182,7 @@ __device__ __forceinline__ void candidates_body(const Seq &S, int pass2, int par
     uint32_t *s_tc = C.tc;
     float *s_tx = C.tx, *s_ty = C.ty;
     const int lane = lane_id(), wv = wave_id();
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lt_mask = lanes_below(lane);
     const Feat &T = (MODE == MODE_ROW) ? S.fb[par].feat[1] : S.fb[par].feat[0];
     const int N = *T.n;
     int M;
@@ -347,11 +364,7 @@ __global__ __launch_bounds__(256) void k_candidates(SeqArg<BV> sa, int pass2, in
         if (S.prm.sensor != 1) return;
         if (need_seq && !seq_reached(S.fb[par].fc->feat_seq, need_seq)) return;
     }
-    __shared__ uint32_t lbuf[4 * KC];
-    __shared__ float s_tx[NF_MAX], s_ty[NF_MAX];
-    __shared__ uint32_t s_tc[NF_MAX];
-    CandLds C;
-    C.lbuf = lbuf, C.tx = s_tx, C.ty = s_ty, C.tc = s_tc;
+    CAND_LDS_DECL
     candidates_body<MODE>(S, pass2, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256);
 }
 
@@ -403,10 +416,7 @@ __global__ __launch_bounds__(256) void k_match_map(SeqArg<BV> sa, int par, seq_t
     if (threadIdx.x == 0) {
         Pose predicted;
         double mmn[14];
-        if (active && !first) {
-            motion_predict(ctl, ctl.last_pose, predicted, mmn);
-            world_to_camera(predicted, w2c);
-        }
+        if (active && !first) predicted_w2c(ctl, w2c, &predicted, mmn);
         if (blockIdx.x == 0) {
             frame_prologue(S, ctl, par, predicted, mmn, active, first, skipped);
             if (active && !first) ctl.counts[C_MAP_SIZE_AT_MATCH] = *S.map_n;
@@ -414,11 +424,8 @@ __global__ __launch_bounds__(256) void k_match_map(SeqArg<BV> sa, int par, seq_t
     }
     if (!active || first) return;
     // no barrier here: the one after the train staging inside candidates_body also publishes w2c
-    __shared__ uint32_t lbuf[4 * KC];
-    __shared__ float s_tx[NF_MAX], s_ty[NF_MAX];
-    __shared__ uint32_t s_tc[NF_MAX];
-    CandLds C;
-    C.lbuf = lbuf, C.tx = s_tx, C.ty = s_ty, C.tc = s_tc, C.w2c = w2c;
+    CAND_LDS_DECL
+    C.w2c = w2c;
     // the points [0, early_done) were projected and listed by k_early_map while the previous frame finished
     candidates_body<MODE_MAP, true>(S, 0, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256, early_points_ran(&ctl, seq), -1);
 }
@@ -496,14 +503,10 @@ __global__ __launch_bounds__(256) void k_early_map(SeqArg<BV> sa, int par, seq_t
     if (threadIdx.x == 0) {
         Pose predicted;
         double mmn[14];
-        motion_predict(ctl, ctl.last_pose, predicted, mmn);
-        world_to_camera(predicted, w2c);
+        predicted_w2c(ctl, w2c, &predicted, mmn);
     }
-    __shared__ uint32_t lbuf[4 * KC];
-    __shared__ float s_tx[NF_MAX], s_ty[NF_MAX];
-    __shared__ uint32_t s_tc[NF_MAX];
-    CandLds C;
-    C.lbuf = lbuf, C.tx = s_tx, C.ty = s_ty, C.tc = s_tc, C.w2c = w2c;
+    CAND_LDS_DECL
+    C.w2c = w2c;
     candidates_body<MODE_MAP, true>(S, 0, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256, 0, n_early);
 }
 
@@ -833,6 +836,18 @@ __device__ __forceinline__ int resolve_super(int b0, int M, NFn nfn, const uint3
     ResolveLds L;                                           \
     L.flag = r_flag, L.tab0 = r_tab, L.tab1 = r_tab + NF_MAX, L.lists = r_lists, L.scan = r_scan, L.misc = r_misc;
 
+// The middle step of a chunked compaction.  Its users walk their points in coalesced chunks of blockDim.x (point k * blockDim.x + t belongs to thread t) and
+// leave one ballot count per (chunk, wavefront) in cnts[k * NWV + wv] -- storage order.  Here ONE block scan turns the n_entries <= blockDim.x counts into
+// exclusive prefixes (*total: their sum); a point's slot is then cnts[k * NWV + wv] + popcount(ballot & lanes_below(lane)).  Barriers on both sides.
+__device__ __forceinline__ void scan_chunk_counts(uint32_t *cnts, int n_entries, int *scan, int *total) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    const int v = (tid < n_entries) ? (int)cnts[tid] : 0;
+    const int ex = block_excl_scan(v, scan, total);
+    if (tid < n_entries) cnts[tid] = (uint32_t)ex;
+    __syncthreads();
+}
+
 template <int MODE>
 // phase 0: all queries; phase 1 (map mode, "early"): queries [0, q_split) only, no per-frame bookkeeping; phase 2 ("late"): queries
 // [q_split, M), continuing from the marks and the match count phase 1 left behind
@@ -882,7 +897,7 @@ __device__ __forceinline__ void resolve_body(const Seq &S, Ctl &ctl, int pass2, 
         const int lane = tid & 63, wv = tid >> 6;
         const int nch = (M - b0 + RES_THREADS - 1) / RES_THREADS;  // <= 32
         uint32_t *cnts = L.lists;  // (the list area is free until the first super-chunk packs)
-        const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+        const uint64_t lt = lanes_below(lane);
         uint32_t hasbits = 0;
         for (int k = 0; k < nch; k++) {
             const int i = b0 + k * RES_THREADS + tid;
@@ -891,14 +906,8 @@ __device__ __forceinline__ void resolve_body(const Seq &S, Ctl &ctl, int pass2, 
             const uint64_t bm = __ballot(has);
             if (lane == 0) cnts[k * NWV + wv] = (uint32_t)__popcll(bm);
         }
-        __syncthreads();
         int total;
-        {
-            const int v = (tid < nch * NWV) ? (int)cnts[tid] : 0;
-            const int ex = block_excl_scan(v, L.scan, &total);
-            if (tid < nch * NWV) cnts[tid] = (uint32_t)ex;
-        }
-        __syncthreads();
+        scan_chunk_counts(cnts, nch * NWV, L.scan, &total);
         for (int k = 0; k < nch; k++) {
             const int i = b0 + k * RES_THREADS + tid;
             const bool has = (hasbits >> k) & 1u;
@@ -1015,6 +1024,58 @@ __device__ __forceinline__ void resolve_body(const Seq &S, Ctl &ctl, int pass2, 
 // bookkeeping of find_matches + LOST decision + clean_untracked_points : lvt_local_map.cpp:201-224, lvt_system.cpp:266-274, lvt_local_map.cpp:393-413
 // (the clean-up does not depend on the pose, so it runs here, ahead of the pose refinement; the reference runs it right after)
 // =================================================================================================
+// ---- what the two bookkeeping bodies below share: everything but how a point's fields are loaded and how the two compactions are scanned ----
+// the LOST decision (lvt_system.cpp:267-272, :199-204), recorded by thread 0.  Returns true when the frame is LOST (block-uniform).
+__device__ __forceinline__ bool decide_lost(const Seq &S, Ctl &ctl, int n_match) {
+    const bool lost = n_match < S.prm.min_matches;
+    if (threadIdx.x == 0) {
+        ctl.n_matches = n_match;
+        ctl.counts[C_N_MATCHES] = n_match;
+        if (lost) {
+            ctl.lost_now = 1;
+            ctl.state = 3;
+            pose_to_Rt(ctl.last_pose, ctl.out_R, ctl.out_t);
+            ctl.out_status = 3;
+        } else {  // push_back / pop_front
+            ctl.last_matches[0] = ctl.last_matches[1];
+            ctl.last_matches[1] = ctl.last_matches[2];
+            ctl.last_matches[2] = n_match;
+        }
+    }
+    return lost;
+}
+// matched point -> edge `off` of the PnP input (the pose refinement takes NF_MAX edges at most)
+__device__ __forceinline__ void put_pnp_edge(const Seq &S, int off, double p0, double p1, double p2, float ox, float oy, int m) {
+    if (off >= NF_MAX) return;
+    S.pnp_X[3 * off] = p0;
+    S.pnp_X[3 * off + 1] = p1;
+    S.pnp_X[3 * off + 2] = p2;
+    S.pnp_obs[2 * off] = ox;
+    S.pnp_obs[2 * off + 1] = oy;
+    S.pnp_feat[off] = m;
+    S.pnp_level[off] = 0;
+}
+// clean_untracked_points (lvt_local_map.cpp:393-413): a surviving point goes to slot `off` of the other map buffer (stable compaction)
+__device__ __forceinline__ void put_survivor(const MapSoA &B, int off, double p0, double p1, double p2, const uint64_t dsc[4], int cnt, int ag, int m) {
+    B.pos[3 * off] = p0, B.pos[3 * off + 1] = p1, B.pos[3 * off + 2] = p2;
+#pragma unroll
+    for (int k = 0; k < 4; k++) B.desc[(size_t)off * 4 + k] = dsc[k];
+    B.counter[off] = cnt;
+    B.age[off] = ag;
+    B.match_idx[off] = m;
+}
+// a LOST frame: the map stays where it is, with the bookkeeping applied
+__device__ __forceinline__ void keep_lost_point(const MapSoA &A, int i, int m, int cnt, int ag) {
+    A.match_idx[i] = m, A.counter[i] = cnt, A.age[i] = ag;
+}
+// the survivors are in the other buffer: it is the map now (thread 0; the callers' barrier, if they need one, stands in front)
+__device__ __forceinline__ void finish_cull(const Seq &S, Ctl &ctl, int cur, int M, int n_keep) {
+    if (threadIdx.x != 0) return;
+    ctl.counts[C_N_CULLED] = M - n_keep;
+    *S.map_cur = cur ^ 1;
+    *S.map_n = n_keep;
+}
+
 // bookkeeping + LOST decision + clean_untracked_points in ONE pass for maps of up to RES_THREADS points (the map of a
 // KITTI sequence holds ~800): every field of a point is loaded once (independent loads: one memory round trip), both
 // compactions (PnP input = matched points, surviving map = counter < untracked_th) come from one packed scan, and the
@@ -1046,49 +1107,15 @@ __device__ __forceinline__ bool bookkeep_cull_small(const Seq &S, Ctl &ctl, int 
     const int ex = block_excl_scan((m >= 0 ? 1 : 0) | (keep ? 0x10000 : 0), scan, &total);
     const int n_match = total & 0xFFFF, n_keep = total >> 16;
     const int offm = ex & 0xFFFF, offk = ex >> 16;
-    if (m >= 0 && offm < NF_MAX) {
-        S.pnp_X[3 * offm] = pos[0];
-        S.pnp_X[3 * offm + 1] = pos[1];
-        S.pnp_X[3 * offm + 2] = pos[2];
-        S.pnp_obs[2 * offm] = ox;
-        S.pnp_obs[2 * offm + 1] = oy;
-        S.pnp_feat[offm] = m;
-        S.pnp_level[offm] = 0;
-    }
-    const bool lost = n_match < S.prm.min_matches;  // lvt_system.cpp:267-272, :199-204
-    if (tid == 0) {
-        ctl.n_matches = n_match;
-        ctl.counts[C_N_MATCHES] = n_match;
-        if (lost) {
-            ctl.lost_now = 1;
-            ctl.state = 3;
-            pose_to_Rt(ctl.last_pose, ctl.out_R, ctl.out_t);
-            ctl.out_status = 3;
-        } else {  // push_back / pop_front
-            ctl.last_matches[0] = ctl.last_matches[1];
-            ctl.last_matches[1] = ctl.last_matches[2];
-            ctl.last_matches[2] = n_match;
-        }
-    }
-    if (lost) {  // the map stays where it is, with the bookkeeping applied
-        if (i < M) A.match_idx[i] = m, A.counter[i] = cnt, A.age[i] = ag;
+    if (m >= 0) put_pnp_edge(S, offm, pos[0], pos[1], pos[2], ox, oy, m);
+    if (decide_lost(S, ctl, n_match)) {
+        if (i < M) keep_lost_point(A, i, m, cnt, ag);
         return true;
     }
-    // clean_untracked_points (lvt_local_map.cpp:393-413): stable compaction into the other buffer
-    if (keep) {
-        B.pos[3 * offk] = pos[0], B.pos[3 * offk + 1] = pos[1], B.pos[3 * offk + 2] = pos[2];
-#pragma unroll
-        for (int k = 0; k < 4; k++) B.desc[(size_t)offk * 4 + k] = dsc[k];
-        B.counter[offk] = cnt;
-        B.age[offk] = ag;
-        B.match_idx[offk] = m;
-    } else if (i < M && m >= 0)
+    if (keep) put_survivor(B, offk, pos[0], pos[1], pos[2], dsc, cnt, ag, m);
+    else if (i < M && m >= 0)
         S.fb[par].feat[0].flag[m] = 0;  // :402-405
-    if (tid == 0) {
-        ctl.counts[C_N_CULLED] = M - n_keep;
-        *S.map_cur = cur ^ 1;
-        *S.map_n = n_keep;
-    }
+    finish_cull(S, ctl, cur, M, n_keep);
     return false;
 }
 
@@ -1105,7 +1132,7 @@ __device__ __forceinline__ bool bookkeep_cull_large(const Seq &S, Ctl &ctl, int 
     const Feat &F = S.fb[par].feat[0];
     const int th = S.prm.untracked_th;
     const int c = (M + RES_THREADS - 1) / RES_THREADS;  // <= MAP_MAX / 1024 = 32 chunks
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lt = lanes_below(lane);
     uint32_t mbits = 0, kbits = 0;  // this thread's point of chunk k: matched / survives
     for (int k = 0; k < c; k++) {
         const int i = k * RES_THREADS + tid;
@@ -1114,75 +1141,42 @@ __device__ __forceinline__ bool bookkeep_cull_large(const Seq &S, Ctl &ctl, int 
         const bool mt = m >= 0, kp = (i < M) && ((cnt + (m == -1 ? 1 : 0)) < th);
         mbits |= (mt ? 1u : 0u) << k, kbits |= (kp ? 1u : 0u) << k;
         const uint64_t bm = __ballot(mt), bk = __ballot(kp);
-        if (lane == 0) cnts[k * NWV + wv] = (uint32_t)__popcll(bm) | ((uint32_t)__popcll(bk) << 16);
+        if (lane == 0) cnts[k * NWV + wv] = (uint32_t)__popcll(bm) | ((uint32_t)__popcll(bk) << 16);  // (two counts in one word: one scan places both)
     }
-    __syncthreads();
-    uint32_t base = 0;
     int total;
-    {   // exclusive scan over the (chunk, wavefront) counts in storage order: c * 16 <= 512 entries, one per thread
-        const int v = (tid < c * NWV) ? (int)cnts[tid] : 0;
-        const int ex = block_excl_scan(v, scan, &total);
-        if (tid < c * NWV) cnts[tid] = (uint32_t)ex;
-    }
-    __syncthreads();
+    scan_chunk_counts(cnts, c * NWV, scan, &total);  // c * 16 <= 512 entries
     const int n_match = (int)((unsigned)total & 0xFFFFu), n_keep = (int)((unsigned)total >> 16);  // (MAP_MAX = 32768 survivors reach bit 31)
-    const bool lost = n_match < S.prm.min_matches;  // lvt_system.cpp:267-272, :199-204
-    if (tid == 0) {
-        ctl.n_matches = n_match;
-        ctl.counts[C_N_MATCHES] = n_match;
-        if (lost) {
-            ctl.lost_now = 1;
-            ctl.state = 3;
-            pose_to_Rt(ctl.last_pose, ctl.out_R, ctl.out_t);
-            ctl.out_status = 3;
-        } else {  // push_back / pop_front
-            ctl.last_matches[0] = ctl.last_matches[1];
-            ctl.last_matches[1] = ctl.last_matches[2];
-            ctl.last_matches[2] = n_match;
-        }
-    }
+    const bool lost = decide_lost(S, ctl, n_match);
     for (int k = 0; k < c; k++) {
         const int i = k * RES_THREADS + tid;
         const bool mt = (mbits >> k) & 1u, kp = (kbits >> k) & 1u;
         const uint64_t bm = __ballot(mt), bk = __ballot(kp);
-        base = cnts[k * NWV + wv];
+        const uint32_t base = cnts[k * NWV + wv];
         const int offm = (int)(base & 0xFFFFu) + __popcll(bm & lt), offk = (int)(base >> 16) + __popcll(bk & lt);
         if (i >= M) continue;
         int m = S.match[i], cnt = A.counter[i], ag = A.age[i];
         if (m == -1) cnt += 1;  // lvt_local_map.cpp:201-224
         else if (m >= 0) ag += 1;
-        if (lost) {  // the map stays where it is, with the bookkeeping applied
-            A.match_idx[i] = m, A.counter[i] = cnt, A.age[i] = ag;
+        if (lost) {  // in place: no compaction, and no barrier behind the loop
+            keep_lost_point(A, i, m, cnt, ag);
+            // (a LOST frame records its matches too, as the small body does: nobody solves for a pose, but lvt_amd_get_matches reads the frame's matches from here)
+            if (mt) put_pnp_edge(S, offm, A.pos[3 * i], A.pos[3 * i + 1], A.pos[3 * i + 2], F.x[m], F.y[m], m);
             continue;
         }
         if (!mt && !kp) continue;
         const double p0 = A.pos[3 * i], p1 = A.pos[3 * i + 1], p2 = A.pos[3 * i + 2];
-        if (mt && offm < NF_MAX) {
-            S.pnp_X[3 * offm] = p0;
-            S.pnp_X[3 * offm + 1] = p1;
-            S.pnp_X[3 * offm + 2] = p2;
-            S.pnp_obs[2 * offm] = F.x[m];
-            S.pnp_obs[2 * offm + 1] = F.y[m];
-            S.pnp_feat[offm] = m;
-            S.pnp_level[offm] = 0;
-        }
-        if (kp) {  // clean_untracked_points (lvt_local_map.cpp:393-413): stable compaction into the other buffer
-            B.pos[3 * offk] = p0, B.pos[3 * offk + 1] = p1, B.pos[3 * offk + 2] = p2;
+        if (mt) put_pnp_edge(S, offm, p0, p1, p2, F.x[m], F.y[m], m);
+        if (kp) {
+            uint64_t dsc[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) B.desc[(size_t)offk * 4 + q] = A.desc[(size_t)i * 4 + q];
-            B.counter[offk] = cnt;
-            B.age[offk] = ag;
-            B.match_idx[offk] = m;
+            for (int q = 0; q < 4; q++) dsc[q] = A.desc[(size_t)i * 4 + q];
+            put_survivor(B, offk, p0, p1, p2, dsc, cnt, ag, m);
         } else if (mt)
             S.fb[par].feat[0].flag[m] = 0;  // :402-405
     }
     if (lost) return true;
     __syncthreads();
-    if (tid == 0) {
-        ctl.counts[C_N_CULLED] = M - n_keep;
-        *S.map_cur = cur ^ 1;
-        *S.map_n = n_keep;
-    }
+    finish_cull(S, ctl, cur, M, n_keep);
     return false;
 }
 
@@ -1211,11 +1205,7 @@ __global__ __launch_bounds__(RES_THREADS) void k_track_mid(SeqArg<BV> sa, int pa
     __syncthreads();
     if (L.misc[2]) {  // rare (< 50 matches): doubled-radius candidate lists are built by this one block
         {
-            CandLds C;  // carve the (not yet used) list area of the resolver
-            C.lbuf = r_lists;                                      // 16 waves x KC words
-            C.tx = reinterpret_cast<float *>(r_lists + 16 * KC);   // NF_MAX
-            C.ty = C.tx + NF_MAX;
-            C.tc = reinterpret_cast<uint32_t *>(C.ty + NF_MAX);
+            CandLds C = cand_lds_from_lists(r_lists);
             candidates_body<MODE_MAP>(S, 1, par, C, wave_id(), RES_THREADS / 64, RES_THREADS);
         }
         __syncthreads();
@@ -2146,11 +2136,7 @@ __global__ __launch_bounds__(1024) void k_triangulate(SeqArg<BV> sa, int par, se
             }
             __syncthreads();
             if (s_row_fallback) {
-                CandLds C;  // carve the (not yet used) list area of the resolver, as k_track_mid's second pass does
-                C.lbuf = r_lists;
-                C.tx = reinterpret_cast<float *>(r_lists + 16 * KC);
-                C.ty = C.tx + NF_MAX;
-                C.tc = reinterpret_cast<uint32_t *>(C.ty + NF_MAX);
+                CandLds C = cand_lds_from_lists(r_lists);
                 candidates_body<MODE_ROW>(S, 0, par, C, wave_id(), RES_THREADS / 64, RES_THREADS);
                 __syncthreads();
             }

@@ -134,4 +134,11 @@ __device__ inline void motion_predict(const Ctl &c, const Pose &cur, Pose &out, 
     q_normalize(out.q);
 }
 
+// The pose a frame's matching starts from and its world -> camera matrix, from the PERSISTENT part of Ctl (last pose, motion-model state) alone.  k_match_map,
+// k_early_map and k_hamming_batched_lists<MODE_MAP> each project map points of the same frame: they must see the same pose, so all three call this.
+__device__ __forceinline__ void predicted_w2c(const Ctl &ctl, double w2c[12], Pose *predicted, double mmn[14]) {
+    motion_predict(ctl, ctl.last_pose, *predicted, mmn);
+    world_to_camera(*predicted, w2c);
+}
+
 }  // namespace lvt

@@ -1251,3 +1251,96 @@ def hamming_count_check(csr):
             if b == 0:
                 stats.append((k, layout, max(want), n_exact))
     return stats
+
+
+# ---- BRIEF at every seam of `inside`, both kernels (test_gpu_brief_seams.py) ---------------------------------------------------------------------------
+# brief_border_keep keeps a corner whose ROUNDED-TO-EVEN position lies in [28, W - 28) x [28, H - 28); BRIEF samples around (int)(x + 0.5), (int)(y + 0.5).
+# The two differ at .5 ties, so the centre (cx, cy) of a kept corner reaches [28, W - 28] x [28, H - 28].  k_brief's 49 x 49 window (radius 24) is inside the
+# image for all of them; k_brief_img's 57 x 57 patch (radius 28, fetched as 64 columns from the word boundary at or left of cx - 28) is not:
+#   bottom    cy = H - 28 (y = H - 28.5 with H odd: H - 29 is even, the tie rounds down and the corner is kept): cy + 28 < H fails
+#   overrun   ((cx - 28) & ~3) + 64 <= pitch fails for cx > W - 33 where the row pitch equals W, i.e. W a multiple of 64: the four last kept columns
+# and such a corner takes the clipped element-wise path.  128 x 97 is the smallest image with W a multiple of 64 that holds the column list W - 40 .. W - 28.
+BRIEF_SEAM_W, BRIEF_SEAM_H, BRIEF_SEAM_DISP, BRIEF_SEAM_FRAMES = 128, 97, 4, 3
+BRIEF_BORDER = 28
+
+
+def brief_seam_corners(W=BRIEF_SEAM_W, H=BRIEF_SEAM_H):
+    """the left eye's corner list (float64, (x, y)): every integer column W - 40 .. W - 28 at two rows; .5 ties and their neighbours on all four borders;
+    interior corners at eight consecutive columns (both parities of cx - 24, all four values of (cx - 28) & 3), whole and fractional"""
+    c = [(float(x), y) for y in (33.0, 60.0) for x in range(W - 40, W - 27)]
+    c += [(x, 45.0 + k) for k, x in enumerate((26.5, 27.5, 28.0, 28.25, 28.5, W - 29.5, W - 29.25, W - 29.0, W - 28.5, W - 27.5))]
+    c += [(44.0 + 3 * k, y) for k, y in enumerate((26.5, 27.5, 28.0, 28.25, 28.5, H - 29.5, H - 29.25, H - 29.0, H - 27.5))]
+    c += [(x, H - 28.5) for x in (36.0, 52.5, 71.0, W - 30.0)]                 # cy = H - 28: below every kept integer row
+    c += [(40.0 + k, 50.0) for k in range(8)] + [(40.3 + k, 39.6) for k in range(8)]
+    return np.array(c, dtype=np.float64)
+
+
+def brief_seam_expected(corners, W=BRIEF_SEAM_W, H=BRIEF_SEAM_H):
+    """(kept mask, cx, cy) of a corner list by the two rules restated in numpy: float32 coordinates, rint (half to even) for the filter, (int)(v + 0.5) in
+    double for the centre"""
+    xy = corners.astype(np.float32)
+    r = np.rint(xy).astype(np.int64)
+    keep = (r[:, 0] >= BRIEF_BORDER) & (r[:, 0] < W - BRIEF_BORDER) & (r[:, 1] >= BRIEF_BORDER) & (r[:, 1] < H - BRIEF_BORDER)
+    c = np.floor(xy.astype(np.float64) + 0.5).astype(np.int64)
+    return keep, c[:, 0], c[:, 1]
+
+
+def brief_seam_tally(corners, W=BRIEF_SEAM_W, H=BRIEF_SEAM_H):
+    """kept corners per seam: on the last centre that is inside (left, top, right, bottom) and on the two conditions that fail for k_brief_img"""
+    keep, cx, cy = brief_seam_expected(corners, W, H)
+    cx, cy = cx[keep], cy[keep]
+    pitch = (W + 63) // 64 * 64
+    overrun = ((cx - 28) & ~3) + 64 > pitch
+    return dict(kept=int(keep.sum()), left=int((cx == 28).sum()), top=int((cy == 28).sum()), right=int((cx == W - 29).sum()),
+                bottom=int((cy == H - 29).sum()), below=int((cy == H - 28).sum()), overrun=int(overrun.sum()),
+                slow_img=int((overrun | (cy + 28 >= H) | (cx + 28 >= W)).sum()),
+                slow_plane=int(((cx - 24 < 0) | (cx + 24 >= W) | (cy - 24 < 0) | (cy + 24 >= H)).sum()),
+                parity=sorted(set(((cx - 24) & 1).tolist())), quarter=sorted(set(((cx - 28) & 3)[~overrun].tolist())))
+
+
+def brief_seam_case():
+    """(params, [(L, R, corners_left, corners_right)]): one noise pair (the right eye is the left one moved BRIEF_SEAM_DISP px), the seam list in the left
+    eye and its partners in the right one, the same frame BRIEF_SEAM_FRAMES times: a static camera that keeps tracking on its own map"""
+    W, H = BRIEF_SEAM_W, BRIEF_SEAM_H
+    prm = lvt_amd.kitti_params(width=W, height=H)
+    L = np.random.default_rng(40).integers(0, 256, (H, W), dtype=np.uint8)
+    R = np.ascontiguousarray(np.roll(L, -BRIEF_SEAM_DISP, axis=1))
+    cl = brief_seam_corners(W, H)
+    cr = cl - [[float(BRIEF_SEAM_DISP), 0.0]]
+    return prm, [(L, R, cl, cr)] * BRIEF_SEAM_FRAMES
+
+
+# ---- bookkeeping across the 1024-point seam, and LOST on a large map (test_gpu_map_capacity.py) -----------------------------------------------------
+# k_track_mid sends a map of up to RES_THREADS = 1024 points through bookkeep_cull_small and a larger one through bookkeep_cull_large.  The recipes above
+# run the large body at 10 k points and more, the parity sequences the small one at ~800.  Two more, of the same construction (a fixed strip of MAPCAP_KEEP
+# corners that every frame matches, fresh corners per texture epoch that triangulate once and are never seen again):
+#   seam   fresh corners per frame chosen so that the map at match time climbs through (896, 1024] into (1024, 1152], is culled back below 1024 and climbs again
+#   lost   a map of more than 1024 points, then a frame without the fixed strip's texture: fewer than min_num_matches matches -> LOST.  The large body applies
+#          its bookkeeping IN PLACE then (no compaction, the map buffer is not swapped): counters and ages of all points are what map() shows afterwards
+# name: (overrides, fresh corners per frame; None = the LOST frame)
+MAPSEAM_RECIPES = {
+    "seam": ({"staged_threshold": 0, "untracked_threshold": 2}, (640, 130, 130, 130, 700, 130, 130)),
+    "lost": ({"staged_threshold": 0, "untracked_threshold": 1000, "min_num_matches_for_tracking": 100}, (640, 300, 300, None, 300)),
+}
+
+
+def mapseam_case(name):
+    """(params, [(L, R, corners_left, corners_right)]): mapcap_frame's construction with the recipe's number of fresh corners per frame.  The LOST frame is a
+    fresh noise pair (nothing of the fixed strip) with forty corners"""
+    overrides, fresh = MAPSEAM_RECIPES[name]
+    prm = lvt_amd.kitti_params(width=MAPCAP_W, height=MAPCAP_H)
+    prm.triangulation_policy = 2
+    for k, v in overrides.items():
+        setattr(prm, k, type(getattr(prm, k))(v))
+    fixed, keep = _mapcap_fixed()
+    frames = []
+    for i, n in enumerate(fresh):
+        rng = np.random.default_rng(300 + i)
+        L = rng.integers(0, 256, (MAPCAP_H, MAPCAP_W), dtype=np.uint8)
+        if n is not None:
+            L[:, :300] = fixed[:, :300]
+        R = np.ascontiguousarray(np.roll(L, -MAPCAP_DISP, axis=1))
+        pts = np.column_stack([rng.integers(340, MAPCAP_W - 40, n or 40), rng.integers(40, MAPCAP_H - 40, n or 40)])
+        cl = np.unique(np.vstack([keep, pts]) if n is not None else pts, axis=0).astype(np.float64)
+        frames.append((L, R, cl, cl - [[float(MAPCAP_DISP), 0.0]]))
+    return prm, frames

@@ -232,6 +232,103 @@ def test_oracle_capacity_option_cuts_all_three_append_sites(oracle_lib):
     assert ref.counts()["map_size"] > 10000
 
 
+# ---- bookkeeping across the 1024-point seam and LOST on a large map (test_gpu_map_capacity.py) ---------------------------------------------------------
+from case_tables import MAPSEAM_RECIPES, RES_THREADS as BOOKKEEP_SMALL_MAX, mapseam_case     # noqa: E402
+
+
+def _mapseam_rows(oracle_lib, name):
+    prm, frames = mapseam_case(name)
+    orc = oracle_lib.Oracle(prm, 1)
+    rows = []
+    for f in frames:
+        orc.track_with_external_corners(*f)
+        rows.append(dict(orc.counts(), status=orc.status))
+    return prm, rows, orc
+
+
+def test_mapseam_seam_matches_on_maps_either_side_of_1024_points(oracle_lib):
+    """`seam`: the map at match time is 938, 1 043, 554, 533, 1 115, 1 102 points: from below k_track_mid's 1024-point threshold to above it, back (a cull
+    of 591 points, taken by the large body, leaves a map for the small one) and above again; every frame TRACKING"""
+    assert BOOKKEEP_SMALL_MAX == 1024
+    prm, rows, _ = _mapseam_rows(oracle_lib, "seam")
+    assert [r["status"] for r in rows] == [2] * len(rows) == [2] * len(MAPSEAM_RECIPES["seam"][1])
+    at_match = [r["map_size_at_match"] for r in rows]
+    assert at_match == [0, 938, 1043, 554, 533, 1115, 1102], at_match
+    assert any(896 < m <= 1024 for m in at_match) and any(1024 < m <= 1152 for m in at_match)
+    side = [m > 1024 for m in at_match[1:]]
+    assert side == [False, True, False, False, True, True]                           # below, above, back, above
+    assert all(r["n_matches"] >= 300 for r in rows[1:]) and all(r["overflow"] == 0 for r in rows)
+    # both bodies compact: a cull on a map of either side, survivors and culled points in the hundreds
+    assert [(r["map_size_at_match"] > 1024, r["n_culled"] > 90) for r in rows[2:]] == [(True, True), (False, True), (False, True), (True, True), (True, True)]
+
+
+def test_mapseam_lost_goes_lost_on_a_map_of_more_than_1024_points(oracle_lib):
+    """`lost`: three frames build a map of 1 420 points, the fourth shows nothing of the fixed strip: 16 matches after the doubled-radius pass, fewer than
+    the 100 the recipe asks for -> LOST, with the bookkeeping applied where the points lie: nothing moves, hundreds of counters step; then the latch"""
+    prm, frames = mapseam_case("lost")
+    assert prm.min_num_matches_for_tracking == 100
+    orc = oracle_lib.Oracle(prm, 1)
+    rows, maps = [], []
+    for f in frames:
+        orc.track_with_external_corners(*f)
+        rows.append(dict(orc.counts(), status=orc.status))
+        maps.append(orc.map())
+    assert [r["status"] for r in rows] == [2, 2, 2, 3, 3]
+    lost = rows[3]
+    assert lost["map_size_at_match"] == 1420 > BOOKKEEP_SMALL_MAX and lost["second_pass"] == 1 and 0 < lost["n_matches"] == 16 < prm.min_num_matches_for_tracking
+    assert lost["map_size"] == 1420 and lost["n_culled"] == 0 and lost["n_triangulated"] == 0
+    before, after = maps[2], maps[3]
+    assert np.array_equal(before[0], after[0]) and np.array_equal(before[3], after[3])           # positions and descriptors stay where they are
+    assert (after[1] - before[1]).min() >= 0 and int((after[1] != before[1]).sum()) > 100        # counters of the visible, unmatched points
+    assert int((after[2] - before[2]).sum()) == lost["n_matches"]                                # ages of the matched ones
+    assert all(np.array_equal(a, b) for a, b in zip(maps[3], maps[4]))                           # LOST is sticky: nothing is computed
+
+
+# ---- BRIEF at every seam of `inside` (test_gpu_brief_seams.py) -----------------------------------------------------------------------------------------
+from case_tables import (BRIEF_BORDER, BRIEF_SEAM_DISP, BRIEF_SEAM_FRAMES, BRIEF_SEAM_H, BRIEF_SEAM_W, brief_seam_case, brief_seam_corners,      # noqa: E402
+                         brief_seam_expected, brief_seam_tally)
+
+
+def test_brief_seam_list_lands_on_every_seam(oracle_lib):
+    """the corner list with the oracle alone: which corners brief_border_keep drops, where the others' centres lie, and that the oracle tracks the three frames"""
+    W, H = BRIEF_SEAM_W, BRIEF_SEAM_H
+    assert W % 64 == 0 and H % 2 == 1 and W - 40 >= BRIEF_BORDER and (W - 64) - 40 < BRIEF_BORDER         # the smallest multiple of 64 that holds the column list
+    cl = brief_seam_corners()
+    assert len(cl) == 65 and len(np.unique(cl, axis=0)) == 65
+    for y in (33.0, 60.0):                                                                                # every integer column W - 40 .. W - 28 at two rows
+        assert sorted(cl[cl[:, 1] == y][:, 0].tolist()) == [float(x) for x in range(W - 40, W - 27)]
+    ties = {(x, y) for x, y in cl.tolist() if x % 1 == 0.5 or y % 1 == 0.5}
+    assert {x for x, y in ties} >= {26.5, 27.5, 28.5, W - 29.5, W - 28.5, W - 27.5} and {y for x, y in ties} >= {26.5, 27.5, 28.5, H - 29.5, H - 28.5, H - 27.5}
+    keep, cx, cy = brief_seam_expected(cl)
+    # dropped by design: column W - 28 twice; 26.5 -> 26, W - 28.5 -> W - 28, W - 27.5 -> W - 28 (W even); 26.5 -> 26, H - 27.5 -> H - 28 (H odd).  Kept ties:
+    # 27.5 -> 28 and 28.5 -> 28 (centres 28 and 29), W - 29.5 -> W - 30 (centre W - 29), H - 29.5 -> H - 30 (centre H - 29), H - 28.5 -> H - 29 (centre H - 28)
+    dropped = {tuple(c) for c in cl[~keep].tolist()}
+    assert dropped == {(W - 28.0, 33.0), (W - 28.0, 60.0), (26.5, 45.0), (W - 28.5, 53.0), (W - 27.5, 54.0), (44.0, 26.5), (68.0, H - 27.5)}, dropped
+    t = brief_seam_tally(cl)
+    assert t == dict(kept=58, left=3, top=3, right=5, bottom=3, below=4, overrun=12, slow_img=15, slow_plane=0, parity=[0, 1], quarter=[0, 1, 2, 3]), t
+    assert min(t[k] for k in ("left", "top", "right", "bottom", "below", "overrun")) >= 3
+    tr = brief_seam_tally(cl - [[float(BRIEF_SEAM_DISP), 0.0]])
+    assert (tr["kept"], tr["below"], tr["overrun"], tr["slow_img"], tr["slow_plane"]) == (58, 4, 4, 8, 0), tr
+    # the oracle keeps exactly those corners, in list order, and tracks the static scene on the map of its first frame
+    prm, frames = brief_seam_case()
+    assert len(frames) == BRIEF_SEAM_FRAMES == 3 and (prm.img_width, prm.img_height) == (W, H)
+    orc = oracle_lib.Oracle(prm, 1)
+    descs = []
+    for i, f in enumerate(frames):
+        orc.track_with_external_corners(*f)
+        c = orc.counts()
+        xy, _, d = orc.features(0)
+        assert np.array_equal(xy, cl.astype(np.float32)[keep]) and c["n_left"] == c["n_right"] == t["kept"] and orc.status == 2, (i, c)
+        assert i == 0 or c["n_matches"] >= 50, (i, c)
+        descs.append(d)
+    assert len(np.unique(descs[0], axis=0)) >= t["kept"] - 8          # (corners that share a centre share a descriptor)
+    # a corner on the clipped path is not a degenerate one: its descriptor differs from that of the same centre one row up
+    kept_c = cl[keep]
+    below = np.flatnonzero(cy[keep] == H - 28)
+    _, up = oracle_lib.brief(frames[0][0], (kept_c[below] - [[0.0, 1.0]]).astype(np.float32))
+    assert len(up) == len(below) == 4 and all(not np.array_equal(a, b) for a, b in zip(up, descs[0][below]))
+
+
 # ---- the domino scenes (test_gpu_resolver_chains.py) ----------------------------------------------------------------------------------------------
 from case_tables import (DOMINO_BEST, DOMINO_MIN_DEPTH, DOMINO_OTHER, DOMINO_RATIO, DOMINO_SECOND, RES_LCAP, RES_THREADS, STAGED_CHAIN_DROPPED,
                          domino_scene, greedy_fixpoint, greedy_serial, map_lists, row_lists, super_chunks)

@@ -4,7 +4,9 @@ Past the capacity the oracle runs with the same capacities (Oracle.set_capacitie
 frame's overflow count) -- include/lvt_c.h, "capacities".  Every frame of every test is compared in full (diff_frame) and in its pose."""
 import pytest
 
-from case_tables import MAP_MAX, MAPCAP_RECIPES, STAGED_MAX, mapcap_case, mapcap_track
+import numpy as np
+
+from case_tables import MAP_MAX, MAPCAP_RECIPES, RES_THREADS, STAGED_MAX, mapcap_case, mapcap_track, mapseam_case
 from parity_util import POSE_TOL, diff_frame, make_case, pose_errors
 
 pytestmark = pytest.mark.gpu
@@ -169,3 +171,45 @@ def test_capacity_cut_in_one_sequence_of_a_lockstep_batch(hip_lib, oracle_lib):
         assert batch.last_error() == ("capacity overflow mask 0x8 in sequence 0" if c0["overflow"] else ""), (i, batch.last_error())
         seen.append(c0["overflow"])
     assert len(seen) == n == 18 and seen == [0] * 16 + [8, 8] and batch.counts(0)["map_size"] == MAP_MAX
+
+
+def test_bookkeeping_either_side_of_1024_points(hip_lib, oracle_lib):
+    """`seam` (case_tables.py; test_case_tables.py holds its sizes): k_track_mid's two bookkeeping bodies in turn -- bookkeep_cull_small on a map of 938
+    points, bookkeep_cull_large on 1 043 (two chunks, the second nearly empty, a cull of 591), the small one again on what that left, the large one on
+    1 115 and 1 102 -- every frame compared in full and in its pose"""
+    from oracle import pyoracle as O
+    prm, frames = mapseam_case("seam")
+    hip = hip_lib.LvtSystem.create(prm, 1)
+    rows = _compare(hip, O.Oracle(prm, 1), frames)
+    hip.close()
+    at_match = [ch["map_size_at_match"] for _, ch, _ in rows]
+    assert any(896 < m <= RES_THREADS for m in at_match) and any(RES_THREADS < m <= 1152 for m in at_match), at_match
+    assert [m > RES_THREADS for m in at_match[1:]] == [False, True, False, False, True, True], at_match
+    assert all(ch["n_culled"] > 90 for _, ch, _ in rows[2:])
+
+
+def test_lost_on_a_map_of_more_than_1024_points(hip_lib, oracle_lib):
+    """`lost`: LOST decided by bookkeep_cull_large (1 420 points at match time), whose LOST branch applies the bookkeeping in place, compacts nothing and
+    returns ahead of its last barrier: the frame's full diff -- counters and ages of the map are those in-place writes --, then the state 3 latch: the
+    last pose again, the map untouched"""
+    from oracle import pyoracle as O
+    prm, frames = mapseam_case("lost")
+    hip, orc = hip_lib.LvtSystem.create(prm, 1), O.Oracle(prm, 1)
+    _compare(hip, orc, frames[:3])
+    before = hip.map()
+    Ro, to = mapcap_track(orc, frames[3])
+    Rh, th = mapcap_track(hip, frames[3])
+    msgs = diff_frame(hip, orc)
+    assert not msgs, msgs[:6]
+    ch = hip.counts()
+    assert hip.get_state() == orc.status == 3 and ch["map_size_at_match"] > RES_THREADS and ch["second_pass"] == 1 and ch["n_matches"] < prm.min_num_matches_for_tracking
+    after, want = hip.map(), orc.map()
+    assert all(np.array_equal(a, b) for a, b in zip(after[1:], want[1:])) and len(after[0]) == len(before[0]) == ch["map_size_at_match"]
+    assert np.array_equal(after[0], before[0]) and np.array_equal(after[3], before[3])              # nothing moved ...
+    assert int((after[1] != before[1]).sum()) > 100 and int((after[2] - before[2]).sum()) == ch["n_matches"]      # ... counters and ages stepped
+    last = th.copy()
+    Ro, to = mapcap_track(orc, frames[4]); Rh, th = mapcap_track(hip, frames[4])                     # LOST is sticky: the last pose, nothing is computed
+    assert hip.get_state() == orc.status == 3 and np.array_equal(th, last) and np.allclose(th, to, atol=1e-9)
+    still, error = hip.map(), hip.last_error()
+    hip.close()
+    assert all(np.array_equal(a, b) for a, b in zip(still, after)) and error == ""
