@@ -1,7 +1,8 @@
 // lvt_euroc -- EuRoC MAV stereo command line harness over the C-ABI (SURVEY 8(f) rows 1 + 2).
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/euroc/euroc_example.cpp:49-175 there):
-//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt]
+//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]]
+// (--clahe: CLAHE contrast equalisation of the rectified frames inside the feature stage, lvt_amd_set_equalisation; absent by default)
 // reads <stamps_dir>/<dataset_name>.txt (one nanosecond stamp per line = the image file stem), the cam0 / cam1 PNGs below
 // <root>/<dataset_name>/mav0/, hands the RAW images to lvt_track -- the two rectifiers with the calibration the reference hard-codes
 // (lvt_amd_rectifier_*: cv::initUndistortRectifyMap + cv::remap INTER_LINEAR) are attached to the tracker once, which rectifies
@@ -12,6 +13,7 @@
 #include "image_io.h"
 
 #include <chrono>
+#include <cstdio>
 #include <iomanip>
 #include <iostream>
 #include <sstream>
@@ -55,10 +57,18 @@ int main(int argc, char **argv) {
     const std::string seq_dir = root_dir + "/" + dataset_name + "/mav0";
     std::string out_name = dataset_name + ".txt";
     long max_frames = -1;
+    lvt_amd_equalisation clahe = {0, 0, 0.f};  // --clahe CLIP[,TX,TY]: equalise the rectified frames (dark sequences); tiles 8 x 8 unless given
     for (int i = 5; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
+        else if (k == "--clahe") {
+            clahe.tiles_x = clahe.tiles_y = 8;
+            if (std::sscanf(argv[i + 1], "%f,%d,%d", &clahe.clip_limit, &clahe.tiles_x, &clahe.tiles_y) < 1) {
+                std::cout << "--clahe CLIP[,TX,TY]: cannot read " << argv[i + 1] << std::endl;
+                return -1;
+            }
+        }
     }
     std::vector<std::string> titles;
     std::vector<double> time_stamps;
@@ -108,6 +118,10 @@ int main(int argc, char **argv) {
     }
     if (lvt_amd_set_rectifiers(vo, rect_l, rect_r) != 0) {  // from here on lvt_track takes the camera's raw images
         std::cout << "failed to attach the rectifiers: " << lvt_amd_last_error(vo) << std::endl;
+        return -1;
+    }
+    if (clahe.tiles_x && lvt_amd_set_equalisation(vo, &clahe) != 0) {
+        std::cout << "failed to set the equalisation: " << lvt_amd_last_error(vo) << std::endl;
         return -1;
     }
     long frame_count = (long)titles.size();

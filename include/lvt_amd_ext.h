@@ -243,7 +243,9 @@ LVT_API int lvt_amd_get_ordering(lvt_handle h);
  * 3 the converted gray image of a handle with a colour pixel format (u8, rows x pitch, before rectification; 0 bytes on a gray handle, and when the
  *   last frame was handed in before the colour format was set: nothing was converted for it),
  * 4 the registered depth plane of a handle with a depth camera (fp32, rows x pitch; 0 bytes without one, and when the last frame was handed in before
- *   the camera was set).
+ *   the camera was set),
+ * 5 the equalised image of a handle with an equalisation record (u8, rows x pitch; 0 bytes without one, and when the last frame was handed in before the
+ *   record was set), 6 the tables that image was made with (u8, tiles_x * tiles_y rows of 256).
  * returns bytes written, pitch via *pitch_out (in elements). */
 LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int cap_bytes, int *pitch_out);
 
@@ -378,6 +380,57 @@ LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera
 LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour,
                                           const void *d_depth, int depth_pitch_bytes, int depth_format, float depth_scale,
                                           void *d_out /* fp32 */, int out_pitch_bytes, void *hip_stream);
+
+/* DIM frames: CLAHE contrast equalisation inside the tracker's feature stage.  The detector's threshold is fixed; on dim images (EuRoC's dark sequences, a
+ * tunnel, lamp light) it finds nothing.  An equalisation record is a property of the handle, or of one sequence of a batch, like the pixel format; the record
+ * is copied.  It is not state: lvt_amd_reset, lvt_amd_batch_reset and snapshots neither hold nor change it.  Once it is set, EVERY frame-taking call on that
+ * handle or sequence, of either sensor, has the gray plane its detector would read equalised first: two launches at the head of the feature stage
+ * (k_clahe_lut: one table per tile; k_clahe_apply: the interpolated gather) write planes the tracker owns, and the frame is tracked from those -- the
+ * detector, the descriptor patches and the box sums all see the equalised plane.  Order: convert (pixel format), then remap (rectifiers), then equalise.
+ * Opt-in: undimmed frames lose a few per cent of their matches when equalised.  A handle or sequence that never sets a record launches exactly what it did
+ * before, and NULL returns a handle to that path.
+ *  The definition.  It follows the published algorithm of cv::CLAHE for 8-bit images; the claim is equality with THIS text, not with OpenCV (known
+ *  differences below).  Input: the W x H gray plane.  Integer arithmetic where written as integer; where written as fp32, one IEEE operation per written
+ *  operation, (float) of an integer rounds to nearest even, rint rounds half to even.
+ *   1. Geometry.  Wp = W + ((-W) mod tiles_x), Hp likewise (a dimension that already divides is not padded); tile_w = Wp / tiles_x, tile_h = Hp / tiles_y,
+ *      area = tile_w * tile_h.  The padded columns and rows mirror the image without repeating the edge pixel: x >= W reads 2 (W - 1) - x, likewise y
+ *      (BORDER_REFLECT_101).
+ *   2. Clip level.  c = clip_limit * (float)area / 256.0f (two fp32 operations, left to right).  clip = area if c >= (float)area (compared in fp32, before any
+ *      conversion); otherwise clip = max((int)c, 1), truncating.
+ *   3. Per tile (tx, ty): hist = the 256-bin histogram of its area padded pixels.  excess = sum of max(hist[i] - clip, 0); every bin is cut to clip;
+ *      batch = excess / 256, residual = excess - 256 * batch; every bin gains batch; if residual > 0: step = max(256 / residual, 1) and the bins
+ *      0, step, 2 step, ... gain 1 each, stopping at residual of them or at bin 255.  One pass: the redistribution is not iterated.
+ *   4. Table.  cum = the inclusive integer prefix sum of hist; lut_scale = 255.0f / (float)area; L[ty][tx][i] = clamp(rint((float)cum[i] * lut_scale), 0, 255).
+ *   5. Pixel (x, y) of value v.  fx = (float)x * (1.0f / (float)tile_w) - 0.5f; x1 = floor(fx); xa = fx - (float)x1; xa1 = 1.0f - xa; x2 = x1 + 1; then -- AFTER
+ *      xa is taken -- x1 and x2 are clamped to [0, tiles_x - 1].  The same for y.
+ *      out = clamp(rint((L[y1][x1][v] * xa1 + L[y1][x2][v] * xa) * ya1 + (L[y2][x1][v] * xa1 + L[y2][x2][v] * xa) * ya), 0, 255), every operation rounded to fp32.
+ *  Known differences from cv::CLAHE: OpenCV computes the clip level in double and converts it to int whatever its size; it pads BOTH dimensions by a whole
+ *  tile count's remainder as soon as one of them does not divide (a dimension that divides then gains tiles pixels, here it gains none); and its builds may
+ *  contract the interpolation's multiply-adds.  None of this has been compared against OpenCV.
+ *  - the record: tiles_x, tiles_y each 1 ... 16, tiles_x <= img_width, tiles_y <= img_height; clip_limit finite and > 0.
+ *  - external corners are in the same coordinates: lvt_track_with_external_corners stays allowed (a handle with rectifiers still refuses it).
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error): a pooled or automatic seat, the batch call on a handle that is not a batch and the other
+ *    way round, seq out of range, a bad record (the sentence names the field and its limits), a handle with frames in flight (set the record before the
+ *    first frame or after every frame has been collected) -- in this order.  A successful set counts as use of an lvt_create handle.
+ *  - lvt_amd_get_equalisation: 1 = a record is set (copied to *out), 0 = none, -1 = bad handle / seq.
+ *  - lvt_amd_get_plane(h, eye, 5, ...) reads the equalised plane of the last frame back (u8, rows x pitch; 0 bytes on a handle without a record, and when the
+ *    last frame went in before the record was set); (h, eye, 6, ...) reads the tables it was made with, tiles_x * tiles_y x 256 bytes, tile (tx, ty) at row
+ *    ty * tiles_x + tx.  lvt_amd_profile_read reports the launches as "k_clahe_lut" and "k_clahe_apply" (a handle with a record only).
+ *  - lvt_amd_equalise_device: the stage alone on caller planes (device pointers, u8): d_src any address, src_pitch >= w; d_dst 4-byte aligned, dst_pitch a
+ *    multiple of 4 and >= w -- every byte of h rows x dst_pitch is written, the columns from w on as zero; w, h 1 ... 8192.  Both launches go to hip_stream; the
+ *    call allocates its table buffer and frees it after synchronising that stream.  0 / -1.
+ *  - lvt_amd_equalisation_plan: host only, no device needed.  out = {Wp, Hp, tile_w, tile_h, area, clip}, *lut_scale (may be NULL) as in 4.; -1 for a record the
+ *    setter would refuse on an image of w x h. */
+typedef struct lvt_amd_equalisation {
+    int   tiles_x, tiles_y;   /* 1 ... 16 each, and <= the image's width / height */
+    float clip_limit;         /* finite, > 0 */
+} lvt_amd_equalisation;
+LVT_API int lvt_amd_set_equalisation(lvt_handle h, const lvt_amd_equalisation *cfg);                /* NULL: plain frames again; 0 / -1 */
+LVT_API int lvt_amd_batch_set_equalisation(lvt_handle h, int seq, const lvt_amd_equalisation *cfg);
+LVT_API int lvt_amd_get_equalisation(lvt_handle h, int seq, lvt_amd_equalisation *out);             /* 1 set, 0 none, -1 bad handle / seq */
+LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void *d_src, int src_pitch, int w, int h, void *d_dst, int dst_pitch,
+                                    void *hip_stream);
+LVT_API int lvt_amd_equalisation_plan(const lvt_amd_equalisation *cfg, int w, int h, int out[6], float *lut_scale);
 
 /* ---- SNAPSHOTS: one sequence's state saved, restored, moved between handles and seats -------------------------------------------------
  * A tracker's state lives in HBM: its control record, the local map, the staged points and the motion model.  A snapshot is a copy of it, device-resident and

@@ -316,6 +316,9 @@ class lvt_system {
      * frames again.  (track() / track_async() take ONE size for both views: a sensor whose depth image has another size goes through lvt_amd_track_rgbd*.)
      * false: refused (last_error() says why), nothing changed. */
     bool set_depth_camera(const lvt_amd_depth_camera *cam) { return lvt_amd_set_depth_camera(m_handle, cam) == 0; }
+    /* ADDITIVE: CLAHE contrast equalisation of the gray plane the detector reads (lvt_amd_equalisation, include/lvt_amd_ext.h, DIM frames): from now on every
+     * frame is equalised by two launches at the head of its feature stage; nullptr: plain frames again.  false: refused (last_error() says why), nothing changed. */
+    bool set_equalisation(const lvt_amd_equalisation *cfg) { return lvt_amd_set_equalisation(m_handle, cfg) == 0; }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
         m_state = lvt_amd_wait_pose(m_handle, q, p);

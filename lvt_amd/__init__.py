@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "lvt_amd_enable_pose_info", "lvt_amd_get_pose_info", "lvt_amd_pose_info_eval", "lvt_amd_pose_info_to_ros",
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
+    "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
 ]
 
 N_COUNTS = 32
@@ -204,6 +205,12 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (   # (dim frames: likewise)
+            ("lvt_amd_set_equalisation", [vp, vp]), ("lvt_amd_batch_set_equalisation", [vp, C.c_int, vp]), ("lvt_amd_get_equalisation", [vp, C.c_int, vp]),
+            ("lvt_amd_equalise_device", [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]), ("lvt_amd_equalisation_plan", [vp, C.c_int, C.c_int, vp, vp])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -271,6 +278,49 @@ def register_depth_device(cam: DepthCamera, params: LvtParameters, d_depth: int,
     pod = params.to_pod()
     return load_library().lvt_amd_register_depth_device(C.byref(cam), C.byref(pod), C.c_void_p(d_depth), int(depth_pitch), int(depth_format), float(depth_scale),
                                                         C.c_void_p(d_out), int(out_pitch), C.c_void_p(stream))
+
+
+class Equalisation(C.Structure):
+    """lvt_amd_equalisation: CLAHE contrast equalisation of the gray plane the detector reads (include/lvt_amd_ext.h, DIM frames) -- tiles = (tiles_x, tiles_y),
+    1 ... 16 each and no more than the image's width / height; clip_limit finite and > 0"""
+    _fields_ = [("tiles_x", C.c_int), ("tiles_y", C.c_int), ("clip_limit", C.c_float)]
+
+    def __init__(self, tiles=(8, 8), clip_limit=3.0):
+        super().__init__(int(tiles[0]), int(tiles[1]), float(clip_limit))
+
+    @property
+    def tiles(self):
+        return (int(self.tiles_x), int(self.tiles_y))
+
+    def __repr__(self):
+        return f"Equalisation(tiles={self.tiles}, clip_limit={float(self.clip_limit)!r})"
+
+
+def _equalisation_of(handle, seq):
+    e = Equalisation()
+    rc = load_library().lvt_amd_get_equalisation(handle, int(seq), C.byref(e))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_equalisation: bad handle or no sequence {seq}")
+    return e if rc == 1 else None
+
+
+def equalise_device(cfg: Equalisation, d_src: int, src_pitch: int, width: int, height: int, d_dst: int, dst_pitch: int, stream: int = 0) -> int:
+    """stage entry: the equalisation alone on device planes (u8; d_src any address, src_pitch >= width; d_dst 4-byte aligned, dst_pitch % 4 == 0 and >= width:
+    every byte of height x dst_pitch is written, the columns from width on as zero); 0 / -1"""
+    return load_library().lvt_amd_equalise_device(C.byref(cfg), C.c_void_p(d_src), int(src_pitch), int(width), int(height), C.c_void_p(d_dst), int(dst_pitch),
+                                                  C.c_void_p(stream))
+
+
+def equalisation_plan(cfg: Equalisation, width: int, height: int):
+    """steps 1 and 2 of the definition for a width x height image: {Wp, Hp, tile_w, tile_h, area, clip, lut_scale}; None for a record the setter would refuse.
+    Host code: needs the library, not a GPU"""
+    out = (C.c_int * 6)()
+    scale = C.c_float(0)
+    if load_library().lvt_amd_equalisation_plan(C.byref(cfg), int(width), int(height), out, C.byref(scale)) != 0:
+        return None
+    d = dict(zip(("Wp", "Hp", "tile_w", "tile_h", "area", "clip"), (int(x) for x in out)))
+    d["lut_scale"] = np.float32(scale.value)
+    return d
 
 
 class SnapshotInfo(C.Structure):
@@ -593,6 +643,17 @@ class LvtSystem:
             self._depth_shape = (int(cam.height), int(cam.width)) if cam is not None else None
         return rc
 
+    def set_equalisation(self, cfg=None, **kw) -> int:
+        """an Equalisation (or its arguments: tiles=, clip_limit=): every frame handed to this system from now on has the gray plane its detector reads
+        equalised first, two launches at the head of the feature stage; None: plain frames again.  0: done; -1: refused (last_error())."""
+        if cfg is None and kw:
+            cfg = Equalisation(**kw)
+        return load_library().lvt_amd_set_equalisation(self._h, C.byref(cfg) if cfg is not None else None)
+
+    def equalisation(self):
+        """the Equalisation that is set, or None"""
+        return _equalisation_of(self._h, 0)
+
     def _depth(self, d):
         """the depth array of a host call: with a depth camera set the library reads cam.height x cam.width elements, and the C-ABI has no size argument for
         them -- an array of any other shape would be read past its end"""
@@ -666,7 +727,7 @@ class LvtSystem:
         name = C.create_string_buffer(64); ms = C.c_double(0); calls = C.c_long(0)
         for slot in range(64):
             if not load_library().lvt_amd_profile_read(self._h, slot, name, 64, C.byref(ms), C.byref(calls)):
-                if slot >= 22:
+                if slot >= 26:   # (past the last slot; the slots below it may be absent on this handle)
                     break
                 continue
             out.append((name.value.decode(), ms.value, calls.value))
@@ -689,7 +750,8 @@ class LvtSystem:
     def plane(self, eye=0, what=0):
         """what=0: corner score map (u8), what=1: 9x9 box sums (u16), what=2: the rectified image of a system with rectifiers (u8; an empty array
         without them), what=3: the converted gray image of a system with a colour pixel format (u8, before rectification; empty on a gray system),
-        what=4: the registered depth plane of a system with a depth camera (float32, +inf where nothing landed; empty without one);
+        what=4: the registered depth plane of a system with a depth camera (float32, +inf where nothing landed; empty without one),
+        what=5: the equalised image of a system with an equalisation (u8; empty without one), what=6: the tables it was made with (tiles x 256, u8);
         returns (rows, pitch) array"""
         cap = 64 << 20
         buf = np.zeros(cap // 8, dtype=np.uint64)
@@ -789,6 +851,15 @@ class LvtBatch:
 
     def depth_camera(self, seq: int):
         return _depth_camera_of(self._h, seq)
+
+    def set_equalisation(self, seq: int, cfg=None, **kw) -> int:
+        """LvtSystem.set_equalisation for sequence `seq` of the batch: its frames are equalised from then on, the other sequences' are not"""
+        if cfg is None and kw:
+            cfg = Equalisation(**kw)
+        return load_library().lvt_amd_batch_set_equalisation(self._h, int(seq), C.byref(cfg) if cfg is not None else None)
+
+    def equalisation(self, seq: int):
+        return _equalisation_of(self._h, seq)
 
     def enable_pose_info(self, on: bool = True) -> int:
         """LvtSystem.enable_pose_info for all sequences of the batch together"""

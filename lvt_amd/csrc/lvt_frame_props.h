@@ -1,5 +1,5 @@
 // lvt_frame_props.h -- the properties a handle, or one sequence of a batch, has besides its parameters (included by lvt_host.hip): rectifiers for raw frames,
-// a pixel format for colour frames, a depth camera for unregistered depth, the pose-uncertainty record.
+// a pixel format for colour frames, a depth camera for unregistered depth, an equalisation record for dim frames, the pose-uncertainty record.
 //
 // THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
 // was, lvt_amd_last_error says why); it needs a quiet handle (no frame in flight); an lvt_create handle is decided under its record's lock; a property is
@@ -74,7 +74,7 @@ static int put_seq_value(Context *c, std::vector<T> &v, int per_seq, const T &no
     return n;
 }
 
-// ---- one packer for the by-value descriptor tables (GrayTable, RectTable, DepthRegTable, StateTable) ------------------------------------------------
+// ---- one packer for the by-value descriptor tables (GrayTable, RectTable, DepthRegTable, ClaheTable, StateTable) ------------------------------------------------
 // blockIdx.y is the descriptor and the grid's x extent follows the largest one (the caller keeps that maximum and clears it in `launch`).
 // THE RULE: add(k) flushes first when the next sequence's k descriptors do not fit; flush() sends what is left; launch(tab, n, first) is told whether it
 // is the step's first launch -- the one its profile slot times, later ones go out untimed.  The launches are the ones four hand-written loops made:
@@ -284,6 +284,104 @@ static int set_depth_camera(lvt_handle h, int seq, bool batch_call, const lvt_am
     });
 }
 
+// ---- dim frames: an equalisation record per handle / per sequence of a batch (Context::equal, k_equalise.hip) -----------------------------------------
+// steps 1 and 2 of the definition (include/lvt_amd_ext.h) for a w x h image
+struct EqualPlan {
+    int Wp, Hp, tile_w, tile_h, area, clip;
+    float lut_scale;
+};
+// "" when the record passes on an image of w x h: names the offending field and its limits otherwise
+static std::string equalisation_check(const lvt_amd_equalisation &e, int w, int h) {
+    if (e.tiles_x < 1 || e.tiles_x > CLAHE_MAX_TILES) return "an equalisation with tiles_x = " + std::to_string(e.tiles_x) + " (1 ... 16)";
+    if (e.tiles_y < 1 || e.tiles_y > CLAHE_MAX_TILES) return "an equalisation with tiles_y = " + std::to_string(e.tiles_y) + " (1 ... 16)";
+    if (!(std::isfinite(e.clip_limit) && e.clip_limit > 0.f)) return "an equalisation whose clip_limit is not finite and > 0";
+    if (e.tiles_x > w) return "an equalisation with tiles_x = " + std::to_string(e.tiles_x) + " on an image " + std::to_string(w) + " pixels wide (tiles_x <= img_width)";
+    if (e.tiles_y > h) return "an equalisation with tiles_y = " + std::to_string(e.tiles_y) + " on an image " + std::to_string(h) + " pixels high (tiles_y <= img_height)";
+    return "";
+}
+static EqualPlan equalisation_plan(const lvt_amd_equalisation &e, int w, int h) {
+    EqualPlan p;
+    p.Wp = w + (e.tiles_x - w % e.tiles_x) % e.tiles_x, p.Hp = h + (e.tiles_y - h % e.tiles_y) % e.tiles_y;
+    p.tile_w = p.Wp / e.tiles_x, p.tile_h = p.Hp / e.tiles_y, p.area = p.tile_w * p.tile_h;
+    const float fa = (float)p.area;
+    const float c = e.clip_limit * fa / 256.0f;  // (two fp32 operations, left to right; may overflow to +inf: then c >= fa)
+    p.clip = (c >= fa) ? p.area : std::max((int)c, 1);
+    p.lut_scale = 255.0f / fa;
+    return p;
+}
+// one image's descriptor: src (any pitch >= w) equalised into dst with the tables in lut
+static ClaheImg clahe_img(const lvt_amd_equalisation &e, const uint8_t *src, int src_pitch, int w, int h, uint8_t *dst, int dst_pitch, uint8_t *lut, int direct) {
+    const EqualPlan p = equalisation_plan(e, w, h);
+    ClaheImg I{};
+    I.src = src, I.dst = dst, I.lut = lut, I.src_pitch = src_pitch, I.dst_pitch = dst_pitch, I.w = w, I.h = h;
+    I.tiles_x = e.tiles_x, I.tiles_y = e.tiles_y, I.tile_w = p.tile_w, I.tile_h = p.tile_h, I.clip = p.clip, I.lut_scale = p.lut_scale;
+    I.inv_tw = 1.0f / (float)p.tile_w, I.inv_th = 1.0f / (float)p.tile_h, I.direct = direct;
+    return I;
+}
+// LVT_AMD_CLAHE_GATHER=l1: k_clahe_apply gathers its tables through L1 instead of staging them in LDS (tools/equalisation.py measures both)
+static int clahe_direct() {
+    static const int v = [] {
+        const char *e = std::getenv("LVT_AMD_CLAHE_GATHER");
+        return (e && std::strcmp(e, "l1") == 0) ? 1 : 0;
+    }();
+    return v;
+}
+// Every image of every sequence that has a record and a frame in this step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in TWO
+// launches per table, behind the conversion and the remap: what is equalised is exactly the plane k_score would have read, and k_gather's box-sum fall-back
+// and k_brief_img see the equalised plane too, through FrameIn::img.  The equalised planes (parity `par`) were read last by the feature stage of frame
+// enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before --; the tables were read last by k_clahe_apply of the previous frame,
+// on this stream; and the source was written on this stream (a pull, k_gray_frames, k_rectify_frames) or belongs to the caller: stream order alone covers
+// the hand-over, and the launches need no gate: they go out ahead of the buffer gate.
+static void equalise_frames(Context *c, int slot, int par, int Bz) {
+    FrameArgs *fw = &frame_args(c, slot);
+    int words = 0, tiles = 0;
+    TablePacker pk(&ClaheTable::im, [&](const ClaheTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 24, k_clahe_lut, dim3(tiles, n), tab);
+        LAUNCH_TABLE(first, 25, k_clahe_apply, dim3((words + 255) / 256, n), tab);
+        words = 0, tiles = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (!c->has_equal(s) || fw[s].absent) continue;
+        const Params &q = c->seq_prm(s);
+        const lvt_amd_equalisation &e = c->equal[(size_t)s];
+        const int dpitch = c->h_seqs[s].plane_pitch, eyes = (c->sensor == 2) ? 1 : 2;
+        ClaheImg *im = pk.add(eyes);
+        for (int k = 0; k < eyes; k++) {
+            im[k] = clahe_img(e, fw[s].img[k], fw[s].img_pitch, q.W, q.H, c->d_eq[((size_t)s * NPAR + par) * 2 + k], dpitch, c->d_eq_lut[(size_t)s * 2 + k], clahe_direct());
+            words = std::max(words, dpitch / 4 * q.H), tiles = std::max(tiles, e.tiles_x * e.tiles_y);
+            fw[s].img[k] = im[k].dst;
+        }
+        if (eyes == 1) fw[s].img[1] = fw[s].img[0];
+        fw[s].img_pitch = dpitch;
+        if (s == 0) c->ring_equalised[slot] = true;
+    }
+    pk.flush();
+}
+static int set_equalisation(lvt_handle h, int seq, bool batch_call, const lvt_amd_equalisation *cfg) {
+    static const PropertyCall call = {"lvt_amd_set_equalisation", 0,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                       "a batch handle takes its equalisation per sequence through lvt_amd_batch_set_equalisation (nothing was changed)"},
+                                      "lvt_amd_batch_set_equalisation on a handle that is not a batch (use lvt_amd_set_equalisation)"};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (cfg) {
+            const std::string why = equalisation_check(*cfg, c->seq_prm(seq).W, c->seq_prm(seq).H);
+            if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        }
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the equalisation before the first frame or after every frame has been collected");
+        if (!cfg && !c->has_equal(seq)) return 0;
+        if (seq == 0) std::fill(std::begin(c->ring_equalised), std::end(c->ring_equalised), false);  // (the last frame went in before THIS record: lvt_amd_get_plane(.., 5 / 6, ..) has nothing of it)
+        if (cfg) {
+            const int eyes = c->sensor == 2 ? 1 : 2;
+            give_planes(c, c->d_eq, 2, seq, eyes, 64);
+            if (c->d_eq_lut.empty()) c->d_eq_lut.assign((size_t)c->B * 2, nullptr);
+            for (int e = 0; e < eyes; e++)
+                if (!c->d_eq_lut[(size_t)seq * 2 + e]) c->d_eq_lut[(size_t)seq * 2 + e] = c->dalloc<uint8_t>((size_t)CLAHE_MAX_TILES * CLAHE_MAX_TILES * 256);
+        }
+        c->n_equal = put_seq_value(c, c->equal, 1, lvt_amd_equalisation{}, seq, {cfg ? *cfg : lvt_amd_equalisation{}}, [](const lvt_amd_equalisation &e) { return e.tiles_x > 0; });
+        return 0;
+    });
+}
+
 // ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ----------------------------------
 static int enable_pose_info(lvt_handle h, int enable) {
     static const PropertyCall call = {"lvt_amd_enable_pose_info", 0, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr, nullptr}, nullptr};
@@ -347,6 +445,43 @@ LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const
     hipLaunchKernelGGL(k_depth_clear, dim3((unsigned)(((words + 3) / 4 + 255) / 256), 1), dim3(256), 0, st, tab);
     hipLaunchKernelGGL(k_depth_register, dim3((unsigned)((I.dw * I.dh + 255) / 256), 1), dim3(256), 0, st, tab);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+LVT_API int lvt_amd_set_equalisation(lvt_handle h, const lvt_amd_equalisation *cfg) { return set_equalisation(h, 0, false, cfg); }
+LVT_API int lvt_amd_batch_set_equalisation(lvt_handle h, int seq, const lvt_amd_equalisation *cfg) { return set_equalisation(h, seq, true, cfg); }
+LVT_API int lvt_amd_get_equalisation(lvt_handle h, int seq, lvt_amd_equalisation *out) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->has_equal(seq)) return 0;
+    if (out) *out = c->equal[(size_t)seq];
+    return 1;
+}
+// host only: steps 1 and 2 of the definition
+LVT_API int lvt_amd_equalisation_plan(const lvt_amd_equalisation *cfg, int w, int h, int out[6], float *lut_scale) {
+    if (!cfg || !out || w < 1 || w > 8192 || h < 1 || h > 8192 || !equalisation_check(*cfg, w, h).empty()) return -1;
+    const EqualPlan p = equalisation_plan(*cfg, w, h);
+    out[0] = p.Wp, out[1] = p.Hp, out[2] = p.tile_w, out[3] = p.tile_h, out[4] = p.area, out[5] = p.clip;
+    if (lut_scale) *lut_scale = p.lut_scale;
+    return 0;
+}
+// the stage alone on caller planes: both launches on the caller's stream; the table buffer lives until the stream has run them
+LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void *d_src, int src_pitch, int w, int h, void *d_dst, int dst_pitch, void *hip_stream) {
+    if (!cfg || !d_src || !d_dst || w < 1 || w > 8192 || h < 1 || h > 8192 || !equalisation_check(*cfg, w, h).empty()) return -1;
+    if (src_pitch < w || dst_pitch < w || (dst_pitch & 3) || ((uintptr_t)d_dst & 3) || (long long)dst_pitch * h > 0x7FFFFFFFll) return -1;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    uint8_t *lut = nullptr;
+    if (hipMalloc((void **)&lut, (size_t)cfg->tiles_x * cfg->tiles_y * 256) != hipSuccess) return -1;
+    ClaheTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.im[0] = clahe_img(*cfg, static_cast<const uint8_t *>(d_src), src_pitch, w, h, static_cast<uint8_t *>(d_dst), dst_pitch, lut, clahe_direct());
+    hipLaunchKernelGGL(k_clahe_lut, dim3(cfg->tiles_x * cfg->tiles_y, 1), dim3(256), 0, st, tab);
+    hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)(((size_t)(dst_pitch / 4) * h + 255) / 256), 1), dim3(256), 0, st, tab);
+    const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    (void)hipFree(lut);
+    return ok ? 0 : -1;
 }
 
 LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) { return enable_pose_info(h, enable); }

@@ -20,6 +20,7 @@
 #include "k_lists.hip"
 #include "k_rectify.hip"
 #include "k_depthreg.hip"
+#include "k_equalise.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
 #include "lvt_odometry.h"
@@ -298,6 +299,16 @@ struct Context {
     int n_depth_cam = 0;                          // sequences with a depth camera
     bool ring_registered[RING] = {};              // per un-collected / last frame: sequence 0's depth went through k_depth_register (lvt_amd_get_plane(.., 4, ..))
     bool has_depth_cam(int s) const { return n_depth_cam > 0 && depth_cam[(size_t)s].width > 0; }
+    // DIM frames (lvt_amd_set_equalisation / lvt_amd_batch_set_equalisation): a sequence with an equalisation record has the gray plane its detector would read --
+    // behind the conversion and the remap -- equalised by two launches at the head of the feature stage (k_clahe_lut, k_clahe_apply), into planes of its own the
+    // frame is then pointed at.  A property of the handle, not state: reset and snapshots leave it alone.
+    std::vector<lvt_amd_equalisation> equal;  // [B] (empty until the first set); tiles_x == 0: none
+    std::vector<uint8_t *> d_eq;              // [B][NPAR][2] equalised planes, each sequence's own pitch (an RGB-D sequence: eye 0 only)
+    std::vector<uint8_t *> d_eq_lut;          // [B][2] the tables of a sequence's eye: 16 x 16 x 256 bytes.  ONE copy: the writer (k_clahe_lut) and the reader
+                                              // (k_clahe_apply) of frame t and the writer of frame t + 1 are on the same in-order stream
+    int n_equal = 0;                          // sequences with the property
+    bool ring_equalised[RING] = {};           // per un-collected / last frame: sequence 0's image went through k_clahe_apply (lvt_amd_get_plane(.., 5, ..))
+    bool has_equal(int s) const { return n_equal > 0 && equal[(size_t)s].tiles_x > 0; }
     // the depth plane the host entry points of sequence 0 take: the camera's size where one is set, else the image's
     size_t depth_px() const { return has_depth_cam(0) ? (size_t)depth_cam[0].width * depth_cam[0].height : (size_t)prm.W * prm.H; }
     int depth_cols() const { return has_depth_cam(0) ? depth_cam[0].width : prm.W; }
@@ -311,7 +322,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 24;
+    static constexpr int PROF_SLOTS = 26;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -863,7 +874,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -947,6 +958,7 @@ struct DepthRegPlan {
 };
 static void convert_colour_frames(Context *c, int slot, int par, int Bz);
 static void rectify_raw_frames(Context *c, int slot, int par, int Bz);
+static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
 static void scatter_depth_planes(Context *c, const DepthRegPlan &plan);
 static void enqueue_frame(Context *c) {
@@ -988,10 +1000,12 @@ static void enqueue_frame(Context *c) {
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
     // ---- the frame properties' launches at its head, ahead of the buffer gate (lvt_frame_props.h: why stream order alone covers each hand-over).  They point the
     //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
-    //      (the reference's order), then the clear of the registered depth planes, whose scatter goes out in front of k_gather.
-    c->ring_converted[slot] = c->ring_registered[slot] = false;
+    //      (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
+    //      in front of k_gather.
+    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = false;
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
+    if (c->n_equal) equalise_frames(c, slot, par, Bz);
     DepthRegPlan dreg;
     if (c->n_depth_cam) begin_depth_registration(c, slot, par, Bz, dreg);
     const bool evo = c->events_only;
@@ -1294,10 +1308,11 @@ static void track_sync(Context *c, double R[3][3], double t[3]) {
 
 static bool size_ok(Context *c, int rows, int cols) { return rows == c->prm.H && cols == c->prm.W; }
 // pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
-// byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes)
+// byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes) and the gray frame of an
+// EQUALISED sequence by k_clahe_lut / k_clahe_apply
 static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) {
     if (c->fmt_of(s) != PIX_GRAY8) return (long long)pitch >= (long long)cols * c->bpp_of(s);
-    return c->has_rect(s) ? pitch >= cols : (pitch & 15) == 0;
+    return (c->has_rect(s) || c->has_equal(s)) ? pitch >= cols : (pitch & 15) == 0;
 }
 
 template <typename T>
@@ -1711,8 +1726,9 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot == 4 && c->n_rect == 0 && c->prof_calls[4] == 0) return 0;  // (a handle without rectifiers has no such launch)
     if (slot == 14 && c->n_colour == 0 && c->prof_calls[14] == 0) return 0;  // (... and one without a colour sequence no k_gray_frames)
     if (slot == 15 && !c->pose_info && c->prof_calls[15] == 0) return 0;  // (... one that never enabled pose uncertainty no k_pose_info)
-    if (slot >= 22 && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
+    if ((slot == 22 || slot == 23) && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
     if ((slot == 17 || slot == 21) && c->n_depth_cam == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without a depth camera no registration launches)
+    if ((slot == 24 || slot == 25) && c->n_equal == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without an equalisation record neither of its launches)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1826,7 +1842,7 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
                 std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : c->has_rect(s) ? "at least the width" : "a multiple of 16");
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s)) ? "at least the width" : "a multiple of 16");
                 return refuse(h, who, buf);
             }
         }
@@ -2551,6 +2567,15 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
         const int e = eye ? 1 : 0;
         const void *src = (what == 0) ? (const void *)FB.score[e] : (const void *)FB.boxsum[e];
         size_t esz = (what == 0) ? 1 : 2;
+        if (what == 5 || what == 6) {  // the equalised image of the last frame (u8, rows x pitch) / the tables it was made with (tiles_x * tiles_y x 256 bytes)
+            if (c->done == 0 || !c->has_equal(0) || !c->ring_equalised[c->last_slot]) return 0;
+            const int ee = c->sensor == 1 ? e : 0;
+            const size_t bytes = what == 5 ? n : (size_t)c->equal[0].tiles_x * c->equal[0].tiles_y * 256;
+            if ((size_t)cap_bytes < bytes) return -1;
+            HIPCHK(c, hipMemcpy(dst, what == 5 ? c->d_eq[(size_t)c->last_par * 2 + ee] : c->d_eq_lut[(size_t)ee], bytes, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = what == 5 ? c->pitch : 256;
+            return (int)bytes;
+        }
         if (what >= 2 && what <= 4) {  // a frame property's plane: 0 bytes unless the last frame went through that stage
             if (c->done == 0) return 0;
             if (what == 2) {  // the rectified image of the last (raw) frame
