@@ -180,7 +180,30 @@ LVT_API int lvt_amd_batch_get_params(lvt_handle h, int seq, lvt_amd_params *out)
 LVT_API int lvt_amd_batch_mixed_tables(const lvt_amd_params *p, int sensor_type, int n_sequences, unsigned *cells, int cells_cap,
                                        unsigned *score, int score_cap, int counts[2]);
 
-/* run all work of this handle on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream) */
+/* ---- a CALLER'S stream ------------------------------------------------------------------------------------------------------
+ * Order this handle's frames behind the work of an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream): the tracking chain runs ON
+ * that stream from the next frame on, and the feature stage -- which stays on a stream of the library's -- waits at the head of every frame for an
+ * event recorded there.  A single handle or a batch (one stream for the whole batch).
+ *  1. INPUTS.  Work enqueued on hip_stream BEFORE a frame call completes before any kernel of that frame reads the caller's planes (image, colour,
+ *     raw or depth); no host synchronisation is needed between a producer kernel and lvt_amd_track_device[_async], lvt_amd_track_rgbd_device[_async],
+ *     lvt_amd_batch_track_device_async[_mixed] or lvt_amd_batch_track_rgbd_device_async.  Without this call the library's streams are its own and are
+ *     ordered behind NOTHING of the caller's: the planes must be complete (host-synchronised) when a frame call is made.
+ *  2. RESULTS.  The records -- poses, states, counters, features, the map -- are bit for bit those of a handle on its private stream fed the same frames.
+ *  3. RELEASE is unchanged: the planes belong to the tracker until the frame has been collected by the host.
+ *  4. The call DRAINS first: the frames in flight are collected on the stream they were enqueued on (lvt_amd_get_host_stats out[1] == out[0] behind it; of
+ *     their records the last one stays readable), then the old stream is synchronised.  The stream may be changed between frames any number of times.
+ *     The stream stays the caller's: lvt_destroy synchronises it and never destroys it; it must outlive the handle or be replaced first.
+ *  5. hip_stream == NULL is the legacy default stream (what the example above is on torch's default stream), for a single handle and for a batch.  (The
+ *     CU-masked feature stream of a batch of 2 - 28 sequences synchronises with the NULL stream as every default-flag stream does; that adds waits for
+ *     EARLIER work only, which is all a gate of this library ever waits for: DESIGN.md section 2, "A caller's stream".)  A producer that keeps the
+ *     stream busy for longer than 20 ms in front of a frame call makes the early stream stand down for that frame, on any stream: reported through
+ *     lvt_amd_last_error, results unaffected.
+ *  6. A pooled handle runs on its pool's streams: it ignores the call and goes on tracking.  On an lvt_create handle the call is a use: the handle keeps
+ *     its own chain when a second lvt_create with the same parameters follows.
+ * COST.  The event lands behind the previous frame's tracking chain on the same stream, so a handle on a caller's stream gives up the overlap of a frame's
+ * feature stage with the tracking of the frame before it (the asynchronous calls still overlap the host with the GPU).  A handle that never makes this
+ * call launches and records exactly what it always did.  Returns nothing: when the event cannot be created the handle stays on the stream it had and
+ * lvt_amd_last_error says so. */
 LVT_API void lvt_amd_set_stream(lvt_handle h, void *hip_stream);
 /* last HIP error string seen by this handle ("" if none); overflow / capacity diagnostics too.  A capacity report is its frame's own: once it has
  * been read here, the next frame collected that fits clears it (read after every frame, the string speaks for that frame; read every N frames, a
@@ -288,8 +311,10 @@ LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_
 
 /* ---- EuRoC pre-step: stereo rectification (reference examples/euroc/euroc_example.cpp:95-107,142-143 = cv::initUndistortRectifyMap
  * with CV_32FC1 maps + cv::remap INTER_LINEAR, BORDER_CONSTANT 0).  K, R, Pnew row-major 3x3, D = k1 k2 p1 p2 k3.
- * The maps are built once on the device; lvt_amd_rectify_device rectifies one 8-bit image already in HBM (dst_pitch % 4 == 0,
- * returns 0 on success), lvt_amd_rectify does the same for tightly packed host buffers. ---- */
+ * The maps are built once on the device; lvt_amd_rectify_device rectifies one 8-bit image already in HBM: ONE launch on hip_stream, in that stream's
+ * order, nothing is synchronised.  src_pitch >= width (the source's padding is never read); dst_pitch >= width and dst_pitch % 4 == 0: every byte of
+ * height x dst_pitch is written, the columns from width on as zero, nothing behind them.  Returns 0; -1 (NULL, a pitch that breaks these rules) and then
+ * nothing was launched.  lvt_amd_rectify does the same for tightly packed host buffers. ---- */
 typedef void *lvt_amd_rectifier;
 LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9],
                                                    const double Pnew[9], int width, int height);

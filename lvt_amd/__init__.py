@@ -675,6 +675,8 @@ class LvtSystem:
         return _pose_info_of(self._h, 0)
 
     def set_stream(self, hip_stream: int):
+        """lvt_amd_set_stream: the tracking chain runs on that HIP stream from the next frame on (torch.cuda.current_stream().cuda_stream; 0: the legacy default
+        stream), and work enqueued on it before a frame call completes before the frame's planes are read.  Drains first; a pooled seat ignores the call"""
         load_library().lvt_amd_set_stream(self._h, C.c_void_p(hip_stream))
 
     # ---- introspection of the last frame (for stage-by-stage parity tests) ----
@@ -903,6 +905,8 @@ class LvtBatch:
         """lvt_system::reset for sequence `seq` alone (drains first).  0: done; -1: refused (last_error())"""
         return load_library().lvt_amd_batch_reset(self._h, int(seq))
 
+    set_stream = LvtSystem.set_stream   # (one stream for the whole batch)
+
     def wait(self):
         R = np.zeros((self.B, 3, 3)); t = np.zeros((self.B, 3)); st = np.zeros(self.B, np.int32)
         load_library().lvt_amd_batch_wait(self._h, _p(R), _p(t), _p(st))
@@ -1033,6 +1037,11 @@ class Rectifier:
         if load_library().lvt_amd_rectify(self._h, _p(a), _p(out)) != 0:
             raise RuntimeError("lvt_amd_rectify failed")
         return out
+
+    def rectify_device(self, d_src: int, src_pitch: int, d_dst: int, dst_pitch: int, stream: int = 0) -> int:
+        """stage entry: the remap alone on device planes, enqueued on `stream` (u8; src_pitch >= width; dst_pitch % 4 == 0 and >= width: every byte of
+        height x dst_pitch is written, the columns from width on as zero); 0 / -1 (refused, nothing enqueued)"""
+        return load_library().lvt_amd_rectify_device(self._h, C.c_void_p(d_src), int(src_pitch), C.c_void_p(d_dst), int(dst_pitch), C.c_void_p(stream))
 
     def close(self):
         if self._h:

@@ -185,6 +185,11 @@ struct Context {
     hipStream_t stream_f = nullptr;  // feature stage
     hipStream_t stream_e = nullptr;  // early part of find_matches of the next frame (behind the previous frame's k_pnp)
     bool own_stream = false;
+    // A CALLER'S stream (lvt_amd_set_stream: own_stream == false).  The caller's planes are read on stream_f, so every step records ev_caller on `stream` at its
+    // head and stream_f waits for it: what the caller enqueued on its stream before the frame call has completed before any kernel of the frame reads a plane.
+    // The event lands behind the previous frame's tracking chain on the same stream: such a handle's feature stage no longer runs ahead of its tracking.  Created
+    // by the first lvt_amd_set_stream; a handle on its private stream never records or waits for it.
+    hipEvent_t ev_caller = nullptr;
     std::vector<void *> allocs;
     const Seq *d_seqs = nullptr;  // written ONCE, by create_context, from h_seqs; no kernel and no later host code writes it (lvt_dev.h: SeqArg)
     std::vector<Seq> h_seqs;   // host mirror (device pointers inside)
@@ -351,9 +356,16 @@ struct Context {
         size_t bytes = ((n * sizeof(T) + 255) / 256) * 256;
         if (bytes == 0) bytes = 256;
         HIPCHK(this, hipMalloc(&p, bytes));
-        HIPCHK(this, hipMemset(p, 0, bytes));
+        zero_now(p, bytes);
         allocs.push_back(p);
         return static_cast<T *>(p);
+    }
+    // hipMemset of device memory goes to the NULL stream and may return before it has run; the streams of a single sequence are non-blocking, i.e. not ordered
+    // behind the NULL stream.  Buffers are also allocated with frames in flight (the image ring of the asynchronous host calls, one slot per frame for the first
+    // RING frames): the pull launched into a fresh plane a few microseconds later must not be overtaken by the plane's own clear
+    void zero_now(void *p, size_t bytes) {
+        HIPCHK(this, hipMemset(p, 0, bytes));
+        HIPCHK(this, hipStreamSynchronize(nullptr));
     }
 
     void dfree(void *p) {  // give a dalloc'ed buffer back before the context ends (nullptr: nothing)
@@ -376,7 +388,7 @@ struct Context {
     Context() {}
     ~Context() {
         if (counted) g_live_contexts[device % MAX_DEVICES].fetch_sub(1);
-        if (stream) (void)hipStreamSynchronize(stream);
+        if (stream || !own_stream) (void)hipStreamSynchronize(stream);  // (a caller's stream may be NULL, the legacy default stream: the chain on it ends before its buffers go)
         if (stream_f) (void)hipStreamSynchronize(stream_f);
         if (stream_e) (void)hipStreamSynchronize(stream_e);
         for (void *p : allocs) (void)hipFree(p);
@@ -389,6 +401,7 @@ struct Context {
         if (ev_depth) (void)hipEventDestroy(ev_depth);
         if (ev_switch) (void)hipEventDestroy(ev_switch);
         if (ev_switch_e) (void)hipEventDestroy(ev_switch_e);
+        if (ev_caller) (void)hipEventDestroy(ev_caller);
         for (auto &x : stage) if (x.h) (void)hipHostFree(x.h);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_done) (void)hipHostFree(h_done);
@@ -672,7 +685,10 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
             // pipeline, 12 alone).  Measured, frames/s with all CUs -> with 224 of 256: 8 sequences 43.5k -> 45.7k, 16: 70.1k -> 74.9k, 24: 82.4k -> 86.6k;
             // 32 sequences are bound by the feature stream itself (k_score is VALU-bound) and lose: 92.6k -> 88.6k, so larger batches keep every CU.
             // LVT_AMD_FEATURE_CUS=n overrides (0: all CUs).  (A CU-masked stream cannot be created non-blocking: it synchronises with the NULL
-            // stream like any default-flag stream -- this library never uses the NULL stream.)
+            // stream like any default-flag stream.  The library's own streams are never the NULL stream; a caller may put the tracking chain there
+            // (lvt_amd_set_stream(h, NULL)).  Every launch of the masked stream then also waits for the NULL-stream work enqueued before it, and every
+            // launch on the NULL stream for the masked stream's earlier work: edges from later to earlier work only, as every gate's wait is
+            // (lvt_handover.h) -- no wait can come to depend on work queued behind it.  DESIGN.md section 2, "A caller's stream".)
             int ncu = 0;
             if (B >= 2 && B <= 28) {
                 int total = 0;
@@ -997,6 +1013,11 @@ static void enqueue_frame(Context *c) {
     const int ext = (B == 1) ? fa[0].ext_corners : 0;  // (a pool's step may mix seats with and without external corners: k_cells is launched, cell_begin skips the seats that bring their own)
     hipStream_t sf = c->stream_f, st = c->stream;
     for (int i = 0; i < Context::PROF_SLOTS; i++) c->ev_used[i] = false;
+    // ---- a caller's stream: the step's planes were written by work the caller enqueued there -- the feature stage, their only reader outside `st` itself, waits for it
+    if (!c->own_stream) {
+        (void)hipEventRecord(c->ev_caller, st);
+        (void)hipStreamWaitEvent(sf, c->ev_caller, 0);
+    }
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
     // ---- the frame properties' launches at its head, ahead of the buffer gate (lvt_frame_props.h: why stream order alone covers each hand-over).  They point the
     //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
@@ -1648,8 +1669,11 @@ LVT_API void lvt_amd_set_stream(lvt_handle h, void *hip_stream) {
     Context *c = static_cast<Context *>(h);
     DeviceGuard guard(c);
     try {
-        drain(c);
+        drain(c);  // the frames in flight are collected on the stream they were enqueued on ...
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // ... and what k_triangulate does behind a record's delivery has ended: nothing of this handle runs on the old stream
+        if (!c->ev_caller) HIPCHK(c, hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));  // (refused: the handle stays on the stream it had)
         if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+        // hip_stream == NULL is the legacy default stream (what torch.cuda.current_stream().cuda_stream is on torch's default stream), for a batch as well: see create_context
         c->stream = static_cast<hipStream_t>(hip_stream);
         c->own_stream = false;
     } catch (...) {

@@ -9,8 +9,9 @@ converting in front of the tracker.  Writes profiles/colour_frames.md.
               gray:   the same sequence as gray frames through a gray handle: what colour costs over gray (3x the bytes over PCIe, one more launch).
               + the host conversion alone, per frame, on one core.
   rgbd_dev    colour planes resident in HBM, three in flight.  new: the colour handle reads them in place (lvt_amd_track_rgbd_device_async).
-              caller: a torch integer expression into a pitched gray plane on the caller's stream, an event the host waits for (the tracker's streams are
-              its own), then the same call on a gray handle.
+              caller: a torch integer expression into a pitched gray plane on the caller's stream, an event the host waits for (this leg's handle keeps its
+              private streams, which are ordered behind nothing of the caller's; lvt_amd_set_stream would order it behind the caller's stream without the
+              host wait, at the price of the feature stage's overlap), then the same call on a gray handle.
   kgray       the k_gray_frames launch as lvt_amd_profile_read reports it (HIP events around the launch), 100 synchronous frames.
   plain       handles that never set a format, both libraries: the stereo headline route (lvt_amd_track_async, KITTI-shaped) and the TUM-shaped RGB-D
               route (lvt_amd_track_rgbd16_async, gray).  The feature must cost them nothing.

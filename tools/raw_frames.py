@@ -6,7 +6,8 @@ against the route the PARENT commit offered, the rectifier as a side tool in fro
               new: lvt_track on raw frames.  parent: 2 x lvt_amd_rectify + lvt_track.
   async_dev   one handle, frames/s, raw planes in HBM, three in flight.
               new: raw lvt_amd_track_device_async.  parent: 2 x lvt_amd_rectify_device on a caller stream + event + lvt_amd_track_device_async
-              (the tracker's streams are its own: the caller waits for the event on the host).
+              (this leg's handle keeps its private streams, ordered behind nothing of the caller's: the caller waits for the event on the host;
+              lvt_amd_set_stream would order the handle behind the caller's stream instead, at the price of the feature stage's overlap).
   async_host  one handle, frames/s, host frames, three in flight.
               new: raw lvt_amd_track_async.  parent: 2 x lvt_amd_rectify to host, then lvt_amd_track_async.
   batch16     a lock-step batch of 16, aggregate frames/s, three steps in flight.
