@@ -551,6 +551,115 @@ LVT_API int lvt_amd_pose_info_eval(const lvt_amd_params *p, const double q_wxyz[
                                    lvt_amd_pose_info *out);
 LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3], double cov_ros[36]);
 
+/* ---- RELOCALISATION: recover a LOST tracker against its kept map ------------------------------------------------------------------------------
+ * The tracker latches LOST at its first frame with fewer than min_num_matches_for_tracking matches and returns the last pose from then on; the reference's
+ * only way out is a reset, which throws the map away.  But a LOST tracker keeps its map, and the feature stage goes on running.  lvt_amd_relocalise is an
+ * explicit call BETWEEN frames on a quiet handle, modelled on lvt_amd_snapshot_apply: it searches the kept map for the last frame handed in -- the frame
+ * lvt_amd_get_features answers for -- with no pose prior, decides whether the result is good enough, and commits the new state; the next frame tracks on
+ * from it in the old map's coordinates.  Any state is accepted (TRACKING, or LOST after any number of frames) as long as the map holds a point; a snapshot
+ * applied in a later session followed by a relocalisation on the first frame continues in the snapshot's coordinates.  Nothing in the per-frame launch
+ * chain changes: a handle that never calls it allocates and launches exactly what it did, and snapshots keep their bytes.
+ * The stages are entry points of their own as well, in the style of lvt_amd_hamming_match_batched and lvt_amd_pnp: the global descriptor match (stage 1)
+ * and hypotheses, scoring and refinement (stages 3 - 5) on correspondences the caller has formed.  The claim is equality with THIS text;
+ * tests/reloc_util.py restates it in numpy.
+ *  Arithmetic.  The 32-bit floats of the observations and the parameters are widened to fp64, everything after that is fp64: one IEEE operation per written
+ *  operation, correctly rounded division and square root, only + - * / sqrt, sums of three in the order ((a b + c d) + e f).  A comparison that involves a NaN
+ *  is false.
+ *   1. Global match.  For every query descriptor i < n_query the two nearest of ALL n_map map descriptors by Hamming distance, ties to the lowest map index
+ *      (cv::BFMatcher::knnMatch with k = 2 and no mask).  No position predicate.  The record is (idx1, d1, idx2, d2), -1 / INT_MAX where there is none.
+ *      On a handle: the queries are the N left features of the last frame, the map the M = map_n points of the live copy (both read on the device, M clamped
+ *      to the capacity).  A feature is ACCEPTED by the tracker's own rule with cnt = min(M, 2): d1 / d2 < tracking_ratio_test_threshold in fp32 (so 0 / 0
+ *      fails) for cnt = 2, d1 <= descriptor_matching_threshold for cnt = 1.  n_matched counts the accepted features.
+ *   2. Correspondences.  A map point claimed by several accepted features keeps the one with the smallest (d1, i).  The survivors, ordered by feature index,
+ *      are the correspondences c = 0 ... n_corr - 1: the map point's position X, the feature's (u, v) = its stored coordinates (undistorted for RGB-D) and a
+ *      camera-frame point Pc, or none.
+ *        RGB-D: Z = the depth the feature stage kept for the feature (inside the near and far planes).
+ *        Stereo: the partner among the right features j with (float)max((int)y_l - 2, 0) <= y_r <= (float)min((int)y_l + 2, img_height) and
+ *          x_l - x_r >= min_disparity in fp32: the top two by Hamming distance (ties to the lowest j), accepted by the tracker's rule with
+ *          triangulation_ratio_test_threshold and cnt = min(candidates, 2).  No exclusivity between left features: this is a hypothesis generator, not the
+ *          row matcher.  Z = (fx baseline) / (x_l - x_r).
+ *        Pc = (((x - cx) Z) / fx, ((y - cy) Z) / fy, Z).
+ *      The correspondences with a point, in order, are numbered 0 ... n3 - 1 (n_with_point).  n3 < 3: status 1.
+ *      (The stage entry lvt_amd_reloc_solve takes the caller's correspondences: X, (u, v), Pc and has_pc.)
+ *   3. Hypotheses.  For h = 0 ... n_hypotheses - 1 and j = 0, 1, 2:  x = seed + (3 h + j + 1) 0x9E3779B97F4A7C15 mod 2^64, then the splitmix64 finaliser
+ *      x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB, x ^= x >> 31; sample j is number (x mod n3) of the correspondences with a
+ *      point.  With a_k = Pc and b_k = X of the three samples, the triad of either set is
+ *          d = p1 - p0, n1 = (dx dx + dy dy) + dz dz, e1 = d / sqrt(n1);   c = e1 x (p2 - p0), n3 = (cx cx + cy cy) + cz cz, e3 = c / sqrt(n3);   e2 = e3 x e1
+ *      with (a x b) = (ay bz - az by, az bx - ax bz, ax by - ay bx), and
+ *          R[i][j] = (e1b[i] e1a[j] + e2b[i] e2a[j]) + e3b[i] e3a[j]      (camera to world)
+ *          mean(p) = ((p0 + p1) + p2) / 3,     t[i] = mean(b)[i] - ((R[i][0] ma[0] + R[i][1] ma[1]) + R[i][2] ma[2])
+ *      A hypothesis scores 0 when two of its samples coincide, or when n1 <= 1e-12 or n3 <= 1e-12 in either set.
+ *   4. Score.  For EVERY correspondence, with or without a Pc:  dx = X - t;  pc[j] = (R[0][j] dx[0] + R[1][j] dx[1]) + R[2][j] dx[2];
+ *          e = ((fx pcx) / pcz + cx - u, (fy pcy) / pcz + cy - v);   an inlier iff pcz > 0 and ex ex + ey ey <= gate_px2.
+ *      The best hypothesis has the largest count, ties to the lowest h.  A count below the success count max(min_inliers, min_num_matches_for_tracking):
+ *      status 2.
+ *   5. Refine.  The inliers of the best hypothesis, in correspondence order, are the edges; the start pose is (quaternion of R, t), the quaternion by the
+ *      branch on the trace / largest diagonal element the odometry accumulator uses.  The solver is the pose refinement of the frame path, the code behind
+ *      lvt_amd_pnp.  n_refined_inliers is what LVT_AMD_C_PNP_INLIERS counts for a frame; below the success count, or a pose that is not finite: status 3.
+ *   6. Commit (status 0, and not dry_run).  The sequence's control record becomes its own with: state TRACKING; the last and the optimised pose = the refined
+ *      pose, the returned R, t and status to match; the motion model at rest at that pose (last pose = it, angular velocity the identity quaternion, linear
+ *      velocity 0, nothing pending); last_matches = {n, n, n} with n = n_refined_inliers; no early-stream work carried (the first frame afterwards is matched
+ *      entirely on the tracking stream); the stream hand-over words of a just-reset record, as a snapshot apply writes them.  The frame number, the map with its
+ *      counters and ages and the staged set stay as they were.  lvt_get_status, lvt_amd_get_pose, lvt_amd_get_last_pose and lvt_amd_get_counts answer from the
+ *      new state at once; the pose-uncertainty record has status 0 until the next tracked frame.  On status 1 ... 3 and on every dry_run not one byte of the
+ *      sequence's state changes; lvt_amd_get_matches still answers for the last frame either way (the solver runs on buffers of the call's own).
+ *  - lvt_amd_relocalise / lvt_amd_batch_relocalise (one sequence of a uniform or mixed batch; its neighbours are untouched): 0 for status 0, 1 for status
+ *    1 ... 3 (nothing was changed), -1 for a refusal: the complete sentence is in lvt_amd_last_error and ends in "(nothing was changed)".  Refused, in this
+ *    order: a bad handle; a pooled or automatic seat; the batch call on a solo handle and the reverse; seq out of range; a bad config field; frames in flight
+ *    (collect every frame first); a handle that has not seen a frame; an empty map; a last frame that was skipped, absent or poisoned (it has no features).
+ *    A HIP failure inside the call is outside that contract: -1, the HIP error's text in lvt_amd_last_error, `out` unwritten.
+ *    Seven launches and the commit on the handle's tracking stream, ONE stream synchronisation, one read-back of the result record; the buffers are allocated
+ *    by the first call.
+ *  - lvt_amd_reloc_config: n_hypotheses 1 ... 1024; gate_px2 and min_disparity finite and > 0; min_inliers >= 3; dry_run 0 or 1.  A field out of range is
+ *    refused (-1, the sentence names the field and ends in "(nothing was changed)"; these calls have no handle: lvt_amd_last_error(NULL) has it).
+ *    lvt_amd_reloc_solve checks min_disparity and dry_run and does not use them.
+ *  - lvt_amd_reloc_result: status 0 = a pose, 1 = fewer than 3 correspondences with a camera-frame point, 2 = the best hypothesis is below the success count,
+ *    3 = the refined pose is not finite or its inliers fall below the success count.  The pose (camera-to-world, as lvt_track returns it) is filled for status
+ *    0 and 3 and zero otherwise.  n_features, n_map and n_matched belong to a handle's call; the stage entry leaves them zero.
+ *  - lvt_amd_reloc_match_device: stage 1 on DEVICE pointers aligned to 16 bytes: d_query n_query x 32 bytes, d_map n_map x 32 bytes, d_out n_query x 4 int32;
+ *    n_query 0 ... 4096, n_map 0 ... 32768.  The map is cut into slices of lvt_amd_reloc_slice_length(n_map) points (32 ... 1024, about 32 slices), a
+ *    workgroup holds one slice in LDS.  Two launches on hip_stream; the call allocates its key buffer and frees it after synchronising that stream.  Returns
+ *    the time between HIP events around the launches in microseconds, < 0 on a refusal or failure.  Environment, read by this entry alone: LVT_AMD_RELOC_MATCH=uniform
+ *    runs the variant that loads the slice's descriptors straight from memory at a wave-uniform address instead of staging them in LDS (same records; for
+ *    measurements, profiles/relocalisation.md).
+ *  - lvt_amd_reloc_solve: stages 3 - 5 on HOST pointers: pts n x 3 f64, obs n x 2 f32, pc n x 3 f64, has_pc n bytes, 0 <= n <= 4096; of `p` the intrinsics
+ *    and min_num_matches_for_tracking are read.  counts_out (n_hypotheses ints), inliers_out (n ints; the first n_hyp_inliers are written), hyp_R (9,
+ *    row-major) and hyp_t (3) -- the best hypothesis, status 0 and 3 only -- may each be NULL.  Returns 0 for status 0, 1 for status 1 ... 3, -1 on a refusal. */
+typedef struct lvt_amd_reloc_config {
+    int      n_hypotheses;    /* 256 */
+    float    gate_px2;        /* 16.0: the scoring gate in px^2 */
+    float    min_disparity;   /* 1.0 */
+    int      min_inliers;     /* 30 */
+    uint64_t seed;            /* 0 */
+    int      dry_run;         /* 0 */
+    int      reserved;
+} lvt_amd_reloc_config;
+typedef struct lvt_amd_reloc_result {
+    int status;
+    int n_features, n_map, n_matched, n_corr, n_with_point;
+    int best_hypothesis, n_hyp_inliers, n_refined_inliers;
+    int reserved;
+    double q_wxyz[4], p[3];
+    double R[3][3], t[3];
+} lvt_amd_reloc_result;
+#define LVT_AMD_RELOC_CONFIG_SIZE 32
+#define LVT_AMD_RELOC_RESULT_SIZE 192
+#ifdef __cplusplus
+static_assert(sizeof(lvt_amd_reloc_config) == LVT_AMD_RELOC_CONFIG_SIZE && sizeof(lvt_amd_reloc_result) == LVT_AMD_RELOC_RESULT_SIZE,
+              "the relocalisation records are part of the ABI");
+#else
+_Static_assert(sizeof(lvt_amd_reloc_config) == LVT_AMD_RELOC_CONFIG_SIZE && sizeof(lvt_amd_reloc_result) == LVT_AMD_RELOC_RESULT_SIZE,
+               "the relocalisation records are part of the ABI");
+#endif
+LVT_API int lvt_amd_relocalise(lvt_handle h, const lvt_amd_reloc_config *cfg /* NULL = defaults */, lvt_amd_reloc_result *out);
+LVT_API int lvt_amd_batch_relocalise(lvt_handle h, int seq, const lvt_amd_reloc_config *cfg, lvt_amd_reloc_result *out);
+LVT_API void lvt_amd_reloc_default_config(lvt_amd_reloc_config *cfg);
+LVT_API int lvt_amd_reloc_slice_length(int n_map);
+LVT_API float lvt_amd_reloc_match_device(const void *d_query, int n_query, const void *d_map, int n_map, void *d_out, void *hip_stream);
+LVT_API int lvt_amd_reloc_solve(const lvt_amd_params *p, const lvt_amd_reloc_config *cfg /* NULL = defaults */, const double *pts, const float *obs,
+                                const double *pc, const uint8_t *has_pc, int n, int *counts_out, int *inliers_out, double *hyp_R, double *hyp_t,
+                                lvt_amd_reloc_result *out);
+
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without
  * ROS: poses are re-expressed in an x-forward / z-up frame (rot_fix = Rz(-pi/2) Rx(-pi/2)), the frame-to-frame delta is moved
@@ -566,6 +675,14 @@ typedef void *lvt_amd_odometry;
 LVT_API lvt_amd_odometry lvt_amd_odometry_create(lvt_handle h, const double base_to_sensor[12] /* 3x4 row-major or NULL */, int reset_pose_on_lost);
 LVT_API void lvt_amd_odometry_destroy(lvt_amd_odometry o);
 LVT_API void lvt_amd_odometry_reset(lvt_amd_odometry o); /* the node's reset_vo service (lvt_ros.cpp:184-198): tracker reset, deltas restart, accumulated pose back to identity */
+/* RELOCALISATION POLICY.  Once set (max_lost_frames > 0), a frame that comes back LOST makes the accumulator call lvt_amd_relocalise on its tracker instead of
+ * resetting it.  On success the relocalised pose is pushed and 1 is returned: last_R / last_p are still those of the last tracked frame, so the published delta
+ * spans the gap and the trajectory stays continuous.  On failure (also: an accumulator without a tracker) nothing is published and nothing is reset -- the map
+ * stays --; the max_lost_frames-th consecutive failure falls back to the reference's reset, exactly as without the policy.  cfg NULL: the default config;
+ * max_lost_frames <= 0: the policy is off and the accumulator behaves as it always did.  0; -1: a bad config field, dry_run = 1 included -- the accumulator's
+ * relocalisation commits -- (the sentence in lvt_amd_last_error(NULL)).  lvt_amd_odometry_push_pose_cov / _update_cov: cov_out is all zero for a frame the
+ * policy relocalised (cov_in and the perturbation map belong to the LOST frame handed in, not to the pose that was published). */
+LVT_API int lvt_amd_odometry_set_relocalisation(lvt_amd_odometry o, const lvt_amd_reloc_config *cfg, int max_lost_frames);
 LVT_API int lvt_amd_odometry_push_pose(lvt_amd_odometry o, const double R[3][3], const double t[3], int status, double stamp_sec,
                                        double pose_out[7], double twist_out[6]);
 LVT_API int lvt_amd_odometry_update(lvt_amd_odometry o, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double stamp_sec,

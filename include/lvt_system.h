@@ -304,6 +304,15 @@ class lvt_system {
         m_bpp = (format == LVT_AMD_PIX_GRAY8) ? 1 : (format >= LVT_AMD_PIX_BGRA8 ? 4 : 3);
         return true;
     }
+    /* ADDITIVE: relocalisation (include/lvt_amd_ext.h, RELOCALISATION): search the kept map for the last frame handed in, with no pose prior.  true: relocalised
+     * and (unless cfg->dry_run) committed -- get_state() is eState_TRACKING, the next track() goes on from the returned pose; false: not this frame (out->status
+     * 1 ... 3, nothing was changed) or refused (last_error() says why).  cfg NULL: the defaults; out may be NULL. */
+    bool relocalise(const lvt_amd_reloc_config *cfg = nullptr, lvt_amd_reloc_result *out = nullptr) {
+        lvt_amd_reloc_result r;
+        const bool ok = lvt_amd_relocalise(m_handle, cfg, out ? out : &r) == 0;
+        if (ok && !(cfg && cfg->dry_run)) m_state = eState_TRACKING;
+        return ok;
+    }
     /* ADDITIVE: pose uncertainty (include/lvt_amd_ext.h, POSE UNCERTAINTY).  enable_pose_info(): from the next frame on every tracked frame carries an
      * lvt_amd_pose_info -- the information matrix of its 2D-3D edges at the returned pose and its inverse, a 6 x 6 covariance for unit pixel noise in
      * the order (position on world axes, rotation on camera axes).  false: refused (frames in flight; last_error() says why), nothing changed.

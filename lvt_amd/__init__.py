@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
+    "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve",
 ]
 
 N_COUNTS = 32
@@ -211,6 +212,14 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes, restype in (   # (relocalisation: likewise)
+            ("lvt_amd_relocalise", [vp, vp, vp], C.c_int), ("lvt_amd_batch_relocalise", [vp, C.c_int, vp, vp], C.c_int),
+            ("lvt_amd_odometry_set_relocalisation", [vp, vp, C.c_int], C.c_int), ("lvt_amd_reloc_default_config", [vp], None), ("lvt_amd_reloc_slice_length", [C.c_int], C.c_int),
+            ("lvt_amd_reloc_match_device", [vp, C.c_int, vp, C.c_int, vp, vp], C.c_float),
+            ("lvt_amd_reloc_solve", [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp], C.c_int)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
     L.lvt_amd_get_debug.argtypes = [vp, vp]
     L.lvt_amd_get_host_stats.argtypes = [vp, vp]
     L.lvt_amd_profile_read.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, vp]
@@ -390,6 +399,112 @@ def pose_info_to_ros(cov, R) -> np.ndarray:
     return out.reshape(6, 6)
 
 
+RELOC_CONFIG_SIZE, RELOC_RESULT_SIZE = 32, 192   # LVT_AMD_RELOC_CONFIG_SIZE / _RESULT_SIZE: pinned in the header too
+
+
+class RelocConfig(C.Structure):
+    """lvt_amd_reloc_config (include/lvt_amd_ext.h, RELOCALISATION): n_hypotheses 1 ... 1024, gate_px2 and min_disparity finite and > 0, min_inliers >= 3"""
+    _fields_ = [("n_hypotheses", C.c_int), ("gate_px2", C.c_float), ("min_disparity", C.c_float), ("min_inliers", C.c_int), ("seed", C.c_uint64),
+                ("dry_run", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, n_hypotheses=256, gate_px2=16.0, min_disparity=1.0, min_inliers=30, seed=0, dry_run=0):
+        super().__init__(int(n_hypotheses), float(gate_px2), float(min_disparity), int(min_inliers), int(seed), int(dry_run), 0)
+
+    def __repr__(self):
+        return (f"RelocConfig(n_hypotheses={self.n_hypotheses}, gate_px2={self.gate_px2}, min_disparity={self.min_disparity}, "
+                f"min_inliers={self.min_inliers}, seed={self.seed}, dry_run={self.dry_run})")
+
+
+class RelocResult(C.Structure):
+    """lvt_amd_reloc_result: status 0 = a pose, 1 = fewer than 3 correspondences with a camera-frame point, 2 = the best hypothesis is below the success
+    count, 3 = the refined pose is not finite or below the success count; the pose (camera-to-world) is filled for status 0 and 3"""
+    _fields_ = [("status", C.c_int), ("n_features", C.c_int), ("n_map", C.c_int), ("n_matched", C.c_int), ("n_corr", C.c_int), ("n_with_point", C.c_int),
+                ("best_hypothesis", C.c_int), ("n_hyp_inliers", C.c_int), ("n_refined_inliers", C.c_int), ("reserved", C.c_int),
+                ("_q", C.c_double * 4), ("_p", C.c_double * 3), ("_R", C.c_double * 9), ("_t", C.c_double * 3)]
+
+    @property
+    def q(self) -> np.ndarray:
+        return np.array(self._q, dtype=np.float64)
+
+    @property
+    def p(self) -> np.ndarray:
+        return np.array(self._p, dtype=np.float64)
+
+    @property
+    def R(self) -> np.ndarray:
+        return np.array(self._R, dtype=np.float64).reshape(3, 3)
+
+    @property
+    def t(self) -> np.ndarray:
+        return np.array(self._t, dtype=np.float64)
+
+
+assert C.sizeof(RelocConfig) == RELOC_CONFIG_SIZE and C.sizeof(RelocResult) == RELOC_RESULT_SIZE
+
+
+def _reloc_config(cfg, kw) -> RelocConfig:
+    if cfg is not None and kw:
+        raise TypeError("either a RelocConfig or its fields as keywords, not both")
+    if cfg is not None and not isinstance(cfg, RelocConfig):
+        raise TypeError("cfg is a RelocConfig")
+    return cfg if cfg is not None else RelocConfig(**kw)
+
+
+def _relocalise(handle, seq, cfg, kw):
+    """the RelocResult of lvt_amd_relocalise (seq None) / lvt_amd_batch_relocalise (status 0: relocalised); a refusal raises ValueError with the library's sentence"""
+    L = load_library()
+    cfg = _reloc_config(cfg, kw)
+    res = RelocResult()
+    rc = L.lvt_amd_relocalise(handle, C.byref(cfg), C.byref(res)) if seq is None else L.lvt_amd_batch_relocalise(handle, int(seq), C.byref(cfg), C.byref(res))
+    if rc < 0:
+        raise ValueError((L.lvt_amd_last_error(handle) or b"").decode())
+    return res
+
+
+def reloc_default_config() -> RelocConfig:
+    """lvt_amd_reloc_default_config: the library's own defaults (host code: needs the library, not a GPU)"""
+    cfg = RelocConfig(0, 0.0, 0.0, 0, 0, 0)
+    load_library().lvt_amd_reloc_default_config(C.byref(cfg))
+    return cfg
+
+
+def reloc_slice_length(n_map: int) -> int:
+    """points per slice the global matcher cuts a map of n_map points into (host code)"""
+    return int(load_library().lvt_amd_reloc_slice_length(int(n_map)))
+
+
+def reloc_match_device(q_desc, t_desc, out, stream: int = 0) -> float:
+    """stage 1 of the relocalisation alone on DEVICE tensors (torch): q_desc (N, 32) u8, t_desc (M, 32) u8, out (N, 4) i32 = (idx1, d1, idx2, d2), -1 / INT_MAX
+    where there is none.  Returns the time of the two launches in us."""
+    L = load_library()
+    us = L.lvt_amd_reloc_match_device(C.c_void_p(q_desc.data_ptr()), int(q_desc.shape[0]), C.c_void_p(t_desc.data_ptr()), int(t_desc.shape[0]),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+    if us < 0:
+        raise RuntimeError("lvt_amd_reloc_match_device failed: " + (L.lvt_amd_last_error(None) or b"").decode())
+    return us
+
+
+def reloc_solve(params: LvtParameters, pts, obs, pc, has_pc, cfg: RelocConfig = None):
+    """stages 3 - 5 of the relocalisation alone on caller data: pts n x 3 (world), obs n x 2 float32, pc n x 3 (camera frame), has_pc n bool.  Returns
+    (RelocResult, counts (n_hypotheses,), inliers of the best hypothesis, hyp_R (3, 3), hyp_t (3,)); the last two are zero unless status is 0 or 3.
+    A refusal raises ValueError with the library's sentence."""
+    L = load_library()
+    pod = params.to_pod()
+    cfg = cfg if cfg is not None else RelocConfig()
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3); obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 2)
+    pc = np.ascontiguousarray(pc, np.float64).reshape(-1, 3); has = np.ascontiguousarray(has_pc, np.uint8).reshape(-1)
+    n = len(pts)
+    if not (len(obs) == len(pc) == len(has) == n):
+        raise ValueError("one observation, one camera-frame point and one flag per world point")
+    counts = np.zeros(max(int(cfg.n_hypotheses), 1), np.int32); inl = np.zeros(max(n, 1), np.int32); hR = np.zeros(9); ht = np.zeros(3)
+    res = RelocResult()
+    rc = L.lvt_amd_reloc_solve(C.byref(pod), C.byref(cfg), _p(pts) if n else None, _p(obs) if n else None, _p(pc) if n else None, _p(has) if n else None, n,
+                               _p(counts), _p(inl), _p(hR), _p(ht), C.byref(res))
+    if rc < 0:
+        raise ValueError((L.lvt_amd_last_error(None) or b"").decode())
+    return res, counts[:cfg.n_hypotheses].copy(), inl[:max(res.n_hyp_inliers, 0) if res.status in (0, 3) else 0].copy(), hR.reshape(3, 3), ht
+
+
 def _params_of(pod):
     return LvtParameters(**{n: getattr(pod, n) for n, _ in ParamsPOD._fields_ if n in LvtParameters.__dataclass_fields__})
 
@@ -515,6 +630,11 @@ class LvtSystem:
     def restore(self, snap: Snapshot) -> int:
         """replace this system's whole state by the snapshot's: the next frame continues the snapshot's trajectory.  0: done; -1: refused (last_error())"""
         return load_library().lvt_amd_snapshot_apply(self._h, 0, snap._h if snap is not None else None)
+
+    def relocalise(self, cfg: RelocConfig = None, **kw) -> RelocResult:
+        """lvt_amd_relocalise: search the kept map for the last frame handed in, with no pose prior; status 0 = relocalised (and, unless dry_run, committed:
+        the next frame tracks on from the returned pose).  Keywords are RelocConfig fields.  A refusal raises ValueError with the library's sentence."""
+        return _relocalise(self._h, None, cfg, kw)
 
     def get_sensor_type(self):
         return self._sensor
@@ -901,6 +1021,10 @@ class LvtBatch:
         arr = (C.c_void_p * self.B)(*[None if x is None else x._h for x in snaps])
         return load_library().lvt_amd_batch_snapshot_apply(self._h, arr)
 
+    def relocalise(self, seq: int, cfg: RelocConfig = None, **kw) -> RelocResult:
+        """lvt_amd_batch_relocalise: LvtSystem.relocalise for sequence seq alone; its neighbours are untouched"""
+        return _relocalise(self._h, seq, cfg, kw)
+
     def reset(self, seq: int) -> int:
         """lvt_system::reset for sequence `seq` alone (drains first).  0: done; -1: refused (last_error())"""
         return load_library().lvt_amd_batch_reset(self._h, int(seq))
@@ -1073,6 +1197,14 @@ class Odometry:
         if rc < 0:
             raise ValueError("bad arguments")
         return (pose, twist) if rc == 1 else None
+
+    def set_relocalisation(self, cfg: RelocConfig = None, max_lost_frames: int = 10, **kw) -> int:
+        """lvt_amd_odometry_set_relocalisation: on a LOST frame relocalise the tracker instead of resetting it; after max_lost_frames failures in a row the
+        reference's reset.  max_lost_frames <= 0 turns the policy off.  A bad config field raises ValueError with the library's sentence."""
+        L = load_library()
+        if L.lvt_amd_odometry_set_relocalisation(self._h, C.byref(_reloc_config(cfg, kw)), int(max_lost_frames)) != 0:
+            raise ValueError((L.lvt_amd_last_error(None) or b"").decode())
+        return 0
 
     def push_pose(self, R, t, status, stamp):
         """returns (pose[x y z qx qy qz qw], twist[6]) or None (LOST -> reset, or a stale time stamp)"""

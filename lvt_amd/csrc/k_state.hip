@@ -88,10 +88,10 @@ static_assert(sizeof(Ctl) % 4 == 0 && offsetof(Ctl, pnp_seq) % 4 == 0 && offseto
 inline ChainWords chain_of(const Ctl &z) {
     return ChainWords{z.pnp_seq, z.gate_ok, z.early_ran_seq, z.early_state, z.track_done_seq, z.late_gate_seq, z.gate_timeouts, z.gate_fatal, z.skip};
 }
-inline void set_chain(Ctl &k, const ChainWords &c) {  // (host: the record an apply leaves in the host ring)
+__host__ __device__ inline void set_chain(Ctl &k, const ChainWords &c) {  // (the record an apply leaves in the host ring; a relocalisation's commit on either side)
     k.pnp_seq = c.pnp_seq, k.gate_ok = c.gate_ok, k.early_ran_seq = c.early_ran_seq, k.early_state = c.early_state, k.track_done_seq = c.track_done_seq;
     k.late_gate_seq = c.late_gate_seq, k.gate_timeouts = c.gate_timeouts, k.gate_fatal = c.gate_fatal, k.skip = c.skip;
-    std::memset(k.dbg, 0, sizeof(k.dbg));
+    for (unsigned i = 0; i < sizeof(k.dbg) / sizeof(k.dbg[0]); i++) k.dbg[i] = 0;
 }
 inline ChainWordsArg chain_arg(const ChainWords &c) {
     ChainWordsArg a;

@@ -2230,7 +2230,11 @@ __global__ __launch_bounds__(1024) void k_triangulate(SeqArg<BV> sa, int par, se
         }
         // LOST: no features as far as any caller can see.  (Not for a pooled handle's idle step: the buffer still holds its last real frame's features.)
         const bool idle = ctl.skip && S.fb[par].fc->absent;  // (no frame for this sequence in this step: its counters stay its last frame's, frame_prologue)
-        if (!ctl.active && !idle) *S.fb[par].feat[0].n = *S.fb[par].feat[1].n = 0;
+        if (!ctl.active && !idle) {
+            FeatCtl &fc = *S.fb[par].fc;  // (the counts stay with the buffer for a relocalisation: FeatCtl::lost_n)
+            fc.lost_n[0] = *S.fb[par].feat[0].n, fc.lost_n[1] = *S.fb[par].feat[1].n, fc.lost_seq = seq;
+            *S.fb[par].feat[0].n = *S.fb[par].feat[1].n = 0;
+        }
         if (!idle) {
             ctl.counts[C_N_LEFT] = *S.fb[par].feat[0].n;
             ctl.counts[C_N_RIGHT] = *S.fb[par].feat[1].n;

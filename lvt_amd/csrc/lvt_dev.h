@@ -151,6 +151,14 @@ struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one
     seq_t skip_seq;     // ... and this frame (sequence number) has no features: the tracking chain skips it
     seq_t feat_seq;  // sequence number of the frame whose features this buffer holds, published by k_feat_done (polled by k_gate)
     FrameIn in;      // this frame's inputs (beside `poison`, the word every feature kernel loads first)
+    // a LOST frame's features are nobody's to see (the frame's epilogue zeroes Feat::n), but the arrays still hold them: their counts, and the frame they
+    // belong to, are kept here for a relocalisation (k_reloc.hip).  Valid only while lost_seq == feat_seq, i.e. while the buffer still holds that frame's
+    // features: nothing clears it -- not a reset (the map is empty then, the call is refused), not a snapshot apply (the buffer still is the target's last
+    // frame, which a relocalisation right behind the apply is meant to use).  The LOST branch also runs for a skipped or poisoned frame, whose count is
+    // garbage: those are caught by skip_seq == feat_seq (k_reloc_corr) before anything changes, and every count is clamped to NF_MAX where it is read.  A frame
+    // skipped through gate_fatal WITHOUT skip_seq set is not caught.
+    int lost_n[2];
+    seq_t lost_seq;
 };
 
 struct Feat {  // one image's lvt_image_features_struct (lvt_image_features_struct.h:62-80), SoA

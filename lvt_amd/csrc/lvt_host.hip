@@ -23,6 +23,7 @@
 #include "k_equalise.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
+#include "k_reloc.hip"
 #include "lvt_odometry.h"
 
 #include <atomic>
@@ -319,6 +320,7 @@ struct Context {
     int depth_cols() const { return has_depth_cam(0) ? depth_cam[0].width : prm.W; }
     size_t depth_cap = 0, depth_ring_cap = 0;     // pixels d_depth[] / d_depth_ring[] hold
     int pitch = 0;
+    RelocBufs reloc{};             // relocalisation: the call's own buffers (allocated by the first call; reloc.work == nullptr before it)
     int *d_snap_status = nullptr;  // snapshots: [B][4] map_cur, map_n, staged_cur, staged_n as k_state_pack found them (allocated by the first take)
     long enq = 0, done = 0;    // frames enqueued / collected
     long delivered = 0;        // frames whose record delivery has been enqueued (k_triangulate, the next frame's k_gate_late, or k_deliver)
@@ -2933,6 +2935,144 @@ LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3]
     sandwich6(M, cov, cov_ros);
 }
 
+// ---- relocalisation: the stages alone on caller data (k_reloc.hip; the definition is in include/lvt_amd_ext.h, "RELOCALISATION") -------------------
+LVT_API void lvt_amd_reloc_default_config(lvt_amd_reloc_config *cfg) {
+    if (!cfg) return;
+    *cfg = lvt_amd_reloc_config{};
+    cfg->n_hypotheses = 256, cfg->gate_px2 = 16.0f, cfg->min_disparity = 1.0f, cfg->min_inliers = 30, cfg->seed = 0, cfg->dry_run = 0;
+}
+// "" when every field is in range, else the complete sentence of the refusal (it names the field)
+static std::string reloc_config_fault(const lvt_amd_reloc_config &c) {
+    char b[200] = "";
+    if (c.n_hypotheses < 1 || c.n_hypotheses > RELOC_HYP_MAX)
+        snprintf(b, sizeof b, "n_hypotheses is %d: it must be 1 ... %d (nothing was changed)", c.n_hypotheses, RELOC_HYP_MAX);
+    else if (!(std::isfinite(c.gate_px2) && c.gate_px2 > 0))
+        snprintf(b, sizeof b, "gate_px2 is %g: it must be finite and > 0 (nothing was changed)", (double)c.gate_px2);
+    else if (!(std::isfinite(c.min_disparity) && c.min_disparity > 0))
+        snprintf(b, sizeof b, "min_disparity is %g: it must be finite and > 0 (nothing was changed)", (double)c.min_disparity);
+    else if (c.min_inliers < 3)
+        snprintf(b, sizeof b, "min_inliers is %d: it must be >= 3 (nothing was changed)", c.min_inliers);
+    else if (c.dry_run != 0 && c.dry_run != 1)
+        snprintf(b, sizeof b, "dry_run is %d: it must be 0 or 1 (nothing was changed)", c.dry_run);
+    return b;
+}
+LVT_API int lvt_amd_reloc_slice_length(int n_map) { return reloc_slice_length(std::max(n_map, 0)); }
+// stage 1 alone.  d_query n_query x 32 B, d_map n_map x 32 B, d_out n_query x 4 int32 (idx1, d1, idx2, d2; -1 / INT_MAX when absent): DEVICE pointers, 16-byte
+// aligned.  Both launches go to hip_stream; the call allocates its key buffer and frees it after synchronising that stream.  Returns the elapsed time of the
+// two launches in microseconds (HIP events), < 0 on a refusal or a HIP failure (lvt_amd_last_error(NULL) has the sentence of a refusal).
+LVT_API float lvt_amd_reloc_match_device(const void *d_query, int n_query, const void *d_map, int n_map, void *d_out, void *hip_stream) {
+    if (n_query < 0 || n_query > NF_MAX || n_map < 0 || n_map > MAP_MAX || (n_query > 0 && (!d_query || !d_out)) || (n_map > 0 && n_query > 0 && !d_map) ||
+        ((uintptr_t)d_query | (uintptr_t)d_map | (uintptr_t)d_out) % 16) {
+        g_snap_err = "lvt_amd_reloc_match_device: n_query must be 0 ... 4096, n_map 0 ... 32768, the pointers device pointers aligned to 16 bytes (nothing was changed)";
+        return -1.0f;
+    }
+    if (n_query == 0) return 0.0f;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int slice = reloc_slice_length(n_map), slices = (n_map + slice - 1) / slice, gx = (n_query + RELOC_THREADS - 1) / RELOC_THREADS;
+    uint2 *keys = nullptr;
+    int *d_dims = nullptr;
+    const int h_dims[3] = {n_query, n_map, 0};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = -1.0f;
+    if (hipMalloc((void **)&keys, (size_t)std::max(slices, 1) * n_query * sizeof(uint2)) == hipSuccess && hipMalloc((void **)&d_dims, sizeof h_dims) == hipSuccess &&
+        hipMemcpy(d_dims, h_dims, sizeof h_dims, hipMemcpyHostToDevice) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+        const RelocDims dims{d_dims, d_dims + 1, d_dims + 2, nullptr};
+        (void)hipEventRecord(e0, st);
+        const char *lab = getenv("LVT_AMD_RELOC_MATCH");  // "uniform": the lab variant without LDS (this stage entry only; a handle's call always stages in LDS)
+        if (slices > 0 && lab && !strcmp(lab, "uniform"))
+            hipLaunchKernelGGL(k_reloc_match<false>, dim3(gx, slices), dim3(RELOC_THREADS), 0, st, (const uint4 *)d_query, (const uint4 *)d_map, (const uint4 *)d_map, dims,
+                               keys);
+        else if (slices > 0)
+            hipLaunchKernelGGL(k_reloc_match<true>, dim3(gx, slices), dim3(RELOC_THREADS), 0, st, (const uint4 *)d_query, (const uint4 *)d_map, (const uint4 *)d_map, dims,
+                               keys);
+        hipLaunchKernelGGL(k_reloc_merge_records, dim3(gx), dim3(RELOC_THREADS), 0, st, (const uint2 *)keys, dims, (int4 *)d_out);
+        (void)hipEventRecord(e1, st);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(keys), (void)hipFree(d_dims);
+    return ms < 0 ? -1.0f : ms * 1000.0f;
+}
+// stages 3 - 5 alone.  Host pointers: pts n x 3 f64 (world), obs n x 2 f32, pc n x 3 f64 (camera frame), has_pc n bytes (0: the correspondence has no point, its
+// pc row is not read), 0 <= n <= 4096.  counts_out (n_hypotheses ints), inliers_out (n ints: the best hypothesis' inliers, the first n_hyp_inliers of them),
+// hyp_R (9) and hyp_t (3) may each be NULL; the last three are written for status 0 and 3 only.  Returns 0 / 1 as lvt_amd_relocalise does, -1 on a refusal.
+LVT_API int lvt_amd_reloc_solve(const lvt_amd_params *pin, const lvt_amd_reloc_config *cfg_in, const double *pts, const float *obs, const double *pc,
+                                const uint8_t *has_pc, int n, int *counts_out, int *inliers_out, double *hyp_R, double *hyp_t, lvt_amd_reloc_result *out) {
+    lvt_amd_reloc_config cfg;
+    lvt_amd_reloc_default_config(&cfg);
+    if (cfg_in) cfg = *cfg_in;
+    if (!pin || !out || n < 0 || n > NF_MAX || (n > 0 && (!pts || !obs || !pc || !has_pc))) {
+        g_snap_err = "lvt_amd_reloc_solve: a NULL argument, or n outside 0 ... 4096 (nothing was changed)";
+        return -1;
+    }
+    const std::string fault = reloc_config_fault(cfg);
+    if (!fault.empty()) {
+        g_snap_err = "lvt_amd_reloc_solve: " + fault;
+        return -1;
+    }
+    Params prm;
+    lvt_amd_params tmp = *pin;
+    if (tmp.img_width <= 0) tmp.img_width = 64;
+    if (tmp.img_height <= 0) tmp.img_height = 64;
+    if (!derive_params(tmp, 1, prm)) {
+        g_snap_err = "lvt_amd_reloc_solve: parameters lvt_amd_create would refuse (nothing was changed)";
+        return -1;
+    }
+    std::vector<int> with_pc;
+    for (int i = 0; i < n; i++)
+        if (has_pc[i]) with_pc.push_back(i);
+    RelocWork w{};
+    w.res.n_corr = n, w.res.n_with_point = (int)with_pc.size();
+    w.res.status = w.res.n_with_point < 3 ? 1 : -1;
+    w.success = std::max(cfg.min_inliers, prm.min_matches);
+    const size_t nn = (size_t)std::max(n, 1);
+    double *dX = nullptr, *dPc = nullptr, *dEX = nullptr, *dErr = nullptr;
+    float *dObs = nullptr, *dEObs = nullptr;
+    int *dWith = nullptr, *dCounts = nullptr, *dInl = nullptr;
+    int8_t *dLevel = nullptr;
+    RelocWork *dW = nullptr;
+    int rc = -1;
+    std::vector<int> counts((size_t)cfg.n_hypotheses, 0);
+    if (hipMalloc((void **)&dX, nn * 24) == hipSuccess && hipMalloc((void **)&dPc, nn * 24) == hipSuccess && hipMalloc((void **)&dEX, nn * 24) == hipSuccess &&
+        hipMalloc((void **)&dErr, nn * 16 + 16) == hipSuccess && hipMalloc((void **)&dObs, nn * 8) == hipSuccess && hipMalloc((void **)&dEObs, nn * 8) == hipSuccess &&
+        hipMalloc((void **)&dWith, nn * 4) == hipSuccess && hipMalloc((void **)&dCounts, counts.size() * 4) == hipSuccess &&
+        hipMalloc((void **)&dInl, nn * 4) == hipSuccess && hipMalloc((void **)&dLevel, nn) == hipSuccess && hipMalloc((void **)&dW, sizeof(RelocWork)) == hipSuccess &&
+        hipMemcpy(dW, &w, sizeof w, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dCounts, 0, counts.size() * 4) == hipSuccess &&
+        (n == 0 || (hipMemcpy(dX, pts, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dPc, pc, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(dObs, obs, (size_t)n * 8, hipMemcpyHostToDevice) == hipSuccess)) &&
+        (with_pc.empty() || hipMemcpy(dWith, with_pc.data(), with_pc.size() * 4, hipMemcpyHostToDevice) == hipSuccess)) {
+        const RelocCorr c{dX, dObs, dPc, dWith, 0, 0};  // (the sizes travel in the work record)
+        const RelocCam cam{(double)prm.fx, (double)prm.fy, (double)prm.cx, (double)prm.cy};
+        const double gate = (double)cfg.gate_px2;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_reloc_refine), hipFuncAttributeMaxDynamicSharedMemorySize, PNP_DYN_BYTES);
+        hipLaunchKernelGGL(k_reloc_score, dim3((cfg.n_hypotheses + 3) / 4), dim3(RELOC_THREADS), 0, 0, c, (const RelocWork *)dW, cam, (uint64_t)cfg.seed, gate, cfg.n_hypotheses,
+                           dCounts);
+        hipLaunchKernelGGL(k_reloc_select, dim3(1), dim3(RELOC_THREADS), 0, 0, c, cam, (uint64_t)cfg.seed, gate, cfg.n_hypotheses, (const int *)dCounts, dW, dInl, dEX,
+                           dEObs);
+        hipLaunchKernelGGL(k_reloc_refine, dim3(1), dim3(PNP_THREADS), PNP_DYN_BYTES, 0, prm, dW, (const double *)dEX, (const float *)dEObs, dErr, dLevel);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(&w, dW, sizeof w, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(counts.data(), dCounts, counts.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            (!inliers_out || w.n_edges <= 0 || hipMemcpy(inliers_out, dInl, (size_t)w.n_edges * 4, hipMemcpyDeviceToHost) == hipSuccess)) {
+            if (w.res.status != 0 && w.res.status != 3) {  // the pose is zero unless the refinement ran
+                for (int k = 0; k < 4; k++) w.res.q_wxyz[k] = 0;
+                for (int k = 0; k < 3; k++) w.res.p[k] = w.res.t[k] = 0;
+                for (int k = 0; k < 9; k++) w.res.R[k / 3][k % 3] = 0;
+            } else {
+                if (hyp_R) std::memcpy(hyp_R, w.hyp_R, sizeof w.hyp_R);
+                if (hyp_t) std::memcpy(hyp_t, w.hyp_t, sizeof w.hyp_t);
+            }
+            if (counts_out) std::memcpy(counts_out, counts.data(), counts.size() * 4);
+            *out = w.res;
+            rc = w.res.status == 0 ? 0 : 1;
+        }
+    }
+    (void)hipFree(dX), (void)hipFree(dPc), (void)hipFree(dEX), (void)hipFree(dErr), (void)hipFree(dObs), (void)hipFree(dEObs), (void)hipFree(dWith);
+    (void)hipFree(dCounts), (void)hipFree(dInl), (void)hipFree(dLevel), (void)hipFree(dW);
+    if (rc < 0) g_snap_err = std::string("lvt_amd_reloc_solve: ") + hipGetErrorString(hipGetLastError());
+    return rc;
+}
+
 // ---- snapshots: one sequence's state saved, restored, moved between handles and seats (k_state.hip) -------------------------------------------
 // Everything is checked before anything changes: a refusal returns -1 / NULL, leaves handle and snapshot as they were and says why in lvt_amd_last_error
 // (lvt_amd_snapshot_import / _describe have no handle: lvt_amd_last_error(NULL) then speaks of the calling thread's last refused import or describe).
@@ -3164,6 +3304,90 @@ static int snapshot_apply(lvt_handle h, const char *who, bool batch_call, int se
     }
     return -1;
 }
+// ---- relocalisation on a handle (k_reloc.hip; include/lvt_amd_ext.h, "RELOCALISATION") ----------------------------------------------------------------
+// Modelled on snapshot_apply: an explicit call between frames on a quiet handle, everything checked before anything changes, all launches on the tracking
+// stream, ONE stream synchronisation and one read-back (the call's work record).  The per-frame chain is not touched.
+static void reloc_buffers(Context *c) {
+    if (c->reloc.work) return;
+    RelocBufs &b = c->reloc;
+    b.keys = c->dalloc<uint2>((size_t)(MAP_MAX / RELOC_SLICE_MAX) * NF_MAX);
+    b.claim = c->dalloc<uint32_t>(MAP_MAX);
+    b.corr_feat = c->dalloc<int>(NF_MAX), b.with_pc = c->dalloc<int>(NF_MAX), b.inl = c->dalloc<int>(NF_MAX), b.counts = c->dalloc<int>(RELOC_HYP_MAX);
+    b.X = c->dalloc<double>(3 * NF_MAX), b.Pc = c->dalloc<double>(3 * NF_MAX), b.eX = c->dalloc<double>(3 * NF_MAX), b.eErr = c->dalloc<double>(2 * NF_MAX + 2);
+    b.uv = c->dalloc<float>(2 * NF_MAX), b.eObs = c->dalloc<float>(2 * NF_MAX);
+    b.has_pc = c->dalloc<uint8_t>(NF_MAX), b.eLevel = c->dalloc<int8_t>(NF_MAX);
+    HIPCHK(c, hipMemset(b.claim, 0xFF, sizeof(uint32_t) * MAP_MAX));  // RELOC_NO_KEY: every call leaves the table as it found it
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_reloc_refine), hipFuncAttributeMaxDynamicSharedMemorySize, PNP_DYN_BYTES));
+    b.work = c->dalloc<RelocWork>(1);
+    HIPCHK(c, hipStreamSynchronize(nullptr));  // (the clears run on the NULL stream, which the tracking stream does not wait for)
+}
+// (h: resolved; the entry points come through with_auto_handle)
+static int relocalise(lvt_handle h, const char *who, bool batch_call, int seq, const lvt_amd_reloc_config *cfg_in, lvt_amd_reloc_result *out) {
+    Context *c = snap_context(h, who, batch_call);
+    if (!c) return -1;
+    DeviceGuard guard(c);
+    try {
+        if (!batch_call && (c->B != 1 || c->mixed)) return refuse_unchanged(h, who, "a batch handle: lvt_amd_batch_relocalise names the sequence");
+        if (!snap_seq_ok(c, who, seq)) return -1;
+        if (!out) return refuse_unchanged(h, who, "no record to return the result in");
+        lvt_amd_reloc_config cfg;
+        lvt_amd_reloc_default_config(&cfg);
+        if (cfg_in) cfg = *cfg_in;
+        const std::string fault = reloc_config_fault(cfg);
+        if (!fault.empty()) return refuse(h, who, fault);
+        if (frames_in_flight(c)) return refuse_unchanged(h, who, "frames in flight: relocalise after every frame has been collected");
+        if (c->done == 0) return refuse_unchanged(h, who, "the handle has not seen a frame");
+        const std::string tag = c->B > 1 ? "sequence " + std::to_string(seq) + ": " : "";
+        if (last_ctl(c, seq).counts[C_MAP_SIZE] <= 0) return refuse_unchanged(h, who, tag + "an empty map");
+        reloc_buffers(c);
+        const Seq &S = c->h_seqs[seq];
+        const Params &prm = S.prm;
+        const FrameBuf &FB = S.fb[c->last_par];
+        RelocSeq rs{};
+        for (int e = 0; e < 2; e++) rs.x[e] = FB.feat[e].x, rs.y[e] = FB.feat[e].y, rs.desc[e] = FB.feat[e].desc, rs.n_feat[e] = FB.feat[e].n, rs.map_pos[e] = S.map[e].pos;
+        rs.depth = FB.feat[0].depth, rs.map_n = S.map_n, rs.map_cur = S.map_cur, rs.fc = FB.fc;
+        const RelocBufs &b = c->reloc;
+        RelocWork w{};
+        w.success = std::max(cfg.min_inliers, prm.min_matches);
+        const ChainWords cw = chain_of(fresh_ctl(c));
+        const RelocDims dims{rs.n_feat[0], rs.map_n, rs.map_cur, rs.fc};
+        const RelocCorr rc{b.X, b.uv, b.Pc, b.with_pc, 0, 0};
+        const RelocCam cam{(double)prm.fx, (double)prm.fy, (double)prm.cx, (double)prm.cy};
+        hipStream_t st = c->stream;
+        HIPCHK(c, hipMemcpyAsync(b.work, &w, sizeof w, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_reloc_match<true>, dim3(NF_MAX / RELOC_THREADS, MAP_MAX / RELOC_SLICE_MAX), dim3(RELOC_THREADS), 0, st, (const uint4 *)rs.desc[0],
+                           (const uint4 *)S.map[0].desc, (const uint4 *)S.map[1].desc, dims, b.keys);
+        hipLaunchKernelGGL(k_reloc_corr, dim3(1), dim3(1024), 0, st, rs, b, prm.track_ratio, prm.desc_th);
+        hipLaunchKernelGGL(k_reloc_points, dim3(NF_MAX / (RELOC_THREADS / 64)), dim3(RELOC_THREADS), 0, st, rs, b, prm, cfg.min_disparity);
+        hipLaunchKernelGGL(k_reloc_list, dim3(1), dim3(1024), 0, st, b);
+        hipLaunchKernelGGL(k_reloc_score, dim3((cfg.n_hypotheses + 3) / 4), dim3(RELOC_THREADS), 0, st, rc, (const RelocWork *)b.work, cam, (uint64_t)cfg.seed,
+                           (double)cfg.gate_px2, cfg.n_hypotheses, b.counts);
+        hipLaunchKernelGGL(k_reloc_select, dim3(1), dim3(RELOC_THREADS), 0, st, rc, cam, (uint64_t)cfg.seed, (double)cfg.gate_px2, cfg.n_hypotheses, (const int *)b.counts,
+                           b.work, b.inl, b.eX, b.eObs);
+        hipLaunchKernelGGL(k_reloc_refine, dim3(1), dim3(PNP_THREADS), PNP_DYN_BYTES, st, prm, b.work, (const double *)b.eX, (const float *)b.eObs, b.eErr, b.eLevel);
+        hipLaunchKernelGGL(k_reloc_commit, dim3(1), dim3(64), 0, st, c->d_ctl[seq], (const RelocWork *)b.work, cw, cfg.dry_run);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&w, b.work, sizeof w, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (w.res.status == RELOC_NO_FEATURES) return refuse_unchanged(h, who, tag + "the last frame was skipped, absent or poisoned: it has no features");
+        if (w.res.status != 0 && w.res.status != 3) {  // the pose is zero unless the refinement ran
+            for (int k = 0; k < 4; k++) w.res.q_wxyz[k] = 0;
+            for (int k = 0; k < 3; k++) w.res.p[k] = w.res.t[k] = 0;
+            for (int k = 0; k < 9; k++) w.res.R[k / 3][k % 3] = 0;
+        }
+        *out = w.res;
+        if (w.res.status != 0) return 1;
+        if (!cfg.dry_run) {  // the host ring answers from the new state at once, as it answers from a snapshot after an apply
+            Ctl k = last_ctl(c, seq);
+            reloc_commit_ctl(k, w.res, cw);
+            for (int r = 0; r < RING; r++) c->h_ctl[r * c->B + seq] = k;
+            pose_info_clear(c, seq);
+        }
+        return 0;
+    } catch (...) {
+    }
+    return -1;
+}
 }  // namespace lvt
 extern "C" {
 
@@ -3207,6 +3431,12 @@ LVT_API int lvt_amd_snapshot_apply(lvt_handle h, int seq, lvt_amd_snapshot s) {
 }
 LVT_API int lvt_amd_batch_snapshot_apply(lvt_handle h, const lvt_amd_snapshot *s) {
     return with_auto_handle(h, [&](lvt_handle t) { return snapshot_apply(t, "lvt_amd_batch_snapshot_apply", true, 0, s); });
+}
+LVT_API int lvt_amd_relocalise(lvt_handle h, const lvt_amd_reloc_config *cfg, lvt_amd_reloc_result *out) {
+    return with_auto_handle(h, [&](lvt_handle t) { return relocalise(t, "lvt_amd_relocalise", false, 0, cfg, out); });
+}
+LVT_API int lvt_amd_batch_relocalise(lvt_handle h, int seq, const lvt_amd_reloc_config *cfg, lvt_amd_reloc_result *out) {
+    return with_auto_handle(h, [&](lvt_handle t) { return relocalise(t, "lvt_amd_batch_relocalise", true, seq, cfg, out); });
 }
 LVT_API int lvt_amd_batch_reset(lvt_handle h, int seq) {
     static const char *who = "lvt_amd_batch_reset";
@@ -3316,11 +3546,40 @@ LVT_API void lvt_amd_odometry_reset(lvt_amd_odometry op) {  // reset_vo (lvt_ros
     o->restart_deltas();
     o->base_to_odom = Rigid();
 }
+// cfg NULL: the default config; max_lost_frames <= 0: the policy is off (the reference's reset on every LOST frame).  0 / -1 (a bad config field)
+LVT_API int lvt_amd_odometry_set_relocalisation(lvt_amd_odometry op, const lvt_amd_reloc_config *cfg, int max_lost_frames) {
+    Odometry *o = static_cast<Odometry *>(op);
+    if (!o) return -1;
+    lvt_amd_reloc_config c;
+    lvt_amd_reloc_default_config(&c);
+    if (cfg) c = *cfg;
+    std::string fault = reloc_config_fault(c);
+    // (a dry run would publish the relocalised pose while the tracker stays LOST, and the failures that lead to the reset would never be counted)
+    if (fault.empty() && c.dry_run) fault = "dry_run is 1: the accumulator's relocalisation commits, dry_run must be 0 (nothing was changed)";
+    if (!fault.empty()) {
+        g_snap_err = "lvt_amd_odometry_set_relocalisation: " + fault;
+        return -1;
+    }
+    o->reloc_cfg = c, o->max_lost_frames = std::max(max_lost_frames, 0), o->lost_run = 0;
+    return 0;
+}
 LVT_API int lvt_amd_odometry_push_pose(lvt_amd_odometry op, const double R[3][3], const double t[3], int status, double stamp_sec,
                                        double pose_out[7], double twist_out[6]) {
     Odometry *o = static_cast<Odometry *>(op);
     if (!o || !R || !t) return -1;
     if (o->have_time && o->last_time > stamp_sec) return 0;  // older than the last published frame: ignored (lvt_ros.cpp:224-229)
+    o->pushed_relocalised = false;
+    if (status != 3) o->lost_run = 0;
+    if (status == 3 && o->max_lost_frames > 0) {  // the relocalisation policy: the map is kept, last_R / last_p stay those of the last tracked frame
+        lvt_amd_reloc_result r;
+        if (o->tracker && lvt_amd_relocalise(o->tracker, &o->reloc_cfg, &r) == 0) {  // the published delta spans the gap: the trajectory stays continuous
+            o->lost_run = 0;
+            o->pushed_relocalised = true;
+            return o->push(&r.R[0][0], r.t, stamp_sec, pose_out, twist_out) ? 1 : 0;
+        }
+        if (++o->lost_run < o->max_lost_frames) return 0;  // nothing is published, nothing is reset
+        o->lost_run = 0;                                   // ... that many failures in a row: the reference's reset, below
+    }
     if (status == 3) {  // LOST: reset the tracker, optionally the accumulated pose; nothing is published (lvt_ros.cpp:241-253)
         if (o->tracker) lvt_amd_reset(o->tracker);
         if (o->reset_pose_on_lost) {
@@ -3351,7 +3610,8 @@ LVT_API int lvt_amd_odometry_push_pose_cov(lvt_amd_odometry op, const double R[3
     double M[36];
     o->perturbation_map(&R[0][0], M);
     const int rc = lvt_amd_odometry_push_pose(op, R, t, status, stamp_sec, pose_out, twist_out);
-    if (rc == 1 && cov_in && cov_out) sandwich6(M, cov_in, cov_out);
+    // (a frame the policy relocalised: M and cov_in belong to the LOST frame handed in, not to the pose that was published -- cov_out stays zero)
+    if (rc == 1 && cov_in && cov_out && !o->pushed_relocalised) sandwich6(M, cov_in, cov_out);
     return rc;
 }
 LVT_API int lvt_amd_odometry_update_cov(lvt_amd_odometry op, unsigned char *left, unsigned char *right, int n_rows, int n_cols, double stamp_sec,

@@ -84,6 +84,11 @@ struct Odometry {
     double last_R[9], last_p[3] = {0, 0, 0};
     bool have_time = false;
     double last_time = 0;
+    // relocalisation policy (lvt_amd_odometry_set_relocalisation): on a LOST frame relocalise the tracker instead of resetting it; `lost_run` consecutive
+    // failures so far, the reference's reset at `max_lost_frames` of them.  Off (max_lost_frames == 0): the reference's policy, as before
+    lvt_amd_reloc_config reloc_cfg{};
+    int max_lost_frames = 0, lost_run = 0;
+    bool pushed_relocalised = false;  // the pose the last push_pose published came from a relocalisation, not from the frame handed in (push_pose_cov: no covariance)
 
     Odometry() {
         // Rz(a) Rx(a), a = -1.57079632679 (the reference's literal, not exactly -pi/2): camera z-forward / x-right -> x-forward / z-up
