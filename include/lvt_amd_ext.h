@@ -559,9 +559,9 @@ LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3]
  * from it in the old map's coordinates.  Any state is accepted (TRACKING, or LOST after any number of frames) as long as the map holds a point; a snapshot
  * applied in a later session followed by a relocalisation on the first frame continues in the snapshot's coordinates.  Nothing in the per-frame launch
  * chain changes: a handle that never calls it allocates and launches exactly what it did, and snapshots keep their bytes.
- * The stages are entry points of their own as well, in the style of lvt_amd_hamming_match_batched and lvt_amd_pnp: the global descriptor match (stage 1)
- * and hypotheses, scoring and refinement (stages 3 - 5) on correspondences the caller has formed.  The claim is equality with THIS text;
- * tests/reloc_util.py restates it in numpy.
+ * The stages are entry points of their own as well, in the style of lvt_amd_hamming_match_batched and lvt_amd_pnp: the global descriptor match (stage 1),
+ * the correspondences (stage 2) on features and a map the caller hands in, and hypotheses, scoring and refinement (stages 3 - 5) on correspondences the
+ * caller has formed.  The claim is equality with THIS text; tests/reloc_util.py restates it in numpy.
  *  Arithmetic.  The 32-bit floats of the observations and the parameters are widened to fp64, everything after that is fp64: one IEEE operation per written
  *  operation, correctly rounded division and square root, only + - * / sqrt, sums of three in the order ((a b + c d) + e f).  A comparison that involves a NaN
  *  is false.
@@ -624,7 +624,23 @@ LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3]
  *    measurements, profiles/relocalisation.md).
  *  - lvt_amd_reloc_solve: stages 3 - 5 on HOST pointers: pts n x 3 f64, obs n x 2 f32, pc n x 3 f64, has_pc n bytes, 0 <= n <= 4096; of `p` the intrinsics
  *    and min_num_matches_for_tracking are read.  counts_out (n_hypotheses ints), inliers_out (n ints; the first n_hyp_inliers are written), hyp_R (9,
- *    row-major) and hyp_t (3) -- the best hypothesis, status 0 and 3 only -- may each be NULL.  Returns 0 for status 0, 1 for status 1 ... 3, -1 on a refusal. */
+ *    row-major) and hyp_t (3) -- the best hypothesis, status 0 and 3 only -- may each be NULL.  Returns 0 for status 0, 1 for status 1 ... 3, -1 on a refusal.
+ *  - lvt_amd_reloc_correspond: stage 2, behind stage 1, on HOST pointers, through the very launches a handle's call makes for them (the capacity grid, every
+ *    size read on the device).  The call lays the data out as a handle holds it, in device buffers of its own, and synchronises once.
+ *      sensor 1 (stereo) or 2 (RGB-D).  Of `p`: img_height, fx, fy, cx, cy, baseline, tracking_ratio_test_threshold, triangulation_ratio_test_threshold and
+ *      descriptor_matching_threshold; of the config: min_disparity (the other fields are checked and not used).
+ *      Left features: x, y (f32), desc (32 bytes each), depth (f32, RGB-D only), 0 <= n_left <= 4096.  Right features: the same without depth,
+ *      0 <= n_right <= 4096; RGB-D ignores them.  The map: map_pos n_map x 3 f64, map_desc n_map x 32 bytes, 0 <= n_map <= 32768.
+ *      map_copy 0 or 1: the copy of the two the map is placed in and the live-copy word names; the OTHER copy gets other_pos / other_desc (n_map rows each;
+ *      NULL: zeros), which a correct call never reads.
+ *      lost_frame 0 or 1.  1: the counts arrive as a LOST frame leaves them -- the feature counts themselves are zero, the counts are the ones the frame's
+ *      epilogue kept beside them, marked as belonging to the frame the buffer holds.
+ *      Out: n_features, n_map, n_matched, n_corr, n_with_point and status of `out` (1 for n_with_point < 3, otherwise -1: stages 3 - 5 have not run; the
+ *      other fields zero).  Per correspondence c < n_corr: corr_feat[c] the feature index, X[3 c ..] , uv[2 c ..], has_pc[c], and -- where has_pc[c] -- Pc[3 c ..];
+ *      with_pc[k], k < n_with_point.  Each array has room for 4096 elements (rows).  They are uploaded as the caller filled them and read back whole: an
+ *      element beyond the counts, and a Pc row without a point, comes back with the caller's bytes.  claims_left (may be NULL): how many entries of the
+ *      mutual filter's claim table are not empty behind the call (a call leaves the table as it found it: 0).
+ *      Returns 0, or -1 on a refusal: a NULL argument, a count or a flag out of range, a bad config field, parameters lvt_amd_create would refuse. */
 typedef struct lvt_amd_reloc_config {
     int      n_hypotheses;    /* 256 */
     float    gate_px2;        /* 16.0: the scoring gate in px^2 */
@@ -659,6 +675,11 @@ LVT_API float lvt_amd_reloc_match_device(const void *d_query, int n_query, const
 LVT_API int lvt_amd_reloc_solve(const lvt_amd_params *p, const lvt_amd_reloc_config *cfg /* NULL = defaults */, const double *pts, const float *obs,
                                 const double *pc, const uint8_t *has_pc, int n, int *counts_out, int *inliers_out, double *hyp_R, double *hyp_t,
                                 lvt_amd_reloc_result *out);
+LVT_API int lvt_amd_reloc_correspond(const lvt_amd_params *p, const lvt_amd_reloc_config *cfg /* NULL = defaults */, int sensor, const float *xl, const float *yl,
+                                     const uint8_t *desc_l, const float *depth_l, int n_left, const float *xr, const float *yr, const uint8_t *desc_r, int n_right,
+                                     const double *map_pos, const uint8_t *map_desc, const double *other_pos, const uint8_t *other_desc, int n_map, int map_copy,
+                                     int lost_frame, lvt_amd_reloc_result *out, int *corr_feat, double *X, float *uv, uint8_t *has_pc, double *Pc, int *with_pc,
+                                     int *claims_left);
 
 /* ---- odometry accumulator: the consumer right behind the path -----------------------------------------------
  * What the reference's ROS node does with every pose (lvt/src/lvt_ros.cpp:86-92 constructor, :215-311 on_stereo_image), without

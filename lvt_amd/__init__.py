@@ -47,7 +47,7 @@ ABI_SYMBOLS = [
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
-    "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve",
+    "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve", "lvt_amd_reloc_correspond",
 ]
 
 N_COUNTS = 32
@@ -216,7 +216,8 @@ def load_library():
             ("lvt_amd_relocalise", [vp, vp, vp], C.c_int), ("lvt_amd_batch_relocalise", [vp, C.c_int, vp, vp], C.c_int),
             ("lvt_amd_odometry_set_relocalisation", [vp, vp, C.c_int], C.c_int), ("lvt_amd_reloc_default_config", [vp], None), ("lvt_amd_reloc_slice_length", [C.c_int], C.c_int),
             ("lvt_amd_reloc_match_device", [vp, C.c_int, vp, C.c_int, vp, vp], C.c_float),
-            ("lvt_amd_reloc_solve", [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp], C.c_int)):
+            ("lvt_amd_reloc_solve", [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp], C.c_int),
+            ("lvt_amd_reloc_correspond", [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 8, C.c_int)):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, restype
@@ -503,6 +504,45 @@ def reloc_solve(params: LvtParameters, pts, obs, pc, has_pc, cfg: RelocConfig = 
     if rc < 0:
         raise ValueError((L.lvt_amd_last_error(None) or b"").decode())
     return res, counts[:cfg.n_hypotheses].copy(), inl[:max(res.n_hyp_inliers, 0) if res.status in (0, 3) else 0].copy(), hR.reshape(3, 3), ht
+
+
+RELOC_CAPACITY = 4096                                            # rows of every output array of lvt_amd_reloc_correspond (NF_MAX)
+RELOC_SENTINEL_INT, RELOC_SENTINEL_F64, RELOC_SENTINEL_F32, RELOC_SENTINEL_BYTE = -77, -7.7e77, np.float32(-7.7e37), 0xEE
+
+
+def reloc_correspond(params: LvtParameters, sensor: int, xy_l, desc_l, map_xyz, map_desc, right=None, depth=None, other=None, map_copy: int = 0,
+                     lost_frame: int = 0, cfg: RelocConfig = None) -> dict:
+    """stage 2 of the relocalisation (behind stage 1) on caller data, through the launches of a handle's call (lvt_amd_reloc_correspond).  xy_l (N, 2) f32,
+    desc_l (N, 32) u8; right = (xy_r, desc_r) for stereo; depth (N,) f32 for RGB-D; map_xyz (M, 3) f64, map_desc (M, 32) u8; other = (xyz, desc) of M rows
+    for the map copy that is NOT live.  Returns the result record's counts and status, and feat, X, uv, has_pc, pc, with_pc UNTRIMMED (RELOC_CAPACITY rows,
+    pre-filled with the RELOC_SENTINEL_* values: what the call does not write keeps them), and claims_left.  A refusal raises ValueError."""
+    L = load_library()
+    pod = params.to_pod()
+    cfg = cfg if cfg is not None else RelocConfig()
+    f32 = lambda a, cols: np.ascontiguousarray(a, np.float32).reshape(-1, cols) if a is not None else np.zeros((0, cols), np.float32)
+    u8 = lambda a: np.ascontiguousarray(a, np.uint8).reshape(-1, 32) if a is not None else np.zeros((0, 32), np.uint8)
+    xy_l, desc_l = f32(xy_l, 2), u8(desc_l)
+    xy_r, desc_r = (f32(right[0], 2), u8(right[1])) if right is not None else (f32(None, 2), u8(None))
+    xl, yl, xr, yr = (np.ascontiguousarray(a) for a in (xy_l[:, 0], xy_l[:, 1], xy_r[:, 0], xy_r[:, 1]))
+    dep = np.ascontiguousarray(depth, np.float32).reshape(-1) if depth is not None else None
+    mpos, mdesc = np.ascontiguousarray(map_xyz, np.float64).reshape(-1, 3), u8(map_desc)
+    opos, odesc = (np.ascontiguousarray(other[0], np.float64).reshape(-1, 3), u8(other[1])) if other is not None else (None, None)
+    n_l, n_r, n_m = len(xy_l), len(xy_r), len(mpos)
+    if len(desc_l) != n_l or len(desc_r) != n_r or len(mdesc) != n_m or (dep is not None and len(dep) != n_l) or (opos is not None and not (len(opos) == len(odesc) == n_m)):
+        raise ValueError("one descriptor (and one depth) per feature, one descriptor per map point, the other map copy as long as the live one")
+    cap = RELOC_CAPACITY
+    out = dict(feat=np.full(cap, RELOC_SENTINEL_INT, np.int32), X=np.full((cap, 3), RELOC_SENTINEL_F64), uv=np.full((cap, 2), RELOC_SENTINEL_F32, np.float32),
+               has_pc=np.full(cap, RELOC_SENTINEL_BYTE, np.uint8), pc=np.full((cap, 3), RELOC_SENTINEL_F64), with_pc=np.full(cap, RELOC_SENTINEL_INT, np.int32))
+    res, left = RelocResult(), C.c_int(-1)
+    ptr = lambda a: _p(a) if a is not None and a.size else None
+    rc = L.lvt_amd_reloc_correspond(C.byref(pod), C.byref(cfg), int(sensor), ptr(xl), ptr(yl), ptr(desc_l), ptr(dep), n_l, ptr(xr), ptr(yr), ptr(desc_r), n_r,
+                                    ptr(mpos), ptr(mdesc), ptr(opos), ptr(odesc), n_m, int(map_copy), int(lost_frame), C.byref(res), _p(out["feat"]), _p(out["X"]),
+                                    _p(out["uv"]), _p(out["has_pc"]), _p(out["pc"]), _p(out["with_pc"]), C.byref(left))
+    if rc < 0:
+        raise ValueError((L.lvt_amd_last_error(None) or b"").decode())
+    out.update(status=res.status, n_features=res.n_features, n_map=res.n_map, n_matched=res.n_matched, n_corr=res.n_corr, n_with_point=res.n_with_point,
+               claims_left=left.value)
+    return out
 
 
 def _params_of(pod):

@@ -2957,6 +2957,17 @@ static std::string reloc_config_fault(const lvt_amd_reloc_config &c) {
     return b;
 }
 LVT_API int lvt_amd_reloc_slice_length(int n_map) { return reloc_slice_length(std::max(n_map, 0)); }
+// stages 1 and 2 of one call: four launches on `st`, the capacity grid, every size read on the device (RelocSeq's scalars and its FeatCtl).  A handle's call
+// (relocalise) and the stage entry lvt_amd_reloc_correspond both come through here: what the entry is held to is what the handle runs.
+static void reloc_launch_correspond(hipStream_t st, const RelocSeq &rs, const uint64_t *mdesc0, const uint64_t *mdesc1, const RelocBufs &b, const Params &prm,
+                                    float min_disparity) {
+    const RelocDims dims{rs.n_feat[0], rs.map_n, rs.map_cur, rs.fc};
+    hipLaunchKernelGGL(k_reloc_match<true>, dim3(NF_MAX / RELOC_THREADS, MAP_MAX / RELOC_SLICE_MAX), dim3(RELOC_THREADS), 0, st, (const uint4 *)rs.desc[0],
+                       (const uint4 *)mdesc0, (const uint4 *)mdesc1, dims, b.keys);
+    hipLaunchKernelGGL(k_reloc_corr, dim3(1), dim3(1024), 0, st, rs, b, prm.track_ratio, prm.desc_th);
+    hipLaunchKernelGGL(k_reloc_points, dim3(NF_MAX / (RELOC_THREADS / 64)), dim3(RELOC_THREADS), 0, st, rs, b, prm, min_disparity);
+    hipLaunchKernelGGL(k_reloc_list, dim3(1), dim3(1024), 0, st, b);
+}
 // stage 1 alone.  d_query n_query x 32 B, d_map n_map x 32 B, d_out n_query x 4 int32 (idx1, d1, idx2, d2; -1 / INT_MAX when absent): DEVICE pointers, 16-byte
 // aligned.  Both launches go to hip_stream; the call allocates its key buffer and frees it after synchronising that stream.  Returns the elapsed time of the
 // two launches in microseconds (HIP events), < 0 on a refusal or a HIP failure (lvt_amd_last_error(NULL) has the sentence of a refusal).
@@ -3070,6 +3081,102 @@ LVT_API int lvt_amd_reloc_solve(const lvt_amd_params *pin, const lvt_amd_reloc_c
     (void)hipFree(dX), (void)hipFree(dPc), (void)hipFree(dEX), (void)hipFree(dErr), (void)hipFree(dObs), (void)hipFree(dEObs), (void)hipFree(dWith);
     (void)hipFree(dCounts), (void)hipFree(dInl), (void)hipFree(dLevel), (void)hipFree(dW);
     if (rc < 0) g_snap_err = std::string("lvt_amd_reloc_solve: ") + hipGetErrorString(hipGetLastError());
+    return rc;
+}
+// stage 2 (behind stage 1) alone, through the launches of a handle's call (reloc_launch_correspond).  Host pointers.  The data is laid out as a handle holds
+// it: feature arrays of both eyes with their device counts, a FeatCtl, two map copies of which map_copy is the live one (the other copy is filled from
+// other_pos / other_desc, zeros when NULL).  lost_frame: the counts are delivered as a LOST frame leaves them (Feat::n zero, FeatCtl::lost_n, lost_seq ==
+// feat_seq).  The six output arrays hold NF_MAX elements each (X, Pc: x 3; uv: x 2): they are uploaded as the caller filled them and read back whole, so an
+// element the kernels do not write comes back with the caller's bytes.  claims_left (may be NULL): entries of the claim table that are not empty behind the
+// call.  Returns 0 (out->status: 1 or -1, as stage 2 leaves it), -1 on a refusal or a HIP failure.
+LVT_API int lvt_amd_reloc_correspond(const lvt_amd_params *pin, const lvt_amd_reloc_config *cfg_in, int sensor, const float *xl, const float *yl,
+                                     const uint8_t *desc_l, const float *depth_l, int n_left, const float *xr, const float *yr, const uint8_t *desc_r, int n_right,
+                                     const double *map_pos, const uint8_t *map_desc, const double *other_pos, const uint8_t *other_desc, int n_map, int map_copy,
+                                     int lost_frame, lvt_amd_reloc_result *out, int *corr_feat, double *X, float *uv, uint8_t *has_pc, double *Pc, int *with_pc,
+                                     int *claims_left) {
+    lvt_amd_reloc_config cfg;
+    lvt_amd_reloc_default_config(&cfg);
+    if (cfg_in) cfg = *cfg_in;
+    const bool stereo = sensor == 1;
+    if (!stereo) n_right = 0;
+    if (!pin || !out || !corr_feat || !X || !uv || !has_pc || !Pc || !with_pc || (sensor != 1 && sensor != 2) || n_left < 0 || n_left > NF_MAX || n_right < 0 ||
+        n_right > NF_MAX || n_map < 0 || n_map > MAP_MAX || (map_copy != 0 && map_copy != 1) || (lost_frame != 0 && lost_frame != 1) ||
+        (n_left > 0 && (!xl || !yl || !desc_l || (!stereo && !depth_l))) || (n_right > 0 && (!xr || !yr || !desc_r)) || (n_map > 0 && (!map_pos || !map_desc))) {
+        g_snap_err = "lvt_amd_reloc_correspond: a NULL argument, sensor not 1 or 2, a feature count outside 0 ... 4096, n_map outside 0 ... 32768, or map_copy or "
+                     "lost_frame not 0 or 1 (nothing was changed)";
+        return -1;
+    }
+    const std::string fault = reloc_config_fault(cfg);
+    if (!fault.empty()) {
+        g_snap_err = "lvt_amd_reloc_correspond: " + fault;
+        return -1;
+    }
+    Params prm;
+    lvt_amd_params tmp = *pin;
+    if (tmp.img_width <= 0) tmp.img_width = 64;
+    if (!derive_params(tmp, sensor, prm)) {
+        g_snap_err = "lvt_amd_reloc_correspond: parameters lvt_amd_create would refuse (nothing was changed)";
+        return -1;
+    }
+    std::vector<void *> owned;
+    bool ok = true;
+    // a device buffer of `bytes` (at least 16): a copy of src, or -- src NULL -- every byte `fill`
+    auto dev = [&](size_t bytes, const void *src, int fill = 0) -> void * {
+        void *p = nullptr;
+        const size_t cap = std::max(bytes, (size_t)16);
+        if (!ok || hipMalloc(&p, cap) != hipSuccess) return ok = false, nullptr;
+        owned.push_back(p);
+        if (hipMemset(p, fill, cap) != hipSuccess || (src && bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess)) ok = false;
+        return p;
+    };
+    // (Feat::n of both eyes, map_n, map_cur)
+    const int h_scalars[4] = {lost_frame ? 0 : n_left, lost_frame ? 0 : n_right, n_map, map_copy};
+    FeatCtl fc{};
+    fc.feat_seq = 1, fc.skip_seq = 0;  // a zeroed record would read as "this frame has no features"
+    if (lost_frame) fc.lost_n[0] = n_left, fc.lost_n[1] = n_right, fc.lost_seq = fc.feat_seq;
+    RelocWork w{};
+    w.res.status = -1;
+    const int *d_scalars = (const int *)dev(sizeof h_scalars, h_scalars);
+    RelocSeq rs{};
+    rs.x[0] = (const float *)dev((size_t)n_left * 4, xl), rs.y[0] = (const float *)dev((size_t)n_left * 4, yl);
+    rs.desc[0] = (const uint64_t *)dev((size_t)n_left * 32, desc_l);
+    rs.depth = stereo ? nullptr : (const float *)dev((size_t)n_left * 4, depth_l);
+    if (stereo) {
+        rs.x[1] = (const float *)dev((size_t)n_right * 4, xr), rs.y[1] = (const float *)dev((size_t)n_right * 4, yr);
+        rs.desc[1] = (const uint64_t *)dev((size_t)n_right * 32, desc_r);
+    }
+    const uint64_t *mdesc[2];
+    mdesc[map_copy] = (const uint64_t *)dev((size_t)n_map * 32, map_desc), mdesc[map_copy ^ 1] = (const uint64_t *)dev((size_t)n_map * 32, other_desc);
+    rs.map_pos[map_copy] = (const double *)dev((size_t)n_map * 24, map_pos), rs.map_pos[map_copy ^ 1] = (const double *)dev((size_t)n_map * 24, other_pos);
+    rs.n_feat[0] = d_scalars, rs.n_feat[1] = d_scalars + 1, rs.map_n = d_scalars + 2, rs.map_cur = d_scalars + 3;
+    rs.fc = (const FeatCtl *)dev(sizeof fc, &fc);
+    const int slice = reloc_slice_length(n_map), slices = (n_map + slice - 1) / slice;
+    RelocBufs b{};
+    b.keys = (uint2 *)dev((size_t)std::max(slices, 1) * std::max(n_left, 1) * sizeof(uint2), nullptr);
+    b.claim = (uint32_t *)dev((size_t)n_map * 4, nullptr, 0xFF);  // RELOC_NO_KEY
+    b.corr_feat = (int *)dev((size_t)NF_MAX * 4, corr_feat), b.with_pc = (int *)dev((size_t)NF_MAX * 4, with_pc);
+    b.X = (double *)dev((size_t)NF_MAX * 24, X), b.Pc = (double *)dev((size_t)NF_MAX * 24, Pc);
+    b.uv = (float *)dev((size_t)NF_MAX * 8, uv), b.has_pc = (uint8_t *)dev((size_t)NF_MAX, has_pc);
+    b.work = (RelocWork *)dev(sizeof w, &w);
+    int rc = -1;
+    if (ok) {
+        reloc_launch_correspond(nullptr, rs, mdesc[0], mdesc[1], b, prm, cfg.min_disparity);
+        std::vector<uint32_t> claim((size_t)n_map);
+        if (hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess && hipMemcpy(&w, b.work, sizeof w, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(corr_feat, b.corr_feat, (size_t)NF_MAX * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(with_pc, b.with_pc, (size_t)NF_MAX * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(X, b.X, (size_t)NF_MAX * 24, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(Pc, b.Pc, (size_t)NF_MAX * 24, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(uv, b.uv, (size_t)NF_MAX * 8, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(has_pc, b.has_pc, (size_t)NF_MAX, hipMemcpyDeviceToHost) == hipSuccess &&
+            (n_map == 0 || hipMemcpy(claim.data(), b.claim, (size_t)n_map * 4, hipMemcpyDeviceToHost) == hipSuccess)) {
+            int left = 0;
+            for (uint32_t k : claim) left += k != RELOC_NO_KEY;
+            if (claims_left) *claims_left = left;
+            *out = w.res;
+            rc = 0;
+        }
+    }
+    for (void *p : owned) (void)hipFree(p);
+    if (rc < 0) g_snap_err = std::string("lvt_amd_reloc_correspond: ") + hipGetErrorString(hipGetLastError());
     return rc;
 }
 
@@ -3350,16 +3457,11 @@ static int relocalise(lvt_handle h, const char *who, bool batch_call, int seq, c
         RelocWork w{};
         w.success = std::max(cfg.min_inliers, prm.min_matches);
         const ChainWords cw = chain_of(fresh_ctl(c));
-        const RelocDims dims{rs.n_feat[0], rs.map_n, rs.map_cur, rs.fc};
         const RelocCorr rc{b.X, b.uv, b.Pc, b.with_pc, 0, 0};
         const RelocCam cam{(double)prm.fx, (double)prm.fy, (double)prm.cx, (double)prm.cy};
         hipStream_t st = c->stream;
         HIPCHK(c, hipMemcpyAsync(b.work, &w, sizeof w, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_reloc_match<true>, dim3(NF_MAX / RELOC_THREADS, MAP_MAX / RELOC_SLICE_MAX), dim3(RELOC_THREADS), 0, st, (const uint4 *)rs.desc[0],
-                           (const uint4 *)S.map[0].desc, (const uint4 *)S.map[1].desc, dims, b.keys);
-        hipLaunchKernelGGL(k_reloc_corr, dim3(1), dim3(1024), 0, st, rs, b, prm.track_ratio, prm.desc_th);
-        hipLaunchKernelGGL(k_reloc_points, dim3(NF_MAX / (RELOC_THREADS / 64)), dim3(RELOC_THREADS), 0, st, rs, b, prm, cfg.min_disparity);
-        hipLaunchKernelGGL(k_reloc_list, dim3(1), dim3(1024), 0, st, b);
+        reloc_launch_correspond(st, rs, S.map[0].desc, S.map[1].desc, b, prm, cfg.min_disparity);
         hipLaunchKernelGGL(k_reloc_score, dim3((cfg.n_hypotheses + 3) / 4), dim3(RELOC_THREADS), 0, st, rc, (const RelocWork *)b.work, cam, (uint64_t)cfg.seed,
                            (double)cfg.gate_px2, cfg.n_hypotheses, b.counts);
         hipLaunchKernelGGL(k_reloc_select, dim3(1), dim3(RELOC_THREADS), 0, st, rc, cam, (uint64_t)cfg.seed, (double)cfg.gate_px2, cfg.n_hypotheses, (const int *)b.counts,

@@ -232,3 +232,20 @@ def make_world(kind: str = "kitti", seed: int = 0, scale: float = 1.0, size=None
         kw.setdefault("depths", (3.0, 5.0, 8.0, 14.0))
         kw.setdefault("motion_scale", 0.3)
     return SynthWorld(seed=seed, **base, **kw)
+
+
+def noise_frame(epoch: int):
+    """one texture epoch of the full-map recipe (tools/relocalisation.py `fullmap`, tests/test_gpu_reloc_correspond.py): a full-size KITTI frame of noise,
+    columns [0, 300) the same in every epoch (the pose stays solvable on the 300 corners there), the right eye the left one moved 12 px (z ~ 32 m), 3 700
+    fresh corners per epoch.  Returns (left, right, corners_left, corners_right) for track_with_external_corners."""
+    W, H, disp = 1241, 376, 12
+    rng0 = np.random.default_rng(0)
+    fixed = rng0.integers(0, 256, (H, W), dtype=np.uint8)
+    keep = np.column_stack([rng0.integers(52, 270, 300), rng0.integers(40, H - 40, 300)])
+    rng = np.random.default_rng(100 + epoch)
+    L = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    L[:, :300] = fixed[:, :300]
+    R = np.ascontiguousarray(np.roll(L, -disp, axis=1))
+    fresh = np.column_stack([rng.integers(340, W - 40, 3700), rng.integers(40, H - 40, 3700)])
+    cl = np.unique(np.vstack([keep, fresh]), axis=0).astype(np.float64)
+    return L, R, cl, cl - [[float(disp), 0.0]]

@@ -307,3 +307,52 @@ def test_odometry_policy_keeps_the_trajectory_across_a_gap_and_falls_back_to_res
         od.set_relocalisation(dry_run=1)
     with pytest.raises(TypeError):
         od.set_relocalisation(hip_lib.RelocConfig(), 3, seed=1)
+
+
+# ---- the correspondence stage's planted cases (tests/reloc_cases.py): each still has the property it is named for ------------------------------------------
+def _reloc_case_names():
+    import reloc_cases
+    return reloc_cases.CASE_NAMES
+
+
+@pytest.mark.parametrize("name", _reloc_case_names())
+def test_correspondence_case_has_its_property(name):
+    """with the restatement alone (global_match, correspondences, camera_points_stereo / _rgbd): the counts cross the block boundaries they are meant to
+    cross, both outcomes of every planted decision are present, the planted partner is the one the definition picks.  A case that has lost its property
+    fails here instead of passing vacuously on the GPU."""
+    import reloc_cases
+    case, ref = reloc_cases.case_and_answer(name)
+    print(name, "--", case["plants"], "| N", ref["n_features"], "M", ref["n_map"], "matched", ref["n_matched"], "corr", ref["n_corr"], "with point", ref["n_with_point"])
+    assert case["plants"] and ref["n_features"] <= RU.NF_MAX and ref["n_map"] <= RU.MAP_MAX
+    case["check"](case, ref)
+
+
+def test_correspondence_cases_cover_the_issue_list():
+    import reloc_cases
+    got = {n: reloc_cases.case_and_answer(n) for n in reloc_cases.CASE_NAMES}
+    sizes = {(r["n_features"], r["n_map"]) for n, (_, r) in got.items() if n.startswith("A-")}
+    assert {(n, 3300) for n in (0, 1, 1023, 1024, 1025, 2049, 4096)} | {(1025, m) for m in (0, 1, 2, 33)} | {(4096, 32768)} == sizes
+    assert max(r["n_corr"] for _, r in got.values()) > 2048 and max(r["n_with_point"] for _, r in got.values()) > 2048
+    assert {c["sensor"] for c, _ in got.values()} == {1, 2} and {c["map_copy"] for c, _ in got.values()} == {0, 1} and any(c["lost_frame"] for c, _ in got.values())
+    assert sorted(r["n_features"] for n, (_, r) in got.items() if n.startswith("F-")) == [1025, 4096]
+
+
+def _correspond(hip_lib, case):
+    return hip_lib.reloc_correspond(case["prm"], case["sensor"], case["xy_l"], case["desc_l"], case["map_xyz"], case["map_desc"], right=case["right"],
+                                    depth=case["depth"], other=case["other"], map_copy=case["map_copy"], lost_frame=case["lost_frame"],
+                                    cfg=lvt_amd.RelocConfig(min_disparity=case["min_disparity"]))
+
+
+def test_correspond_refusals_without_a_device(hip_lib):
+    """host code: every refusal of lvt_amd_reloc_correspond is decided before the device is touched"""
+    import dataclasses
+    import reloc_cases
+    case, _ = reloc_cases.case_and_answer("A-N1-M3300")
+    for change, word in ((dict(sensor=3), "sensor"), (dict(map_copy=2), "map_copy"), (dict(lost_frame=-1), "lost_frame"), (dict(min_disparity=0.0), "min_disparity"),
+                         (dict(sensor=2), "NULL"), (dict(prm=dataclasses.replace(case["prm"], img_height=0)), "parameters")):
+        with pytest.raises(ValueError) as e:
+            _correspond(hip_lib, dict(case, **change))
+        assert word in str(e.value) and str(e.value).startswith("lvt_amd_reloc_correspond: ") and str(e.value).endswith("(nothing was changed)"), str(e.value)
+    big = np.zeros((4097, 2), np.float32)
+    with pytest.raises(ValueError, match="4096.*nothing was changed"):
+        _correspond(hip_lib, dict(case, xy_l=big, desc_l=np.zeros((4097, 32), np.uint8)))

@@ -75,37 +75,21 @@ def leg_call():
             "n_refined_inliers": r.n_refined_inliers}
 
 
-def _noise_frame(epoch):
-    """one texture epoch of the full-map recipe: noise, columns [0, 300) the same in every epoch (the pose stays solvable on the 300 corners there), the right
-    eye the left one moved 12 px (z ~ 32 m), 3 700 fresh corners per epoch"""
-    import numpy as np
-    W, H, disp = 1241, 376, 12
-    rng0 = np.random.default_rng(0)
-    fixed = rng0.integers(0, 256, (H, W), dtype=np.uint8)
-    keep = np.column_stack([rng0.integers(52, 270, 300), rng0.integers(40, H - 40, 300)])
-    rng = np.random.default_rng(100 + epoch)
-    L = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    L[:, :300] = fixed[:, :300]
-    R = np.ascontiguousarray(np.roll(L, -disp, axis=1))
-    fresh = np.column_stack([rng.integers(340, W - 40, 3700), rng.integers(40, H - 40, 3700)])
-    cl = np.unique(np.vstack([keep, fresh]), axis=0).astype(np.float64)
-    return L, R, cl, cl - [[float(disp), 0.0]]
-
-
 def leg_fullmap():
     sys.path.insert(0, ROOT)
     import numpy as np
     import lvt_amd
+    from lvt_amd.synth import noise_frame
     prm = lvt_amd.kitti_params(width=1241, height=376)
     prm.triangulation_policy, prm.staged_threshold, prm.untracked_threshold = 2, 0, 1000
     s = lvt_amd.LvtSystem.create(prm, 1)
     for e in range(12):
-        s.track_with_external_corners(*_noise_frame(e))
+        s.track_with_external_corners(*noise_frame(e))
     map_size, state = s.counts()["map_size"], s.get_state()
     flat = np.full((376, 1241), 110, np.uint8)
     s.track(flat, flat)
     lost = s.get_state()
-    s.track_with_external_corners(*_noise_frame(4))      # (an epoch whose points are in the map: those behind the cut never got in)
+    s.track_with_external_corners(*noise_frame(4))      # (an epoch whose points are in the map: those behind the cut never got in)
     ts = []
     for _ in range(25):
         t0 = time.perf_counter()
