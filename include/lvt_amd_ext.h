@@ -246,6 +246,26 @@ LVT_API int lvt_amd_get_matches(lvt_handle h, int *feat_idx, double *xyz, int ca
 LVT_API int lvt_amd_get_row_matches(lvt_handle h, int *pairs, int cap);
 LVT_API int lvt_amd_get_map(lvt_handle h, double *xyz, int *counter, int *age, uint8_t *desc, int cap);
 LVT_API int lvt_amd_get_staged(lvt_handle h, double *xyz, int *counter, uint8_t *desc, int cap);
+/* The candidate lists of the last frame, as the list builders left them (for tests that hold the builders to a reference list by list).  Every match starts from
+ * such a list: per query the train features that pass the window predicate, as keys (distance << 16 | index), ascending.  which = LVT_AMD_LISTS_MAP: the map
+ * points' lists against the left features (of the second pass, where one ran), _STAGED: the staged points' lists behind the pose, _ROW: the left features' lists
+ * against the right features.  keys (n x kc words) and counts (n): valid are keys[q][0 .. min(counts[q], kc)); a count above kc says the list overflowed and only
+ * the count holds.  proj (n x 2) / vis (n): the queries of the map / staged lists as the device used them (untouched for _ROW, whose queries are the left
+ * features).  Lists the frame did not build (first frame, LOST at its start, RGB-D row lists, staged lists without a pose or without staging) come back with n = 0.
+ * A single-sequence handle only; host side only (copies behind a drain: no launch, nothing a frame computes changes).  Any pointer may be NULL (not copied).
+ * Returns n, or -1: bad handle, a batch, `which` out of range, cap < n (info, when given, is filled in nevertheless). */
+enum { LVT_AMD_LISTS_MAP = 0, LVT_AMD_LISTS_STAGED = 1, LVT_AMD_LISTS_ROW = 2 };
+typedef struct {
+    int kc;                 /* list capacity */
+    int stood_down_map;     /* the binned list kernel left this frame's early map lists / row lists to the wavefront-per-query builder behind it */
+    int stood_down_row;     /* (0 on a handle that does not run the binned kernel) */
+    int pass2;              /* find_matches' second pass ran: the map lists are those of the doubled radius */
+    int n_early;            /* map points [0, n_early) were listed on the early stream, the rest by the frame's own prologue */
+    int binned;             /* the handle runs the binned list kernel in front of the wavefront-per-query builders */
+    int n;                  /* queries of the lists asked for (what the call returns when cap suffices) */
+    int reserved;
+} lvt_amd_list_info;
+LVT_API int lvt_amd_get_candidate_lists(lvt_handle h, int which, unsigned *keys, int *counts, float *proj, signed char *vis, int cap, lvt_amd_list_info *info);
 LVT_API void lvt_amd_get_pose(lvt_handle h, double q_wxyz[4], double p[3]);
 /* pose (as the tracker holds it) and state (1 / 2 / 3, -1 on error) of the frame the last tracking call returned; unlike lvt_amd_get_pose and
    lvt_get_status it does not wait for that frame's tail (staged update, triangulation) when the call returned on the early pose */

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "lvt_amd_default_params", "lvt_amd_params_from_file", "lvt_amd_create", "lvt_amd_reset",
     "lvt_amd_track_rgbd", "lvt_amd_track_device", "lvt_amd_track_device_async", "lvt_amd_wait",
     "lvt_amd_set_stream", "lvt_amd_last_error", "lvt_amd_get_counts", "lvt_amd_get_features",
-    "lvt_amd_get_matches", "lvt_amd_get_row_matches", "lvt_amd_get_map", "lvt_amd_get_staged",
+    "lvt_amd_get_matches", "lvt_amd_get_row_matches", "lvt_amd_get_map", "lvt_amd_get_staged", "lvt_amd_get_candidate_lists",
     "lvt_amd_get_pose", "lvt_amd_get_last_pose", "lvt_amd_get_predicted_pose", "lvt_amd_get_plane", "lvt_amd_pnp", "lvt_amd_pnp_detail",
     "lvt_amd_hamming_match_batched", "lvt_amd_hamming_match_batched_n", "lvt_amd_rectifier_create", "lvt_amd_rectifier_destroy",
     "lvt_amd_rectify_device", "lvt_amd_rectify", "lvt_amd_rectifier_get_maps",
@@ -54,6 +54,9 @@ N_COUNTS = 32
 COUNT_NAMES = ["n_left", "n_right", "map_size", "staged_size", "n_matches", "second_pass", "n_row_matches",
                "n_triangulated", "triangulated", "retry_left", "retry_right", "pnp_iters", "pnp_inliers",
                "map_size_at_match", "n_staged_erased", "n_staged_promoted", "n_culled", "frame", "overflow", "pnp_borderline", "row_fallback", "pnp_trials", "pnp_rejections", "pnp_terminates"]
+
+LISTS_WHICH = {"map": 0, "staged": 1, "row": 2}   # LVT_AMD_LISTS_*
+LIST_INFO_NAMES = ["kc", "stood_down_map", "stood_down_row", "pass2", "n_early", "binned", "n"]   # lvt_amd_list_info
 
 eState_NOT_INITIALIZED, eState_TRACKING, eState_LOST = 1, 2, 3
 eSensor_STEREO, eSensor_RGBD = 1, 2
@@ -117,6 +120,8 @@ def load_library():
     L.lvt_amd_get_row_matches.argtypes = [vp, vp, C.c_int]
     L.lvt_amd_get_map.argtypes = [vp, vp, vp, vp, vp, C.c_int]
     L.lvt_amd_get_staged.argtypes = [vp, vp, vp, vp, C.c_int]
+    L.lvt_amd_get_candidate_lists.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    L.lvt_amd_get_candidate_lists.restype = C.c_int
     L.lvt_amd_get_pose.argtypes = [vp, vp, vp]
     L.lvt_amd_get_last_pose.argtypes = [vp, vp, vp]
     L.lvt_amd_get_predicted_pose.argtypes = [vp, vp, vp]
@@ -869,6 +874,27 @@ class LvtSystem:
         xyz = np.zeros((cap, 3)); cnt = np.zeros(cap, np.int32); desc = np.zeros((cap, 32), np.uint8)
         n = load_library().lvt_amd_get_staged(self._h, _p(xyz), _p(cnt), _p(desc), cap)
         return xyz[:n].copy(), cnt[:n].copy(), desc[:n].copy()
+
+    def candidate_lists(self, which, cap=None):
+        """the last frame's candidate lists as their builders left them (lvt_amd_get_candidate_lists): which = 'map' | 'staged' | 'row'.
+        Returns a dict: keys (n x kc uint32, distance << 16 | index), counts (n), proj (n x 2 f32) and vis (n int8) -- the map / staged queries as the
+        device used them, empty for 'row' -- and info (the lvt_amd_list_info record as a dict).  Raises ValueError when the library refuses the call."""
+        w = LISTS_WHICH[which] if isinstance(which, str) else int(which)
+        L = load_library()
+        info = np.zeros(8, np.int32)
+        if cap is None:   # the size first (a call with no room fills in the record only)
+            L.lvt_amd_get_candidate_lists(self._h, w, None, None, None, None, 0, _p(info))
+            cap = int(info[6])
+        kc = 128
+        keys = np.zeros((max(cap, 1), kc), np.uint32); counts = np.zeros(max(cap, 1), np.int32)
+        proj = np.zeros((max(cap, 1), 2), np.float32); vis = np.zeros(max(cap, 1), np.int8)
+        n = L.lvt_amd_get_candidate_lists(self._h, w, _p(keys), _p(counts), _p(proj), _p(vis), cap, _p(info))
+        if n < 0:
+            raise ValueError("lvt_amd_get_candidate_lists refused the call (bad handle, a batch, `which` out of range, or cap too small)")
+        assert int(info[0]) == kc
+        m = 0 if w == LISTS_WHICH["row"] else n
+        return {"keys": keys[:n].copy(), "counts": counts[:n].copy(), "proj": proj[:m].copy(), "vis": vis[:m].copy(),
+                "info": dict(zip(LIST_INFO_NAMES, (int(v) for v in info[:7])))}
 
     def pose(self):
         q = np.zeros(4); p = np.zeros(3)

@@ -364,6 +364,7 @@ __global__ __launch_bounds__(256) void k_candidates(SeqArg<BV> sa, int pass2, in
         if (S.prm.sensor != 1) return;
         if (need_seq && !seq_reached(S.fb[par].fc->feat_seq, need_seq)) return;
     }
+    if (MODE == MODE_STAGED && blockIdx.x == 0 && threadIdx.x == 0) S.lists_fb[LFB_STAGED_N] = *S.staged_n;  // (debug slot: lvt_amd_get_candidate_lists)
     CAND_LDS_DECL
     candidates_body<MODE>(S, pass2, par, C, blockIdx.x * 4 + wave_id(), gridDim.x * 4, 256);
 }
@@ -1200,7 +1201,10 @@ __global__ __launch_bounds__(RES_THREADS) void k_track_mid(SeqArg<BV> sa, int pa
         const int n_early = early_points_ran(&ctl, seq);
         resolve_body<MODE_MAP>(S, ctl, 0, par, L, r_tab, n_early > 0 ? 2 : 0, n_early);
         __syncthreads();
-        if (threadIdx.x == 0) ctl.early_done = 0;  // consumed; this frame's k_pnp publishes the next one
+        if (threadIdx.x == 0) {
+            ctl.early_done = 0;  // consumed; this frame's k_pnp publishes the next one
+            S.lists_fb[LFB_EARLY_N] = n_early;  // (debug slot: lvt_amd_get_candidate_lists)
+        }
     }
     __syncthreads();
     if (L.misc[2]) {  // rare (< 50 matches): doubled-radius candidate lists are built by this one block

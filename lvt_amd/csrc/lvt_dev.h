@@ -192,6 +192,11 @@ struct FrameBuf {
     FeatCtl *fc;
 };
 
+// words of Seq::lists_fb.  The first two steer the frame (k_candidates / k_early_map run where the binned kernel stood down); the other two are debug slots nobody on
+// the device reads: what lvt_amd_get_candidate_lists reports about the frame whose lists it copies
+enum { LFB_MAP = 0, LFB_ROW = 1, LFB_EARLY_N = 2 /* map points the early stream listed (k_track_mid, as it consumes Ctl::early_done) */,
+       LFB_STAGED_N = 3 /* staged points when k_candidates<STAGED> listed them */, LFB_WORDS = 4 };
+
 struct Seq {
     Params prm;
     Ctl *ctl;
@@ -204,7 +209,7 @@ struct Seq {
     uint32_t *strip_kp[2];
     int *strip_n[2];
     int *cell_big[2];           // [CELLS_MAX] 1: this pass's k_cells left the cell to k_cells_strip / k_cells_big
-    int *lists_fb;              // [2] k_hamming_batched_lists (map / row) stood down: the wave-per-query kernel behind it builds the lists
+    int *lists_fb;              // [LFB_WORDS] k_hamming_batched_lists (map / row) stood down: the wave-per-query kernel behind it builds the lists; + the read-back's debug words
     // map + staged, ping-pong
     MapSoA map[2], staged[2];
     int *map_cur, *map_n, *staged_cur, *staged_n;   // device scalars

@@ -799,7 +799,7 @@ static Context *create_context(const lvt_amd_params *in, bool mixed, int sensor,
                 S.strip_n[e] = c->dalloc_uncached<int>((size_t)CELLS_MAX * STRIPS);
                 S.cell_big[e] = c->dalloc<int>(CELLS_MAX);
             }
-            S.lists_fb = c->dalloc<int>(2);
+            S.lists_fb = c->dalloc<int>(LFB_WORDS);
             for (int par = 0; par < NPAR; par++) {
                 FrameBuf &FB = S.fb[par];
                 FB.fc = c->dalloc<FeatCtl>(1);
@@ -2493,6 +2493,59 @@ LVT_API int lvt_amd_get_staged(lvt_handle h, double *xyz, int *counter, uint8_t 
         Context *c = v.c;
         const Seq &S = c->h_seqs[v.s];
         return get_points(c, S.staged, S.staged_cur, S.staged_n, xyz, counter, nullptr, desc, cap);
+    } catch (...) {
+    }
+    return -1;
+}
+// The candidate lists of the last frame as their builders left them (tests/test_gpu_candidate_lists.py holds them to a reference, list by list): only the
+// builders store to Seq::cand / ncand, scand / sncand and rcand / rncand (candidates_body and k_hamming_batched_lists), and proj / vis, sproj / svis are written
+// by the projections in front of them, so all of it is final once the frame is collected.  Host only: copies, no launch.  The early stream may still be running
+// behind a collected frame (a k_triangulate that built its row lists itself does not wait for the early stream's), so every stream of the handle is
+// synchronised first.  A single-sequence handle only (a batch's lists are the same kernels fetching their Seq differently).
+LVT_API int lvt_amd_get_candidate_lists(lvt_handle h, int which, unsigned *keys, int *counts, float *proj, signed char *vis, int cap, lvt_amd_list_info *info) {
+    h = resolve_handle(h);
+    if (!is_ctx(h) || which < LVT_AMD_LISTS_MAP || which > LVT_AMD_LISTS_ROW) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (c->B != 1) return -1;
+    DeviceGuard guard(c);
+    try {
+        drain(c);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream_f));
+        HIPCHK(c, hipStreamSynchronize(c->stream_e));
+        const Seq &S = c->h_seqs[0];
+        const Ctl &rec = last_ctl(c);
+        const int par = c->last_par;
+        int fbw[LFB_WORDS] = {0, 0, 0, 0};
+        d2h(c, fbw, S.lists_fb, (size_t)LFB_WORDS);
+        // what the frame built: nothing before the first frame is collected; map lists on a frame that tracked against a map; staged lists behind a pose, where points
+        // are staged at all; row lists on every stereo frame whose features the frame kept (a LOST frame's epilogue hides them: its count is 0)
+        const bool tracked = c->done > 0 && rec.active && !rec.first_frame;
+        int n = 0;
+        if (which == LVT_AMD_LISTS_MAP && tracked) n = rec.counts[C_MAP_SIZE_AT_MATCH];
+        if (which == LVT_AMD_LISTS_STAGED && tracked && !rec.lost_now && S.prm.staged_th > 0) n = fbw[LFB_STAGED_N];
+        if (which == LVT_AMD_LISTS_ROW && c->done > 0 && c->sensor == 1) n = rec.counts[C_N_LEFT];
+        const int lim = which == LVT_AMD_LISTS_MAP ? MAP_MAX : which == LVT_AMD_LISTS_STAGED ? STAGED_MAX : NF_MAX;
+        n = std::min(std::max(n, 0), lim);
+        if (info) {
+            info->kc = KC;
+            info->stood_down_map = fbw[LFB_MAP], info->stood_down_row = fbw[LFB_ROW];
+            info->pass2 = tracked ? rec.do_pass2 : 0;
+            info->n_early = tracked ? fbw[LFB_EARLY_N] : 0;
+            info->binned = c->binned_lists ? 1 : 0;
+            info->n = n;
+            info->reserved = 0;
+        }
+        if (n > cap) return -1;
+        const uint32_t *dk = which == LVT_AMD_LISTS_MAP ? S.cand : which == LVT_AMD_LISTS_STAGED ? S.scand : S.rcand + (size_t)par * NF_MAX * KC;
+        const int *dn = which == LVT_AMD_LISTS_MAP ? S.ncand : which == LVT_AMD_LISTS_STAGED ? S.sncand : S.rncand + (size_t)par * NF_MAX;
+        d2h(c, keys, dk, (size_t)n * KC);
+        d2h(c, counts, dn, (size_t)n);
+        if (which != LVT_AMD_LISTS_ROW) {
+            d2h(c, proj, which == LVT_AMD_LISTS_MAP ? S.proj : S.sproj, (size_t)n * 2);
+            d2h(c, reinterpret_cast<int8_t *>(vis), which == LVT_AMD_LISTS_MAP ? S.vis : S.svis, (size_t)n);
+        }
+        return n;
     } catch (...) {
     }
     return -1;

@@ -250,9 +250,10 @@ def test_candidate_lists_longer_than_their_capacity(hip_lib, oracle_lib, monkeyp
 
 @pytest.mark.parametrize("binned", ["0", "1"], ids=["wave_per_query_lists", "binned_list_kernel"])
 def test_more_than_2048_features_per_image(hip_lib, oracle_lib, monkeypatch, binned):
-    """2 600 external corners per image: more than the 2 048 features the binned list kernel holds in its LDS image -- with
-    LVT_AMD_BINNED_LISTS=1 it must stand down for these frames (k_lists.hip: N > 2048) and the wave-per-query kernels behind it build
-    the lists; either way matches, maps and poses are the oracle's"""
+    """2 600 external corners per image: more than the 1 536 features (LS_NMAX) the binned list kernel holds in its LDS image -- with
+    LVT_AMD_BINNED_LISTS=1 it must stand down for these frames (k_lists.hip: N > 1536) and the wave-per-query kernels behind it build
+    the lists; either way matches, maps and poses are the oracle's.  (The name is from before the kernel's rebuild, when the image held 2 048; the counts
+    at the switch itself -- 1 535, 1 536, 1 537 -- and the stood-down flag are held in test_gpu_candidate_lists.py.)"""
     from oracle import pyoracle as O
     monkeypatch.setenv("LVT_AMD_BINNED_LISTS", binned)
     world, prm, sensor = make_case("kitti", 14, 1.0)
