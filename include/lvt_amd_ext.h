@@ -638,7 +638,7 @@ LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3]
  *    0 and 3 and zero otherwise.  n_features, n_map and n_matched belong to a handle's call; the stage entry leaves them zero.
  *  - lvt_amd_reloc_match_device: stage 1 on DEVICE pointers aligned to 16 bytes: d_query n_query x 32 bytes, d_map n_map x 32 bytes, d_out n_query x 4 int32;
  *    n_query 0 ... 4096, n_map 0 ... 32768.  The map is cut into slices of lvt_amd_reloc_slice_length(n_map) points (32 ... 1024, about 32 slices), a
- *    workgroup holds one slice in LDS.  Two launches on hip_stream; the call allocates its key buffer and frees it after synchronising that stream.  Returns
+ *    workgroup holds one slice in LDS.  Two launches on hip_stream; the call allocates its key buffer and frees it once that stream has run them.  Returns
  *    the time between HIP events around the launches in microseconds, < 0 on a refusal or failure.  Environment, read by this entry alone: LVT_AMD_RELOC_MATCH=uniform
  *    runs the variant that loads the slice's descriptors straight from memory at a wave-uniform address instead of staging them in LDS (same records; for
  *    measurements, profiles/relocalisation.md).

@@ -1132,12 +1132,15 @@ def mixed_tables(params_list, sensor_type: int = eSensor_STEREO):
     return cells, score
 
 
+def _pnp_inputs(params, q_in, p_in, pts, obs):
+    """what lvt_amd_pnp, _pnp_detail and _pnp_trace are called with: the library, the parameter record and the four arrays as the C ABI reads them"""
+    return (load_library(), params.to_pod(), np.ascontiguousarray(q_in, np.float64), np.ascontiguousarray(p_in, np.float64),
+            np.ascontiguousarray(pts, np.float64), np.ascontiguousarray(obs, np.float32))
+
+
 def pnp(params: LvtParameters, q_in, p_in, pts, obs):
     """stage entry: motion-only BA on caller data (reference lvt_pnp_solver.cpp:60-128)"""
-    L = load_library()
-    pod = params.to_pod()
-    q_in = np.ascontiguousarray(q_in, np.float64); p_in = np.ascontiguousarray(p_in, np.float64)
-    pts = np.ascontiguousarray(pts, np.float64); obs = np.ascontiguousarray(obs, np.float32)
+    L, pod, q_in, p_in, pts, obs = _pnp_inputs(params, q_in, p_in, pts, obs)
     q = np.zeros(4); p = np.zeros(3); calls = C.c_int(0)
     inl = L.lvt_amd_pnp(C.byref(pod), _p(q_in), _p(p_in), _p(pts), _p(obs), len(pts), _p(q), _p(p), C.byref(calls))
     if inl < 0:
@@ -1148,10 +1151,7 @@ def pnp(params: LvtParameters, q_in, p_in, pts, obs):
 def pnp_detail(params: LvtParameters, q_in, p_in, pts, obs):
     """lvt_amd_pnp with the chi2 gates laid open: (q, p, inliers, solve calls, err (n x 2: what the second gate saw), level (n: 1 = demoted),
     borderline = gate decisions taken within 1e-8 of the threshold)"""
-    L = load_library()
-    pod = params.to_pod()
-    q_in = np.ascontiguousarray(q_in, np.float64); p_in = np.ascontiguousarray(p_in, np.float64)
-    pts = np.ascontiguousarray(pts, np.float64); obs = np.ascontiguousarray(obs, np.float32)
+    L, pod, q_in, p_in, pts, obs = _pnp_inputs(params, q_in, p_in, pts, obs)
     n = len(pts)
     q = np.zeros(4); p = np.zeros(3); calls = C.c_int(0); border = C.c_int(0)
     err = np.zeros((n, 2)); level = np.zeros(n, np.int32)
@@ -1164,10 +1164,7 @@ def pnp_detail(params: LvtParameters, q_in, p_in, pts, obs):
 def pnp_trace(params: LvtParameters, q_in, p_in, pts, obs, trace_cap=256):
     """lvt_amd_pnp_trace: (q, p, inliers, solve calls, trace rows (trials x 4: lambda, chi2 at the estimate, chi2 of the trial, rho),
     (trials, rejections, terminates))"""
-    L = load_library()
-    pod = params.to_pod()
-    q_in = np.ascontiguousarray(q_in, np.float64); p_in = np.ascontiguousarray(p_in, np.float64)
-    pts = np.ascontiguousarray(pts, np.float64); obs = np.ascontiguousarray(obs, np.float32)
+    L, pod, q_in, p_in, pts, obs = _pnp_inputs(params, q_in, p_in, pts, obs)
     q = np.zeros(4); p = np.zeros(3); calls = C.c_int(0)
     tr = np.zeros((trace_cap, 4)); st = np.zeros(3, np.int32)
     inl = L.lvt_amd_pnp_trace(C.byref(pod), _p(q_in), _p(p_in), _p(pts), _p(obs), len(pts), _p(q), _p(p), C.byref(calls), None, None, None,

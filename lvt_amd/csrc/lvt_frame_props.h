@@ -472,16 +472,15 @@ LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void 
     if (!cfg || !d_src || !d_dst || w < 1 || w > 8192 || h < 1 || h > 8192 || !equalisation_check(*cfg, w, h).empty()) return -1;
     if (src_pitch < w || dst_pitch < w || (dst_pitch & 3) || ((uintptr_t)d_dst & 3) || (long long)dst_pitch * h > 0x7FFFFFFFll) return -1;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    uint8_t *lut = nullptr;
-    if (hipMalloc((void **)&lut, (size_t)cfg->tiles_x * cfg->tiles_y * 256) != hipSuccess) return -1;
+    StageScratch S;  // (lvt_stage_entries.h)
+    uint8_t *lut = S.buf<uint8_t>((size_t)cfg->tiles_x * cfg->tiles_y * 256);
+    if (!S.ok()) return -1;
     ClaheTable tab;
     std::memset(&tab, 0, sizeof(tab));
     tab.im[0] = clahe_img(*cfg, static_cast<const uint8_t *>(d_src), src_pitch, w, h, static_cast<uint8_t *>(d_dst), dst_pitch, lut, clahe_direct());
     hipLaunchKernelGGL(k_clahe_lut, dim3(cfg->tiles_x * cfg->tiles_y, 1), dim3(256), 0, st, tab);
     hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)(((size_t)(dst_pitch / 4) * h + 255) / 256), 1), dim3(256), 0, st, tab);
-    const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-    (void)hipFree(lut);
-    return ok ? 0 : -1;
+    return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
 }
 
 LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) { return enable_pose_info(h, enable); }

@@ -129,8 +129,6 @@ static void launch_stage_copy(hipStream_t st, const uint8_t *src, float *d_dst, 
 // Counted PER DEVICE: handles on different GPUs of one process share no hardware queue and no CU.
 constexpr int MAX_DEVICES = 64;
 static std::atomic<int> g_live_contexts[MAX_DEVICES];
-// snapshots: why the calling thread's last lvt_amd_snapshot_import / _describe was refused (they have no handle to report to: lvt_amd_last_error(NULL))
-static thread_local std::string g_snap_err;
 
 // An lvt_handle is either a Context (a sequence, or a lock-step batch, with its own launch chain) or a PoolSlot (lvt_pool.h: one sequence of a
 // lock-step batch SHARED by the pooled handles of a device); the first word tells them apart.
@@ -1491,6 +1489,13 @@ static int refuse(lvt_handle h, const char *who, const std::string &why) {
         static_cast<Context *>(h)->set_error(msg);
     return -1;
 }
+// The calling thread's last refusal from a call that has no handle to report to -- a stage entry, a snapshot import or describe, the odometry accumulator's
+// relocalisation policy: lvt_amd_last_error(NULL) reads it.  Only refuse_call writes it.
+static thread_local std::string g_call_refusal;
+static int refuse_call(const char *who, const std::string &why) {
+    g_call_refusal = std::string(who) + ": " + why;
+    return -1;
+}
 // what an entry point says to a pooled handle / a handle of the other sensor / a batch handle where it takes solo ones (nullptr: refused without a report)
 struct Refusals {
     const char *pooled, *sensor, *batch;
@@ -1557,6 +1562,7 @@ static const uint8_t *host_plane(Context *c, const uint8_t *view, const void *sr
 
 using namespace lvt;
 
+#include "lvt_stage_entries.h"
 #include "lvt_frame_props.h"
 
 // =================================================================================================
@@ -1690,7 +1696,7 @@ LVT_API const char *lvt_amd_last_error(lvt_handle h) {
         acopy = lvt_amd_last_error(A->impl);
         return acopy.c_str();
     }
-    if (!h) return g_snap_err.empty() ? "no handle (creation failed: bad parameters, or no HIP device -- there is no CPU fallback)" : g_snap_err.c_str();
+    if (!h) return g_call_refusal.empty() ? "no handle (creation failed: bad parameters, or no HIP device -- there is no CPU fallback)" : g_call_refusal.c_str();
     if (is_slot(h)) {
         PoolSlot *S = static_cast<PoolSlot *>(h);
         std::lock_guard<std::mutex> g(S->pool->mu);
@@ -2678,198 +2684,8 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
     return -1;
 }
 
-// ---- stage entry: motion-only BA on caller data ---------------------------------------------------
-// err_out (2n doubles, may be NULL): the edge errors the second chi2 gate saw; level_out (n ints, may be NULL): 1 = demoted by a gate;
-// *borderline (may be NULL): gate decisions taken within PNP_GATE_MARGIN of the threshold
-// trace (trace_cap rows x 4 doubles, may be NULL): one row per LM trial {lambda, chi2 at the estimate, chi2 of the trial, rho}; stats (may be NULL):
-// {trials, rejected trials, passes ended by Terminate}
-LVT_API int lvt_amd_pnp_trace(const lvt_amd_params *pin, const double q_in[4], const double p_in[3], const double *pts, const float *obs, int n,
-                              double q_out[4], double p_out[3], int *n_solve_calls, double *err_out, int *level_out, int *borderline,
-                              double *trace, int trace_cap, int stats[3]) {
-    Params prm;
-    lvt_amd_params tmp = *pin;
-    if (tmp.img_width <= 0) tmp.img_width = 64;
-    if (tmp.img_height <= 0) tmp.img_height = 64;
-    if (!derive_params(tmp, 1, prm)) return -1;
-    double *dX = nullptr, *dErr = nullptr;
-    float *dObs = nullptr;
-    int8_t *dLevel = nullptr;
-    Pose *dOut = nullptr;
-    int *dInfo = nullptr;
-    double *dTrace = nullptr;
-    if (!trace || trace_cap < 0) trace_cap = 0;
-    int rc = -1;
-    const size_t nn = (size_t)std::max(n, 1);
-    if (hipMalloc((void **)&dX, nn * 24) == hipSuccess && hipMalloc((void **)&dErr, nn * 16 + 16) == hipSuccess &&
-        hipMalloc((void **)&dObs, nn * 8) == hipSuccess && hipMalloc((void **)&dLevel, nn) == hipSuccess &&
-        hipMalloc((void **)&dOut, sizeof(Pose)) == hipSuccess && hipMalloc((void **)&dInfo, 32) == hipSuccess &&
-        hipMalloc((void **)&dTrace, (size_t)std::max(trace_cap, 1) * 32) == hipSuccess) {
-        (void)hipMemcpy(dX, pts, (size_t)n * 24, hipMemcpyHostToDevice);
-        (void)hipMemcpy(dObs, obs, (size_t)n * 8, hipMemcpyHostToDevice);
-        Pose prior;
-        for (int k = 0; k < 4; k++) prior.q[k] = q_in[k];
-        for (int k = 0; k < 3; k++) prior.p[k] = p_in[k];
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pnp_standalone), hipFuncAttributeMaxDynamicSharedMemorySize, PNP_DYN_BYTES);
-        hipLaunchKernelGGL(k_pnp_standalone, dim3(1), dim3(PNP_THREADS), PNP_DYN_BYTES, 0, prm, prior, dX, dObs, dErr, dLevel, n, dOut, dInfo,
-                           trace_cap ? dTrace : (double *)nullptr, trace_cap);
-        Pose out;
-        int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpy(&out, dOut, sizeof(Pose), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(info, dInfo, 32, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (stats) stats[0] = info[3], stats[1] = info[4], stats[2] = info[5];
-            if (trace_cap && hipMemcpy(trace, dTrace, (size_t)std::min(trace_cap, std::max(info[3], 0)) * 32, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
-            for (int k = 0; k < 4; k++) q_out[k] = out.q[k];
-            for (int k = 0; k < 3; k++) p_out[k] = out.p[k];
-            if (n_solve_calls) *n_solve_calls = info[0];
-            if (borderline) *borderline = info[2];
-            rc = (rc == -2) ? -1 : info[1];
-            if (err_out && hipMemcpy(err_out, dErr, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
-            if (level_out) {
-                std::vector<int8_t> lv((size_t)std::max(n, 1));
-                if (hipMemcpy(lv.data(), dLevel, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
-                for (int i = 0; i < n; i++) level_out[i] = lv[i];
-            }
-        }
-    }
-    (void)hipFree(dX), (void)hipFree(dErr), (void)hipFree(dObs), (void)hipFree(dLevel), (void)hipFree(dOut), (void)hipFree(dInfo), (void)hipFree(dTrace);
-    return rc;
-}
-LVT_API int lvt_amd_pnp_detail(const lvt_amd_params *pin, const double q_in[4], const double p_in[3], const double *pts, const float *obs, int n,
-                               double q_out[4], double p_out[3], int *n_solve_calls, double *err_out, int *level_out, int *borderline) {
-    return lvt_amd_pnp_trace(pin, q_in, p_in, pts, obs, n, q_out, p_out, n_solve_calls, err_out, level_out, borderline, nullptr, 0, nullptr);
-}
-LVT_API int lvt_amd_pnp(const lvt_amd_params *pin, const double q_in[4], const double p_in[3], const double *pts, const float *obs, int n,
-                        double q_out[4], double p_out[3], int *n_solve_calls) {
-    return lvt_amd_pnp_detail(pin, q_in, p_in, pts, obs, n, q_out, p_out, n_solve_calls, nullptr, nullptr, nullptr);
-}
-
-// ---- stage entry: the constant-velocity motion model on caller data (the contract of the oracle's lvto_motion_predict) -------------
-// state = {last_q[4], ang_vel[4], last_p[3], lin_vel[3]} in, the model's next state out; (q, p) the current pose; runs on the current device.  0 / -1
-LVT_API int lvt_amd_motion_predict(double state[14], const double q[4], const double p[3], double q_out[4], double p_out[3]) {
-    if (!state || !q || !p || !q_out || !p_out) return -1;
-    Ctl *dCtl = nullptr;
-    double *dIo = nullptr;
-    double io[21];
-    for (int k = 0; k < 14; k++) io[k] = state[k];
-    for (int k = 0; k < 4; k++) io[14 + k] = q[k];
-    for (int k = 0; k < 3; k++) io[18 + k] = p[k];
-    int rc = -1;
-    if (hipMalloc((void **)&dCtl, sizeof(Ctl)) == hipSuccess && hipMalloc((void **)&dIo, sizeof(io)) == hipSuccess &&
-        hipMemset(dCtl, 0, sizeof(Ctl)) == hipSuccess && hipMemcpy(dIo, io, sizeof(io), hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_motion_predict_standalone, dim3(1), dim3(64), 0, 0, dCtl, dIo);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(io, dIo, sizeof(io), hipMemcpyDeviceToHost) == hipSuccess) {
-            for (int k = 0; k < 14; k++) state[k] = io[k];
-            for (int k = 0; k < 4; k++) q_out[k] = io[14 + k];
-            for (int k = 0; k < 3; k++) p_out[k] = io[18 + k];
-            rc = 0;
-        }
-    }
-    (void)hipFree(dCtl), (void)hipFree(dIo);
-    return rc;
-}
-
-
-// ---- stage entry: batched masked 2-NN Hamming matcher on device-resident problems --------------------
-LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_xy, const void *t_desc, const void *t_xy, const void *t_flag,
-                                              int B, int M, int N, float r2, int mode, int img_rows, int img_cols, void *out,
-                                              void *hip_stream, int launches) {
-    if (launches < 1) launches = 1;
-    if (B > 0 && M > 0 && M <= HB_MMAX && N == 0) {  // an empty train set: knnMatch returns nothing for every query
-        hipLaunchKernelGGL(k_hamming_none, dim3((unsigned)(((size_t)B * M + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
-                           static_cast<int4 *>(out), (size_t)B * M);
-        return hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)) == hipSuccess ? 0.0f : -1.0f;
-    }
-    if (B <= 0 || M <= 0 || N <= 0 || N > HB_NMAX || M > HB_MMAX) {
-        std::fprintf(stderr, "lvt_amd_hamming_match_batched: bad sizes B=%d M=%d N=%d (N <= %d, M <= %d)\n", B, M, N, HB_NMAX, HB_MMAX);
-        return -1.0f;
-    }
-    HammingArgs a;
-    a.q_desc = static_cast<const uint64_t *>(q_desc);
-    a.q_xy = static_cast<const float2 *>(q_xy);
-    a.t_desc = static_cast<const uint64_t *>(t_desc);
-    a.t_xy = static_cast<const float2 *>(t_xy);
-    a.t_flag = static_cast<const uint8_t *>(t_flag);
-    a.out = static_cast<int4 *>(out);
-    a.M = M, a.N = N, a.r2 = r2, a.img_rows = img_rows, a.img_cols = img_cols;
-    a.dbg = nullptr;
-    long long *d_dbg = nullptr;
-    if (std::getenv("LVT_AMD_HAMMING_DEBUG") && hipMalloc((void **)&d_dbg, 64) == hipSuccess && hipMemset(d_dbg, 0, 64) == hipSuccess) a.dbg = d_dbg;
-    if (mode == 1) {
-        a.nbx = 1, a.nby = img_rows + 1, a.csr = 0;
-    } else {
-        a.nbx = (int)std::ceil(img_cols / (float)HASH_CELL), a.nby = (int)std::ceil(img_rows / (float)HASH_CELL);
-        a.csr = std::max(1, (int)std::ceil(std::sqrt(r2) / (float)HASH_CELL));
-    }
-    // the variant fixes how many candidate ranges a query keeps in registers (k_hamming.hip)
-    void (*kern)(HammingArgs) = nullptr;
-    {
-        const int qpt = (M + HB_THREADS - 1) / HB_THREADS;
-        const int tpt = (N + HB_THREADS - 1) / HB_THREADS;
-#define LVT_PICK_T(MODE_, NSP_, Q_)                                                                                               \
-    ((tpt == 1) ? k_hamming_batched<MODE_, NSP_, Q_, 1> : (tpt == 2) ? k_hamming_batched<MODE_, NSP_, Q_, 2> :                   \
-     (tpt == 3) ? k_hamming_batched<MODE_, NSP_, Q_, 3> : k_hamming_batched<MODE_, NSP_, Q_, 4>)
-#define LVT_PICK(MODE_, NSP_)                                                                                                     \
-    kern = (qpt == 1) ? LVT_PICK_T(MODE_, NSP_, 1) : (qpt == 2) ? LVT_PICK_T(MODE_, NSP_, 2) : (qpt == 3) ? LVT_PICK_T(MODE_, NSP_, 3) \
-                                                                                                          : LVT_PICK_T(MODE_, NSP_, 4)
-        if (mode == 1) LVT_PICK(1, 1);
-        else if (a.csr == 1) LVT_PICK(0, 3);
-        else if (a.csr == 2) LVT_PICK(0, 5);
-        else LVT_PICK(0, 0);
-#undef LVT_PICK_T
-#undef LVT_PICK
-    }
-    // a workgroup's 160 KiB hold the carve-up AND the kernel's static arrays (s_scan, s_hist, s_recheck): a size that leaves them no room is refused
-    // here, not at the launch
-    const size_t lds = hamming_lds_bytes(N, M, a.nbx * a.nby);
-    hipFuncAttributes fattr;
-    if (hipFuncGetAttributes(&fattr, reinterpret_cast<const void *>(kern)) != hipSuccess) {
-        std::fprintf(stderr, "lvt_amd_hamming_match_batched: hipFuncGetAttributes failed\n");
-        return -1.0f;
-    }
-    if (lds + fattr.sharedSizeBytes > 160 * 1024) {
-        std::fprintf(stderr, "lvt_amd_hamming_match_batched: %zu + %zu bytes of LDS needed\n", lds, (size_t)fattr.sharedSizeBytes);
-        return -1.0f;
-    }
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    hipEvent_t e0, e1;
-    {
-        const hipError_t c0 = hipEventCreate(&e0), c1 = hipEventCreate(&e1);
-        if (c0 != hipSuccess || c1 != hipSuccess) {
-            std::fprintf(stderr, "lvt_amd_hamming_match_batched: hipEventCreate failed: %s / %s\n", hipGetErrorString(c0), hipGetErrorString(c1));
-            return -1.0f;
-        }
-    }
-    float ms = -1.0f;
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipEventRecord(e0, st);
-    for (int l = 0; l < launches; l++) hipLaunchKernelGGL(kern, dim3(B), dim3(HB_THREADS), lds, st, a);
-    const hipError_t elaunch = hipGetLastError();
-    (void)hipEventRecord(e1, st);
-    const hipError_t es = hipEventSynchronize(e1);
-    hipError_t ee = hipErrorUnknown;
-    if (es == hipSuccess && elaunch == hipSuccess) ee = hipEventElapsedTime(&ms, e0, e1);
-    if (ee != hipSuccess || ms < 0)
-        std::fprintf(stderr, "lvt_amd_hamming_match_batched: attr=%s launch=%s sync=%s elapsed=%s ms=%f (B=%d M=%d N=%d lds=%zu)\n",
-                     hipGetErrorString(ea), hipGetErrorString(elaunch), hipGetErrorString(es), hipGetErrorString(ee), ms, B, M, N, lds);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (d_dbg) {
-        long long hd[8] = {};
-        (void)hipMemcpy(hd, d_dbg, 64, hipMemcpyDeviceToHost);
-        if (hd[7] == 0) hd[7] = hd[5];
-        std::fprintf(stderr, "hamming phases (cycles): load+zero %lld count %lld scan %lld scatter+qcount %lld qsort %lld radius+qsort2 %lld descriptors %lld total %lld\n",
-                     hd[1] - hd[0], hd[2] - hd[1], hd[3] - hd[2], hd[4] - hd[3], hd[5] - hd[4], hd[7] - hd[5], hd[6] - hd[7], hd[6] - hd[0]);
-        (void)hipFree(d_dbg);
-    }
-    return (ee != hipSuccess || ms < 0) ? -1.0f : ms * 1000.0f / (float)launches;
-}
-
-LVT_API float lvt_amd_hamming_match_batched(const void *q_desc, const void *q_xy, const void *t_desc, const void *t_xy, const void *t_flag,
-                                            int B, int M, int N, float r2, int mode, int img_rows, int img_cols, void *out,
-                                            void *hip_stream) {
-    return lvt_amd_hamming_match_batched_n(q_desc, q_xy, t_desc, t_xy, t_flag, B, M, N, r2, mode, img_rows, img_cols, out, hip_stream, 1);
-}
-
+// (the stage entries -- lvt_amd_pnp*, lvt_amd_motion_predict, lvt_amd_hamming_match_batched*, lvt_amd_pose_info_eval, lvt_amd_reloc_match_device / _solve /
+// _correspond: lvt_stage_entries.h)
 
 // ---- EuRoC pre-step: rectification -------------------------------------------------------------------------------------
 LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9], const double Pnew[9], int width,
@@ -2951,32 +2767,6 @@ LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier h, float *map1, float *
 }
 
 // (the properties of a handle -- rectifiers, pixel format, depth camera, pose info -- and their entry points: lvt_frame_props.h)
-// ---- stage entry: the pose-uncertainty record on caller data (k_poseinfo.hip) ---------------------------------------------------------------------
-LVT_API int lvt_amd_pose_info_eval(const lvt_amd_params *pin, const double q_wxyz[4], const double pos[3], const double *pts, const float *obs, int n,
-                                   lvt_amd_pose_info *out) {
-    if (!pin || !q_wxyz || !pos || !out || n < 0 || n > NF_MAX || (n > 0 && (!pts || !obs))) return -1;
-    Params prm;
-    lvt_amd_params tmp = *pin;
-    if (tmp.img_width <= 0) tmp.img_width = 64;
-    if (tmp.img_height <= 0) tmp.img_height = 64;
-    if (!derive_params(tmp, 1, prm)) return -1;
-    double *dX = nullptr;
-    float *dObs = nullptr;
-    lvt_amd_pose_info *dOut = nullptr;
-    int rc = -1;
-    const size_t nn = (size_t)std::max(n, 1);
-    if (hipMalloc((void **)&dX, nn * 24) == hipSuccess && hipMalloc((void **)&dObs, nn * 8) == hipSuccess &&
-        hipMalloc((void **)&dOut, sizeof(lvt_amd_pose_info)) == hipSuccess &&
-        (n == 0 || (hipMemcpy(dX, pts, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dObs, obs, (size_t)n * 8, hipMemcpyHostToDevice) == hipSuccess))) {
-        Pose pose;
-        for (int k = 0; k < 4; k++) pose.q[k] = q_wxyz[k];
-        for (int k = 0; k < 3; k++) pose.p[k] = pos[k];
-        hipLaunchKernelGGL(k_pose_info_standalone, dim3(1), dim3(PI_THREADS), 0, 0, prm, pose, dX, dObs, n, dOut);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dOut, sizeof(lvt_amd_pose_info), hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-    }
-    (void)hipFree(dX), (void)hipFree(dObs), (void)hipFree(dOut);
-    return rc;
-}
 // host only: the rotation part moved from camera axes to fixed world axes, M cov M^T with M = blockdiag(I, R)
 LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3], double cov_ros[36]) {
     if (!cov || !R || !cov_ros) return;
@@ -2988,250 +2778,13 @@ LVT_API void lvt_amd_pose_info_to_ros(const double cov[36], const double R[3][3]
     sandwich6(M, cov, cov_ros);
 }
 
-// ---- relocalisation: the stages alone on caller data (k_reloc.hip; the definition is in include/lvt_amd_ext.h, "RELOCALISATION") -------------------
+// ---- relocalisation: the defaults and the slice length (the stages alone on caller data, and what they share with a handle's call: lvt_stage_entries.h) ----
 LVT_API void lvt_amd_reloc_default_config(lvt_amd_reloc_config *cfg) {
     if (!cfg) return;
     *cfg = lvt_amd_reloc_config{};
     cfg->n_hypotheses = 256, cfg->gate_px2 = 16.0f, cfg->min_disparity = 1.0f, cfg->min_inliers = 30, cfg->seed = 0, cfg->dry_run = 0;
 }
-// "" when every field is in range, else the complete sentence of the refusal (it names the field)
-static std::string reloc_config_fault(const lvt_amd_reloc_config &c) {
-    char b[200] = "";
-    if (c.n_hypotheses < 1 || c.n_hypotheses > RELOC_HYP_MAX)
-        snprintf(b, sizeof b, "n_hypotheses is %d: it must be 1 ... %d (nothing was changed)", c.n_hypotheses, RELOC_HYP_MAX);
-    else if (!(std::isfinite(c.gate_px2) && c.gate_px2 > 0))
-        snprintf(b, sizeof b, "gate_px2 is %g: it must be finite and > 0 (nothing was changed)", (double)c.gate_px2);
-    else if (!(std::isfinite(c.min_disparity) && c.min_disparity > 0))
-        snprintf(b, sizeof b, "min_disparity is %g: it must be finite and > 0 (nothing was changed)", (double)c.min_disparity);
-    else if (c.min_inliers < 3)
-        snprintf(b, sizeof b, "min_inliers is %d: it must be >= 3 (nothing was changed)", c.min_inliers);
-    else if (c.dry_run != 0 && c.dry_run != 1)
-        snprintf(b, sizeof b, "dry_run is %d: it must be 0 or 1 (nothing was changed)", c.dry_run);
-    return b;
-}
 LVT_API int lvt_amd_reloc_slice_length(int n_map) { return reloc_slice_length(std::max(n_map, 0)); }
-// stages 1 and 2 of one call: four launches on `st`, the capacity grid, every size read on the device (RelocSeq's scalars and its FeatCtl).  A handle's call
-// (relocalise) and the stage entry lvt_amd_reloc_correspond both come through here: what the entry is held to is what the handle runs.
-static void reloc_launch_correspond(hipStream_t st, const RelocSeq &rs, const uint64_t *mdesc0, const uint64_t *mdesc1, const RelocBufs &b, const Params &prm,
-                                    float min_disparity) {
-    const RelocDims dims{rs.n_feat[0], rs.map_n, rs.map_cur, rs.fc};
-    hipLaunchKernelGGL(k_reloc_match<true>, dim3(NF_MAX / RELOC_THREADS, MAP_MAX / RELOC_SLICE_MAX), dim3(RELOC_THREADS), 0, st, (const uint4 *)rs.desc[0],
-                       (const uint4 *)mdesc0, (const uint4 *)mdesc1, dims, b.keys);
-    hipLaunchKernelGGL(k_reloc_corr, dim3(1), dim3(1024), 0, st, rs, b, prm.track_ratio, prm.desc_th);
-    hipLaunchKernelGGL(k_reloc_points, dim3(NF_MAX / (RELOC_THREADS / 64)), dim3(RELOC_THREADS), 0, st, rs, b, prm, min_disparity);
-    hipLaunchKernelGGL(k_reloc_list, dim3(1), dim3(1024), 0, st, b);
-}
-// stage 1 alone.  d_query n_query x 32 B, d_map n_map x 32 B, d_out n_query x 4 int32 (idx1, d1, idx2, d2; -1 / INT_MAX when absent): DEVICE pointers, 16-byte
-// aligned.  Both launches go to hip_stream; the call allocates its key buffer and frees it after synchronising that stream.  Returns the elapsed time of the
-// two launches in microseconds (HIP events), < 0 on a refusal or a HIP failure (lvt_amd_last_error(NULL) has the sentence of a refusal).
-LVT_API float lvt_amd_reloc_match_device(const void *d_query, int n_query, const void *d_map, int n_map, void *d_out, void *hip_stream) {
-    if (n_query < 0 || n_query > NF_MAX || n_map < 0 || n_map > MAP_MAX || (n_query > 0 && (!d_query || !d_out)) || (n_map > 0 && n_query > 0 && !d_map) ||
-        ((uintptr_t)d_query | (uintptr_t)d_map | (uintptr_t)d_out) % 16) {
-        g_snap_err = "lvt_amd_reloc_match_device: n_query must be 0 ... 4096, n_map 0 ... 32768, the pointers device pointers aligned to 16 bytes (nothing was changed)";
-        return -1.0f;
-    }
-    if (n_query == 0) return 0.0f;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const int slice = reloc_slice_length(n_map), slices = (n_map + slice - 1) / slice, gx = (n_query + RELOC_THREADS - 1) / RELOC_THREADS;
-    uint2 *keys = nullptr;
-    int *d_dims = nullptr;
-    const int h_dims[3] = {n_query, n_map, 0};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = -1.0f;
-    if (hipMalloc((void **)&keys, (size_t)std::max(slices, 1) * n_query * sizeof(uint2)) == hipSuccess && hipMalloc((void **)&d_dims, sizeof h_dims) == hipSuccess &&
-        hipMemcpy(d_dims, h_dims, sizeof h_dims, hipMemcpyHostToDevice) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-        const RelocDims dims{d_dims, d_dims + 1, d_dims + 2, nullptr};
-        (void)hipEventRecord(e0, st);
-        const char *lab = getenv("LVT_AMD_RELOC_MATCH");  // "uniform": the lab variant without LDS (this stage entry only; a handle's call always stages in LDS)
-        if (slices > 0 && lab && !strcmp(lab, "uniform"))
-            hipLaunchKernelGGL(k_reloc_match<false>, dim3(gx, slices), dim3(RELOC_THREADS), 0, st, (const uint4 *)d_query, (const uint4 *)d_map, (const uint4 *)d_map, dims,
-                               keys);
-        else if (slices > 0)
-            hipLaunchKernelGGL(k_reloc_match<true>, dim3(gx, slices), dim3(RELOC_THREADS), 0, st, (const uint4 *)d_query, (const uint4 *)d_map, (const uint4 *)d_map, dims,
-                               keys);
-        hipLaunchKernelGGL(k_reloc_merge_records, dim3(gx), dim3(RELOC_THREADS), 0, st, (const uint2 *)keys, dims, (int4 *)d_out);
-        (void)hipEventRecord(e1, st);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(keys), (void)hipFree(d_dims);
-    return ms < 0 ? -1.0f : ms * 1000.0f;
-}
-// stages 3 - 5 alone.  Host pointers: pts n x 3 f64 (world), obs n x 2 f32, pc n x 3 f64 (camera frame), has_pc n bytes (0: the correspondence has no point, its
-// pc row is not read), 0 <= n <= 4096.  counts_out (n_hypotheses ints), inliers_out (n ints: the best hypothesis' inliers, the first n_hyp_inliers of them),
-// hyp_R (9) and hyp_t (3) may each be NULL; the last three are written for status 0 and 3 only.  Returns 0 / 1 as lvt_amd_relocalise does, -1 on a refusal.
-LVT_API int lvt_amd_reloc_solve(const lvt_amd_params *pin, const lvt_amd_reloc_config *cfg_in, const double *pts, const float *obs, const double *pc,
-                                const uint8_t *has_pc, int n, int *counts_out, int *inliers_out, double *hyp_R, double *hyp_t, lvt_amd_reloc_result *out) {
-    lvt_amd_reloc_config cfg;
-    lvt_amd_reloc_default_config(&cfg);
-    if (cfg_in) cfg = *cfg_in;
-    if (!pin || !out || n < 0 || n > NF_MAX || (n > 0 && (!pts || !obs || !pc || !has_pc))) {
-        g_snap_err = "lvt_amd_reloc_solve: a NULL argument, or n outside 0 ... 4096 (nothing was changed)";
-        return -1;
-    }
-    const std::string fault = reloc_config_fault(cfg);
-    if (!fault.empty()) {
-        g_snap_err = "lvt_amd_reloc_solve: " + fault;
-        return -1;
-    }
-    Params prm;
-    lvt_amd_params tmp = *pin;
-    if (tmp.img_width <= 0) tmp.img_width = 64;
-    if (tmp.img_height <= 0) tmp.img_height = 64;
-    if (!derive_params(tmp, 1, prm)) {
-        g_snap_err = "lvt_amd_reloc_solve: parameters lvt_amd_create would refuse (nothing was changed)";
-        return -1;
-    }
-    std::vector<int> with_pc;
-    for (int i = 0; i < n; i++)
-        if (has_pc[i]) with_pc.push_back(i);
-    RelocWork w{};
-    w.res.n_corr = n, w.res.n_with_point = (int)with_pc.size();
-    w.res.status = w.res.n_with_point < 3 ? 1 : -1;
-    w.success = std::max(cfg.min_inliers, prm.min_matches);
-    const size_t nn = (size_t)std::max(n, 1);
-    double *dX = nullptr, *dPc = nullptr, *dEX = nullptr, *dErr = nullptr;
-    float *dObs = nullptr, *dEObs = nullptr;
-    int *dWith = nullptr, *dCounts = nullptr, *dInl = nullptr;
-    int8_t *dLevel = nullptr;
-    RelocWork *dW = nullptr;
-    int rc = -1;
-    std::vector<int> counts((size_t)cfg.n_hypotheses, 0);
-    if (hipMalloc((void **)&dX, nn * 24) == hipSuccess && hipMalloc((void **)&dPc, nn * 24) == hipSuccess && hipMalloc((void **)&dEX, nn * 24) == hipSuccess &&
-        hipMalloc((void **)&dErr, nn * 16 + 16) == hipSuccess && hipMalloc((void **)&dObs, nn * 8) == hipSuccess && hipMalloc((void **)&dEObs, nn * 8) == hipSuccess &&
-        hipMalloc((void **)&dWith, nn * 4) == hipSuccess && hipMalloc((void **)&dCounts, counts.size() * 4) == hipSuccess &&
-        hipMalloc((void **)&dInl, nn * 4) == hipSuccess && hipMalloc((void **)&dLevel, nn) == hipSuccess && hipMalloc((void **)&dW, sizeof(RelocWork)) == hipSuccess &&
-        hipMemcpy(dW, &w, sizeof w, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dCounts, 0, counts.size() * 4) == hipSuccess &&
-        (n == 0 || (hipMemcpy(dX, pts, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dPc, pc, (size_t)n * 24, hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(dObs, obs, (size_t)n * 8, hipMemcpyHostToDevice) == hipSuccess)) &&
-        (with_pc.empty() || hipMemcpy(dWith, with_pc.data(), with_pc.size() * 4, hipMemcpyHostToDevice) == hipSuccess)) {
-        const RelocCorr c{dX, dObs, dPc, dWith, 0, 0};  // (the sizes travel in the work record)
-        const RelocCam cam{(double)prm.fx, (double)prm.fy, (double)prm.cx, (double)prm.cy};
-        const double gate = (double)cfg.gate_px2;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_reloc_refine), hipFuncAttributeMaxDynamicSharedMemorySize, PNP_DYN_BYTES);
-        hipLaunchKernelGGL(k_reloc_score, dim3((cfg.n_hypotheses + 3) / 4), dim3(RELOC_THREADS), 0, 0, c, (const RelocWork *)dW, cam, (uint64_t)cfg.seed, gate, cfg.n_hypotheses,
-                           dCounts);
-        hipLaunchKernelGGL(k_reloc_select, dim3(1), dim3(RELOC_THREADS), 0, 0, c, cam, (uint64_t)cfg.seed, gate, cfg.n_hypotheses, (const int *)dCounts, dW, dInl, dEX,
-                           dEObs);
-        hipLaunchKernelGGL(k_reloc_refine, dim3(1), dim3(PNP_THREADS), PNP_DYN_BYTES, 0, prm, dW, (const double *)dEX, (const float *)dEObs, dErr, dLevel);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(&w, dW, sizeof w, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(counts.data(), dCounts, counts.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            (!inliers_out || w.n_edges <= 0 || hipMemcpy(inliers_out, dInl, (size_t)w.n_edges * 4, hipMemcpyDeviceToHost) == hipSuccess)) {
-            if (w.res.status != 0 && w.res.status != 3) {  // the pose is zero unless the refinement ran
-                for (int k = 0; k < 4; k++) w.res.q_wxyz[k] = 0;
-                for (int k = 0; k < 3; k++) w.res.p[k] = w.res.t[k] = 0;
-                for (int k = 0; k < 9; k++) w.res.R[k / 3][k % 3] = 0;
-            } else {
-                if (hyp_R) std::memcpy(hyp_R, w.hyp_R, sizeof w.hyp_R);
-                if (hyp_t) std::memcpy(hyp_t, w.hyp_t, sizeof w.hyp_t);
-            }
-            if (counts_out) std::memcpy(counts_out, counts.data(), counts.size() * 4);
-            *out = w.res;
-            rc = w.res.status == 0 ? 0 : 1;
-        }
-    }
-    (void)hipFree(dX), (void)hipFree(dPc), (void)hipFree(dEX), (void)hipFree(dErr), (void)hipFree(dObs), (void)hipFree(dEObs), (void)hipFree(dWith);
-    (void)hipFree(dCounts), (void)hipFree(dInl), (void)hipFree(dLevel), (void)hipFree(dW);
-    if (rc < 0) g_snap_err = std::string("lvt_amd_reloc_solve: ") + hipGetErrorString(hipGetLastError());
-    return rc;
-}
-// stage 2 (behind stage 1) alone, through the launches of a handle's call (reloc_launch_correspond).  Host pointers.  The data is laid out as a handle holds
-// it: feature arrays of both eyes with their device counts, a FeatCtl, two map copies of which map_copy is the live one (the other copy is filled from
-// other_pos / other_desc, zeros when NULL).  lost_frame: the counts are delivered as a LOST frame leaves them (Feat::n zero, FeatCtl::lost_n, lost_seq ==
-// feat_seq).  The six output arrays hold NF_MAX elements each (X, Pc: x 3; uv: x 2): they are uploaded as the caller filled them and read back whole, so an
-// element the kernels do not write comes back with the caller's bytes.  claims_left (may be NULL): entries of the claim table that are not empty behind the
-// call.  Returns 0 (out->status: 1 or -1, as stage 2 leaves it), -1 on a refusal or a HIP failure.
-LVT_API int lvt_amd_reloc_correspond(const lvt_amd_params *pin, const lvt_amd_reloc_config *cfg_in, int sensor, const float *xl, const float *yl,
-                                     const uint8_t *desc_l, const float *depth_l, int n_left, const float *xr, const float *yr, const uint8_t *desc_r, int n_right,
-                                     const double *map_pos, const uint8_t *map_desc, const double *other_pos, const uint8_t *other_desc, int n_map, int map_copy,
-                                     int lost_frame, lvt_amd_reloc_result *out, int *corr_feat, double *X, float *uv, uint8_t *has_pc, double *Pc, int *with_pc,
-                                     int *claims_left) {
-    lvt_amd_reloc_config cfg;
-    lvt_amd_reloc_default_config(&cfg);
-    if (cfg_in) cfg = *cfg_in;
-    const bool stereo = sensor == 1;
-    if (!stereo) n_right = 0;
-    if (!pin || !out || !corr_feat || !X || !uv || !has_pc || !Pc || !with_pc || (sensor != 1 && sensor != 2) || n_left < 0 || n_left > NF_MAX || n_right < 0 ||
-        n_right > NF_MAX || n_map < 0 || n_map > MAP_MAX || (map_copy != 0 && map_copy != 1) || (lost_frame != 0 && lost_frame != 1) ||
-        (n_left > 0 && (!xl || !yl || !desc_l || (!stereo && !depth_l))) || (n_right > 0 && (!xr || !yr || !desc_r)) || (n_map > 0 && (!map_pos || !map_desc))) {
-        g_snap_err = "lvt_amd_reloc_correspond: a NULL argument, sensor not 1 or 2, a feature count outside 0 ... 4096, n_map outside 0 ... 32768, or map_copy or "
-                     "lost_frame not 0 or 1 (nothing was changed)";
-        return -1;
-    }
-    const std::string fault = reloc_config_fault(cfg);
-    if (!fault.empty()) {
-        g_snap_err = "lvt_amd_reloc_correspond: " + fault;
-        return -1;
-    }
-    Params prm;
-    lvt_amd_params tmp = *pin;
-    if (tmp.img_width <= 0) tmp.img_width = 64;
-    if (!derive_params(tmp, sensor, prm)) {
-        g_snap_err = "lvt_amd_reloc_correspond: parameters lvt_amd_create would refuse (nothing was changed)";
-        return -1;
-    }
-    std::vector<void *> owned;
-    bool ok = true;
-    // a device buffer of `bytes` (at least 16): a copy of src, or -- src NULL -- every byte `fill`
-    auto dev = [&](size_t bytes, const void *src, int fill = 0) -> void * {
-        void *p = nullptr;
-        const size_t cap = std::max(bytes, (size_t)16);
-        if (!ok || hipMalloc(&p, cap) != hipSuccess) return ok = false, nullptr;
-        owned.push_back(p);
-        if (hipMemset(p, fill, cap) != hipSuccess || (src && bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess)) ok = false;
-        return p;
-    };
-    // (Feat::n of both eyes, map_n, map_cur)
-    const int h_scalars[4] = {lost_frame ? 0 : n_left, lost_frame ? 0 : n_right, n_map, map_copy};
-    FeatCtl fc{};
-    fc.feat_seq = 1, fc.skip_seq = 0;  // a zeroed record would read as "this frame has no features"
-    if (lost_frame) fc.lost_n[0] = n_left, fc.lost_n[1] = n_right, fc.lost_seq = fc.feat_seq;
-    RelocWork w{};
-    w.res.status = -1;
-    const int *d_scalars = (const int *)dev(sizeof h_scalars, h_scalars);
-    RelocSeq rs{};
-    rs.x[0] = (const float *)dev((size_t)n_left * 4, xl), rs.y[0] = (const float *)dev((size_t)n_left * 4, yl);
-    rs.desc[0] = (const uint64_t *)dev((size_t)n_left * 32, desc_l);
-    rs.depth = stereo ? nullptr : (const float *)dev((size_t)n_left * 4, depth_l);
-    if (stereo) {
-        rs.x[1] = (const float *)dev((size_t)n_right * 4, xr), rs.y[1] = (const float *)dev((size_t)n_right * 4, yr);
-        rs.desc[1] = (const uint64_t *)dev((size_t)n_right * 32, desc_r);
-    }
-    const uint64_t *mdesc[2];
-    mdesc[map_copy] = (const uint64_t *)dev((size_t)n_map * 32, map_desc), mdesc[map_copy ^ 1] = (const uint64_t *)dev((size_t)n_map * 32, other_desc);
-    rs.map_pos[map_copy] = (const double *)dev((size_t)n_map * 24, map_pos), rs.map_pos[map_copy ^ 1] = (const double *)dev((size_t)n_map * 24, other_pos);
-    rs.n_feat[0] = d_scalars, rs.n_feat[1] = d_scalars + 1, rs.map_n = d_scalars + 2, rs.map_cur = d_scalars + 3;
-    rs.fc = (const FeatCtl *)dev(sizeof fc, &fc);
-    const int slice = reloc_slice_length(n_map), slices = (n_map + slice - 1) / slice;
-    RelocBufs b{};
-    b.keys = (uint2 *)dev((size_t)std::max(slices, 1) * std::max(n_left, 1) * sizeof(uint2), nullptr);
-    b.claim = (uint32_t *)dev((size_t)n_map * 4, nullptr, 0xFF);  // RELOC_NO_KEY
-    b.corr_feat = (int *)dev((size_t)NF_MAX * 4, corr_feat), b.with_pc = (int *)dev((size_t)NF_MAX * 4, with_pc);
-    b.X = (double *)dev((size_t)NF_MAX * 24, X), b.Pc = (double *)dev((size_t)NF_MAX * 24, Pc);
-    b.uv = (float *)dev((size_t)NF_MAX * 8, uv), b.has_pc = (uint8_t *)dev((size_t)NF_MAX, has_pc);
-    b.work = (RelocWork *)dev(sizeof w, &w);
-    int rc = -1;
-    if (ok) {
-        reloc_launch_correspond(nullptr, rs, mdesc[0], mdesc[1], b, prm, cfg.min_disparity);
-        std::vector<uint32_t> claim((size_t)n_map);
-        if (hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess && hipMemcpy(&w, b.work, sizeof w, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(corr_feat, b.corr_feat, (size_t)NF_MAX * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(with_pc, b.with_pc, (size_t)NF_MAX * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(X, b.X, (size_t)NF_MAX * 24, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(Pc, b.Pc, (size_t)NF_MAX * 24, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(uv, b.uv, (size_t)NF_MAX * 8, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(has_pc, b.has_pc, (size_t)NF_MAX, hipMemcpyDeviceToHost) == hipSuccess &&
-            (n_map == 0 || hipMemcpy(claim.data(), b.claim, (size_t)n_map * 4, hipMemcpyDeviceToHost) == hipSuccess)) {
-            int left = 0;
-            for (uint32_t k : claim) left += k != RELOC_NO_KEY;
-            if (claims_left) *claims_left = left;
-            *out = w.res;
-            rc = 0;
-        }
-    }
-    for (void *p : owned) (void)hipFree(p);
-    if (rc < 0) g_snap_err = std::string("lvt_amd_reloc_correspond: ") + hipGetErrorString(hipGetLastError());
-    return rc;
-}
 
 // ---- snapshots: one sequence's state saved, restored, moved between handles and seats (k_state.hip) -------------------------------------------
 // Everything is checked before anything changes: a refusal returns -1 / NULL, leaves handle and snapshot as they were and says why in lvt_amd_last_error
@@ -3634,10 +3187,7 @@ LVT_API long long lvt_amd_snapshot_export(lvt_amd_snapshot s, void *host_buf, lo
 }
 LVT_API lvt_amd_snapshot lvt_amd_snapshot_import(const void *bytes, long long n, int device) {
     const std::string why = snap_validate(bytes, n, true);
-    if (!why.empty()) {
-        g_snap_err = "lvt_amd_snapshot_import: " + why;
-        return nullptr;
-    }
+    if (!why.empty()) return refuse_call("lvt_amd_snapshot_import", why), nullptr;
     int cur = 0;
     if (device < 0 && hipGetDevice(&cur) == hipSuccess) device = cur;
     Snapshot *p = new Snapshot();
@@ -3652,26 +3202,23 @@ LVT_API lvt_amd_snapshot lvt_amd_snapshot_import(const void *bytes, long long n,
              hipMemcpy(p->d_blob, &p->hdr, sizeof(SnapHeader), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
-        g_snap_err = std::string("lvt_amd_snapshot_import: ") + hipGetErrorString(hipGetLastError());
+        refuse_call("lvt_amd_snapshot_import", hipGetErrorString(hipGetLastError()));
         snap_free(p);
         return nullptr;
     }
-    g_snap_err.clear();
+    g_call_refusal.clear();
     return p;
 }
 LVT_API int lvt_amd_snapshot_describe(const void *bytes, long long n, lvt_amd_snapshot_info *out, lvt_amd_params *prm) {  // host code only
     const std::string why = snap_validate(bytes, n, true);
-    if (!why.empty()) {
-        g_snap_err = "lvt_amd_snapshot_describe: " + why;
-        return -1;
-    }
+    if (!why.empty()) return refuse_call("lvt_amd_snapshot_describe", why);
     SnapHeader h;
     Ctl k;
     std::memcpy(&h, bytes, sizeof(h));
     std::memcpy(&k, static_cast<const uint8_t *>(bytes) + h.off[SEC_CTL], sizeof(Ctl));
     if (out) snap_info(h, k, -1, out);
     if (prm) *prm = h.prm;
-    g_snap_err.clear();
+    g_call_refusal.clear();
     return 0;
 }
 LVT_API void lvt_amd_snapshot_destroy(lvt_amd_snapshot s) { snap_free(snap_of(s)); }
@@ -3711,10 +3258,7 @@ LVT_API int lvt_amd_odometry_set_relocalisation(lvt_amd_odometry op, const lvt_a
     std::string fault = reloc_config_fault(c);
     // (a dry run would publish the relocalised pose while the tracker stays LOST, and the failures that lead to the reset would never be counted)
     if (fault.empty() && c.dry_run) fault = "dry_run is 1: the accumulator's relocalisation commits, dry_run must be 0 (nothing was changed)";
-    if (!fault.empty()) {
-        g_snap_err = "lvt_amd_odometry_set_relocalisation: " + fault;
-        return -1;
-    }
+    if (!fault.empty()) return refuse_call("lvt_amd_odometry_set_relocalisation", fault);
     o->reloc_cfg = c, o->max_lost_frames = std::max(max_lost_frames, 0), o->lost_run = 0;
     return 0;
 }
