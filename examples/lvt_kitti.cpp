@@ -4,6 +4,7 @@
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/kitti/kitti_example.cpp:49-152 there):
 //     lvt_kitti <sequences_dir> <seq_number> [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--covariance FILE]
+//                [--mask LEFT[,RIGHT]]
 // reads <sequences_dir>/NN/image_0/%06d.{png,pgm} and image_1/..., the OpenCV-YAML calibration (camera_matrix, baseline)
 // and vo_config.yaml, tracks every frame until the sequence ends or the tracker is LOST, writes NN.txt in the KITTI
 // 3x4 row format with the reference's precision (fixed, 9 digits) and prints the mean per-frame track() time.
@@ -12,6 +13,8 @@
 // --covariance FILE (not in the reference): the tracker also evaluates every frame's pose uncertainty (lvt_system::enable_pose_info) and FILE receives one
 // line per tracked frame: frame, status, n_inliers and the six sigmas (square roots of the covariance's diagonal: metres x y z, radians x y z; zeros
 // unless the status is 1).  Without the option nothing of this runs.
+// --mask LEFT[,RIGHT] (not in the reference): feature masks (lvt_system::set_mask), 8-bit PNG or PGM files of the frames' size, a pixel != 0: key points
+// allowed -- the ego vehicle's bonnet, an overlay.  LEFT alone masks the left eye only.  A file of another size is refused before the first frame.
 #include "../include/lvt_system.h"
 
 #include "image_io.h"
@@ -66,7 +69,7 @@ int main(int argc, char **argv) {
     char seq_cstr[16];
     std::snprintf(seq_cstr, sizeof seq_cstr, "%02d", std::atoi(argv[2]));
     const std::string seq_str(seq_cstr), dir_prefix = std::string(argv[1]) + "/" + seq_str;
-    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name;
+    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name, mask_names;
     long max_frames = -1;
     for (int i = 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -75,6 +78,7 @@ int main(int argc, char **argv) {
         else if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
         else if (k == "--covariance") cov_name = argv[i + 1];
+        else if (k == "--mask") mask_names = argv[i + 1];
     }
     double K[9], baseline = 0;
     if (!read_calib(calib, K, baseline)) {
@@ -114,6 +118,29 @@ int main(int argc, char **argv) {
             return -1;
         }
         cov_file << std::scientific << std::setprecision(9);
+    }
+    if (!mask_names.empty()) {
+        const size_t comma = mask_names.find(',');
+        const std::string names[2] = {mask_names.substr(0, comma), comma == std::string::npos ? std::string() : mask_names.substr(comma + 1)};
+        Gray mask[2];
+        for (int e = 0; e < 2; e++) {
+            if (names[e].empty()) continue;
+            if (!load_image(names[e], mask[e], err)) {
+                std::cout << "failed to read the mask " << names[e] << " (" << err << ")" << std::endl;
+                lvt_system::destroy(vo);
+                return -1;
+            }
+            if (mask[e].w != left.w || mask[e].h != left.h) {
+                std::cout << "the mask " << names[e] << " is " << mask[e].w << " x " << mask[e].h << ", the frames are " << left.w << " x " << left.h << std::endl;
+                lvt_system::destroy(vo);
+                return -1;
+            }
+        }
+        if (!vo->set_mask(names[0].empty() ? nullptr : mask[0].px.data(), names[1].empty() ? nullptr : mask[1].px.data())) {
+            std::cout << "failed to set the mask: " << vo->last_error() << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
     }
     // like the reference, the trajectory has one row per frame of the sequence; frames after a LOST keep the default pose
     long frame_count = 0;

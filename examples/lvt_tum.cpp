@@ -1,13 +1,15 @@
 // lvt_tum -- TUM RGB-D command line harness over the C-ABI.
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/tum_rgbd/tum_rgbd_example.cpp:49-150 there):
-//     lvt_tum <tum_sequences_root_dir> <associations_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt]
+//     lvt_tum <tum_sequences_root_dir> <associations_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--mask FILE]
 // reads <associations_dir>/<dataset_name>.txt ("t_rgb rgb/xxx.png t_depth depth/xxx.png" per line), the colour and the 16-bit
 // depth PNGs below <root>/<dataset_name>/, hands the decoded RGB to the tracker as it is (LVT_AMD_PIX_RGB8: the conversion to gray, cv::cvtColor's
 // weights, is the first launch of the frame's feature stage; a dataset of gray PNGs goes in as gray) and the PNG's 16-bit depth plane to
 // lvt_amd_track_rgbd16_async with 1.0f / 5000.0f metres per unit (the tracker computes value * (1.0f / 5000.0f) in float where it has key
 // points -- what cv::Mat::convertTo gives the reference for every pixel) and writes <dataset_name>.txt in
 // the TUM trajectory format "t x y z qx qy qz qw" with the reference's precision (6 digits for t, 7 for the rest).
+// --mask FILE (not in the reference): a feature mask (lvt_amd_set_mask), an 8-bit PNG or PGM of the configured image size, a pixel != 0: key points allowed.
+// A file of another size is refused before the first frame.
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
 #include "image_io.h"
@@ -25,12 +27,13 @@ int main(int argc, char **argv) {
         return -1;
     }
     const std::string root_dir = argv[1], associations_dir = argv[2], dataset_name = argv[3], config_file_name = argv[4];
-    std::string out_name = dataset_name + ".txt";
+    std::string out_name = dataset_name + ".txt", mask_name;
     long max_frames = -1;
     for (int i = 5; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
+        else if (k == "--mask") mask_name = argv[i + 1];
     }
     std::vector<std::string> rgb_titles, depth_titles;
     std::vector<double> time_stamps;
@@ -66,6 +69,22 @@ int main(int argc, char **argv) {
     if (!vo) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;
         return -1;
+    }
+    if (!mask_name.empty()) {
+        Gray mask;
+        std::string err;
+        if (!load_image(mask_name, mask, err)) {
+            std::cout << "failed to read the mask " << mask_name << " (" << err << ")" << std::endl;
+            return -1;
+        }
+        if (mask.w != params.img_width || mask.h != params.img_height) {
+            std::cout << "the mask " << mask_name << " is " << mask.w << " x " << mask.h << ", the frames are " << params.img_width << " x " << params.img_height << std::endl;
+            return -1;
+        }
+        if (lvt_amd_set_mask(vo, mask.px.data(), nullptr) != 0) {
+            std::cout << "failed to set the mask: " << lvt_amd_last_error(vo) << std::endl;
+            return -1;
+        }
     }
     long frame_count = (long)rgb_titles.size();
     if (max_frames >= 0 && max_frames < frame_count) frame_count = max_frames;

@@ -288,7 +288,8 @@ LVT_API int lvt_amd_get_ordering(lvt_handle h);
  * 4 the registered depth plane of a handle with a depth camera (fp32, rows x pitch; 0 bytes without one, and when the last frame was handed in before
  *   the camera was set),
  * 5 the equalised image of a handle with an equalisation record (u8, rows x pitch; 0 bytes without one, and when the last frame was handed in before the
- *   record was set), 6 the tables that image was made with (u8, tiles_x * tiles_y rows of 256).
+ *   record was set), 6 the tables that image was made with (u8, tiles_x * tiles_y rows of 256),
+ * 7 the eye's feature mask as the tracker holds it (u8, rows x pitch, the padding columns zero; 0 bytes for an eye without one; needs no frame).
  * returns bytes written, pitch via *pitch_out (in elements). */
 LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int cap_bytes, int *pitch_out);
 
@@ -476,6 +477,48 @@ LVT_API int lvt_amd_get_equalisation(lvt_handle h, int seq, lvt_amd_equalisation
 LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void *d_src, int src_pitch, int w, int h, void *d_dst, int dst_pitch,
                                     void *hip_stream);
 LVT_API int lvt_amd_equalisation_plan(const lvt_amd_equalisation *cfg, int w, int h, int out[6], float *lut_scale);
+
+/* FEATURE MASKS: key points on masked pixels are dropped inside the tracker's feature stage.  The ego vehicle's bonnet, a robot's own arm, timestamp and logo
+ * overlays, the black surround of a rectified wide-angle lens, pixels a segmentation network has labelled movable: all of them give well-textured, strongly
+ * matching features that are wrong.  A mask is a property of the handle, or of one sequence of a batch, like the pixel format; masks are NOT offered for pooled
+ * and automatic seats.  A handle or sequence that never sets a mask launches exactly what it did.
+ *
+ * DEFINITION (tests/mask_util.py restates it in numpy; the checks hold the tracker to it bit for bit).  A mask is an 8-bit image of the sequence's
+ * img_width x img_height, one per eye, on the pixel grid the detector reads: the rectified grid where rectifiers are attached, otherwise the frame's own grid.
+ * A byte != 0 means "key points allowed" (OpenCV's convention).  For every feature the gather step kept, in its output order:
+ *     ix = (int)(bx + 0.5f);  iy = (int)(by + 0.5f)          -- fp32 add, then truncation: cv::KeyPointsFilter::runByPixelsMask
+ *     keep = 0 <= ix < W && 0 <= iy < H && mask[iy][ix] != 0
+ * (bx, by) is the raw pixel BRIEF samples at -- for an RGB-D handle with lens distortion NOT the undistorted (x, y) the feature is reported with.  The kept
+ * features stay in order (a stable compaction) and the feature count becomes their number: everything downstream -- BRIEF, the hash cells, row matching, map
+ * matching, a LOST frame's kept count, relocalisation -- sees only them.  Consequences:
+ *  - ORDERING.  The filter acts after detection, ANMS, the border filter and the RGB-D depth filter, and after the truncation to 4096 features.  The "fewer
+ *    than 200 corners" retry is still decided on the unmasked count.  A masked corner may still have suppressed an unmasked neighbour in NMS / ANMS and used some
+ *    of its cell's budget: what OpenCV's own mask does with a grid detector.
+ *  - An ALL-ZERO mask leaves no features: the frame behaves like a frame without features.
+ *  - A mask is a property, not state: lvt_amd_reset and snapshots neither hold nor change it; the snapshot bytes are what they were.
+ *  - EXTERNAL corners (lvt_track_with_external_corners) are filtered the same way, in the same coordinates: that is where fractional coordinates meet the
+ *    rounding rule (k + 0.5 belongs to pixel k + 1; -0.7 belongs to pixel 0).
+ * One launch (k_mask_features, reported under that name by lvt_amd_profile_read for a handle with a mask) between the gather step and BRIEF.
+ *
+ * CALLS.  lvt_amd_set_mask / lvt_amd_batch_set_mask take tightly packed host buffers (img_width bytes per row); lvt_amd_set_mask_device /
+ * lvt_amd_batch_set_mask_device take planes in HBM at any address and any pitch >= img_width.  One eye may be NULL (no mask for that eye); both NULL unsets the
+ * property.  The tracker keeps its own copy: the data is copied in the order of the handle's tracking stream -- the caller's stream where lvt_amd_set_stream
+ * gave one -- and the copy has completed before the call returns; the caller's buffer is free then.  The mask holds for every later frame until it is set again.
+ * Refused under the "Frame properties" contract, in this order, each with -1, the handle as it was and the sentence in lvt_amd_last_error ending in
+ * "(nothing was changed)": a bad handle (no report); a pooled or automatic seat; the batch call on a solo handle and the solo call on a batch; seq out of
+ * range; a pitch smaller than the width; a right-eye mask on an RGB-D handle; frames in flight.  A successful set counts as a use of an lvt_create handle.
+ *  - lvt_amd_get_mask_stats: out = {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for (an eye without a mask
+ *    reports 0, 0).  1 = written; 0 = the sequence has no mask, or its last frame went in before the masks it has now were set; -1 = bad handle / seq.
+ *  - lvt_amd_get_plane(h, eye, 7, ...) reads the mask back.
+ *  - lvt_amd_mask_features: the stage alone on caller data (host pointers).  The n <= 4096 features' eight arrays are compacted in place against a
+ *    width x height mask of `pitch` bytes per row and come back whole; returns the new count, -1 on a refusal (lvt_amd_last_error(NULL)). */
+LVT_API int lvt_amd_set_mask(lvt_handle h, const void *left, const void *right);                    /* 0 / -1 */
+LVT_API int lvt_amd_batch_set_mask(lvt_handle h, int seq, const void *left, const void *right);
+LVT_API int lvt_amd_set_mask_device(lvt_handle h, const void *d_left, int pitch_left, const void *d_right, int pitch_right);
+LVT_API int lvt_amd_batch_set_mask_device(lvt_handle h, int seq, const void *d_left, int pitch_left, const void *d_right, int pitch_right);
+LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]);
+LVT_API int lvt_amd_mask_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth, int16_t *hcx, int16_t *hcy, const uint8_t *mask,
+                                  int width, int height, int pitch);
 
 /* ---- SNAPSHOTS: one sequence's state saved, restored, moved between handles and seats -------------------------------------------------
  * A tracker's state lives in HBM: its control record, the local map, the staged points and the motion model.  A snapshot is a copy of it, device-resident and

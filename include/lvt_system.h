@@ -328,6 +328,11 @@ class lvt_system {
     /* ADDITIVE: CLAHE contrast equalisation of the gray plane the detector reads (lvt_amd_equalisation, include/lvt_amd_ext.h, DIM frames): from now on every
      * frame is equalised by two launches at the head of its feature stage; nullptr: plain frames again.  false: refused (last_error() says why), nothing changed. */
     bool set_equalisation(const lvt_amd_equalisation *cfg) { return lvt_amd_set_equalisation(m_handle, cfg) == 0; }
+    /* ADDITIVE: feature masks (include/lvt_amd_ext.h, FEATURE MASKS): tightly packed 8-bit images of img_width x img_height on the pixel grid the detector reads,
+     * a byte != 0: key points allowed.  From now on every frame loses the key points on masked pixels inside its feature stage (one launch between the gather
+     * step and BRIEF).  One eye may be nullptr (no mask for it); both nullptr: no masks again.  The buffers are copied before the call returns.
+     * false: refused (last_error() says why), nothing changed. */
+    bool set_mask(const unsigned char *left, const unsigned char *right = nullptr) { return lvt_amd_set_mask(m_handle, left, right) == 0; }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
         m_state = lvt_amd_wait_pose(m_handle, q, p);

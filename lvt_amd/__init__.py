@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
+    "lvt_amd_set_mask", "lvt_amd_batch_set_mask", "lvt_amd_set_mask_device", "lvt_amd_batch_set_mask_device", "lvt_amd_get_mask_stats", "lvt_amd_mask_features",
     "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve", "lvt_amd_reloc_correspond",
 ]
 
@@ -217,6 +218,13 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (   # (feature masks: likewise)
+            ("lvt_amd_set_mask", [vp, vp, vp]), ("lvt_amd_batch_set_mask", [vp, C.c_int, vp, vp]), ("lvt_amd_set_mask_device", [vp, vp, C.c_int, vp, C.c_int]),
+            ("lvt_amd_batch_set_mask_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int]), ("lvt_amd_get_mask_stats", [vp, C.c_int, vp]),
+            ("lvt_amd_mask_features", [C.c_int] + [vp] * 9 + [C.c_int] * 3)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     for name, argtypes, restype in (   # (relocalisation: likewise)
             ("lvt_amd_relocalise", [vp, vp, vp], C.c_int), ("lvt_amd_batch_relocalise", [vp, C.c_int, vp, vp], C.c_int),
             ("lvt_amd_odometry_set_relocalisation", [vp, vp, C.c_int], C.c_int), ("lvt_amd_reloc_default_config", [vp], None), ("lvt_amd_reloc_slice_length", [C.c_int], C.c_int),
@@ -336,6 +344,54 @@ def equalisation_plan(cfg: Equalisation, width: int, height: int):
     d = dict(zip(("Wp", "Hp", "tile_w", "tile_h", "area", "clip"), (int(x) for x in out)))
     d["lut_scale"] = np.float32(scale.value)
     return d
+
+
+def _mask_of(handle, seq, mask):
+    """a feature mask as the C-ABI takes it: a contiguous (H, W) uint8 array of the sequence's image size (bool arrays become 0 / 1), or None.  The C-ABI has
+    no size argument for a host mask: an array of another shape would be read past its end, so it raises here"""
+    if mask is None:
+        return None
+    a = np.ascontiguousarray(mask, dtype=np.uint8)
+    pod = ParamsPOD()
+    if load_library().lvt_amd_batch_get_params(handle, int(seq), C.byref(pod)) and a.shape != (pod.img_height, pod.img_width):
+        raise ValueError(f"a mask of shape {a.shape} on a sequence of {pod.img_height} x {pod.img_width} pixels")
+    if a.ndim != 2:
+        raise ValueError(f"a mask of shape {a.shape}: expected (H, W)")
+    return a
+
+
+def _mask_stats_of(handle, seq):
+    out = np.zeros(4, dtype=np.int32)
+    rc = load_library().lvt_amd_get_mask_stats(handle, int(seq), _p(out))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_mask_stats: bad handle or no sequence {seq}")
+    if rc == 0:
+        return None
+    return {"kept": (int(out[0]), int(out[2])), "dropped": (int(out[1]), int(out[3]))}
+
+
+def mask_features(x, y, resp, bx, by, depth, hcx, hcy, mask, width: int = None, height: int = None):
+    """stage entry: the feature-mask kernel alone on n <= 4096 features (include/lvt_amd_ext.h, FEATURE MASKS).  mask: a 2-D uint8 array whose row stride is the
+    pitch (a view into a wider array keeps its pitch); width / height default to its shape.  Returns (n_kept, x, y, resp, bx, by, depth, hcx, hcy): the arrays as
+    the kernel left them, the first n_kept elements being the kept features in order.  RuntimeError with the reason when refused."""
+    f = [np.array(a, dtype=np.float32).ravel() for a in (x, y, resp, bx, by, depth)]
+    h = [np.array(a, dtype=np.int16).ravel() for a in (hcx, hcy)]
+    n = f[0].size
+    if any(a.size != n for a in f + h):
+        raise ValueError("the eight feature arrays differ in length")
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        raise ValueError("mask: a 2-D uint8 array with contiguous rows")
+    width = m.shape[1] if width is None else int(width)
+    height = m.shape[0] if height is None else int(height)
+    pitch = m.strides[0]
+    flat = np.zeros(pitch * height, dtype=np.uint8)   # (the rows with their padding, as the plane lies in memory)
+    rows = np.lib.stride_tricks.as_strided(flat, shape=(height, m.shape[1]), strides=(pitch, 1))
+    rows[:] = m[:height]
+    rc = load_library().lvt_amd_mask_features(n, *[_p(a) for a in f + h], _p(flat), width, height, pitch)
+    if rc < 0:
+        raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_mask_features failed")
+    return (rc, *f, *h)
 
 
 class SnapshotInfo(C.Structure):
@@ -819,6 +875,23 @@ class LvtSystem:
         """the Equalisation that is set, or None"""
         return _equalisation_of(self._h, 0)
 
+    def set_mask(self, left=None, right=None) -> int:
+        """feature masks, (H, W) uint8 or bool arrays on the pixel grid the detector reads, != 0: key points allowed.  Every frame handed to this system from now
+        on loses the key points on masked pixels inside the feature stage (one launch between the gather step and BRIEF).  One eye may be None (no mask for
+        it); both None: no masks again.  The arrays are copied before the call returns.  0: done; -1: refused (last_error())."""
+        l, r = _mask_of(self._h, 0, left), _mask_of(self._h, 0, right)
+        return load_library().lvt_amd_set_mask(self._h, _p(l), _p(r))
+
+    def set_mask_device(self, d_left: int = 0, pitch_left: int = 0, d_right: int = 0, pitch_right: int = 0) -> int:
+        """set_mask from planes in HBM (device addresses, any alignment, pitch >= width in bytes; 0: no mask for that eye), copied in the order of the system's
+        tracking stream before the call returns"""
+        return load_library().lvt_amd_set_mask_device(self._h, C.c_void_p(d_left or None), int(pitch_left), C.c_void_p(d_right or None), int(pitch_right))
+
+    def mask_stats(self):
+        """{"kept": (left, right), "dropped": (left, right)} of the last frame's mask launch (an eye without a mask: 0, 0); None without a mask, or when the
+        last frame went in before the masks were set"""
+        return _mask_stats_of(self._h, 0)
+
     def _depth(self, d):
         """the depth array of a host call: with a depth camera set the library reads cam.height x cam.width elements, and the C-ABI has no size argument for
         them -- an array of any other shape would be read past its end"""
@@ -915,7 +988,7 @@ class LvtSystem:
         name = C.create_string_buffer(64); ms = C.c_double(0); calls = C.c_long(0)
         for slot in range(64):
             if not load_library().lvt_amd_profile_read(self._h, slot, name, 64, C.byref(ms), C.byref(calls)):
-                if slot >= 26:   # (past the last slot; the slots below it may be absent on this handle)
+                if slot >= 27:   # (past the last slot; the slots below it may be absent on this handle)
                     break
                 continue
             out.append((name.value.decode(), ms.value, calls.value))
@@ -939,7 +1012,8 @@ class LvtSystem:
         """what=0: corner score map (u8), what=1: 9x9 box sums (u16), what=2: the rectified image of a system with rectifiers (u8; an empty array
         without them), what=3: the converted gray image of a system with a colour pixel format (u8, before rectification; empty on a gray system),
         what=4: the registered depth plane of a system with a depth camera (float32, +inf where nothing landed; empty without one),
-        what=5: the equalised image of a system with an equalisation (u8; empty without one), what=6: the tables it was made with (tiles x 256, u8);
+        what=5: the equalised image of a system with an equalisation (u8; empty without one), what=6: the tables it was made with (tiles x 256, u8),
+        what=7: the eye's feature mask as the system holds it (u8; empty without one);
         returns (rows, pitch) array"""
         cap = 64 << 20
         buf = np.zeros(cap // 8, dtype=np.uint64)
@@ -1048,6 +1122,18 @@ class LvtBatch:
 
     def equalisation(self, seq: int):
         return _equalisation_of(self._h, seq)
+
+    def set_mask(self, seq: int, left=None, right=None) -> int:
+        """LvtSystem.set_mask for sequence `seq` of the batch: its key points are filtered from then on, the other sequences' are not"""
+        l, r = _mask_of(self._h, seq, left), _mask_of(self._h, seq, right)
+        return load_library().lvt_amd_batch_set_mask(self._h, int(seq), _p(l), _p(r))
+
+    def set_mask_device(self, seq: int, d_left: int = 0, pitch_left: int = 0, d_right: int = 0, pitch_right: int = 0) -> int:
+        return load_library().lvt_amd_batch_set_mask_device(self._h, int(seq), C.c_void_p(d_left or None), int(pitch_left), C.c_void_p(d_right or None),
+                                                            int(pitch_right))
+
+    def mask_stats(self, seq: int):
+        return _mask_stats_of(self._h, seq)
 
     def enable_pose_info(self, on: bool = True) -> int:
         """LvtSystem.enable_pose_info for all sequences of the batch together"""

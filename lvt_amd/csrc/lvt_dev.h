@@ -159,6 +159,9 @@ struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one
     // skipped through gate_fatal WITHOUT skip_seq set is not caught.
     int lost_n[2];
     seq_t lost_seq;
+    // feature masks (k_mask.hip): what k_mask_features kept and dropped of this frame's features, per eye.  Scratch like lost_n: written only by the launch of a
+    // masked sequence, read by lvt_amd_get_mask_stats
+    int mask_kept[2], mask_dropped[2];
 };
 
 struct Feat {  // one image's lvt_image_features_struct (lvt_image_features_struct.h:62-80), SoA

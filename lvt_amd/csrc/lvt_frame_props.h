@@ -52,15 +52,15 @@ static int set_property(lvt_handle h, const PropertyCall &k, int seq, bool batch
         return -1;
     });
 }
-// sequence seq's planes (each of its own plane_pitch x H elements + pad) in a [B][NPAR][stride] vector: sized at its first use, `eyes` <= stride planes per
-// parity allocated where they do not exist yet
+// sequence seq's planes (each of its own plane_pitch x H elements + pad) in a [B][copies][stride] vector: sized at its first use, `eyes` <= stride planes per
+// parity allocated where they do not exist yet (copies == 1: planes no frame in flight writes, one per eye)
 template <typename T>
-static void give_planes(Context *c, std::vector<T *> &planes, int stride, int seq, int eyes, size_t pad) {
-    if (planes.empty()) planes.assign((size_t)c->B * NPAR * stride, nullptr);
+static void give_planes(Context *c, std::vector<T *> &planes, int stride, int seq, int eyes, size_t pad, int copies = NPAR) {
+    if (planes.empty()) planes.assign((size_t)c->B * copies * stride, nullptr);
     const size_t plane = (size_t)c->h_seqs[seq].plane_pitch * c->seq_prm(seq).H;
-    for (int par = 0; par < NPAR; par++)
+    for (int par = 0; par < copies; par++)
         for (int e = 0; e < eyes; e++) {
-            T *&d = planes[((size_t)seq * NPAR + par) * stride + e];
+            T *&d = planes[((size_t)seq * copies + par) * stride + e];
             if (!d) d = c->dalloc<T>(plane + pad);
         }
 }
@@ -382,6 +382,75 @@ static int set_equalisation(lvt_handle h, int seq, bool batch_call, const lvt_am
     });
 }
 
+// ---- feature masks: u8 planes per handle / per sequence of a batch, one per eye (Context::d_mask, k_mask.hip) -------------------------------------------
+// Every sequence of the step, masked or not, takes a slot of the table (slot k of a launch is sequence z0 + k; an eye without a mask, and every eye of a
+// sequence without one, is a NULL pointer and leaves at the kernel's top); a table none of whose sequences has a mask is not launched.  The launch stands
+// directly behind k_gather and ahead of k_brief / k_brief_img, in both orderings.  The planes are written only by a set on a quiet handle, whose copy has
+// completed before the set returns; the Feat arrays are written by k_gather just ahead and read by k_brief just behind, on this stream: stream order alone
+// covers the hand-over, no gate.
+static void mask_features(Context *c, int slot, int par, int Bz) {
+    const FrameArgs *fw = &frame_args(c, slot);
+    int z0 = 0;
+    bool any = false, timed = false;
+    TablePacker pk(&MaskTable::s, [&](const MaskTable &tab, int n, bool) {
+        if (any && !timed) LAUNCH(26, c->stream_f, k_mask_features, dim3(1, 2, n), dim3(1024), 0, c->d_seqs, tab, par, z0);
+        else if (any) hipLaunchKernelGGL(k_mask_features, dim3(1, 2, n), dim3(1024), 0, c->stream_f, c->d_seqs, tab, par, z0);
+        timed = timed || any;
+        z0 += n, any = false;
+    });
+    for (int s = 0; s < Bz; s++) {
+        MaskSeq &M = *pk.add(1);
+        for (int e = 0; e < 2; e++) {
+            const bool on = c->has_mask(s, e) && !fw[s].absent;
+            M.mask[e] = on ? c->d_mask[(size_t)s * 2 + e] : nullptr;
+            M.pitch[e] = c->h_seqs[s].plane_pitch;
+            any = any || on;
+        }
+    }
+    pk.flush();
+    c->ring_masked[slot] = timed;
+}
+// left / right: tightly packed host planes (device == false: the pitch is the width) or planes in HBM at any address and the given pitch; NULL: that eye has no
+// mask; both NULL: the sequence has none
+static int set_mask(lvt_handle h, int seq, bool batch_call, bool device, const void *left, int pitch_l, const void *right, int pitch_r) {
+    static const PropertyCall host_call = {"lvt_amd_set_mask", 0,
+                                           {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                            "a batch handle takes its masks per sequence through lvt_amd_batch_set_mask (nothing was changed)"},
+                                           "lvt_amd_batch_set_mask on a handle that is not a batch (use lvt_amd_set_mask)"};
+    static const PropertyCall device_call = {"lvt_amd_set_mask_device", 0,
+                                             {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                              "a batch handle takes its masks per sequence through lvt_amd_batch_set_mask_device (nothing was changed)"},
+                                             "lvt_amd_batch_set_mask_device on a handle that is not a batch (use lvt_amd_set_mask_device)"};
+    const PropertyCall &call = device ? device_call : host_call;
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        const Params &q = c->seq_prm(seq);
+        const void *src[2] = {left, right};
+        const int pitch[2] = {device ? pitch_l : q.W, device ? pitch_r : q.W};
+        for (int e = 0; e < 2; e++)
+            if (src[e] && pitch[e] < q.W)
+                return refuse_unchanged(t, call.who, "a mask pitch of " + std::to_string(pitch[e]) + " bytes on a sequence " + std::to_string(q.W) + " pixels wide (pitch >= img_width)");
+        if (right && c->sensor == 2) return refuse_unchanged(t, call.who, "a right-eye mask on an RGB-D handle (it has one image: pass NULL for the right eye)");
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the mask before the first frame or after every frame has been collected");
+        if (!left && !right && !(c->has_mask(seq, 0) || c->has_mask(seq, 1))) return 0;
+        std::fill(std::begin(c->ring_masked), std::end(c->ring_masked), false);  // (the last frame went in under OTHER masks: lvt_amd_get_mask_stats has nothing of it)
+        if (left || right) {
+            give_planes(c, c->d_mask, 2, seq, c->sensor == 2 ? 1 : 2, 64, 1);
+            // in the order of the handle's tracking stream (the caller's, where lvt_amd_set_stream gave one): a device plane the caller wrote on that stream is
+            // complete before it is read, and the copy has completed before the call returns -- no frame's launch can overtake it
+            for (int e = 0; e < 2; e++)
+                if (src[e])
+                    HIPCHK(c, hipMemcpy2DAsync(c->d_mask[(size_t)seq * 2 + e], (size_t)c->h_seqs[seq].plane_pitch, src[e], (size_t)pitch[e], (size_t)q.W, (size_t)q.H,
+                                               device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        if (c->mask_on.empty()) c->mask_on.assign((size_t)c->B * 2, 0);
+        c->mask_on[(size_t)seq * 2] = left != nullptr, c->mask_on[(size_t)seq * 2 + 1] = right != nullptr;
+        c->n_mask = 0;
+        for (int s = 0; s < c->B; s++) c->n_mask += (c->mask_on[(size_t)s * 2] || c->mask_on[(size_t)s * 2 + 1]) ? 1 : 0;
+        return 0;
+    });
+}
+
 // ---- pose uncertainty (k_poseinfo.hip): a property of the handle like the pixel format, refused where that is refused ----------------------------------
 static int enable_pose_info(lvt_handle h, int enable) {
     static const PropertyCall call = {"lvt_amd_enable_pose_info", 0, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr, nullptr}, nullptr};
@@ -481,6 +550,69 @@ LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void 
     hipLaunchKernelGGL(k_clahe_lut, dim3(cfg->tiles_x * cfg->tiles_y, 1), dim3(256), 0, st, tab);
     hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)(((size_t)(dst_pitch / 4) * h + 255) / 256), 1), dim3(256), 0, st, tab);
     return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
+}
+
+LVT_API int lvt_amd_set_mask(lvt_handle h, const void *left, const void *right) { return set_mask(h, 0, false, false, left, 0, right, 0); }
+LVT_API int lvt_amd_batch_set_mask(lvt_handle h, int seq, const void *left, const void *right) { return set_mask(h, seq, true, false, left, 0, right, 0); }
+LVT_API int lvt_amd_set_mask_device(lvt_handle h, const void *d_left, int pitch_left, const void *d_right, int pitch_right) {
+    return set_mask(h, 0, false, true, d_left, pitch_left, d_right, pitch_right);
+}
+LVT_API int lvt_amd_batch_set_mask_device(lvt_handle h, int seq, const void *d_left, int pitch_left, const void *d_right, int pitch_right) {
+    return set_mask(h, seq, true, true, d_left, pitch_left, d_right, pitch_right);
+}
+// out: {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for; an eye without a mask reports 0, 0
+LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]) {
+    h = resolve_handle(h);
+    if (out) out[0] = out[1] = out[2] = out[3] = 0;
+    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has a mask)
+    if (!is_ctx(h) || !out) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    DeviceGuard guard(c);
+    try {
+        drain(c);
+        if (c->done == 0 || !(c->has_mask(seq, 0) || c->has_mask(seq, 1)) || !c->ring_masked[c->last_slot]) return 0;
+        FeatCtl fc;
+        d2h(c, &fc, c->h_seqs[seq].fb[c->last_par].fc, 1);
+        for (int e = 0; e < 2; e++)
+            if (c->has_mask(seq, e)) out[2 * e] = fc.mask_kept[e], out[2 * e + 1] = fc.mask_dropped[e];
+        return 1;
+    } catch (...) {
+    }
+    return -1;
+}
+// the stage alone on caller data (host pointers): the n features' eight arrays are compacted IN PLACE under the rule of "FEATURE MASKS" against a width x height
+// mask of `pitch` bytes per row, and every array comes back whole -- the elements behind the new count hold what the kernel left there.  Returns the new
+// count, -1 on a refusal (lvt_amd_last_error(NULL)) or a HIP failure.
+LVT_API int lvt_amd_mask_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth, int16_t *hcx, int16_t *hcy, const uint8_t *mask,
+                                  int width, int height, int pitch) {
+    const char *who = "lvt_amd_mask_features";
+    if (n < 0 || n > NF_MAX || !mask || width < 1 || width > 8192 || height < 1 || height > 8192 || pitch < width ||
+        (n > 0 && (!x || !y || !resp || !bx || !by || !depth || !hcx || !hcy)))
+        return refuse_call(who, "a NULL argument, n outside 0 ... 4096, a size outside 1 ... 8192 or a pitch smaller than the width (nothing was changed)");
+    const size_t nn = (size_t)n;
+    StageScratch S;
+    Seq hs;
+    std::memset(&hs, 0, sizeof(hs));
+    hs.prm.W = width, hs.prm.H = height, hs.prm.sensor = 1;
+    Feat &F = hs.fb[0].feat[0];
+    F.x = S.buf<float>(nn, x), F.y = S.buf<float>(nn, y), F.resp = S.buf<float>(nn, resp);
+    F.bx = S.buf<float>(nn, bx), F.by = S.buf<float>(nn, by), F.depth = S.buf<float>(nn, depth);
+    F.hcx = S.buf<int16_t>(nn, hcx), F.hcy = S.buf<int16_t>(nn, hcy);
+    F.n = S.buf<int>(1, &n);
+    hs.fb[0].fc = S.buf<FeatCtl>(1);
+    MaskTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.s[0].mask[0] = S.buf<uint8_t>((size_t)pitch * height, mask), tab.s[0].pitch[0] = pitch;
+    const Seq *d_seq = S.buf<Seq>(1, &hs);
+    if (!S.ok()) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    hipLaunchKernelGGL(k_mask_features, dim3(1, 1, 1), dim3(1024), 0, 0, d_seq, tab, 0, 0);
+    int n_new = -1;
+    if (hipGetLastError() == hipSuccess && S.fetch(&n_new, (const int *)F.n, 1) && S.fetch(x, (const float *)F.x, nn) && S.fetch(y, (const float *)F.y, nn) &&
+        S.fetch(resp, (const float *)F.resp, nn) && S.fetch(bx, (const float *)F.bx, nn) && S.fetch(by, (const float *)F.by, nn) &&
+        S.fetch(depth, (const float *)F.depth, nn) && S.fetch(hcx, (const int16_t *)F.hcx, nn) && S.fetch(hcy, (const int16_t *)F.hcy, nn))
+        return n_new;
+    return refuse_call(who, hipGetErrorString(hipGetLastError()));
 }
 
 LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) { return enable_pose_info(h, enable); }

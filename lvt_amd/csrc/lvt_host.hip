@@ -21,6 +21,7 @@
 #include "k_rectify.hip"
 #include "k_depthreg.hip"
 #include "k_equalise.hip"
+#include "k_mask.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
 #include "k_reloc.hip"
@@ -313,6 +314,14 @@ struct Context {
     int n_equal = 0;                          // sequences with the property
     bool ring_equalised[RING] = {};           // per un-collected / last frame: sequence 0's image went through k_clahe_apply (lvt_amd_get_plane(.., 5, ..))
     bool has_equal(int s) const { return n_equal > 0 && equal[(size_t)s].tiles_x > 0; }
+    // FEATURE MASKS (lvt_amd_set_mask / lvt_amd_batch_set_mask and their _device forms): a sequence with a mask has the key points k_gather kept filtered by ONE
+    // k_mask_features launch between k_gather and k_brief.  The planes are the tracker's own copies, per EYE and not per parity: a set needs a quiet handle, so
+    // no frame in flight ever reads a plane that is being written.  A property of the handle, not state: reset and snapshots leave it alone.
+    std::vector<uint8_t *> d_mask;            // [B][2] u8 planes, each sequence's own pitch (allocated at the first set, kept across an unset)
+    std::vector<uint8_t> mask_on;             // [B][2] != 0: the eye has a mask (empty until the first set)
+    int n_mask = 0;                           // sequences with a mask on either eye
+    bool ring_masked[RING] = {};              // per un-collected / last frame: the step went through k_mask_features under the masks the handle has now
+    bool has_mask(int s, int e) const { return n_mask > 0 && mask_on[(size_t)s * 2 + e] != 0; }
     // the depth plane the host entry points of sequence 0 take: the camera's size where one is set, else the image's
     size_t depth_px() const { return has_depth_cam(0) ? (size_t)depth_cam[0].width * depth_cam[0].height : (size_t)prm.W * prm.H; }
     int depth_cols() const { return has_depth_cam(0) ? depth_cam[0].width : prm.W; }
@@ -327,7 +336,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 26;
+    static constexpr int PROF_SLOTS = 27;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -890,7 +899,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -977,6 +986,7 @@ static void rectify_raw_frames(Context *c, int slot, int par, int Bz);
 static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
 static void scatter_depth_planes(Context *c, const DepthRegPlan &plan);
+static void mask_features(Context *c, int slot, int par, int Bz);
 static void enqueue_frame(Context *c) {
     HostTimer ht(&c->host_enq_us);
     c->host_enq_n++;
@@ -1023,7 +1033,7 @@ static void enqueue_frame(Context *c) {
     //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
     //      (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
     //      in front of k_gather.
-    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = false;
+    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = false;
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
     if (c->n_equal) equalise_frames(c, slot, par, Bz);
@@ -1091,6 +1101,7 @@ static void enqueue_frame(Context *c) {
     }
     scatter_depth_planes(c, dreg);  // (behind the wait for ev_depth: a host call's depth plane arrives on the early stream)
     LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
+    if (c->n_mask) mask_features(c, slot, par, Bz);  // (the seam: k_gather has written the Feat arrays and *F.n, k_brief reads them)
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
     if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
     else LAUNCH_S(6, sf, k_brief, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
@@ -1761,6 +1772,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if ((slot == 22 || slot == 23) && c->prof_calls[22] + c->prof_calls[23] == 0) return 0;  // (... and one that never took or applied a snapshot neither state kernel)
     if ((slot == 17 || slot == 21) && c->n_depth_cam == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without a depth camera no registration launches)
     if ((slot == 24 || slot == 25) && c->n_equal == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without an equalisation record neither of its launches)
+    if (slot == 26 && c->n_mask == 0 && c->prof_calls[26] == 0) return 0;  // (... and one that never set a mask no k_mask_features)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -2660,6 +2672,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             HIPCHK(c, hipMemcpy(dst, what == 5 ? c->d_eq[(size_t)c->last_par * 2 + ee] : c->d_eq_lut[(size_t)ee], bytes, hipMemcpyDeviceToHost));
             if (pitch_out) *pitch_out = what == 5 ? c->pitch : 256;
             return (int)bytes;
+        }
+        if (what == 7) {  // the eye's mask as the tracker holds it (u8, rows x pitch, the padding columns zero); 0 bytes without one.  A property: needs no frame
+            if (!c->has_mask(0, e)) return 0;
+            if ((size_t)cap_bytes < n) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_mask[(size_t)e], n, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->pitch;
+            return (int)n;
         }
         if (what >= 2 && what <= 4) {  // a frame property's plane: 0 bytes unless the last frame went through that stage
             if (c->done == 0) return 0;
