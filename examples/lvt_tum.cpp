@@ -2,6 +2,7 @@
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/tum_rgbd/tum_rgbd_example.cpp:49-150 there):
 //     lvt_tum <tum_sequences_root_dir> <associations_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--mask FILE]
+//                [--depth-guard [R,N,ABS,REL]]
 // reads <associations_dir>/<dataset_name>.txt ("t_rgb rgb/xxx.png t_depth depth/xxx.png" per line), the colour and the 16-bit
 // depth PNGs below <root>/<dataset_name>/, hands the decoded RGB to the tracker as it is (LVT_AMD_PIX_RGB8: the conversion to gray, cv::cvtColor's
 // weights, is the first launch of the frame's feature stage; a dataset of gray PNGs goes in as gray) and the PNG's 16-bit depth plane to
@@ -10,11 +11,15 @@
 // the TUM trajectory format "t x y z qx qy qz qw" with the reference's precision (6 digits for t, 7 for the rest).
 // --mask FILE (not in the reference): a feature mask (lvt_amd_set_mask), an 8-bit PNG or PGM of the configured image size, a pixel != 0: key points allowed.
 // A file of another size is refused before the first frame.
+// --depth-guard R,N,ABS,REL (not in the reference): a depth guard (lvt_amd_set_depth_guard): key points whose depth sample has fewer than N of the
+// (2R+1)^2 - 1 samples around it valid and within ABS + REL * depth metres of it are dropped.  The bare flag gives lvt_amd_depth_guard_default's record
+// (1,4,0.01,0.02).  A record outside its ranges is refused before the first frame.
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
 #include "image_io.h"
 
 #include <chrono>
+#include <cstdio>
 #include <iomanip>
 #include <iostream>
 #include <sstream>
@@ -29,8 +34,24 @@ int main(int argc, char **argv) {
     const std::string root_dir = argv[1], associations_dir = argv[2], dataset_name = argv[3], config_file_name = argv[4];
     std::string out_name = dataset_name + ".txt", mask_name;
     long max_frames = -1;
-    for (int i = 5; i + 1 < argc; i += 2) {
+    bool guarded = false;
+    lvt_amd_depth_guard guard;
+    lvt_amd_depth_guard_default(&guard);
+    for (int i = 5; i < argc; i += 2) {
         const std::string k = argv[i];
+        if (k == "--depth-guard") {  // (the one option whose value may be left out)
+            guarded = true;
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                if (std::sscanf(argv[i + 1], "%d,%d,%f,%f", &guard.radius, &guard.min_support, &guard.tol_abs, &guard.tol_rel) != 4) {
+                    std::cout << "--depth-guard takes R,N,ABS,REL (got " << argv[i + 1] << ")" << std::endl;
+                    return -1;
+                }
+            } else {
+                i--;
+            }
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
         else if (k == "--mask") mask_name = argv[i + 1];
@@ -85,6 +106,10 @@ int main(int argc, char **argv) {
             std::cout << "failed to set the mask: " << lvt_amd_last_error(vo) << std::endl;
             return -1;
         }
+    }
+    if (guarded && lvt_amd_set_depth_guard(vo, &guard) != 0) {
+        std::cout << "failed to set the depth guard: " << lvt_amd_last_error(vo) << std::endl;
+        return -1;
     }
     long frame_count = (long)rgb_titles.size();
     if (max_frames >= 0 && max_frames < frame_count) frame_count = max_frames;

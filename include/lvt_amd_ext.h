@@ -520,6 +520,61 @@ LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]);
 LVT_API int lvt_amd_mask_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth, int16_t *hcx, int16_t *hcy, const uint8_t *mask,
                                   int width, int height, int pitch);
 
+/* DEPTH GUARD: RGB-D key points whose depth has no support around it are dropped inside the tracker's feature stage.  A key point's depth is ONE pixel of the
+ * depth plane, depth[(int)y][(int)x] (the reference does the same), and corners cluster where that sample is worst: on occlusion boundaries, where the corner a
+ * foreground edge makes with background texture is no 3-D point; on the flying pixels a time-of-flight or structured-light sensor delivers between foreground and
+ * background; on lone valid pixels inside holes.  A guard is a property of an RGB-D handle, or of one sequence of an RGB-D batch, like the depth camera; it is
+ * NOT offered for pooled and automatic seats, and a stereo handle is refused.  A handle or sequence that never sets a guard launches exactly what it did.
+ *
+ * DEFINITION (tests/depth_guard_util.py restates it in numpy; the checks hold the tracker to it bit for bit).  The record is
+ *     radius 1 ... 3;  min_support 1 ... (2 * radius + 1)^2 - 1;  tol_abs, tol_rel finite and >= 0 (metres, and a share of the depth)
+ * and lvt_amd_depth_guard_default gives {1, 4, 0.01f, 0.02f}.  The plane is the one the gather step sampled, with its pitch, format and scale: the registered
+ * fp32 plane where a depth camera is set, the 16-bit plane with its scale where the frame came in as LVT_AMD_DEPTH_U16.  A pixel's sample s is what the gather
+ * step would have read there: the value itself (fp32), or (float)raw * scale in ONE rounded fp32 multiply (16-bit).  A sample is VALID when
+ * near_plane <= s && s <= far_plane; a NaN is not valid.  For every feature the gather step kept, in its output order, with (bx, by) the raw position BRIEF
+ * samples at:
+ *     cx = (int)bx;  cy = (int)by                  -- truncation, the gather step's own pixel; inside the plane when bx > -1 && bx < W && by > -1 && by < H
+ *     d_c = s(cx, cy);  the feature is dropped when the pixel is outside the plane or d_c is not valid
+ *     t = tol_abs + tol_rel * d_c                  -- two rounded fp32 operations, the product first; no fused multiply-add
+ *     support = the number of (dx, dy) != (0, 0) with |dx|, |dy| <= radius and (cx + dx, cy + dy) inside the plane whose sample s is valid and has
+ *               fabsf(s - d_c) <= t                -- one rounded fp32 subtraction
+ *     keep = support >= min_support
+ * The kept features stay in order (a stable compaction) and the feature count becomes their number; the depth a kept feature reports stays the centre sample.
+ * Consequences:
+ *  - ORDERING.  The guard acts after detection, ANMS, the border filter and the depth-range filter, and after the truncation to 4096 features; it acts BEFORE the
+ *    feature mask, whose statistics count what the guard left.  The "fewer than 200 corners" retry is decided as before, on the detector's count.
+ *  - The window is clipped at the plane's border: a key point near it has fewer neighbours to draw support from, never an implied one.
+ *  - In a registered plane a pixel nothing landed on (+inf) is simply not valid.
+ *  - FRACTIONAL positions are guarded at their truncated pixel, the gather step's own.  The tracker never meets one: lvt_track_with_external_corners is a stereo
+ *    entry (as in the reference) and a stereo handle has no guard; lvt_amd_depth_guard_features takes positions of any bit pattern.
+ *  - A guard is a property, not state: lvt_amd_reset and snapshots neither hold nor change it; the snapshot bytes are what they were.
+ *  - EQUIVALENCE.  Detected corners are integers, so a guarded frame equals the unguarded tracker fed the plane where(keep, depth, 0), keep being the rule above
+ *    evaluated at every pixel: a zero fails the depth-range test of the gather step exactly where the guard would have dropped the key point, and the retry does
+ *    not look at depth.  This ends at the truncation: in a frame with more than 4096 key points behind the depth-range test (reported as a capacity overflow) the
+ *    guard thins the first 4096, while the zeroed plane lets later ones move up.  Lens distortion is covered: the gather step and the guard read the same
+ *    raw pixel, whatever (x, y) the feature is reported with.
+ * One launch (k_depth_guard, reported under that name by lvt_amd_profile_read for a handle with a guard) directly behind the gather step.
+ *
+ * CALLS.  lvt_amd_set_depth_guard / lvt_amd_batch_set_depth_guard copy the record; NULL unsets the property.  Refused under the "Frame properties" contract, in
+ * this order, each with -1, the handle as it was and the sentence in lvt_amd_last_error ending in "(nothing was changed)": a bad handle (no report); a pooled or
+ * automatic seat; a stereo handle; the batch call on a solo handle and the solo call on a batch; seq out of range; a record outside the ranges above (the
+ * sentence names the field and its limits); frames in flight.
+ *  - lvt_amd_get_depth_guard: 1 = *out written; 0 = the sequence has no guard; -1 = bad handle / seq.
+ *  - lvt_amd_get_depth_guard_stats: out = {kept, dropped} of the frame lvt_amd_get_counts answers for.  1 = written; 0 = the sequence has no guard, its last
+ *    frame went in before the record it has now was set, or it sat the last collected step of its batch out; -1 = bad handle / seq.
+ *  - lvt_amd_depth_guard_features: the stage alone on caller data (host pointers).  The n <= 4096 features' eight arrays are compacted in place against a
+ *    width x height depth plane of `pitch_elems` elements per row (depth_format LVT_AMD_DEPTH_F32 / _U16, depth_scale for the latter) and come back whole;
+ *    returns the new count, -1 on a refusal (lvt_amd_last_error(NULL)). */
+typedef struct { int radius; int min_support; float tol_abs; float tol_rel; } lvt_amd_depth_guard;
+LVT_API void lvt_amd_depth_guard_default(lvt_amd_depth_guard *out);
+LVT_API int lvt_amd_set_depth_guard(lvt_handle h, const lvt_amd_depth_guard *cfg);                  /* 0 / -1 */
+LVT_API int lvt_amd_batch_set_depth_guard(lvt_handle h, int seq, const lvt_amd_depth_guard *cfg);
+LVT_API int lvt_amd_get_depth_guard(lvt_handle h, int seq, lvt_amd_depth_guard *out);
+LVT_API int lvt_amd_get_depth_guard_stats(lvt_handle h, int seq, int out[2]);
+LVT_API int lvt_amd_depth_guard_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth_of, int16_t *hcx, int16_t *hcy,
+                                         const void *depth, int depth_format, float depth_scale, int width, int height, int pitch_elems, float near_plane,
+                                         float far_plane, const lvt_amd_depth_guard *cfg);
+
 /* ---- SNAPSHOTS: one sequence's state saved, restored, moved between handles and seats -------------------------------------------------
  * A tracker's state lives in HBM: its control record, the local map, the staged points and the motion model.  A snapshot is a copy of it, device-resident and
  * owned by the library: ONE contiguous allocation (header | control record | the live map and staged arrays, the first map_n / staged_n points in storage

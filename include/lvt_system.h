@@ -333,6 +333,10 @@ class lvt_system {
      * step and BRIEF).  One eye may be nullptr (no mask for it); both nullptr: no masks again.  The buffers are copied before the call returns.
      * false: refused (last_error() says why), nothing changed. */
     bool set_mask(const unsigned char *left, const unsigned char *right = nullptr) { return lvt_amd_set_mask(m_handle, left, right) == 0; }
+    /* ADDITIVE: depth guard (include/lvt_amd_ext.h, DEPTH GUARD) of an RGB-D system: from now on every frame loses the key points whose depth sample has fewer than
+     * min_support of the (2 * radius + 1)^2 - 1 samples around it valid and within tol_abs + tol_rel * depth of it (one launch directly behind the gather step);
+     * lvt_amd_depth_guard_default fills the usual record.  nullptr: no guard again.  false: refused (last_error() says why), nothing changed. */
+    bool set_depth_guard(const lvt_amd_depth_guard *cfg) { return lvt_amd_set_depth_guard(m_handle, cfg) == 0; }
     lvt_pose wait_pose() {
         double q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0};
         m_state = lvt_amd_wait_pose(m_handle, q, p);

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
     "lvt_amd_set_mask", "lvt_amd_batch_set_mask", "lvt_amd_set_mask_device", "lvt_amd_batch_set_mask_device", "lvt_amd_get_mask_stats", "lvt_amd_mask_features",
+    "lvt_amd_depth_guard_default", "lvt_amd_set_depth_guard", "lvt_amd_batch_set_depth_guard", "lvt_amd_get_depth_guard", "lvt_amd_get_depth_guard_stats", "lvt_amd_depth_guard_features",
     "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve", "lvt_amd_reloc_correspond",
 ]
 
@@ -225,6 +226,13 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes, restype in (   # (depth guard: likewise)
+            ("lvt_amd_depth_guard_default", [vp], None), ("lvt_amd_set_depth_guard", [vp, vp], C.c_int), ("lvt_amd_batch_set_depth_guard", [vp, C.c_int, vp], C.c_int),
+            ("lvt_amd_get_depth_guard", [vp, C.c_int, vp], C.c_int), ("lvt_amd_get_depth_guard_stats", [vp, C.c_int, vp], C.c_int),
+            ("lvt_amd_depth_guard_features", [C.c_int] + [vp] * 9 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp], C.c_int)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
     for name, argtypes, restype in (   # (relocalisation: likewise)
             ("lvt_amd_relocalise", [vp, vp, vp], C.c_int), ("lvt_amd_batch_relocalise", [vp, C.c_int, vp, vp], C.c_int),
             ("lvt_amd_odometry_set_relocalisation", [vp, vp, C.c_int], C.c_int), ("lvt_amd_reloc_default_config", [vp], None), ("lvt_amd_reloc_slice_length", [C.c_int], C.c_int),
@@ -391,6 +399,77 @@ def mask_features(x, y, resp, bx, by, depth, hcx, hcy, mask, width: int = None, 
     rc = load_library().lvt_amd_mask_features(n, *[_p(a) for a in f + h], _p(flat), width, height, pitch)
     if rc < 0:
         raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_mask_features failed")
+    return (rc, *f, *h)
+
+
+class DepthGuard(C.Structure):
+    """lvt_amd_depth_guard: an RGB-D key point is kept when at least min_support of the (2 * radius + 1)^2 - 1 depth samples around its own are valid and within
+    tol_abs + tol_rel * depth of it (include/lvt_amd_ext.h, DEPTH GUARD) -- radius 1 ... 3, min_support 1 ... (2 * radius + 1)^2 - 1, tolerances finite and >= 0.
+    The defaults are lvt_amd_depth_guard_default's"""
+    _fields_ = [("radius", C.c_int), ("min_support", C.c_int), ("tol_abs", C.c_float), ("tol_rel", C.c_float)]
+
+    def __init__(self, radius=1, min_support=4, tol_abs=0.01, tol_rel=0.02):
+        super().__init__(int(radius), int(min_support), float(tol_abs), float(tol_rel))
+
+    def __repr__(self):
+        return f"DepthGuard(radius={int(self.radius)}, min_support={int(self.min_support)}, tol_abs={float(self.tol_abs)!r}, tol_rel={float(self.tol_rel)!r})"
+
+
+def depth_guard_default() -> DepthGuard:
+    """the record lvt_amd_depth_guard_default fills"""
+    g = DepthGuard(0, 0, 0.0, 0.0)
+    load_library().lvt_amd_depth_guard_default(C.byref(g))
+    return g
+
+
+def _depth_guard_arg(cfg, kw):
+    if cfg is None and kw:
+        cfg = DepthGuard(**kw)
+    return cfg
+
+
+def _depth_guard_of(handle, seq):
+    g = DepthGuard()
+    rc = load_library().lvt_amd_get_depth_guard(handle, int(seq), C.byref(g))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_depth_guard: bad handle or no sequence {seq}")
+    return g if rc == 1 else None
+
+
+def _depth_guard_stats_of(handle, seq):
+    out = np.zeros(2, dtype=np.int32)
+    rc = load_library().lvt_amd_get_depth_guard_stats(handle, int(seq), _p(out))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_depth_guard_stats: bad handle or no sequence {seq}")
+    if rc == 0:
+        return None
+    return {"kept": int(out[0]), "dropped": int(out[1])}
+
+
+def depth_guard_features(x, y, resp, bx, by, depth_of, hcx, hcy, depth, cfg: DepthGuard, near_plane: float, far_plane: float, depth_scale: float = 0.0,
+                         width: int = None, height: int = None):
+    """stage entry: the depth-guard kernel alone on n <= 4096 features (include/lvt_amd_ext.h, DEPTH GUARD).  depth: a 2-D float32 (metres) or uint16 (raw units,
+    metres = raw * depth_scale) array whose row stride is the pitch (a view into a wider array keeps its pitch); width / height default to its shape.  Returns
+    (n_kept, x, y, resp, bx, by, depth_of, hcx, hcy): the arrays as the kernel left them, the first n_kept elements being the kept features in order.
+    RuntimeError with the reason when refused."""
+    f = [np.array(a, dtype=np.float32).ravel() for a in (x, y, resp, bx, by, depth_of)]
+    h = [np.array(a, dtype=np.int16).ravel() for a in (hcx, hcy)]
+    n = f[0].size
+    if any(a.size != n for a in f + h):
+        raise ValueError("the eight feature arrays differ in length")
+    d = np.asarray(depth)
+    if d.dtype not in (np.float32, np.uint16) or d.ndim != 2 or d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize or d.strides[0] % d.itemsize:
+        raise ValueError("depth: a 2-D float32 or uint16 array with contiguous rows")
+    width = d.shape[1] if width is None else int(width)
+    height = d.shape[0] if height is None else int(height)
+    pitch = d.strides[0] // d.itemsize
+    flat = np.zeros(pitch * height, dtype=d.dtype)   # (the rows with their padding, as the plane lies in memory)
+    rows = np.lib.stride_tricks.as_strided(flat, shape=(height, d.shape[1]), strides=(pitch * d.itemsize, d.itemsize))
+    rows[:] = d[:height]
+    rc = load_library().lvt_amd_depth_guard_features(n, *[_p(a) for a in f + h], _p(flat), 1 if d.dtype == np.uint16 else 0, float(depth_scale), width, height, pitch,
+                                                     float(near_plane), float(far_plane), C.byref(cfg))
+    if rc < 0:
+        raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_depth_guard_features failed")
     return (rc, *f, *h)
 
 
@@ -892,6 +971,21 @@ class LvtSystem:
         last frame went in before the masks were set"""
         return _mask_stats_of(self._h, 0)
 
+    def set_depth_guard(self, cfg=None, **kw) -> int:
+        """a DepthGuard (or its arguments: radius=, min_support=, tol_abs=, tol_rel=): every RGB-D frame handed to this system from now on loses the key points
+        whose depth sample has too little support around it, one launch directly behind the gather step; None: no guard again.  0: done; -1: refused
+        (last_error())."""
+        cfg = _depth_guard_arg(cfg, kw)
+        return load_library().lvt_amd_set_depth_guard(self._h, C.byref(cfg) if cfg is not None else None)
+
+    def depth_guard(self):
+        """the DepthGuard that is set, or None"""
+        return _depth_guard_of(self._h, 0)
+
+    def depth_guard_stats(self):
+        """{"kept": n, "dropped": n} of the last frame's guard launch; None without a guard, or when the last frame went in before the record was set"""
+        return _depth_guard_stats_of(self._h, 0)
+
     def _depth(self, d):
         """the depth array of a host call: with a depth camera set the library reads cam.height x cam.width elements, and the C-ABI has no size argument for
         them -- an array of any other shape would be read past its end"""
@@ -988,7 +1082,7 @@ class LvtSystem:
         name = C.create_string_buffer(64); ms = C.c_double(0); calls = C.c_long(0)
         for slot in range(64):
             if not load_library().lvt_amd_profile_read(self._h, slot, name, 64, C.byref(ms), C.byref(calls)):
-                if slot >= 27:   # (past the last slot; the slots below it may be absent on this handle)
+                if slot >= 28:   # (past the last slot; the slots below it may be absent on this handle)
                     break
                 continue
             out.append((name.value.decode(), ms.value, calls.value))
@@ -1134,6 +1228,17 @@ class LvtBatch:
 
     def mask_stats(self, seq: int):
         return _mask_stats_of(self._h, seq)
+
+    def set_depth_guard(self, seq: int, cfg=None, **kw) -> int:
+        """LvtSystem.set_depth_guard for sequence `seq` of an RGB-D batch: its key points are guarded from then on, the other sequences' are not"""
+        cfg = _depth_guard_arg(cfg, kw)
+        return load_library().lvt_amd_batch_set_depth_guard(self._h, int(seq), C.byref(cfg) if cfg is not None else None)
+
+    def depth_guard(self, seq: int):
+        return _depth_guard_of(self._h, seq)
+
+    def depth_guard_stats(self, seq: int):
+        return _depth_guard_stats_of(self._h, seq)
 
     def enable_pose_info(self, on: bool = True) -> int:
         """LvtSystem.enable_pose_info for all sequences of the batch together"""

@@ -162,6 +162,9 @@ struct FeatCtl {        // per-frame state of the FEATURE stage (own stream, one
     // feature masks (k_mask.hip): what k_mask_features kept and dropped of this frame's features, per eye.  Scratch like lost_n: written only by the launch of a
     // masked sequence, read by lvt_amd_get_mask_stats
     int mask_kept[2], mask_dropped[2];
+    // depth guard (k_depthguard.hip): what k_depth_guard kept and dropped of this frame's features.  Scratch likewise: written only by the launch of a guarded
+    // sequence, read by lvt_amd_get_depth_guard_stats
+    int guard_kept, guard_dropped;
 };
 
 struct Feat {  // one image's lvt_image_features_struct (lvt_image_features_struct.h:62-80), SoA

@@ -1,5 +1,6 @@
 // lvt_frame_props.h -- the properties a handle, or one sequence of a batch, has besides its parameters (included by lvt_host.hip): rectifiers for raw frames,
-// a pixel format for colour frames, a depth camera for unregistered depth, an equalisation record for dim frames, the pose-uncertainty record.
+// a pixel format for colour frames, a depth camera for unregistered depth, an equalisation record for dim frames, a depth guard and feature masks behind the
+// gather step, the pose-uncertainty record.
 //
 // THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
 // was, lvt_amd_last_error says why); it needs a quiet handle (no frame in flight); an lvt_create handle is decided under its record's lock; a property is
@@ -382,6 +383,64 @@ static int set_equalisation(lvt_handle h, int seq, bool batch_call, const lvt_am
     });
 }
 
+// ---- depth guard: a record per RGB-D handle / per sequence of an RGB-D batch (Context::depth_guard, k_depthguard.hip) ------------------------------------
+// "" when the record passes: names the offending field and its limits otherwise
+static std::string depth_guard_check(const lvt_amd_depth_guard &g) {
+    if (g.radius < 1 || g.radius > 3) return "a depth guard with radius = " + std::to_string(g.radius) + " (1 ... 3)";
+    const int most = (2 * g.radius + 1) * (2 * g.radius + 1) - 1;
+    if (g.min_support < 1 || g.min_support > most)
+        return "a depth guard with min_support = " + std::to_string(g.min_support) + " at radius " + std::to_string(g.radius) + " (1 ... " + std::to_string(most) + ")";
+    if (!(std::isfinite(g.tol_abs) && g.tol_abs >= 0.f)) return "a depth guard whose tol_abs is not finite and >= 0";
+    if (!(std::isfinite(g.tol_rel) && g.tol_rel >= 0.f)) return "a depth guard whose tol_rel is not finite and >= 0";
+    return "";
+}
+// Every sequence of the step, guarded or not, takes a slot of the table (slot k of a launch is sequence z0 + k; a sequence without a guard, or without a frame
+// in this step, has radius 0 and leaves at the kernel's top); a table none of whose sequences has a guard is not launched.  The launch stands directly behind
+// k_gather and ahead of k_mask_features and k_brief / k_brief_img, in both orderings.  The depth plane is the one FeatCtl::in names -- k_gather has just read
+// it on this stream, so whatever made it complete for k_gather (the wait for ev_depth, k_depth_register) holds for the guard --, and the Feat arrays are
+// written by k_gather just ahead and read just behind, on this stream: stream order alone covers the hand-over, no gate.
+static void guard_features(Context *c, int slot, int par, int Bz) {
+    const FrameArgs *fw = &frame_args(c, slot);
+    int z0 = 0;
+    bool any = false, timed = false;
+    TablePacker pk(&GuardTable::s, [&](const GuardTable &tab, int n, bool) {
+        if (any && !timed) LAUNCH(27, c->stream_f, k_depth_guard, dim3(1, 1, n), dim3(1024), 0, c->d_seqs, tab, par, z0);
+        else if (any) hipLaunchKernelGGL(k_depth_guard, dim3(1, 1, n), dim3(1024), 0, c->stream_f, c->d_seqs, tab, par, z0);
+        timed = timed || any;
+        z0 += n, any = false;
+    });
+    for (int s = 0; s < Bz; s++) {
+        GuardSeq &G = *pk.add(1);
+        // EVERY field of EVERY slot is written: the packer's table is zeroed once, at its construction, and after a flush slot k still holds the record of
+        // the sequence GUARD_PACK places before this one
+        const bool on = c->has_guard(s) && !fw[s].absent;
+        G = on ? GuardSeq{c->depth_guard[(size_t)s].radius, c->depth_guard[(size_t)s].min_support, c->depth_guard[(size_t)s].tol_abs, c->depth_guard[(size_t)s].tol_rel}
+               : GuardSeq{};
+        any = any || on;
+    }
+    pk.flush();
+    c->ring_guarded[slot] = timed;
+}
+static int set_depth_guard(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_guard *cfg) {
+    static const PropertyCall call = {"lvt_amd_set_depth_guard", 2,
+                                      {"a pooled handle (pooled handles are stereo only) (nothing was changed)",
+                                       "a stereo handle (it has no depth plane to guard) (nothing was changed)",
+                                       "a batch handle takes its depth guards per sequence through lvt_amd_batch_set_depth_guard (nothing was changed)"},
+                                      "lvt_amd_batch_set_depth_guard on a handle that is not a batch (use lvt_amd_set_depth_guard)"};
+    // (an lvt_create handle is a stereo handle: refused like one)
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (cfg) {
+            const std::string why = depth_guard_check(*cfg);
+            if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        }
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the depth guard before the first frame or after every frame has been collected");
+        if (!cfg && !c->has_guard(seq)) return 0;
+        std::fill(std::begin(c->ring_guarded), std::end(c->ring_guarded), false);  // (the last frame went in under ANOTHER record: lvt_amd_get_depth_guard_stats has nothing of it)
+        c->n_guard = put_seq_value(c, c->depth_guard, 1, lvt_amd_depth_guard{}, seq, {cfg ? *cfg : lvt_amd_depth_guard{}}, [](const lvt_amd_depth_guard &g) { return g.radius > 0; });
+        return 0;
+    });
+}
+
 // ---- feature masks: u8 planes per handle / per sequence of a batch, one per eye (Context::d_mask, k_mask.hip) -------------------------------------------
 // Every sequence of the step, masked or not, takes a slot of the table (slot k of a launch is sequence z0 + k; an eye without a mask, and every eye of a
 // sequence without one, is a NULL pointer and leaves at the kernel's top); a table none of whose sequences has a mask is not launched.  The launch stands
@@ -550,6 +609,85 @@ LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void 
     hipLaunchKernelGGL(k_clahe_lut, dim3(cfg->tiles_x * cfg->tiles_y, 1), dim3(256), 0, st, tab);
     hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)(((size_t)(dst_pitch / 4) * h + 255) / 256), 1), dim3(256), 0, st, tab);
     return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
+}
+
+LVT_API void lvt_amd_depth_guard_default(lvt_amd_depth_guard *out) {
+    if (out) *out = lvt_amd_depth_guard{1, 4, 0.01f, 0.02f};
+}
+LVT_API int lvt_amd_set_depth_guard(lvt_handle h, const lvt_amd_depth_guard *cfg) { return set_depth_guard(h, 0, false, cfg); }
+LVT_API int lvt_amd_batch_set_depth_guard(lvt_handle h, int seq, const lvt_amd_depth_guard *cfg) { return set_depth_guard(h, seq, true, cfg); }
+LVT_API int lvt_amd_get_depth_guard(lvt_handle h, int seq, lvt_amd_depth_guard *out) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!c->has_guard(seq)) return 0;
+    if (out) *out = c->depth_guard[(size_t)seq];
+    return 1;
+}
+// out: {kept, dropped} of the frame lvt_amd_get_counts answers for; 0 for a sequence of a batch that sat the last collected step out
+LVT_API int lvt_amd_get_depth_guard_stats(lvt_handle h, int seq, int out[2]) {
+    h = resolve_handle(h);
+    if (out) out[0] = out[1] = 0;
+    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has a guard)
+    if (!is_ctx(h) || !out) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    DeviceGuard guard(c);
+    try {
+        drain(c);
+        if (c->done == 0 || !c->has_guard(seq) || !c->ring_guarded[c->last_slot]) return 0;
+        if (frame_args(c, c->last_slot, seq).absent) return 0;  // (ring_guarded is per step: a sequence that sat the step out went through no launch in it)
+        FeatCtl fc;
+        d2h(c, &fc, c->h_seqs[seq].fb[c->last_par].fc, 1);
+        out[0] = fc.guard_kept, out[1] = fc.guard_dropped;
+        return 1;
+    } catch (...) {
+    }
+    return -1;
+}
+// the stage alone on caller data (host pointers): the n features' eight arrays are compacted IN PLACE under the rule of "DEPTH GUARD" against a width x height
+// depth plane of `pitch_elems` elements per row, and every array comes back whole -- the elements behind the new count hold what the kernel left there.
+// Returns the new count, -1 on a refusal (lvt_amd_last_error(NULL)) or a HIP failure.
+LVT_API int lvt_amd_depth_guard_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth_of, int16_t *hcx, int16_t *hcy, const void *depth,
+                                         int depth_format, float depth_scale, int width, int height, int pitch_elems, float near_plane, float far_plane,
+                                         const lvt_amd_depth_guard *cfg) {
+    const char *who = "lvt_amd_depth_guard_features";
+    if (n < 0 || n > NF_MAX || !depth || !cfg || width < 1 || width > 8192 || height < 1 || height > 8192 || pitch_elems < width ||
+        (n > 0 && (!x || !y || !resp || !bx || !by || !depth_of || !hcx || !hcy)))
+        return refuse_call(who, "a NULL argument, n outside 0 ... 4096, a size outside 1 ... 8192 or a pitch smaller than the width (nothing was changed)");
+    if (depth_format != DEPTH_F32 && depth_format != DEPTH_U16) return refuse_call(who, "unknown depth format " + std::to_string(depth_format) + " (nothing was changed)");
+    if (depth_format == DEPTH_U16 && !(std::isfinite(depth_scale) && depth_scale > 0.f)) return refuse_call(who, "a 16-bit plane whose depth_scale is not finite and > 0 (nothing was changed)");
+    const std::string why = depth_guard_check(*cfg);
+    if (!why.empty()) return refuse_call(who, why + " (nothing was changed)");
+    const size_t nn = (size_t)n, esz = depth_format == DEPTH_U16 ? 2 : 4;
+    StageScratch S;
+    Seq hs;
+    std::memset(&hs, 0, sizeof(hs));
+    hs.prm.W = width, hs.prm.H = height, hs.prm.sensor = 2, hs.prm.near_plane = near_plane, hs.prm.far_plane = far_plane;
+    Feat &F = hs.fb[0].feat[0];
+    F.x = S.buf<float>(nn, x), F.y = S.buf<float>(nn, y), F.resp = S.buf<float>(nn, resp);
+    F.bx = S.buf<float>(nn, bx), F.by = S.buf<float>(nn, by), F.depth = S.buf<float>(nn, depth_of);
+    F.hcx = S.buf<int16_t>(nn, hcx), F.hcy = S.buf<int16_t>(nn, hcy);
+    F.n = S.buf<int>(1, &n);
+    FeatCtl fc;
+    std::memset(&fc, 0, sizeof(fc));
+    fc.in.depth_img = reinterpret_cast<const float *>(S.buf<uint8_t>((size_t)pitch_elems * height * esz, static_cast<const uint8_t *>(depth)));
+    fc.in.depth_pitch = pitch_elems, fc.in.depth_format = depth_format, fc.in.depth_scale = depth_format == DEPTH_U16 ? depth_scale : 0.f;
+    hs.fb[0].fc = S.buf<FeatCtl>(1, &fc);
+    GuardTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.s[0] = GuardSeq{cfg->radius, cfg->min_support, cfg->tol_abs, cfg->tol_rel};
+    const Seq *d_seq = S.buf<Seq>(1, &hs);
+    if (!S.ok()) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    hipLaunchKernelGGL(k_depth_guard, dim3(1, 1, 1), dim3(1024), 0, 0, d_seq, tab, 0, 0);
+    int n_new = -1;
+    if (hipGetLastError() == hipSuccess && S.fetch(&n_new, (const int *)F.n, 1) && S.fetch(x, (const float *)F.x, nn) && S.fetch(y, (const float *)F.y, nn) &&
+        S.fetch(resp, (const float *)F.resp, nn) && S.fetch(bx, (const float *)F.bx, nn) && S.fetch(by, (const float *)F.by, nn) &&
+        S.fetch(depth_of, (const float *)F.depth, nn) && S.fetch(hcx, (const int16_t *)F.hcx, nn) && S.fetch(hcy, (const int16_t *)F.hcy, nn))
+        return n_new;
+    return refuse_call(who, hipGetErrorString(hipGetLastError()));
 }
 
 LVT_API int lvt_amd_set_mask(lvt_handle h, const void *left, const void *right) { return set_mask(h, 0, false, false, left, 0, right, 0); }

@@ -21,6 +21,7 @@
 #include "k_rectify.hip"
 #include "k_depthreg.hip"
 #include "k_equalise.hip"
+#include "k_depthguard.hip"
 #include "k_mask.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
@@ -322,6 +323,12 @@ struct Context {
     int n_mask = 0;                           // sequences with a mask on either eye
     bool ring_masked[RING] = {};              // per un-collected / last frame: the step went through k_mask_features under the masks the handle has now
     bool has_mask(int s, int e) const { return n_mask > 0 && mask_on[(size_t)s * 2 + e] != 0; }
+    // DEPTH GUARD (lvt_amd_set_depth_guard / lvt_amd_batch_set_depth_guard): an RGB-D sequence with a record has the key points k_gather kept filtered by ONE
+    // k_depth_guard launch directly behind k_gather, ahead of k_mask_features.  A property of the handle, not state: reset and snapshots leave it alone.
+    std::vector<lvt_amd_depth_guard> depth_guard;  // [B] (empty until the first set; radius 0: the sequence has none)
+    int n_guard = 0;                          // sequences with a guard
+    bool ring_guarded[RING] = {};             // per un-collected / last frame: the step went through k_depth_guard under the records the handle has now
+    bool has_guard(int s) const { return n_guard > 0 && depth_guard[(size_t)s].radius > 0; }
     // the depth plane the host entry points of sequence 0 take: the camera's size where one is set, else the image's
     size_t depth_px() const { return has_depth_cam(0) ? (size_t)depth_cam[0].width * depth_cam[0].height : (size_t)prm.W * prm.H; }
     int depth_cols() const { return has_depth_cam(0) ? depth_cam[0].width : prm.W; }
@@ -336,7 +343,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 27;
+    static constexpr int PROF_SLOTS = 28;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -899,7 +906,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -987,6 +994,7 @@ static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
 static void scatter_depth_planes(Context *c, const DepthRegPlan &plan);
 static void mask_features(Context *c, int slot, int par, int Bz);
+static void guard_features(Context *c, int slot, int par, int Bz);
 static void enqueue_frame(Context *c) {
     HostTimer ht(&c->host_enq_us);
     c->host_enq_n++;
@@ -1033,7 +1041,7 @@ static void enqueue_frame(Context *c) {
     //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
     //      (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
     //      in front of k_gather.
-    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = false;
+    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = c->ring_guarded[slot] = false;
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
     if (c->n_equal) equalise_frames(c, slot, par, Bz);
@@ -1101,6 +1109,7 @@ static void enqueue_frame(Context *c) {
     }
     scatter_depth_planes(c, dreg);  // (behind the wait for ev_depth: a host call's depth plane arrives on the early stream)
     LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
+    if (c->n_guard) guard_features(c, slot, par, Bz);  // (directly behind k_gather: the plane it sampled is the plane the guard reads)
     if (c->n_mask) mask_features(c, slot, par, Bz);  // (the seam: k_gather has written the Feat arrays and *F.n, k_brief reads them)
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
     if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
@@ -1773,6 +1782,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if ((slot == 17 || slot == 21) && c->n_depth_cam == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without a depth camera no registration launches)
     if ((slot == 24 || slot == 25) && c->n_equal == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without an equalisation record neither of its launches)
     if (slot == 26 && c->n_mask == 0 && c->prof_calls[26] == 0) return 0;  // (... and one that never set a mask no k_mask_features)
+    if (slot == 27 && c->n_guard == 0 && c->prof_calls[27] == 0) return 0;  // (... and one that never set a depth guard no k_depth_guard)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
