@@ -508,7 +508,8 @@ LVT_API int lvt_amd_equalisation_plan(const lvt_amd_equalisation *cfg, int w, in
  * "(nothing was changed)": a bad handle (no report); a pooled or automatic seat; the batch call on a solo handle and the solo call on a batch; seq out of
  * range; a pitch smaller than the width; a right-eye mask on an RGB-D handle; frames in flight.  A successful set counts as a use of an lvt_create handle.
  *  - lvt_amd_get_mask_stats: out = {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for (an eye without a mask
- *    reports 0, 0).  1 = written; 0 = the sequence has no mask, or its last frame went in before the masks it has now were set; -1 = bad handle / seq.
+ *    reports 0, 0).  1 = written; 0 = the sequence has no mask, its last frame went in before the masks it has now were set, or it sat the last collected
+ *    step of its batch out; -1 = bad handle / seq.
  *  - lvt_amd_get_plane(h, eye, 7, ...) reads the mask back.
  *  - lvt_amd_mask_features: the stage alone on caller data (host pointers).  The n <= 4096 features' eight arrays are compacted in place against a
  *    width x height mask of `pitch` bytes per row and come back whole; returns the new count, -1 on a refusal (lvt_amd_last_error(NULL)). */

@@ -263,6 +263,45 @@ def _u8(img, bpp=1):
     return a
 
 
+def _record_of(fn_name, Struct, handle, seq):
+    """a per-sequence property record through its getter: the record, None where the sequence has none"""
+    r = Struct()
+    rc = getattr(load_library(), fn_name)(handle, int(seq), C.byref(r))
+    if rc < 0:
+        raise IndexError(f"{fn_name}: bad handle or no sequence {seq}")
+    return r if rc == 1 else None
+
+
+def _stats_of(fn_name, width, handle, seq):
+    """a filter's `width` stats words of the last collected frame as ints, None where the getter has nothing to report"""
+    out = np.zeros(width, dtype=np.int32)
+    rc = getattr(load_library(), fn_name)(handle, int(seq), _p(out))
+    if rc < 0:
+        raise IndexError(f"{fn_name}: bad handle or no sequence {seq}")
+    return [int(v) for v in out] if rc == 1 else None
+
+
+def _feature_arrays(x, y, resp, bx, by, depth, hcx, hcy):
+    """the eight arrays of n features as a filter's stage entry takes them, as fresh copies: (n, [six float32, two int16])"""
+    a = [np.array(v, dtype=np.float32).ravel() for v in (x, y, resp, bx, by, depth)] + [np.array(v, dtype=np.int16).ravel() for v in (hcx, hcy)]
+    if any(v.size != a[0].size for v in a):
+        raise ValueError("the eight feature arrays differ in length")
+    return a[0].size, a
+
+
+def _padded_plane(a, dtypes, width=None, height=None):
+    """a 2-D array of one of `dtypes` whose row stride is the pitch (a view into a wider array keeps its pitch), as the plane lies in memory: (the rows with
+    their padding as one flat copy, pitch in elements, width, height), the last two defaulting to the array's shape.  None for any other array"""
+    a = np.asarray(a)
+    if a.dtype not in dtypes or a.ndim != 2 or a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+        return None
+    height = a.shape[0] if height is None else int(height)
+    pitch = a.strides[0] // a.itemsize
+    flat = np.zeros(pitch * height, dtype=a.dtype)
+    np.lib.stride_tricks.as_strided(flat, shape=(height, a.shape[1]), strides=a.strides)[:] = a[:height]
+    return flat, pitch, a.shape[1] if width is None else int(width), height
+
+
 class DepthCamera(C.Structure):
     """lvt_amd_depth_camera: the camera an RGB-D sensor delivers its depth plane in (include/lvt_amd_ext.h, UNREGISTERED DEPTH) -- its image size, its pinhole
     (no distortion) and p_colour = R p_depth + t in metres"""
@@ -295,11 +334,7 @@ class DepthCamera(C.Structure):
 
 
 def _depth_camera_of(handle, seq):
-    cam = DepthCamera()
-    rc = load_library().lvt_amd_get_depth_camera(handle, int(seq), C.byref(cam))
-    if rc < 0:
-        raise IndexError(f"lvt_amd_get_depth_camera: bad handle or no sequence {seq}")
-    return cam if rc == 1 else None
+    return _record_of("lvt_amd_get_depth_camera", DepthCamera, handle, seq)
 
 
 def register_depth_device(cam: DepthCamera, params: LvtParameters, d_depth: int, depth_pitch: int, depth_format: int, depth_scale: float, d_out: int,
@@ -328,11 +363,7 @@ class Equalisation(C.Structure):
 
 
 def _equalisation_of(handle, seq):
-    e = Equalisation()
-    rc = load_library().lvt_amd_get_equalisation(handle, int(seq), C.byref(e))
-    if rc < 0:
-        raise IndexError(f"lvt_amd_get_equalisation: bad handle or no sequence {seq}")
-    return e if rc == 1 else None
+    return _record_of("lvt_amd_get_equalisation", Equalisation, handle, seq)
 
 
 def equalise_device(cfg: Equalisation, d_src: int, src_pitch: int, width: int, height: int, d_dst: int, dst_pitch: int, stream: int = 0) -> int:
@@ -369,37 +400,23 @@ def _mask_of(handle, seq, mask):
 
 
 def _mask_stats_of(handle, seq):
-    out = np.zeros(4, dtype=np.int32)
-    rc = load_library().lvt_amd_get_mask_stats(handle, int(seq), _p(out))
-    if rc < 0:
-        raise IndexError(f"lvt_amd_get_mask_stats: bad handle or no sequence {seq}")
-    if rc == 0:
-        return None
-    return {"kept": (int(out[0]), int(out[2])), "dropped": (int(out[1]), int(out[3]))}
+    out = _stats_of("lvt_amd_get_mask_stats", 4, handle, seq)
+    return out and {"kept": (out[0], out[2]), "dropped": (out[1], out[3])}
 
 
 def mask_features(x, y, resp, bx, by, depth, hcx, hcy, mask, width: int = None, height: int = None):
     """stage entry: the feature-mask kernel alone on n <= 4096 features (include/lvt_amd_ext.h, FEATURE MASKS).  mask: a 2-D uint8 array whose row stride is the
     pitch (a view into a wider array keeps its pitch); width / height default to its shape.  Returns (n_kept, x, y, resp, bx, by, depth, hcx, hcy): the arrays as
     the kernel left them, the first n_kept elements being the kept features in order.  RuntimeError with the reason when refused."""
-    f = [np.array(a, dtype=np.float32).ravel() for a in (x, y, resp, bx, by, depth)]
-    h = [np.array(a, dtype=np.int16).ravel() for a in (hcx, hcy)]
-    n = f[0].size
-    if any(a.size != n for a in f + h):
-        raise ValueError("the eight feature arrays differ in length")
-    m = np.asarray(mask)
-    if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+    n, arrays = _feature_arrays(x, y, resp, bx, by, depth, hcx, hcy)
+    plane = _padded_plane(mask, (np.uint8,), width, height)
+    if plane is None:
         raise ValueError("mask: a 2-D uint8 array with contiguous rows")
-    width = m.shape[1] if width is None else int(width)
-    height = m.shape[0] if height is None else int(height)
-    pitch = m.strides[0]
-    flat = np.zeros(pitch * height, dtype=np.uint8)   # (the rows with their padding, as the plane lies in memory)
-    rows = np.lib.stride_tricks.as_strided(flat, shape=(height, m.shape[1]), strides=(pitch, 1))
-    rows[:] = m[:height]
-    rc = load_library().lvt_amd_mask_features(n, *[_p(a) for a in f + h], _p(flat), width, height, pitch)
+    flat, pitch, width, height = plane
+    rc = load_library().lvt_amd_mask_features(n, *[_p(a) for a in arrays], _p(flat), width, height, pitch)
     if rc < 0:
         raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_mask_features failed")
-    return (rc, *f, *h)
+    return (rc, *arrays)
 
 
 class DepthGuard(C.Structure):
@@ -429,21 +446,12 @@ def _depth_guard_arg(cfg, kw):
 
 
 def _depth_guard_of(handle, seq):
-    g = DepthGuard()
-    rc = load_library().lvt_amd_get_depth_guard(handle, int(seq), C.byref(g))
-    if rc < 0:
-        raise IndexError(f"lvt_amd_get_depth_guard: bad handle or no sequence {seq}")
-    return g if rc == 1 else None
+    return _record_of("lvt_amd_get_depth_guard", DepthGuard, handle, seq)
 
 
 def _depth_guard_stats_of(handle, seq):
-    out = np.zeros(2, dtype=np.int32)
-    rc = load_library().lvt_amd_get_depth_guard_stats(handle, int(seq), _p(out))
-    if rc < 0:
-        raise IndexError(f"lvt_amd_get_depth_guard_stats: bad handle or no sequence {seq}")
-    if rc == 0:
-        return None
-    return {"kept": int(out[0]), "dropped": int(out[1])}
+    out = _stats_of("lvt_amd_get_depth_guard_stats", 2, handle, seq)
+    return out and {"kept": out[0], "dropped": out[1]}
 
 
 def depth_guard_features(x, y, resp, bx, by, depth_of, hcx, hcy, depth, cfg: DepthGuard, near_plane: float, far_plane: float, depth_scale: float = 0.0,
@@ -452,25 +460,16 @@ def depth_guard_features(x, y, resp, bx, by, depth_of, hcx, hcy, depth, cfg: Dep
     metres = raw * depth_scale) array whose row stride is the pitch (a view into a wider array keeps its pitch); width / height default to its shape.  Returns
     (n_kept, x, y, resp, bx, by, depth_of, hcx, hcy): the arrays as the kernel left them, the first n_kept elements being the kept features in order.
     RuntimeError with the reason when refused."""
-    f = [np.array(a, dtype=np.float32).ravel() for a in (x, y, resp, bx, by, depth_of)]
-    h = [np.array(a, dtype=np.int16).ravel() for a in (hcx, hcy)]
-    n = f[0].size
-    if any(a.size != n for a in f + h):
-        raise ValueError("the eight feature arrays differ in length")
-    d = np.asarray(depth)
-    if d.dtype not in (np.float32, np.uint16) or d.ndim != 2 or d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize or d.strides[0] % d.itemsize:
+    n, arrays = _feature_arrays(x, y, resp, bx, by, depth_of, hcx, hcy)
+    plane = _padded_plane(depth, (np.float32, np.uint16), width, height)
+    if plane is None:
         raise ValueError("depth: a 2-D float32 or uint16 array with contiguous rows")
-    width = d.shape[1] if width is None else int(width)
-    height = d.shape[0] if height is None else int(height)
-    pitch = d.strides[0] // d.itemsize
-    flat = np.zeros(pitch * height, dtype=d.dtype)   # (the rows with their padding, as the plane lies in memory)
-    rows = np.lib.stride_tricks.as_strided(flat, shape=(height, d.shape[1]), strides=(pitch * d.itemsize, d.itemsize))
-    rows[:] = d[:height]
-    rc = load_library().lvt_amd_depth_guard_features(n, *[_p(a) for a in f + h], _p(flat), 1 if d.dtype == np.uint16 else 0, float(depth_scale), width, height, pitch,
-                                                     float(near_plane), float(far_plane), C.byref(cfg))
+    flat, pitch, width, height = plane
+    rc = load_library().lvt_amd_depth_guard_features(n, *[_p(a) for a in arrays], _p(flat), 1 if flat.dtype == np.uint16 else 0, float(depth_scale), width, height,
+                                                     pitch, float(near_plane), float(far_plane), C.byref(cfg))
     if rc < 0:
         raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_depth_guard_features failed")
-    return (rc, *f, *h)
+    return (rc, *arrays)
 
 
 class SnapshotInfo(C.Structure):

@@ -2,13 +2,10 @@
 // (lvt_amd_set_depth_guard; include/lvt_amd_ext.h has the definition under DEPTH GUARD, tests/depth_guard_util.py restates it in numpy).  ONE launch directly
 // behind k_gather, which writes the Feat arrays and *F.n from ONE pixel of the depth plane per key point, and ahead of k_mask_features, k_brief and k_brief_img,
 // which read them: no existing kernel body changes, and a handle that never set a guard launches exactly what it did.
-//   k_depth_guard : one workgroup of 1024 threads per sequence, in the shape of k_mask_features.  It walks the *F.n features k_gather kept in chunks of 1024: a
-//                   thread loads its feature's eight values into registers, reads the sample under k_gather's own pixel again and the (2r+1)^2 - 1 samples
-//                   around it, counts those that are valid and within the tolerance of the centre, and the chunk's exclusive scan (block_excl_scan) gives the
-//                   kept features their places.  The compaction is IN PLACE and stable: every load of a chunk has completed -- the scan's barriers stand
-//                   between -- before any store of the chunk, a store goes to an index <= the thread's own, so a later chunk is never overwritten before it is
-//                   read; `flag` is already zero below the old count and is not touched; F.depth keeps the centre sample k_gather stored.
-//                   Thread 0 stores the new *F.n and FeatCtl::guard_kept / guard_dropped.
+//   k_depth_guard : one workgroup of 1024 threads per sequence, in the shape of k_mask_features.  The walk and its in-place compaction are compact_features
+//                   (lvt_dev.h, which says why it is safe).  The rule reads the sample under k_gather's own pixel again (depth_sample, the function k_gather
+//                   calls) and the (2r+1)^2 - 1 samples around it and counts those that are valid and within the tolerance of the centre; F.depth keeps the
+//                   centre sample k_gather stored.  Thread 0 stores FeatCtl::guard_kept / guard_dropped.
 // A THREAD PER FEATURE, not a few lanes per feature with a cross-lane sum.  The window's loads do not depend on one another and the radius is a template
 // argument, so a thread's 8 / 24 / 48 loads unroll, and a frame's <= 4096 features are <= 4 chunks of 16 waves.  What the launch costs is the fetch of the
 // window's cache lines through ONE compute unit -- a feature's window spans 3 / 5 / 7 rows of the plane, each another line, and k_gather has pulled only the
@@ -40,10 +37,8 @@ struct GuardPlane {
     float scale, near_plane, far_plane;
     int W, H;
 };
-// the sample k_gather would have read at element i: the value itself, or ONE rounded fp32 multiply of the exactly converted 16-bit raw
-__device__ __forceinline__ float guard_sample(const GuardPlane &P, size_t i) {
-    return (P.fmt == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(P.img)[i], P.scale) : P.img[i];
-}
+// the sample k_gather reads at element i
+__device__ __forceinline__ float guard_sample(const GuardPlane &P, size_t i) { return depth_sample(P.img, P.fmt, P.scale, i); }
 __device__ __forceinline__ bool guard_valid(const GuardPlane &P, float s) { return P.near_plane <= s && s <= P.far_plane; }  // (a NaN fails both)
 
 // the support of the sample d_c at pixel (cx, cy), inside the plane: the window's samples other than the centre that lie inside the plane, are valid and within
@@ -85,39 +80,13 @@ __global__ __launch_bounds__(1024) void k_depth_guard(const Seq *seqs, GuardTabl
     if (ctl.poison) return;
     __shared__ int scan[16];
     const Feat &F = FB.feat[0];
-    const int tid = threadIdx.x;
     GuardPlane P;
     P.img = ctl.in.depth_img, P.pitch = ctl.in.depth_pitch, P.fmt = ctl.in.depth_format, P.scale = ctl.in.depth_scale;
     P.near_plane = S.prm.near_plane, P.far_plane = S.prm.far_plane;
     P.W = S.prm.W, P.H = S.prm.H;
-    const int n_in = min(max(*F.n, 0), NF_MAX);
-    int n_out = 0;
-    for (int base = 0; base < n_in; base += 1024) {
-        const int g = base + tid;
-        bool keep = false;
-        float x = 0, y = 0, r = 0, bx = 0, by = 0, dep = 0;
-        int16_t hcx = 0, hcy = 0;
-        if (g < n_in) {
-            x = F.x[g], y = F.y[g], r = F.resp[g];
-            bx = F.bx[g], by = F.by[g];
-            dep = F.depth[g];
-            hcx = F.hcx[g], hcy = F.hcy[g];
-            keep = guard_keep(P, G, bx, by);
-        }
-        int total;
-        const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);   // (its barriers: every load of the chunk, *F.n included, is complete)
-        if (keep && off != g) {   // off <= g; a feature that stays where it is needs no store
-            F.x[off] = x, F.y[off] = y, F.resp[off] = r;
-            F.bx[off] = bx, F.by[off] = by;
-            F.depth[off] = dep;
-            F.hcx[off] = hcx, F.hcy[off] = hcy;
-        }
-        n_out += total;
-    }
-    if (tid == 0) {
-        *F.n = n_out;
-        ctl.guard_kept = n_out, ctl.guard_dropped = n_in - n_out;
-    }
+    int n_in;
+    const int n_out = compact_features(F, scan, &n_in, [&](float bx, float by) { return guard_keep(P, G, bx, by); });
+    if (threadIdx.x == 0) ctl.guard_kept = n_out, ctl.guard_dropped = n_in - n_out;
 }
 
 }  // namespace lvt

@@ -1933,9 +1933,7 @@ __global__ __launch_bounds__(1024) void k_gather(SeqArg<BV> sa, int par) {
             keep = brief_border_keep(x, y, H, W);
             if (keep && rgbd) {  // handler.cpp:255-265 (depth at the distorted pixel), :268-294
                 const size_t di = (size_t)((int)y) * depth_pitch + (int)x;
-                // DEPTH_U16: one 16-bit load, an exact conversion and ONE rounded fp32 multiply -- what a caller's own `(float)raw * scale` gives, so a
-                // 16-bit frame tracks exactly like its fp32 conversion; raw 0 ("no depth") is 0.0f and falls to the near-plane test below
-                dep = (depth_format == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(depth_img)[di], depth_scale) : depth_img[di];
+                dep = depth_sample(depth_img, depth_format, depth_scale, di);  // (a DEPTH_U16 raw 0, "no depth", is 0.0f and falls to the near-plane test below)
                 keep = (dep >= S.prm.near_plane && dep <= S.prm.far_plane);
                 if (keep && S.prm.undistort) {
                     undistort_point(S.prm, x, y, x, y);

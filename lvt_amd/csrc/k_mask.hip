@@ -1,13 +1,10 @@
 // k_mask.hip -- feature masks: key points on masked pixels are dropped inside the feature stage (lvt_amd_set_mask; include/lvt_amd_ext.h has the definition,
 // tests/mask_util.py restates it in numpy).  ONE launch at the seam between k_gather, which writes the Feat arrays and *F.n, and k_brief / k_brief_img, which
 // read them: no existing kernel body changes, and a handle that never set a mask launches exactly what it did.
-//   k_mask_features : one workgroup of 1024 threads per (sequence, eye).  It walks the *F.n features k_gather kept in chunks of 1024, in the shape of
-//                     k_gather's output loop: a thread loads its feature's eight values into registers, fetches the mask byte under the pixel BRIEF samples at
-//                     (an ordinary load: the kept corners of a frame touch a few thousand scattered bytes of a plane that stays in L2 from frame to frame) and
-//                     the chunk's exclusive scan (block_excl_scan) gives the kept features their places.  The compaction is IN PLACE and stable: every load
-//                     of a chunk has completed -- the scan's barriers stand between -- before any store of the chunk, a store goes to an index <= the
-//                     thread's own, so a later chunk is never overwritten before it is read; `flag` is already zero below the old count and is not touched.
-//                     Thread 0 stores the new *F.n and the eye's kept / dropped counts (FeatCtl::mask_kept / mask_dropped).
+//   k_mask_features : one workgroup of 1024 threads per (sequence, eye).  The walk and its in-place compaction are compact_features (lvt_dev.h, which says why
+//                     it is safe).  The rule fetches the mask byte under the pixel BRIEF samples at (an ordinary load: the kept corners of a frame touch a few
+//                     thousand scattered bytes of a plane that stays in L2 from frame to frame).  Thread 0 stores the eye's kept / dropped counts
+//                     (FeatCtl::mask_kept / mask_dropped).
 // The per-sequence mask pointers and pitches travel BY VALUE like GrayTable / RectTable: blockIdx.z is the slot, slot k belongs to sequence z0 + k, and a
 // sequence or an eye without a mask has a NULL pointer and leaves at the top.  No scratch.
 #include "lvt_dev.h"
@@ -45,36 +42,10 @@ __global__ __launch_bounds__(1024) void k_mask_features(const Seq *seqs, MaskTab
     if (ctl.poison) return;
     __shared__ int scan[16];
     const Feat &F = FB.feat[eye];
-    const int tid = threadIdx.x;
     const int W = S.prm.W, H = S.prm.H;
-    const int n_in = min(max(*F.n, 0), NF_MAX);
-    int n_out = 0;
-    for (int base = 0; base < n_in; base += 1024) {
-        const int g = base + tid;
-        bool keep = false;
-        float x = 0, y = 0, r = 0, bx = 0, by = 0, dep = 0;
-        int16_t hcx = 0, hcy = 0;
-        if (g < n_in) {
-            x = F.x[g], y = F.y[g], r = F.resp[g];
-            bx = F.bx[g], by = F.by[g];
-            dep = F.depth[g];
-            hcx = F.hcx[g], hcy = F.hcy[g];
-            keep = mask_keep(mask, pitch, W, H, bx, by);
-        }
-        int total;
-        const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);   // (its barriers: every load of the chunk, *F.n included, is complete)
-        if (keep && off != g) {   // off <= g; a feature that stays where it is needs no store
-            F.x[off] = x, F.y[off] = y, F.resp[off] = r;
-            F.bx[off] = bx, F.by[off] = by;
-            F.depth[off] = dep;
-            F.hcx[off] = hcx, F.hcy[off] = hcy;
-        }
-        n_out += total;
-    }
-    if (tid == 0) {
-        *F.n = n_out;
-        ctl.mask_kept[eye] = n_out, ctl.mask_dropped[eye] = n_in - n_out;
-    }
+    int n_in;
+    const int n_out = compact_features(F, scan, &n_in, [&](float bx, float by) { return mask_keep(mask, pitch, W, H, bx, by); });
+    if (threadIdx.x == 0) ctl.mask_kept[eye] = n_out, ctl.mask_dropped[eye] = n_in - n_out;
 }
 
 }  // namespace lvt

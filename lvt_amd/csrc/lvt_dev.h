@@ -308,6 +308,50 @@ __device__ __forceinline__ int block_excl_scan(int v, int *scratch, int *total) 
     return base + incl - v;
 }
 
+// The walk of a filter behind k_gather (k_depth_guard, k_mask_features): one workgroup of 1024 threads compacts the *F.n features k_gather kept, in chunks of
+// 1024 and in the shape of k_gather's output loop.  A thread loads its feature's eight values into registers, keep_of(bx, by) is the filter's rule, and the
+// chunk's exclusive scan gives the kept features their places.  Returns the new count, which thread 0 has stored to *F.n; *n_before receives the old one.
+// IN PLACE and stable, and safe because: every load of a chunk, *F.n included, has completed -- the scan's barriers stand between -- before any store of the
+// chunk; a store goes to an index <= the thread's own, so a later chunk is never overwritten before it is read; `flag` is already zero below the old count
+// and is not touched.  Elements behind the new count keep what they held.
+template <typename Keep>
+__device__ __forceinline__ int compact_features(const Feat &F, int *scan, int *n_before, Keep keep_of) {
+    const int tid = threadIdx.x;
+    const int n_in = min(max(*F.n, 0), NF_MAX);
+    int n_out = 0;
+    for (int base = 0; base < n_in; base += 1024) {
+        const int g = base + tid;
+        bool keep = false;
+        float x = 0, y = 0, r = 0, bx = 0, by = 0, dep = 0;
+        int16_t hcx = 0, hcy = 0;
+        if (g < n_in) {
+            x = F.x[g], y = F.y[g], r = F.resp[g];
+            bx = F.bx[g], by = F.by[g];
+            dep = F.depth[g];
+            hcx = F.hcx[g], hcy = F.hcy[g];
+            keep = keep_of(bx, by);
+        }
+        int total;
+        const int off = n_out + block_excl_scan(keep ? 1 : 0, scan, &total);
+        if (keep && off != g) {   // off <= g; a feature that stays where it is needs no store
+            F.x[off] = x, F.y[off] = y, F.resp[off] = r;
+            F.bx[off] = bx, F.by[off] = by;
+            F.depth[off] = dep;
+            F.hcx[off] = hcx, F.hcy[off] = hcy;
+        }
+        n_out += total;
+    }
+    if (tid == 0) *F.n = n_out;
+    *n_before = n_in;
+    return n_out;
+}
+
+// the sample of a depth plane at element i: the value itself, or -- DEPTH_U16 -- one 16-bit load, an exact conversion and ONE rounded fp32 multiply: what a
+// caller's own `(float)raw * scale` gives, so a 16-bit frame tracks exactly like its fp32 conversion; raw 0 ("no depth") is 0.0f
+__device__ __forceinline__ float depth_sample(const float *img, int fmt, float scale, size_t i) {
+    return (fmt == DEPTH_U16) ? __fmul_rn((float)reinterpret_cast<const uint16_t *>(img)[i], scale) : img[i];
+}
+
 // A sequence's descriptor is IMMUTABLE: the host writes it at creation (create_context) and nobody writes it afterwards -- every kernel takes it const.  It reaches
 // the kernels either BY VALUE (single sequence: its fields are kernel arguments, fetched with the kernel's own argument load) or as an element of the device array
 // (lock-step batch: one more dependent memory hop at every kernel head).  Whatever changes from frame to frame lies BEHIND its pointers (Ctl, FeatCtl -- the

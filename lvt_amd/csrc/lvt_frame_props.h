@@ -5,7 +5,7 @@
 // THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
 // was, lvt_amd_last_error says why); it needs a quiet handle (no frame in flight); an lvt_create handle is decided under its record's lock; a property is
 // configuration, not state (reset and snapshots leave it alone); and a context without the property launches what it always did.
-// Here: the one path every such call takes (frames_in_flight, with_auto_handle, set_property), the one packer of the by-value descriptor tables, the
+// Here: the one path every such call takes (frames_in_flight, with_auto_handle, set_property), the one packer of the by-value descriptor tables and the one frame of the two filters behind the gather, the
 // setters and getters, and the launches the properties add to the head of a frame's feature stage (enqueue_frame calls them in this file's order).
 #pragma once
 
@@ -104,6 +104,35 @@ struct TablePacker {
     do {                                                                    \
         if (first) LAUNCH(slot, c->stream_f, kern, grid, dim3(256), 0, tab); \
         else hipLaunchKernelGGL(kern, grid, dim3(256), 0, c->stream_f, tab); \
+    } while (0)
+
+// ---- one frame for the filters behind the gather (k_depth_guard, k_mask_features) ---------------------------------------------------------------------------
+// EVERY sequence of the step takes a slot (slot k of a launch is sequence z0 + k): fill(s, slot) writes sequence s's record and says whether the filter is on
+// for it in this step.  The slot is cleared first -- the packer's table is zeroed once, at its construction, and after a flush slot k still holds the record of
+// the sequence CAP places before --, so a sequence that is off leaves at the kernel's top.  A table none of whose sequences is on is not launched; the first
+// one launched is the step's timed one: launch(tab, n, z0, timed_first).  Returns whether anything was launched (the step's ring flag).
+template <typename Table, typename Desc, int CAP, typename Fill, typename Launch>
+static bool filter_gathered(Desc (Table::*slots)[CAP], int Bz, Fill fill, Launch launch) {
+    int z0 = 0;
+    bool any = false, timed = false;
+    TablePacker pk(slots, [&](const Table &tab, int n, bool) {
+        if (any) launch(tab, n, z0, !timed);
+        timed = timed || any;
+        z0 += n, any = false;
+    });
+    for (int s = 0; s < Bz; s++) {
+        Desc &d = *pk.add(1);
+        d = Desc{};
+        any = fill(s, d) || any;
+    }
+    pk.flush();
+    return timed;
+}
+// a filter's launch on the feature stream, a workgroup of 1024 threads per grid cell: timed by `slot` when it is the step's first
+#define LAUNCH_FILTER(first, slot, kern, grid, tab, z0)                                              \
+    do {                                                                                             \
+        if (first) LAUNCH(slot, c->stream_f, kern, grid, dim3(1024), 0, c->d_seqs, tab, par, z0);    \
+        else hipLaunchKernelGGL(kern, grid, dim3(1024), 0, c->stream_f, c->d_seqs, tab, par, z0);    \
     } while (0)
 
 // ---- colour frames: a pixel format per handle / per sequence of a batch (Context::pixfmt) ------------------------------------------------------------
@@ -394,32 +423,21 @@ static std::string depth_guard_check(const lvt_amd_depth_guard &g) {
     if (!(std::isfinite(g.tol_rel) && g.tol_rel >= 0.f)) return "a depth guard whose tol_rel is not finite and >= 0";
     return "";
 }
-// Every sequence of the step, guarded or not, takes a slot of the table (slot k of a launch is sequence z0 + k; a sequence without a guard, or without a frame
-// in this step, has radius 0 and leaves at the kernel's top); a table none of whose sequences has a guard is not launched.  The launch stands directly behind
-// k_gather and ahead of k_mask_features and k_brief / k_brief_img, in both orderings.  The depth plane is the one FeatCtl::in names -- k_gather has just read
-// it on this stream, so whatever made it complete for k_gather (the wait for ev_depth, k_depth_register) holds for the guard --, and the Feat arrays are
-// written by k_gather just ahead and read just behind, on this stream: stream order alone covers the hand-over, no gate.
+// A sequence without a guard, or without a frame in this step, has radius 0 (filter_gathered).  The launch stands directly behind k_gather and ahead of
+// k_mask_features and k_brief / k_brief_img, in both orderings.  The depth plane is the one FeatCtl::in names -- k_gather has just read it on this stream, so
+// whatever made it complete for k_gather (the wait for ev_depth, k_depth_register) holds for the guard --, and the Feat arrays are written by k_gather just
+// ahead and read just behind, on this stream: stream order alone covers the hand-over, no gate.
 static void guard_features(Context *c, int slot, int par, int Bz) {
     const FrameArgs *fw = &frame_args(c, slot);
-    int z0 = 0;
-    bool any = false, timed = false;
-    TablePacker pk(&GuardTable::s, [&](const GuardTable &tab, int n, bool) {
-        if (any && !timed) LAUNCH(27, c->stream_f, k_depth_guard, dim3(1, 1, n), dim3(1024), 0, c->d_seqs, tab, par, z0);
-        else if (any) hipLaunchKernelGGL(k_depth_guard, dim3(1, 1, n), dim3(1024), 0, c->stream_f, c->d_seqs, tab, par, z0);
-        timed = timed || any;
-        z0 += n, any = false;
-    });
-    for (int s = 0; s < Bz; s++) {
-        GuardSeq &G = *pk.add(1);
-        // EVERY field of EVERY slot is written: the packer's table is zeroed once, at its construction, and after a flush slot k still holds the record of
-        // the sequence GUARD_PACK places before this one
-        const bool on = c->has_guard(s) && !fw[s].absent;
-        G = on ? GuardSeq{c->depth_guard[(size_t)s].radius, c->depth_guard[(size_t)s].min_support, c->depth_guard[(size_t)s].tol_abs, c->depth_guard[(size_t)s].tol_rel}
-               : GuardSeq{};
-        any = any || on;
-    }
-    pk.flush();
-    c->ring_guarded[slot] = timed;
+    c->ring_guarded[slot] = filter_gathered(
+        &GuardTable::s, Bz,
+        [&](int s, GuardSeq &G) {
+            if (!c->has_guard(s) || fw[s].absent) return false;
+            const lvt_amd_depth_guard &g = c->depth_guard[(size_t)s];
+            G = GuardSeq{g.radius, g.min_support, g.tol_abs, g.tol_rel};
+            return true;
+        },
+        [&](const GuardTable &tab, int n, int z0, bool first) { LAUNCH_FILTER(first, 27, k_depth_guard, dim3(1, 1, n), tab, z0); });
 }
 static int set_depth_guard(lvt_handle h, int seq, bool batch_call, const lvt_amd_depth_guard *cfg) {
     static const PropertyCall call = {"lvt_amd_set_depth_guard", 2,
@@ -442,32 +460,22 @@ static int set_depth_guard(lvt_handle h, int seq, bool batch_call, const lvt_amd
 }
 
 // ---- feature masks: u8 planes per handle / per sequence of a batch, one per eye (Context::d_mask, k_mask.hip) -------------------------------------------
-// Every sequence of the step, masked or not, takes a slot of the table (slot k of a launch is sequence z0 + k; an eye without a mask, and every eye of a
-// sequence without one, is a NULL pointer and leaves at the kernel's top); a table none of whose sequences has a mask is not launched.  The launch stands
+// An eye without a mask, and every eye of a sequence without one or without a frame in this step, is a NULL pointer (filter_gathered).  The launch stands
 // directly behind k_gather and ahead of k_brief / k_brief_img, in both orderings.  The planes are written only by a set on a quiet handle, whose copy has
 // completed before the set returns; the Feat arrays are written by k_gather just ahead and read by k_brief just behind, on this stream: stream order alone
 // covers the hand-over, no gate.
 static void mask_features(Context *c, int slot, int par, int Bz) {
     const FrameArgs *fw = &frame_args(c, slot);
-    int z0 = 0;
-    bool any = false, timed = false;
-    TablePacker pk(&MaskTable::s, [&](const MaskTable &tab, int n, bool) {
-        if (any && !timed) LAUNCH(26, c->stream_f, k_mask_features, dim3(1, 2, n), dim3(1024), 0, c->d_seqs, tab, par, z0);
-        else if (any) hipLaunchKernelGGL(k_mask_features, dim3(1, 2, n), dim3(1024), 0, c->stream_f, c->d_seqs, tab, par, z0);
-        timed = timed || any;
-        z0 += n, any = false;
-    });
-    for (int s = 0; s < Bz; s++) {
-        MaskSeq &M = *pk.add(1);
-        for (int e = 0; e < 2; e++) {
-            const bool on = c->has_mask(s, e) && !fw[s].absent;
-            M.mask[e] = on ? c->d_mask[(size_t)s * 2 + e] : nullptr;
-            M.pitch[e] = c->h_seqs[s].plane_pitch;
-            any = any || on;
-        }
-    }
-    pk.flush();
-    c->ring_masked[slot] = timed;
+    c->ring_masked[slot] = filter_gathered(
+        &MaskTable::s, Bz,
+        [&](int s, MaskSeq &M) {
+            for (int e = 0; e < 2; e++) {
+                M.mask[e] = c->has_mask(s, e) && !fw[s].absent ? c->d_mask[(size_t)s * 2 + e] : nullptr;
+                M.pitch[e] = c->h_seqs[s].plane_pitch;
+            }
+            return M.mask[0] || M.mask[1];
+        },
+        [&](const MaskTable &tab, int n, int z0, bool first) { LAUNCH_FILTER(first, 26, k_mask_features, dim3(1, 2, n), tab, z0); });
 }
 // left / right: tightly packed host planes (device == false: the pitch is the width) or planes in HBM at any address and the given pitch; NULL: that eye has no
 // mask; both NULL: the sequence has none
@@ -525,6 +533,78 @@ static int enable_pose_info(lvt_handle h, int enable) {
         return 0;
     });
 }
+
+// ---- what the properties' getters and the two filters' stage entries share -----------------------------------------------------------------------------
+// a property's record of sequence seq: 1 with *out (may be NULL) where it has one, 0 where it has none (a seat never has one), -1: no such handle or sequence
+template <typename T>
+static int get_seq_record(lvt_handle h, int seq, bool (Context::*has)(int) const, std::vector<T> Context::*vec, T *out) {
+    h = resolve_handle(h, false);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    const Context *c = static_cast<const Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    if (!(c->*has)(seq)) return 0;
+    if (out) *out = (c->*vec)[(size_t)seq];
+    return 1;
+}
+// a filter's stats getter: out[0 .. width) zeroed, then 1 with pick(c, fc) on the FeatCtl of the frame lvt_amd_get_counts answers for, 0 where there is nothing
+// to report -- a seat, no frame yet, a sequence the filter is not set for (has), a step the filter did not run in under the present records (ring is per
+// STEP) or one this sequence sat out: it went through no launch in it, its FeatCtl holds an older frame's words --, -1 otherwise
+template <typename Has, typename Pick>
+static int get_filter_stats(lvt_handle h, int seq, int *out, int width, Has has, bool (Context::*ring)[RING], Pick pick) {
+    h = resolve_handle(h);
+    if (out) std::fill_n(out, width, 0);
+    if (is_slot(h)) return seq == 0 ? 0 : -1;
+    if (!is_ctx(h) || !out) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B) return -1;
+    DeviceGuard guard(c);
+    try {
+        drain(c);
+        if (c->done == 0 || !has(c, seq) || !(c->*ring)[c->last_slot] || frame_args(c, c->last_slot, seq).absent) return 0;
+        FeatCtl fc;
+        d2h(c, &fc, c->h_seqs[seq].fb[c->last_par].fc, 1);
+        pick(c, fc);
+        return 1;
+    } catch (...) {
+    }
+    return -1;
+}
+// One filter's stage entry, the part both have: the caller's n features in a host-built Seq (sequence 0, parity 0, the left eye) whose eight arrays, count and
+// FeatCtl live in the call's StageScratch.  The entry fills seq().prm and featctl().in, asks upload() for the device Seq, launches, and takes fetch()'s answer.
+struct StageFeatures {
+    static constexpr float *Feat::*F32[6] = {&Feat::x, &Feat::y, &Feat::resp, &Feat::bx, &Feat::by, &Feat::depth};
+    static constexpr int16_t *Feat::*I16[2] = {&Feat::hcx, &Feat::hcy};
+    StageScratch S;
+    Seq hs;
+    FeatCtl fc;
+    float *f[6];    // the caller's arrays, in F32's order ...
+    int16_t *h[2];  // ... and in I16's
+    size_t nn;
+    StageFeatures(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth, int16_t *hcx, int16_t *hcy) : f{x, y, resp, bx, by, depth}, h{hcx, hcy}, nn((size_t)n) {
+        std::memset(&hs, 0, sizeof(hs)), std::memset(&fc, 0, sizeof(fc));
+        for (int k = 0; k < 6; k++) feat().*F32[k] = S.buf<float>(nn, f[k]);
+        for (int k = 0; k < 2; k++) feat().*I16[k] = S.buf<int16_t>(nn, h[k]);
+        feat().n = S.buf<int>(1, &n);
+    }
+    Seq &seq() { return hs; }
+    Feat &feat() { return hs.fb[0].feat[0]; }
+    FeatCtl &featctl() { return fc; }
+    // the device Seq, NULL on a HIP failure
+    const Seq *upload() {
+        hs.fb[0].fc = S.buf<FeatCtl>(1, &fc);
+        const Seq *d = S.buf<Seq>(1, &hs);
+        return S.ok() ? d : nullptr;
+    }
+    // behind the launch: the new count with every array back whole -- the elements behind the count hold what the kernel left there --, -1 on a HIP failure
+    int fetch() {
+        int n_new = -1;
+        bool ok = hipGetLastError() == hipSuccess && S.fetch(&n_new, (const int *)feat().n, 1);
+        for (int k = 0; k < 6; k++) ok = ok && S.fetch(f[k], (const float *)(feat().*F32[k]), nn);
+        for (int k = 0; k < 2; k++) ok = ok && S.fetch(h[k], (const int16_t *)(feat().*I16[k]), nn);
+        return ok ? n_new : -1;
+    }
+};
 }  // namespace lvt
 
 // ---- the properties' C-ABI ----------------------------------------------------------------------------------------------------------------------------
@@ -544,16 +624,7 @@ LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
 
 LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam) { return set_depth_camera(h, 0, false, cam); }
 LVT_API int lvt_amd_batch_set_depth_camera(lvt_handle h, int seq, const lvt_amd_depth_camera *cam) { return set_depth_camera(h, seq, true, cam); }
-LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out) {
-    h = resolve_handle(h, false);
-    if (is_slot(h)) return seq == 0 ? 0 : -1;
-    if (!is_ctx(h)) return -1;
-    const Context *c = static_cast<const Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    if (!c->has_depth_cam(seq)) return 0;
-    if (out) *out = c->depth_cam[(size_t)seq];
-    return 1;
-}
+LVT_API int lvt_amd_get_depth_camera(lvt_handle h, int seq, lvt_amd_depth_camera *out) { return get_seq_record(h, seq, &Context::has_depth_cam, &Context::depth_cam, out); }
 // the stage alone on caller data: clear, then scatter, on the caller's stream
 LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const lvt_amd_params *colour, const void *d_depth, int depth_pitch_bytes,
                                           int depth_format, float depth_scale, void *d_out, int out_pitch_bytes, void *hip_stream) {
@@ -577,16 +648,7 @@ LVT_API int lvt_amd_register_depth_device(const lvt_amd_depth_camera *cam, const
 
 LVT_API int lvt_amd_set_equalisation(lvt_handle h, const lvt_amd_equalisation *cfg) { return set_equalisation(h, 0, false, cfg); }
 LVT_API int lvt_amd_batch_set_equalisation(lvt_handle h, int seq, const lvt_amd_equalisation *cfg) { return set_equalisation(h, seq, true, cfg); }
-LVT_API int lvt_amd_get_equalisation(lvt_handle h, int seq, lvt_amd_equalisation *out) {
-    h = resolve_handle(h, false);
-    if (is_slot(h)) return seq == 0 ? 0 : -1;
-    if (!is_ctx(h)) return -1;
-    const Context *c = static_cast<const Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    if (!c->has_equal(seq)) return 0;
-    if (out) *out = c->equal[(size_t)seq];
-    return 1;
-}
+LVT_API int lvt_amd_get_equalisation(lvt_handle h, int seq, lvt_amd_equalisation *out) { return get_seq_record(h, seq, &Context::has_equal, &Context::equal, out); }
 // host only: steps 1 and 2 of the definition
 LVT_API int lvt_amd_equalisation_plan(const lvt_amd_equalisation *cfg, int w, int h, int out[6], float *lut_scale) {
     if (!cfg || !out || w < 1 || w > 8192 || h < 1 || h > 8192 || !equalisation_check(*cfg, w, h).empty()) return -1;
@@ -616,36 +678,11 @@ LVT_API void lvt_amd_depth_guard_default(lvt_amd_depth_guard *out) {
 }
 LVT_API int lvt_amd_set_depth_guard(lvt_handle h, const lvt_amd_depth_guard *cfg) { return set_depth_guard(h, 0, false, cfg); }
 LVT_API int lvt_amd_batch_set_depth_guard(lvt_handle h, int seq, const lvt_amd_depth_guard *cfg) { return set_depth_guard(h, seq, true, cfg); }
-LVT_API int lvt_amd_get_depth_guard(lvt_handle h, int seq, lvt_amd_depth_guard *out) {
-    h = resolve_handle(h, false);
-    if (is_slot(h)) return seq == 0 ? 0 : -1;
-    if (!is_ctx(h)) return -1;
-    const Context *c = static_cast<const Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    if (!c->has_guard(seq)) return 0;
-    if (out) *out = c->depth_guard[(size_t)seq];
-    return 1;
-}
+LVT_API int lvt_amd_get_depth_guard(lvt_handle h, int seq, lvt_amd_depth_guard *out) { return get_seq_record(h, seq, &Context::has_guard, &Context::depth_guard, out); }
 // out: {kept, dropped} of the frame lvt_amd_get_counts answers for; 0 for a sequence of a batch that sat the last collected step out
 LVT_API int lvt_amd_get_depth_guard_stats(lvt_handle h, int seq, int out[2]) {
-    h = resolve_handle(h);
-    if (out) out[0] = out[1] = 0;
-    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has a guard)
-    if (!is_ctx(h) || !out) return -1;
-    Context *c = static_cast<Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    DeviceGuard guard(c);
-    try {
-        drain(c);
-        if (c->done == 0 || !c->has_guard(seq) || !c->ring_guarded[c->last_slot]) return 0;
-        if (frame_args(c, c->last_slot, seq).absent) return 0;  // (ring_guarded is per step: a sequence that sat the step out went through no launch in it)
-        FeatCtl fc;
-        d2h(c, &fc, c->h_seqs[seq].fb[c->last_par].fc, 1);
-        out[0] = fc.guard_kept, out[1] = fc.guard_dropped;
-        return 1;
-    } catch (...) {
-    }
-    return -1;
+    return get_filter_stats(h, seq, out, 2, [](const Context *c, int s) { return c->has_guard(s); }, &Context::ring_guarded,
+                            [&](const Context *, const FeatCtl &fc) { out[0] = fc.guard_kept, out[1] = fc.guard_dropped; });
 }
 // the stage alone on caller data (host pointers): the n features' eight arrays are compacted IN PLACE under the rule of "DEPTH GUARD" against a width x height
 // depth plane of `pitch_elems` elements per row, and every array comes back whole -- the elements behind the new count hold what the kernel left there.
@@ -661,33 +698,20 @@ LVT_API int lvt_amd_depth_guard_features(int n, float *x, float *y, float *resp,
     if (depth_format == DEPTH_U16 && !(std::isfinite(depth_scale) && depth_scale > 0.f)) return refuse_call(who, "a 16-bit plane whose depth_scale is not finite and > 0 (nothing was changed)");
     const std::string why = depth_guard_check(*cfg);
     if (!why.empty()) return refuse_call(who, why + " (nothing was changed)");
-    const size_t nn = (size_t)n, esz = depth_format == DEPTH_U16 ? 2 : 4;
-    StageScratch S;
-    Seq hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.prm.W = width, hs.prm.H = height, hs.prm.sensor = 2, hs.prm.near_plane = near_plane, hs.prm.far_plane = far_plane;
-    Feat &F = hs.fb[0].feat[0];
-    F.x = S.buf<float>(nn, x), F.y = S.buf<float>(nn, y), F.resp = S.buf<float>(nn, resp);
-    F.bx = S.buf<float>(nn, bx), F.by = S.buf<float>(nn, by), F.depth = S.buf<float>(nn, depth_of);
-    F.hcx = S.buf<int16_t>(nn, hcx), F.hcy = S.buf<int16_t>(nn, hcy);
-    F.n = S.buf<int>(1, &n);
-    FeatCtl fc;
-    std::memset(&fc, 0, sizeof(fc));
-    fc.in.depth_img = reinterpret_cast<const float *>(S.buf<uint8_t>((size_t)pitch_elems * height * esz, static_cast<const uint8_t *>(depth)));
-    fc.in.depth_pitch = pitch_elems, fc.in.depth_format = depth_format, fc.in.depth_scale = depth_format == DEPTH_U16 ? depth_scale : 0.f;
-    hs.fb[0].fc = S.buf<FeatCtl>(1, &fc);
+    StageFeatures T(n, x, y, resp, bx, by, depth_of, hcx, hcy);
+    Params &q = T.seq().prm;
+    q.W = width, q.H = height, q.sensor = 2, q.near_plane = near_plane, q.far_plane = far_plane;
+    FrameIn &in = T.featctl().in;
+    in.depth_img = reinterpret_cast<const float *>(T.S.buf<uint8_t>((size_t)pitch_elems * height * (depth_format == DEPTH_U16 ? 2 : 4), static_cast<const uint8_t *>(depth)));
+    in.depth_pitch = pitch_elems, in.depth_format = depth_format, in.depth_scale = depth_format == DEPTH_U16 ? depth_scale : 0.f;
     GuardTable tab;
     std::memset(&tab, 0, sizeof(tab));
     tab.s[0] = GuardSeq{cfg->radius, cfg->min_support, cfg->tol_abs, cfg->tol_rel};
-    const Seq *d_seq = S.buf<Seq>(1, &hs);
-    if (!S.ok()) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    const Seq *d_seq = T.upload();
+    if (!d_seq) return refuse_call(who, hipGetErrorString(hipGetLastError()));
     hipLaunchKernelGGL(k_depth_guard, dim3(1, 1, 1), dim3(1024), 0, 0, d_seq, tab, 0, 0);
-    int n_new = -1;
-    if (hipGetLastError() == hipSuccess && S.fetch(&n_new, (const int *)F.n, 1) && S.fetch(x, (const float *)F.x, nn) && S.fetch(y, (const float *)F.y, nn) &&
-        S.fetch(resp, (const float *)F.resp, nn) && S.fetch(bx, (const float *)F.bx, nn) && S.fetch(by, (const float *)F.by, nn) &&
-        S.fetch(depth_of, (const float *)F.depth, nn) && S.fetch(hcx, (const int16_t *)F.hcx, nn) && S.fetch(hcy, (const int16_t *)F.hcy, nn))
-        return n_new;
-    return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    const int n_new = T.fetch();
+    return n_new >= 0 ? n_new : refuse_call(who, hipGetErrorString(hipGetLastError()));
 }
 
 LVT_API int lvt_amd_set_mask(lvt_handle h, const void *left, const void *right) { return set_mask(h, 0, false, false, left, 0, right, 0); }
@@ -698,26 +722,14 @@ LVT_API int lvt_amd_set_mask_device(lvt_handle h, const void *d_left, int pitch_
 LVT_API int lvt_amd_batch_set_mask_device(lvt_handle h, int seq, const void *d_left, int pitch_left, const void *d_right, int pitch_right) {
     return set_mask(h, seq, true, true, d_left, pitch_left, d_right, pitch_right);
 }
-// out: {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for; an eye without a mask reports 0, 0
+// out: {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for; an eye without a mask reports 0, 0; 0 for a sequence
+// of a batch that sat the last collected step out
 LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]) {
-    h = resolve_handle(h);
-    if (out) out[0] = out[1] = out[2] = out[3] = 0;
-    if (is_slot(h)) return seq == 0 ? 0 : -1;  // (a seat never has a mask)
-    if (!is_ctx(h) || !out) return -1;
-    Context *c = static_cast<Context *>(h);
-    if (seq < 0 || seq >= c->B) return -1;
-    DeviceGuard guard(c);
-    try {
-        drain(c);
-        if (c->done == 0 || !(c->has_mask(seq, 0) || c->has_mask(seq, 1)) || !c->ring_masked[c->last_slot]) return 0;
-        FeatCtl fc;
-        d2h(c, &fc, c->h_seqs[seq].fb[c->last_par].fc, 1);
-        for (int e = 0; e < 2; e++)
-            if (c->has_mask(seq, e)) out[2 * e] = fc.mask_kept[e], out[2 * e + 1] = fc.mask_dropped[e];
-        return 1;
-    } catch (...) {
-    }
-    return -1;
+    return get_filter_stats(h, seq, out, 4, [](const Context *c, int s) { return c->has_mask(s, 0) || c->has_mask(s, 1); }, &Context::ring_masked,
+                            [&](const Context *c, const FeatCtl &fc) {
+                                for (int e = 0; e < 2; e++)
+                                    if (c->has_mask(seq, e)) out[2 * e] = fc.mask_kept[e], out[2 * e + 1] = fc.mask_dropped[e];
+                            });
 }
 // the stage alone on caller data (host pointers): the n features' eight arrays are compacted IN PLACE under the rule of "FEATURE MASKS" against a width x height
 // mask of `pitch` bytes per row, and every array comes back whole -- the elements behind the new count hold what the kernel left there.  Returns the new
@@ -728,29 +740,17 @@ LVT_API int lvt_amd_mask_features(int n, float *x, float *y, float *resp, float 
     if (n < 0 || n > NF_MAX || !mask || width < 1 || width > 8192 || height < 1 || height > 8192 || pitch < width ||
         (n > 0 && (!x || !y || !resp || !bx || !by || !depth || !hcx || !hcy)))
         return refuse_call(who, "a NULL argument, n outside 0 ... 4096, a size outside 1 ... 8192 or a pitch smaller than the width (nothing was changed)");
-    const size_t nn = (size_t)n;
-    StageScratch S;
-    Seq hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.prm.W = width, hs.prm.H = height, hs.prm.sensor = 1;
-    Feat &F = hs.fb[0].feat[0];
-    F.x = S.buf<float>(nn, x), F.y = S.buf<float>(nn, y), F.resp = S.buf<float>(nn, resp);
-    F.bx = S.buf<float>(nn, bx), F.by = S.buf<float>(nn, by), F.depth = S.buf<float>(nn, depth);
-    F.hcx = S.buf<int16_t>(nn, hcx), F.hcy = S.buf<int16_t>(nn, hcy);
-    F.n = S.buf<int>(1, &n);
-    hs.fb[0].fc = S.buf<FeatCtl>(1);
+    StageFeatures T(n, x, y, resp, bx, by, depth, hcx, hcy);
+    Params &q = T.seq().prm;
+    q.W = width, q.H = height, q.sensor = 1;
     MaskTable tab;
     std::memset(&tab, 0, sizeof(tab));
-    tab.s[0].mask[0] = S.buf<uint8_t>((size_t)pitch * height, mask), tab.s[0].pitch[0] = pitch;
-    const Seq *d_seq = S.buf<Seq>(1, &hs);
-    if (!S.ok()) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    tab.s[0].mask[0] = T.S.buf<uint8_t>((size_t)pitch * height, mask), tab.s[0].pitch[0] = pitch;
+    const Seq *d_seq = T.upload();
+    if (!d_seq) return refuse_call(who, hipGetErrorString(hipGetLastError()));
     hipLaunchKernelGGL(k_mask_features, dim3(1, 1, 1), dim3(1024), 0, 0, d_seq, tab, 0, 0);
-    int n_new = -1;
-    if (hipGetLastError() == hipSuccess && S.fetch(&n_new, (const int *)F.n, 1) && S.fetch(x, (const float *)F.x, nn) && S.fetch(y, (const float *)F.y, nn) &&
-        S.fetch(resp, (const float *)F.resp, nn) && S.fetch(bx, (const float *)F.bx, nn) && S.fetch(by, (const float *)F.by, nn) &&
-        S.fetch(depth, (const float *)F.depth, nn) && S.fetch(hcx, (const int16_t *)F.hcx, nn) && S.fetch(hcy, (const int16_t *)F.hcy, nn))
-        return n_new;
-    return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    const int n_new = T.fetch();
+    return n_new >= 0 ? n_new : refuse_call(who, hipGetErrorString(hipGetLastError()));
 }
 
 LVT_API int lvt_amd_enable_pose_info(lvt_handle h, int enable) { return enable_pose_info(h, enable); }

@@ -1,7 +1,7 @@
 // lvt_stage_entries.h -- the calls that run ONE stage alone on caller data (included by lvt_host.hip): the pose solver, the motion model, the batched Hamming
 // matcher, the pose-uncertainty record and the stages of the relocalisation.  Every differential test goes through them.  (lvt_amd_equalise_device, the
 // CLAHE stage alone, stays beside clahe_img in lvt_frame_props.h and uses the same helpers; so do lvt_amd_mask_features and lvt_amd_depth_guard_features, the
-// two filters behind k_gather, beside their setters there.)
+// two filters behind k_gather, beside their setters there: what the two share -- the features into a host-built Seq, the upload, the fetch -- is StageFeatures.)
 //
 // WHAT they share: a call has no handle, so a refusal goes to the calling thread (refuse_call, lvt_amd_last_error(NULL)); its parameters come through
 // stage_params; all of its device memory comes from one StageScratch, which frees it when the call returns, whichever way it returns; a call that reports a time

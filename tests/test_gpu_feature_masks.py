@@ -173,6 +173,7 @@ def test_stage_entry_equals_numpy_bit_for_bit(hip_lib, pattern, pitch):
         for name, a, g in zip(("x", "y", "resp", "bx", "by", "depth", "hcx", "hcy"), arrays, got[1:]):
             bits = np.uint32 if a.dtype == np.float32 else np.int16
             assert np.array_equal(g[:got[0]].view(bits), a[want].view(bits)), (pattern, n, name)
+            assert np.array_equal(g[got[0]:].view(bits), a[got[0]:].view(bits)), (pattern, n, name, "the tail was touched: the compaction is in place")
 
 
 def test_stage_entry_refusals(hip_lib):
@@ -398,7 +399,9 @@ def solo_records(hip_lib, q, left, right, dev, frames):
 def test_mixed_batch_of_masked_plain_and_absent(hip_lib, oracle_lib):
     """three sequences in one chain, three steps in flight: 0 = 621 x 187 under the bonnet (left) and the checkerboard (right); 1 = 613 x 185, no mask; 2 =
     621 x 187 under the ellipse (left eye only), sitting out steps 2 and 4.  The masked sequences against the oracle chains, state and pose of every step and
-    the counters behind the last; every sequence's poses, states and counters are those of a solo handle with the same masks, bit for bit"""
+    the counters behind the last; every sequence's poses, states and counters are those of a solo handle with the same masks, bit for bit.  Then a seventh
+    step that sequences 1 and 2 sit out: the absent masked sequence reports no statistics (the step's launch did not run for it: its FeatCtl holds an older
+    frame's counts), the present one the solo handle's"""
     q = stereo()
     bw, bprm, _ = make_case("kitti", 32, size=(613, 185))
     bframes = [tuple(np.ascontiguousarray(a) for a in bw.render_stereo(i)) for i in range(6)]
@@ -406,7 +409,7 @@ def test_mixed_batch_of_masked_plain_and_absent(hip_lib, oracle_lib):
     batch = hip_lib.LvtBatch([q.prm, bprm, q.prm])
     assert batch.set_mask(0, q.masks["bonnet"], q.masks["checkerboard"]) == 0 and batch.set_mask(2, q.masks["ellipse"], None) == 0, batch.last_error()
     assert batch.mask_stats(1) is None
-    nsteps, which, f2 = 6, [], 0
+    nsteps, which, f2, after = 6, [], 0, {}
     for k in range(6):
         which.append([k, k, None if k in (2, 4) else f2])
         f2 += 0 if k in (2, 4) else 1
@@ -429,7 +432,8 @@ def test_mixed_batch_of_masked_plain_and_absent(hip_lib, oracle_lib):
     for s, (left, right) in ((0, ("bonnet", "checkerboard")), (2, ("ellipse", None))):
         steps = [k for k in range(nsteps) if which[k][s] is not None]
         ref, _, _ = q.chain(left, right, len(steps))
-        solo = solo_records(hip_lib, q, left, right, dev, range(len(steps)))
+        solo = solo_records(hip_lib, q, left, right, dev, range(len(steps) + 1))   # (one frame more: the seventh step)
+        solo, after[s] = solo[:-1], solo[-1]
         for j, k in enumerate(steps):
             R, t, st = got[k]
             assert st[s] == ref[j][2] == 2, f"sequence {s} step {k}: state {st[s]}"
@@ -445,6 +449,10 @@ def test_mixed_batch_of_masked_plain_and_absent(hip_lib, oracle_lib):
         assert orc.status == 2 == got[k][2][1]
         close_to(got[k][0][1], got[k][1][1], (np.array(Ro), np.array(to)), f"sequence 1 step {k}")
     counts_equal(batch.counts(1), orc.counts(), "sequence 1 after the last step")
+    assert batch.track_device_async_mixed([ptr(0, 6, 0), None, None], [ptr(0, 6, 1), None, None], [q.H, 185, q.H], [q.W, 613, q.W], [q.pitch, bpitch, q.pitch]) == 0, batch.last_error()
+    batch.wait()
+    assert batch.mask_stats(2) is None, ("a masked sequence that sat the last collected step out reports an older frame's counts", batch.mask_stats(2))
+    assert batch.mask_stats(0) == after[0][4] and sum(batch.mask_stats(0)["dropped"]) > 0, (batch.mask_stats(0), after[0][4])
 
 
 def test_uniform_batch_with_more_masked_sequences_than_one_table_holds(hip_lib, oracle_lib):
