@@ -4,7 +4,7 @@
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/kitti/kitti_example.cpp:49-152 there):
 //     lvt_kitti <sequences_dir> <seq_number> [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--covariance FILE]
-//                [--mask LEFT[,RIGHT]]
+//                [--mask LEFT[,RIGHT]] [--labels DIR --drop L1,L2,... [--dilate R]]
 // reads <sequences_dir>/NN/image_0/%06d.{png,pgm} and image_1/..., the OpenCV-YAML calibration (camera_matrix, baseline)
 // and vo_config.yaml, tracks every frame until the sequence ends or the tracker is LOST, writes NN.txt in the KITTI
 // 3x4 row format with the reference's precision (fixed, 9 digits) and prints the mean per-frame track() time.
@@ -15,6 +15,10 @@
 // unless the status is 1).  Without the option nothing of this runs.
 // --mask LEFT[,RIGHT] (not in the reference): feature masks (lvt_system::set_mask), 8-bit PNG or PGM files of the frames' size, a pixel != 0: key points
 // allowed -- the ego vehicle's bonnet, an overlay.  LEFT alone masks the left eye only.  A file of another size is refused before the first frame.
+// --labels DIR --drop L1,L2,... [--dilate R] (not in the reference): per-frame label masks (lvt_system::set_label_mask / frame_labels).  DIR/%06d.png
+// (or .pgm), an 8-bit image of ANY size -- a segmentation network's output, usually a fraction of the frame's -- holds the left eye's labels of that frame;
+// key points on pixels whose label is among L1,L2,..., widened by R pixels (0 ... 15, default 0), are dropped.  The first file fixes the label size; a frame
+// whose file is missing gets no labels.  The same trajectory format.
 #include "../include/lvt_system.h"
 
 #include "image_io.h"
@@ -69,7 +73,8 @@ int main(int argc, char **argv) {
     char seq_cstr[16];
     std::snprintf(seq_cstr, sizeof seq_cstr, "%02d", std::atoi(argv[2]));
     const std::string seq_str(seq_cstr), dir_prefix = std::string(argv[1]) + "/" + seq_str;
-    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name, mask_names;
+    std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name, mask_names, labels_dir, drop_list;
+    int dilate = 0;
     long max_frames = -1;
     for (int i = 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -79,6 +84,9 @@ int main(int argc, char **argv) {
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
         else if (k == "--covariance") cov_name = argv[i + 1];
         else if (k == "--mask") mask_names = argv[i + 1];
+        else if (k == "--labels") labels_dir = argv[i + 1];
+        else if (k == "--drop") drop_list = argv[i + 1];
+        else if (k == "--dilate") dilate = std::atoi(argv[i + 1]);
     }
     double K[9], baseline = 0;
     if (!read_calib(calib, K, baseline)) {
@@ -142,6 +150,36 @@ int main(int argc, char **argv) {
             return -1;
         }
     }
+    auto label_name = [&](long i) {
+        char name[32];
+        std::snprintf(name, sizeof name, "/%06ld.png", i);
+        return labels_dir + name;
+    };
+    Gray labels;
+    lvt_amd_label_mask label_cfg{};
+    if (!labels_dir.empty()) {
+        if (!load_image(label_name(0), labels, err)) {
+            std::cout << "failed to read the labels " << label_name(0) << " (" << err << ")" << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
+        label_cfg.label_width = labels.w, label_cfg.label_height = labels.h, label_cfg.dilate = dilate;
+        std::stringstream ds(drop_list);
+        for (std::string item; std::getline(ds, item, ',');) {
+            const int l = std::atoi(item.c_str());
+            if (item.empty() || l < 0 || l > 255) {
+                std::cout << "--drop takes labels 0 ... 255, separated by commas" << std::endl;
+                lvt_system::destroy(vo);
+                return -1;
+            }
+            label_cfg.drop[l] = 1;
+        }
+        if (!vo->set_label_mask(&label_cfg)) {
+            std::cout << "failed to set the label mask: " << vo->last_error() << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
+    }
     // like the reference, the trajectory has one row per frame of the sequence; frames after a LOST keep the default pose
     long frame_count = 0;
     for (;; frame_count++) {
@@ -162,6 +200,12 @@ int main(int argc, char **argv) {
             break;
         }
         std::cout << "Frame number: " << i << "\r" << std::flush;
+        if (!labels_dir.empty() && (i == 0 || load_image(label_name(i), labels, err))) {  // (frame 0's are loaded; a missing file: no labels for the frame)
+            if (labels.w != label_cfg.label_width || labels.h != label_cfg.label_height || !vo->frame_labels(labels.px.data())) {
+                std::cout << "frame " << i << ": labels of another size, or refused: " << vo->last_error() << std::endl;
+                break;
+            }
+        }
         const auto t0 = std::chrono::steady_clock::now();
         const bool queued = vo->track_async(lvt_image_view(left.px.data(), left.h, left.w), lvt_image_view(right.px.data(), right.h, right.w));
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

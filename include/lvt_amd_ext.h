@@ -521,6 +521,67 @@ LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]);
 LVT_API int lvt_amd_mask_features(int n, float *x, float *y, float *resp, float *bx, float *by, float *depth, int16_t *hcx, int16_t *hcy, const uint8_t *mask,
                                   int width, int height, int pitch);
 
+/* LABEL MASKS: a segmentation image travels with each frame.  A feature mask (above) is a property and needs a quiet handle; a segmentation network delivers
+ * a new image every frame, usually at 1/4 or 1/8 of the image's size, as class ids, and is least reliable on object outlines -- where corners sit.  A LABEL MASK
+ * record is the property (how a label image becomes a mask); the label images themselves are attached per frame, WITH FRAMES IN FLIGHT, and the tracker builds
+ * that frame's mask plane itself: upsampling, the class table and the dilation in one launch.  Not offered for pooled and automatic seats.  A handle or
+ * sequence that never sets a record launches exactly what it did.
+ *
+ * DEFINITION (tests/label_mask_util.py restates it in numpy; pure integer arithmetic, the checks hold the tracker to it bit for bit).  The record is
+ *     label_width, label_height  1 ... 8192 each: the size of the label image, independent of the image size (smaller or larger)
+ *     drop[256]                  a byte != 0: label l forbids key points
+ *     dilate                     0 ... 15, in pixels of the detector's grid
+ * For a frame that carries a label image `lab` of that size for an eye, with W, H the sequence's image size and `static` the eye's mask from lvt_amd_set_mask
+ * where it has one:
+ *     lx(x) = (x * label_width) / W        ly(y) = (y * label_height) / H      -- integer division; the products stay below 2^27
+ *     f0(x, y) = drop[lab[ly(y)][lx(x)]] != 0
+ *     f(x, y)  = OR of f0(x', y') over |x' - x| <= dilate, |y' - y| <= dilate, 0 <= x' < W, 0 <= y' < H      -- a square window, clipped, never wrapped
+ *     m(x, y)  = (!f(x, y) && (no static mask || static[y][x] != 0)) ? 255 : 0
+ * m is the plane k_mask_features filters that eye of that frame with, under its unchanged rule (ix = (int)(bx + 0.5f), ...).  Everything FEATURE MASKS states
+ * about ordering holds as it stands: the filter acts after detection, ANMS, the border filter, the depth filter and the guard; the retry is decided on the
+ * unmasked count; external corners are filtered the same way; labels live on the grid the detector reads, the rectified grid where rectifiers are attached.
+ * An eye that got no label image, a frame that got none and a sequence without a record are filtered as before: by the static mask alone, or not at all.
+ *
+ * THE RECORD.  lvt_amd_set_label_mask / lvt_amd_batch_set_label_mask copy the record; NULL unsets it.  Refused under the "Frame properties" contract with the
+ * checks of lvt_amd_set_mask in their order, each with -1, the handle as it was and the sentence in lvt_amd_last_error ending in "(nothing was changed)": a bad
+ * handle (no report); a pooled or automatic seat; the batch call on a solo handle and the solo call on a batch; seq out of range; a record outside the ranges
+ * above (the sentence names the field and its limits); frames in flight.  The record is not state: lvt_amd_reset and snapshots neither hold nor change it.
+ *  - lvt_amd_get_label_mask: 1 = *out written; 0 = the sequence has no record; -1 = bad handle / seq.
+ *
+ * PER FRAME.  lvt_amd_frame_labels_device takes u8 planes in HBM at any address and any pitch >= label_width; lvt_amd_frame_labels takes tightly packed host
+ * buffers (label_width bytes per row).  seq is 0 on a solo handle (the calls have ONE spelling).  Both are accepted with frames in flight.
+ *  - BINDING.  The images belong to the NEXT frame submitted for that sequence after the call, whatever entry point submits it (lvt_track,
+ *    lvt_track_with_external_corners, lvt_amd_track_async, the device and RGB-D entries, the batch calls), and that frame alone consumes them.  The frame is
+ *    named by its number, lvt_amd_get_host_stats' out[0] + 1 at the time of the call: a frame lvt_amd_track_async still holds back has its number already and
+ *    can never take the labels meant for the frame behind it.
+ *  - A second call before the frame replaces the first; both pointers NULL clears a pending attachment; one eye NULL: that eye gets no labels.
+ *    lvt_amd_reset / lvt_amd_batch_reset drop a pending attachment.
+ *  - A batch step consumes every sequence's attachment, also that of a sequence that sits the step out (nothing is built for it).
+ *  - Device planes are read in place on the feature stream: they must stay valid and unchanged until that frame has been collected (the rule of the device
+ *    image entries).  Host buffers are free when the call returns; the call does not wait for the frames in flight -- it copies into a page-locked ring of
+ *    8 slots and makes room first, so that the slot's last user (8 frames ago) has been collected.
+ *  - Refused with -1, the sentence in lvt_amd_last_error ending in "(nothing was attached)", in this order: a bad handle (no report); a pooled or automatic
+ *    seat; seq out of range; a sequence without a record; a pitch below label_width; right-eye labels on an RGB-D handle.
+ *
+ * READ-BACK.  lvt_amd_get_mask_stats also answers for a frame that was filtered through labels (an eye that was filtered neither way reports 0, 0);
+ * lvt_amd_get_plane(h, eye, 8, ...) returns the plane built for the last collected frame (u8, rows x pitch, padding columns zero; 0 bytes where none was
+ * built); lvt_amd_profile_read reports the launch as "k_label_mask", only for a handle with a record.
+ *  - lvt_amd_build_label_mask: the stage alone on caller data (host pointers).  `labels` is label_height rows of label_pitch >= label_width bytes, the static
+ *    mask (or NULL) H rows of static_pitch >= W bytes, `out` H rows of out_pitch bytes (a multiple of 4, >= W) which come back whole -- the padding columns
+ *    zero.  0, or -1 on a refusal (lvt_amd_last_error(NULL)) or a HIP failure. */
+typedef struct lvt_amd_label_mask {
+    int label_width, label_height;
+    uint8_t drop[256];
+    int dilate;
+} lvt_amd_label_mask;
+LVT_API int lvt_amd_set_label_mask(lvt_handle h, const lvt_amd_label_mask *cfg);                    /* 0 / -1 */
+LVT_API int lvt_amd_batch_set_label_mask(lvt_handle h, int seq, const lvt_amd_label_mask *cfg);
+LVT_API int lvt_amd_get_label_mask(lvt_handle h, int seq, lvt_amd_label_mask *out);
+LVT_API int lvt_amd_frame_labels(lvt_handle h, int seq, const void *left, const void *right);      /* 0 / -1 */
+LVT_API int lvt_amd_frame_labels_device(lvt_handle h, int seq, const void *d_left, int pitch_left, const void *d_right, int pitch_right);
+LVT_API int lvt_amd_build_label_mask(const lvt_amd_label_mask *cfg, const uint8_t *labels, int label_pitch, int W, int H, const uint8_t *static_or_NULL,
+                                     int static_pitch, uint8_t *out, int out_pitch);
+
 /* DEPTH GUARD: RGB-D key points whose depth has no support around it are dropped inside the tracker's feature stage.  A key point's depth is ONE pixel of the
  * depth plane, depth[(int)y][(int)x] (the reference does the same), and corners cluster where that sample is worst: on occlusion boundaries, where the corner a
  * foreground edge makes with background texture is no 3-D point; on the flying pixels a time-of-flight or structured-light sensor delivers between foreground and

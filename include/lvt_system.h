@@ -333,6 +333,12 @@ class lvt_system {
      * step and BRIEF).  One eye may be nullptr (no mask for it); both nullptr: no masks again.  The buffers are copied before the call returns.
      * false: refused (last_error() says why), nothing changed. */
     bool set_mask(const unsigned char *left, const unsigned char *right = nullptr) { return lvt_amd_set_mask(m_handle, left, right) == 0; }
+    /* ADDITIVE: label masks (include/lvt_amd_ext.h, LABEL MASKS): the record says how a label image becomes a frame's feature mask (its size, the labels that
+     * forbid key points, a dilation); nullptr: no record again.  frame_labels hands over the tightly packed 8-bit label images (label_width x label_height) of
+     * the NEXT frame given to this system, with frames in flight; the buffers are copied before the call returns.  One eye may be nullptr (no labels for it);
+     * both nullptr clears a pending attachment.  false: refused (last_error() says why), nothing changed / attached. */
+    bool set_label_mask(const lvt_amd_label_mask *cfg) { return lvt_amd_set_label_mask(m_handle, cfg) == 0; }
+    bool frame_labels(const unsigned char *left, const unsigned char *right = nullptr) { return lvt_amd_frame_labels(m_handle, 0, left, right) == 0; }
     /* ADDITIVE: depth guard (include/lvt_amd_ext.h, DEPTH GUARD) of an RGB-D system: from now on every frame loses the key points whose depth sample has fewer than
      * min_support of the (2 * radius + 1)^2 - 1 samples around it valid and within tol_abs + tol_rel * depth of it (one launch directly behind the gather step);
      * lvt_amd_depth_guard_default fills the usual record.  nullptr: no guard again.  false: refused (last_error() says why), nothing changed. */

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
     "lvt_amd_set_mask", "lvt_amd_batch_set_mask", "lvt_amd_set_mask_device", "lvt_amd_batch_set_mask_device", "lvt_amd_get_mask_stats", "lvt_amd_mask_features",
+    "lvt_amd_set_label_mask", "lvt_amd_batch_set_label_mask", "lvt_amd_get_label_mask", "lvt_amd_frame_labels", "lvt_amd_frame_labels_device", "lvt_amd_build_label_mask",
     "lvt_amd_depth_guard_default", "lvt_amd_set_depth_guard", "lvt_amd_batch_set_depth_guard", "lvt_amd_get_depth_guard", "lvt_amd_get_depth_guard_stats", "lvt_amd_depth_guard_features",
     "lvt_amd_relocalise", "lvt_amd_batch_relocalise", "lvt_amd_odometry_set_relocalisation", "lvt_amd_reloc_default_config", "lvt_amd_reloc_slice_length", "lvt_amd_reloc_match_device", "lvt_amd_reloc_solve", "lvt_amd_reloc_correspond",
 ]
@@ -223,6 +224,13 @@ def load_library():
             ("lvt_amd_set_mask", [vp, vp, vp]), ("lvt_amd_batch_set_mask", [vp, C.c_int, vp, vp]), ("lvt_amd_set_mask_device", [vp, vp, C.c_int, vp, C.c_int]),
             ("lvt_amd_batch_set_mask_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int]), ("lvt_amd_get_mask_stats", [vp, C.c_int, vp]),
             ("lvt_amd_mask_features", [C.c_int] + [vp] * 9 + [C.c_int] * 3)):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (   # (label masks: likewise)
+            ("lvt_amd_set_label_mask", [vp, vp]), ("lvt_amd_batch_set_label_mask", [vp, C.c_int, vp]), ("lvt_amd_get_label_mask", [vp, C.c_int, vp]),
+            ("lvt_amd_frame_labels", [vp, C.c_int, vp, vp]), ("lvt_amd_frame_labels_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int]),
+            ("lvt_amd_build_label_mask", [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int])):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
@@ -417,6 +425,79 @@ def mask_features(x, y, resp, bx, by, depth, hcx, hcy, mask, width: int = None, 
     if rc < 0:
         raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_mask_features failed")
     return (rc, *arrays)
+
+
+class LabelMask(C.Structure):
+    """lvt_amd_label_mask: how the label image that travels with a frame becomes that frame's feature mask (include/lvt_amd_ext.h, LABEL MASKS) -- the label
+    image's size (label_width, label_height, 1 ... 8192 each, independent of the image size), the labels that forbid key points (`drop`: an iterable of
+    label values, or 256 flags) and `dilate` (0 ... 15 pixels of the detector's grid)"""
+    _fields_ = [("label_width", C.c_int), ("label_height", C.c_int), ("drop", C.c_uint8 * 256), ("dilate", C.c_int)]
+
+    def __init__(self, label_width=0, label_height=0, drop=(), dilate=0):
+        flags = (C.c_uint8 * 256)()
+        drop = list(drop)
+        if len(drop) == 256:
+            for l, v in enumerate(drop):
+                flags[l] = 1 if v else 0
+        else:
+            for l in drop:
+                flags[int(l)] = 1
+        super().__init__(int(label_width), int(label_height), flags, int(dilate))
+
+    def dropped(self):
+        """the label values that forbid key points"""
+        return [l for l in range(256) if self.drop[l]]
+
+    def __repr__(self):
+        return f"LabelMask(label_width={int(self.label_width)}, label_height={int(self.label_height)}, drop={self.dropped()}, dilate={int(self.dilate)})"
+
+
+def _labels_of(handle, seq, labels):
+    """a label image as lvt_amd_frame_labels takes it: a contiguous (label_height, label_width) uint8 array, or None.  The C-ABI has no size argument for a
+    host image: an array of another shape would be read past its end, so it raises here"""
+    if labels is None:
+        return None
+    a = np.ascontiguousarray(labels, dtype=np.uint8)
+    rec = _record_of("lvt_amd_get_label_mask", LabelMask, handle, seq)
+    if rec is not None and a.shape != (rec.label_height, rec.label_width):
+        raise ValueError(f"a label image of shape {a.shape} under a record of {rec.label_height} x {rec.label_width} labels")
+    return a
+
+
+def _frame_labels(handle, seq, left, right, pitch_left, pitch_right):
+    """numpy arrays (host images), or device addresses with their pitches"""
+    L = load_library()
+    if isinstance(left, (int, np.integer)) or isinstance(right, (int, np.integer)):
+        return L.lvt_amd_frame_labels_device(handle, int(seq), C.c_void_p(int(left) if left else None), int(pitch_left), C.c_void_p(int(right) if right else None),
+                                             int(pitch_right))
+    l, r = _labels_of(handle, seq, left), _labels_of(handle, seq, right)
+    return L.lvt_amd_frame_labels(handle, int(seq), _p(l), _p(r))
+
+
+def build_label_mask(cfg: LabelMask, labels, width: int, height: int, static=None, out_pitch: int = None):
+    """stage entry: k_label_mask alone (include/lvt_amd_ext.h, LABEL MASKS).  labels: a 2-D uint8 array of cfg's size whose row stride is the pitch and whose
+    address is kept modulo 4 on the device (a view keeps both); static: None or a 2-D uint8 array of (height, width), likewise.  Returns the (height,
+    out_pitch) uint8 plane, the padding columns included (out_pitch defaults to the width rounded up to 64).  RuntimeError with the reason when refused."""
+    def view(a, what):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != 2 or a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            raise ValueError(f"{what}: a 2-D uint8 array with contiguous rows")
+        return a
+    labels = view(labels, "labels")
+    if labels.shape != (cfg.label_height, cfg.label_width):
+        raise ValueError(f"labels of shape {labels.shape} under a record of {cfg.label_height} x {cfg.label_width} labels")
+    if static is not None:
+        static = view(static, "static")
+        if static.shape != (height, width):
+            raise ValueError(f"a static mask of shape {static.shape} on an image of {height} x {width} pixels")
+    out_pitch = (int(width) + 63) // 64 * 64 if out_pitch is None else int(out_pitch)
+    out = np.full((int(height), max(out_pitch, 1)), 0xEE, np.uint8)
+    rc = load_library().lvt_amd_build_label_mask(C.byref(cfg), C.c_void_p(labels.ctypes.data), int(labels.strides[0]), int(width), int(height),
+                                                 C.c_void_p(static.ctypes.data) if static is not None else None, int(static.strides[0]) if static is not None else 0,
+                                                 _p(out), out_pitch)
+    if rc != 0:
+        raise RuntimeError((load_library().lvt_amd_last_error(None) or b"").decode() or "lvt_amd_build_label_mask failed")
+    return out
 
 
 class DepthGuard(C.Structure):
@@ -970,6 +1051,23 @@ class LvtSystem:
         last frame went in before the masks were set"""
         return _mask_stats_of(self._h, 0)
 
+    def set_label_mask(self, cfg=None, **kw) -> int:
+        """a LabelMask (or its arguments: label_width=, label_height=, drop=, dilate=): from now on a frame may be handed a label image per eye
+        (frame_labels), which the feature stage turns into that frame's mask in one launch; None: no record again.  0: done; -1: refused (last_error())."""
+        if cfg is None and kw:
+            cfg = LabelMask(**kw)
+        return load_library().lvt_amd_set_label_mask(self._h, C.byref(cfg) if cfg is not None else None)
+
+    def label_mask(self):
+        """the LabelMask that is set, or None"""
+        return _record_of("lvt_amd_get_label_mask", LabelMask, self._h, 0)
+
+    def frame_labels(self, left=None, right=None, pitch_left: int = 0, pitch_right: int = 0) -> int:
+        """the label images of the NEXT frame handed to this system, accepted with frames in flight: (label_height, label_width) uint8 arrays, copied before
+        the call returns, or device addresses (ints) with their pitches in bytes, read in place until that frame has been collected.  One eye may be None (no
+        labels for it); both None clears a pending attachment.  0: done; -1: refused (last_error())."""
+        return _frame_labels(self._h, 0, left, right, pitch_left, pitch_right)
+
     def set_depth_guard(self, cfg=None, **kw) -> int:
         """a DepthGuard (or its arguments: radius=, min_support=, tol_abs=, tol_rel=): every RGB-D frame handed to this system from now on loses the key points
         whose depth sample has too little support around it, one launch directly behind the gather step; None: no guard again.  0: done; -1: refused
@@ -1227,6 +1325,19 @@ class LvtBatch:
 
     def mask_stats(self, seq: int):
         return _mask_stats_of(self._h, seq)
+
+    def set_label_mask(self, seq: int, cfg=None, **kw) -> int:
+        """LvtSystem.set_label_mask for sequence `seq` of the batch"""
+        if cfg is None and kw:
+            cfg = LabelMask(**kw)
+        return load_library().lvt_amd_batch_set_label_mask(self._h, int(seq), C.byref(cfg) if cfg is not None else None)
+
+    def label_mask(self, seq: int):
+        return _record_of("lvt_amd_get_label_mask", LabelMask, self._h, seq)
+
+    def frame_labels(self, seq: int, left=None, right=None, pitch_left: int = 0, pitch_right: int = 0) -> int:
+        """LvtSystem.frame_labels for sequence `seq`: the label images of its frame in the NEXT step, whether or not it takes part in it"""
+        return _frame_labels(self._h, seq, left, right, pitch_left, pitch_right)
 
     def set_depth_guard(self, seq: int, cfg=None, **kw) -> int:
         """LvtSystem.set_depth_guard for sequence `seq` of an RGB-D batch: its key points are guarded from then on, the other sequences' are not"""

@@ -1,6 +1,6 @@
 // lvt_frame_props.h -- the properties a handle, or one sequence of a batch, has besides its parameters (included by lvt_host.hip): rectifiers for raw frames,
 // a pixel format for colour frames, a depth camera for unregistered depth, an equalisation record for dim frames, a depth guard and feature masks behind the
-// gather step, the pose-uncertainty record.
+// gather step, label masks whose images travel with each frame, the pose-uncertainty record.
 //
 // THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
 // was, lvt_amd_last_error says why); it needs a quiet handle (no frame in flight); an lvt_create handle is decided under its record's lock; a property is
@@ -464,13 +464,15 @@ static int set_depth_guard(lvt_handle h, int seq, bool batch_call, const lvt_amd
 // directly behind k_gather and ahead of k_brief / k_brief_img, in both orderings.  The planes are written only by a set on a quiet handle, whose copy has
 // completed before the set returns; the Feat arrays are written by k_gather just ahead and read by k_brief just behind, on this stream: stream order alone
 // covers the hand-over, no gate.
+// An eye the step built a label plane for (build_label_masks, below) is handed THAT plane -- it holds the static mask already --; called where n_mask || n_label.
 static void mask_features(Context *c, int slot, int par, int Bz) {
     const FrameArgs *fw = &frame_args(c, slot);
     c->ring_masked[slot] = filter_gathered(
         &MaskTable::s, Bz,
         [&](int s, MaskSeq &M) {
             for (int e = 0; e < 2; e++) {
-                M.mask[e] = c->has_mask(s, e) && !fw[s].absent ? c->d_mask[(size_t)s * 2 + e] : nullptr;
+                if (c->built_label(slot, s, e)) M.mask[e] = c->d_lmask[((size_t)s * NPAR + par) * 2 + e];
+                else M.mask[e] = c->has_mask(s, e) && !fw[s].absent ? c->d_mask[(size_t)s * 2 + e] : nullptr;
                 M.pitch[e] = c->h_seqs[s].plane_pitch;
             }
             return M.mask[0] || M.mask[1];
@@ -515,6 +517,129 @@ static int set_mask(lvt_handle h, int seq, bool batch_call, bool device, const v
         c->n_mask = 0;
         for (int s = 0; s < c->B; s++) c->n_mask += (c->mask_on[(size_t)s * 2] || c->mask_on[(size_t)s * 2 + 1]) ? 1 : 0;
         return 0;
+    });
+}
+
+// ---- label masks: a record per handle / per sequence of a batch, a label image per eye and FRAME (Context::label, Context::label_ring, k_labelmask.hip) ------
+// "" when the record passes: names the offending field and its limits otherwise
+static std::string label_mask_check(const lvt_amd_label_mask &r) {
+    if (r.label_width < 1 || r.label_width > 8192) return "a label mask with label_width = " + std::to_string(r.label_width) + " (1 ... 8192)";
+    if (r.label_height < 1 || r.label_height > 8192) return "a label mask with label_height = " + std::to_string(r.label_height) + " (1 ... 8192)";
+    if (r.dilate < 0 || r.dilate > LABEL_MAX_DILATE) return "a label mask with dilate = " + std::to_string(r.dilate) + " (0 ... 15)";
+    return "";
+}
+// one image's descriptor: the label image under record r onto a W x H grid, ANDed with the static mask (or NULL), into dst
+static LabelImg label_img(const lvt_amd_label_mask &r, const uint8_t *lab, int lab_pitch, int W, int H, const uint8_t *stat, int stat_pitch, uint8_t *dst, int dst_pitch) {
+    LabelImg I{};
+    I.lab = lab, I.stat = stat, I.dst = dst;
+    I.lab_pitch = lab_pitch, I.lw = r.label_width, I.lh = r.label_height, I.stat_pitch = stat_pitch, I.dst_pitch = dst_pitch, I.W = W, I.H = H, I.dilate = r.dilate;
+    for (int l = 0; l < 256; l++)
+        if (r.drop[l]) I.drop[l >> 5] |= 1u << (l & 31);
+    return I;
+}
+// workgroups of k_label_mask for a plane of dst_pitch x H: tiles of 32 x 32 over the pitch
+static int label_tiles(int dst_pitch, int H) { return ((dst_pitch / 4 + 7) / 8) * ((H + LABEL_TILE - 1) / LABEL_TILE); }
+// Every eye of every sequence that has a record, a frame in this step and an attachment TAGGED with this frame's number (enq + 1), in one launch.  An attachment
+// with another tag stays where it is: it belongs to a later frame (the one behind a held frame), or to a step long gone, and the next call for that slot
+// overwrites it.  The built plane (parity `par`) was read last by k_mask_features of frame enq - NPAR, which was enqueued on this stream earlier; the label source
+// was written by lvt_amd_frame_labels' copy on this stream or belongs to the caller (on a caller's stream: behind the step's ev_caller wait); the static mask is
+// written only on a quiet handle: stream order alone covers the hand-over, no gate.
+static void build_label_masks(Context *c, int slot, int par, int Bz) {
+    const FrameArgs *fw = &frame_args(c, slot);
+    const long long frame = (long long)c->enq + 1;
+    int tiles = 0;
+    TablePacker pk(&LabelTable::im, [&](const LabelTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 28, k_label_mask, dim3(tiles, n), tab);
+        tiles = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        const Context::LabelAttach &A = c->label_ring[(size_t)slot * c->B + s];
+        if (!c->has_label(s) || A.frame != frame || fw[s].absent) continue;
+        const Params &q = c->seq_prm(s);
+        const int dpitch = c->h_seqs[s].plane_pitch;
+        for (int e = 0; e < 2; e++) {
+            if (!A.src[e]) continue;
+            *pk.add(1) = label_img(c->label[(size_t)s], A.src[e], A.pitch[e], q.W, q.H, c->has_mask(s, e) ? c->d_mask[(size_t)s * 2 + e] : nullptr, dpitch,
+                                   c->d_lmask[((size_t)s * NPAR + par) * 2 + e], dpitch);
+            tiles = std::max(tiles, label_tiles(dpitch, q.H));
+            c->label_built[((size_t)slot * c->B + s) * 2 + e] = 1;
+        }
+    }
+    pk.flush();
+}
+static int set_label_mask(lvt_handle h, int seq, bool batch_call, const lvt_amd_label_mask *cfg) {
+    static const PropertyCall call = {"lvt_amd_set_label_mask", 0,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                       "a batch handle takes its label masks per sequence through lvt_amd_batch_set_label_mask (nothing was changed)"},
+                                      "lvt_amd_batch_set_label_mask on a handle that is not a batch (use lvt_amd_set_label_mask)"};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (cfg) {
+            const std::string why = label_mask_check(*cfg);
+            if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        }
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the label mask before the first frame or after every frame has been collected");
+        if (!cfg && !c->has_label(seq)) return 0;
+        std::fill(std::begin(c->ring_masked), std::end(c->ring_masked), false);  // (the last frame went in under ANOTHER record: lvt_amd_get_mask_stats has nothing of it)
+        if (c->label_ring.empty()) c->label_ring.assign((size_t)RING * c->B, Context::LabelAttach{}), c->label_built.assign((size_t)RING * c->B * 2, 0);
+        std::fill(c->label_built.begin(), c->label_built.end(), (uint8_t)0);
+        for (int r = 0; r < RING; r++) c->label_ring[(size_t)r * c->B + seq] = Context::LabelAttach{};  // (an attachment made under the old record has the old size)
+        if (!c->h_lab_stage.empty() && c->h_lab_stage[(size_t)seq]) {  // (the host calls' ring is sized by the record: reserved again by the next host call)
+            (void)hipHostFree(c->h_lab_stage[(size_t)seq]);
+            c->dfree(c->d_lab_ring[(size_t)seq]);
+            c->h_lab_stage[(size_t)seq] = c->d_lab_ring[(size_t)seq] = nullptr;
+        }
+        if (cfg) give_planes(c, c->d_lmask, 2, seq, c->sensor == 2 ? 1 : 2, 64);
+        c->n_label = put_seq_value(c, c->label, 1, lvt_amd_label_mask{}, seq, {cfg ? *cfg : lvt_amd_label_mask{}}, [](const lvt_amd_label_mask &r) { return r.label_width > 0; });
+        return 0;
+    });
+}
+// The label images of sequence seq's NEXT frame.  left / right: tightly packed host images (device == false) or planes in HBM at any address and the given
+// pitch; NULL: that eye gets no labels; both NULL: a pending attachment is cleared.  Accepted with frames in flight: nothing here waits for them, except that a
+// host call makes room the way upload_async does -- this slot's staging was read last by the copy of the frame RING places before, which has been collected then.
+static int frame_labels(lvt_handle h, int seq, bool device, const void *left, int pitch_l, const void *right, int pitch_r) {
+    const char *who = device ? "lvt_amd_frame_labels_device" : "lvt_amd_frame_labels";
+    return with_auto_handle(h, [&](lvt_handle t) -> int {
+        Context *c = frame_context(t, who, 0, true, {"a pooled handle (its frames ride a chain shared with other handles) (nothing was attached)", nullptr, nullptr});
+        if (!c) return -1;
+        DeviceGuard guard(c);
+        try {
+            if (seq < 0 || seq >= c->B) return refuse(t, who, "no sequence " + std::to_string(seq) + " in this handle (nothing was attached)");
+            if (!c->has_label(seq)) return refuse(t, who, "a sequence without a label-mask record: set one with lvt_amd_set_label_mask first (nothing was attached)");
+            const lvt_amd_label_mask &r = c->label[(size_t)seq];
+            const void *src[2] = {left, right};
+            const int pitch[2] = {device ? pitch_l : r.label_width, device ? pitch_r : r.label_width};
+            for (int e = 0; e < 2; e++)
+                if (src[e] && pitch[e] < r.label_width)
+                    return refuse(t, who, "a label pitch of " + std::to_string(pitch[e]) + " bytes on label images " + std::to_string(r.label_width) + " pixels wide (pitch >= label_width) (nothing was attached)");
+            if (right && c->sensor == 2) return refuse(t, who, "right-eye labels on an RGB-D handle (it has one image: pass NULL for the right eye) (nothing was attached)");
+            if (c->early_pending) drain(c);  // (a synchronous call's frame whose pose has been returned: its tail has long finished)
+            const int held = c->pend.valid ? 1 : 0;  // (the held frame owns number enq + 1 and slot enq % RING)
+            const int slot = (int)((c->enq + held) % RING);
+            Context::LabelAttach &A = c->label_ring[(size_t)slot * c->B + seq];
+            A = Context::LabelAttach{};
+            if (!left && !right) return 0;
+            if (!device) {
+                while (c->enq + held - c->done >= RING - 1) collect_oldest(c);
+                const size_t img = (size_t)r.label_width * r.label_height, stride = (img + 15) & ~(size_t)15;
+                if (c->h_lab_stage.empty()) c->h_lab_stage.assign((size_t)c->B, nullptr), c->d_lab_ring.assign((size_t)c->B, nullptr);
+                if (!c->h_lab_stage[(size_t)seq]) {
+                    HIPCHK(c, hipHostMalloc((void **)&c->h_lab_stage[(size_t)seq], stride * 2 * RING, hipHostMallocDefault));
+                    c->d_lab_ring[(size_t)seq] = c->dalloc<uint8_t>(stride * 2 * RING);
+                }
+                for (int e = 0; e < 2; e++) {
+                    if (!src[e]) continue;
+                    const size_t off = ((size_t)slot * 2 + e) * stride;
+                    std::memcpy(c->h_lab_stage[(size_t)seq] + off, src[e], img);
+                    HIPCHK(c, hipMemcpyAsync(c->d_lab_ring[(size_t)seq] + off, c->h_lab_stage[(size_t)seq] + off, img, hipMemcpyHostToDevice, c->stream_f));
+                    src[e] = c->d_lab_ring[(size_t)seq] + off;
+                }
+            }
+            for (int e = 0; e < 2; e++) A.src[e] = static_cast<const uint8_t *>(src[e]), A.pitch[e] = pitch[e];
+            A.frame = (long long)c->enq + held + 1;  // (written last: a refusal above leaves nothing attached)
+            return 0;
+        } catch (...) {
+        }
+        return -1;
     });
 }
 
@@ -725,11 +850,53 @@ LVT_API int lvt_amd_batch_set_mask_device(lvt_handle h, int seq, const void *d_l
 // out: {kept left, dropped left, kept right, dropped right} of the frame lvt_amd_get_counts answers for; an eye without a mask reports 0, 0; 0 for a sequence
 // of a batch that sat the last collected step out
 LVT_API int lvt_amd_get_mask_stats(lvt_handle h, int seq, int out[4]) {
-    return get_filter_stats(h, seq, out, 4, [](const Context *c, int s) { return c->has_mask(s, 0) || c->has_mask(s, 1); }, &Context::ring_masked,
+    // (an eye is reported where it has a static mask or the last collected step built a label plane for it: asked behind the drain, so last_slot is that step's)
+    auto filtered = [](const Context *c, int s, int e) { return c->has_mask(s, e) || c->built_label(c->last_slot, s, e); };
+    return get_filter_stats(h, seq, out, 4, [&](const Context *c, int s) { return filtered(c, s, 0) || filtered(c, s, 1); }, &Context::ring_masked,
                             [&](const Context *c, const FeatCtl &fc) {
                                 for (int e = 0; e < 2; e++)
-                                    if (c->has_mask(seq, e)) out[2 * e] = fc.mask_kept[e], out[2 * e + 1] = fc.mask_dropped[e];
+                                    if (filtered(c, seq, e)) out[2 * e] = fc.mask_kept[e], out[2 * e + 1] = fc.mask_dropped[e];
                             });
+}
+LVT_API int lvt_amd_set_label_mask(lvt_handle h, const lvt_amd_label_mask *cfg) { return set_label_mask(h, 0, false, cfg); }
+LVT_API int lvt_amd_batch_set_label_mask(lvt_handle h, int seq, const lvt_amd_label_mask *cfg) { return set_label_mask(h, seq, true, cfg); }
+LVT_API int lvt_amd_get_label_mask(lvt_handle h, int seq, lvt_amd_label_mask *out) { return get_seq_record(h, seq, &Context::has_label, &Context::label, out); }
+LVT_API int lvt_amd_frame_labels(lvt_handle h, int seq, const void *left, const void *right) { return frame_labels(h, seq, false, left, 0, right, 0); }
+LVT_API int lvt_amd_frame_labels_device(lvt_handle h, int seq, const void *d_left, int pitch_left, const void *d_right, int pitch_right) {
+    return frame_labels(h, seq, true, d_left, pitch_left, d_right, pitch_right);
+}
+// the stage alone on caller data (host pointers): k_label_mask builds the W x H plane of "LABEL MASKS" from a label image of cfg's size and, where given, a
+// static mask, into `out`, whose H rows of out_pitch bytes come back whole.  The device copies of the label image and the static mask keep the caller's
+// addresses modulo 4 (an odd address stays odd), and the device plane stands between guard bytes the call checks behind the launch.  0, or -1 on a refusal
+// (lvt_amd_last_error(NULL)) or a HIP failure.
+LVT_API int lvt_amd_build_label_mask(const lvt_amd_label_mask *cfg, const uint8_t *labels, int label_pitch, int W, int H, const uint8_t *static_or_NULL,
+                                     int static_pitch, uint8_t *out, int out_pitch) {
+    const char *who = "lvt_amd_build_label_mask";
+    if (!cfg || !labels || !out || W < 1 || W > 8192 || H < 1 || H > 8192 || out_pitch < W || (out_pitch & 3) || (static_or_NULL && static_pitch < W))
+        return refuse_call(who, "a NULL argument, a size outside 1 ... 8192, a pitch smaller than the width or an output pitch that is no multiple of 4 (nothing was changed)");
+    const std::string why = label_mask_check(*cfg);
+    if (!why.empty()) return refuse_call(who, why + " (nothing was changed)");
+    if (label_pitch < cfg->label_width) return refuse_call(who, "a label pitch smaller than label_width (nothing was changed)");
+    constexpr size_t GUARD = 64;
+    constexpr int GUARD_BYTE = 0x5A;
+    StageScratch S;
+    const size_t lab_bytes = (size_t)label_pitch * cfg->label_height, stat_bytes = static_or_NULL ? (size_t)static_pitch * H : 0, out_bytes = (size_t)out_pitch * H;
+    const size_t lab_off = (uintptr_t)labels & 3, stat_off = (uintptr_t)static_or_NULL & 3;
+    uint8_t *d_lab = S.buf<uint8_t>(lab_bytes + 4), *d_stat = static_or_NULL ? S.buf<uint8_t>(stat_bytes + 4) : nullptr;
+    uint8_t *d_out = S.buf<uint8_t>(out_bytes + 2 * GUARD, nullptr, GUARD_BYTE);
+    if (!S.ok() || hipMemcpy(d_lab + lab_off, labels, lab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        (d_stat && hipMemcpy(d_stat + stat_off, static_or_NULL, stat_bytes, hipMemcpyHostToDevice) != hipSuccess))
+        return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    LabelTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.im[0] = label_img(*cfg, d_lab + lab_off, label_pitch, W, H, d_stat ? d_stat + stat_off : nullptr, static_pitch, d_out + GUARD, out_pitch);
+    hipLaunchKernelGGL(k_label_mask, dim3(label_tiles(out_pitch, H), 1), dim3(256), 0, 0, tab);
+    std::vector<uint8_t> back(out_bytes + 2 * GUARD);
+    if (hipGetLastError() != hipSuccess || !S.fetch(back.data(), (const uint8_t *)d_out, back.size())) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    for (size_t k = 0; k < GUARD; k++)
+        if (back[k] != GUARD_BYTE || back[GUARD + out_bytes + k] != GUARD_BYTE) return refuse_call(who, "the kernel wrote outside the plane");
+    std::memcpy(out, back.data() + GUARD, out_bytes);
+    return 0;
 }
 // the stage alone on caller data (host pointers): the n features' eight arrays are compacted IN PLACE under the rule of "FEATURE MASKS" against a width x height
 // mask of `pitch` bytes per row, and every array comes back whole -- the elements behind the new count hold what the kernel left there.  Returns the new

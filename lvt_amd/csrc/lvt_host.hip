@@ -23,6 +23,7 @@
 #include "k_equalise.hip"
 #include "k_depthguard.hip"
 #include "k_mask.hip"
+#include "k_labelmask.hip"
 #include "k_state.hip"
 #include "k_poseinfo.hip"
 #include "k_reloc.hip"
@@ -323,6 +324,24 @@ struct Context {
     int n_mask = 0;                           // sequences with a mask on either eye
     bool ring_masked[RING] = {};              // per un-collected / last frame: the step went through k_mask_features under the masks the handle has now
     bool has_mask(int s, int e) const { return n_mask > 0 && mask_on[(size_t)s * 2 + e] != 0; }
+    // LABEL MASKS (lvt_amd_set_label_mask / lvt_amd_batch_set_label_mask, lvt_amd_frame_labels / _device): a sequence with a record may be handed a label image per
+    // eye for its NEXT frame, with frames in flight.  The attachment waits in a ring beside h_fargs, in the slot that frame will use and TAGGED with its number
+    // (enq + 1 at its enqueue_frame): a frame held in `pend` has its number already and never takes the labels meant for the frame behind it.  enqueue_frame puts
+    // ONE k_label_mask launch at the head of the feature stage that builds the plane (per feature-buffer parity) k_mask_features then filters that eye with.
+    // The record is a property of the handle, not state: reset and snapshots leave it alone (a reset drops a pending attachment).
+    struct LabelAttach {
+        long long frame = 0;                  // the frame number the images belong to; 0: nothing attached
+        const uint8_t *src[2] = {nullptr, nullptr};  // device addresses (the caller's planes, or this slot's own copies); nullptr: the eye has no labels
+        int pitch[2] = {0, 0};
+    };
+    std::vector<lvt_amd_label_mask> label;    // [B] (empty until the first set); label_width == 0: none
+    std::vector<uint8_t *> d_lmask;           // [B][NPAR][2] built planes, each sequence's own pitch
+    std::vector<LabelAttach> label_ring;      // [RING][B]
+    std::vector<uint8_t> label_built;         // [RING][B][2] != 0: the step built a plane for the eye (what k_mask_features of that step was handed)
+    std::vector<uint8_t *> h_lab_stage, d_lab_ring;  // [B] host calls: RING x 2 label images, page-locked / in HBM (allocated by the sequence's first host call)
+    int n_label = 0;                          // sequences with a record
+    bool has_label(int s) const { return n_label > 0 && label[(size_t)s].label_width > 0; }
+    bool built_label(int slot, int s, int e) const { return !label_built.empty() && label_built[((size_t)slot * B + s) * 2 + e] != 0; }
     // DEPTH GUARD (lvt_amd_set_depth_guard / lvt_amd_batch_set_depth_guard): an RGB-D sequence with a record has the key points k_gather kept filtered by ONE
     // k_depth_guard launch directly behind k_gather, ahead of k_mask_features.  A property of the handle, not state: reset and snapshots leave it alone.
     std::vector<lvt_amd_depth_guard> depth_guard;  // [B] (empty until the first set; radius 0: the sequence has none)
@@ -343,7 +362,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 28;
+    static constexpr int PROF_SLOTS = 29;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -419,6 +438,7 @@ struct Context {
         if (ev_switch_e) (void)hipEventDestroy(ev_switch_e);
         if (ev_caller) (void)hipEventDestroy(ev_caller);
         for (auto &x : stage) if (x.h) (void)hipHostFree(x.h);
+        for (uint8_t *x : h_lab_stage) if (x) (void)hipHostFree(x);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_done) (void)hipHostFree(h_done);
         if (h_pose) (void)hipHostFree(h_pose);
@@ -621,6 +641,7 @@ static void reset_state(Context *c, int only = -1) {  // lvt_system::reset (lvt_
         HIPCHK(c, hipMemsetAsync(c->h_seqs[s].staged_cur, 0, sizeof(int), c->stream));
         for (int r = 0; r < RING; r++) c->h_ctl[r * c->B + s] = z;
         pose_info_clear(c, s);
+        for (int r = 0; r < RING && !c->label_ring.empty(); r++) c->label_ring[(size_t)r * c->B + s] = Context::LabelAttach{};  // (a pending attachment goes with the frames)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
 }
@@ -906,7 +927,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard", "k_label_mask"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -994,6 +1015,7 @@ static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
 static void scatter_depth_planes(Context *c, const DepthRegPlan &plan);
 static void mask_features(Context *c, int slot, int par, int Bz);
+static void build_label_masks(Context *c, int slot, int par, int Bz);
 static void guard_features(Context *c, int slot, int par, int Bz);
 static void enqueue_frame(Context *c) {
     HostTimer ht(&c->host_enq_us);
@@ -1042,11 +1064,13 @@ static void enqueue_frame(Context *c) {
     //      (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
     //      in front of k_gather.
     c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = c->ring_guarded[slot] = false;
+    if (!c->label_built.empty()) std::fill_n(c->label_built.begin() + (size_t)slot * B * 2, (size_t)B * 2, (uint8_t)0);
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
     if (c->n_equal) equalise_frames(c, slot, par, Bz);
     DepthRegPlan dreg;
     if (c->n_depth_cam) begin_depth_registration(c, slot, par, Bz, dreg);
+    if (c->n_label) build_label_masks(c, slot, par, Bz);
     const bool evo = c->events_only;
     const bool feat_pack = B > 1 && Bz <= FEAT_PACK && c->feat_pack;  // (k_feat_begin_pack: the buffer gate rides in it)
     if (c->enq >= NPAR) {
@@ -1110,7 +1134,7 @@ static void enqueue_frame(Context *c) {
     scatter_depth_planes(c, dreg);  // (behind the wait for ev_depth: a host call's depth plane arrives on the early stream)
     LAUNCH_S(5, sf, k_gather, dim3(1, 2, Bz), dim3(1024), CELLS_LDS_BYTES, par);
     if (c->n_guard) guard_features(c, slot, par, Bz);  // (directly behind k_gather: the plane it sampled is the plane the guard reads)
-    if (c->n_mask) mask_features(c, slot, par, Bz);  // (the seam: k_gather has written the Feat arrays and *F.n, k_brief reads them)
+    if (c->n_mask || c->n_label) mask_features(c, slot, par, Bz);  // (the seam: k_gather has written the Feat arrays and *F.n, k_brief reads them)
     const bool brief_publishes = !evo && B == 1;  // (single sequence: k_brief's last workgroup publishes feat_seq; see k_feat_done)
     if (c->brief_from_image) LAUNCH_S(6, sf, k_brief_img, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
     else LAUNCH_S(6, sf, k_brief, dim3(64, 2, Bz), dim3(256), 0, par, brief_publishes ? (seq_t)(c->enq + 1) : (seq_t)0);
@@ -1783,6 +1807,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if ((slot == 24 || slot == 25) && c->n_equal == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without an equalisation record neither of its launches)
     if (slot == 26 && c->n_mask == 0 && c->prof_calls[26] == 0) return 0;  // (... and one that never set a mask no k_mask_features)
     if (slot == 27 && c->n_guard == 0 && c->prof_calls[27] == 0) return 0;  // (... and one that never set a depth guard no k_depth_guard)
+    if (slot == 28 && c->n_label == 0 && c->prof_calls[28] == 0) return 0;  // (... and one that never set a label-mask record no k_label_mask)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -2687,6 +2712,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             if (!c->has_mask(0, e)) return 0;
             if ((size_t)cap_bytes < n) return -1;
             HIPCHK(c, hipMemcpy(dst, c->d_mask[(size_t)e], n, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->pitch;
+            return (int)n;
+        }
+        if (what == 8) {  // the plane k_label_mask built for the eye of the last frame (u8, rows x pitch, the padding columns zero); 0 bytes where none was built
+            if (c->done == 0 || !c->built_label(c->last_slot, 0, e)) return 0;
+            if ((size_t)cap_bytes < n) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_lmask[(size_t)c->last_par * 2 + e], n, hipMemcpyDeviceToHost));
             if (pitch_out) *pitch_out = c->pitch;
             return (int)n;
         }
