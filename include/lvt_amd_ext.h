@@ -335,8 +335,28 @@ LVT_API float lvt_amd_hamming_match_batched_n(const void *q_desc, const void *q_
  * The maps are built once on the device; lvt_amd_rectify_device rectifies one 8-bit image already in HBM: ONE launch on hip_stream, in that stream's
  * order, nothing is synchronised.  src_pitch >= width (the source's padding is never read); dst_pitch >= width and dst_pitch % 4 == 0: every byte of
  * height x dst_pitch is written, the columns from width on as zero, nothing behind them.  Returns 0; -1 (NULL, a pitch that breaks these rules) and then
- * nothing was launched.  lvt_amd_rectify does the same for tightly packed host buffers. ---- */
+ * nothing was launched.  lvt_amd_rectify does the same for tightly packed host buffers.
+ *
+ * RECTIFICATION, the arithmetic of one output pixel.  For a map entry m (either map) the 1/32-px fixed-point value is
+ *   - cvRound(m * 32.f), round half to even, when the fp32 product is finite and inside (-2^31, 2^31);
+ *   - INT_MIN otherwise (NaN, an infinity, |m * 32.f| >= 2^31).
+ * The sample's corner is (sxf >> 5, syf >> 5) (an arithmetic shift: it floors), each clamped to -32768 ... 32767; the fractions are sxf & 31, syf & 31 (never
+ * negative); the four weights are (32 - ax)(32 - ay) 32, ax (32 - ay) 32, (32 - ax) ay 32, ax ay 32, except 32767, 0, 0, 1 where both fractions are zero; a
+ * source pixel outside sw x sh counts as 0; the pixel is (sum + 2^14) >> 15, clamped to 0 ... 255.  An INT_MIN entry is at -32768 behind the shift and the
+ * clamp: outside every source, and the pixel is 0.  The map builder produces such entries where the homogeneous coordinate of a row passes through zero (the
+ * rectifying rotation puts the new camera's horizon inside the image) and on a garbage calibration, which lvt_amd_rectifier_create accepts.  The INT_MIN
+ * part of the rule is cv::remap on x86 as OpenCV's source reads (cvRound(float) is cvtss2si, whose answer outside int is 0x80000000), not as something run.
+ *
+ * lvt_amd_remap_device: that arithmetic alone on caller data.  d_src (sh rows of src_pitch >= sw bytes, any address) and d_dst (dh rows of dst_pitch bytes,
+ * dst_pitch >= dw, dst_pitch % 4 == 0, 4-byte aligned) are DEVICE pointers, map1 / map2 HOST arrays of dw x dh floats; the map's size need not be the
+ * source's.  route 0: k_rectify on the float maps (lvt_amd_rectify_device's launch); route 1: k_rectify_fix, then k_rectify_frames with a table of one image
+ * (a tracker's feature stage).  Every byte of dh x dst_pitch is written, the columns from dw on as zero, nothing else.  Null stream; returns when the plane is
+ * written.  *launches (may be NULL): kernels launched.  Refused (-1, *launches = 0, nothing launched, the sentence in lvt_amd_last_error(NULL)): a NULL
+ * pointer, a size <= 0, src_pitch < sw, dst_pitch < dw or dst_pitch % 4 != 0 or a misaligned d_dst, src_pitch * sh or dst_pitch * dh beyond INT_MAX, an
+ * unknown route. ---- */
 typedef void *lvt_amd_rectifier;
+LVT_API int lvt_amd_remap_device(const void *d_src, int sw, int sh, int src_pitch, const float *map1, const float *map2, int dw, int dh,
+                                 void *d_dst, int dst_pitch, int route, int *launches);
 LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9],
                                                    const double Pnew[9], int width, int height);
 LVT_API void lvt_amd_rectifier_destroy(lvt_amd_rectifier r);

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "lvt_amd_get_matches", "lvt_amd_get_row_matches", "lvt_amd_get_map", "lvt_amd_get_staged", "lvt_amd_get_candidate_lists",
     "lvt_amd_get_pose", "lvt_amd_get_last_pose", "lvt_amd_get_predicted_pose", "lvt_amd_get_plane", "lvt_amd_pnp", "lvt_amd_pnp_detail",
     "lvt_amd_hamming_match_batched", "lvt_amd_hamming_match_batched_n", "lvt_amd_rectifier_create", "lvt_amd_rectifier_destroy",
-    "lvt_amd_rectify_device", "lvt_amd_rectify", "lvt_amd_rectifier_get_maps",
+    "lvt_amd_rectify_device", "lvt_amd_rectify", "lvt_amd_rectifier_get_maps", "lvt_amd_remap_device",
     "lvt_amd_odometry_create", "lvt_amd_odometry_destroy", "lvt_amd_odometry_reset", "lvt_amd_odometry_push_pose", "lvt_amd_odometry_update", "lvt_amd_profile_enable", "lvt_amd_profile_read", "lvt_amd_get_debug", "lvt_amd_get_timeline", "lvt_amd_get_ordering",
     "lvt_amd_batch_create", "lvt_amd_batch_size", "lvt_amd_batch_track_device_async", "lvt_amd_batch_wait",
     "lvt_amd_batch_get_counts", "lvt_amd_create_on_device", "lvt_amd_get_device", "lvt_amd_wait_status", "lvt_amd_get_host_stats",
@@ -145,6 +145,8 @@ def load_library():
     L.lvt_amd_rectify_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.lvt_amd_rectify.argtypes = [vp, vp, vp]
     L.lvt_amd_rectifier_get_maps.argtypes = [vp, vp, vp]
+    L.lvt_amd_remap_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.lvt_amd_remap_device.restype = C.c_int
     L.lvt_amd_odometry_create.restype = vp
     L.lvt_amd_odometry_create.argtypes = [vp, vp, C.c_int]
     L.lvt_amd_odometry_destroy.argtypes = [vp]
@@ -1499,6 +1501,24 @@ def hamming_match_batched(q_desc, q_xy, t_desc, t_xy, t_flag, r2: float, mode: i
     if us < 0:
         raise RuntimeError("lvt_amd_hamming_match_batched failed")
     return us  # (0.0 for an empty train set: nothing was timed)
+
+
+def remap_device(d_src: int, sw: int, sh: int, src_pitch: int, map1, map2, d_dst: int, dst_pitch: int, route: int = 0):
+    """stage entry: the rectifier's remap alone ("RECTIFICATION", include/lvt_amd_ext.h).  d_src / d_dst are device addresses (u8 planes of sh x src_pitch and
+    dh x dst_pitch bytes), map1 / map2 host float32 arrays of one shape (dh, dw), which need not be the source's; route 0 = k_rectify, route 1 = k_rectify_fix +
+    k_rectify_frames.  Returns (rc, kernels launched): (0, 1 or 2), or (-1, 0) on a refusal, whose sentence is last_call_error()."""
+    m1 = np.ascontiguousarray(map1, np.float32); m2 = np.ascontiguousarray(map2, np.float32)
+    if m1.ndim != 2 or m1.shape != m2.shape:
+        raise ValueError("map1 and map2 must be two-dimensional and of one shape")
+    n = C.c_int(-1)
+    rc = load_library().lvt_amd_remap_device(C.c_void_p(d_src), int(sw), int(sh), int(src_pitch), _p(m1), _p(m2), m1.shape[1], m1.shape[0], C.c_void_p(d_dst),
+                                             int(dst_pitch), int(route), C.byref(n))
+    return rc, n.value
+
+
+def last_call_error() -> str:
+    """the sentence of the calling thread's last refused handle-less call (lvt_amd_last_error(NULL))"""
+    return (load_library().lvt_amd_last_error(None) or b"").decode()
 
 
 class Rectifier:

@@ -62,8 +62,13 @@ __device__ __forceinline__ int remap_fixed(const uint8_t *src, int sw, int sh, i
     const int r = (v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3 + (1 << 14)) >> 15;
     return min(max(r, 0), 255);
 }
-// float map -> 1/32-px fixed point: cvRound, round half to even.  A pure function of the map value: k_rectify_fix stores exactly what k_rectify computes per pixel
-__device__ __forceinline__ int map_to_fixed(float m) { return __float2int_rn(m * 32.f); }
+// float map -> 1/32-px fixed point: cvRound, round half to even, where the fp32 product is finite and inside (-2^31, 2^31); INT_MIN otherwise (NaN fails both
+// comparisons), which >> 5 and the clamp put at -32768: outside every source, the pixel is 0 ("RECTIFICATION", include/lvt_amd_ext.h).  A pure function of the
+// map value: k_rectify_fix stores exactly what k_rectify computes per pixel
+__device__ __forceinline__ int map_to_fixed(float m) {
+    const float p = m * 32.f;
+    return (p > -2147483648.f && p < 2147483648.f) ? __float2int_rn(p) : INT_MIN;
+}
 __device__ __forceinline__ int remap_one(const uint8_t *src, int sw, int sh, int sstep, float mx, float my) {
     return remap_fixed(src, sw, sh, sstep, map_to_fixed(mx), map_to_fixed(my));
 }

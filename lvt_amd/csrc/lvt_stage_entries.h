@@ -1,4 +1,4 @@
-// lvt_stage_entries.h -- the calls that run ONE stage alone on caller data (included by lvt_host.hip): the pose solver, the motion model, the batched Hamming
+// lvt_stage_entries.h -- the calls that run ONE stage alone on caller data (included by lvt_host.hip): the pose solver, the motion model, the rectifier's remap, the batched Hamming
 // matcher, the pose-uncertainty record and the stages of the relocalisation.  Every differential test goes through them.  (lvt_amd_equalise_device, the
 // CLAHE stage alone, stays beside clahe_img in lvt_frame_props.h and uses the same helpers; so do lvt_amd_mask_features and lvt_amd_depth_guard_features, the
 // two filters behind k_gather, beside their setters there: what the two share -- the features into a host-built Seq, the upload, the fetch -- is StageFeatures.)
@@ -173,6 +173,46 @@ LVT_API int lvt_amd_motion_predict(double state[14], const double q[4], const do
     if (hipGetLastError() != hipSuccess || !S.fetch(io, dIo, 21)) return -1;
     std::copy_n(io, 14, state);
     std::copy_n(io + 14, 4, q_out), std::copy_n(io + 18, 3, p_out);
+    return 0;
+}
+
+// ---- the remap alone, on caller maps (k_rectify.hip; the definition is in include/lvt_amd_ext.h, "RECTIFICATION") ---------------------------------------------------
+// d_src (sh rows of src_pitch bytes, any address) and d_dst (dh rows of dst_pitch bytes, 4-byte aligned) are DEVICE pointers; map1, map2 are HOST arrays of
+// dw x dh floats.  route 0: k_rectify on the float maps (what lvt_amd_rectify_device launches); route 1: k_rectify_fix, then k_rectify_frames with a one-image
+// RectTable (what a tracker's feature stage launches).  Runs on the null stream and returns when the plane is written.  *launches (may be NULL): the kernels
+// the call launched, 0 on a refusal.  0, or -1 on a refusal (lvt_amd_last_error(NULL)) or a HIP failure.
+LVT_API int lvt_amd_remap_device(const void *d_src, int sw, int sh, int src_pitch, const float *map1, const float *map2, int dw, int dh, void *d_dst,
+                                 int dst_pitch, int route, int *launches) {
+    const char *who = "lvt_amd_remap_device";
+    if (launches) *launches = 0;
+    if (!d_src || !map1 || !map2 || !d_dst) return refuse_call(who, "a NULL argument (nothing was launched)");
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return refuse_call(who, "a size that is not positive (nothing was launched)");
+    if (src_pitch < sw) return refuse_call(who, "a source pitch smaller than the source width (nothing was launched)");
+    if (dst_pitch < dw || (dst_pitch & 3) || ((uintptr_t)d_dst & 3))
+        return refuse_call(who, "a destination pitch smaller than the map width or no multiple of 4, or a destination that is not 4-byte aligned (nothing was launched)");
+    if ((long long)src_pitch * sh > INT_MAX || (long long)dst_pitch * dh > INT_MAX)
+        return refuse_call(who, "a plane of more than INT_MAX bytes (nothing was launched)");
+    if (route != 0 && route != 1) return refuse_call(who, "unknown route " + std::to_string(route) + " (nothing was launched)");
+    const size_t n = (size_t)dw * dh;
+    StageScratch S;
+    const float *d_map1 = S.buf<float>(n, map1), *d_map2 = S.buf<float>(n, map2);
+    int2 *d_fix = route == 1 ? S.buf<int2>(n) : nullptr;
+    if (!S.ok()) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    int launched = 0;
+    if (route == 0) {
+        hipLaunchKernelGGL(k_rectify, dim3((dst_pitch / 4 + 255) / 256, dh), dim3(256), 0, 0, static_cast<const uint8_t *>(d_src), sw, sh, src_pitch, d_map1, d_map2,
+                           dw, dh, static_cast<uint8_t *>(d_dst), dst_pitch);
+        launched = 1;
+    } else {
+        RectTable tab;
+        std::memset(&tab, 0, sizeof(tab));
+        tab.im[0] = RectImg{static_cast<const uint8_t *>(d_src), d_fix, static_cast<uint8_t *>(d_dst), src_pitch, dst_pitch, sw, sh, dw, dh};
+        hipLaunchKernelGGL(k_rectify_fix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_map1, d_map2, d_fix, n);
+        hipLaunchKernelGGL(k_rectify_frames, dim3((dst_pitch / 4 * dh + 255) / 256, 1), dim3(256), 0, 0, tab);
+        launched = 2;
+    }
+    if (launches) *launches = launched;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return refuse_call(who, hipGetErrorString(hipGetLastError()));
     return 0;
 }
 

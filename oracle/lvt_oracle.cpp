@@ -1670,10 +1670,19 @@ void lvto_init_undistort_rectify_map(const double K[9], const double D[5], const
 // cv::remap, 8UC1, INTER_LINEAR, BORDER_CONSTANT(0): coordinates rounded to 1/32 px (cvRound = round-half-even of x*32),
 // weights from initInterTab2D: (32-fx)(32-fy)*32 ... as shorts, except the all-integer entry, whose 32768 saturates to
 // 32767 and is repaired by +1 on the LAST weight (the table's sum fix-up scans from index ksize/2 = 1).
+// The DOMAIN of a map entry m: cvRound(m * 32.f) where the fp32 product is finite and inside (-2^31, 2^31), INT_MIN otherwise -- after >> 5 and the
+// saturation an INT_MIN entry is at -32768, outside every source, and the pixel is 0.  Where this comes from: the reference calls cv::remap and has no text
+// of its own here; the round-half-even of an in-range product is cvRound as OpenCV documents it, but the INT_MIN of everything else is a READING of
+// OpenCV's source, not something run: on x86 cvRound(float) is cvtss2si, whose answer for NaN and for every out-of-range value is the integer indefinite
+// 0x80000000.  ((int)lrintf wrapped modulo 2^32 here instead, and a NaN or an infinity sampled source pixel (0, 0).)
+static int map_to_fixed(float m) {
+    const float p = m * 32.f;
+    return (p > -2147483648.f && p < 2147483648.f) ? (int)lrintf(p) : INT_MIN;
+}
 void lvto_remap_bilinear(const uint8_t *src, int sw, int sh, int sstep, const float *map1, const float *map2, int dw, int dh, uint8_t *dst) {
     for (int y = 0; y < dh; y++)
         for (int x = 0; x < dw; x++) {
-            const int sxf = (int)lrintf(map1[(size_t)y * dw + x] * 32.f), syf = (int)lrintf(map2[(size_t)y * dw + x] * 32.f);
+            const int sxf = map_to_fixed(map1[(size_t)y * dw + x]), syf = map_to_fixed(map2[(size_t)y * dw + x]);
             auto sat16 = [](int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); };
             const int sx = sat16(sxf >> 5), sy = sat16(syf >> 5), ax = sxf & 31, ay = syf & 31;
             int w0 = (32 - ax) * (32 - ay) * 32, w1 = ax * (32 - ay) * 32, w2 = (32 - ax) * ay * 32, w3 = ax * ay * 32;

@@ -20,7 +20,7 @@ def declared_symbols():
 def test_library_exports_every_declared_symbol(hip_lib):
     decl = declared_symbols()
     assert {"lvt_create", "lvt_destroy", "lvt_track", "lvt_track_with_external_corners", "lvt_get_status"} <= set(decl)
-    assert {"lvt_amd_pnp", "lvt_amd_pnp_detail", "lvt_amd_pnp_trace", "lvt_amd_motion_predict"} <= set(decl)     # the stage entry points on caller data
+    assert {"lvt_amd_pnp", "lvt_amd_pnp_detail", "lvt_amd_pnp_trace", "lvt_amd_motion_predict", "lvt_amd_remap_device"} <= set(decl)     # the stage entry points on caller data
     assert sorted(decl) == sorted(lvt_amd.ABI_SYMBOLS)
     lib = ctypes.CDLL(lvt_amd.LIB_PATH)
     for s in decl:
@@ -106,6 +106,21 @@ def test_motion_predict_refuses_a_null_argument_without_a_device(hip_lib):
         args = [None if k == missing else p(a) for k, a in enumerate(arrs)]
         assert L.lvt_amd_motion_predict(*args) == -1, missing
         assert all((a == 7.0).all() for a in arrs)
+
+
+def test_remap_device_refuses_a_null_argument_without_a_device(hip_lib):
+    """lvt_amd_remap_device: -1 for any NULL pointer before the device is touched, the sentence with the calling thread, the launch count 0 and the
+    destination unchanged (host addresses stand in for device pointers: the call is refused before any is looked at)"""
+    import numpy as np
+    L = hip_lib.load_library()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    for missing in range(4):
+        src, m1, m2, dst = np.full(16, 7, np.uint8), np.full(16, 1.0, np.float32), np.full(16, 1.0, np.float32), np.full(16, 7, np.uint8)
+        a = [None if k == missing else p(x) for k, x in enumerate((src, m1, m2, dst))]
+        n = ctypes.c_int(5)
+        assert L.lvt_amd_remap_device(a[0], 4, 4, 4, a[1], a[2], 4, 4, a[3], 4, 0, ctypes.byref(n)) == -1, missing
+        assert n.value == 0 and (dst == 7).all() and (src == 7).all()
+        assert hip_lib.last_call_error() == "lvt_amd_remap_device: a NULL argument (nothing was launched)", hip_lib.last_call_error()
 
 
 def test_product_does_not_reference_the_oracle():
