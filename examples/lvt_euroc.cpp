@@ -1,13 +1,24 @@
 // lvt_euroc -- EuRoC MAV stereo command line harness over the C-ABI (SURVEY 8(f) rows 1 + 2).
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/euroc/euroc_example.cpp:49-175 there):
-//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]]
+//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE]
 // (--clahe: CLAHE contrast equalisation of the rectified frames inside the feature stage, lvt_amd_set_equalisation; absent by default)
 // reads <stamps_dir>/<dataset_name>.txt (one nanosecond stamp per line = the image file stem), the cam0 / cam1 PNGs below
 // <root>/<dataset_name>/mav0/, hands the RAW images to lvt_track -- the two rectifiers with the calibration the reference hard-codes
 // (lvt_amd_rectifier_*: cv::initUndistortRectifyMap + cv::remap INTER_LINEAR) are attached to the tracker once, which rectifies
 // every frame at the head of its feature stage (lvt_amd_set_rectifiers) --, maps the camera pose into the body
 // frame (T_BS * T_cam) and writes <dataset_name>.txt in the TUM format "t x y z qx qy qz qw" (6 / 7 digits).
+//
+// --lens FILE (not in the reference): the calibration comes from FILE instead of the hard-coded EuRoC one, so any folder of the same mav0 layout runs -- a
+// TUM-VI sequence with its equidistant lenses, a rational-polynomial rig, raw images of another size than the tracked one ("LENS MODELS",
+// include/lvt_amd_ext.h).  FILE is flat `key: number` lines (what the config reader takes; # starts a comment, a missing key reads as 0):
+//     dst_width, dst_height      the rectified (tracked) size
+//     P0 ... P8                  the new camera matrix, row-major; fx fy cx cy of the tracker are P0 P4 P2 P5
+//     baseline                   metres
+//     left_model, right_model    0 = radtan (plumb_bob / rational_polynomial), 1 = fisheye (equidistant)
+//     left_width, left_height    the RAW image's size (right_ likewise; the two are equal)
+//     left_K0 ... left_K8        the raw camera matrix, row-major;  left_D0 ... left_D11  the coefficients;  left_R0 ... left_R8  the rectifying rotation
+//     Tbs0 ... Tbs11             (optional) body-from-camera, 3 x 4 row-major; absent: the identity, the trajectory is the left camera's
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
 #include "image_io.h"
@@ -17,6 +28,7 @@
 #include <iomanip>
 #include <iostream>
 #include <sstream>
+#include <utility>
 
 using namespace lvt_io;
 
@@ -46,22 +58,45 @@ void rotation_to_quaternion(const double m[3][3], double q[4]) {
     }
 }
 
+// the flat `key: number` reader of the config files (lvt_amd_params_from_file's rules): # starts a comment, a line without a number behind its colon is skipped
+bool read_numbers(const std::string &path, std::vector<std::pair<std::string, double>> &kv) {
+    std::ifstream f(path);
+    if (!f.is_open()) return false;
+    std::string line;
+    while (std::getline(f, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        const size_t colon = line.find(':');
+        if (colon == std::string::npos || line[0] == '%') continue;
+        const size_t a = line.find_first_not_of(" \t"), b = line.find_last_not_of(" \t", colon ? colon - 1 : 0);
+        if (a == std::string::npos || a >= colon) continue;
+        const char *num = line.c_str() + colon + 1;
+        char *end = nullptr;
+        const double v = std::strtod(num, &end);
+        if (end == num) continue;
+        kv.emplace_back(line.substr(a, b - a + 1), v);
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc < 5) {
-        std::cout << "Usage ./lvt_euroc euroc_root_dir stamps_dir dataset_name config_file_name [--max-frames N] [--out name.txt]" << std::endl;
+        std::cout << "Usage ./lvt_euroc euroc_root_dir stamps_dir dataset_name config_file_name [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE]" << std::endl;
         return -1;
     }
     const std::string root_dir = argv[1], stamps_dir = argv[2], dataset_name = argv[3], config_file_name = argv[4];
     const std::string seq_dir = root_dir + "/" + dataset_name + "/mav0";
     std::string out_name = dataset_name + ".txt";
     long max_frames = -1;
+    std::string lens_file;  // --lens FILE: the calibration of both eyes, P and the tracked size
     lvt_amd_equalisation clahe = {0, 0, 0.f};  // --clahe CLIP[,TX,TY]: equalise the rectified frames (dark sequences); tiles 8 x 8 unless given
     for (int i = 5; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
+        else if (k == "--lens") lens_file = argv[i + 1];
         else if (k == "--clahe") {
             clahe.tiles_x = clahe.tiles_y = 8;
             if (std::sscanf(argv[i + 1], "%f,%d,%d", &clahe.clip_limit, &clahe.tiles_x, &clahe.tiles_y) < 1) {
@@ -102,15 +137,51 @@ int main(int argc, char **argv) {
                           -0.007035845251224894, -0.007729688520722713, 0.007064130529506649, 0.999945173484644};
     const double dl[5] = {-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0};
     const double dr[5] = {-0.28368365, 0.07451284, -0.00010473, -3.555907e-05, 0.0};
-    const int W = 752, H = 480;
+    int W = 752, H = 480;    // the RAW images' size
     params.fx = 435.2046959714599f, params.fy = 435.2046959714599f, params.cx = 367.4517211914062f, params.cy = 252.2008514404297f;
     params.baseline = 0.110077842f;
     params.img_width = W, params.img_height = H;
-    const double Tbs[4][4] = {{0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975},
+    double Tbs[4][4] = {{0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975},
                               {0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768},
                               {-0.0257744366974, 0.00375618835797, 0.999660727178, 0.00981073058949},
                               {0.0, 0.0, 0.0, 1.0}};
-    lvt_amd_rectifier rect_l = lvt_amd_rectifier_create(kl, dl, rl, pn, W, H), rect_r = lvt_amd_rectifier_create(kr, dr, rr, pn, W, H);
+    lvt_amd_rectifier rect_l = nullptr, rect_r = nullptr;
+    if (lens_file.empty()) {
+        rect_l = lvt_amd_rectifier_create(kl, dl, rl, pn, W, H), rect_r = lvt_amd_rectifier_create(kr, dr, rr, pn, W, H);
+    } else {
+        std::vector<std::pair<std::string, double>> kv;
+        if (!read_numbers(lens_file, kv)) {
+            std::cout << "Unable to open the lens file " << lens_file << std::endl;
+            return -1;
+        }
+        bool has_tbs = false;
+        auto get = [&](const std::string &k) -> double {
+            for (auto &e : kv)
+                if (e.first == k) return e.second;
+            return 0.0;
+        };
+        for (auto &e : kv) has_tbs = has_tbs || e.first.compare(0, 3, "Tbs") == 0;
+        double P[9];
+        for (int k = 0; k < 9; k++) P[k] = get("P" + std::to_string(k));
+        const int dw = (int)std::nearbyint(get("dst_width")), dh = (int)std::nearbyint(get("dst_height"));
+        lvt_amd_lens lens[2];
+        double Rr[2][9];
+        for (int e = 0; e < 2; e++) {
+            const std::string eye = e ? "right_" : "left_";
+            lens[e].model = (int)std::nearbyint(get(eye + "model"));
+            lens[e].width = (int)std::nearbyint(get(eye + "width")), lens[e].height = (int)std::nearbyint(get(eye + "height"));
+            for (int k = 0; k < 9; k++) lens[e].K[k] = get(eye + "K" + std::to_string(k)), Rr[e][k] = get(eye + "R" + std::to_string(k));
+            for (int k = 0; k < 12; k++) lens[e].D[k] = get(eye + "D" + std::to_string(k));
+        }
+        params.fx = (float)P[0], params.fy = (float)P[4], params.cx = (float)P[2], params.cy = (float)P[5];
+        params.baseline = (float)get("baseline");
+        params.img_width = dw, params.img_height = dh;
+        W = lens[0].width, H = lens[0].height;
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) Tbs[r][c] = has_tbs ? get("Tbs" + std::to_string(4 * r + c)) : (r == c ? 1.0 : 0.0);
+        rect_l = lvt_amd_rectifier_create_lens(&lens[0], Rr[0], P, dw, dh);
+        if (rect_l) rect_r = lvt_amd_rectifier_create_lens(&lens[1], Rr[1], P, dw, dh);
+    }
     lvt_handle vo = lvt_amd_create(&params, 1 /* STEREO */);
     if (!rect_l || !rect_r || !vo) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;

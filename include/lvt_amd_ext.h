@@ -364,21 +364,76 @@ LVT_API int lvt_amd_rectify_device(lvt_amd_rectifier r, const void *d_src, int s
                                    void *hip_stream);
 LVT_API int lvt_amd_rectify(lvt_amd_rectifier r, const unsigned char *src, unsigned char *dst);
 LVT_API int lvt_amd_rectifier_get_maps(lvt_amd_rectifier r, float *map1, float *map2);
+
+/* LENS MODELS: a rectifier from a lens record, for a raw image of any size.  lvt_amd_rectifier_create knows the five-coefficient plumb-bob lens and one size;
+ * lvt_amd_rectifier_create_lens takes the three models a calibration arrives in (ROS CameraInfo, Kalibr, OpenCV) and a SOURCE (the raw image,
+ * lens.width x lens.height) that need not be the DESTINATION (the rectified image and the maps, dst_width x dst_height):
+ *   - LVT_AMD_LENS_RADTAN: plumb_bob (D[5 ...] zero) and rational_polynomial, OpenCV's order k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, unused ones zero;
+ *   - LVT_AMD_LENS_FISHEYE: equidistant (cv::fisheye, Kalibr pinhole-equi), D = k1 k2 k3 k4; D[4 ...] is not read.
+ * The text below is the definition: the maps are equal to it, bit for bit (FISHEYE: up to the last bit of atan, see there).  It follows the published
+ * arithmetic of cv::initUndistortRectifyMap and cv::fisheye::initUndistortRectifyMap with CV_32FC1 maps, with two known differences: the tilted-sensor terms
+ * (tauX, tauY) are not taken, and cv::fisheye inverts Pnew R by SVD where both models here use the closed form below.
+ *
+ * Shared by both models.  All arithmetic is fp64, one IEEE operation per written operation (no fused multiply-add), operands left to right.
+ *   - iR is the inverse of the product Pnew R (each entry summed over k ascending) by cofactors: d = S0 (S4 S8 - S5 S7) - S1 (S3 S8 - S5 S6) + S2 (S3 S7 - S4 S6);
+ *     d == 0: iR = I; otherwise every cofactor times (1 / d) -- what lvt_amd_rectifier_create computes.
+ *   - for destination row i: _x = i iR[1] + iR[2], _y = i iR[4] + iR[5], _w = i iR[7] + iR[8] at column 0; stepping one column adds iR[0], iR[3], iR[6].
+ *     This is a left-to-right chain of rounded adds along the row, and the chain IS the definition (start + j step rounds differently).
+ * RADTAN.  iw = 1 / _w, x = _x iw, y = _y iw, x2 = x x, y2 = y y, r2 = x2 + y2, _2xy = 2 x y,
+ *     kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2),
+ *     xd = x kr + p1 _2xy + p2 (r2 + 2 x2) + s1 r2 + (s2 r2) r2,    yd = y kr + p1 (r2 + 2 y2) + p2 _2xy + s3 r2 + (s4 r2) r2,
+ *     u = fx xd + u0, v = fy yd + v0.  With k4 ... s4 zero and equal sizes these are lvt_amd_rectifier_create's maps, bit for bit.
+ * FISHEYE.  If _w <= 0 (a ray from behind the new camera): u = (_x > 0) ? -inf : +inf, v = (_y > 0) ? -inf : +inf.  Otherwise
+ *     x = _x / _w, y = _y / _w, r = sqrt(x x + y y), theta = atan(r), t2 = theta theta, t4 = t2 t2, t6 = t4 t2, t8 = t4 t4,
+ *     theta_d = theta ((((1 + k1 t2) + k2 t4) + k3 t6) + k4 t8), scale = (r == 0) ? 1 : theta_d / r,
+ *     u = (fx x) scale + u0, v = (fy y) scale + v0.
+ *     sqrt and the divisions are correctly rounded; atan is the device library's, which may differ from another libm's in its last bit.
+ * Both maps are (float)u, (float)v.  Everything behind them is RECTIFICATION above: the 1/32-px fixed point, INT_MIN for NaN, infinities and out-of-range
+ * values (the pixel is 0), and the remap from a source of lens.width x lens.height.
+ *  - the remap stays bilinear (no area filter): a source more than about twice the destination each way aliases.  Choose Pnew and the destination accordingly.
+ *  - with such a rectifier lvt_amd_rectify takes a tightly packed lens.width x lens.height image and writes a dst_width x dst_height one; lvt_amd_rectify_device
+ *    wants src_pitch >= lens.width, and the destination rules are unchanged; lvt_amd_rectifier_get_maps writes dst_width x dst_height floats per map.
+ *  - lvt_amd_rectifier_create_lens returns NULL, with the sentence in lvt_amd_last_error(NULL) ending in "(nothing was created)", in this order, for: a NULL
+ *    argument; an unknown model; a source side outside 1 ... 8192; a destination side outside 1 ... 8192; a non-finite field of K or D (FISHEYE: of D[0 ... 3]);
+ *    a non-finite field of R or Pnew.  A singular Pnew R is accepted as by lvt_amd_rectifier_create (iR = I).
+ *  - lvt_amd_rectifier_get_info: the record the rectifier was made from (FISHEYE: D[4 ...] read back as zero; a rectifier of lvt_amd_rectifier_create: RADTAN,
+ *    its five coefficients, width x height both ways) and dst_size = {dst_width, dst_height}.  0; -1 for a NULL argument.
+ *  - not here: the tilted-sensor and omnidirectional (Mei) models; computing R and Pnew from a stereo extrinsic (cv::stereoRectify). */
+enum { LVT_AMD_LENS_RADTAN = 0, LVT_AMD_LENS_FISHEYE = 1 };
+typedef struct lvt_amd_lens {
+    int model;
+    int width, height;     /* of the RAW image, 1 ... 8192 each way */
+    double K[9];           /* row-major; fx, fy, u0, v0 are read */
+    double D[12];          /* RADTAN: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (OpenCV's order, unused ones zero); FISHEYE: k1 k2 k3 k4, the rest ignored */
+} lvt_amd_lens;
+LVT_API lvt_amd_rectifier lvt_amd_rectifier_create_lens(const lvt_amd_lens *lens, const double R[9], const double Pnew[9], int dst_width, int dst_height);
+LVT_API int lvt_amd_rectifier_get_info(lvt_amd_rectifier r, lvt_amd_lens *lens_out, int dst_size[2]);   /* 0 / -1 */
+
 /* RAW stereo frames: rectification inside the tracker's feature stage.  With a pair of rectifiers attached, every stereo frame handed to the handle --
  * lvt_track, lvt_amd_track_async, lvt_amd_track_device[_async]; a batch: the sequences with rectifiers in lvt_amd_batch_track_device_async[_mixed] -- is a RAW
  * frame: one launch at the head of the feature stage (k_rectify_frames: both eyes of every such sequence of the step) rectifies it into planes the tracker
  * owns, byte for byte what lvt_amd_rectify_device writes, and the frame is tracked from those.  No host round trip, no second upload, no launch or stream of the
  * caller's to order.  A handle or sequence without rectifiers launches exactly what it did before.
+ *  - THE FRAME'S SIZE.  A pair's DESTINATION size is the sequence's img_width x img_height; its two SOURCE sizes (lvt_amd_rectifier_create: the same size;
+ *    lvt_amd_rectifier_create_lens: the lens's width x height) are equal to each other and need not be the destination's.  From the attach on the sequence's
+ *    frame size is the source size: every stereo entry point takes n_rows x n_cols = the source's and refuses anything else, the tracker's own size
+ *    included; a batch sequence in lvt_amd_batch_track_device_async_mixed likewise (sit-outs as ever), and lvt_amd_batch_track_device_async wants its one size
+ *    to be every sequence's.  Detaching returns the sequence to its own size.  What is sized by the frame's bytes follows the source (the staging buffers,
+ *    the image ring and the fused pull of lvt_amd_track_async, with a colour format the colour and the converted planes: convert at the source's size, then
+ *    remap); everything behind the rectified plane -- equalisation, masks, label masks, the detector -- stays at the sequence's size.  A pair whose source is
+ *    the destination's size allocates and launches exactly what it always did.
  *  - host entry points pull the raw images where they pulled the rectified ones (the staged planes of the call, the fused pull of lvt_amd_track_async included);
  *    device entry points read the caller's raw planes in place: any pitch >= n_cols (the pitch % 16 rule applies to rectified planes only); the planes must
  *    stay valid until the frame has been collected, as always.
  *  - the rectifiers are BORROWED: they must outlive the handle or be detached first (NULL, NULL detaches; one NULL is refused); several sequences and handles may
  *    share a pair.
- *  - refused (-1, nothing changed, the reason in lvt_amd_last_error): a rectifier whose size is not the sequence's img_width x img_height or that was created on
- *    another device, an RGB-D handle, a pooled or automatic seat, seq out of range, a handle with frames in flight (attach before the first frame or after every
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error), in this order behind the handle's kind: one rectifier NULL; per rectifier, left first, a
+ *    DESTINATION size that is not the sequence's img_width x img_height, then one created on another device; two source sizes that differ (the sentence names
+ *    both); frames in flight.  Also an RGB-D handle, a pooled or automatic seat, seq out of range, a handle with frames in flight (attach before the first frame or after every
  *    frame has been collected).  A successful attach counts as use of an lvt_create handle: it stays on its own chain when a second lvt_create arrives.
  *  - lvt_track_with_external_corners on such a handle is refused (nothing is tracked, lvt_amd_last_error says so): the corners would be in rectified coordinates.
- *  - lvt_amd_get_plane(h, eye, 2, ...) reads the rectified image of the last frame back (u8, rows x pitch; 0 for a handle without rectifiers);
+ *  - lvt_amd_get_plane(h, eye, 2, ...) reads the rectified image of the last frame back (u8, rows x pitch; 0 for a handle without rectifiers); what = 3 (the
+ *    converted gray image of a colour handle, before the remap) has the SOURCE's rows and a pitch of its own when the source is not the sequence's size;
  *    lvt_amd_profile_read reports the launch as "k_rectify_frames". */
 LVT_API int lvt_amd_set_rectifiers(lvt_handle h, lvt_amd_rectifier left, lvt_amd_rectifier right);
 LVT_API int lvt_amd_batch_set_rectifiers(lvt_handle h, int seq, lvt_amd_rectifier left, lvt_amd_rectifier right);

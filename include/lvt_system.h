@@ -271,7 +271,8 @@ class lvt_system {
     }
 
     /* stereo: two rectified 8-bit gray images -- or the camera's RAW images, once a pair of rectifiers has been attached with
-     * lvt_amd_set_rectifiers(native_handle(), left, right) (include/lvt_amd_ext.h); RGB-D: gray + 32-bit float depth in metres (lvt_system.cpp:157-207).
+     * lvt_amd_set_rectifiers(native_handle(), left, right) (include/lvt_amd_ext.h; rectifiers of lvt_amd_rectifier_create or, for a rational or fisheye lens
+     * and raw images of another size than the tracker's, of lvt_amd_rectifier_create_lens: the views then have the lens's width x height); RGB-D: gray + 32-bit float depth in metres (lvt_system.cpp:157-207).
      * Returns the camera-to-world pose of the left camera in the first frame's left-camera frame; after LOST, the last pose. */
     lvt_pose track(const lvt_image_view &img1, const lvt_image_view &img2) {
         double R[3][3], t[3];

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "lvt_amd_get_pose", "lvt_amd_get_last_pose", "lvt_amd_get_predicted_pose", "lvt_amd_get_plane", "lvt_amd_pnp", "lvt_amd_pnp_detail",
     "lvt_amd_hamming_match_batched", "lvt_amd_hamming_match_batched_n", "lvt_amd_rectifier_create", "lvt_amd_rectifier_destroy",
     "lvt_amd_rectify_device", "lvt_amd_rectify", "lvt_amd_rectifier_get_maps", "lvt_amd_remap_device",
+    "lvt_amd_rectifier_create_lens", "lvt_amd_rectifier_get_info",
     "lvt_amd_odometry_create", "lvt_amd_odometry_destroy", "lvt_amd_odometry_reset", "lvt_amd_odometry_push_pose", "lvt_amd_odometry_update", "lvt_amd_profile_enable", "lvt_amd_profile_read", "lvt_amd_get_debug", "lvt_amd_get_timeline", "lvt_amd_get_ordering",
     "lvt_amd_batch_create", "lvt_amd_batch_size", "lvt_amd_batch_track_device_async", "lvt_amd_batch_wait",
     "lvt_amd_batch_get_counts", "lvt_amd_create_on_device", "lvt_amd_get_device", "lvt_amd_wait_status", "lvt_amd_get_host_stats",
@@ -145,6 +146,10 @@ def load_library():
     L.lvt_amd_rectify_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.lvt_amd_rectify.argtypes = [vp, vp, vp]
     L.lvt_amd_rectifier_get_maps.argtypes = [vp, vp, vp]
+    if hasattr(L, "lvt_amd_rectifier_create_lens"):   # (lens models: a library built before they existed -- LVT_AMD_LIB, A/B runs -- lacks them)
+        L.lvt_amd_rectifier_create_lens.restype = vp
+        L.lvt_amd_rectifier_create_lens.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+        L.lvt_amd_rectifier_get_info.argtypes = [vp, vp, vp]
     L.lvt_amd_remap_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.lvt_amd_remap_device.restype = C.c_int
     L.lvt_amd_odometry_create.restype = vp
@@ -1000,7 +1005,9 @@ class LvtSystem:
 
     def set_rectifiers(self, left, right) -> int:
         """attach a pair of Rectifier objects (or None, None to detach): every stereo frame handed to this system is then a RAW frame, rectified at the head of
-        its feature stage.  0: done; -1: refused (last_error() says why).  The rectifiers are borrowed: keep them alive while they are attached."""
+        its feature stage.  The pair's destination (w x h) is this system's image size; its source size (src_w x src_h, the same for both) is the shape every
+        frame has from then on -- Rectifier.from_lens makes rectifiers whose source is not the destination's size.  0: done; -1: refused (last_error() says
+        why).  The rectifiers are borrowed: keep them alive while they are attached."""
         rc = load_library().lvt_amd_set_rectifiers(self._h, left._h if left is not None else None, right._h if right is not None else None)
         if rc == 0:
             self._rect = (left, right)
@@ -1521,17 +1528,71 @@ def last_call_error() -> str:
     return (load_library().lvt_amd_last_error(None) or b"").decode()
 
 
+LENS_RADTAN, LENS_FISHEYE = 0, 1   # LVT_AMD_LENS_*
+
+
+class _LensRecord(C.Structure):   # lvt_amd_lens
+    _fields_ = [("model", C.c_int), ("width", C.c_int), ("height", C.c_int), ("K", C.c_double * 9), ("D", C.c_double * 12)]
+
+
+class Lens:
+    """lvt_amd_lens ("LENS MODELS", include/lvt_amd_ext.h): the model (LENS_RADTAN / LENS_FISHEYE), the RAW image's size, K (3 x 3) and the distortion
+    coefficients -- RADTAN: up to 12 in OpenCV's order k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, FISHEYE: k1 k2 k3 k4; a shorter D is padded with zeros."""
+
+    def __init__(self, model: int, width: int, height: int, K, D):
+        D = np.asarray(D, np.float64).reshape(-1)
+        if D.size > 12:
+            raise ValueError(f"a lens has at most 12 distortion coefficients, not {D.size}")
+        self.model, self.width, self.height = int(model), int(width), int(height)
+        self.K = np.array(K, np.float64).reshape(3, 3)
+        self.D = np.concatenate([D, np.zeros(12 - D.size)])
+
+    def _record(self) -> _LensRecord:
+        return _LensRecord(self.model, self.width, self.height, (C.c_double * 9)(*self.K.reshape(-1)), (C.c_double * 12)(*self.D))
+
+    def __repr__(self):
+        return f"Lens(model={self.model}, width={self.width}, height={self.height}, K={self.K.tolist()}, D={self.D.tolist()})"
+
+
 class Rectifier:
-    """cv::initUndistortRectifyMap + cv::remap(INTER_LINEAR) on the GPU (the EuRoC example's pre-step, SURVEY 8(f) row 2)."""
+    """cv::initUndistortRectifyMap + cv::remap(INTER_LINEAR) on the GPU (the EuRoC example's pre-step, SURVEY 8(f) row 2).  w x h is the DESTINATION (the
+    rectified image, the maps), src_w x src_h the SOURCE (the raw image): equal for Rectifier(...), the lens's own size for Rectifier.from_lens(...)."""
 
     def __init__(self, K, D, R, P, width: int, height: int):
         L = load_library()
         a = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (K, D, R, P)]
         self._keep = a
         self.w, self.h = width, height
+        self.src_w, self.src_h = width, height
         self._h = L.lvt_amd_rectifier_create(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), width, height)
         if not self._h:
             raise RuntimeError("lvt_amd_rectifier_create returned NULL")
+
+    @classmethod
+    def from_lens(cls, lens: "Lens", R, P, dst_width: int, dst_height: int) -> "Rectifier":
+        """lvt_amd_rectifier_create_lens: a RADTAN (up to twelve coefficients) or FISHEYE lens, a raw image of lens.width x lens.height rectified to
+        dst_width x dst_height.  ValueError with the library's sentence when the record is refused."""
+        L = load_library()
+        self = cls.__new__(cls)
+        self._h = None
+        rec = lens._record()
+        a = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (R, P)]
+        if a[0].size != 9 or a[1].size != 9:
+            raise ValueError("R and P are 3 x 3")
+        self._keep = a
+        self.w, self.h = int(dst_width), int(dst_height)
+        self.src_w, self.src_h = lens.width, lens.height
+        self._h = L.lvt_amd_rectifier_create_lens(C.byref(rec), _p(a[0]), _p(a[1]), self.w, self.h)
+        if not self._h:
+            raise ValueError(last_call_error() or "lvt_amd_rectifier_create_lens returned NULL")
+        return self
+
+    def info(self):
+        """(Lens, (dst_width, dst_height)): the record this rectifier was made from (lvt_amd_rectifier_get_info)"""
+        rec, size = _LensRecord(), (C.c_int * 2)()
+        if load_library().lvt_amd_rectifier_get_info(self._h, C.byref(rec), size) != 0:
+            raise RuntimeError("lvt_amd_rectifier_get_info failed")
+        return Lens(rec.model, rec.width, rec.height, list(rec.K), list(rec.D)), (int(size[0]), int(size[1]))
 
     def maps(self):
         m1 = np.zeros((self.h, self.w), np.float32); m2 = np.zeros((self.h, self.w), np.float32)
@@ -1540,14 +1601,17 @@ class Rectifier:
         return m1, m2
 
     def rectify(self, img):
+        """a raw (src_h, src_w) image -> the rectified (h, w) one"""
         a = _u8(img)
+        if a.shape != (self.src_h, self.src_w):
+            raise ValueError(f"a raw image of {a.shape[1]} x {a.shape[0]} for a rectifier whose source is {self.src_w} x {self.src_h}")
         out = np.zeros((self.h, self.w), np.uint8)
         if load_library().lvt_amd_rectify(self._h, _p(a), _p(out)) != 0:
             raise RuntimeError("lvt_amd_rectify failed")
         return out
 
     def rectify_device(self, d_src: int, src_pitch: int, d_dst: int, dst_pitch: int, stream: int = 0) -> int:
-        """stage entry: the remap alone on device planes, enqueued on `stream` (u8; src_pitch >= width; dst_pitch % 4 == 0 and >= width: every byte of
+        """stage entry: the remap alone on device planes, enqueued on `stream` (u8; src_pitch >= the source's width; dst_pitch % 4 == 0 and >= width: every byte of
         height x dst_pitch is written, the columns from width on as zero); 0 / -1 (refused, nothing enqueued)"""
         return load_library().lvt_amd_rectify_device(self._h, C.c_void_p(d_src), int(src_pitch), C.c_void_p(d_dst), int(dst_pitch), C.c_void_p(stream))
 

@@ -149,15 +149,15 @@ static void convert_colour_frames(Context *c, int slot, int par, int Bz) {
     });
     for (int s = 0; s < Bz; s++) {
         if (c->fmt_of(s) == PIX_GRAY8 || fw[s].absent) continue;
-        const Params &q = c->seq_prm(s);
-        const int dpitch = c->h_seqs[s].plane_pitch, eyes = (c->sensor == 2) ? 1 : 2;
+        const int fW = c->frame_W(s), fH = c->frame_H(s);  // (the frame's size: a raw frame's where rectifiers of another source size follow)
+        const int dpitch = c->frame_pitch(s), eyes = (c->sensor == 2) ? 1 : 2;
         GrayImg *im = pk.add(eyes);
         for (int e = 0; e < eyes; e++) {
             GrayImg &I = im[e];
             I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
             I.dst = c->d_gray[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
-            I.w = q.W, I.h = q.H, I.fmt = c->fmt_of(s);
-            words = std::max(words, dpitch / 4 * q.H);
+            I.w = fW, I.h = fH, I.fmt = c->fmt_of(s);
+            words = std::max(words, dpitch / 4 * fH);
             fw[s].img[e] = I.dst;
         }
         if (eyes == 1) fw[s].img[1] = fw[s].img[0];
@@ -165,6 +165,22 @@ static void convert_colour_frames(Context *c, int slot, int par, int Bz) {
         if (s == 0) c->ring_converted[slot] = true;
     }
     pk.flush();
+}
+// sequence seq's converted planes hold a frame of its present size (frame_pitch x frame_H): allocated at their first use, and again when the frame has grown
+// or shrunk since (rectifiers of another source size attached or detached; no frame is in flight then)
+static void give_gray_planes(Context *c, int seq) {
+    const int eyes = c->sensor == 2 ? 1 : 2;
+    const size_t bytes = (size_t)c->frame_pitch(seq) * c->frame_H(seq) + 64;
+    if (c->d_gray.empty()) c->d_gray.assign((size_t)c->B * NPAR * 2, nullptr);
+    if (c->gray_bytes.empty()) c->gray_bytes.assign((size_t)c->B, 0);
+    if (c->gray_bytes[(size_t)seq] == bytes) return;
+    for (int par = 0; par < NPAR; par++)
+        for (int e = 0; e < eyes; e++) {
+            uint8_t *&d = c->d_gray[((size_t)seq * NPAR + par) * 2 + e];
+            c->dfree(d);
+            d = c->dalloc<uint8_t>(bytes);
+        }
+    c->gray_bytes[(size_t)seq] = bytes;
 }
 static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) {
     static const PropertyCall call = {"lvt_amd_set_pixel_format", 0,
@@ -175,7 +191,7 @@ static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) 
         if (format < PIX_GRAY8 || format > PIX_RGBA8) return refuse_unchanged(t, call.who, "unknown pixel format " + std::to_string(format));
         if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the format before the first frame or after every frame has been collected");
         if (format == c->fmt_of(seq)) return 0;
-        if (format != PIX_GRAY8) give_planes(c, c->d_gray, 2, seq, c->sensor == 2 ? 1 : 2, 64);
+        if (format != PIX_GRAY8) give_gray_planes(c, seq);
         if (seq == 0 && pix_bpp(format) != c->bpp_of(0)) stage_release(c);  // (the pinned staging of the host entry points is sized by bpp: reserved again at the next frame)
         c->n_colour = put_seq_value(c, c->pixfmt, 1, (int)PIX_GRAY8, seq, {format}, [](int f) { return f != PIX_GRAY8; });
         return 0;
@@ -197,13 +213,14 @@ static void rectify_raw_frames(Context *c, int slot, int par, int Bz) {
         if (!c->has_rect(s) || fw[s].absent) continue;
         const Params &q = c->seq_prm(s);
         const int dpitch = c->h_seqs[s].plane_pitch;
+        const Rectifier *r0 = c->rect[2 * (size_t)s];
         RectImg *im = pk.add(2);
         for (int e = 0; e < 2; e++) {
             RectImg &I = im[e];
             I.src = fw[s].img[e], I.src_pitch = fw[s].img_pitch;
             I.map = c->rect[2 * (size_t)s + e]->d_fix;
             I.dst = c->d_rect[((size_t)s * NPAR + par) * 2 + e], I.dst_pitch = dpitch;
-            I.sw = I.dw = q.W, I.sh = I.dh = q.H;
+            I.sw = r0->sw, I.sh = r0->sh, I.dw = q.W, I.dh = q.H;  // (the source: the lens's size, the same for both eyes; the destination: the sequence's)
             words = std::max(words, dpitch / 4 * q.H);
             fw[s].img[e] = I.dst;
         }
@@ -224,14 +241,21 @@ static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectif
         const Params &q = c->seq_prm(seq);
         for (Rectifier *r : {rl, rr}) {
             if (!r) continue;
-            if (r->w != q.W || r->h != q.H)
+            if (r->w != q.W || r->h != q.H)  // (its DESTINATION: what it writes is what the sequence tracks)
                 return refuse_unchanged(t, call.who, "a rectifier of " + std::to_string(r->w) + " x " + std::to_string(r->h) + " on a sequence of " + std::to_string(q.W) + " x " + std::to_string(q.H));
             if (r->device != c->device)
                 return refuse_unchanged(t, call.who, "a rectifier created on device " + std::to_string(r->device) + ", the handle owns device " + std::to_string(c->device));
         }
+        if (rl && (rl->sw != rr->sw || rl->sh != rr->sh))  // (one frame size per sequence: both eyes arrive through one n_rows x n_cols)
+            return refuse_unchanged(t, call.who, "the left rectifier's source is " + std::to_string(rl->sw) + " x " + std::to_string(rl->sh) + ", the right one's " + std::to_string(rr->sw) + " x " + std::to_string(rr->sh) + ": a sequence's two raw images have one size");
         if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: attach before the first frame or after every frame has been collected");
         if (rl) give_planes(c, c->d_rect, 2, seq, 2, 64);
+        const int fW = c->frame_W(seq), fH = c->frame_H(seq);
         c->n_rect = put_seq_value(c, c->rect, 2, (Rectifier *)nullptr, seq, {rl, rr}, [](const Rectifier *r) { return r != nullptr; });
+        if (c->frame_W(seq) != fW || c->frame_H(seq) != fH) {  // the frame's size changed: what is sized by its bytes follows (a same-size attach: nothing)
+            if (seq == 0) frame_planes_release(c);
+            if (c->fmt_of(seq) != PIX_GRAY8) give_gray_planes(c, seq);
+        }
         return 0;
     });
 }

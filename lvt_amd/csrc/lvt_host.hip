@@ -140,7 +140,9 @@ constexpr uint64_t CTX_MAGIC = 0x4C56545F43545831ull, SLOT_MAGIC = 0x4C56545F534
 // EuRoC pre-step (k_rectify.hip): the maps of one camera.  Stand-alone (lvt_amd_rectify[_device]) or attached to a tracker, whose feature stage then
 // starts with k_rectify_frames (lvt_amd_set_rectifiers)
 struct Rectifier {
-    int w = 0, h = 0, pitch = 0;
+    int w = 0, h = 0, pitch = 0;                 // the DESTINATION (the maps' size) and the pitch of d_dst
+    int sw = 0, sh = 0;                          // the SOURCE: the raw image, lens.width x lens.height
+    lvt_amd_lens lens = {};                      // the record it was made from (lvt_amd_rectifier_get_info)
     int device = 0;                              // the HIP device the maps live on
     float *d_map1 = nullptr, *d_map2 = nullptr;
     int2 *d_fix = nullptr;                       // both maps interleaved, 1/32-px fixed point (k_rectify_fix): what k_rectify_frames reads
@@ -268,7 +270,7 @@ struct Context {
         FrameArgs f{};
         const uint8_t *src[2] = {nullptr, nullptr};
         uint8_t *dst[2] = {nullptr, nullptr};
-        int row_bytes = 0, pitch = 0;  // the pulled planes: bytes per row (n_cols, times bpp on a colour handle) and their pitch
+        int row_bytes = 0, rows = 0, pitch = 0;  // the pulled planes: bytes per row (n_cols, times bpp on a colour handle), rows and their pitch
     } pend;
     NextPull next_pull{};   // what this enqueue_frame's k_cells pulls (src[0] == nullptr: nothing)
     bool fuse_pull = true;  // LVT_AMD_FUSED_PULL=0: every frame pulls its own images at the head of its feature stage
@@ -283,11 +285,25 @@ struct Context {
     std::vector<uint8_t *> d_rect;     // [B][NPAR][2] rectified planes, each sequence's own pitch
     int n_rect = 0;                    // sequences with rectifiers
     bool has_rect(int s) const { return n_rect > 0 && rect[2 * (size_t)s] != nullptr; }
+    // THE FRAME'S SIZE of sequence s: what every stereo entry point takes.  The sequence's own img_width x img_height, or, with rectifiers attached, their
+    // SOURCE size (both eyes' are equal: set_rectifiers) -- the raw image need not have the tracker's size ("LENS MODELS", include/lvt_amd_ext.h).  Everything
+    // allocated or sized by the frame's bytes follows it (staging, the host entry points' planes, the colour and converted planes); everything behind the
+    // rectified plane stays at the sequence's size.  `resized`: the two differ -- only then does anything here allocate or launch differently.
+    int frame_W(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sw : seq_prm(s).W; }
+    int frame_H(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sh : seq_prm(s).H; }
+    bool resized(int s) const { return has_rect(s) && (frame_W(s) != seq_prm(s).W || frame_H(s) != seq_prm(s).H); }
+    // pitch of the context's own gray planes of sequence s at the frame's size (a resized sequence: its own; otherwise plane_pitch, as ever)
+    int frame_pitch(int s) const { return resized(s) ? (frame_W(s) + 63) / 64 * 64 : h_seqs[(size_t)s].plane_pitch; }
+    // the host entry points of a RESIZED handle pull gray raw images into these planes instead of d_img / d_img_ring (allocated when first needed, at the
+    // source's size; given back when the frame's size changes: frame_planes_release)
+    uint8_t *d_raw[NPAR][2] = {};
+    uint8_t *d_raw_ring[RING][2] = {};
     // COLOUR frames (lvt_amd_set_pixel_format / lvt_amd_batch_set_pixel_format): a sequence with a colour format takes interleaved colour images through every
     // frame-taking entry point.  As for raw frames the FrameArgs name the colour planes (the caller's, or the context's own pulled ones), and enqueue_frame puts
     // ONE k_gray_frames launch at the head of the feature stage -- ahead of the rectify block -- that writes the sequence's own gray planes and points the frame at them.
     std::vector<int> pixfmt;           // [B] LVT_AMD_PIX_* (empty until the first colour set: every sequence gray)
-    std::vector<uint8_t *> d_gray;     // [B][NPAR][2] converted planes, each sequence's own pitch (an RGB-D sequence: eye 0 only)
+    std::vector<uint8_t *> d_gray;     // [B][NPAR][2] converted planes, each sequence's frame_pitch (an RGB-D sequence: eye 0 only)
+    std::vector<size_t> gray_bytes;    // [B] bytes each of the sequence's converted planes holds (0: none yet)
     int n_colour = 0;                  // sequences with a colour format
     bool ring_converted[RING] = {};    // per un-collected / last frame: sequence 0's image went through k_gray_frames (what lvt_amd_get_plane(.., 3, ..) may read back)
     int fmt_of(int s) const { return n_colour > 0 ? pixfmt[(size_t)s] : PIX_GRAY8; }
@@ -296,7 +312,7 @@ struct Context {
     // 4 bytes per pixel): per feature buffer for the synchronous calls, per RING slot for the asynchronous ones
     uint8_t *d_col[NPAR][2] = {};
     uint8_t *d_col_ring[RING][2] = {};
-    int colour_pitch() const { return (prm.W * bpp_of(0) + 63) / 64 * 64; }
+    int colour_pitch() const { return (frame_W(0) * bpp_of(0) + 63) / 64 * 64; }
     // UNREGISTERED DEPTH (lvt_amd_set_depth_camera / lvt_amd_batch_set_depth_camera): a sequence with a depth camera takes its depth plane as the sensor
     // delivers it -- the camera's size, either format -- through every RGB-D entry point.  As for colour frames the FrameArgs name the sensor's plane (the
     // caller's, or the context's own pulled one), and enqueue_frame registers it into the sequence's own fp32 plane (k_depth_clear at the head of the feature
@@ -1304,7 +1320,7 @@ static void flush_pending(Context *c, const NextPull *np = nullptr) {
     if (!c->pend.valid) return;
     Context::PendingFrame &q = c->pend;
     q.valid = false;
-    if (!q.pulled) hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, q.src[0], q.src[1], q.dst[0], q.dst[1], q.row_bytes, c->prm.H, q.pitch);
+    if (!q.pulled) hipLaunchKernelGGL(k_stage_in, dim3(128, 2), dim3(256), 0, c->stream_f, q.src[0], q.src[1], q.dst[0], q.dst[1], q.row_bytes, q.rows, q.pitch);
     frame_args(c, next_slot(c)) = q.f;
     if (np) c->next_pull = *np, c->fused_pulls++;
     enqueue_frame(c);
@@ -1371,7 +1387,8 @@ static void track_sync(Context *c, double R[3][3], double t[3]) {
     if (!wait_pose_or_frame(c, R, t)) result_out(c, 0, R, t);
 }
 
-static bool size_ok(Context *c, int rows, int cols) { return rows == c->prm.H && cols == c->prm.W; }
+// (the frame's size: the handle's own, or its rectifiers' source size -- Context::frame_W)
+static bool size_ok(Context *c, int rows, int cols) { return rows == c->frame_H(0) && cols == c->frame_W(0); }
 // pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
 // byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes) and the gray frame of an
 // EQUALISED sequence by k_clahe_lut / k_clahe_apply
@@ -1591,6 +1608,15 @@ static void stage_release(Context *c) {  // (no frame in flight: nothing reads t
                 (void)hipHostFree(st[i].h);
                 st[i] = HostStage{};
             }
+}
+// The frame's size of sequence 0 changed (rectifiers of another source size attached or detached; no frame in flight): everything of the host entry points
+// that was sized by it goes back and is reserved again, at the new size, by the next frame -- the staging, the colour planes, the raw planes.
+static void frame_planes_release(Context *c) {
+    stage_release(c);
+    for (int i = 0; i < NPAR; i++)
+        for (int e = 0; e < 2; e++) c->dfree(c->d_col[i][e]), c->dfree(c->d_raw[i][e]), c->d_col[i][e] = c->d_raw[i][e] = nullptr;
+    for (int i = 0; i < RING; i++)
+        for (int e = 0; e < 2; e++) c->dfree(c->d_col_ring[i][e]), c->dfree(c->d_raw_ring[i][e]), c->d_col_ring[i][e] = c->d_raw_ring[i][e] = nullptr;
 }
 // a host plane as the device reads it: its view (device_view) when it is page-locked, otherwise its copy at offset `off` of the staging buffer; counted either way
 static const uint8_t *host_plane(Context *c, const uint8_t *view, const void *src, size_t bytes, const HostStage &st, size_t off) {
@@ -1917,11 +1943,11 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
         for (int s = 0; s < c->B; s++) {
             if (!d_left[s]) continue;
             present++;
-            const Params &q = c->seq_prm(s);
-            if (!d_right[s] || n_rows[s] != q.H || n_cols[s] != q.W || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
+            const int fW = c->frame_W(s), fH = c->frame_H(s);  // (a sequence with rectifiers: their source's size)
+            if (!d_right[s] || n_rows[s] != fH || n_cols[s] != fW || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
                 std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], q.W, q.H, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s)) ? "at least the width" : "a multiple of 16");
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], fW, fH, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s)) ? "at least the width" : "a multiple of 16");
                 return refuse(h, who, buf);
             }
         }
@@ -1948,8 +1974,12 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
             return;
         }
         bool pitch_ok = true;  // (one pitch for the whole step: it must suit the raw and the rectified sequences alike)
-        for (int s = 0; s < c->B; s++) pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols);
-        if (!size_ok(c, n_rows, n_cols) || !pitch_ok) {
+        bool sizes_ok = true;  // (... and one size: a sequence whose rectifiers have another source size than the rest needs the mixed call)
+        for (int s = 0; s < c->B; s++) {
+            pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols);
+            sizes_ok = sizes_ok && n_rows == c->frame_H(s) && n_cols == c->frame_W(s);
+        }
+        if (!sizes_ok || !pitch_ok) {
             refuse(h, who, "image size / pitch mismatch");
             return;
         }
@@ -2035,7 +2065,12 @@ LVT_API void lvt_amd_track_device(lvt_handle h, const void *d_left, const void *
 // the context's own colour planes (Context::d_col / d_col_ring), allocated when first needed and sized for 4 bytes per pixel: the format may change later
 static void colour_planes(Context *c, uint8_t *(&d)[2], int eyes) {
     for (int e = 0; e < eyes; e++)
-        if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)((c->prm.W * 4 + 63) / 64 * 64) * c->prm.H + 64);
+        if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)((c->frame_W(0) * 4 + 63) / 64 * 64) * c->frame_H(0) + 64);
+}
+// the context's own raw planes of a RESIZED handle (Context::d_raw / d_raw_ring), allocated when first needed at the source's size
+static void raw_planes(Context *c, uint8_t *(&d)[2]) {
+    for (int e = 0; e < 2; e++)
+        if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)c->frame_pitch(0) * c->frame_H(0) + 64);
 }
 // the context's own depth planes of the synchronous host calls (Context::d_depth) hold dpix pixels: allocated at creation for the image's size, again when a
 // depth camera with a larger plane has been set (no frame is in flight then)
@@ -2064,9 +2099,11 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     // a COLOUR handle: the image is a byte image n_cols * bpp wide; it is pulled into the context's colour planes and enqueue_frame converts it from there
     const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp;
+    const bool raw = bpp == 1 && c->resized(0);  // (gray raw frames of another size than the tracker's: planes of their own)
     if (bpp > 1) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
-    uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : c->d_img[par];
-    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
+    if (raw) raw_planes(c, c->d_raw[par]);
+    uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : raw ? c->d_raw[par] : c->d_img[par];
+    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
     // (a handle with a depth camera: the depth plane is the sensor's, the camera's size -- staged, pulled and handed on unchanged)
     const size_t dpix = rgbd ? c->depth_px() : 0;
     const int dcols = c->depth_cols();
@@ -2134,11 +2171,13 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     // (a COLOUR handle: byte images n_cols * bpp wide into the context's colour planes, as in upload_and_track; the fused pull carries them like gray ones)
     const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp, plane = (size_t)c->pitch * c->prm.H;
+    const bool raw = bpp == 1 && c->resized(0);  // (as in upload_and_track)
     if (bpp > 1) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
-    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->pitch;
+    if (raw) raw_planes(c, c->d_raw_ring[slot]);
+    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
     const size_t dpix = rgbd ? c->depth_px() : 0;  // (a handle with a depth camera: the sensor's plane, the camera's size)
     const int dcols = c->depth_cols();
-    if (!c->d_img_ring[0][0]) {  // first asynchronous host-buffer call
+    if (!raw && !c->d_img_ring[0][0]) {  // first asynchronous host-buffer call
         for (int r = 0; r < RING; r++)
             for (int e = 0; e < (rgbd ? 1 : 2); e++) c->d_img_ring[r][e] = c->dalloc<uint8_t>(plane + 64);
     }
@@ -2154,7 +2193,8 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     HostStage &stg = c->stage_ring[slot];
     if (!v0 || !v1) stage_reserve(c, stg, nbytes, dpix);
     hipStream_t sp = c->stream_f;
-    uint8_t *d0 = (bpp > 1) ? c->d_col_ring[slot][0] : c->d_img_ring[slot][0], *d1 = (bpp > 1) ? c->d_col_ring[slot][1] : c->d_img_ring[slot][1];
+    uint8_t *const *dring = (bpp > 1) ? c->d_col_ring[slot] : raw ? c->d_raw_ring[slot] : c->d_img_ring[slot];
+    uint8_t *d0 = dring[0], *d1 = dring[1];
     const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0);
     if (!rgbd) {
         const uint8_t *s1 = host_plane(c, v1, second, nbytes, stg, stg.second);
@@ -2167,7 +2207,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
         Context::PendingFrame &q = c->pend;
         q.valid = true, q.pulled = carried;
         q.src[0] = s0, q.src[1] = s1, q.dst[0] = d0, q.dst[1] = d1;
-        q.row_bytes = row_bytes, q.pitch = ipitch;
+        q.row_bytes = row_bytes, q.rows = n_rows, q.pitch = ipitch;
         q.f = stereo_args(d0, d1, ipitch);
         c->async_frames++;
         if (!c->fuse_pull) flush_pending(c);
@@ -2730,6 +2770,13 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             } else if (what == 3) {  // the converted gray image of the last (colour) frame, before rectification
                 if (c->fmt_of(0) == PIX_GRAY8 || !c->ring_converted[c->last_slot]) return 0;
                 src = c->d_gray[(size_t)c->last_par * 2 + (c->sensor == 1 ? e : 0)], esz = 1;
+                if (c->resized(0)) {  // (converted BEFORE the remap: the raw frame's size, its own pitch)
+                    const size_t gbytes = (size_t)c->frame_pitch(0) * c->frame_H(0);
+                    if ((size_t)cap_bytes < gbytes) return -1;
+                    HIPCHK(c, hipMemcpy(dst, src, gbytes, hipMemcpyDeviceToHost));
+                    if (pitch_out) *pitch_out = c->frame_pitch(0);
+                    return (int)gbytes;
+                }
             } else {  // the registered depth plane of the last frame (fp32, pitch words per row)
                 if (!c->has_depth_cam(0) || !c->ring_registered[c->last_slot]) return 0;
                 src = c->d_reg[(size_t)c->last_par], esz = sizeof(float);
@@ -2749,41 +2796,54 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
 // _correspond: lvt_stage_entries.h)
 
 // ---- EuRoC pre-step: rectification -------------------------------------------------------------------------------------
-LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9], const double Pnew[9], int width,
-                                                   int height) {
-    if (!K || !D || !R || !Pnew || width <= 0 || height <= 0) return nullptr;
+// iR = (Pnew * R)^-1: 3x3 product in k-ascending order, closed-form inverse (cv::gemm / cv::invert for 3x3 doubles)
+static void inverse_PR(const double Pnew[9], const double R[9], double out[9]) {
+    double AR[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double s = 0;
+            for (int k = 0; k < 3; k++) s += Pnew[3 * i + k] * R[3 * k + j];
+            AR[3 * i + j] = s;
+        }
+    const double *S = AR;
+    double ir[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+    if (d != 0.) {
+        d = 1. / d;
+        ir[0] = (S[4] * S[8] - S[5] * S[7]) * d, ir[1] = (S[2] * S[7] - S[1] * S[8]) * d, ir[2] = (S[1] * S[5] - S[2] * S[4]) * d;
+        ir[3] = (S[5] * S[6] - S[3] * S[8]) * d, ir[4] = (S[0] * S[8] - S[2] * S[6]) * d, ir[5] = (S[2] * S[3] - S[0] * S[5]) * d;
+        ir[6] = (S[3] * S[7] - S[4] * S[6]) * d, ir[7] = (S[1] * S[6] - S[0] * S[7]) * d, ir[8] = (S[0] * S[4] - S[1] * S[3]) * d;
+    }
+    for (int k = 0; k < 9; k++) out[k] = ir[k];
+}
+// a rectifier of a sw x sh source and a dw x dh destination with everything allocated and no map built yet; nullptr: no device, or no memory
+static Rectifier *rectifier_alloc(int sw, int sh, int dw, int dh) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return nullptr;  // no CPU fallback
     Rectifier *r = new (std::nothrow) Rectifier;
     if (!r) return nullptr;
-    r->w = width, r->h = height, r->pitch = ((width + 63) / 64) * 64;
-    const size_t n = (size_t)width * height;
+    r->w = dw, r->h = dh, r->pitch = ((dw + 63) / 64) * 64, r->sw = sw, r->sh = sh;
+    const size_t n = (size_t)dw * dh;
     if (hipGetDevice(&r->device) != hipSuccess || hipMalloc((void **)&r->d_fix, n * sizeof(int2)) != hipSuccess ||
         hipMalloc((void **)&r->d_map1, n * 4) != hipSuccess || hipMalloc((void **)&r->d_map2, n * 4) != hipSuccess ||
-        hipMalloc((void **)&r->d_src, n) != hipSuccess || hipMalloc((void **)&r->d_dst, (size_t)r->pitch * height) != hipSuccess) {
+        hipMalloc((void **)&r->d_src, (size_t)sw * sh) != hipSuccess || hipMalloc((void **)&r->d_dst, (size_t)r->pitch * dh) != hipSuccess) {
         lvt_amd_rectifier_destroy(r);
         return nullptr;
     }
+    return r;
+}
+
+LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const double D[5], const double R[9], const double Pnew[9], int width,
+                                                   int height) {
+    if (!K || !D || !R || !Pnew || width <= 0 || height <= 0) return nullptr;
+    Rectifier *r = rectifier_alloc(width, height, width, height);
+    if (!r) return nullptr;
+    const size_t n = (size_t)width * height;
+    r->lens.model = LVT_AMD_LENS_RADTAN, r->lens.width = width, r->lens.height = height;
+    for (int k = 0; k < 9; k++) r->lens.K[k] = K[k];
+    for (int k = 0; k < 5; k++) r->lens.D[k] = D[k];
     RectifyArgs a;
-    {   // iR = (Pnew * R)^-1: 3x3 product in k-ascending order, closed-form inverse (cv::gemm / cv::invert for 3x3 doubles)
-        double AR[9];
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) {
-                double s = 0;
-                for (int k = 0; k < 3; k++) s += Pnew[3 * i + k] * R[3 * k + j];
-                AR[3 * i + j] = s;
-            }
-        const double *S = AR;
-        double ir[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-        if (d != 0.) {
-            d = 1. / d;
-            ir[0] = (S[4] * S[8] - S[5] * S[7]) * d, ir[1] = (S[2] * S[7] - S[1] * S[8]) * d, ir[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-            ir[3] = (S[5] * S[6] - S[3] * S[8]) * d, ir[4] = (S[0] * S[8] - S[2] * S[6]) * d, ir[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-            ir[6] = (S[3] * S[7] - S[4] * S[6]) * d, ir[7] = (S[1] * S[6] - S[0] * S[7]) * d, ir[8] = (S[0] * S[4] - S[1] * S[3]) * d;
-        }
-        for (int k = 0; k < 9; k++) a.ir[k] = ir[k];
-    }
+    inverse_PR(Pnew, R, a.ir);
     a.fx = K[0], a.fy = K[4], a.u0 = K[2], a.v0 = K[5];
     a.k1 = D[0], a.k2 = D[1], a.p1 = D[2], a.p2 = D[3], a.k3 = D[4];
     a.w = width, a.h = height;
@@ -2796,6 +2856,60 @@ LVT_API lvt_amd_rectifier lvt_amd_rectifier_create(const double K[9], const doub
     return r;
 }
 
+// "" when the arguments pass; the checks in the contract's order ("LENS MODELS", include/lvt_amd_ext.h)
+static std::string lens_check(const lvt_amd_lens *lens, const double R[9], const double Pnew[9], int dw, int dh) {
+    if (!lens || !R || !Pnew) return "NULL argument";
+    if (lens->model != LVT_AMD_LENS_RADTAN && lens->model != LVT_AMD_LENS_FISHEYE) return "unknown lens model " + std::to_string(lens->model);
+    if (lens->width < 1 || lens->width > 8192 || lens->height < 1 || lens->height > 8192)
+        return "a source of " + std::to_string(lens->width) + " x " + std::to_string(lens->height) + " pixels (1 ... 8192 each way)";
+    if (dw < 1 || dw > 8192 || dh < 1 || dh > 8192) return "a destination of " + std::to_string(dw) + " x " + std::to_string(dh) + " pixels (1 ... 8192 each way)";
+    bool finite = true;
+    for (double v : lens->K) finite = finite && std::isfinite(v);
+    for (int k = 0; k < (lens->model == LVT_AMD_LENS_FISHEYE ? 4 : 12); k++) finite = finite && std::isfinite(lens->D[k]);  // (FISHEYE: D[4 ...] is not read)
+    if (!finite) return "a lens with a non-finite field of K or D";
+    for (int k = 0; k < 9; k++) finite = finite && std::isfinite(R[k]) && std::isfinite(Pnew[k]);
+    if (!finite) return "a non-finite field of R or Pnew";
+    return "";
+}
+LVT_API lvt_amd_rectifier lvt_amd_rectifier_create_lens(const lvt_amd_lens *lens, const double R[9], const double Pnew[9], int dst_width, int dst_height) {
+    static const char *who = "lvt_amd_rectifier_create_lens";
+    const std::string why = lens_check(lens, R, Pnew, dst_width, dst_height);
+    if (!why.empty()) {
+        refuse_call(who, why + " (nothing was created)");
+        return nullptr;
+    }
+    Rectifier *r = rectifier_alloc(lens->width, lens->height, dst_width, dst_height);
+    if (!r) {
+        refuse_call(who, "no HIP device, or no memory for the maps (nothing was created)");
+        return nullptr;
+    }
+    r->lens = *lens;
+    if (lens->model == LVT_AMD_LENS_FISHEYE)
+        for (int k = 4; k < 12; k++) r->lens.D[k] = 0;  // (ignored: the record reads back as what was used)
+    LensArgs a;
+    inverse_PR(Pnew, R, a.ir);
+    a.fx = lens->K[0], a.fy = lens->K[4], a.u0 = lens->K[2], a.v0 = lens->K[5];
+    for (int k = 0; k < 12; k++) a.d[k] = r->lens.D[k];
+    a.w = dst_width, a.h = dst_height;
+    const size_t n = (size_t)dst_width * dst_height;
+    if (lens->model == LVT_AMD_LENS_FISHEYE) hipLaunchKernelGGL(k_rectify_map_fisheye, dim3((dst_height + 63) / 64), dim3(64), 0, 0, a, r->d_map1, r->d_map2);
+    else hipLaunchKernelGGL(k_rectify_map_radtan, dim3((dst_height + 63) / 64), dim3(64), 0, 0, a, r->d_map1, r->d_map2);
+    hipLaunchKernelGGL(k_rectify_fix, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, r->d_map1, r->d_map2, r->d_fix, n);
+    if (hipDeviceSynchronize() != hipSuccess) {
+        lvt_amd_rectifier_destroy(r);
+        refuse_call(who, "building the maps failed on the device (nothing was created)");
+        return nullptr;
+    }
+    return r;
+}
+LVT_API int lvt_amd_rectifier_get_info(lvt_amd_rectifier h, lvt_amd_lens *lens_out, int dst_size[2]) {
+    Rectifier *r = static_cast<Rectifier *>(h);
+    if (!r || !lens_out || !dst_size) return -1;
+    *lens_out = r->lens;
+    dst_size[0] = r->w, dst_size[1] = r->h;
+    return 0;
+}
+
 LVT_API void lvt_amd_rectifier_destroy(lvt_amd_rectifier h) {
     Rectifier *r = static_cast<Rectifier *>(h);
     if (!r) return;
@@ -2805,18 +2919,18 @@ LVT_API void lvt_amd_rectifier_destroy(lvt_amd_rectifier h) {
 
 LVT_API int lvt_amd_rectify_device(lvt_amd_rectifier h, const void *d_src, int src_pitch, void *d_dst, int dst_pitch, void *hip_stream) {
     Rectifier *r = static_cast<Rectifier *>(h);
-    if (!r || !d_src || !d_dst || src_pitch < r->w || dst_pitch < r->w || (dst_pitch & 3)) return -1;
+    if (!r || !d_src || !d_dst || src_pitch < r->sw || dst_pitch < r->w || (dst_pitch & 3)) return -1;
     hipLaunchKernelGGL(k_rectify, dim3((dst_pitch / 4 + 255) / 256, r->h), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
-                       static_cast<const uint8_t *>(d_src), r->w, r->h, src_pitch, r->d_map1, r->d_map2, r->w, r->h, static_cast<uint8_t *>(d_dst), dst_pitch);
+                       static_cast<const uint8_t *>(d_src), r->sw, r->sh, src_pitch, r->d_map1, r->d_map2, r->w, r->h, static_cast<uint8_t *>(d_dst), dst_pitch);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 LVT_API int lvt_amd_rectify(lvt_amd_rectifier h, const unsigned char *src, unsigned char *dst) {
     Rectifier *r = static_cast<Rectifier *>(h);
     if (!r || !src || !dst) return -1;
-    const size_t n = (size_t)r->w * r->h;
+    const size_t n = (size_t)r->sw * r->sh;  // (the source is the lens's size, tightly packed)
     if (hipMemcpy(r->d_src, src, n, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (lvt_amd_rectify_device(r, r->d_src, r->w, r->d_dst, r->pitch, nullptr) != 0) return -1;
+    if (lvt_amd_rectify_device(r, r->d_src, r->sw, r->d_dst, r->pitch, nullptr) != 0) return -1;
     return hipMemcpy2D(dst, (size_t)r->w, r->d_dst, (size_t)r->pitch, (size_t)r->w, (size_t)r->h, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 
