@@ -67,14 +67,14 @@ bool read_calib(const std::string &path, double K[9], double &baseline) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        std::cout << "Usage ./lvt_kitti sequences_dir seq_number [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt]" << std::endl;
+        std::cout << "Usage ./lvt_kitti sequences_dir seq_number [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--reduce F]" << std::endl;
         return -1;
     }
     char seq_cstr[16];
     std::snprintf(seq_cstr, sizeof seq_cstr, "%02d", std::atoi(argv[2]));
     const std::string seq_str(seq_cstr), dir_prefix = std::string(argv[1]) + "/" + seq_str;
     std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name, mask_names, labels_dir, drop_list;
-    int dilate = 0;
+    int dilate = 0, reduce = 1;
     long max_frames = -1;
     for (int i = 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -87,6 +87,7 @@ int main(int argc, char **argv) {
         else if (k == "--labels") labels_dir = argv[i + 1];
         else if (k == "--drop") drop_list = argv[i + 1];
         else if (k == "--dilate") dilate = std::atoi(argv[i + 1]);
+        else if (k == "--reduce") reduce = std::atoi(argv[i + 1]);
     }
     double K[9], baseline = 0;
     if (!read_calib(calib, K, baseline)) {
@@ -109,12 +110,26 @@ int main(int argc, char **argv) {
         std::cout << "failed to get image sequences (" << err << ")" << std::endl;
         return -1;
     }
+    // --reduce F: the PNGs are F times the size the tracker runs at.  The tracker is created at W / F x H / F with the calibration of the REDUCED image (reduced
+    // pixel x covers source columns [F x, F x + F): f' = f / F, c' = (c + 0.5) / F - 0.5, in double) and is handed the decoded full-size frames.
+    if (reduce < 1 || reduce > 8 || left.w / reduce < 1 || left.h / reduce < 1) {
+        std::cout << "--reduce takes a factor 1 ... 8 that leaves at least one pixel each way" << std::endl;
+        return -1;
+    }
+    const int frame_w = left.w, frame_h = left.h;
+    const double F = (double)reduce;
+    if (reduce > 1) K[0] /= F, K[4] /= F, K[2] = (K[2] + 0.5) / F - 0.5, K[5] = (K[5] + 0.5) / F - 0.5;
     params.fx = (float)K[0], params.fy = (float)K[4], params.cx = (float)K[2], params.cy = (float)K[5];
     params.baseline = (float)baseline;
-    params.img_width = left.w, params.img_height = left.h;
+    params.img_width = frame_w / reduce, params.img_height = frame_h / reduce;
     lvt_system *vo = lvt_system::create(params, lvt_system::eSensor_STEREO);
     if (!vo) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;
+        return -1;
+    }
+    if (reduce > 1 && !vo->set_reduction(reduce, frame_w, frame_h)) {
+        std::cout << "failed to set the reduction: " << vo->last_error() << std::endl;
+        lvt_system::destroy(vo);
         return -1;
     }
     std::ofstream cov_file;
@@ -138,8 +153,9 @@ int main(int argc, char **argv) {
                 lvt_system::destroy(vo);
                 return -1;
             }
-            if (mask[e].w != left.w || mask[e].h != left.h) {
-                std::cout << "the mask " << names[e] << " is " << mask[e].w << " x " << mask[e].h << ", the frames are " << left.w << " x " << left.h << std::endl;
+            if (mask[e].w != params.img_width || mask[e].h != params.img_height) {  // (the detector's grid: with --reduce the reduced image's)
+                std::cout << "the mask " << names[e] << " is " << mask[e].w << " x " << mask[e].h << ", the frames are " << params.img_width << " x " << params.img_height
+                          << (reduce > 1 ? " behind the reduction" : "") << std::endl;
                 lvt_system::destroy(vo);
                 return -1;
             }
@@ -195,7 +211,7 @@ int main(int argc, char **argv) {
     Gray nleft, nright;
     bool have = true;
     for (long i = 0; i < frame_count && have; i++) {
-        if (left.w != params.img_width || left.h != params.img_height || right.w != left.w || right.h != left.h) {
+        if (left.w != frame_w || left.h != frame_h || right.w != left.w || right.h != left.h) {
             std::cout << "frame " << i << ": image size changed" << std::endl;
             break;
         }

@@ -459,7 +459,61 @@ LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format);                 
 LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format);  /* 0 / -1 */
 LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq);                    /* format, -1: bad handle / seq */
 
-/* UNREGISTERED DEPTH: depth registration inside the tracker's feature stage.  Without a depth camera the depth plane of an RGB-D frame is taken as registered
+/* FRAME REDUCTION: large frames, averaged down by an integer factor inside the tracker's feature stage.  The tracker's capacities are shaped for KITTI- and
+ * VGA-sized images; cameras deliver 1080p to 4K.  A reduction is a property of the handle, or of one sequence of a batch, like the pixel format; the record is
+ * copied.  It is not state: lvt_amd_reset, lvt_amd_batch_reset and snapshots neither hold nor change it.  Once it is set, EVERY frame-taking call on that
+ * handle or sequence, of either sensor, takes frames of the record's width x height, and one launch at the head of the feature stage (k_reduce_frames: every
+ * such image of the step) averages them into planes the tracker owns; the frame is tracked from those.  A handle or sequence that never sets a record
+ * allocates and launches exactly what it did, and factor = 1 returns a handle to that path and releases what was sized by the large frame.
+ *  THE DEFINITION (tests/reduce_util.py restates it in numpy; the checks hold the kernel to it byte for byte).
+ *   - bW x bH is the BASE size: the rectifiers' source size where a pair is attached, else the sequence's img_width x img_height.
+ *   - a record is valid when factor is 1 ... 8 and width, height are 1 ... 16384; for factor f >= 2 also width / f == bW and height / f == bH (integer
+ *     division): the frame may carry up to f - 1 trailing columns and rows, which are never read.
+ *   - for a gray frame g and 0 <= x < bW, 0 <= y < bH:
+ *         S = sum over dy, dx in [0, f) of g[f y + dy][f x + dx];      out[y][x] = (S + (f f >> 1)) / (f f)        (integer division; S <= 255 f f)
+ *   - a colour frame is converted first, per pixel, by the formula of COLOUR frames above; the gray image is then averaged.
+ *   - ORDER in the feature stage: convert, REDUCE, remap, equalise.  Everything behind the reduced plane stays at the sizes it has without a reduction: the
+ *     rectified planes, equalisation, masks, label masks, the detector and everything downstream.
+ *   - GEOMETRY.  Reduced pixel x covers source columns [f x, f x + f), so with pixel centres at integers a pinhole of the frame becomes
+ *         fx' = fx / f,   cx' = (cx + 0.5) / f - 0.5,   fy' = fy / f,   cy' = (cy + 0.5) / f - 0.5;
+ *     distortion coefficients (functions of the normalised ray) and the baseline in metres are unchanged.  The sequence's lvt_amd_params are those of the
+ *     REDUCED image: the caller computes them (lvt_amd_lens_reduced does, for a lens record).
+ *   - the gain over picking pixels has been measured on synthetic texture only (profiles/frame_reduction.md); it has not been measured on real footage.
+ *  - THE FRAME'S SIZE is the record's width x height at every entry point; anything else is refused like any other wrong size, the tracker's own included.
+ *    What is sized by the frame's bytes follows it (the staging buffers, the planes the host entry points pull into, the colour and the converted planes).
+ *  - host buffers are tightly packed at the frame's size.  Device planes are read in place: any base address, any pitch >= width * bpp (where base and pitch
+ *    are multiples of 4 the kernel loads 8- and 16-byte vectors, otherwise bytes: the same result).
+ *  - RECTIFIERS first, then the reduction: the reduced image is the rectifiers' source (make them from lvt_amd_lens_reduced's record).  With a reduction in
+ *    force lvt_amd_set_rectifiers / lvt_amd_batch_set_rectifiers, attach or detach, are refused: clear the reduction first.
+ *  - lvt_track_with_external_corners on such a handle is refused (nothing is tracked): the call cannot know which image the corners are in.
+ *  - RGB-D: a frame on a sequence with a reduction and WITHOUT a depth camera is refused before anything is enqueued -- the depth plane has no size of its own.
+ *    A depth plane registered to the large colour image enters through lvt_amd_set_depth_camera with identity extrinsics and the large image's pinhole.
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error, every sentence ending "(nothing was changed)"), in this order: a pooled or automatic seat;
+ *    the batch call on a handle that is not a batch and the other way round; seq out of range; a bad record (NULL, then factor, width, height, then the
+ *    size that does not reduce to the base -- the sentence names both); a handle with frames in flight.  A successful set counts as use of an lvt_create handle.
+ *  - lvt_amd_get_reduction: 1 = a reduction is in force (copied to *out), 0 = none, -1 = bad handle / seq.
+ *  - lvt_amd_get_plane(h, eye, 9, ...) reads the reduced plane of the last frame back (u8, bH rows, its pitch in *pitch_out, the padding columns zero; 0 bytes
+ *    without a reduction); what = 3 (the converted gray of a colour handle) then has the frame's rows and a pitch of its own.  lvt_amd_profile_read reports the
+ *    launch as "k_reduce_frames" (a handle with a reduction only).
+ *  - lvt_amd_reduce_device: the stage alone on caller planes (device pointers, u8).  d_src: src_h rows of src_pitch >= src_w bytes, any address; d_dst:
+ *    src_h / factor rows of dst_pitch bytes, dst_pitch >= src_w / factor, dst_pitch % 4 == 0, 4-byte aligned; factor 2 ... 8, sides factor ... 16384.  Every
+ *    byte of the destination rows is written, the columns from src_w / factor on as zero, nothing else.  Null stream; returns when the plane is written.
+ *    *launches (may be NULL): kernels launched.  0, or -1 (*launches = 0, nothing launched, the sentence in lvt_amd_last_error(NULL)).
+ *  - lvt_amd_lens_reduced: host only, no device.  *out = the lens of the reduced image by the GEOMETRY rule, in double (K[0], K[4] divided; K[2], K[5]
+ *    shifted; width, height by integer division; model and D copied).  factor 1 ... 8; -1 for a NULL argument, another factor, or a side that reduces to 0.
+ *  - not here: fusing the colour conversion into the reduction; a non-integer factor. */
+typedef struct lvt_amd_reduction {
+    int factor;           /* 1 = off; 2 ... 8 */
+    int width, height;    /* the FRAME's size in pixels, as every entry point will then take it */
+} lvt_amd_reduction;
+LVT_API int lvt_amd_set_reduction(lvt_handle h, const lvt_amd_reduction *r);                        /* 0 / -1 */
+LVT_API int lvt_amd_batch_set_reduction(lvt_handle h, int seq, const lvt_amd_reduction *r);
+LVT_API int lvt_amd_get_reduction(lvt_handle h, int seq, lvt_amd_reduction *out);                   /* 1 set, 0 none, -1 bad handle / seq */
+LVT_API int lvt_amd_reduce_device(const void *d_src, int src_w, int src_h, int src_pitch, int factor,
+                                  void *d_dst, int dst_pitch, int *launches);                       /* the stage alone, caller planes in HBM */
+LVT_API int lvt_amd_lens_reduced(const lvt_amd_lens *in, int factor, lvt_amd_lens *out);            /* host only, no device */
+
+/* UNREGISTERED DEPTH: depth registration inside the tracker's feature stage. Without a depth camera the depth plane of an RGB-D frame is taken as registered
  * to the gray image (TUM's files, sensors that register in hardware).  A depth camera says that the plane is delivered in ANOTHER camera -- its own size,
  * its own pinhole, a rigid offset from the colour camera (RealSense D4xx: the left infrared camera; Azure Kinect, Orbbec: a second camera a few centimetres
  * away).  It is a property of the handle, or of one sequence of a batch, like the pixel format; the record is copied.  It is not state: it is neither in

@@ -329,6 +329,14 @@ class lvt_system {
     /* ADDITIVE: CLAHE contrast equalisation of the gray plane the detector reads (lvt_amd_equalisation, include/lvt_amd_ext.h, DIM frames): from now on every
      * frame is equalised by two launches at the head of its feature stage; nullptr: plain frames again.  false: refused (last_error() says why), nothing changed. */
     bool set_equalisation(const lvt_amd_equalisation *cfg) { return lvt_amd_set_equalisation(m_handle, cfg) == 0; }
+    /* ADDITIVE: large frames (lvt_amd_reduction, include/lvt_amd_ext.h, FRAME REDUCTION): from now on every image handed to this system is width x height
+     * pixels and is averaged down by `factor` (2 ... 8) by one launch at the head of its feature stage; width / factor x height / factor must be the system's
+     * own image size, whose parameters are those of the REDUCED image.  factor 1: frames of the system's own size again.  false: refused (last_error() says
+     * why), nothing changed. */
+    bool set_reduction(int factor, int width, int height) {
+        const lvt_amd_reduction r = {factor, width, height};
+        return lvt_amd_set_reduction(m_handle, &r) == 0;
+    }
     /* ADDITIVE: feature masks (include/lvt_amd_ext.h, FEATURE MASKS): tightly packed 8-bit images of img_width x img_height on the pixel grid the detector reads,
      * a byte != 0: key points allowed.  From now on every frame loses the key points on masked pixels inside its feature stage (one launch between the gather
      * step and BRIEF).  One eye may be nullptr (no mask for it); both nullptr: no masks again.  The buffers are copied before the call returns.

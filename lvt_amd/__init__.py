@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
+    "lvt_amd_set_reduction", "lvt_amd_batch_set_reduction", "lvt_amd_get_reduction", "lvt_amd_reduce_device", "lvt_amd_lens_reduced",
     "lvt_amd_set_mask", "lvt_amd_batch_set_mask", "lvt_amd_set_mask_device", "lvt_amd_batch_set_mask_device", "lvt_amd_get_mask_stats", "lvt_amd_mask_features",
     "lvt_amd_set_label_mask", "lvt_amd_batch_set_label_mask", "lvt_amd_get_label_mask", "lvt_amd_frame_labels", "lvt_amd_frame_labels_device", "lvt_amd_build_label_mask",
     "lvt_amd_depth_guard_default", "lvt_amd_set_depth_guard", "lvt_amd_batch_set_depth_guard", "lvt_amd_get_depth_guard", "lvt_amd_get_depth_guard_stats", "lvt_amd_depth_guard_features",
@@ -227,6 +228,12 @@ def load_library():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (   # (frame reduction: likewise)
+            ("lvt_amd_set_reduction", [vp, vp]), ("lvt_amd_batch_set_reduction", [vp, C.c_int, vp]), ("lvt_amd_get_reduction", [vp, C.c_int, vp]),
+            ("lvt_amd_reduce_device", [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]), ("lvt_amd_lens_reduced", [vp, C.c_int, vp])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
     for name, argtypes in (   # (feature masks: likewise)
             ("lvt_amd_set_mask", [vp, vp, vp]), ("lvt_amd_batch_set_mask", [vp, C.c_int, vp, vp]), ("lvt_amd_set_mask_device", [vp, vp, C.c_int, vp, C.c_int]),
             ("lvt_amd_batch_set_mask_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int]), ("lvt_amd_get_mask_stats", [vp, C.c_int, vp]),
@@ -398,6 +405,44 @@ def equalisation_plan(cfg: Equalisation, width: int, height: int):
     d = dict(zip(("Wp", "Hp", "tile_w", "tile_h", "area", "clip"), (int(x) for x in out)))
     d["lut_scale"] = np.float32(scale.value)
     return d
+
+
+class Reduction(C.Structure):
+    """lvt_amd_reduction: large frames averaged down by an integer factor at the head of the feature stage (include/lvt_amd_ext.h, FRAME REDUCTION) -- factor
+    1 = off, 2 ... 8; width x height is the FRAME's size, as every entry point then takes it: width // factor x height // factor must be the sequence's base
+    size (its rectifiers' source size, else its own image size)"""
+    _fields_ = [("factor", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+    def __init__(self, factor=1, width=1, height=1):
+        super().__init__(int(factor), int(width), int(height))
+
+    def __repr__(self):
+        return f"Reduction(factor={int(self.factor)}, width={int(self.width)}, height={int(self.height)})"
+
+
+def _reduction_of(handle, seq):
+    return _record_of("lvt_amd_get_reduction", Reduction, handle, seq)
+
+
+def _reduction_arg(cfg, kw):
+    if cfg is None:
+        cfg = Reduction(**kw) if kw else Reduction(1, 1, 1)   # (None: off)
+    return cfg
+
+
+def reduce_device(d_src: int, src_w: int, src_h: int, src_pitch: int, factor: int, d_dst: int, dst_pitch: int):
+    """stage entry: the reduction alone on device planes (u8; d_src any address, src_pitch >= src_w; d_dst 4-byte aligned, dst_pitch % 4 == 0 and
+    >= src_w // factor: every byte of src_h // factor rows x dst_pitch is written, the padding columns as zero).  Returns (rc, kernels launched): (0, 1), or
+    (-1, 0) on a refusal, whose sentence is last_call_error()."""
+    n = C.c_int(-1)
+    rc = load_library().lvt_amd_reduce_device(C.c_void_p(d_src), int(src_w), int(src_h), int(src_pitch), int(factor), C.c_void_p(d_dst), int(dst_pitch), C.byref(n))
+    return rc, n.value
+
+
+def reduced_intrinsics(fx: float, fy: float, cx: float, cy: float, f: int):
+    """(fx, fy, cx, cy) of the image reduced by f: reduced pixel x covers source columns [f x, f x + f), so fx' = fx / f and cx' = (cx + 0.5) / f - 0.5"""
+    f = float(f)
+    return fx / f, fy / f, (cx + 0.5) / f - 0.5, (cy + 0.5) / f - 0.5
 
 
 def _mask_of(handle, seq, mask):
@@ -1043,6 +1088,17 @@ class LvtSystem:
         """the Equalisation that is set, or None"""
         return _equalisation_of(self._h, 0)
 
+    def set_reduction(self, cfg=None, **kw) -> int:
+        """a Reduction (or its arguments: factor=, width=, height=): every frame handed to this system from now on is (height, width) large and is averaged down
+        by `factor` by one launch at the head of the feature stage; None or factor 1: frames of the system's own size again.  0: done; -1: refused
+        (last_error())."""
+        cfg = _reduction_arg(cfg, kw)
+        return load_library().lvt_amd_set_reduction(self._h, C.byref(cfg))
+
+    def reduction(self):
+        """the Reduction in force, or None"""
+        return _reduction_of(self._h, 0)
+
     def set_mask(self, left=None, right=None) -> int:
         """feature masks, (H, W) uint8 or bool arrays on the pixel grid the detector reads, != 0: key points allowed.  Every frame handed to this system from now
         on loses the key points on masked pixels inside the feature stage (one launch between the gather step and BRIEF).  One eye may be None (no mask for
@@ -1188,7 +1244,7 @@ class LvtSystem:
         name = C.create_string_buffer(64); ms = C.c_double(0); calls = C.c_long(0)
         for slot in range(64):
             if not load_library().lvt_amd_profile_read(self._h, slot, name, 64, C.byref(ms), C.byref(calls)):
-                if slot >= 28:   # (past the last slot; the slots below it may be absent on this handle)
+                if slot >= 29:   # (past the last slot; the slots below it may be absent on this handle)
                     break
                 continue
             out.append((name.value.decode(), ms.value, calls.value))
@@ -1322,6 +1378,14 @@ class LvtBatch:
 
     def equalisation(self, seq: int):
         return _equalisation_of(self._h, seq)
+
+    def set_reduction(self, seq: int, cfg=None, **kw) -> int:
+        """LvtSystem.set_reduction for sequence `seq` of the batch: its frames are large from then on, the other sequences' are not"""
+        cfg = _reduction_arg(cfg, kw)
+        return load_library().lvt_amd_batch_set_reduction(self._h, int(seq), C.byref(cfg))
+
+    def reduction(self, seq: int):
+        return _reduction_of(self._h, seq)
 
     def set_mask(self, seq: int, left=None, right=None) -> int:
         """LvtSystem.set_mask for sequence `seq` of the batch: its key points are filtered from then on, the other sequences' are not"""
@@ -1549,6 +1613,13 @@ class Lens:
 
     def _record(self) -> _LensRecord:
         return _LensRecord(self.model, self.width, self.height, (C.c_double * 9)(*self.K.reshape(-1)), (C.c_double * 12)(*self.D))
+
+    def reduced(self, f: int) -> "Lens":
+        """lvt_amd_lens_reduced: the lens of this image reduced by f (a Reduction's geometry); host code, needs the library and no GPU"""
+        rec, out = self._record(), _LensRecord()
+        if load_library().lvt_amd_lens_reduced(C.byref(rec), int(f), C.byref(out)) != 0:
+            raise ValueError(f"lvt_amd_lens_reduced refused factor {f} on a lens of {self.width} x {self.height}")
+        return Lens(out.model, out.width, out.height, list(out.K), list(out.D))
 
     def __repr__(self):
         return f"Lens(model={self.model}, width={self.width}, height={self.height}, K={self.K.tolist()}, D={self.D.tolist()})"

@@ -1,5 +1,5 @@
 // lvt_frame_props.h -- the properties a handle, or one sequence of a batch, has besides its parameters (included by lvt_host.hip): rectifiers for raw frames,
-// a pixel format for colour frames, a depth camera for unregistered depth, an equalisation record for dim frames, a depth guard and feature masks behind the
+// a pixel format for colour frames, a reduction for large frames, a depth camera for unregistered depth, an equalisation record for dim frames, a depth guard and feature masks behind the
 // gather step, label masks whose images travel with each frame, the pose-uncertainty record.
 //
 // THE CONTRACT they share ("Frame properties"): a call is checked before anything changes and refused with a reason (-1, the handle as it
@@ -198,6 +198,92 @@ static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) 
     });
 }
 
+// ---- large frames: a reduction per handle / per sequence of a batch (Context::red, k_reduce.hip) -------------------------------------------------------
+// "" when the record passes on a sequence whose base size is bW x bH: names the offending field and its limits otherwise
+static std::string reduction_check(const lvt_amd_reduction &r, int bW, int bH) {
+    if (r.factor < 1 || r.factor > REDUCE_MAX_FACTOR) return "a reduction with factor = " + std::to_string(r.factor) + " (1 ... 8)";
+    if (r.width < 1 || r.width > REDUCE_MAX_SIDE) return "a reduction with width = " + std::to_string(r.width) + " (1 ... 16384)";
+    if (r.height < 1 || r.height > REDUCE_MAX_SIDE) return "a reduction with height = " + std::to_string(r.height) + " (1 ... 16384)";
+    if (r.factor >= 2 && (r.width / r.factor != bW || r.height / r.factor != bH))
+        return "a frame of " + std::to_string(r.width) + " x " + std::to_string(r.height) + " reduced by " + std::to_string(r.factor) + " is " + std::to_string(r.width / r.factor) + " x " +
+               std::to_string(r.height / r.factor) + ", the sequence takes " + std::to_string(bW) + " x " + std::to_string(bH);
+    return "";
+}
+// one image's descriptor: a gray frame (any address, any pitch >= f w) reduced by f into the w x h plane dst
+static ReduceImg reduce_img(const uint8_t *src, int src_pitch, int f, uint8_t *dst, int dst_pitch, int w, int h) {
+    ReduceImg I{};
+    I.src = src, I.dst = dst, I.src_pitch = src_pitch, I.dst_pitch = dst_pitch, I.w = w, I.h = h, I.f = f;
+    return I;
+}
+static dim3 reduce_grid(int words, int n) { return dim3((unsigned)((words + REDUCE_THREADS - 1) / REDUCE_THREADS), (unsigned)n); }
+// Every image of every sequence that has a reduction and a frame in this step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in one
+// launch, BEHIND the conversion (a colour frame is averaged as the gray image it converts to) and AHEAD of the rectify block (the rectifiers' source is the
+// reduced image).  The reduced planes (parity `par`) were read last by the feature stage of frame enq - NPAR (k_rectify_frames, k_clahe_*, or k_score,
+// k_gather, k_brief_img: all on this stream, all enqueued before), and the source was written on this stream (a pull, k_gray_frames) or belongs to the
+// caller: stream order alone covers the hand-over, no gate.
+static void reduce_frames(Context *c, int slot, int par, int Bz) {
+    FrameArgs *fw = &frame_args(c, slot);
+    int words = 0;
+    TablePacker pk(&ReduceTable::im, [&](const ReduceTable &tab, int n, bool first) {
+        if (first) LAUNCH(29, c->stream_f, k_reduce_frames, reduce_grid(words, n), dim3(REDUCE_THREADS), 0, tab);
+        else hipLaunchKernelGGL(k_reduce_frames, reduce_grid(words, n), dim3(REDUCE_THREADS), 0, c->stream_f, tab);
+        words = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (!c->has_reduce(s) || fw[s].absent) continue;
+        const int bW = c->base_W(s), bH = c->base_H(s), dpitch = c->base_pitch(s), eyes = (c->sensor == 2) ? 1 : 2;
+        ReduceImg *im = pk.add(eyes);
+        for (int e = 0; e < eyes; e++) {
+            im[e] = reduce_img(fw[s].img[e], fw[s].img_pitch, c->red[(size_t)s].factor, c->d_red[((size_t)s * NPAR + par) * 2 + e], dpitch, bW, bH);
+            words = std::max(words, dpitch / 4 * bH);
+            fw[s].img[e] = im[e].dst;
+        }
+        if (eyes == 1) fw[s].img[1] = fw[s].img[0];
+        fw[s].img_pitch = dpitch;
+        if (s == 0) c->ring_reduced[slot] = true;
+    }
+    pk.flush();
+}
+// sequence seq's reduced planes hold an image of its base size (base_pitch x base_H): allocated at the set, again when the base has changed since, and given
+// back (on == false) when the reduction is cleared; no frame is in flight then
+static void give_red_planes(Context *c, int seq, bool on) {
+    const int eyes = c->sensor == 2 ? 1 : 2;
+    const size_t bytes = on ? (size_t)c->base_pitch(seq) * c->base_H(seq) + 64 : 0;
+    if (c->d_red.empty()) c->d_red.assign((size_t)c->B * NPAR * 2, nullptr);
+    if (c->red_bytes.empty()) c->red_bytes.assign((size_t)c->B, 0);
+    if (c->red_bytes[(size_t)seq] == bytes) return;
+    for (int par = 0; par < NPAR; par++)
+        for (int e = 0; e < eyes; e++) {
+            uint8_t *&d = c->d_red[((size_t)seq * NPAR + par) * 2 + e];
+            c->dfree(d);
+            d = bytes ? c->dalloc<uint8_t>(bytes) : nullptr;
+        }
+    c->red_bytes[(size_t)seq] = bytes;
+}
+static int set_reduction(lvt_handle h, int seq, bool batch_call, const lvt_amd_reduction *r) {
+    static const PropertyCall call = {"lvt_amd_set_reduction", 0,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                       "a batch handle takes its reductions per sequence through lvt_amd_batch_set_reduction (nothing was changed)"},
+                                      "lvt_amd_batch_set_reduction on a handle that is not a batch (use lvt_amd_set_reduction)"};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (!r) return refuse_unchanged(t, call.who, "a NULL record (factor 1 clears a reduction)");
+        const std::string why = reduction_check(*r, c->base_W(seq), c->base_H(seq));
+        if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the reduction before the first frame or after every frame has been collected");
+        const bool on = r->factor >= 2;
+        if (!on && !c->has_reduce(seq)) return 0;
+        if (seq == 0) std::fill(std::begin(c->ring_reduced), std::end(c->ring_reduced), false);  // (the last frame went in under ANOTHER record: lvt_amd_get_plane(.., 9, ..) has nothing of it)
+        const int fW = c->frame_W(seq), fH = c->frame_H(seq);
+        c->n_reduce = put_seq_value(c, c->red, 1, lvt_amd_reduction{}, seq, {on ? *r : lvt_amd_reduction{}}, [](const lvt_amd_reduction &x) { return x.factor >= 2; });
+        give_red_planes(c, seq, on);
+        if (c->frame_W(seq) != fW || c->frame_H(seq) != fH) {  // the frame's size changed: what is sized by its bytes follows, as in set_rectifiers
+            if (seq == 0) frame_planes_release(c);
+            if (c->fmt_of(seq) != PIX_GRAY8) give_gray_planes(c, seq);
+        }
+        return 0;
+    });
+}
+
 // ---- raw frames: rectifiers attached to a tracker (Context::rect) -----------------------------------------------------------------------------------
 // Both eyes of every sequence that has rectifiers and a frame in this step, in one launch.  The rectified planes (parity `par`) were read last by the
 // feature stage of frame enq - NPAR -- k_score, k_gather, k_brief_img: all on this stream, all enqueued before -- so stream order alone covers the
@@ -236,6 +322,8 @@ static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectif
                                        "a batch handle takes its rectifiers per sequence through lvt_amd_batch_set_rectifiers (nothing was changed)"},
                                       nullptr};
     return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (c->has_reduce(seq))  // (the reduction was checked against THIS base size: rectifiers first, then the reduction)
+            return refuse_unchanged(t, call.who, "a sequence with a reduction in force: clear it first (lvt_amd_set_reduction, factor 1), attach or detach, then set it again");
         if ((left == nullptr) != (right == nullptr)) return refuse_unchanged(t, call.who, "one rectifier is NULL (both, or NULL, NULL to detach)");
         Rectifier *rl = static_cast<Rectifier *>(left), *rr = static_cast<Rectifier *>(right);
         const Params &q = c->seq_prm(seq);
@@ -820,6 +908,42 @@ LVT_API int lvt_amd_equalise_device(const lvt_amd_equalisation *cfg, const void 
     hipLaunchKernelGGL(k_clahe_lut, dim3(cfg->tiles_x * cfg->tiles_y, 1), dim3(256), 0, st, tab);
     hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)(((size_t)(dst_pitch / 4) * h + 255) / 256), 1), dim3(256), 0, st, tab);
     return hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
+}
+
+LVT_API int lvt_amd_set_reduction(lvt_handle h, const lvt_amd_reduction *r) { return set_reduction(h, 0, false, r); }
+LVT_API int lvt_amd_batch_set_reduction(lvt_handle h, int seq, const lvt_amd_reduction *r) { return set_reduction(h, seq, true, r); }
+LVT_API int lvt_amd_get_reduction(lvt_handle h, int seq, lvt_amd_reduction *out) { return get_seq_record(h, seq, &Context::has_reduce, &Context::red, out); }
+// the stage alone on caller planes: a table of one image, the null stream; returns when the plane is written
+LVT_API int lvt_amd_reduce_device(const void *d_src, int src_w, int src_h, int src_pitch, int factor, void *d_dst, int dst_pitch, int *launches) {
+    const char *who = "lvt_amd_reduce_device";
+    if (launches) *launches = 0;
+    if (!d_src || !d_dst) return refuse_call(who, "a NULL argument (nothing was launched)");
+    if (factor < 2 || factor > REDUCE_MAX_FACTOR) return refuse_call(who, "factor = " + std::to_string(factor) + " (2 ... 8) (nothing was launched)");
+    if (src_w < factor || src_w > REDUCE_MAX_SIDE || src_h < factor || src_h > REDUCE_MAX_SIDE)
+        return refuse_call(who, "a source side outside factor ... 16384 (nothing was launched)");
+    const int w = src_w / factor, h = src_h / factor;
+    if (src_pitch < src_w) return refuse_call(who, "a source pitch smaller than the source width (nothing was launched)");
+    if (dst_pitch < w || (dst_pitch & 3) || ((uintptr_t)d_dst & 3))
+        return refuse_call(who, "a destination pitch smaller than the reduced width or no multiple of 4, or a destination that is not 4-byte aligned (nothing was launched)");
+    ReduceTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.im[0] = reduce_img(static_cast<const uint8_t *>(d_src), src_pitch, factor, static_cast<uint8_t *>(d_dst), dst_pitch, w, h);
+    hipLaunchKernelGGL(k_reduce_frames, reduce_grid(dst_pitch / 4 * h, 1), dim3(REDUCE_THREADS), 0, 0, tab);
+    if (launches) *launches = 1;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return refuse_call(who, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+// host only: the lens of the image k_reduce_frames writes from an image of lens *in.  Reduced pixel x covers source [f x, f x + f): f' = f / factor,
+// c' = (c + 0.5) / factor - 0.5, in double; the sizes by integer division; the model and the distortion coefficients (functions of the normalised ray) unchanged
+LVT_API int lvt_amd_lens_reduced(const lvt_amd_lens *in, int factor, lvt_amd_lens *out) {
+    if (!in || !out || factor < 1 || factor > REDUCE_MAX_FACTOR || in->width / factor < 1 || in->height / factor < 1) return -1;
+    lvt_amd_lens r = *in;
+    const double f = (double)factor;
+    r.width = in->width / factor, r.height = in->height / factor;
+    r.K[0] = in->K[0] / f, r.K[4] = in->K[4] / f;
+    r.K[2] = (in->K[2] + 0.5) / f - 0.5, r.K[5] = (in->K[5] + 0.5) / f - 0.5;
+    *out = r;
+    return 0;
 }
 
 LVT_API void lvt_amd_depth_guard_default(lvt_amd_depth_guard *out) {

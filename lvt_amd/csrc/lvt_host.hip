@@ -19,6 +19,7 @@
 #include "k_hamming.hip"
 #include "k_lists.hip"
 #include "k_rectify.hip"
+#include "k_reduce.hip"
 #include "k_depthreg.hip"
 #include "k_equalise.hip"
 #include "k_depthguard.hip"
@@ -289,11 +290,27 @@ struct Context {
     // SOURCE size (both eyes' are equal: set_rectifiers) -- the raw image need not have the tracker's size ("LENS MODELS", include/lvt_amd_ext.h).  Everything
     // allocated or sized by the frame's bytes follows it (staging, the host entry points' planes, the colour and converted planes); everything behind the
     // rectified plane stays at the sequence's size.  `resized`: the two differ -- only then does anything here allocate or launch differently.
-    int frame_W(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sw : seq_prm(s).W; }
-    int frame_H(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sh : seq_prm(s).H; }
-    bool resized(int s) const { return has_rect(s) && (frame_W(s) != seq_prm(s).W || frame_H(s) != seq_prm(s).H); }
+    // With a REDUCTION in force (lvt_amd_set_reduction, below) there are three sizes: the FRAME (the record's width x height, what the entry points take), the
+    // BASE (the reduced plane: the rectifiers' source where a pair is attached, else the sequence's) and the sequence's.  Without one the frame IS the base.
+    int base_W(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sw : seq_prm(s).W; }
+    int base_H(int s) const { return has_rect(s) ? rect[2 * (size_t)s]->sh : seq_prm(s).H; }
+    int frame_W(int s) const { return has_reduce(s) ? red[(size_t)s].width : base_W(s); }
+    int frame_H(int s) const { return has_reduce(s) ? red[(size_t)s].height : base_H(s); }
+    bool resized(int s) const { return (has_rect(s) || has_reduce(s)) && (frame_W(s) != seq_prm(s).W || frame_H(s) != seq_prm(s).H); }
     // pitch of the context's own gray planes of sequence s at the frame's size (a resized sequence: its own; otherwise plane_pitch, as ever)
     int frame_pitch(int s) const { return resized(s) ? (frame_W(s) + 63) / 64 * 64 : h_seqs[(size_t)s].plane_pitch; }
+    // ... and of its reduced planes, at the base size: what frame_pitch is to a sequence with rectifiers alone
+    int base_pitch(int s) const { return (base_W(s) != seq_prm(s).W || base_H(s) != seq_prm(s).H) ? (base_W(s) + 63) / 64 * 64 : h_seqs[(size_t)s].plane_pitch; }
+    // LARGE frames (lvt_amd_set_reduction / lvt_amd_batch_set_reduction): a sequence with a reduction takes frames of the record's width x height through every
+    // frame-taking entry point.  As for colour frames the FrameArgs name the large planes (the caller's, or the context's own pulled ones), and enqueue_frame puts
+    // ONE k_reduce_frames launch at the head of the feature stage -- behind the conversion, ahead of the rectify block -- that writes the sequence's own reduced
+    // planes (per feature-buffer parity, the base size) and points the frame at them.  A property of the handle, not state: reset and snapshots leave it alone.
+    std::vector<lvt_amd_reduction> red;  // [B] (empty until the first set); factor < 2: none
+    std::vector<uint8_t *> d_red;        // [B][NPAR][2] reduced planes, each sequence's base_pitch (an RGB-D sequence: eye 0 only)
+    std::vector<size_t> red_bytes;       // [B] bytes each of the sequence's reduced planes holds (0: none)
+    int n_reduce = 0;                    // sequences with a reduction
+    bool ring_reduced[RING] = {};        // per un-collected / last frame: sequence 0's image went through k_reduce_frames (lvt_amd_get_plane(.., 9, ..))
+    bool has_reduce(int s) const { return n_reduce > 0 && red[(size_t)s].factor >= 2; }
     // the host entry points of a RESIZED handle pull gray raw images into these planes instead of d_img / d_img_ring (allocated when first needed, at the
     // source's size; given back when the frame's size changes: frame_planes_release)
     uint8_t *d_raw[NPAR][2] = {};
@@ -378,7 +395,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 29;
+    static constexpr int PROF_SLOTS = 30;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -943,7 +960,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard", "k_label_mask"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard", "k_label_mask", "k_reduce_frames"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -1026,6 +1043,7 @@ struct DepthRegPlan {
     int n = 0;  // tables
 };
 static void convert_colour_frames(Context *c, int slot, int par, int Bz);
+static void reduce_frames(Context *c, int slot, int par, int Bz);
 static void rectify_raw_frames(Context *c, int slot, int par, int Bz);
 static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
@@ -1076,12 +1094,13 @@ static void enqueue_frame(Context *c) {
     }
     // ---- feature stage (stream_f): may start as soon as the tracking chain of frame enq-NPAR released this buffer
     // ---- the frame properties' launches at its head, ahead of the buffer gate (lvt_frame_props.h: why stream order alone covers each hand-over).  They point the
-    //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then remap
-    //      (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
+    //      step's FrameArgs at the planes they write, so they come before k_score<true> / k_feat_begin* carries the records to the device: convert, then reduce
+    //      (a large frame is averaged as the gray image the caller would have handed in), then remap (the reference's order), then equalise (the plane k_score would have read), then the clear of the registered depth planes, whose scatter goes out
     //      in front of k_gather.
-    c->ring_converted[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = c->ring_guarded[slot] = false;
+    c->ring_converted[slot] = c->ring_reduced[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = c->ring_guarded[slot] = false;
     if (!c->label_built.empty()) std::fill_n(c->label_built.begin() + (size_t)slot * B * 2, (size_t)B * 2, (uint8_t)0);
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
+    if (c->n_reduce) reduce_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
     if (c->n_equal) equalise_frames(c, slot, par, Bz);
     DepthRegPlan dreg;
@@ -1389,12 +1408,15 @@ static void track_sync(Context *c, double R[3][3], double t[3]) {
 
 // (the frame's size: the handle's own, or its rectifiers' source size -- Context::frame_W)
 static bool size_ok(Context *c, int rows, int cols) { return rows == c->frame_H(0) && cols == c->frame_W(0); }
+// a reduced RGB-D sequence takes its depth plane through a depth camera: without one the plane has no size of its own (the frame's? the sequence's?)
+static bool reduced_without_depth_camera(const Context *c, int s) { return c->sensor == 2 && c->has_reduce(s) && !c->has_depth_cam(s); }
+static const char *kReducedNoDepthCamera = "an RGB-D frame on a sequence with a reduction and no depth camera: the depth plane has no size of its own (set one with lvt_amd_set_depth_camera; a plane registered to the large image: identity extrinsics and the large image's pinhole)";
 // pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
 // byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes) and the gray frame of an
-// EQUALISED sequence by k_clahe_lut / k_clahe_apply
+// EQUALISED sequence by k_clahe_lut / k_clahe_apply; a LARGE frame (a reduction in force) is read by k_reduce_frames, whose byte path takes any base and pitch
 static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) {
     if (c->fmt_of(s) != PIX_GRAY8) return (long long)pitch >= (long long)cols * c->bpp_of(s);
-    return (c->has_rect(s) || c->has_equal(s)) ? pitch >= cols : (pitch & 15) == 0;
+    return (c->has_rect(s) || c->has_equal(s) || c->has_reduce(s)) ? pitch >= cols : (pitch & 15) == 0;
 }
 
 template <typename T>
@@ -1834,6 +1856,7 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot == 26 && c->n_mask == 0 && c->prof_calls[26] == 0) return 0;  // (... and one that never set a mask no k_mask_features)
     if (slot == 27 && c->n_guard == 0 && c->prof_calls[27] == 0) return 0;  // (... and one that never set a depth guard no k_depth_guard)
     if (slot == 28 && c->n_label == 0 && c->prof_calls[28] == 0) return 0;  // (... and one that never set a label-mask record no k_label_mask)
+    if (slot == 29 && c->n_reduce == 0 && c->prof_calls[29] == 0) return 0;  // (... and one that never set a reduction no k_reduce_frames)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1947,7 +1970,7 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             if (!d_right[s] || n_rows[s] != fH || n_cols[s] != fW || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
                 char buf[200];
                 std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], fW, fH, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s)) ? "at least the width" : "a multiple of 16");
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], fW, fH, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s) || c->has_reduce(s)) ? "at least the width" : "a multiple of 16");
                 return refuse(h, who, buf);
             }
         }
@@ -2068,8 +2091,8 @@ static void colour_planes(Context *c, uint8_t *(&d)[2], int eyes) {
         if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)((c->frame_W(0) * 4 + 63) / 64 * 64) * c->frame_H(0) + 64);
 }
 // the context's own raw planes of a RESIZED handle (Context::d_raw / d_raw_ring), allocated when first needed at the source's size
-static void raw_planes(Context *c, uint8_t *(&d)[2]) {
-    for (int e = 0; e < 2; e++)
+static void raw_planes(Context *c, uint8_t *(&d)[2], int eyes = 2) {
+    for (int e = 0; e < eyes; e++)
         if (!d[e]) d[e] = c->dalloc<uint8_t>((size_t)c->frame_pitch(0) * c->frame_H(0) + 64);
 }
 // the context's own depth planes of the synchronous host calls (Context::d_depth) hold dpix pixels: allocated at creation for the image's size, again when a
@@ -2091,6 +2114,10 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
         refuse(c, "lvt_track", "image size differs from the configured img_width/img_height");
         return;
     }
+    if (rgbd && reduced_without_depth_camera(c, 0)) {
+        refuse(c, "lvt_amd_track_rgbd", std::string(kReducedNoDepthCamera) + " (nothing was enqueued)");
+        return;
+    }
     // (the previous synchronous call may have returned on its early pose: its frame's tail -- staged update, triangulation -- runs
     //  while this call copies the new images into the staging buffer of THIS frame's feature buffer; the drain comes after)
     flush_pending(c);  // a held lvt_amd_track_async frame goes out FIRST: it takes a frame number, and this frame's buffers (images, corner lists) are chosen by number
@@ -2101,7 +2128,7 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp;
     const bool raw = bpp == 1 && c->resized(0);  // (gray raw frames of another size than the tracker's: planes of their own)
     if (bpp > 1) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
-    if (raw) raw_planes(c, c->d_raw[par]);
+    if (raw) raw_planes(c, c->d_raw[par], rgbd ? 1 : 2);
     uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : raw ? c->d_raw[par] : c->d_img[par];
     const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
     // (a handle with a depth camera: the depth plane is the sensor's, the camera's size -- staged, pulled and handed on unchanged)
@@ -2122,7 +2149,7 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s1, s1, dimg[1], dimg[1], row_bytes, n_rows, ipitch);
     else hipLaunchKernelGGL(k_stage_in, dim3(128, rgbd ? 1 : 2), dim3(256), 0, sf, s0, s1, dimg[0], dimg[1], row_bytes, n_rows, ipitch);
     drain(c);
-    FrameArgs f = stereo_args(dimg[0], dimg[(bpp > 1 && rgbd) ? 0 : 1], ipitch);  // (an RGB-D handle has one colour plane)
+    FrameArgs f = stereo_args(dimg[0], dimg[(rgbd && (bpp > 1 || raw)) ? 0 : 1], ipitch);  // (an RGB-D handle has one colour plane, and one raw plane)
     if (rgbd) {
         // The depth plane (1.2 MB: ~60 us of CPU copy into the staging buffer when the caller's buffer is pageable, ~45 us of PCIe pull)
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
@@ -2163,6 +2190,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     if (c->B != 1 || (rgbd ? c->sensor != 2 : c->sensor != 1)) return refuse(c, who, "wrong sensor type for this entry point (or a batch handle)");
     if (!left || !second || !size_ok(c, n_rows, n_cols))
         return refuse(c, who, "image size differs from the configured img_width/img_height (the frame was NOT enqueued)");
+    if (rgbd && reduced_without_depth_camera(c, 0)) return refuse(c, who, std::string(kReducedNoDepthCamera) + " (nothing was enqueued)");
     if (c->early_pending) drain(c);
     if (rgbd) flush_pending(c);
     const int held = c->pend.valid ? 1 : 0;  // (the held frame owns slot enq % RING)
@@ -2173,7 +2201,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp, plane = (size_t)c->pitch * c->prm.H;
     const bool raw = bpp == 1 && c->resized(0);  // (as in upload_and_track)
     if (bpp > 1) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
-    if (raw) raw_planes(c, c->d_raw_ring[slot]);
+    if (raw) raw_planes(c, c->d_raw_ring[slot], rgbd ? 1 : 2);
     const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
     const size_t dpix = rgbd ? c->depth_px() : 0;  // (a handle with a depth camera: the sensor's plane, the camera's size)
     const int dcols = c->depth_cols();
@@ -2296,15 +2324,21 @@ static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale)
     return true;
 }
 // one sequence's device planes against its parameters; "" when they pass (dcols: the width of its depth plane -- its depth camera's, else the image's)
-static std::string rgbd_planes_check(const Params &q, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp, int dcols) {
+// (fW x fH: the sequence's frame size -- its own, or its reduction's; large: a reduction is in force, and k_reduce_frames reads the gray plane in place)
+static std::string rgbd_planes_check(int fW, int fH, bool large, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp, int dcols) {
     const int esz = (fmt == DEPTH_U16) ? 2 : 4;
     char buf[240];
     if (!d_gray || !d_depth) return "NULL gray or depth plane";
-    if (n_rows != q.H || n_cols != q.W) {
-        std::snprintf(buf, sizeof(buf), "image size %d x %d, expected %d x %d", n_cols, n_rows, q.W, q.H);
+    if (n_rows != fH || n_cols != fW) {
+        std::snprintf(buf, sizeof(buf), "image size %d x %d, expected %d x %d", n_cols, n_rows, fW, fH);
         return buf;
     }
-    if (bpp > 1) {  // a colour sequence: k_gray_frames reads the plane byte-wise -- any address, any pitch that holds a row
+    if (large && bpp == 1) {  // a large gray frame: any address, any pitch that holds a row
+        if (gray_pitch < n_cols) {
+            std::snprintf(buf, sizeof(buf), "gray plane: pitch (%d) must hold a row of %d bytes", gray_pitch, n_cols);
+            return buf;
+        }
+    } else if (bpp > 1) {  // a colour sequence: k_gray_frames reads the plane byte-wise -- any address, any pitch that holds a row
         if ((long long)gray_pitch < (long long)n_cols * bpp) {
             std::snprintf(buf, sizeof(buf), "colour plane: pitch (%d) must hold a row of %d bytes", gray_pitch, n_cols * bpp);
             return buf;
@@ -2330,7 +2364,8 @@ static int track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_by
     DeviceGuard guard(c);
     try {
         if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
-        const std::string why = rgbd_planes_check(c->prm, d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0), c->depth_cols());
+        if (reduced_without_depth_camera(c, 0)) return rgbd_refuse(h, who, kReducedNoDepthCamera);
+        const std::string why = rgbd_planes_check(c->frame_W(0), c->frame_H(0), c->has_reduce(0), d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0), c->depth_cols());
         if (!why.empty()) return rgbd_refuse(h, who, why);
         if (sync) {
             drain(c);
@@ -2411,7 +2446,8 @@ LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *cons
         for (int s = 0; s < c->B; s++) {
             if (!d_gray[s]) continue;
             present++;
-            const std::string why = rgbd_planes_check(c->seq_prm(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s),
+            if (reduced_without_depth_camera(c, s)) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + kReducedNoDepthCamera);
+            const std::string why = rgbd_planes_check(c->frame_W(s), c->frame_H(s), c->has_reduce(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s),
                                                       c->has_depth_cam(s) ? c->depth_cam[(size_t)s].width : n_cols[s]);
             if (!why.empty()) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + why);
         }
@@ -2466,6 +2502,10 @@ LVT_API void lvt_track_with_external_corners(lvt_handle h, unsigned char *left, 
         DeviceGuard guard(c);
         if (c->has_rect(0)) {  // the images would be raw, the corners in rectified coordinates the caller does not have
             refuse(h, "lvt_track_with_external_corners", "refused on a handle with rectifiers attached (the frame was NOT tracked; detach them with lvt_amd_set_rectifiers(h, NULL, NULL))");
+            return;
+        }
+        if (c->has_reduce(0)) {  // likewise: the corners would be in the large frame's coordinates, or the reduced image's -- the call cannot know
+            refuse(h, "lvt_track_with_external_corners", "refused on a handle with a reduction in force (the frame was NOT tracked; clear it with lvt_amd_set_reduction, factor 1)");
             return;
         }
         if (cut[0]) c->set_error(cut);
@@ -2761,6 +2801,14 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
             HIPCHK(c, hipMemcpy(dst, c->d_lmask[(size_t)c->last_par * 2 + e], n, hipMemcpyDeviceToHost));
             if (pitch_out) *pitch_out = c->pitch;
             return (int)n;
+        }
+        if (what == 9) {  // the reduced image of the last (large) frame, ahead of the remap (u8, the BASE size: base_H rows x base_pitch); 0 bytes without a reduction
+            if (c->done == 0 || !c->has_reduce(0) || !c->ring_reduced[c->last_slot]) return 0;
+            const size_t bytes = (size_t)c->base_pitch(0) * c->base_H(0);
+            if ((size_t)cap_bytes < bytes) return -1;
+            HIPCHK(c, hipMemcpy(dst, c->d_red[(size_t)c->last_par * 2 + (c->sensor == 1 ? e : 0)], bytes, hipMemcpyDeviceToHost));
+            if (pitch_out) *pitch_out = c->base_pitch(0);
+            return (int)bytes;
         }
         if (what >= 2 && what <= 4) {  // a frame property's plane: 0 bytes unless the last frame went through that stage
             if (c->done == 0) return 0;
