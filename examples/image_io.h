@@ -1,5 +1,5 @@
 // image_io.h -- the image readers of the dataset harnesses (no OpenCV: zlib only).
-// PNG: 8/16-bit gray, gray+alpha, RGB, RGBA, non-interlaced; PGM: binary P5.  Colour is reduced to gray with
+// PNG: 8/16-bit gray, gray+alpha, RGB, RGBA, non-interlaced; PGM: binary P5, maxval up to 65535 (two bytes per sample, most significant first).  Colour is reduced to gray with
 // cv::cvtColor's fixed-point weights -- and kept, interleaved R G B, for callers that hand the tracker colour frames (LVT_AMD_PIX_RGB8);
 // 16-bit samples are kept (depth maps) and also narrowed to their high byte.
 #pragma once
@@ -135,10 +135,20 @@ inline bool decode_pgm(const std::vector<unsigned char> &buf, Gray &img, std::st
     if (token() != "P5") return err = "not a binary PGM", false;
     const int w = std::atoi(token().c_str()), h = std::atoi(token().c_str()), mx = std::atoi(token().c_str());
     pos++;  // single whitespace after maxval
-    if (w <= 0 || h <= 0 || mx <= 0 || mx > 255 || pos + (size_t)w * h > buf.size()) return err = "unsupported PGM", false;
+    const size_t bps = mx > 255 ? 2 : 1;  // (the format: maxval above 255 means two bytes per sample, big-endian)
+    if (w <= 0 || h <= 0 || mx <= 0 || mx > 65535 || pos + (size_t)w * h * bps > buf.size()) return err = "unsupported PGM", false;
     img.w = w, img.h = h;
-    img.px.assign(buf.begin() + (long)pos, buf.begin() + (long)(pos + (size_t)w * h));
     img.px16.clear(), img.rgb.clear();
+    if (bps == 1) {
+        img.px.assign(buf.begin() + (long)pos, buf.begin() + (long)(pos + (size_t)w * h));
+        return true;
+    }
+    img.px.resize((size_t)w * h), img.px16.resize((size_t)w * h);
+    for (size_t i = 0; i < (size_t)w * h; i++) {  // bytes swapped on read: px16 is in the host's order; px is the high byte, as for 16-bit PNGs
+        const unsigned char hi = buf[pos + 2 * i], lo = buf[pos + 2 * i + 1];
+        img.px16[i] = (uint16_t)((hi << 8) | lo);
+        img.px[i] = hi;
+    }
     return true;
 }
 

@@ -1,7 +1,7 @@
 // lvt_euroc -- EuRoC MAV stereo command line harness over the C-ABI (SURVEY 8(f) rows 1 + 2).
 //
 // Same argv, inputs and outputs as the reference's example binary (examples/euroc/euroc_example.cpp:49-175 there):
-//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE]
+//     lvt_euroc <euroc_root_dir> <stamps_dir> <dataset_name> <config_file_name> [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE] [--mono16 LO,HI|auto[,LOPM,HIPM,SPAN]]
 // (--clahe: CLAHE contrast equalisation of the rectified frames inside the feature stage, lvt_amd_set_equalisation; absent by default)
 // reads <stamps_dir>/<dataset_name>.txt (one nanosecond stamp per line = the image file stem), the cam0 / cam1 PNGs below
 // <root>/<dataset_name>/mav0/, hands the RAW images to lvt_track -- the two rectifiers with the calibration the reference hard-codes
@@ -19,6 +19,10 @@
 //     left_width, left_height    the RAW image's size (right_ likewise; the two are equal)
 //     left_K0 ... left_K8        the raw camera matrix, row-major;  left_D0 ... left_D11  the coefficients;  left_R0 ... left_R8  the rectifying rotation
 //     Tbs0 ... Tbs11             (optional) body-from-camera, 3 x 4 row-major; absent: the identity, the trajectory is the left camera's
+//
+// --mono16 LO,HI | auto[,LOPM,HIPM,SPAN] (not in the reference): the images are 16-bit binary PGMs (<stamp>.pgm, maxval > 255: thermal cameras, 10 / 12-bit
+// machine vision) and go to the tracker as they are, LVT_AMD_SENSOR_MONO16 ("SENSOR FORMATS", include/lvt_amd_ext.h): a fixed window [LO, HI], or one found per
+// frame from the frame's histogram with LOPM / HIPM permille of the pixels allowed below / above it and a smallest width SPAN (defaults 5, 5, 256).
 #include "../include/lvt_amd_ext.h"
 #include "../include/lvt_c.h"
 #include "image_io.h"
@@ -83,7 +87,7 @@ bool read_numbers(const std::string &path, std::vector<std::pair<std::string, do
 
 int main(int argc, char **argv) {
     if (argc < 5) {
-        std::cout << "Usage ./lvt_euroc euroc_root_dir stamps_dir dataset_name config_file_name [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE]" << std::endl;
+        std::cout << "Usage ./lvt_euroc euroc_root_dir stamps_dir dataset_name config_file_name [--max-frames N] [--out name.txt] [--clahe CLIP[,TX,TY]] [--lens FILE] [--mono16 LO,HI|auto[,LOPM,HIPM,SPAN]]" << std::endl;
         return -1;
     }
     const std::string root_dir = argv[1], stamps_dir = argv[2], dataset_name = argv[3], config_file_name = argv[4];
@@ -92,9 +96,23 @@ int main(int argc, char **argv) {
     long max_frames = -1;
     std::string lens_file;  // --lens FILE: the calibration of both eyes, P and the tracked size
     lvt_amd_equalisation clahe = {0, 0, 0.f};  // --clahe CLIP[,TX,TY]: equalise the rectified frames (dark sequences); tiles 8 x 8 unless given
+    lvt_amd_sensor_format mono16 = {LVT_AMD_SENSOR_NONE, 0, 0, 0, 5, 5, 256, {0}};  // --mono16: 16-bit PGMs, mapped to 8 bits inside the feature stage
     for (int i = 5; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--out") out_name = argv[i + 1];
+        if (k == "--mono16") {
+            const std::string v = argv[i + 1];
+            mono16.format = LVT_AMD_SENSOR_MONO16;
+            if (v.compare(0, 4, "auto") == 0) {
+                mono16.auto_window = 1;
+                if (v.size() > 4 && std::sscanf(v.c_str() + 4, ",%d,%d,%d", &mono16.lo_permille, &mono16.hi_permille, &mono16.min_span) < 1) mono16.format = -1;
+            } else if (std::sscanf(v.c_str(), "%d,%d", &mono16.lo, &mono16.hi) != 2) {
+                mono16.format = -1;
+            }
+            if (mono16.format < 0) {
+                std::cout << "--mono16 LO,HI|auto[,LOPM,HIPM,SPAN]: cannot read " << v << std::endl;
+                return -1;
+            }
+        } else if (k == "--out") out_name = argv[i + 1];
         else if (k == "--max-frames") max_frames = std::atol(argv[i + 1]);
         else if (k == "--lens") lens_file = argv[i + 1];
         else if (k == "--clahe") {
@@ -118,7 +136,7 @@ int main(int argc, char **argv) {
         while (std::getline(f, line)) {
             while (!line.empty() && std::isspace((unsigned char)line.back())) line.pop_back();
             if (line.empty()) continue;
-            titles.push_back(line + ".png");
+            titles.push_back(line + (mono16.format ? ".pgm" : ".png"));
             time_stamps.push_back(std::atof(line.c_str()) / 1e9);
         }
     }
@@ -195,6 +213,10 @@ int main(int argc, char **argv) {
         std::cout << "failed to set the equalisation: " << lvt_amd_last_error(vo) << std::endl;
         return -1;
     }
+    if (mono16.format && lvt_amd_set_sensor_format(vo, &mono16) != 0) {
+        std::cout << "failed to set the sensor format: " << lvt_amd_last_error(vo) << std::endl;
+        return -1;
+    }
     long frame_count = (long)titles.size();
     if (max_frames >= 0 && max_frames < frame_count) frame_count = max_frames;
     std::vector<double> poses;  // q (w x y z), p of the BODY per processed frame
@@ -205,13 +227,14 @@ int main(int argc, char **argv) {
         Gray left, right;
         std::string err;
         if (!load_image(seq_dir + "/cam0/data/" + titles[i], left, err) || !load_image(seq_dir + "/cam1/data/" + titles[i], right, err) || left.w != W ||
-            left.h != H || right.w != W || right.h != H) {
-            std::cout << "Failed to load image " << titles[i] << std::endl;
+            left.h != H || right.w != W || right.h != H || (mono16.format && (left.px16.empty() || right.px16.empty()))) {
+            std::cout << "Failed to load image " << titles[i] << (mono16.format ? " (--mono16 takes binary PGMs with maxval > 255)" : "") << std::endl;
             break;
         }
         const auto t0 = std::chrono::steady_clock::now();
         double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
-        lvt_track(vo, left.px.data(), right.px.data(), H, W, R, t);
+        if (mono16.format) lvt_track(vo, reinterpret_cast<unsigned char *>(left.px16.data()), reinterpret_cast<unsigned char *>(right.px16.data()), H, W, R, t);
+        else lvt_track(vo, left.px.data(), right.px.data(), H, W, R, t);
         total_time += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         double body[3][4];  // Tbs * [R t; 0 1]
         for (int r = 0; r < 3; r++)

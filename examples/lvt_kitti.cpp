@@ -19,6 +19,9 @@
 // (or .pgm), an 8-bit image of ANY size -- a segmentation network's output, usually a fraction of the frame's -- holds the left eye's labels of that frame;
 // key points on pixels whose label is among L1,L2,..., widened by R pixels (0 ... 15, default 0), are dropped.  The first file fixes the label size; a frame
 // whose file is missing gets no labels.  The same trajectory format.
+// --bayer RGGB|BGGR|GRBG|GBRG (not in the reference): the files are 8-bit Bayer mosaics as a machine-vision camera delivers them (8-bit gray PNG or PGM whose
+// pixels are the samples); they go to the tracker as they are and are demosaiced to gray inside the feature stage (lvt_system::set_sensor_format, "SENSOR
+// FORMATS" in include/lvt_amd_ext.h).
 #include "../include/lvt_system.h"
 
 #include "image_io.h"
@@ -67,7 +70,7 @@ bool read_calib(const std::string &path, double K[9], double &baseline) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        std::cout << "Usage ./lvt_kitti sequences_dir seq_number [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--reduce F]" << std::endl;
+        std::cout << "Usage ./lvt_kitti sequences_dir seq_number [--config vo_config.yaml] [--calib calib/NN.yml] [--max-frames N] [--out NN.txt] [--reduce F] [--bayer RGGB|BGGR|GRBG|GBRG]" << std::endl;
         return -1;
     }
     char seq_cstr[16];
@@ -75,6 +78,7 @@ int main(int argc, char **argv) {
     const std::string seq_str(seq_cstr), dir_prefix = std::string(argv[1]) + "/" + seq_str;
     std::string config = "vo_config.yaml", calib = "calib/" + seq_str + ".yml", out_name = seq_str + ".txt", cov_name, mask_names, labels_dir, drop_list;
     int dilate = 0, reduce = 1;
+    std::string bayer;  // --bayer PATTERN: the files are 8-bit Bayer mosaics, demosaiced to gray inside the feature stage (lvt_system::set_sensor_format)
     long max_frames = -1;
     for (int i = 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -88,6 +92,7 @@ int main(int argc, char **argv) {
         else if (k == "--drop") drop_list = argv[i + 1];
         else if (k == "--dilate") dilate = std::atoi(argv[i + 1]);
         else if (k == "--reduce") reduce = std::atoi(argv[i + 1]);
+        else if (k == "--bayer") bayer = argv[i + 1];
     }
     double K[9], baseline = 0;
     if (!read_calib(calib, K, baseline)) {
@@ -126,6 +131,20 @@ int main(int argc, char **argv) {
     if (!vo) {
         std::cout << "failed to create the tracker: " << lvt_amd_last_error(nullptr) << std::endl;
         return -1;
+    }
+    if (!bayer.empty()) {
+        lvt_amd_sensor_format sf = {LVT_AMD_SENSOR_NONE, 0, 0, 0, 0, 0, 0, {0}};
+        sf.format = bayer == "RGGB" ? LVT_AMD_SENSOR_BAYER_RGGB8 : bayer == "BGGR" ? LVT_AMD_SENSOR_BAYER_BGGR8 : bayer == "GRBG" ? LVT_AMD_SENSOR_BAYER_GRBG8 : bayer == "GBRG" ? LVT_AMD_SENSOR_BAYER_GBRG8 : -1;
+        if (sf.format < 0) {
+            std::cout << "--bayer takes RGGB, BGGR, GRBG or GBRG" << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
+        if (!vo->set_sensor_format(&sf)) {
+            std::cout << "failed to set the sensor format: " << vo->last_error() << std::endl;
+            lvt_system::destroy(vo);
+            return -1;
+        }
     }
     if (reduce > 1 && !vo->set_reduction(reduce, frame_w, frame_h)) {
         std::cout << "failed to set the reduction: " << vo->last_error() << std::endl;

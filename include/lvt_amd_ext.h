@@ -459,6 +459,71 @@ LVT_API int lvt_amd_set_pixel_format(lvt_handle h, int format);                 
 LVT_API int lvt_amd_batch_set_pixel_format(lvt_handle h, int seq, int format);  /* 0 / -1 */
 LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq);                    /* format, -1: bad handle / seq */
 
+/* SENSOR FORMATS: Bayer mosaics, YUV 4:2:2 and 16-bit gray, turned into 8-bit gray inside the tracker's feature stage.  A sensor format is a property of the
+ * handle, or of one sequence of a batch, like the pixel format; the record is copied.  It is not state: lvt_amd_reset, lvt_amd_batch_reset and snapshots
+ * neither hold nor change it.  Once it is set, EVERY frame-taking call on that handle or sequence, of either sensor (on an RGB-D sequence it describes the one
+ * image), host or device, synchronous or asynchronous, the batch calls uniform and mixed, sit-outs included, takes the sensor's plane, and one launch at the
+ * head of the feature stage (k_sensor_frames: every such image of the step, in k_gray_frames' place: convert, reduce, remap, equalise) writes the gray planes
+ * the frame is tracked from.  A handle or sequence that never sets one allocates and launches exactly what it did; format = LVT_AMD_SENSOR_NONE unsets the
+ * property, frees what only it allocated and returns the handle to that path.
+ *  THE DEFINITION -- integer arithmetic throughout; tests/sensor_util.py restates it in numpy and the checks hold the kernels to it byte for byte (the claim
+ *  is equality with this text, not with any library's demosaicing).
+ *   - BAYER (8 bit).  The pattern names the colours of pixels (0,0), (1,0) / (0,1), (1,1).  A channel that is missing at a pixel is the mean of the nearest
+ *     samples of that colour -- 4 diagonal, 4 axial or 2 axial -- kept unscaled as X4 = 4 x the value: the sum of four, twice the sum of two, or four times
+ *     the pixel's own sample.  Neighbours outside the image are mirrored without repeating the edge (-1 -> 1, W -> W - 2; rows likewise): the colour phase is
+ *     kept.       gray = (4899 R4 + 9617 G4 + 1868 B4 + 32768) >> 16            (one rounding; the largest sum is 16 744 448)
+ *     A flat field R = G = B = v gives v.  A mosaic of an image that is constant per channel has X4 = 4 X everywhere, and (4 s + 32768) >> 16 ==
+ *     (s + 8192) >> 14: it gives exactly the value of COLOUR frames above for that colour.
+ *   - YUYV / UYVY (YUV 4:2:2).  gray[y][x] = row[2 x] / row[2 x + 1].  No range expansion (a limited-range 16 ... 235 luma stays 16 ... 235).
+ *   - MONO16 (little-endian uint16_t), window [lo, hi]:   g = min(max(v, lo), hi);   out = ((g - lo) * 255 + ((hi - lo) >> 1)) / (hi - lo)   (truncating;
+ *     below 2^24).  auto_window = 0: the record's lo, hi.  auto_window = 1: per image and per frame from the frame's own histogram -- 4096 bins of v >> 4
+ *     over the W x H pixels, cum(b) = pixels in bins <= b, N = W H, 64-bit products:
+ *         lo_bin = the smallest b with cum(b) * 1000 > lo_permille * N;     hi_bin = the smallest b with cum(b) * 1000 >= (1000 - hi_permille) * N;
+ *         lo = 16 lo_bin, hi = 16 hi_bin + 15;   where hi - lo < min_span:  mid = (lo + hi) >> 1, lo = max(0, mid - (min_span >> 1)), hi = lo + min_span,
+ *         and if hi > 65535 then hi = 65535, lo = hi - min_span.
+ *     Two further launches in front of the conversion (k_sensor_hist, k_sensor_levels), only where a sequence asks for it.  Each frame stands alone: the
+ *     window is NOT smoothed over frames.
+ *  - a row is W bytes (Bayer) or 2 W bytes (YUYV, UYVY, MONO16); n_rows / n_cols stay in PIXELS.  Host buffers are tightly packed.  Device planes are read in
+ *    place at any address and any pitch that holds a row; MONO16 needs an even address and an even pitch and is refused otherwise.
+ *  - MUTUALLY EXCLUSIVE with a colour pixel format: either setter is refused on a sequence that has the other.
+ *  - external corners are in the same coordinates: lvt_track_with_external_corners stays allowed.
+ *  - refused (-1, nothing changed, the reason in lvt_amd_last_error, every sentence ending "(nothing was changed)"), in this order: a pooled or automatic
+ *    seat; the batch call on a handle that is not a batch and the other way round; seq out of range; a bad record -- NULL; an unknown format; for MONO16
+ *    auto_window outside 0 ... 1, then (fixed) lo, hi outside 0 <= lo < hi <= 65535 or (auto) lo_permille, hi_permille outside 0 ... 499, min_span outside
+ *    1 ... 65535; for Bayer a frame narrower or lower than 2 pixels: the sentence names the field --; a sequence with a colour pixel format; a handle with
+ *    frames in flight.  A successful set counts as use of an lvt_create handle.  The fields a format does not use are ignored.
+ *  - lvt_amd_get_sensor_format: 1 = a format is set (copied to *out), 0 = none, -1 = bad handle / seq.
+ *  - lvt_amd_get_sensor_window: the window image `eye` (0 / 1; RGB-D: 0) of sequence seq was mapped with in the last collected frame: 1 with lo, hi; 0 where
+ *    there is none (no MONO16 format, no frame yet, or the sequence SAT OUT of the last collected step -- whatever it tracked before: the answer is about
+ *    that step, and it is 1 again after the next step the sequence has a frame in); -1 = bad handle / seq / eye.  A fixed window reports
+ *    the record's.
+ *  - lvt_amd_get_plane(h, eye, 3, ...) reads the converted plane of the last frame back, as for colour.  lvt_amd_profile_read reports the launches as
+ *    "k_sensor_frames", "k_sensor_hist" and "k_sensor_levels" (the first for a handle with a sensor format only, the other two for one with an auto window only).
+ *  - lvt_amd_convert_sensor_device: the stage alone on caller planes (device pointers).  src: height rows of src_pitch_bytes >= a row, any address (MONO16:
+ *    even); dst: height rows of dst_pitch bytes, dst_pitch >= width, dst_pitch % 4 == 0, 4-byte aligned; sides 1 ... 16384 (Bayer: 2 ...).  Every byte of the
+ *    destination rows is written, the columns from width on as zero, nothing else.  window_out (may be NULL): the window a MONO16 image was mapped with
+ *    ({0, 0} for the other formats).  Null stream; returns when the plane is written.  0, or -1 (nothing launched, the sentence in lvt_amd_last_error(NULL)).
+ *  - not here: range expansion for YUV; smoothing of the auto window over frames; 10- and 12-bit PACKED formats; planar NV12, whose Y plane already is a gray
+ *    plane with a pitch and enters as one. */
+enum { LVT_AMD_SENSOR_NONE = 0,
+       LVT_AMD_SENSOR_BAYER_RGGB8 = 16, LVT_AMD_SENSOR_BAYER_BGGR8 = 17, LVT_AMD_SENSOR_BAYER_GRBG8 = 18, LVT_AMD_SENSOR_BAYER_GBRG8 = 19,
+       LVT_AMD_SENSOR_YUYV = 24, LVT_AMD_SENSOR_UYVY = 25,
+       LVT_AMD_SENSOR_MONO16 = 32 };
+typedef struct {
+    int format;
+    int auto_window;        /* MONO16: 0 = [lo, hi] below, 1 = from each frame's histogram */
+    int lo, hi;             /* MONO16 fixed window, 0 <= lo < hi <= 65535 */
+    int lo_permille, hi_permille;   /* MONO16 auto: share of pixels allowed below / above the window, each 0 ... 499 */
+    int min_span;           /* MONO16 auto: smallest hi - lo, 1 ... 65535 */
+    int reserved[1];
+} lvt_amd_sensor_format;
+LVT_API int lvt_amd_set_sensor_format(lvt_handle h, const lvt_amd_sensor_format *f);
+LVT_API int lvt_amd_batch_set_sensor_format(lvt_handle h, int seq, const lvt_amd_sensor_format *f);
+LVT_API int lvt_amd_get_sensor_format(lvt_handle h, int seq, lvt_amd_sensor_format *out);
+LVT_API int lvt_amd_get_sensor_window(lvt_handle h, int seq, int eye, int *lo, int *hi);   /* the window the last collected frame was mapped with */
+LVT_API int lvt_amd_convert_sensor_device(const lvt_amd_sensor_format *f, const void *src, int src_pitch_bytes, int width, int height,
+                                          uint8_t *dst, int dst_pitch, int window_out[2]);   /* the stage alone, on caller planes in HBM */
+
 /* FRAME REDUCTION: large frames, averaged down by an integer factor inside the tracker's feature stage.  The tracker's capacities are shaped for KITTI- and
  * VGA-sized images; cameras deliver 1080p to 4K.  A reduction is a property of the handle, or of one sequence of a batch, like the pixel format; the record is
  * copied.  It is not state: lvt_amd_reset, lvt_amd_batch_reset and snapshots neither hold nor change it.  Once it is set, EVERY frame-taking call on that

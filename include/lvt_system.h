@@ -329,6 +329,14 @@ class lvt_system {
     /* ADDITIVE: CLAHE contrast equalisation of the gray plane the detector reads (lvt_amd_equalisation, include/lvt_amd_ext.h, DIM frames): from now on every
      * frame is equalised by two launches at the head of its feature stage; nullptr: plain frames again.  false: refused (last_error() says why), nothing changed. */
     bool set_equalisation(const lvt_amd_equalisation *cfg) { return lvt_amd_set_equalisation(m_handle, cfg) == 0; }
+    /* ADDITIVE: sensor formats (lvt_amd_sensor_format, include/lvt_amd_ext.h, SENSOR FORMATS): from now on every image handed to this system is the sensor's
+     * plane -- an 8-bit Bayer mosaic, YUV 4:2:2 or little-endian 16-bit gray -- and is turned into 8-bit gray by one launch at the head of its feature stage
+     * (two more where a MONO16 record asks for an auto window).  nullptr, or format LVT_AMD_SENSOR_NONE: plain frames again.  false: refused (last_error()
+     * says why), nothing changed. */
+    bool set_sensor_format(const lvt_amd_sensor_format *f) {
+        const lvt_amd_sensor_format none = {LVT_AMD_SENSOR_NONE, 0, 0, 0, 0, 0, 0, {0}};
+        return lvt_amd_set_sensor_format(m_handle, f ? f : &none) == 0;
+    }
     /* ADDITIVE: large frames (lvt_amd_reduction, include/lvt_amd_ext.h, FRAME REDUCTION): from now on every image handed to this system is width x height
      * pixels and is averaged down by `factor` (2 ... 8) by one launch at the head of its feature stage; width / factor x height / factor must be the system's
      * own image size, whose parameters are those of the REDUCED image.  factor 1: frames of the system's own size again.  false: refused (last_error() says

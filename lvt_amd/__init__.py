@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lvt_amd_odometry_push_pose_cov", "lvt_amd_odometry_update_cov",
     "lvt_amd_set_depth_camera", "lvt_amd_batch_set_depth_camera", "lvt_amd_get_depth_camera", "lvt_amd_register_depth_device",
     "lvt_amd_set_equalisation", "lvt_amd_batch_set_equalisation", "lvt_amd_get_equalisation", "lvt_amd_equalise_device", "lvt_amd_equalisation_plan",
+    "lvt_amd_set_sensor_format", "lvt_amd_batch_set_sensor_format", "lvt_amd_get_sensor_format", "lvt_amd_get_sensor_window", "lvt_amd_convert_sensor_device",
     "lvt_amd_set_reduction", "lvt_amd_batch_set_reduction", "lvt_amd_get_reduction", "lvt_amd_reduce_device", "lvt_amd_lens_reduced",
     "lvt_amd_set_mask", "lvt_amd_batch_set_mask", "lvt_amd_set_mask_device", "lvt_amd_batch_set_mask_device", "lvt_amd_get_mask_stats", "lvt_amd_mask_features",
     "lvt_amd_set_label_mask", "lvt_amd_batch_set_label_mask", "lvt_amd_get_label_mask", "lvt_amd_frame_labels", "lvt_amd_frame_labels_device", "lvt_amd_build_label_mask",
@@ -67,6 +68,12 @@ eState_NOT_INITIALIZED, eState_TRACKING, eState_LOST = 1, 2, 3
 eSensor_STEREO, eSensor_RGBD = 1, 2
 PIX_GRAY8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8 = 0, 1, 2, 3, 4   # LVT_AMD_PIX_*: interleaved 8-bit formats a handle / a batch sequence takes its frames in
 PIX_BPP = {PIX_GRAY8: 1, PIX_BGR8: 3, PIX_RGB8: 3, PIX_BGRA8: 4, PIX_RGBA8: 4}
+# LVT_AMD_SENSOR_*: the camera's own layouts a handle / a batch sequence takes its frames in (SensorFormat): 8-bit Bayer mosaics, YUV 4:2:2, 16-bit gray
+SENSOR_NONE = 0
+SENSOR_BAYER_RGGB8, SENSOR_BAYER_BGGR8, SENSOR_BAYER_GRBG8, SENSOR_BAYER_GBRG8 = 16, 17, 18, 19
+SENSOR_YUYV, SENSOR_UYVY = 24, 25
+SENSOR_MONO16 = 32
+SENSOR_BPP = {SENSOR_NONE: 1, SENSOR_BAYER_RGGB8: 1, SENSOR_BAYER_BGGR8: 1, SENSOR_BAYER_GRBG8: 1, SENSOR_BAYER_GBRG8: 1, SENSOR_YUYV: 2, SENSOR_UYVY: 2, SENSOR_MONO16: 2}
 DEPTH_F32, DEPTH_U16 = 0, 1   # LVT_AMD_DEPTH_F32 (metres) / LVT_AMD_DEPTH_U16 (raw sensor units: metres = raw * depth_scale)
 
 _lib = None
@@ -225,6 +232,13 @@ def load_library():
     for name, argtypes in (   # (dim frames: likewise)
             ("lvt_amd_set_equalisation", [vp, vp]), ("lvt_amd_batch_set_equalisation", [vp, C.c_int, vp]), ("lvt_amd_get_equalisation", [vp, C.c_int, vp]),
             ("lvt_amd_equalise_device", [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]), ("lvt_amd_equalisation_plan", [vp, C.c_int, C.c_int, vp, vp])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, C.c_int
+    for name, argtypes in (   # (sensor formats: likewise)
+            ("lvt_amd_set_sensor_format", [vp, vp]), ("lvt_amd_batch_set_sensor_format", [vp, C.c_int, vp]), ("lvt_amd_get_sensor_format", [vp, C.c_int, vp]),
+            ("lvt_amd_get_sensor_window", [vp, C.c_int, C.c_int, vp, vp]),
+            ("lvt_amd_convert_sensor_device", [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp])):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes, fn.restype = argtypes, C.c_int
@@ -405,6 +419,68 @@ def equalisation_plan(cfg: Equalisation, width: int, height: int):
     d = dict(zip(("Wp", "Hp", "tile_w", "tile_h", "area", "clip"), (int(x) for x in out)))
     d["lut_scale"] = np.float32(scale.value)
     return d
+
+
+class SensorFormat(C.Structure):
+    """lvt_amd_sensor_format: the camera's own pixel layout, turned into 8-bit gray at the head of the feature stage (include/lvt_amd_ext.h, SENSOR FORMATS) --
+    format SENSOR_NONE = off, a Bayer pattern, SENSOR_YUYV / SENSOR_UYVY, or SENSOR_MONO16 with a window: fixed [lo, hi] (auto_window = 0) or found per
+    frame from the frame's histogram (auto_window = 1: lo_permille / hi_permille of the pixels may fall below / above it, min_span is its smallest width)"""
+    _fields_ = [("format", C.c_int), ("auto_window", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("lo_permille", C.c_int), ("hi_permille", C.c_int),
+                ("min_span", C.c_int), ("reserved", C.c_int * 1)]
+
+    def __init__(self, format=SENSOR_NONE, auto_window=0, lo=0, hi=65535, lo_permille=0, hi_permille=0, min_span=1):
+        super().__init__(int(format), int(auto_window), int(lo), int(hi), int(lo_permille), int(hi_permille), int(min_span))
+
+    def __repr__(self):
+        return (f"SensorFormat(format={int(self.format)}, auto_window={int(self.auto_window)}, lo={int(self.lo)}, hi={int(self.hi)}, "
+                f"lo_permille={int(self.lo_permille)}, hi_permille={int(self.hi_permille)}, min_span={int(self.min_span)})")
+
+
+def _sensor_format_of(handle, seq):
+    return _record_of("lvt_amd_get_sensor_format", SensorFormat, handle, seq)
+
+
+def _sensor_format_arg(cfg, kw):
+    if cfg is None:
+        cfg = SensorFormat(**kw) if kw else SensorFormat(SENSOR_NONE)   # (None: off)
+    elif not isinstance(cfg, SensorFormat):
+        cfg = SensorFormat(int(cfg), **kw)                               # (a bare format constant)
+    return cfg
+
+
+def _sensor_window_of(handle, seq, eye):
+    lo, hi = C.c_int(0), C.c_int(0)
+    rc = load_library().lvt_amd_get_sensor_window(handle, int(seq), int(eye), C.byref(lo), C.byref(hi))
+    if rc < 0:
+        raise IndexError(f"lvt_amd_get_sensor_window: bad handle, no sequence {seq} or no image {eye}")
+    return (lo.value, hi.value) if rc == 1 else None
+
+
+def sensor_plane(img, fmt: int):
+    """a sensor's host plane as bytes, (H, W) for a Bayer mosaic and (H, W, 2) for the 16-bit-per-pixel formats: a YUV 4:2:2 plane may come as (H, 2 W) or
+    (H, W, 2) uint8, a MONO16 plane is (H, W) uint16 (little-endian, as this host stores it).  Views, no copies, where the array is contiguous."""
+    fmt = int(fmt)
+    if fmt == SENSOR_MONO16:
+        a = img if (isinstance(img, np.ndarray) and img.dtype == np.uint16 and img.flags.c_contiguous) else np.ascontiguousarray(img, dtype=np.uint16)
+        if a.ndim != 2:
+            raise ValueError(f"a MONO16 plane of shape {a.shape}: expected (H, W) uint16")
+        return a.view(np.uint8).reshape(a.shape[0], a.shape[1], 2)
+    a = img if (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags.c_contiguous) else np.ascontiguousarray(img, dtype=np.uint8)
+    if fmt in (SENSOR_YUYV, SENSOR_UYVY) and a.ndim == 2:
+        if a.shape[1] % 2:
+            raise ValueError(f"a YUV 4:2:2 plane of shape {a.shape}: a row is 2 W bytes")
+        return a.reshape(a.shape[0], a.shape[1] // 2, 2)
+    return a
+
+
+def convert_sensor_device(cfg: SensorFormat, d_src: int, src_pitch: int, width: int, height: int, d_dst: int, dst_pitch: int):
+    """stage entry: the sensor-format conversion alone on device planes (d_src: `height` rows of src_pitch bytes, any address -- MONO16: even --; d_dst
+    4-byte aligned, dst_pitch % 4 == 0 and >= width: every byte of height x dst_pitch is written, the padding columns as zero).  Returns (rc, window):
+    (0, (lo, hi)) for MONO16, (0, None) otherwise, (-1, None) on a refusal, whose sentence is last_call_error()."""
+    win = (C.c_int * 2)(0, 0)
+    rc = load_library().lvt_amd_convert_sensor_device(C.byref(cfg) if cfg is not None else None, C.c_void_p(d_src), int(src_pitch), int(width), int(height),
+                                                      C.c_void_p(d_dst), int(dst_pitch), win)
+    return rc, ((win[0], win[1]) if rc == 0 and int(cfg.format) == SENSOR_MONO16 else None)
 
 
 class Reduction(C.Structure):
@@ -888,7 +964,12 @@ class LvtSystem:
     def __init__(self, handle, sensor_type):
         self._h = handle
         self._sensor = sensor_type
-        self._bpp = 1   # bytes per pixel of the handle's pixel format (set_pixel_format)
+        self._bpp = 1   # bytes per pixel of the handle's pixel format (set_pixel_format), or of its sensor format
+        self._sfmt = SENSOR_NONE   # the handle's sensor format (set_sensor_format)
+
+    def _img(self, img):
+        """a host image as the entry points take it: (H, W) gray, (H, W, bpp) colour, or the sensor's plane (sensor_plane)"""
+        return _u8(sensor_plane(img, self._sfmt) if self._sfmt else img, self._bpp)
 
     # lvt_system::create(const lvt_parameters&, eSensor)  -- lvt_system.cpp:70-127
     @classmethod
@@ -971,9 +1052,9 @@ class LvtSystem:
     def track(self, img1, img2, depth_scale=None):
         """RGB-D: img2 is the depth image -- floats (metres), or a uint16 array of raw sensor units with depth_scale = metres per unit"""
         R = np.zeros((3, 3)); t = np.zeros(3)
-        a = _u8(img1, self._bpp)
+        a = self._img(img1)
         if self._sensor == eSensor_STEREO:
-            b = _u8(img2, self._bpp)
+            b = self._img(img2)
             load_library().lvt_track(self._h, _p(a), _p(b), a.shape[0], a.shape[1], _p(R), _p(t))
         elif isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
@@ -988,7 +1069,7 @@ class LvtSystem:
     # lvt_system::track_with_external_corners  -- lvt_system.cpp:209-250
     def track_with_external_corners(self, left, right, corners_left, corners_right):
         R = np.zeros((3, 3)); t = np.zeros(3)
-        a, b = _u8(left, self._bpp), _u8(right, self._bpp)
+        a, b = self._img(left), self._img(right)
         cl = np.ascontiguousarray(corners_left, dtype=np.float64).reshape(-1, 2)
         cr = np.ascontiguousarray(corners_right, dtype=np.float64).reshape(-1, 2)
         load_library().lvt_track_with_external_corners(self._h, _p(a), _p(b), a.shape[0], a.shape[1], _p(cl), len(cl),
@@ -1021,9 +1102,9 @@ class LvtSystem:
     def track_async(self, img1, img2, depth_scale=None) -> int:
         """lvt_amd_track_async / lvt_amd_track_rgbd_async: HOST images, the call returns once the frame is enqueued (0) or rejected (-1).
         The arrays are used as they are (no copy here): a page-locked one must stay alive and unchanged until the frame is collected."""
-        a = _u8(img1, self._bpp)   # (a contiguous uint8 array passes through as it is)
+        a = self._img(img1)   # (a contiguous uint8 array passes through as it is)
         if self._sensor == eSensor_STEREO:
-            b = _u8(img2, self._bpp)
+            b = self._img(img2)
             return load_library().lvt_amd_track_async(self._h, _p(a), _p(b), a.shape[0], a.shape[1])
         if isinstance(img2, np.ndarray) and img2.dtype == np.uint16:
             if depth_scale is None:
@@ -1062,12 +1143,32 @@ class LvtSystem:
         """PIX_GRAY8 ... PIX_RGBA8: every frame handed to this system from now on is in that format -- host images (H, W, bpp) uint8, device planes with any
         base address and any pitch >= W * bpp; the conversion to gray is the first launch of the frame's feature stage.  0: done; -1: refused (last_error())."""
         rc = load_library().lvt_amd_set_pixel_format(self._h, int(fmt))
-        if rc == 0:
+        if rc == 0 and not self._sfmt:   # (GRAY8 on a handle with a sensor format is accepted and changes nothing)
             self._bpp = PIX_BPP[int(fmt)]
         return rc
 
     def pixel_format(self) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, 0)
+
+    def set_sensor_format(self, cfg=None, **kw) -> int:
+        """a SensorFormat (or a SENSOR_* constant, or its arguments: format=, auto_window=, lo=, hi=, lo_permille=, hi_permille=, min_span=): every frame handed
+        to this system from now on is the sensor's plane -- a Bayer mosaic (H, W) uint8, YUV 4:2:2 (H, 2 W) uint8, MONO16 (H, W) uint16; device planes at any
+        address and any pitch that holds a row -- and is turned into gray by the first launch of the frame's feature stage.  None or SENSOR_NONE: plain
+        frames again.  0: done; -1: refused (last_error())."""
+        cfg = _sensor_format_arg(cfg, kw)
+        rc = load_library().lvt_amd_set_sensor_format(self._h, C.byref(cfg))
+        if rc == 0 and (self._sfmt or int(cfg.format)):   # (SENSOR_NONE on a handle without a sensor format is accepted and changes nothing: a colour handle keeps its bpp)
+            self._sfmt = int(cfg.format)
+            self._bpp = SENSOR_BPP[self._sfmt]
+        return rc
+
+    def sensor_format(self):
+        """the SensorFormat in force, or None"""
+        return _sensor_format_of(self._h, 0)
+
+    def sensor_window(self, eye: int = 0):
+        """(lo, hi) the MONO16 image `eye` of the last collected frame was mapped with (a fixed window: the record's), or None"""
+        return _sensor_window_of(self._h, 0, eye)
 
     def set_depth_camera(self, cam) -> int:
         """a DepthCamera: every RGB-D frame handed to this system from now on brings its depth plane as the sensor delivers it -- (cam.height, cam.width),
@@ -1244,7 +1345,7 @@ class LvtSystem:
         name = C.create_string_buffer(64); ms = C.c_double(0); calls = C.c_long(0)
         for slot in range(64):
             if not load_library().lvt_amd_profile_read(self._h, slot, name, 64, C.byref(ms), C.byref(calls)):
-                if slot >= 29:   # (past the last slot; the slots below it may be absent on this handle)
+                if slot >= 32:   # (past the last slot; the slots below it may be absent on this handle)
                     break
                 continue
             out.append((name.value.decode(), ms.value, calls.value))
@@ -1362,6 +1463,17 @@ class LvtBatch:
 
     def pixel_format(self, seq: int) -> int:
         return load_library().lvt_amd_get_pixel_format(self._h, int(seq))
+
+    def set_sensor_format(self, seq: int, cfg=None, **kw) -> int:
+        """LvtSystem.set_sensor_format for sequence `seq` of the batch: its planes are the sensor's from then on, the other sequences' are not"""
+        cfg = _sensor_format_arg(cfg, kw)
+        return load_library().lvt_amd_batch_set_sensor_format(self._h, int(seq), C.byref(cfg))
+
+    def sensor_format(self, seq: int):
+        return _sensor_format_of(self._h, seq)
+
+    def sensor_window(self, seq: int, eye: int = 0):
+        return _sensor_window_of(self._h, seq, eye)
 
     def set_depth_camera(self, seq: int, cam) -> int:
         """LvtSystem.set_depth_camera for sequence `seq` of the batch: its depth planes are the sensor's from then on, the other sequences' are not"""

@@ -189,6 +189,7 @@ static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) 
                                       "lvt_amd_batch_set_pixel_format on a handle that is not a batch (use lvt_amd_set_pixel_format)"};
     return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
         if (format < PIX_GRAY8 || format > PIX_RGBA8) return refuse_unchanged(t, call.who, "unknown pixel format " + std::to_string(format));
+        if (format != PIX_GRAY8 && c->has_sensor(seq)) return refuse_unchanged(t, call.who, "a colour pixel format on a sequence with a sensor format: a frame is one or the other (unset it first: lvt_amd_set_sensor_format, format LVT_AMD_SENSOR_NONE)");
         if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the format before the first frame or after every frame has been collected");
         if (format == c->fmt_of(seq)) return 0;
         if (format != PIX_GRAY8) give_gray_planes(c, seq);
@@ -196,6 +197,170 @@ static int set_pixel_format(lvt_handle h, int seq, bool batch_call, int format) 
         c->n_colour = put_seq_value(c, c->pixfmt, 1, (int)PIX_GRAY8, seq, {format}, [](int f) { return f != PIX_GRAY8; });
         return 0;
     });
+}
+
+// ---- sensor formats: Bayer, YUV 4:2:2, 16-bit gray per handle / per sequence of a batch (Context::sens, k_sensor.hip) -------------------------------------
+// "" when the record passes on a sequence whose frames are fW x fH: names the offending field and its limits otherwise
+static std::string sensor_format_check(const lvt_amd_sensor_format &f, int fW, int fH) {
+    if (f.format == SENSOR_NONE) return "";
+    if (!sensor_known(f.format)) return "unknown sensor format " + std::to_string(f.format);
+    if (f.format == SENSOR_MONO16) {
+        if (f.auto_window < 0 || f.auto_window > 1) return "a MONO16 format with auto_window = " + std::to_string(f.auto_window) + " (0 ... 1)";
+        if (!f.auto_window) {
+            if (f.lo < 0 || f.lo > 65534) return "a MONO16 window with lo = " + std::to_string(f.lo) + " (0 ... 65534)";
+            if (f.hi <= f.lo || f.hi > 65535) return "a MONO16 window with hi = " + std::to_string(f.hi) + " (lo + 1 ... 65535)";
+        } else {
+            if (f.lo_permille < 0 || f.lo_permille > 499) return "a MONO16 auto window with lo_permille = " + std::to_string(f.lo_permille) + " (0 ... 499)";
+            if (f.hi_permille < 0 || f.hi_permille > 499) return "a MONO16 auto window with hi_permille = " + std::to_string(f.hi_permille) + " (0 ... 499)";
+            if (f.min_span < 1 || f.min_span > 65535) return "a MONO16 auto window with min_span = " + std::to_string(f.min_span) + " (1 ... 65535)";
+        }
+    }
+    if (sensor_is_bayer(f.format)) {
+        if (fW < 2) return "a Bayer format on frames of width = " + std::to_string(fW) + " (2 or more)";
+        if (fH < 2) return "a Bayer format on frames of height = " + std::to_string(fH) + " (2 or more)";
+    }
+    return "";
+}
+// one image's descriptor (win / hist: the auto window's two buffers, nullptr for every other record)
+static SensorImg sensor_img(const lvt_amd_sensor_format &f, const uint8_t *src, int src_pitch, int w, int h, uint8_t *dst, int dst_pitch, const int *win, uint32_t *hist) {
+    SensorImg I{};
+    I.src = src, I.dst = dst, I.win = win, I.hist = hist, I.src_pitch = src_pitch, I.dst_pitch = dst_pitch, I.w = w, I.h = h, I.fmt = f.format;
+    I.lo = f.lo, I.hi = f.hi, I.lo_pm = f.lo_permille, I.hi_pm = f.hi_permille, I.min_span = f.min_span;
+    return I;
+}
+static dim3 sensor_hist_grid(int pixels2, int n) {
+    const int per = SENSOR_HIST_THREADS * SENSOR_HIST_WORDS;
+    return dim3((unsigned)((pixels2 + per - 1) / per), (unsigned)n);
+}
+// Every image of every sequence that has a sensor format and a frame in this step -- both eyes of a stereo sequence, the one image of an RGB-D sequence -- in
+// one launch, in k_gray_frames' place: AHEAD of the reduce, rectify and equalise blocks and of the buffer gate.  The ordering argument is the colour
+// formats': the gray planes (parity `par`) were read last by the feature stage of frame enq - NPAR (k_reduce_frames, k_rectify_frames, k_clahe_*, or
+// k_score, k_gather, k_brief_img: all on this stream, all enqueued before), and the source was written by a pull on this stream or belongs to the caller:
+// stream order alone covers the hand-over, no gate.  The auto window's launches come first, on the same stream: k_sensor_hist adds into bins that
+// k_sensor_levels of the frame before left zero (same stream, enqueued before), k_sensor_levels writes the step's windows into this ring slot's record,
+// which k_sensor_frames behind it reads and which nothing writes again before the slot is reused, RING frames later, behind this frame's collection.
+static void convert_sensor_frames(Context *c, int slot, int par, int Bz) {
+    FrameArgs *fw = &frame_args(c, slot);
+    const int eyes = (c->sensor == 2) ? 1 : 2;
+    if (!c->sens_mapped.empty()) std::fill_n(c->sens_mapped.begin() + (size_t)slot * c->B, (size_t)c->B, (uint8_t)0);
+    auto win_of = [&](int s, int e) -> int * { return c->has_sensor_auto(s) ? c->d_sens_win + (((size_t)slot * c->B + s) * 2 + e) * 2 : nullptr; };
+    auto img_of = [&](int s, int e) {
+        return sensor_img(c->sens[(size_t)s], fw[s].img[e], fw[s].img_pitch, c->frame_W(s), c->frame_H(s), c->d_gray[((size_t)s * NPAR + par) * 2 + e], c->frame_pitch(s), win_of(s, e),
+                          c->has_sensor_auto(s) ? c->d_sens_hist[(size_t)s] + (size_t)e * SENSOR_BINS : nullptr);
+    };
+    if (c->n_sensor_auto) {
+        int words = 0;
+        TablePacker pk(&SensorTable::im, [&](const SensorTable &tab, int n, bool first) {
+            if (first) {
+                LAUNCH(31, c->stream_f, k_sensor_hist, sensor_hist_grid(words, n), dim3(SENSOR_HIST_THREADS), 0, tab);
+                LAUNCH(32, c->stream_f, k_sensor_levels, dim3(n), dim3(256), 0, tab);
+            } else {
+                hipLaunchKernelGGL(k_sensor_hist, sensor_hist_grid(words, n), dim3(SENSOR_HIST_THREADS), 0, c->stream_f, tab);
+                hipLaunchKernelGGL(k_sensor_levels, dim3(n), dim3(256), 0, c->stream_f, tab);
+            }
+            words = 0;
+        });
+        for (int s = 0; s < Bz; s++) {
+            if (!c->has_sensor_auto(s) || fw[s].absent) continue;
+            SensorImg *im = pk.add(eyes);
+            for (int e = 0; e < eyes; e++) {
+                im[e] = img_of(s, e);
+                words = std::max(words, (im[e].w + 1) / 2 * im[e].h);
+            }
+        }
+        pk.flush();
+    }
+    int words = 0;
+    TablePacker pk(&SensorTable::im, [&](const SensorTable &tab, int n, bool first) {
+        LAUNCH_TABLE(first, 30, k_sensor_frames, dim3((words + 255) / 256, n), tab);
+        words = 0;
+    });
+    for (int s = 0; s < Bz; s++) {
+        if (!c->has_sensor(s) || fw[s].absent) continue;
+        SensorImg *im = pk.add(eyes);
+        for (int e = 0; e < eyes; e++) {
+            im[e] = img_of(s, e);
+            words = std::max(words, im[e].dst_pitch / 4 * im[e].h);
+        }
+        for (int e = 0; e < eyes; e++) fw[s].img[e] = im[e].dst;
+        if (eyes == 1) fw[s].img[1] = fw[s].img[0];
+        fw[s].img_pitch = c->frame_pitch(s);
+        if (s == 0) c->ring_converted[slot] = true;
+        if (c->sens[(size_t)s].format == SENSOR_MONO16) c->sens_mapped[(size_t)slot * c->B + s] = 1;
+    }
+    pk.flush();
+}
+// sequence seq's converted planes go back (its sensor format was unset: nothing else uses them, a colour format and a sensor format exclude each other)
+static void take_gray_planes(Context *c, int seq) {
+    if (c->d_gray.empty() || c->gray_bytes[(size_t)seq] == 0) return;
+    for (int par = 0; par < NPAR; par++)
+        for (int e = 0; e < 2; e++) {
+            uint8_t *&d = c->d_gray[((size_t)seq * NPAR + par) * 2 + e];
+            c->dfree(d);
+            d = nullptr;
+        }
+    c->gray_bytes[(size_t)seq] = 0;
+}
+static int set_sensor_format(lvt_handle h, int seq, bool batch_call, const lvt_amd_sensor_format *f) {
+    static const PropertyCall call = {"lvt_amd_set_sensor_format", 0,
+                                      {"a pooled handle (its frames ride a chain shared with other handles) (nothing was changed)", nullptr,
+                                       "a batch handle takes its sensor formats per sequence through lvt_amd_batch_set_sensor_format (nothing was changed)"},
+                                      "lvt_amd_batch_set_sensor_format on a handle that is not a batch (use lvt_amd_set_sensor_format)"};
+    return set_property(h, call, seq, batch_call, [&](lvt_handle t, Context *c) -> int {
+        if (!f) return refuse_unchanged(t, call.who, "a NULL record (format LVT_AMD_SENSOR_NONE unsets a sensor format)");
+        const std::string why = sensor_format_check(*f, c->frame_W(seq), c->frame_H(seq));
+        if (!why.empty()) return refuse_unchanged(t, call.who, why);
+        const bool on = f->format != SENSOR_NONE;
+        if (on && c->fmt_of(seq) != PIX_GRAY8)
+            return refuse_unchanged(t, call.who, "a sensor format on a sequence with a colour pixel format: a frame is one or the other (return it to LVT_AMD_PIX_GRAY8 first: lvt_amd_set_pixel_format)");
+        if (frames_in_flight(c)) return refuse_unchanged(t, call.who, "frames in flight: set the sensor format before the first frame or after every frame has been collected");
+        if (!on && !c->has_sensor(seq)) return 0;
+        lvt_amd_sensor_format rec = on ? *f : lvt_amd_sensor_format{};
+        rec.reserved[0] = 0;
+        if (seq == 0) {  // (the host entry points' staging and planes are sized by the frame's bytes; the last frame went in under ANOTHER record)
+            frame_planes_release(c);
+            std::fill(std::begin(c->ring_converted), std::end(c->ring_converted), false);
+        }
+        c->n_sensor = put_seq_value(c, c->sens, 1, lvt_amd_sensor_format{}, seq, {rec}, [](const lvt_amd_sensor_format &x) { return x.format != SENSOR_NONE; });
+        c->n_sensor_auto = 0;
+        for (int s = 0; s < c->B; s++) c->n_sensor_auto += c->has_sensor_auto(s) ? 1 : 0;
+        if (c->sens_mapped.empty()) c->sens_mapped.assign((size_t)RING * c->B, 0);
+        std::fill(c->sens_mapped.begin(), c->sens_mapped.end(), (uint8_t)0);
+        if (on) give_gray_planes(c, seq);
+        else take_gray_planes(c, seq);
+        if (c->d_sens_hist.empty()) c->d_sens_hist.assign((size_t)c->B, nullptr);
+        uint32_t *&hist = c->d_sens_hist[(size_t)seq];
+        if (c->has_sensor_auto(seq)) {
+            if (!hist) hist = c->dalloc<uint32_t>((size_t)2 * SENSOR_BINS);
+            if (!c->d_sens_win) c->d_sens_win = c->dalloc<int>((size_t)RING * c->B * 4);
+        } else {
+            c->dfree(hist), hist = nullptr;
+            if (c->n_sensor_auto == 0) c->dfree(c->d_sens_win), c->d_sens_win = nullptr;
+        }
+        return 0;
+    });
+}
+// the window image `eye` of sequence seq was mapped with in the last collected frame
+static int get_sensor_window(lvt_handle h, int seq, int eye, int *lo, int *hi) {
+    h = resolve_handle(h);
+    if (is_slot(h)) return (seq == 0 && (eye == 0 || eye == 1)) ? 0 : -1;
+    if (!is_ctx(h)) return -1;
+    Context *c = static_cast<Context *>(h);
+    if (seq < 0 || seq >= c->B || eye < 0 || eye > (c->sensor == 2 ? 0 : 1)) return -1;
+    DeviceGuard guard(c);
+    try {
+        // (frames that are still in flight stay in flight: the LAST COLLECTED frame's record is read, and its k_sensor_levels has run -- the frame was collected.
+        //  A synchronous call's frame whose pose has been returned is nobody's to collect: it is drained, as in frames_in_flight)
+        if (c->early_pending) drain(c);
+        if (c->done == 0 || !c->has_sensor(seq) || c->sens[(size_t)seq].format != SENSOR_MONO16 || !c->sens_mapped[(size_t)c->last_slot * c->B + seq]) return 0;
+        int w[2] = {c->sens[(size_t)seq].lo, c->sens[(size_t)seq].hi};
+        if (c->has_sensor_auto(seq)) HIPCHK(c, hipMemcpy(w, c->d_sens_win + (((size_t)c->last_slot * c->B + seq) * 2 + eye) * 2, sizeof(w), hipMemcpyDeviceToHost));
+        if (lo) *lo = w[0];
+        if (hi) *hi = w[1];
+        return 1;
+    } catch (...) {
+    }
+    return -1;
 }
 
 // ---- large frames: a reduction per handle / per sequence of a batch (Context::red, k_reduce.hip) -------------------------------------------------------
@@ -278,7 +443,7 @@ static int set_reduction(lvt_handle h, int seq, bool batch_call, const lvt_amd_r
         give_red_planes(c, seq, on);
         if (c->frame_W(seq) != fW || c->frame_H(seq) != fH) {  // the frame's size changed: what is sized by its bytes follows, as in set_rectifiers
             if (seq == 0) frame_planes_release(c);
-            if (c->fmt_of(seq) != PIX_GRAY8) give_gray_planes(c, seq);
+            if (c->converts(seq)) give_gray_planes(c, seq);
         }
         return 0;
     });
@@ -342,7 +507,7 @@ static int set_rectifiers(lvt_handle h, int seq, bool batch_call, lvt_amd_rectif
         c->n_rect = put_seq_value(c, c->rect, 2, (Rectifier *)nullptr, seq, {rl, rr}, [](const Rectifier *r) { return r != nullptr; });
         if (c->frame_W(seq) != fW || c->frame_H(seq) != fH) {  // the frame's size changed: what is sized by its bytes follows (a same-size attach: nothing)
             if (seq == 0) frame_planes_release(c);
-            if (c->fmt_of(seq) != PIX_GRAY8) give_gray_planes(c, seq);
+            if (c->converts(seq)) give_gray_planes(c, seq);
         }
         return 0;
     });
@@ -857,6 +1022,49 @@ LVT_API int lvt_amd_get_pixel_format(lvt_handle h, int seq) {
     if (!is_ctx(h)) return -1;
     const Context *c = static_cast<const Context *>(h);
     return (seq < 0 || seq >= c->B) ? -1 : c->fmt_of(seq);
+}
+
+LVT_API int lvt_amd_set_sensor_format(lvt_handle h, const lvt_amd_sensor_format *f) { return set_sensor_format(h, 0, false, f); }
+LVT_API int lvt_amd_batch_set_sensor_format(lvt_handle h, int seq, const lvt_amd_sensor_format *f) { return set_sensor_format(h, seq, true, f); }
+LVT_API int lvt_amd_get_sensor_format(lvt_handle h, int seq, lvt_amd_sensor_format *out) { return get_seq_record(h, seq, &Context::has_sensor, &Context::sens, out); }
+LVT_API int lvt_amd_get_sensor_window(lvt_handle h, int seq, int eye, int *lo, int *hi) { return get_sensor_window(h, seq, eye, lo, hi); }
+// the stage alone on caller planes: tables of one image, the null stream (an auto window: the histogram and the levels first); returns when the plane is written
+LVT_API int lvt_amd_convert_sensor_device(const lvt_amd_sensor_format *f, const void *src, int src_pitch_bytes, int width, int height, uint8_t *dst, int dst_pitch,
+                                          int window_out[2]) {
+    const char *who = "lvt_amd_convert_sensor_device";
+    if (window_out) window_out[0] = window_out[1] = 0;
+    if (!f || !src || !dst) return refuse_call(who, "a NULL argument (nothing was launched)");
+    if (f->format == SENSOR_NONE) return refuse_call(who, "format LVT_AMD_SENSOR_NONE converts nothing (nothing was launched)");
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) return refuse_call(who, "a side outside 1 ... 16384 (nothing was launched)");
+    const std::string why = sensor_format_check(*f, width, height);
+    if (!why.empty()) return refuse_call(who, why + " (nothing was launched)");
+    const int row = width * sensor_bpp(f->format);
+    if (src_pitch_bytes < row) return refuse_call(who, "a source pitch of " + std::to_string(src_pitch_bytes) + " does not hold a row of " + std::to_string(row) + " bytes (nothing was launched)");
+    if (f->format == SENSOR_MONO16 && (((uintptr_t)src | (uintptr_t)(unsigned)src_pitch_bytes) & 1))
+        return refuse_call(who, "a MONO16 plane needs an even address and an even pitch (nothing was launched)");
+    if (dst_pitch < width || (dst_pitch & 3) || ((uintptr_t)dst & 3))
+        return refuse_call(who, "a destination pitch smaller than the width or no multiple of 4, or a destination that is not 4-byte aligned (nothing was launched)");
+    const bool aut = f->format == SENSOR_MONO16 && f->auto_window != 0;
+    StageScratch S;  // (lvt_stage_entries.h)
+    uint32_t *hist = aut ? S.buf<uint32_t>(SENSOR_BINS) : nullptr;
+    int *win = aut ? S.buf<int>(2) : nullptr;
+    if (!S.ok()) return refuse_call(who, "no device memory for the histogram (nothing was launched)");
+    SensorTable tab;
+    std::memset(&tab, 0, sizeof(tab));
+    tab.im[0] = sensor_img(*f, static_cast<const uint8_t *>(src), src_pitch_bytes, width, height, dst, dst_pitch, win, hist);
+    if (aut) {
+        hipLaunchKernelGGL(k_sensor_hist, sensor_hist_grid((width + 1) / 2 * height, 1), dim3(SENSOR_HIST_THREADS), 0, 0, tab);
+        hipLaunchKernelGGL(k_sensor_levels, dim3(1), dim3(256), 0, 0, tab);
+    }
+    hipLaunchKernelGGL(k_sensor_frames, dim3((unsigned)((dst_pitch / 4 * height + 255) / 256), 1), dim3(256), 0, 0, tab);
+    hipError_t err = hipGetLastError();  // (the launches'; reading it clears it, so it is kept)
+    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+    if (err != hipSuccess) return refuse_call(who, hipGetErrorString(err));
+    if (f->format == SENSOR_MONO16 && window_out) {
+        window_out[0] = f->lo, window_out[1] = f->hi;
+        if (aut && !S.fetch(window_out, win, 2)) return refuse_call(who, "the window could not be read back");
+    }
+    return 0;
 }
 
 LVT_API int lvt_amd_set_depth_camera(lvt_handle h, const lvt_amd_depth_camera *cam) { return set_depth_camera(h, 0, false, cam); }

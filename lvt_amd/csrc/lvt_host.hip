@@ -20,6 +20,7 @@
 #include "k_lists.hip"
 #include "k_rectify.hip"
 #include "k_reduce.hip"
+#include "k_sensor.hip"
 #include "k_depthreg.hip"
 #include "k_equalise.hip"
 #include "k_depthguard.hip"
@@ -324,7 +325,21 @@ struct Context {
     int n_colour = 0;                  // sequences with a colour format
     bool ring_converted[RING] = {};    // per un-collected / last frame: sequence 0's image went through k_gray_frames (what lvt_amd_get_plane(.., 3, ..) may read back)
     int fmt_of(int s) const { return n_colour > 0 ? pixfmt[(size_t)s] : PIX_GRAY8; }
-    int bpp_of(int s) const { return pix_bpp(fmt_of(s)); }
+    // SENSOR formats (lvt_amd_set_sensor_format / lvt_amd_batch_set_sensor_format): a sequence with one takes the sensor's plane -- a Bayer mosaic, YUV 4:2:2,
+    // 16-bit gray -- through every frame-taking entry point.  It takes the colour formats' route and their planes (a sequence has one or the other, never
+    // both): the FrameArgs name the sensor's plane, and enqueue_frame puts ONE k_sensor_frames launch in k_gray_frames' place that writes d_gray and points
+    // the frame at it; a MONO16 sequence with an auto window gets k_sensor_hist and k_sensor_levels in front.  A property of the handle, not state.
+    std::vector<lvt_amd_sensor_format> sens;  // [B] (empty until the first set); format == 0: none
+    std::vector<uint32_t *> d_sens_hist;      // [B] 2 x 4096 bins of a sequence with an auto window (zero between frames: k_sensor_levels clears them)
+    int *d_sens_win = nullptr;                // [RING][B][2 eyes][lo, hi]: the windows k_sensor_levels found, per un-collected frame (allocated with the first auto window)
+    std::vector<uint8_t> sens_mapped;         // [RING][B] != 0: the sequence's frame of that step went through k_sensor_frames as MONO16
+    int n_sensor = 0, n_sensor_auto = 0;      // sequences with a sensor format / with an auto window
+    bool has_sensor(int s) const { return n_sensor > 0 && sens[(size_t)s].format != SENSOR_NONE; }
+    bool has_sensor_auto(int s) const { return has_sensor(s) && sens[(size_t)s].format == SENSOR_MONO16 && sens[(size_t)s].auto_window != 0; }
+    // "this sequence converts": it has a colour or a sensor format -- its frames are byte images bpp_of(s) * width wide that a launch at the head of the feature
+    // stage turns into d_gray (a Bayer sequence converts at one byte per pixel)
+    bool converts(int s) const { return fmt_of(s) != PIX_GRAY8 || has_sensor(s); }
+    int bpp_of(int s) const { return has_sensor(s) ? sensor_bpp(sens[(size_t)s].format) : pix_bpp(fmt_of(s)); }
     // host entry points of a colour handle pull the colour bytes -- a byte image n_cols * bpp wide -- into these planes (allocated when first needed, sized for
     // 4 bytes per pixel): per feature buffer for the synchronous calls, per RING slot for the asynchronous ones
     uint8_t *d_col[NPAR][2] = {};
@@ -395,7 +410,7 @@ struct Context {
     std::string err;
     // optional per-kernel timing with HIP events on the launch streams (lvt_amd_profile_*)
     bool prof = false;
-    static constexpr int PROF_SLOTS = 30;
+    static constexpr int PROF_SLOTS = 33;
     hipEvent_t ev[PROF_SLOTS][2] = {};
     bool ev_used[PROF_SLOTS] = {};
     double prof_ms[PROF_SLOTS] = {};
@@ -960,7 +975,7 @@ static const char *kProfNames[Context::PROF_SLOTS] = {
     "k_feat_begin", "k_gate [early stream: waits for the previous k_pnp]", "k_score", "k_cells(pass0)", "k_rectify_frames", "k_gather(+ the rare retry pass)", "k_brief", "k_gate_late [waits for the early stream]",
     "k_match_map(wait for the early stream + begin + new points)", "k_early_map [early stream]", "k_early_mid [early stream]", "k_hamming_batched_lists(map) [early stream]", "k_track_mid(resolve+pass2+bookkeep+cull)", "k_pnp(+project staged)", "k_gray_frames",
     "k_pose_info", "k_candidates(staged)", "k_depth_clear", "k_candidates(row) [early stream]", "k_hamming_batched_lists(row)", "k_triangulate(staged update+row resolve+triangulate+finalize)", "k_depth_register",
-    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard", "k_label_mask", "k_reduce_frames"};
+    "k_state_pack", "k_state_unpack", "k_clahe_lut", "k_clahe_apply", "k_mask_features", "k_depth_guard", "k_label_mask", "k_reduce_frames", "k_sensor_frames", "k_sensor_hist", "k_sensor_levels"};
 
 #define LAUNCH(slot, st, kern, grid, block, lds, ...)                              \
     do {                                                                           \
@@ -1044,6 +1059,7 @@ struct DepthRegPlan {
 };
 static void convert_colour_frames(Context *c, int slot, int par, int Bz);
 static void reduce_frames(Context *c, int slot, int par, int Bz);
+static void convert_sensor_frames(Context *c, int slot, int par, int Bz);
 static void rectify_raw_frames(Context *c, int slot, int par, int Bz);
 static void equalise_frames(Context *c, int slot, int par, int Bz);
 static void begin_depth_registration(Context *c, int slot, int par, int Bz, DepthRegPlan &plan);
@@ -1100,6 +1116,7 @@ static void enqueue_frame(Context *c) {
     c->ring_converted[slot] = c->ring_reduced[slot] = c->ring_registered[slot] = c->ring_equalised[slot] = c->ring_masked[slot] = c->ring_guarded[slot] = false;
     if (!c->label_built.empty()) std::fill_n(c->label_built.begin() + (size_t)slot * B * 2, (size_t)B * 2, (uint8_t)0);
     if (c->n_colour) convert_colour_frames(c, slot, par, Bz);
+    if (c->n_sensor) convert_sensor_frames(c, slot, par, Bz);  // (a sequence has a colour or a sensor format, never both: the same place in the order)
     if (c->n_reduce) reduce_frames(c, slot, par, Bz);
     if (c->n_rect) rectify_raw_frames(c, slot, par, Bz);
     if (c->n_equal) equalise_frames(c, slot, par, Bz);
@@ -1414,8 +1431,12 @@ static const char *kReducedNoDepthCamera = "an RGB-D frame on a sequence with a 
 // pitch of a caller's device plane of sequence s: a rectified frame feeds k_score's word loads (a multiple of 16); a RAW frame (rectifiers attached) is read
 // byte-wise by k_rectify_frames: any pitch that holds a row; so is a COLOUR frame by k_gray_frames (a row is cols * bpp bytes) and the gray frame of an
 // EQUALISED sequence by k_clahe_lut / k_clahe_apply; a LARGE frame (a reduction in force) is read by k_reduce_frames, whose byte path takes any base and pitch
+// (a MONO16 sequence's planes are read as 16-bit words: an odd address is refused here, an odd pitch by device_pitch_ok)
+static bool sensor_address_ok(const Context *c, int s, const void *a, const void *b) {
+    return !(c->has_sensor(s) && c->sens[(size_t)s].format == SENSOR_MONO16) || ((((uintptr_t)a | (uintptr_t)b) & 1) == 0);
+}
 static bool device_pitch_ok(const Context *c, int s, int pitch, int cols) {
-    if (c->fmt_of(s) != PIX_GRAY8) return (long long)pitch >= (long long)cols * c->bpp_of(s);
+    if (c->converts(s)) return (long long)pitch >= (long long)cols * c->bpp_of(s) && !(c->has_sensor(s) && c->sens[(size_t)s].format == SENSOR_MONO16 && (pitch & 1));
     return (c->has_rect(s) || c->has_equal(s) || c->has_reduce(s)) ? pitch >= cols : (pitch & 15) == 0;
 }
 
@@ -1857,6 +1878,8 @@ LVT_API int lvt_amd_profile_read(lvt_handle h, int slot, char *name, int name_ca
     if (slot == 27 && c->n_guard == 0 && c->prof_calls[27] == 0) return 0;  // (... and one that never set a depth guard no k_depth_guard)
     if (slot == 28 && c->n_label == 0 && c->prof_calls[28] == 0) return 0;  // (... and one that never set a label-mask record no k_label_mask)
     if (slot == 29 && c->n_reduce == 0 && c->prof_calls[29] == 0) return 0;  // (... and one that never set a reduction no k_reduce_frames)
+    if (slot == 30 && c->n_sensor == 0 && c->prof_calls[30] == 0) return 0;  // (... and one that never set a sensor format no k_sensor_frames)
+    if ((slot == 31 || slot == 32) && c->n_sensor_auto == 0 && c->prof_calls[slot] == 0) return 0;  // (... and one without an auto window no k_sensor_hist / k_sensor_levels)
     std::snprintf(name, name_cap, "%s", kProfNames[slot]);
     *total_ms = c->prof_ms[slot];
     *calls = c->prof_calls[slot];
@@ -1880,7 +1903,7 @@ static void track_device(lvt_handle h, const void *d_left, const void *d_right, 
         Context *c = frame_context(h, who, 1, true, {nullptr, "a stereo entry point on an RGB-D handle (the frame was NOT enqueued; use lvt_amd_track_rgbd_device)", nullptr});
         if (!c) return;
         DeviceGuard guard(c);
-        if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols)) {
+        if (!size_ok(c, n_rows, n_cols) || !device_pitch_ok(c, 0, pitch_bytes, n_cols) || !sensor_address_ok(c, 0, d_left, d_right)) {
             refuse(h, who, "image size / pitch mismatch");
             return;  // outputs untouched, like the reference on an exception
         }
@@ -1967,10 +1990,10 @@ LVT_API int lvt_amd_batch_track_device_async_mixed(lvt_handle h, const void *con
             if (!d_left[s]) continue;
             present++;
             const int fW = c->frame_W(s), fH = c->frame_H(s);  // (a sequence with rectifiers: their source's size)
-            if (!d_right[s] || n_rows[s] != fH || n_cols[s] != fW || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s]) {
+            if (!d_right[s] || n_rows[s] != fH || n_cols[s] != fW || !device_pitch_ok(c, s, pitch_bytes[s], n_cols[s]) || pitch_bytes[s] < n_cols[s] || !sensor_address_ok(c, s, d_left[s], d_right[s])) {
                 char buf[200];
                 std::snprintf(buf, sizeof(buf), "sequence %d: image size / pitch mismatch (%d x %d, pitch %d; expected %d x %d, pitch %s)",
-                              s, n_cols[s], n_rows[s], pitch_bytes[s], fW, fH, c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s) || c->has_reduce(s)) ? "at least the width" : "a multiple of 16");
+                              s, n_cols[s], n_rows[s], pitch_bytes[s], fW, fH, c->has_sensor(s) ? "at least a row of the sensor's plane (MONO16: even, at an even address)" : c->fmt_of(s) != PIX_GRAY8 ? "at least a row of colour pixels" : (c->has_rect(s) || c->has_equal(s) || c->has_reduce(s)) ? "at least the width" : "a multiple of 16");
                 return refuse(h, who, buf);
             }
         }
@@ -1999,7 +2022,7 @@ LVT_API void lvt_amd_batch_track_device_async(lvt_handle h, const void *const *d
         bool pitch_ok = true;  // (one pitch for the whole step: it must suit the raw and the rectified sequences alike)
         bool sizes_ok = true;  // (... and one size: a sequence whose rectifiers have another source size than the rest needs the mixed call)
         for (int s = 0; s < c->B; s++) {
-            pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols);
+            pitch_ok = pitch_ok && device_pitch_ok(c, s, pitch_bytes, n_cols) && sensor_address_ok(c, s, d_left[s], d_right[s]);
             sizes_ok = sizes_ok && n_rows == c->frame_H(s) && n_cols == c->frame_W(s);
         }
         if (!sizes_ok || !pitch_ok) {
@@ -2126,11 +2149,12 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     // a COLOUR handle: the image is a byte image n_cols * bpp wide; it is pulled into the context's colour planes and enqueue_frame converts it from there
     const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp;
-    const bool raw = bpp == 1 && c->resized(0);  // (gray raw frames of another size than the tracker's: planes of their own)
-    if (bpp > 1) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
+    const bool raw = !c->converts(0) && c->resized(0);  // (gray raw frames of another size than the tracker's: planes of their own)
+    const bool conv = c->converts(0);  // (a colour or a sensor format: a Bayer mosaic has bpp == 1 and still converts)
+    if (conv) colour_planes(c, c->d_col[par], rgbd ? 1 : 2);
     if (raw) raw_planes(c, c->d_raw[par], rgbd ? 1 : 2);
-    uint8_t *const *dimg = (bpp > 1) ? c->d_col[par] : raw ? c->d_raw[par] : c->d_img[par];
-    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
+    uint8_t *const *dimg = conv ? c->d_col[par] : raw ? c->d_raw[par] : c->d_img[par];
+    const int ipitch = conv ? c->colour_pitch() : c->frame_pitch(0);
     // (a handle with a depth camera: the depth plane is the sensor's, the camera's size -- staged, pulled and handed on unchanged)
     const size_t dpix = rgbd ? c->depth_px() : 0;
     const int dcols = c->depth_cols();
@@ -2149,7 +2173,7 @@ static void upload_and_track(Context *c, const unsigned char *left, const void *
     if (split) hipLaunchKernelGGL(k_stage_in, dim3(128, 1), dim3(256), 0, sf, s1, s1, dimg[1], dimg[1], row_bytes, n_rows, ipitch);
     else hipLaunchKernelGGL(k_stage_in, dim3(128, rgbd ? 1 : 2), dim3(256), 0, sf, s0, s1, dimg[0], dimg[1], row_bytes, n_rows, ipitch);
     drain(c);
-    FrameArgs f = stereo_args(dimg[0], dimg[(rgbd && (bpp > 1 || raw)) ? 0 : 1], ipitch);  // (an RGB-D handle has one colour plane, and one raw plane)
+    FrameArgs f = stereo_args(dimg[0], dimg[(rgbd && (conv || raw)) ? 0 : 1], ipitch);  // (an RGB-D handle has one colour plane, and one raw plane)
     if (rgbd) {
         // The depth plane (1.2 MB: ~60 us of CPU copy into the staging buffer when the caller's buffer is pageable, ~45 us of PCIe pull)
         // is not needed before k_gather's depth filter.  Both happen once the detection kernels are enqueued -- the copy on the
@@ -2199,10 +2223,10 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     // (a COLOUR handle: byte images n_cols * bpp wide into the context's colour planes, as in upload_and_track; the fused pull carries them like gray ones)
     const int bpp = c->bpp_of(0), row_bytes = n_cols * bpp;
     const size_t npix = (size_t)n_rows * n_cols, nbytes = npix * bpp, plane = (size_t)c->pitch * c->prm.H;
-    const bool raw = bpp == 1 && c->resized(0);  // (as in upload_and_track)
-    if (bpp > 1) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
+    const bool conv = c->converts(0), raw = !conv && c->resized(0);  // (as in upload_and_track)
+    if (conv) colour_planes(c, c->d_col_ring[slot], rgbd ? 1 : 2);
     if (raw) raw_planes(c, c->d_raw_ring[slot], rgbd ? 1 : 2);
-    const int ipitch = (bpp > 1) ? c->colour_pitch() : c->frame_pitch(0);
+    const int ipitch = conv ? c->colour_pitch() : c->frame_pitch(0);
     const size_t dpix = rgbd ? c->depth_px() : 0;  // (a handle with a depth camera: the sensor's plane, the camera's size)
     const int dcols = c->depth_cols();
     if (!raw && !c->d_img_ring[0][0]) {  // first asynchronous host-buffer call
@@ -2221,7 +2245,7 @@ static int upload_async(Context *c, const unsigned char *left, const void *secon
     HostStage &stg = c->stage_ring[slot];
     if (!v0 || !v1) stage_reserve(c, stg, nbytes, dpix);
     hipStream_t sp = c->stream_f;
-    uint8_t *const *dring = (bpp > 1) ? c->d_col_ring[slot] : raw ? c->d_raw_ring[slot] : c->d_img_ring[slot];
+    uint8_t *const *dring = conv ? c->d_col_ring[slot] : raw ? c->d_raw_ring[slot] : c->d_img_ring[slot];
     uint8_t *d0 = dring[0], *d1 = dring[1];
     const uint8_t *s0 = host_plane(c, v0, left, nbytes, stg, 0);
     if (!rgbd) {
@@ -2325,7 +2349,7 @@ static bool depth_format_ok(lvt_handle h, const char *who, int fmt, float scale)
 }
 // one sequence's device planes against its parameters; "" when they pass (dcols: the width of its depth plane -- its depth camera's, else the image's)
 // (fW x fH: the sequence's frame size -- its own, or its reduction's; large: a reduction is in force, and k_reduce_frames reads the gray plane in place)
-static std::string rgbd_planes_check(int fW, int fH, bool large, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp, int dcols) {
+static std::string rgbd_planes_check(int fW, int fH, bool large, const void *d_gray, int gray_pitch, const void *d_depth, int depth_pitch, int fmt, int n_rows, int n_cols, int bpp, int dcols, int sfmt = SENSOR_NONE) {
     const int esz = (fmt == DEPTH_U16) ? 2 : 4;
     char buf[240];
     if (!d_gray || !d_depth) return "NULL gray or depth plane";
@@ -2333,7 +2357,16 @@ static std::string rgbd_planes_check(int fW, int fH, bool large, const void *d_g
         std::snprintf(buf, sizeof(buf), "image size %d x %d, expected %d x %d", n_cols, n_rows, fW, fH);
         return buf;
     }
-    if (large && bpp == 1) {  // a large gray frame: any address, any pitch that holds a row
+    if (sfmt != SENSOR_NONE) {  // a sensor's plane: k_sensor_frames reads it in place -- any address, any pitch that holds a row (MONO16: both even)
+        if ((long long)gray_pitch < (long long)n_cols * bpp) {
+            std::snprintf(buf, sizeof(buf), "sensor plane: pitch (%d) must hold a row of %d bytes", gray_pitch, n_cols * bpp);
+            return buf;
+        }
+        if (sfmt == SENSOR_MONO16 && (((uintptr_t)d_gray | (uintptr_t)(unsigned)gray_pitch) & 1)) {
+            std::snprintf(buf, sizeof(buf), "sensor plane: a MONO16 plane needs an even address and an even pitch (%d)", gray_pitch);
+            return buf;
+        }
+    } else if (large && bpp == 1) {  // a large gray frame: any address, any pitch that holds a row
         if (gray_pitch < n_cols) {
             std::snprintf(buf, sizeof(buf), "gray plane: pitch (%d) must hold a row of %d bytes", gray_pitch, n_cols);
             return buf;
@@ -2365,7 +2398,7 @@ static int track_rgbd_device(lvt_handle h, const void *d_gray, int gray_pitch_by
     try {
         if (!depth_format_ok(h, who, depth_format, depth_scale)) return -1;
         if (reduced_without_depth_camera(c, 0)) return rgbd_refuse(h, who, kReducedNoDepthCamera);
-        const std::string why = rgbd_planes_check(c->frame_W(0), c->frame_H(0), c->has_reduce(0), d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0), c->depth_cols());
+        const std::string why = rgbd_planes_check(c->frame_W(0), c->frame_H(0), c->has_reduce(0), d_gray, gray_pitch_bytes, d_depth, depth_pitch_bytes, depth_format, n_rows, n_cols, c->bpp_of(0), c->depth_cols(), c->has_sensor(0) ? c->sens[0].format : SENSOR_NONE);
         if (!why.empty()) return rgbd_refuse(h, who, why);
         if (sync) {
             drain(c);
@@ -2448,7 +2481,7 @@ LVT_API int lvt_amd_batch_track_rgbd_device_async(lvt_handle h, const void *cons
             present++;
             if (reduced_without_depth_camera(c, s)) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + kReducedNoDepthCamera);
             const std::string why = rgbd_planes_check(c->frame_W(s), c->frame_H(s), c->has_reduce(s), d_gray[s], gray_pitch_bytes[s], d_depth[s], depth_pitch_bytes[s], depth_format, n_rows[s], n_cols[s], c->bpp_of(s),
-                                                      c->has_depth_cam(s) ? c->depth_cam[(size_t)s].width : n_cols[s]);
+                                                      c->has_depth_cam(s) ? c->depth_cam[(size_t)s].width : n_cols[s], c->has_sensor(s) ? c->sens[(size_t)s].format : SENSOR_NONE);
             if (!why.empty()) return rgbd_refuse(h, who, "sequence " + std::to_string(s) + ": " + why);
         }
         if (!present) return rgbd_refuse(h, who, "no sequence has a frame in this step");
@@ -2816,7 +2849,7 @@ LVT_API int lvt_amd_get_plane(lvt_handle h, int eye, int what, void *dst, int ca
                 if (!c->has_rect(0)) return 0;
                 src = c->d_rect[(size_t)c->last_par * 2 + e], esz = 1;
             } else if (what == 3) {  // the converted gray image of the last (colour) frame, before rectification
-                if (c->fmt_of(0) == PIX_GRAY8 || !c->ring_converted[c->last_slot]) return 0;
+                if (!c->converts(0) || !c->ring_converted[c->last_slot]) return 0;
                 src = c->d_gray[(size_t)c->last_par * 2 + (c->sensor == 1 ? e : 0)], esz = 1;
                 if (c->resized(0)) {  // (converted BEFORE the remap: the raw frame's size, its own pitch)
                     const size_t gbytes = (size_t)c->frame_pitch(0) * c->frame_H(0);
